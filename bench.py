@@ -7,6 +7,10 @@ HiFiGAN-NSF -> trim -> peak-normalise, output left in HBM. Random-init weights o
 architectures (no checkpoints offline). Multi-GPU: one process per GPU, each rank converts its
 own utterances (weak scaling, no data-path collective); only the timing max uses RCCL.
 
+A plain run sets up, warms up, times --steps steps, writes the last step's output under --dump-outputs DIR if given, and
+prints the line. --full adds, in passes of their own after the timed steps, the roofline, the host-io rate and the CPU
+baseline (null in the line otherwise).
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -49,7 +53,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--samples", type=int, default=C2_SAMPLES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure, each in passes of its own after the timed steps: the "
+                         "roofline (per-launch HIP events), the host-io rate, the CPU baseline (C2); the roofline pass "
+                         "(C3). Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "at most 64 MB in all, a fixed seeded sample of a larger array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--config", choices=["c2", "c3", "c4", "c5"], default="c2",
                     help="c2 (default, the headline line): full pipeline, 13.5 s utterance per step; c3: HiFiGAN-NSF "
                          "generator alone, B=32 x 400 frames per step; c5: 16 realtime streams, one 256 ms hop per step")
@@ -63,8 +74,8 @@ def parse():
                     help="exercise the --gpus N self-launch and the collectives on the CPU (RVCX_DIST_BACKEND=gloo): "
                          "every rank runs a tiny host loop instead of the device pipeline; no GPU is touched")
     ap.add_argument("--roofline-pass", choices=["inline", "after"], default="after",
-                    help="inline: HIP events around every conv launch of the timed steps; after: the timed steps "
-                         "run without events and an identical K-step pass right after carries them")
+                    help="with --full. inline: HIP events around every conv launch of the timed steps; after: the timed "
+                         "steps run without events and an identical K-step pass right after carries them")
     a = ap.parse_args()
     a.steps_given = a.steps is not None
     if a.steps is None:
@@ -197,6 +208,25 @@ def _pmc_traffic():
     return (round(rec["traffic_bytes_per_launch"]), step), f"profiles/pmc_traffic.json (tree {tree}, {rec.get('file')})"
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: the tensors the last timed step returned, as DIR/<name>.npy in float32 (<name>_rank<r> when
+    there is more than one rank). The cap of 64 MB is shared evenly; an array above its share is written as a fixed
+    sample of its flattened elements (PCG64(0) indices without replacement, sorted), the same from run to run."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    cap = DUMP_CAP_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(args.dump_outputs, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), a)
+
+
 def _timed(step, args, dev, dist):
     for i in range(args.warmup):
         step(i)
@@ -223,32 +253,41 @@ def bench_c3(args, eng, dev, dist, rank, world):
     z = torch.as_tensor(rng.standard_normal((B, 192, T)).astype(np.float32), device=dev)
     f0 = torch.as_tensor(synthetic.f0_walk(B, T, seed=3), dtype=torch.float32, device=dev)
     sid = torch.zeros(B, dtype=torch.int32, device=dev)
-    el = _timed(lambda i: eng.dec_only(z, f0, sid, seed=i), args, dev, dist)
+    last = {}
+
+    def step(i):
+        last["audio"] = eng.dec_only(z, f0, sid, seed=i)
+
+    el = _timed(step, args, dev, dist)
     eng.check_device_status()
-    # roofline: an identical K-step pass right after the timed one carries the per-conv events (they are not
-    # in the timed region)
-    eng.profile_read()
-    eng.profile(True)
-    for i in range(args.steps):
-        eng.dec_only(z, f0, sid, seed=args.warmup + i)
-    eng.profile(False)
-    k_ms, k_flops, k_n, c_ms = eng.profile_read(with_ceiling=True)
+    dump_outputs(args, rank, world, last)
     audio_sec = B * T * eng.upp / 48000.0
     tot = reduce_throughput(dist, args.steps * audio_sec, el, device=dev)
-    tf = k_flops / (k_ms / 1e3) / 1e12 if k_ms > 0 else 0.0
-    peak = k_flops / (c_ms / 1e3) / 1e12 if c_ms > 0 else SPLIT_PEAK_TFLOPS
+    roofline = None
+    if args.full:
+        # roofline: an identical K-step pass right after the timed one carries the per-conv events (they are not
+        # in the timed region)
+        eng.profile_read()
+        eng.profile(True)
+        for i in range(args.steps):
+            eng.dec_only(z, f0, sid, seed=args.warmup + i)
+        eng.profile(False)
+        k_ms, k_flops, k_n, c_ms = eng.profile_read(with_ceiling=True)
+        tf = k_flops / (k_ms / 1e3) / 1e12 if k_ms > 0 else 0.0
+        peak = k_flops / (c_ms / 1e3) / 1e12 if c_ms > 0 else SPLIT_PEAK_TFLOPS
+        roofline = {"bound": "mfma", "achieved": round(tf, 3), "peak": round(peak, 1), "unit": "TFLOP/s",
+                    "frac": round(tf / peak, 4), "traffic": None,
+                    "peak_basis": "FLOP-weighted MFMA ceiling of the launches' arithmetic: dense 2500 TF / 3 "
+                                  "products (two-plane fp16 split, the generator) or / 6 (three-plane bf16 split)",
+                    "kernel": CONV_KERNEL + " (events on a separate K-step pass after the timed one)",
+                    "alg_gflop_per_step": round(k_flops / args.steps / 1e9, 2)}
     return {"metric": "audio-sec/sec HiFiGAN-NSF generator (C3)", "value": round(tot["value"], 3),
             "unit": "audio-sec/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(tot["elapsed"] / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "fp32-accurate (two-plane fp16 MFMA split)", "data": "synthetic z ~ N(0,1), f0 random walk; random-init weights",
             "config": {"workload": "C3: generator alone, B=32 x 400 frames (128 s of 48 kHz audio) per step",
                        "parallelism": f"dp{world}"},
-            "roofline": {"bound": "mfma", "achieved": round(tf, 3), "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(tf / peak, 4), "traffic": None,
-                         "peak_basis": "FLOP-weighted MFMA ceiling of the launches' arithmetic: dense 2500 TF / 3 "
-                                       "products (two-plane fp16 split, the generator) or / 6 (three-plane bf16 split)",
-                         "kernel": CONV_KERNEL + " (events on a separate K-step pass after the timed one)",
-                         "alg_gflop_per_step": round(k_flops / args.steps / 1e9, 2)}}
+            "roofline": roofline}
 
 
 def _c4_row(arg):
@@ -291,9 +330,11 @@ def bench_c4(args, eng, dev, dist, rank, world):
     ldo = ((n + 2 * int(opts.t_pad)) // 160) * eng.upp
     out = torch.empty((args.batch, ldo), dtype=torch.float32, device=dev)
 
+    last = {}
+
     def convert(ids, step):
         rows = torch.tensor([pos[i] for i in ids], device=dev)
-        y = eng.pipeline_batch(audio.index_select(0, rows), opts, sids=0, seed=step, out=out)
+        y = last["audio"] = eng.pipeline_batch(audio.index_select(0, rows), opts, sids=0, seed=step, out=out)
         rec = torch.empty((len(ids), 4), dtype=torch.float64, device=dev)
         rec[:, 0] = torch.tensor(ids, dtype=torch.float64, device=dev)
         rec[:, 1] = float(y.shape[1])
@@ -306,6 +347,7 @@ def bench_c4(args, eng, dev, dist, rank, world):
     recs, el = offline.run(p, convert, sync=lambda: torch.cuda.synchronize(dev), dist=dist,
                            steps=args.steps if args.steps_given else None)
     eng.check_device_status()
+    dump_outputs(args, rank, world, last)
     tot = offline.finish(p, job, recs, el, dist=dist, device=dev)
     nsteps = len(recs)
     r = tot["records"]
@@ -347,6 +389,7 @@ def bench_c5(args, eng, dev, dist, rank, world):
 
     el = _timed(step, args, dev, dist)
     eng.check_device_status()
+    dump_outputs(args, rank, world, {"audio": grp.out, "vol": grp.vol})  # the buffers process() returns
     lat = np.array(lat[args.warmup:]) * 1e3
     hop_sec = block / 48000.0
     tot = reduce_throughput(dist, args.steps * S * hop_sec, el, device=dev)
@@ -492,7 +535,7 @@ def main():
         step(i, host_io=True)
     torch.cuda.synchronize(dev)
     eng.profile_read()  # drop anything recorded so far
-    eng.profile(args.roofline_pass == "inline")
+    eng.profile(args.full and args.roofline_pass == "inline")
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -504,6 +547,45 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     eng.profile(False)
+    eng.check_device_status()  # a device-side fault flag (BiGRU hand-off) voids the run
+    assert y.numel() > 0 and bool(torch.isfinite(y).all())
+    dump_outputs(args, rank, world, {"audio": y})  # before the --full passes reuse the output buffer
+    from rvcx.sharding import reduce_throughput
+
+    audio_sec = n / SR_IN
+    # whole job: audio-seconds summed over ranks / wall time maxed over ranks
+    tot = reduce_throughput(dist, args.steps * audio_sec, t1 - t0, device=dev)
+    elapsed = tot["elapsed"]
+    ms_per_step = elapsed / args.steps * 1000.0
+    value = tot["value"]
+    roofline = cpu = host_io = None
+    if args.full:
+        roofline, cpu, host_io = c2_full(args, eng, step, n, dev, dist, rank, world)
+    if rank == 0:
+        rec = {
+            "metric": "audio-sec/sec (realtime factor) RVCv2 48kHz pipeline",
+            "value": round(value, 3), "unit": "audio-sec/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "fp32-accurate (two-plane fp16 MFMA split)", "data": "synthetic (speech-like, seeded); "
+            "random-init weights of the RVCv2-48k / ContentVec / RMVPE architectures",
+            "config": {"workload": "C2: full RVCv2 48kHz pipeline, one 13.5 s utterance per step per GPU",
+                       "samples_16k": n, "audio_sec_per_step_per_gpu": round(audio_sec, 5), "x_pad": 1,
+                       "f0_method": "rmvpe", "index_rate": 0, "protect": 0.33, "parallelism": f"dp{world}"},
+            # roofline, cpu_baseline and host_io are measured in passes of their own: null without --full
+            "roofline": roofline, "cpu_baseline": cpu, "effective_config": eng.config_info(), "host_io": host_io,
+        }
+        print(json.dumps(rec))
+    if dist:
+        dist.destroy_process_group()
+    eng.close()
+
+
+def c2_full(args, eng, step, n, dev, dist, rank, world):
+    """--full on C2, after the timed steps: the same K steps from pinned host input to pinned host output, the
+    roofline of the conv family (events inline in the timed steps, or on an identical K-step pass here) and the CPU
+    baseline. Returns the line's (roofline, cpu_baseline, host_io)."""
+    from rvcx.sharding import reduce_throughput
+
     # the same K steps from pinned host input to pinned host output (PCIe-inclusive; reported beside value)
     if dist:
         dist.barrier()
@@ -521,17 +603,8 @@ def main():
             step(args.warmup + i)
         eng.profile(False)
     (k_ms, k_flops, k_launches, c_ms), fams = eng.profile_read_kinds()
-    eng.check_device_status()  # a device-side fault flag (BiGRU hand-off) voids the run
-    from rvcx.sharding import reduce_throughput
-
-    audio_sec = n / SR_IN
-    # whole job: audio-seconds summed over ranks / wall time maxed over ranks
-    tot = reduce_throughput(dist, args.steps * audio_sec, t1 - t0, device=dev)
-    tot_io = reduce_throughput(dist, args.steps * audio_sec, th1 - th0, device=dev)
-    elapsed = tot["elapsed"]
-    ms_per_step = elapsed / args.steps * 1000.0
-    value = tot["value"]
-    assert y.numel() > 0 and bool(torch.isfinite(y).all())
+    eng.check_device_status()
+    tot_io = reduce_throughput(dist, args.steps * n / SR_IN, th1 - th0, device=dev)
 
     achieved_tflops = k_flops / (k_ms / 1000.0) / 1e12 if k_ms > 0 else 0.0
     # FLOP-weighted ceiling of the launches' own arithmetic: the launches' time at their ceilings / their time
@@ -566,27 +639,12 @@ def main():
             cpu = cpu_baseline(n)
         except Exception as e:  # reported, never fatal
             cpu = {"error": repr(e)}
-    if rank == 0:
-        rec = {
-            "metric": "audio-sec/sec (realtime factor) RVCv2 48kHz pipeline",
-            "value": round(value, 3), "unit": "audio-sec/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "fp32-accurate (two-plane fp16 MFMA split)", "data": "synthetic (speech-like, seeded); "
-            "random-init weights of the RVCv2-48k / ContentVec / RMVPE architectures",
-            "config": {"workload": "C2: full RVCv2 48kHz pipeline, one 13.5 s utterance per step per GPU",
-                       "samples_16k": n, "audio_sec_per_step_per_gpu": round(audio_sec, 5), "x_pad": 1,
-                       "f0_method": "rmvpe", "index_rate": 0, "protect": 0.33, "parallelism": f"dp{world}"},
-            "roofline": roofline, "cpu_baseline": cpu, "effective_config": eng.config_info(),
-            # SURVEY §8(d)'s definition: pinned host audio in -> pinned host audio out, the H2D (1.7 MB fp64) and
-            # D2H (2.6 MB fp32) copies on the compute stream inside the timed loop; value above is HBM-resident
-            "host_io": {"value": round(tot_io["value"], 3), "unit": "audio-sec/sec",
-                        "ms_per_step": round(tot_io["elapsed"] / args.steps * 1000.0, 3),
-                        "timed": "pinned host input -> H2D -> pipeline -> D2H -> pinned host output, same K steps"},
-        }
-        print(json.dumps(rec))
-    if dist:
-        dist.destroy_process_group()
-    eng.close()
+    # SURVEY §8(d)'s definition: pinned host audio in -> pinned host audio out, the H2D (1.7 MB fp64) and
+    # D2H (2.6 MB fp32) copies on the compute stream inside the timed loop; the line's value is HBM-resident
+    host_io = {"value": round(tot_io["value"], 3), "unit": "audio-sec/sec",
+               "ms_per_step": round(tot_io["elapsed"] / args.steps * 1000.0, 3),
+               "timed": "pinned host input -> H2D -> pipeline -> D2H -> pinned host output, same K steps"}
+    return roofline, cpu, host_io
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@
 # Steps run in order; each has its own time limit and the script stops at the first failure.
 #   tests[=PATHS]     pytest -m gpu (default: tests/), thread-method timeouts
 #   smoke             __graft_entry__.smoke()
-#   bench[=ARGS]      bench.py (ARGS with ',' for spaces, e.g. bench=--config,c3,--no-cpu-baseline)
+#   bench[=ARGS]      bench.py --full (ARGS with ',' for spaces, e.g. bench=--config,c3,--no-cpu-baseline)
 #   configs           C3 / C5 / C4 bench lines (no CPU baseline)
 #   prof              rocprofv3 --kernel-trace --stats of the C2 bench + timeline + kernel-family table
 #   pmc               the three HBM / MFMA PMC passes of one C2 step (tools/pmc_traffic.sh)
@@ -40,23 +40,23 @@ for step in "$@"; do
       timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1 || { tail -20 $O/smoke_$TAG.log; exit 1; }
       tail -1 $O/smoke_$TAG.log ;;
     bench)
-      timeout -k 10 500 python -u bench.py ${arg//,/ } > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { tail -20 $O/bench_$TAG.err; exit 1; }
+      timeout -k 10 500 python -u bench.py --full ${arg//,/ } > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { tail -20 $O/bench_$TAG.err; exit 1; }
       tail -1 $O/bench_$TAG.json | cut -c1-400 ;;
     configs)
       for c in c3 c5 c4; do
-        timeout -k 10 500 python -u bench.py --config $c --no-cpu-baseline > $O/bench_${TAG}_$c.json 2> $O/bench_${TAG}_$c.err || { tail -5 $O/bench_${TAG}_$c.err; exit 1; }
+        timeout -k 10 500 python -u bench.py --full --config $c --no-cpu-baseline > $O/bench_${TAG}_$c.json 2> $O/bench_${TAG}_$c.err || { tail -5 $O/bench_${TAG}_$c.err; exit 1; }
         python3 -c "import json; d=json.loads(open('$O/bench_${TAG}_$c.json').read().strip().splitlines()[-1]); print('$c', d['value'], d['unit'], d['ms_per_step'])"
       done ;;
     prof)
       # 1 warm-up + 3 timed + 3 host-io + 3 roofline-event steps = 10 pipeline calls traced (the summaries divide by 10)
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ${arg//,/ } > $O/prof_$TAG.log 2>&1 || { tail -20 $O/prof_$TAG.log; exit 1; }
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${arg//,/ } > $O/prof_$TAG.log 2>&1 || { tail -20 $O/prof_$TAG.log; exit 1; }
       DB=$(find $O/prof_$TAG -name "*.db" | head -1)
       python3 tools/timeline.py "$DB" 2 -v > $O/timeline_$TAG.txt 2>&1
       python3 tools/prof_summary.py "$DB" 10 > $O/kstats_$TAG.txt 2>&1
       python3 tools/kfamily.py "$DB" 10 > $O/kfamily_$TAG.txt 2>&1
       head -30 $O/kstats_$TAG.txt ;;
     pmc)
-      bash tools/pmc_traffic.sh || exit 1
+      bash tools/pmc_traffic.sh $O || exit 1
       python3 tools/pmc_traffic.py gpurun_out > $O/pmc_traffic_$TAG.json || exit 1
       python3 tools/pmc_shapes.py gpurun_out 40 > $O/pmc_shapes_$TAG.txt 2>&1
       head -12 $O/pmc_shapes_$TAG.txt ;;
@@ -85,14 +85,14 @@ for step in "$@"; do
       IFS=';' read -ra envs <<< "X=0;$arg"
       for rep in 1 2; do
         for e in "${envs[@]}"; do
-          env RVCX_EXPERIMENTAL=1 ${e//,/ } timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/ab_$TAG.log 2>&1 || { echo "bench failed $e"; tail -5 $O/ab_$TAG.log; exit 1; }
+          env RVCX_EXPERIMENTAL=1 ${e//,/ } timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/ab_$TAG.log 2>&1 || { echo "bench failed $e"; tail -5 $O/ab_$TAG.log; exit 1; }
           echo "$e $(c2line $O/ab_$TAG.log)"
         done
       done ;;
     ablib)
       for rep in 1 2 3; do
         for lib in "$arg" retrieval-based-voice-conversion-mlx_amd/rvcx/librvcx.so; do
-          RVCX_LIB=$lib timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/ab_$TAG.log 2>&1 || { echo "bench failed $lib"; tail -5 $O/ab_$TAG.log; exit 1; }
+          RVCX_LIB=$lib timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/ab_$TAG.log 2>&1 || { echo "bench failed $lib"; tail -5 $O/ab_$TAG.log; exit 1; }
           echo "$lib $(c2line $O/ab_$TAG.log)"
         done
       done ;;
