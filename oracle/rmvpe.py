@@ -63,11 +63,12 @@ def rmvpe_mel_basis() -> np.ndarray:
 
 def mel_spectrogram(audio: torch.Tensor) -> torch.Tensor:
     """MelSpectrogram.forward(keyshift=0, speed=1, center=True) (RMVPE.py:388-417). audio [B, N]."""
-    window = torch.hann_window(1024)
+    window = torch.hann_window(1024, dtype=audio.dtype)
     fft = torch.stft(audio, n_fft=1024, hop_length=160, win_length=1024, window=window,
                      center=True, return_complex=True)
     mag = torch.sqrt(fft.real.pow(2) + fft.imag.pow(2))
-    mel = torch.matmul(torch.from_numpy(rmvpe_mel_basis()), mag)
+    # the basis is data: float32-valued in every dtype
+    mel = torch.matmul(torch.from_numpy(rmvpe_mel_basis()).to(audio.dtype), mag)
     return torch.log(torch.clamp(mel, min=1e-5))
 
 
@@ -111,8 +112,8 @@ def deep_unet(w, cfg, x):
 
 
 def bigru(w, x):
-    """BiGRU (RMVPE.py:543-564) = nn.GRU(384, 256, bidirectional, batch_first)."""
-    gru = torch.nn.GRU(x.shape[-1], 256, num_layers=1, batch_first=True, bidirectional=True)
+    """BiGRU (RMVPE.py:543-564) = nn.GRU(384, 256, bidirectional, batch_first), in the input's dtype."""
+    gru = torch.nn.GRU(x.shape[-1], 256, num_layers=1, batch_first=True, bidirectional=True, dtype=x.dtype)
     sd = {k[len("fc.0.gru."):]: _t(w, k) for k in w if k.startswith("fc.0.gru.")}
     gru.load_state_dict(sd)
     gru.eval()

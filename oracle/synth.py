@@ -1,7 +1,9 @@
 """Oracle: SynthesizerTrnMs768NSFsid.infer (TextEncoder -> flow reverse -> HiFiGAN-NSF).
 
-TEST INFRASTRUCTURE ONLY (see oracle/__init__.py). Functional torch-CPU fp32
-restatement over a fused-weight dict ``w`` (reference state-dict names).
+TEST INFRASTRUCTURE ONLY (see oracle/__init__.py). Functional torch-CPU
+restatement over a fused-weight dict ``w`` (reference state-dict names): fp32 as
+the reference runs it; the HiFi-GAN-NSF path follows the dtype of ``w`` and the
+inputs, so it also runs in float64 (tests/parity_anchor.py).
 """
 from __future__ import annotations
 
@@ -162,7 +164,7 @@ def sine_source(f0: Tensor, upp: int, sr: int, eps: Tensor, lin_w: Tensor, lin_b
     inc = inc + F.pad(cum, (0, 0, 1, 0), mode="constant")
     phase = inc.reshape(B, -1, 1)
     sine = torch.sin(2 * np.pi * phase) * 0.1
-    uv = (f0 > 0.0).float()
+    uv = (f0 > 0.0).to(f0.dtype)
     uv = F.interpolate(uv.transpose(2, 1), scale_factor=float(upp), mode="nearest").transpose(2, 1)
     amp = uv * 0.003 + (1 - uv) * (0.1 / 3)
     noise = amp * eps.reshape(B, -1, 1)

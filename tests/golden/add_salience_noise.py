@@ -29,13 +29,6 @@ from rvcx.config import RMVPE_CFG  # noqa: E402
 from rvcx.weights import normalize_state  # noqa: E402
 
 
-def bigru_any_dtype(w, x):
-    """orm.bigru with the GRU module in the input's dtype (the oracle's nn.GRU is created fp32)."""
-    gru = torch.nn.GRU(x.shape[-1], 256, num_layers=1, batch_first=True, bidirectional=True).to(x.dtype)
-    gru.load_state_dict({k[len("fc.0.gru."):]: w[k].to(x.dtype) for k in w if k.startswith("fc.0.gru.")})
-    return gru.eval()(x)[0]
-
-
 def clips():
     ios = np.load(os.path.join(OUT, "ios_kat.npz"))["input_audio"].astype(np.float64)
     return {"pipeline_c2_ios.npz": ios,
@@ -44,7 +37,6 @@ def clips():
 
 
 def main():
-    orm.bigru = bigru_any_dtype
     w = normalize_state(synthetic.rmvpe_state(5))
     bh, ah = signal.butter(N=5, Wn=48, btype="high", fs=16000)  # rvc/infer/pipeline.py:22-27, :439, :459
     for name, audio in clips().items():

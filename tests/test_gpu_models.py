@@ -1,10 +1,18 @@
 """HIP path (librvcx.so through the C-ABI) vs the reference's own outputs (golden fixtures)
-and vs the CPU oracle, on seeded synthetic weights and injected noise."""
+and vs the CPU oracle, on seeded synthetic weights and injected noise.
+
+The fixed bars (1e-3 HuBERT and salience, 2e-3 waveforms, 1e-4 latents) stay; beside them the five module fixtures
+(synth_t64, synth_b2_ragged, dec_b2_t24, hubert_1s, rmvpe_1s) carry anchored bars (tests/parity_anchor.py): the oracle
+runs on the fixture's own inputs in float64 and float32, the stored output must sit within 2 x that fp32-vs-fp64 gap
+of float64, and the device within (K + 1) = 9 x the gap of the stored output (K = 8 against float64, plus the one gap
+the fixture itself is away from it)."""
 import numpy as np
 import pytest
 import torch
 
+import parity_anchor as pa
 from conftest import golden
+from parity_anchor import K, anchor, check
 
 pytestmark = pytest.mark.gpu
 
@@ -14,7 +22,20 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))
 
 
-def test_synth_t64_vs_reference(engine):
+def anchored(name, dev, stored, ref64, gap, old_bar, absolute=False):
+    """The stored reference output within 2 gap of float64, then the device within (K + 1) gap of the stored output;
+    the measured error is printed beside the fixed bar it also passed."""
+    stored = np.asarray(stored).reshape(ref64.shape)
+    check(f"{name} fixture vs fp64", stored, ref64, gap, 2, absolute)
+    err = check(f"{name} device vs fixture", np.asarray(dev).reshape(ref64.shape), stored, gap, K + 1, absolute)
+    print(f"{name}: measured {err:.3e}, fixed bar {old_bar:g}")
+
+
+def synth_anchor(w, g):
+    return anchor(pa.synth_fn(w, g["phone"], g["lengths"], g["pitch"], g["f0"], g["sid"], g["eps_z"], g["eps_src"]))
+
+
+def test_synth_t64_vs_reference(engine, synth_w):
     from oracle.metrics import spectrogram_correlation
 
     g = golden("synth_t64.npz")
@@ -29,9 +50,13 @@ def test_synth_t64_vs_reference(engine):
     ref = g["o"].reshape(o.shape)
     assert rel_err(o, ref) < 2e-3, rel_err(o, ref)
     assert spectrogram_correlation(o[0], ref[0]) > 0.999
+    anc = synth_anchor(synth_w, g)
+    anchored("synth_t64 z_p", zp.transpose(0, 2, 1), g["z_p"].transpose(0, 2, 1), *anc["z_p"], 1e-4)
+    anchored("synth_t64 z", z.transpose(0, 2, 1), g["z"].transpose(0, 2, 1), *anc["z"], 1e-4)
+    anchored("synth_t64 o", o, g["o"], *anc["o"], 2e-3)
 
 
-def test_synth_ragged_batch_vs_reference(engine):
+def test_synth_ragged_batch_vs_reference(engine, synth_w):
     g = golden("synth_b2_ragged.npz")
     out, zp, z = engine.synth_infer(g["phone"], g["lengths"], g["pitch"], g["f0"], g["sid"], eps_z=g["eps_z"],
                                     eps_src=g["eps_src"], want_latents=True)
@@ -42,14 +67,18 @@ def test_synth_ragged_batch_vs_reference(engine):
     ref = g["o"].reshape(o.shape)
     # the generator is unmasked: ragged tails carry garbage in both implementations, compare everything
     assert rel_err(o, ref) < 2e-3, rel_err(o, ref)
+    anc = synth_anchor(synth_w, g)
+    anchored("synth_b2_ragged z_p", zp.transpose(0, 2, 1), g["z_p"].transpose(0, 2, 1), *anc["z_p"], 1e-4)
+    anchored("synth_b2_ragged o", o, g["o"], *anc["o"], 2e-3)
 
 
-def test_dec_vs_reference(engine):
+def test_dec_vs_reference(engine, synth_w):
     g = golden("dec_b2_t24.npz")
     out = engine.dec_only(g["z"], g["f0"], g["sid"], eps_src=g["eps_src"])
     o = out.cpu().numpy()
     ref = g["o"].reshape(o.shape)
     assert rel_err(o, ref) < 2e-3, rel_err(o, ref)
+    anchored("dec_b2_t24 o", o, g["o"], *anchor(pa.dec_fn(synth_w, g["z"], g["f0"], g["sid"], g["eps_src"]))["out"], 2e-3)
 
 
 @pytest.mark.parametrize("name", ["synth_t64.npz", "synth_b2_ragged.npz"])
@@ -67,15 +96,16 @@ def test_synth_noise_branch_ahead_is_bit_identical(engine, name):
     assert torch.equal(out, ref), float((out - ref).abs().max())
 
 
-def test_hubert_vs_reference(engine):
+def test_hubert_vs_reference(engine, hubert_w):
     g = golden("hubert_1s.npz")
     f = engine.hubert(g["audio"]).cpu().numpy()
     ref = g["feats"][0]
     assert f.shape == ref.shape
     assert rel_err(f, ref) < 1e-3, rel_err(f, ref)
+    anchored("hubert_1s feats", f, g["feats"], *anchor(pa.hubert_fn(hubert_w, g["audio"][None]))["out"], 1e-3)
 
 
-def test_rmvpe_vs_reference(engine):
+def test_rmvpe_vs_reference(engine, rmvpe_w):
     from oracle.metrics import cents_agreement
 
     g = golden("rmvpe_1s.npz")
@@ -86,6 +116,8 @@ def test_rmvpe_vs_reference(engine):
     assert rel_err(hid, g["hidden"]) < 1e-3, rel_err(hid, g["hidden"])
     acc, vuv = cents_agreement(f0, g["f0"], 50.0)
     assert acc >= 0.99 and vuv >= 0.995, (acc, vuv)
+    anchored("rmvpe_1s hidden", hid, g["hidden"], *anchor(pa.rmvpe_fn(rmvpe_w, g["audio"][None]))["out"], 1e-3,
+             absolute=True)
 
 
 def test_rmvpe_decode_kat_on_device(engine):
