@@ -430,6 +430,47 @@ int rvcx_conv1d_gen(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const 
                     int N, int taps, int dilation, int pad, int pre_act, float pre_slope, int act, float slope,
                     const float* d_res, int acc_mode, float acc_div, int kernel, float* d_y, void* stream);
 
+/* One 1-D contraction in any form the runtime issues (csrc/runtime_synth.cpp, runtime_fe.cpp), described field by
+ * field as the dispatcher's own record (ConvArgs, csrc/rvcx_kernels.h) takes it. All pointers are device pointers, all
+ * strides in floats; w is [taps][N][C_in] per group (rvcx_conv1d's layout), bias [N] per group.
+ *   input     pre(x[b][row][c]) * pre_mask[b][row], zero outside [0, T_in); row = m stride - pad + tap dil
+ *   value     v = act(alpha (acc + bias [+ res: res_mode 1])); res_mode 2: v + res, 3: res - v; acc_mode 1: y + v,
+ *             2: (y + v) / acc_div; then v * mask[b][m]. act / pre_act: 0 none, 1 leaky ReLU(slope), 2 ReLU, 3 erf GELU,
+ *             4 tanh, 5 sigmoid, 6 log(max(v, slope))
+ *   batch     entry (b, g) of batch x batch_inner reads / writes at b *_bs + g *_bs2 (the masks and gate_g: b only)
+ *   gate_h    > 0: y[m][c] = tanh(v[c] + g[c]) sigmoid(v[c + gate_h] + g[c + gate_h]), v = acc + bias, N = 2 gate_h,
+ *             g = gate_g + b gate_g_bs; no other epilogue field
+ *   ln_g      set: y[m] = LN(res[m] + v[m]) ln_g + ln_b over the N <= 1024 columns (res_mode 0, acc_mode 0)
+ *   nz_har    set: + nz_b[c] + nz_w[c nz_stride] har[b nz_bs + (m nz_u + p) nz_stride] at column n = p nz_C + c (the
+ *             fused NSF noise conv: nz_kk = 1, N = nz_u nz_C, an unsplit weight-streamed or weight-stationary launch)
+ * The gate and the LayerNorm live in the split-K combine: they need a contraction of at least two 32-channel steps.
+ * route 0 = the size policy as the runtime applies it to a static weight, 1 = exact fp32 MFMA, 2 = the LDS-staged bf16
+ * split (a non-static weight), 3 = the weight-streamed tile the policy picks, 4 = gather-streamed, 5 =
+ * weight-stationary. A forced route that does not admit the form returns RVCX_E_SHAPE before anything is launched; it
+ * never runs on another kernel. no_splitk keeps the contraction in one slice. *kind_out (optional) gets the kernel
+ * family that ran (rvcx_profile_kind_name's index), *ksplit_out (optional) the planned split count. The caller owns
+ * every extent: nothing is checked against an allocation. Exposed for numerics tests. */
+typedef struct {
+  const float* x; const float* w; const float* bias; const float* res; const float* mask; const float* pre_mask;
+  float* y;
+  int T_in, C_in, N, taps, dil, pad, stride, T_out;
+  int ldx, ldy, ldr;
+  int batch;
+  int64_t x_bs, y_bs, res_bs, mask_bs, pre_mask_bs;
+  int batch_inner;
+  int64_t x_bs2, w_bs2, y_bs2, res_bs2, bias_bs2;
+  int pre_act; float pre_slope;
+  int act; float slope; float alpha;
+  int res_mode, acc_mode; float acc_div;
+  int gate_h; const float* gate_g; int64_t gate_g_bs;
+  const float* ln_g; const float* ln_b; float ln_eps;
+  const float* nz_har; int64_t nz_bs;
+  int nz_stride, nz_kk, nz_u, nz_C;
+  const float* nz_w; const float* nz_b;
+  int route, no_splitk;
+} rvcx_conv_test_desc;
+int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* desc, int* kind_out, int* ksplit_out, void* stream);
+
 /* One 3x3 / pad-1 Conv2d forward, NHWC: d_x [H][W][C_in], d_w [9][N][C_in] (torch weight [N][C_in][3][3] permuted to
  * (kh * 3 + kw, N, C_in)), d_bias [N] (optional), d_y [H][W][N]; act 0 none, 1 ReLU. The RMVPE U-Net's conv
  * (RMVPE.py:13-57 ConvBlockRes, torch.nn.Conv2d(kernel 3, padding 1)), exposed for the numerics tests of its

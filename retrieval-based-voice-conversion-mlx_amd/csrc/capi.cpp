@@ -910,6 +910,102 @@ int rvcx_conv1d_gen(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const 
   });
 }
 
+int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* d, int* kind_out, int* ksplit_out, void* stream) {
+  return guard(ctx, [&] {
+    set_device(ctx);
+    ctx->check_device_status();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d || !d->x || !d->w || !d->y || d->T_in <= 0 || d->C_in <= 0 || d->N <= 0 || d->taps <= 0 || d->dil <= 0 ||
+        d->stride <= 0 || d->pad < 0 || d->T_out <= 0 || d->batch <= 0 || d->batch_inner <= 0 || d->ldx < d->C_in ||
+        d->ldy < (d->gate_h > 0 ? d->gate_h : d->N) || d->pre_act < 0 || d->pre_act > ACT_LOGCLAMP || d->act < 0 ||
+        d->act > ACT_LOGCLAMP || d->res_mode < RES_NONE || d->res_mode > RES_RSUB_POST || d->acc_mode < ACC_STORE ||
+        d->acc_mode > ACC_ADD_DIV || (d->res_mode != RES_NONE && !d->res) || (d->res && d->ldr != 0 && d->ldr < d->N) ||
+        d->route < 0 || d->route > 5 || d->gate_h < 0 || (d->gate_h > 0 && !d->gate_g) ||
+        (d->ln_g && (!d->ln_b || !d->res)) ||
+        (d->nz_har && (!d->nz_w || !d->nz_b || d->nz_C <= 0 || d->nz_u <= 0 || d->nz_stride <= 0)) ||
+        ctx->is_weight(d->w))
+      throw Error(RVCX_E_INVALID, "rvcx_conv1d_ex: bad argument");
+    if ((int64_t)(d->T_out - 1) * d->stride + (int64_t)(d->taps - 1) * d->dil + 1 > d->T_in + 2 * (int64_t)d->pad)
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: T_out exceeds the padded input");
+    if ((int64_t)d->taps * d->N * d->C_in > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: size out of range");
+    ConvArgs a;
+    a.x = d->x; a.x_bs = d->x_bs; a.x_bs2 = d->x_bs2; a.ldx = d->ldx; a.T_in = d->T_in; a.C_in = d->C_in;
+    a.pre_act = d->pre_act; a.pre_slope = d->pre_slope; a.pre_mask = d->pre_mask; a.pre_mask_bs = d->pre_mask_bs;
+    a.w = d->w; a.ldw = d->C_in; a.w_ts = (long long)d->N * d->C_in; a.w_bs2 = d->w_bs2;
+    a.taps = d->taps; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
+    a.y = d->y; a.y_bs = d->y_bs; a.y_bs2 = d->y_bs2; a.ldy = d->ldy; a.T_out = d->T_out; a.N = d->N;
+    a.bias = d->bias; a.bias_bs2 = d->bias_bs2; a.alpha = d->alpha; a.act = d->act; a.slope = d->slope;
+    a.res = d->res; a.res_bs = d->res_bs; a.res_bs2 = d->res_bs2; a.ldr = d->ldr; a.res_mode = d->res_mode;
+    a.mask = d->mask; a.mask_bs = d->mask_bs; a.acc_mode = d->acc_mode; a.acc_div = d->acc_div;
+    a.gate_h = d->gate_h; a.gate_g = d->gate_g; a.gate_g_bs = d->gate_g_bs;
+    a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps;
+    a.batch = d->batch; a.batch_inner = d->batch_inner;
+    a.nz_har = d->nz_har; a.nz_bs = d->nz_bs; a.nz_stride = d->nz_stride; a.nz_kk = d->nz_kk; a.nz_u = d->nz_u;
+    a.nz_C = d->nz_C; a.nz_w = d->nz_w; a.nz_b = d->nz_b;
+    a.no_splitk = d->no_splitk ? 1 : 0;
+    // the combine-time epilogues as their kernels take them (launch_splitk_reduce's conditions)
+    if (a.ln_g && (a.N > 1024 || a.batch_inner != 1 || a.res_mode != RES_NONE || a.acc_mode != ACC_STORE || a.gate_h > 0))
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the combine's LayerNorm takes N <= 1024, one group, no other residual");
+    if (a.gate_h > 0 && (a.N != 2 * a.gate_h || a.batch_inner != 1 || a.act != ACT_NONE || a.alpha != 1.f || a.res ||
+                         a.mask || a.acc_mode != ACC_STORE))
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the combine's gate takes N = 2 gate_h and no other epilogue field");
+    if (a.nz_har && (a.nz_kk != 1 || a.N != a.nz_u * a.nz_C || a.gate_h > 0 || a.ln_g))
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the fused noise conv takes one tap and N = nz_u nz_C");
+    // the route: what launch_conv will decide (a.wsb) is fixed here, so the family is known before the launch
+    int wsb = 0, expect = -1;
+    if (d->route == 1 || d->route == 2) {
+      a.math = d->route;
+      expect = d->route == 1 ? CK_GEMM : CK_EMU;
+    } else {
+      a.w_static = 1;
+      if (ctx->conv_math > 0) a.math = ctx->conv_math;
+      if (d->route == 0) {
+        wsb = conv_wsb_route(a, false);
+      } else {
+        a.math = 3;
+        if (d->route == 3) {
+          if (!conv_wsb_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: form not eligible for the weight-streamed kernel");
+          a.force_cfg = conv_wsb_pick(a);
+          wsb = 1;
+          expect = CK_WSB16;
+        } else if (d->route == 4) {
+          if (!conv_gs_eligible(a, false) || a.nz_har)
+            throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: form not eligible for the gather-streamed kernel");
+          a.force_cfg = 30;
+          wsb = 2;
+          expect = CK_GS;
+        } else {
+          a.force_cfg = 40;
+          wsb = 1;
+          expect = CK_WST;
+        }
+      }
+      if (wsb) {
+        // a fresh image every call (rvcx_conv1d's reason), in the format launch_conv would build
+        a.wsplit_fmt = conv_math_of(a) == 3 ? WSPLIT_H16 : WSPLIT_BF16;
+        a.wsplit_npad = conv_wsplit_npad(a.N);
+        void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), s);
+        check(conv_wsplit_build(a, img, s), "conv_wsplit_build");
+        a.wsplit = img;
+      }
+    }
+    ConvArgs p = a;
+    p.wsb = wsb;
+    conv_plan_splitk(p, false);
+    if (d->route == 5 && !conv_wst_fits(p, false))
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: form not eligible for the weight-stationary kernel");
+    if (!wsb && expect >= 0 && conv_unstreamed_kind(p) != expect)
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the dispatcher gives this shape to another kernel family");
+    if ((a.gate_h > 0 || a.ln_g) && p.ksplit < 2)
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the gate / LayerNorm need a contraction that splits (two steps, no_splitk off)");
+    if (a.nz_har && (wsb != 1 || p.ksplit > 1))
+      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the fused noise conv needs an unsplit weight-streamed / weight-stationary launch");
+    if (ksplit_out) *ksplit_out = p.ksplit;
+    launch_conv(*ctx, a, false, s, -1.0);
+    if (kind_out) *kind_out = conv_last_kind();
+  });
+}
+
 int rvcx_conv2d3x3(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w, const float* d_bias,
                    int N, int act, int math, float* d_y, void* stream) {
   return guard(ctx, [&] {

@@ -1166,6 +1166,10 @@ int conv_wsb_route(const ConvArgs& a, bool two_d) {
 }
 
 int conv_math_of(const ConvArgs& a) { return conv_math(a); }
+int conv_unstreamed_kind(const ConvArgs& a) {
+  if (tiny_fits(a) || (!(a.ws && a.ksplit > 1) && rows1x1_fits(a, false))) return CK_TINY;
+  return pick_cfg<false>(a) >= 10 ? CK_EMU : CK_GEMM;
+}
 hipError_t conv1d(const ConvArgs& a, hipStream_t s) { return dispatch<false>(a, s); }
 hipError_t conv2d(const ConvArgs& a, hipStream_t s) { return dispatch<true>(a, s); }
 

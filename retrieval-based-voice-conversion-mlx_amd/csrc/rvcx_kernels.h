@@ -152,6 +152,8 @@ int conv_last_kind();
 const char* conv_kind_name(int k);
 // the contraction arithmetic a launch gets: ConvArgs::math, else RVCX_CONV_MATH (1 fp32 MFMA, 2 bf16 split, 3 fp16 split)
 int conv_math_of(const ConvArgs& a);
+// the family conv1d gives a 1-D launch that no streamed kernel takes (a.wsb == 0): CK_TINY, CK_EMU or CK_GEMM
+int conv_unstreamed_kind(const ConvArgs& a);
 hipError_t conv2d(const ConvArgs& a, hipStream_t s);
 // 3x3/pad-1 2-D convs with C_in, N in {16, 32} on 16x16x4 MFMA fragments (conv2d_small.hip); conv2d routes
 // the shapes conv2d_small_fits accepts there

@@ -29,7 +29,7 @@ EXPORTS = [
     "rvcx_index_retrieve", "rvcx_rt_default_desc", "rvcx_rt_default_opts", "rvcx_rt_create", "rvcx_rt_destroy",
     "rvcx_rt_geometry", "rvcx_rt_reset", "rvcx_rt_process", "rvcx_hubert_batch", "rvcx_rmvpe_batch",
     "rvcx_pipeline_batch", "rvcx_set_highpass_sos", "rvcx_highpass_pad", "rvcx_device_status", "rvcx_index_parse",
-    "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
+    "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
     "rvcx_crepe_decode",
 ]
@@ -86,6 +86,32 @@ class RtOpts(ctypes.Structure):
                 ("volume_envelope", ctypes.c_double), ("f0_autotune", ctypes.c_int),
                 ("f0_autotune_strength", ctypes.c_double), ("proposed_pitch", ctypes.c_int),
                 ("proposed_pitch_threshold", ctypes.c_double), ("gen_precision", ctypes.c_int)]
+
+
+class ConvTestDesc(ctypes.Structure):
+    """rvcx_conv_test_desc (include/rvcx.h): one 1-D contraction as the dispatcher's record takes it."""
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p),
+        ("mask", ctypes.c_void_p), ("pre_mask", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("T_in", ctypes.c_int), ("C_in", ctypes.c_int), ("N", ctypes.c_int), ("taps", ctypes.c_int),
+        ("dil", ctypes.c_int), ("pad", ctypes.c_int), ("stride", ctypes.c_int), ("T_out", ctypes.c_int),
+        ("ldx", ctypes.c_int), ("ldy", ctypes.c_int), ("ldr", ctypes.c_int),
+        ("batch", ctypes.c_int),
+        ("x_bs", ctypes.c_int64), ("y_bs", ctypes.c_int64), ("res_bs", ctypes.c_int64), ("mask_bs", ctypes.c_int64),
+        ("pre_mask_bs", ctypes.c_int64),
+        ("batch_inner", ctypes.c_int),
+        ("x_bs2", ctypes.c_int64), ("w_bs2", ctypes.c_int64), ("y_bs2", ctypes.c_int64), ("res_bs2", ctypes.c_int64),
+        ("bias_bs2", ctypes.c_int64),
+        ("pre_act", ctypes.c_int), ("pre_slope", ctypes.c_float),
+        ("act", ctypes.c_int), ("slope", ctypes.c_float), ("alpha", ctypes.c_float),
+        ("res_mode", ctypes.c_int), ("acc_mode", ctypes.c_int), ("acc_div", ctypes.c_float),
+        ("gate_h", ctypes.c_int), ("gate_g", ctypes.c_void_p), ("gate_g_bs", ctypes.c_int64),
+        ("ln_g", ctypes.c_void_p), ("ln_b", ctypes.c_void_p), ("ln_eps", ctypes.c_float),
+        ("nz_har", ctypes.c_void_p), ("nz_bs", ctypes.c_int64),
+        ("nz_stride", ctypes.c_int), ("nz_kk", ctypes.c_int), ("nz_u", ctypes.c_int), ("nz_C", ctypes.c_int),
+        ("nz_w", ctypes.c_void_p), ("nz_b", ctypes.c_void_p),
+        ("route", ctypes.c_int), ("no_splitk", ctypes.c_int),
+    ]
 
 
 _lib: Optional[ctypes.CDLL] = None
@@ -170,6 +196,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_conv1d": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
         "rvcx_conv1d_gen": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, i32, f32, i32,
                                   vp, vp]),
+        "rvcx_conv1d_ex": (i32, [vp, P(ConvTestDesc), P(i32), P(i32), vp]),
         "rvcx_conv2d3x3": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
         "rvcx_convtranspose2d_s2": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
         "rvcx_flash_attention": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, vp, vp, vp]),

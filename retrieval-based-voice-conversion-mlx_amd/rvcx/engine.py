@@ -609,6 +609,67 @@ class Engine:
                                              float(acc_div), kn, _ptr(y), self.stream()), "conv1d_gen")
         return y
 
+    ROUTES = {"policy": 0, "f32": 1, "emu": 2, "wsb": 3, "gs": 4, "wst": 5}
+
+    def conv1d_ex(self, x, w, y, *, T_in: int, C_in: int, N: int, T_out: int, ldx: int, ldy: int, taps: int = 1,
+                  dil: int = 1, pad: int = 0, stride: int = 1, ldr: int = 0, bias=None, res=None, mask=None,
+                  pre_mask=None, batch: int = 1, x_bs: int = 0, y_bs: int = 0, res_bs: int = 0, mask_bs: int = 0,
+                  pre_mask_bs: int = 0, batch_inner: int = 1, x_bs2: int = 0, w_bs2: int = 0, y_bs2: int = 0,
+                  res_bs2: int = 0, bias_bs2: int = 0, pre_act: int = 0, pre_slope: float = 0.0, act: int = 0,
+                  slope: float = 0.0, alpha: float = 1.0, res_mode: int = 0, acc_mode: int = 0, acc_div: float = 1.0,
+                  gate_h: int = 0, gate_g=None, gate_g_bs: int = 0, ln_g=None, ln_b=None, ln_eps: float = 1e-5,
+                  nz_har=None, nz_bs: int = 0, nz_stride: int = 0, nz_kk: int = 0, nz_u: int = 1, nz_C: int = 0,
+                  nz_w=None, nz_b=None, route="policy", no_splitk: bool = False):
+        """One 1-D contraction in any form the runtime issues (rvcx_conv1d_ex, include/rvcx.h): the fields of the
+        dispatcher's record, strides in floats. Every operand is a float32 tensor on this device and is passed as it
+        is -- a view's offset is its base pointer, nothing is copied or made contiguous -- and `y` is written in place.
+        Each operand's extent (the last element the form addresses) is checked against the storage behind its tensor
+        before the launch (ValueError). Returns (y, kernel family name, planned split count)."""
+        torch = self.torch
+        G, B, i64 = int(batch_inner), int(batch), int
+
+        def span(t, name, last):
+            """`last`: the largest element offset from t's first element that the form addresses."""
+            if t is None:
+                return None
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device):
+                raise ValueError(f"conv1d_ex: {name} must be a float32 tensor on {self.device}")
+            room = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+            if last < 0 or last >= room:
+                raise ValueError(f"conv1d_ex: {name} addresses element {last}, its storage holds {room} from the view")
+            return t.data_ptr()
+
+        ncol = gate_h if gate_h > 0 else N
+        d = _lib.ConvTestDesc()
+        d.x = span(x, "x", (B - 1) * x_bs + (G - 1) * x_bs2 + (T_in - 1) * ldx + C_in - 1)
+        d.w = span(w, "w", (G - 1) * w_bs2 + taps * N * C_in - 1)
+        d.y = span(y, "y", (B - 1) * y_bs + (G - 1) * y_bs2 + (T_out - 1) * ldy + ncol - 1)
+        d.bias = span(bias, "bias", (G - 1) * bias_bs2 + N - 1)
+        d.res = span(res, "res", (B - 1) * res_bs + (G - 1) * res_bs2 + (T_out - 1) * ldr + N - 1)
+        d.mask = span(mask, "mask", (B - 1) * mask_bs + T_out - 1)
+        d.pre_mask = span(pre_mask, "pre_mask", (B - 1) * pre_mask_bs + T_in - 1)
+        d.gate_g = span(gate_g, "gate_g", (B - 1) * gate_g_bs + N - 1)
+        d.ln_g, d.ln_b = span(ln_g, "ln_g", N - 1), span(ln_b, "ln_b", N - 1)
+        d.nz_har = span(nz_har, "nz_har", (B - 1) * nz_bs + (T_out * nz_u - 1) * nz_stride + max(nz_kk, 1) - 1)
+        d.nz_w = span(nz_w, "nz_w", nz_C * max(nz_stride, 1) * max(-(-nz_kk // max(nz_stride, 1)), 1) - 1)
+        d.nz_b = span(nz_b, "nz_b", nz_C - 1)
+        for k, v in dict(T_in=T_in, C_in=C_in, N=N, taps=taps, dil=dil, pad=pad, stride=stride, T_out=T_out, ldx=ldx,
+                         ldy=ldy, ldr=ldr, batch=B, x_bs=x_bs, y_bs=y_bs, res_bs=res_bs, mask_bs=mask_bs,
+                         pre_mask_bs=pre_mask_bs, batch_inner=G, x_bs2=x_bs2, w_bs2=w_bs2, y_bs2=y_bs2,
+                         res_bs2=res_bs2, bias_bs2=bias_bs2, pre_act=pre_act, act=act, res_mode=res_mode,
+                         acc_mode=acc_mode, gate_h=gate_h, gate_g_bs=gate_g_bs, nz_bs=nz_bs, nz_stride=nz_stride,
+                         nz_kk=nz_kk, nz_u=nz_u, nz_C=nz_C).items():
+            setattr(d, k, i64(v))
+        d.pre_slope, d.slope, d.alpha, d.acc_div, d.ln_eps = (float(pre_slope), float(slope), float(alpha),
+                                                              float(acc_div), float(ln_eps))
+        d.route = self.ROUTES[route] if isinstance(route, str) else int(route)
+        d.no_splitk = 1 if no_splitk else 0
+        kind, ksplit = ctypes.c_int(-1), ctypes.c_int(0)
+        self._check(self.lib.rvcx_conv1d_ex(self.ctx, ctypes.byref(d), ctypes.byref(kind), ctypes.byref(ksplit),
+                                            self.stream()), "conv1d_ex")
+        name = self.lib.rvcx_profile_kind_name(kind.value)
+        return y, (name.decode() if name else "other"), int(ksplit.value)
+
     def conv2d3x3(self, x, w, bias=None, relu: bool = False, math: str = "default"):
         """torch.nn.functional.conv2d(x.permute(2, 0, 1)[None], w, bias, padding=1)[0].permute(1, 2, 0) on the device
         kernel: x [H][W][C_in] (NHWC), w [N][C_in][3][3] (torch layout) -> [H][W][N] fp32 (rvcx_conv2d3x3); math
