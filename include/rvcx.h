@@ -33,7 +33,13 @@ typedef enum {
   RVCX_E_CAPACITY = -6 /* caller's output buffer too small */
 } rvcx_status;
 
-typedef enum { RVCX_MODEL_SYNTH = 0, RVCX_MODEL_HUBERT = 1, RVCX_MODEL_RMVPE = 2, RVCX_MODEL_CREPE = 3 } rvcx_model;
+typedef enum {
+  RVCX_MODEL_SYNTH = 0,
+  RVCX_MODEL_HUBERT = 1,
+  RVCX_MODEL_RMVPE = 2,
+  RVCX_MODEL_CREPE = 3,
+  RVCX_MODEL_FCPE = 4
+} rvcx_model;
 
 /* Synthesizer hyper-parameters = the 18-element ``cpt["config"]`` list of an RVC .pth
  * (rvc/train/process/extract_model.py:62-81) plus text_enc_hidden_dim (768 for v2). */
@@ -117,6 +123,43 @@ int rvcx_crepe_ex(rvcx_ctx* ctx, const float* d_audio, int64_t n, float f0_min, 
  * torchcrepe's viterbi + rvc/'s filters for 1) on caller-given probabilities d_probs [F][360]. */
 int rvcx_crepe_decode(rvcx_ctx* ctx, const float* d_probs, int64_t F, float f0_min, float f0_max, float threshold,
                       int semantics, const float* d_dither, float* d_f0, float* d_periodicity, void* stream);
+
+/* FCPE (f0 method "fcpe" of rvc/): the network of rvc/lib/predictors/FCPE.py, as FCPEInfer builds it from a
+ * checkpoint {"config": ..., "model": state_dict} (:731-756). rvcx_fcpe_desc carries the sizes of that config
+ * (config["mel"]: sampling_rate, n_fft, win_size, hop_size, num_mels, fmin, fmax -- Wav2Mel / STFT :767-783, :79-100;
+ * config["model"]: n_layers, n_chans, out_dims -- FCPE.__init__ :571-647; the attention is SelfAttention's 8 heads
+ * x 64 with nb_features = projection_matrix.shape[0], :462-512). Set it before rvcx_finalize(RVCX_MODEL_FCPE).
+ * Weights: RVCX_MODEL_FCPE under the module's state-dict names (stack.*, decoder._layers.N.{norm, attn.to_q/k/v/out,
+ * attn.fast_attention.projection_matrix, conformer.net.{0,2,4.conv,6}}, norm, dense_out with its weight-norm fused
+ * to dense_out.weight, cent_table). Supported: n_fft == win_size, win_size % 32 == hop_size % 32 == 0, num_mels % 32
+ * == 0, n_chans % 32 == 0 and <= 1024, nb_features <= 512, else RVCX_E_SHAPE. */
+typedef struct {
+  int sampling_rate, n_fft, win_size, hop_size, num_mels;
+  float fmin, fmax;
+  int n_layers, n_chans, out_dims;
+} rvcx_fcpe_desc;
+int rvcx_set_fcpe_config(rvcx_ctx* ctx, const rvcx_fcpe_desc* desc);
+
+/* FCPEInfer.__call__(audio, sr = sampling_rate, threshold) (FCPE.py:758-764) and, with interp_uv,
+ * FCPEF0Predictor.compute_f0's tail (:904-910). d_audio [n] fp32 at the config's sampling rate (no resampling:
+ * Wav2Mel.extract_mel's sample_rate == self.sample_rate branch, :790-813) -> mel (STFT.get_mel :102-168: pad
+ * (win - hop) / 2 left and max((win - hop + 1) / 2, win - n - left) right, reflect when that is < n else zeros;
+ * |STFT|, center = False; log mel; F = n / hop + 1 frames, the last one repeated when the STFT gives one fewer) ->
+ * FCPE.forward (:657-665: conv stack, n_layers x (Performer attention + Conformer conv module), LayerNorm, dense_out,
+ * sigmoid) -> salience [F][out_dims] -> decoder_mode 0 cents_local_decoder (:696-711, the default "local_argmax") or
+ * 1 cents_decoder (:683-694, "argmax"), cent_to_f0 (:713-714); f0 = 0 where the frame maximum <= threshold.
+ * interp_uv = 1: FCPEF0Predictor.post_process (:877-902) follows: the track is expanded to pad_to frames
+ * (repeat_expand, nearest; pad_to <= 0: F) and interpolated linearly through the unvoiced frames, the first / last
+ * voiced value held at the ends, zeros when no frame is voiced (:908-909).
+ * d_f0: fp64 [max(F, pad_to)] (the raw track holds the network's fp32 values exactly; np.interp's output is fp64);
+ * d_salience (optional) fp32 [F][out_dims]. cap_frames >= the frames written, *frames_out = their count. */
+int rvcx_fcpe(rvcx_ctx* ctx, const float* d_audio, int64_t n, float threshold, int decoder_mode, int interp_uv,
+              int64_t pad_to, double* d_f0, float* d_salience, int64_t cap_frames, int64_t* frames_out, void* stream);
+/* The decode alone (the tail of rvcx_fcpe after the network: FCPE.py:683-714, :877-902) on caller-given salience
+ * d_salience [F][out_dims], with the loaded model's cent table and hop / sampling rate. d_f0 fp64 [pad_to when
+ * interp_uv and pad_to > 0, else F]. */
+int rvcx_fcpe_decode(rvcx_ctx* ctx, const float* d_salience, int64_t F, float threshold, int decoder_mode,
+                     int interp_uv, int64_t pad_to, double* d_f0, void* stream);
 
 /* split_audio.process_audio (rvc/lib/tools/split_audio.py:5-27; rvc/infer/infer.py:282-284): the non-silent
  * intervals librosa.effects.split(audio, top_db=-silence_thresh_db, frame_length=int(min_silence_len_ms/1000*sr),
@@ -219,7 +262,10 @@ typedef struct {
   int f0_method;                    /* 0 = RMVPE (default), 1 = CREPE with the loaded RVCX_MODEL_CREPE weights
                                        (PitchExtractor.extract, pitch_extractors.py:155-156; f0_min 50, f0_max
                                        1100, threshold 0.1), 2 = CREPE as rvc/ runs it (pipeline.py:223-234;
-                                       rvcx_crepe_ex semantics 1, without the dither) */
+                                       rvcx_crepe_ex semantics 1, without the dither), 3 = FCPE with the loaded
+                                       RVCX_MODEL_FCPE weights (rvc/lib/predictors/f0.py:77-87: the raw track,
+                                       zeros where unvoiced; the model's hop must be 160 at 16 kHz) */
+  float fcpe_threshold;             /* FCPE's voicing threshold (FCPE.get_f0's filter_radius, f0.py:71); <= 0: 0.006 */
 } rvcx_pipeline_opts;
 
 /* Defaults of the rvc/ Config (x_pad 1, x_query 6, x_center 38, x_max 41; rvc/configs/config.py) at
@@ -244,7 +290,8 @@ int rvcx_pipeline_ex(rvcx_ctx* ctx, const double* d_audio, int64_t n, const rvcx
  * (batched RMVPE, HuBERT and Synthesizer.infer); row b of d_out (stride ldo) receives Pipeline.pipeline's
  * output for utterance b, n_out samples. Noise when injected: d_eps_z [B][inter][T], d_eps_src [B][T*upp].
  * Optional outputs: d_f0 [B][F] the adjusted f0 of each row (as rvcx_pipeline_ex's d_f0), d_hidden [B][F][360] the
- * RMVPE salience each row's f0 was decoded from (RMVPE f0 method only), F = 1 + (n + 2 t_pad)/160. */
+ * RMVPE salience each row's f0 was decoded from (RMVPE f0 method only), F = 1 + (n + 2 t_pad)/160. CREPE and FCPE
+ * (f0_method 1-3) run per row. */
 int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t lda, int B,
                         const rvcx_pipeline_opts* opts, const int32_t* sids, const float* d_eps_z,
                         const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
@@ -265,6 +312,8 @@ int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, doub
  *   so an arena of that size holds the call; the pool is released again before it returns. Inputs above t_max are
  *   sized on the worst-case split plan (the longest chunk any audio can give: the pipeline processes its chunks
  *   longest first, so the work buffers grow only inside the first chunk), so the size holds for any audio of n samples.
+ *   With f0_method 3 the FCPE network's scratch (mel, activations, the attention's ctx / ksum slab images) is carved
+ *   in place of RMVPE's; the call is then sized under f0_method 0 as well and the larger size is reported.
  * rvcx_set_workspace: hand the context a caller-owned device arena (e.g. a torch uint8 tensor's data_ptr(), 256-B
  *   aligned), valid until replaced or the context is destroyed: the pool is then carved from it and never allocated,
  *   and a call that would need more fails with RVCX_E_OOM. NULL, 0 returns to internal allocation. The current pool

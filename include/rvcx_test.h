@@ -1,0 +1,31 @@
+/*
+ * rvcx — kernel-level entry points for the numerics tests. Exported from librvcx.so beside the public C ABI
+ * (include/rvcx.h) but not part of it: a product links rvcx.h alone. Conventions as there (device pointers, the
+ * call is asynchronous on `stream`, rvcx_status returned, rvcx_last_error for the message).
+ */
+#ifndef RVCX_TEST_H_
+#define RVCX_TEST_H_
+
+#include "rvcx.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Performer (FAVOR+) linear attention on the kernels of csrc/performer_attn.hip, as FCPE's SelfAttention runs it
+ * after its q / k / v projections (rvc/lib/predictors/FCPE.py: FastAttention.forward :439-459, softmax_kernel
+ * :179-212, linear_attention :354-363): d_q, d_k, d_v [H][T][64], d_P [M][64] (projection_matrix, M <= 512) ->
+ * d_out [H][T][64]. */
+int rvcx_performer_attention(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int H, int T,
+                             const float* d_P, int M, float* d_out, void* stream);
+
+/* The FCPE network's input alone, as rvcx_fcpe forms it (rvc/lib/predictors/FCPE.py: Wav2Mel.extract_mel :790-813 over
+ * STFT.get_mel :102-168): d_audio [n] fp32 at the loaded model's sampling rate -> d_mel [F][num_mels], the log-mel of
+ * every band, F = n / hop + 1 frames (*frames_out; cap_frames >= F). Needs RVCX_MODEL_FCPE finalized. */
+int rvcx_fcpe_mel(rvcx_ctx* ctx, const float* d_audio, int64_t n, float* d_mel, int64_t cap_frames,
+                  int64_t* frames_out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RVCX_TEST_H_ */

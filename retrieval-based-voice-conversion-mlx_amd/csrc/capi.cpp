@@ -9,6 +9,7 @@
 #include <unistd.h>
 #include <vector>
 
+#include "../../include/rvcx_test.h"
 #include "runtime.h"
 
 extern char** environ;
@@ -351,7 +352,7 @@ int rvcx_set_synth_config(rvcx_ctx* ctx, const rvcx_synth_desc* d) {
 
 int rvcx_upload(rvcx_ctx* ctx, int model, const char* name, const float* host, const int64_t* shape, int ndim) {
   return guard(ctx, [&] {
-    if (model < 0 || model > 3 || !name || !host || (ndim > 0 && !shape) || ndim < 0 || ndim > 8)
+    if (model < 0 || model > RVCX_MODEL_FCPE || !name || !host || (ndim > 0 && !shape) || ndim < 0 || ndim > 8)
       throw Error(RVCX_E_INVALID, "rvcx_upload: bad arguments");
     HostTensor t;
     size_t n = 1;
@@ -377,6 +378,8 @@ int rvcx_finalize(rvcx_ctx* ctx, int model) {
       finalize_rmvpe(*ctx);
     } else if (model == RVCX_MODEL_CREPE) {
       finalize_crepe(*ctx);
+    } else if (model == RVCX_MODEL_FCPE) {
+      finalize_fcpe(*ctx);
     } else {
       throw Error(RVCX_E_INVALID, "unknown model");
     }
@@ -464,6 +467,80 @@ int rvcx_crepe_decode(rvcx_ctx* ctx, const float* d_probs, int64_t F, float f0_m
       check(crepe_decode(d_probs, (int)F, 1200.0 * std::log2(f0_min / 10.0), 1200.0 * std::log2(f0_max / 10.0),
                          threshold, f0r, pr, d_f0, nullptr, d_periodicity, s), "crepe_decode");
     }
+  });
+}
+
+int rvcx_set_fcpe_config(rvcx_ctx* ctx, const rvcx_fcpe_desc* d) {
+  return guard(ctx, [&] {
+    if (!d) throw Error(RVCX_E_INVALID, "null desc");
+    FcpeCfg g;
+    g.sr = d->sampling_rate;
+    g.n_fft = d->n_fft;
+    g.win = d->win_size;
+    g.hop = d->hop_size;
+    g.n_mels = d->num_mels;
+    g.fmin = d->fmin;
+    g.fmax = d->fmax;
+    g.n_layers = d->n_layers;
+    g.n_chans = d->n_chans;
+    g.out_dims = d->out_dims;
+    if (g.sr < 1 || g.n_fft < 1 || g.win < 1 || g.hop < 1 || g.n_mels < 1 || g.n_layers < 1 || g.n_layers > 64 ||
+        g.n_chans < 1 || g.out_dims < 1)
+      throw Error(RVCX_E_INVALID, "rvcx_set_fcpe_config: sizes must be positive");
+    ctx->fcfg = g;
+    ctx->ready[RVCX_MODEL_FCPE] = false;
+  });
+}
+
+int rvcx_fcpe(rvcx_ctx* ctx, const float* d_audio, int64_t n, float threshold, int decoder_mode, int interp_uv,
+              int64_t pad_to, double* d_f0, float* d_salience, int64_t cap_frames, int64_t* frames_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+    if (!d_audio || !d_f0 || n <= 0 || decoder_mode < 0 || decoder_mode > 1 || pad_to < 0)
+      throw Error(RVCX_E_INVALID, "rvcx_fcpe: bad arguments");
+    set_device(ctx);
+    const int64_t F = fcpe_forward(*ctx, d_audio, n, threshold, decoder_mode, interp_uv ? 1 : 0, pad_to, d_f0,
+                                   d_salience, cap_frames, static_cast<hipStream_t>(stream));
+    if (frames_out) *frames_out = F;
+  });
+}
+
+int rvcx_fcpe_decode(rvcx_ctx* ctx, const float* d_salience, int64_t F, float threshold, int decoder_mode,
+                     int interp_uv, int64_t pad_to, double* d_f0, void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+    if (!d_salience || !d_f0 || F <= 0 || decoder_mode < 0 || decoder_mode > 1 || pad_to < 0)
+      throw Error(RVCX_E_INVALID, "rvcx_fcpe_decode: bad arguments");
+    set_device(ctx);
+    fcpe_decode_run(*ctx, d_salience, F, threshold, decoder_mode, interp_uv ? 1 : 0, pad_to, d_f0,
+                    static_cast<hipStream_t>(stream));
+  });
+}
+
+int rvcx_fcpe_mel(rvcx_ctx* ctx, const float* d_audio, int64_t n, float* d_mel, int64_t cap_frames, int64_t* frames_out,
+                  void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+    if (!d_audio || !d_mel || n <= 0) throw Error(RVCX_E_INVALID, "rvcx_fcpe_mel: bad arguments");
+    if (cap_frames < fcpe_frames(*ctx, n)) throw Error(RVCX_E_CAPACITY, "rvcx_fcpe_mel: output capacity too small");
+    set_device(ctx);
+    const int F = fcpe_mel(*ctx, d_audio, n, d_mel, static_cast<hipStream_t>(stream));
+    if (frames_out) *frames_out = F;
+  });
+}
+
+int rvcx_performer_attention(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int H, int T,
+                             const float* d_P, int M, float* d_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_q || !d_k || !d_v || !d_P || !d_out || H <= 0 || T <= 0 || M <= 0)
+      throw Error(RVCX_E_INVALID, "rvcx_performer_attention: bad argument");
+    if (M > PERFORMER_MAX_FEATURES || (long long)H * T * 64 > INT32_MAX)
+      throw Error(RVCX_E_SHAPE, "rvcx_performer_attention: at most 512 features and 2^31 elements per operand");
+    set_device(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* ws = ctx->buf<float>("perf.test.ws", (size_t)performer_ws_floats(H, T, M), s);
+    check(performer_attention(d_q, d_k, d_v, (long long)T * 64, 64, H, T, d_P, M, ws, d_out, (long long)T * 64, 64, s),
+          "performer_attention");
   });
 }
 
@@ -711,16 +788,27 @@ int rvcx_workspace_bytes(rvcx_ctx* ctx, int B, int64_t n, const rvcx_pipeline_op
       RVCX_HIP(hipMalloc(&audio.p, sizeof(double) * (size_t)(B * n)));
       RVCX_HIP(hipMalloc(&out.p, sizeof(float) * (size_t)(B * cap)));
       RVCX_HIP(hipMemsetAsync(audio.p, 0, sizeof(double) * (size_t)(B * n), s));
-      if (B == 1) {
-        pipeline_forward_ex(*ctx, static_cast<const double*>(audio.p), n, *opts, nullptr, nullptr, 0,
-                            static_cast<float*>(out.p), cap, nullptr, s);
-      } else {
-        std::vector<int32_t> sids((size_t)B, opts->sid);
-        pipeline_forward_batch(*ctx, static_cast<const double*>(audio.p), n, n, B, *opts, sids.data(), nullptr, nullptr, 0,
-                               static_cast<float*>(out.p), cap, nullptr, nullptr, s);
+      auto measure = [&](const rvcx_pipeline_opts& o) {
+        if (B == 1) {
+          pipeline_forward_ex(*ctx, static_cast<const double*>(audio.p), n, o, nullptr, nullptr, 0,
+                              static_cast<float*>(out.p), cap, nullptr, s);
+        } else {
+          std::vector<int32_t> sids((size_t)B, o.sid);
+          pipeline_forward_batch(*ctx, static_cast<const double*>(audio.p), n, n, B, o, sids.data(), nullptr, nullptr, 0,
+                                 static_cast<float*>(out.p), cap, nullptr, nullptr, s);
+        }
+        RVCX_HIP(hipStreamSynchronize(s));
+        return (int64_t)ctx->carved;
+      };
+      need = measure(*opts);
+      if (opts->f0_method == 3) {
+        // FCPE's scratch is carved in place of RMVPE's, which can be the larger: the size also holds the same call
+        // with the default f0 method, so an arena sized for "fcpe" serves a caller that switches back
+        rvcx_pipeline_opts o0 = *opts;
+        o0.f0_method = 0;
+        ctx->release_pool();
+        need = std::max(need, measure(o0));
       }
-      RVCX_HIP(hipStreamSynchronize(s));
-      need = (int64_t)ctx->carved;
       // the per-chunk HuBERT feature buffers (pl.hb<i>) sum to the same total over any split plan up to one row and
       // the 256-B rounding per chunk
       if (B == 1 && opts->t_max > 0 && n + 160 > opts->t_max && opts->t_center > 0) {

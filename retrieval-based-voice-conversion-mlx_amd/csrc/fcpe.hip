@@ -1,0 +1,279 @@
+// Non-GEMM kernels of the FCPE pitch network (rvc/lib/predictors/FCPE.py): the STFT magnitude of its mel, the input
+// stack's GroupNorm + LeakyReLU, the Conformer module's GLU + depthwise conv + Swish, the cents decoders and
+// FCPEF0Predictor.post_process. The Performer attention is performer_attn.hip; the convs and linears run on the
+// implicit-GEMM family.
+#include <algorithm>
+#include <cmath>
+
+#include "rvcx_kernels.h"
+
+namespace rvcx {
+
+namespace {
+
+constexpr int TB = 256;
+
+inline unsigned nblocks(long long n, int per = TB) {
+  long long b = (n + per - 1) / per;
+  if (b > 65535LL * 32) b = 65535LL * 32;
+  return (unsigned)(b < 1 ? 1 : b);
+}
+
+__device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
+
+// sqrt(re^2 + im^2 + 1e-9) (FCPE.py:154) in rows of ldm floats: bins 0 .. nb - 1, then zeros up to ldm
+__global__ void k_fcpe_mag(const float* spec, int F, int nb, float* mag, int ldm) {
+  const long long n = (long long)F * ldm;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int f = (int)(i / ldm), k = (int)(i % ldm);
+    float v = 0.f;
+    if (k < nb) {
+      const float re = spec[(long long)f * 2 * nb + k];
+      const float im = spec[(long long)f * 2 * nb + nb + k];
+      v = sqrtf(re * re + im * im + 1e-9f);
+    }
+    mag[i] = v;
+  }
+}
+
+// GroupNorm(G, C) over time-major x [T][C] in place, then LeakyReLU(slope) (FCPE.py:626-630: the statistics of a
+// group run over its C / G channels x T frames). Two launches: k_gn_stats sums each of GN_TCHUNKS time chunks of a
+// group in fp64 (a fixed tree over the workgroup) into ws [G][GN_TCHUNKS][2]; k_gn_apply adds the chunks in chunk
+// order (every thread the same sequence: no atomics, run-to-run bit identical) and normalises.
+constexpr int GN_TCHUNKS = FCPE_GN_CHUNKS;
+__global__ __launch_bounds__(256) void k_gn_stats(const float* x, int T, int C, int G, double* ws) {
+  __shared__ double s1[256], s2[256];
+  const int g = blockIdx.y, cg = C / G, c0 = g * cg;
+  const int per = (T + GN_TCHUNKS - 1) / GN_TCHUNKS;
+  const int t_lo = min(T, (int)blockIdx.x * per), t_hi = min(T, t_lo + per);
+  const long long n = (long long)(t_hi - t_lo) * cg;
+  double a = 0.0, b = 0.0;
+  for (long long i = threadIdx.x; i < n; i += blockDim.x) {
+    const double v = x[(t_lo + i / cg) * C + c0 + (int)(i % cg)];
+    a += v;
+    b += v * v;
+  }
+  s1[threadIdx.x] = a;
+  s2[threadIdx.x] = b;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      s1[threadIdx.x] += s1[threadIdx.x + o];
+      s2[threadIdx.x] += s2[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    ws[((long long)g * GN_TCHUNKS + blockIdx.x) * 2] = s1[0];
+    ws[((long long)g * GN_TCHUNKS + blockIdx.x) * 2 + 1] = s2[0];
+  }
+}
+__global__ __launch_bounds__(256) void k_gn_apply(float* x, int T, int C, int G, const double* ws, const float* gamma,
+                                                  const float* beta, float eps, float slope) {
+  const int g = blockIdx.y, cg = C / G, c0 = g * cg;
+  const long long n = (long long)T * cg;
+  double a = 0.0, b = 0.0;
+  for (int k = 0; k < GN_TCHUNKS; ++k) {
+    a += ws[((long long)g * GN_TCHUNKS + k) * 2];
+    b += ws[((long long)g * GN_TCHUNKS + k) * 2 + 1];
+  }
+  const double mean = a / (double)n;
+  const double var = fmax(b / (double)n - mean * mean, 0.0);
+  const float mu = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)eps));
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int c = c0 + (int)(i % cg);
+    float* p = x + (i / cg) * C + c;
+    const float v = (*p - mu) * rstd * gamma[c] + beta[c];
+    *p = v > 0.f ? v : v * slope;
+  }
+}
+
+// ConformerConvModule's middle (FCPE.py:339-344) as one kernel over the 1x1 conv's output x [T][2 C2]:
+//   g[t][c] = x[t][c] sigmoid(x[t][C2 + c])                         GLU (formed while the tile is loaded)
+//   y[t][c] = swish(b[c] + sum_k w[k][c] g[t + k - pad][c])         depthwise conv, zero padding, Swish
+// One workgroup per (64 channels, 32 output frames): the GLU'd rows t0 - pad .. t0 + 31 + K - 1 - pad sit in LDS.
+constexpr int DW_T = 32, DW_MAXK = 64;
+__global__ __launch_bounds__(256) void k_glu_dw_swish(const float* x, int T, int C2, const float* w, const float* b,
+                                                       int K, int pad, float* y) {
+  __shared__ float g[(DW_T + DW_MAXK - 1) * 64];
+  const int cl = threadIdx.x & 63, tg = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  const int t0 = blockIdx.y * DW_T;
+  const int rows = DW_T + K - 1;
+  for (int i = tg; i < rows; i += 4) {
+    const int t = t0 - pad + i;
+    float v = 0.f;
+    if (t >= 0 && t < T) {
+      const float* xr = x + (long long)t * 2 * C2;
+      v = xr[c] * sigmoidf(xr[C2 + c]);
+    }
+    g[i * 64 + cl] = v;
+  }
+  __syncthreads();
+  const float bias = b[c];
+#pragma unroll
+  for (int j = 0; j < DW_T / 4; ++j) {
+    const int r = tg * (DW_T / 4) + j;
+    if (t0 + r >= T) break;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) acc = fmaf(w[k * C2 + c], g[(r + k) * 64 + cl], acc);
+    const float v = acc + bias;
+    y[(long long)(t0 + r) * C2 + c] = v * sigmoidf(v);
+  }
+}
+
+// cents_local_decoder / cents_decoder + cent_to_f0 (FCPE.py:683-714): one wave per frame of salience [F][nb].
+//   mode 0 "local_argmax": the first maximal bin, its +-4 window with every index clamped to [0, nb - 1] (a clamped
+//          index counts once per window slot, as torch.gather does), cents = sum(ci y) / sum(y) over the 9 slots
+//   mode 1 "argmax": cents = sum(ci y) / sum(y) over all bins
+// f0 = 10 * 2^(cents / 1200), 0 where max <= threshold (the reference's -inf cents). The fp32 products are summed in
+// fp64 and the quotient is taken in fp32; f0 is written as the exact fp32 value in fp64.
+__global__ void k_fcpe_decode(const float* sal, int F, int nb, const float* cent, float thr, int mode, double* f0) {
+  const int f = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (f >= F) return;
+  const float* s = sal + (long long)f * nb;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  double num = 0.0, den = 0.0;
+  for (int k = lane; k < nb; k += 64) {
+    const float v = s[k];
+    if (v > best) {
+      best = v;
+      bi = k;
+    }
+    num += (double)(cent[k] * v);
+    den += (double)v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+    num += __shfl_xor(num, o, 64);
+    den += __shfl_xor(den, o, 64);
+  }
+  if (lane != 0) return;
+  if (mode == 0) {
+    num = 0.0;
+    den = 0.0;
+    for (int j = 0; j < 9; ++j) {
+      const int k = min(max(bi - 4 + j, 0), nb - 1);
+      num += (double)(cent[k] * s[k]);
+      den += (double)s[k];
+    }
+  }
+  const float cents = (float)num / (float)den;
+  f0[f] = best <= thr ? 0.0 : (double)(10.f * exp2f(cents / 1200.f));
+}
+
+// FCPEF0Predictor.post_process (FCPE.py:877-902) on a raw track f0 [F]: e[i] = f0[nearest(i)] for i < n
+// (repeat_expand: torch's nearest interpolation), then np.interp through the frames with e != 0, the first / last
+// of them held at the ends; zeros when there is none.
+__device__ __forceinline__ int nearest_src(int i, int F, int n) {  // ATen nearest_idx (UpSample.h)
+  if (n == F) return i;
+  if (n == 2 * F) return i >> 1;
+  const float scale = (float)F / (float)n;
+  return min((int)floorf((float)i * scale), F - 1);
+}
+
+// prev[i] / next[i]: the nearest index <= i / >= i with e != 0 (-1 / n when none). One workgroup; thread k owns
+// the segment [k L, (k + 1) L).
+__global__ __launch_bounds__(1024) void k_fcpe_voiced_links(const double* f0, int F, int n, int* prev, int* next) {
+  __shared__ int last[1024], first[1024];
+  const int L = (n + 1023) / 1024;
+  const int lo = min(n, (int)threadIdx.x * L), hi = min(n, lo + L);
+  int la = -1, fi = n;
+  for (int i = lo; i < hi; ++i)
+    if (f0[nearest_src(i, F, n)] != 0.0) {
+      la = i;
+      if (fi == n) fi = i;
+    }
+  last[threadIdx.x] = la;
+  first[threadIdx.x] = fi;
+  __syncthreads();
+  int carry = -1;
+  for (int k = (int)threadIdx.x - 1; k >= 0 && carry < 0; --k) carry = last[k];
+  for (int i = lo; i < hi; ++i) {
+    if (f0[nearest_src(i, F, n)] != 0.0) carry = i;
+    prev[i] = carry;
+  }
+  carry = n;
+  for (int k = (int)threadIdx.x + 1; k < 1024 && carry == n; ++k) carry = first[k];
+  for (int i = hi - 1; i >= lo; --i) {
+    if (f0[nearest_src(i, F, n)] != 0.0) carry = i;
+    next[i] = carry;
+  }
+}
+
+__global__ void k_fcpe_interp(const double* f0, int F, int n, const int* prev, const int* next, double hop, double sr,
+                              double* out) {
+#pragma clang fp contract(off)  // numpy rounds every product and sum separately
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int p = prev[i], q = next[i];
+  double v;
+  if (p < 0 && q >= n) {
+    v = 0.0;
+  } else if (p < 0) {
+    v = f0[nearest_src(q, F, n)];
+  } else if (q >= n || p == i) {
+    v = f0[nearest_src(p, F, n)];
+  } else {
+    // np.interp: slope (x - xp[j]) + fp[j] with xp = hop / sr * index (time_org), x = i * hop / sr (time_frame).
+    // At a voiced frame (p == i, above) the value itself is returned; np.interp's x and xp there can differ by an
+    // ulp, in which case it interpolates from the neighbouring segment: a difference of ~1e-16 relative
+    const double fp0 = f0[nearest_src(p, F, n)], fp1 = f0[nearest_src(q, F, n)];
+    const double step = hop / sr;
+    const double x0 = step * (double)p, x1 = step * (double)q, xx = ((double)i * hop) / sr;
+    const double slope = (fp1 - fp0) / (x1 - x0);
+    v = slope * (xx - x0) + fp0;
+  }
+  out[i] = v;
+}
+
+}  // namespace
+
+hipError_t fcpe_magnitude(const float* spec, int F, int nbins, float* mag, int ldm, hipStream_t s) {
+  if (ldm < nbins) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_mag, dim3(nblocks((long long)F * ldm)), dim3(TB), 0, s, spec, F, nbins, mag, ldm);
+  return hipGetLastError();
+}
+
+hipError_t groupnorm_lrelu(float* x, int T, int C, int G, const float* gamma, const float* beta, float eps, float slope,
+                           double* ws, hipStream_t s) {
+  if (T < 1 || G < 1 || C % G || !ws) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_gn_stats, dim3(GN_TCHUNKS, G), dim3(256), 0, s, x, T, C, G, ws);
+  const long long n = (long long)T * (C / G);
+  hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), G), dim3(256), 0, s, x, T,
+                     C, G, ws, gamma, beta, eps, slope);
+  return hipGetLastError();
+}
+
+hipError_t glu_dwconv_swish(const float* x, int T, int C2, const float* w, const float* b, int K, int pad, float* y,
+                            hipStream_t s) {
+  if (T < 1 || C2 % 64 || K < 1 || K > DW_MAXK || pad < 0 || pad >= K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_glu_dw_swish, dim3(C2 / 64, (T + DW_T - 1) / DW_T), dim3(256), 0, s, x, T, C2, w, b, K, pad, y);
+  return hipGetLastError();
+}
+
+hipError_t fcpe_decode(const float* sal, int F, int nb, const float* cent, float thr, int mode, double* f0,
+                       hipStream_t s) {
+  if (F < 1 || nb < 1 || mode < 0 || mode > 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_decode, dim3((F + 3) / 4), dim3(256), 0, s, sal, F, nb, cent, thr, mode, f0);
+  return hipGetLastError();
+}
+
+hipError_t fcpe_post_process(const double* f0, int F, int n, int hop, int sr, int* links, double* out,
+                             hipStream_t s) {
+  if (F < 1 || n < 1 || hop < 1 || sr < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_voiced_links, dim3(1), dim3(1024), 0, s, f0, F, n, links, links + n);
+  hipLaunchKernelGGL(k_fcpe_interp, dim3(nblocks(n)), dim3(TB), 0, s, f0, F, n, links, links + n, (double)hop,
+                     (double)sr, out);
+  return hipGetLastError();
+}
+
+}  // namespace rvcx

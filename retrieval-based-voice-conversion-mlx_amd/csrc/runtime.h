@@ -75,6 +75,16 @@ struct SynthCfg {
   long long src_noise_total(int B, long long T) const;
 };
 
+// FCPE hyper-parameters: config["mel"] / config["model"] of an FCPE checkpoint (FCPE.py:731-756, rvcx_fcpe_desc)
+struct FcpeCfg {
+  int sr = 16000, n_fft = 1024, win = 1024, hop = 160, n_mels = 128;
+  double fmin = 0.0, fmax = 8000.0;
+  int n_layers = 6, n_chans = 512, out_dims = 360;
+  int n_heads = 8, dim_head = 64;  // SelfAttention's defaults (FCPE.py:466-468), fixed in FCPE
+  int n_feat = 0;                  // projection_matrix rows, from the weights (finalize_fcpe)
+  int conv_k = 31;                 // ConformerConvModule's depthwise kernel (FCPE.py:329)
+};
+
 // ConvTranspose1d lowered to a polyphase conv: input row for output q, tap t is q + t - pad.
 struct UpsLayer {
   int cin = 0, cout = 0, u = 0, k = 0, taps = 0, pad = 0;
@@ -93,9 +103,10 @@ struct Ctx {
   std::string err;
   SynthCfg scfg;
   bool synth_cfg_set = false;
-  std::map<std::string, HostTensor> host[4];  // synth, hubert, rmvpe, crepe
+  FcpeCfg fcfg;
+  std::map<std::string, HostTensor> host[5];  // synth, hubert, rmvpe, crepe, fcpe
   std::map<std::string, std::unique_ptr<DevBuf>> dev;  // packed weights
-  bool ready[4] = {false, false, false, false};
+  bool ready[5] = {false, false, false, false, false};
   std::vector<UpsLayer> ups;
   // pipeline high-pass (rvc/infer/pipeline.py:22-27), normalised so a[0] = 1
   int hp_order = 0;
@@ -284,6 +295,18 @@ void refinegan_forward(Ctx& c, int B, int T, const float* z_btc, const float* ma
 void finalize_hubert(Ctx& c);
 void finalize_rmvpe(Ctx& c);
 void finalize_crepe(Ctx& c);
+void finalize_fcpe(Ctx& c);
+// FCPEInfer.__call__ (+ FCPEF0Predictor.post_process when interp_uv) on audio [n] fp32 (rvc/lib/predictors/FCPE.py
+// :758-764, :877-910): f0 fp64 [frames], salience [F][out_dims] optional. Returns the frames written to f0
+// (F = n / hop + 1, or pad_to when interp_uv and pad_to > 0); cap = the capacity of f0 in frames.
+int64_t fcpe_frames(const Ctx& c, int64_t n);
+// the network's input alone: Wav2Mel.extract_mel (FCPE.py:790-813) -> mel [fcpe_frames(n)][n_mels]; returns the frames
+int fcpe_mel(Ctx& c, const float* audio, int64_t n, float* mel, hipStream_t s);
+int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
+                     double* f0, float* sal_out, int64_t cap, hipStream_t s);
+// the decoders + post_process alone on salience [F][out_dims]
+int64_t fcpe_decode_run(Ctx& c, const float* sal, int64_t F, float thr, int mode, int interp_uv, int64_t pad_to,
+                        double* f0, hipStream_t s);
 // librosa.effects.split of split_audio.process_audio (rvc/lib/tools/split_audio.py:5-27): intervals [cnt][2]
 int64_t split_intervals(Ctx& c, const double* audio, int64_t n, int sr, double silence_thresh_db, int min_silence_ms,
                         int64_t* iv, int64_t cap, hipStream_t s);

@@ -226,15 +226,27 @@ int proposed_key(const std::vector<double>& f0, double threshold) {
   return (int)std::max(-12.0, std::min(12.0, key));
 }
 
+// f0_method of rvcx_pipeline_opts against the loaded models
+static void check_f0_method(const Ctx& c, const rvcx_pipeline_opts& o) {
+  if (o.f0_method < 0 || o.f0_method > 3)
+    throw Error(RVCX_E_INVALID, "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX), 2 (crepe, rvc/) or 3 (fcpe)");
+  if (!c.scfg.f0) return;
+  if ((o.f0_method == 1 || o.f0_method == 2) && !c.ready[RVCX_MODEL_CREPE])
+    throw Error(RVCX_E_STATE, "pipeline: f0_method crepe but no CREPE weights finalized");
+  if (o.f0_method == 3) {
+    if (!c.ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "pipeline: f0_method fcpe but no FCPE weights finalized");
+    if (c.fcfg.sr != 16000 || c.fcfg.hop != 160)  // the pipeline's pitch frames are 160 samples at 16 kHz
+      throw Error(RVCX_E_SHAPE, "pipeline: the FCPE model must run at 16 kHz with hop_size 160");
+  }
+}
+static float fcpe_thr(const rvcx_pipeline_opts& o) { return o.fcpe_threshold > 0 ? o.fcpe_threshold : 0.006f; }
+
 int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
                             const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
                             double* f0_out, hipStream_t s) {
   if (c.hp_order == 0) throw Error(RVCX_E_STATE, "pipeline: high-pass filter not configured");
   if (o.t_pad < 0 || o.t_pad_tgt < 0 || o.t_pad >= n) throw Error(RVCX_E_INVALID, "pipeline: bad t_pad");
-  if (o.f0_method < 0 || o.f0_method > 2)
-    throw Error(RVCX_E_INVALID, "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX) or 2 (crepe, rvc/)");
-  if (o.f0_method >= 1 && c.scfg.f0 && !c.ready[RVCX_MODEL_CREPE])
-    throw Error(RVCX_E_STATE, "pipeline: f0_method crepe but no CREPE weights finalized");
+  check_f0_method(c, o);
   if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "pipeline: index_rate > 0 but no feature index loaded");
   if (o.index_rate > 0 && c.ivf->view.d != c.scfg.emb_dim)
     throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension does not match the model's feature width");
@@ -370,8 +382,14 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
       gate_here(s);
       rest(s);
     }
-    float* f0f = c.buf<float>("pl.f0f", (size_t)F, s);
-    crepe_forward(c, pad32, m, 50.0, 1100.0, 0.1f, f0f, f0, nullptr, nullptr, s, o.f0_method == 2 ? 1 : 0);
+    if (o.f0_method == 3) {
+      // FCPE.get_f0 (rvc/lib/predictors/f0.py:71-89; pipeline.py's "fcpe" branch): the raw local_argmax track over
+      // the whole padded input, F = 1 + m / 160 frames
+      fcpe_forward(c, pad32, m, fcpe_thr(o), 0, 0, 0, f0, nullptr, F, s);
+    } else {
+      float* f0f = c.buf<float>("pl.f0f", (size_t)F, s);
+      crepe_forward(c, pad32, m, 50.0, 1100.0, 0.1f, f0f, f0, nullptr, nullptr, s, o.f0_method == 2 ? 1 : 0);
+    }
   } else {
     rmvpe_forward(c, pad32, m, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, nullptr, s);
   }
@@ -479,10 +497,7 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
   if (c.hp_order == 0) throw Error(RVCX_E_STATE, "pipeline: high-pass filter not configured");
   if (o.t_pad < 0 || o.t_pad_tgt < 0 || o.t_pad >= n) throw Error(RVCX_E_INVALID, "pipeline: bad t_pad");
-  if (o.f0_method < 0 || o.f0_method > 2)
-    throw Error(RVCX_E_INVALID, "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX) or 2 (crepe, rvc/)");
-  if (o.f0_method >= 1 && c.scfg.f0 && !c.ready[RVCX_MODEL_CREPE])
-    throw Error(RVCX_E_STATE, "pipeline: f0_method crepe but no CREPE weights finalized");
+  check_f0_method(c, o);
   if (o.t_max > 0 && n + 160 > o.t_max)
     throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
   if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "pipeline: index_rate > 0 but no feature index loaded");
@@ -510,7 +525,10 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   int32_t* pitch = nullptr;
   float* pitchf = nullptr;
   if (guided) {
-  if (o.f0_method >= 1) {  // CREPE per utterance (frames of all rows would not batch any better: B x F frames)
+  if (o.f0_method == 3) {  // FCPE per utterance, as CREPE below
+    for (int b = 0; b < B; ++b)
+      fcpe_forward(c, pad32 + (size_t)b * ldm, m, fcpe_thr(o), 0, 0, 0, f0 + (size_t)b * F, nullptr, F, s);
+  } else if (o.f0_method >= 1) {  // CREPE per utterance (frames of all rows would not batch any better: B x F frames)
     float* f0f = c.buf<float>("pb.f0f", (size_t)F, s);
     for (int b = 0; b < B; ++b)
       crepe_forward(c, pad32 + (size_t)b * ldm, m, 50.0, 1100.0, 0.1f, f0f, f0 + (size_t)b * F, nullptr, nullptr, s,
@@ -617,6 +635,7 @@ rvcx_pipeline_opts default_pipeline_opts() {
   o.f0_autotune_strength = 1.0;
   o.proposed_pitch_threshold = 155.0;
   o.volume_envelope = 1.0;
+  o.fcpe_threshold = 0.006f;
   return o;
 }
 

@@ -12,7 +12,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RVCX_LIB", os.path.join(_HERE, "librvcx.so"))
 
-RVCX_MODEL_SYNTH, RVCX_MODEL_HUBERT, RVCX_MODEL_RMVPE, RVCX_MODEL_CREPE = 0, 1, 2, 3
+RVCX_MODEL_SYNTH, RVCX_MODEL_HUBERT, RVCX_MODEL_RMVPE, RVCX_MODEL_CREPE, RVCX_MODEL_FCPE = 0, 1, 2, 3, 4
 
 STATUS = {
     0: "RVCX_OK", -1: "RVCX_E_INVALID", -2: "RVCX_E_SHAPE", -3: "RVCX_E_HIP", -4: "RVCX_E_OOM",
@@ -31,8 +31,10 @@ EXPORTS = [
     "rvcx_pipeline_batch", "rvcx_set_highpass_sos", "rvcx_highpass_pad", "rvcx_device_status", "rvcx_index_parse",
     "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
-    "rvcx_crepe_decode",
+    "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode",
 ]
+# kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
+TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_fcpe_mel"]
 
 
 class RvcxLibraryError(ImportError):
@@ -70,7 +72,16 @@ class PipelineOpts(ctypes.Structure):
         ("f0_autotune", ctypes.c_int), ("f0_autotune_strength", ctypes.c_double), ("proposed_pitch", ctypes.c_int),
         ("proposed_pitch_threshold", ctypes.c_double), ("volume_envelope", ctypes.c_double),
         ("mlx_semantics", ctypes.c_int), ("index_rate", ctypes.c_double), ("f0_method", ctypes.c_int),
+        ("fcpe_threshold", ctypes.c_float),
     ]
+
+
+class FcpeDesc(ctypes.Structure):
+    """rvcx_fcpe_desc (include/rvcx.h)."""
+    _fields_ = [("sampling_rate", ctypes.c_int), ("n_fft", ctypes.c_int), ("win_size", ctypes.c_int),
+                ("hop_size", ctypes.c_int), ("num_mels", ctypes.c_int), ("fmin", ctypes.c_float),
+                ("fmax", ctypes.c_float), ("n_layers", ctypes.c_int), ("n_chans", ctypes.c_int),
+                ("out_dims", ctypes.c_int)]
 
 
 class RtDesc(ctypes.Structure):
@@ -161,6 +172,11 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_crepe": (i32, [vp, vp, i64, f32, f32, f32, vp, vp, vp, i64, P(i64), vp]),
         "rvcx_crepe_ex": (i32, [vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp, i64, P(i64), vp]),
         "rvcx_crepe_decode": (i32, [vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp]),
+        "rvcx_set_fcpe_config": (i32, [vp, P(FcpeDesc)]),
+        "rvcx_fcpe": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp, i64, P(i64), vp]),
+        "rvcx_fcpe_decode": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp]),
+        "rvcx_fcpe_mel": (i32, [vp, vp, i64, vp, i64, P(i64), vp]),
+        "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
         "rvcx_split_audio": (i32, [vp, vp, i64, i32, f64, i32, P(i64), i64, P(i64), vp]),
         "rvcx_index_load": (i32, [vp, vp, i64]),
         "rvcx_index_unload": (i32, [vp]),
@@ -216,7 +232,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
 def exported_symbols(path: Optional[str] = None):
     """Names of the C-ABI entry points that resolve in the library (no compute call)."""
     lib = load(path)
-    return [n for n in EXPORTS if hasattr(lib, n)]
+    return [n for n in EXPORTS + TEST_EXPORTS if hasattr(lib, n)]
 
 
 def index_parse(data: bytes) -> dict:

@@ -37,7 +37,8 @@ class Engine:
             raise _lib.RvcxError(rc, f"rvcx_create(device={device}) failed")
         self.ctx = ctx
         self.synth_cfg: Optional[SynthConfig] = None
-        self.loaded = {"synth": False, "hubert": False, "rmvpe": False, "crepe": None}
+        self.loaded = {"synth": False, "hubert": False, "rmvpe": False, "crepe": None, "fcpe": None}
+        self.fcpe_cfg = None
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -175,6 +176,105 @@ class Engine:
                                                float(threshold), {"mlx": 0, "rvc": 1}[semantics], _ptr(d),
                                                f0.data_ptr(), per.data_ptr(), self.stream()), "crepe_decode")
         return f0, per
+
+    def load_fcpe(self, state: Mapping[str, np.ndarray], config: Mapping, key=None):
+        """An FCPE checkpoint's ``model`` state dict and ``config`` (rvc/lib/predictors/FCPE.py:731-756;
+        rvcx.weights.load_fcpe_weights): the sizes go to rvcx_set_fcpe_config, the weights (dense_out's weight-norm
+        fused) to RVCX_MODEL_FCPE. `key` names what was loaded so callers can skip a reload."""
+        from .weights import check_fcpe_state, fcpe_sizes
+
+        st = check_fcpe_state(state, config)
+        z = fcpe_sizes(config)
+        d = _lib.FcpeDesc()
+        d.sampling_rate, d.n_fft, d.win_size, d.hop_size, d.num_mels = z["sampling_rate"], z["n_fft"], z["win_size"], \
+            z["hop_size"], z["num_mels"]
+        d.fmin, d.fmax = float(z["fmin"]), float(z["fmax"])
+        d.n_layers, d.n_chans, d.out_dims = z["n_layers"], z["n_chans"], z["out_dims"]
+        self._check(self.lib.rvcx_set_fcpe_config(self.ctx, ctypes.byref(d)), "set_fcpe_config")
+        self.upload_state(_lib.RVCX_MODEL_FCPE, st)
+        self.fcpe_cfg = z
+        self.loaded["fcpe"] = key if key is not None else True
+
+    _FCPE_DECODERS = {"local_argmax": 0, "argmax": 1}
+
+    def _fcpe_frames(self, n: int) -> int:
+        """Frames FCPEInfer gives for n samples (Wav2Mel.extract_mel, FCPE.py:805-813)."""
+        z = self.fcpe_cfg
+        win, hop = z["win_size"], z["hop_size"]
+        pl = (win - hop) // 2
+        pr = max((win - hop + 1) // 2, win - n - pl)
+        fs = (n + pl + pr - win) // hop + 1
+        nf = n // hop + 1
+        return fs + 1 if nf > fs else nf
+
+    def fcpe(self, audio, threshold: float = 0.006, decoder: str = "local_argmax", interp_uv: bool = False,
+             pad_to=None, want_salience: bool = False, sample_rate=None):
+        """FCPEInfer.__call__ (rvc/lib/predictors/FCPE.py:758-764) on device: audio [N] at the model's sampling rate
+        -> f0 fp64 [N // hop + 1], zeros where the frame maximum <= threshold (and the salience [F, out_dims]).
+        interp_uv: FCPEF0Predictor.post_process follows (:877-902; nearest expansion to pad_to frames, linear
+        interpolation through the unvoiced ones) -> fp64 [pad_to or F]. sample_rate, when given, must be the
+        model's: Wav2Mel's resampling branch (:795-803) is not built."""
+        if self.fcpe_cfg is None:
+            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        if sample_rate is not None and int(sample_rate) != self.fcpe_cfg["sampling_rate"]:
+            raise ValueError(f"fcpe: audio at {sample_rate} Hz, the model's mel runs at "
+                             f"{self.fcpe_cfg['sampling_rate']} Hz (resampling is not supported)")
+        t = self.torch
+        a = self._dev(audio, t.float32).reshape(-1)
+        n = a.numel()
+        F = self._fcpe_frames(n)
+        n_out = int(pad_to) if (interp_uv and pad_to) else F
+        f0 = t.empty((n_out,), dtype=t.float64, device=self.device)
+        sal = t.empty((F, self.fcpe_cfg["out_dims"]), dtype=t.float32, device=self.device) if want_salience else None
+        fo = ctypes.c_int64(0)
+        self._check(self.lib.rvcx_fcpe(self.ctx, a.data_ptr(), n, float(threshold), self._FCPE_DECODERS[decoder],
+                                       1 if interp_uv else 0, int(pad_to or 0), f0.data_ptr(), _ptr(sal), n_out,
+                                       ctypes.byref(fo), self.stream()), "fcpe")
+        assert fo.value == n_out, (fo.value, n_out)
+        return (f0, sal) if want_salience else f0
+
+    def fcpe_decode(self, salience, threshold: float = 0.006, decoder: str = "local_argmax", interp_uv: bool = False,
+                    pad_to=None):
+        """rvcx_fcpe_decode: the cents decoder (+ post_process) alone on salience [F][out_dims] -> f0 fp64."""
+        if self.fcpe_cfg is None:
+            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        t = self.torch
+        p = self._dev(salience, t.float32).reshape(-1, self.fcpe_cfg["out_dims"]).contiguous()
+        F = int(p.shape[0])
+        n_out = int(pad_to) if (interp_uv and pad_to) else F
+        f0 = t.empty((n_out,), dtype=t.float64, device=self.device)
+        self._check(self.lib.rvcx_fcpe_decode(self.ctx, p.data_ptr(), F, float(threshold),
+                                              self._FCPE_DECODERS[decoder], 1 if interp_uv else 0, int(pad_to or 0),
+                                              f0.data_ptr(), self.stream()), "fcpe_decode")
+        return f0
+
+    def fcpe_mel(self, audio):
+        """The FCPE network's input alone (rvcx_fcpe_mel, include/rvcx_test.h): audio [N] -> log-mel [F, num_mels]."""
+        if self.fcpe_cfg is None:
+            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        t = self.torch
+        a = self._dev(audio, t.float32).reshape(-1)
+        F = self._fcpe_frames(a.numel())
+        mel = t.empty((F, self.fcpe_cfg["num_mels"]), dtype=t.float32, device=self.device)
+        fo = ctypes.c_int64(0)
+        self._check(self.lib.rvcx_fcpe_mel(self.ctx, a.data_ptr(), a.numel(), mel.data_ptr(), F, ctypes.byref(fo),
+                                           self.stream()), "fcpe_mel")
+        assert fo.value == F, (fo.value, F)
+        return mel
+
+    def performer_attention(self, q, k, v, proj):
+        """The Performer attention kernels alone (rvcx_performer_attention, include/rvcx_test.h): q, k, v
+        [H][T][64], proj [M][64] -> [H][T][64]."""
+        t = self.torch
+        q, k, v, pm = (self._dev(x, t.float32) for x in (q, k, v, proj))
+        H, T, D = (int(x) for x in q.shape)
+        if D != 64 or k.shape != q.shape or v.shape != q.shape or pm.shape[1] != 64:
+            raise ValueError("performer_attention: q, k, v [H][T][64] and proj [M][64]")
+        out = t.empty_like(q)
+        self._check(self.lib.rvcx_performer_attention(self.ctx, q.data_ptr(), k.data_ptr(), v.data_ptr(), H, T,
+                                                      pm.data_ptr(), int(pm.shape[0]), out.data_ptr(), self.stream()),
+                    "performer_attention")
+        return out
 
     @property
     def upp(self) -> int:

@@ -132,13 +132,37 @@ class CREPE:
 
 class FCPE:
     """rvc_mlx/lib/mlx/fcpe.py FCPE (:50-163): the reference's MLX FCPE is a stub that runs RMVPE with threshold x 5
-    (:129-132); this keeps exactly that behaviour on the device RMVPE."""
+    (:129-132); without weights this keeps exactly that behaviour on the device RMVPE.
 
-    def __init__(self, engine: Engine):
+    With weights -- a checkpoint of rvc/lib/predictors/FCPE.py ({"config", "model"}, FCPEInfer :731-756) as
+    `weights_path`, or its `state` and `config` -- it runs that network on device instead, as rvc/'s FCPE.get_f0 does
+    (rvc/lib/predictors/f0.py:71-89: local_argmax decode, zeros where unvoiced)."""
+
+    def __init__(self, engine: Engine, weights_path=None, state=None, config=None):
         self.engine = engine
+        self.network = weights_path is not None or state is not None
+        if not self.network:
+            return
+        if engine is None:
+            raise TypeError("FCPE needs the rvcx Engine it runs on (engine=...)")
+        if state is not None and config is None:
+            raise TypeError("FCPE(state=...) needs the checkpoint's config too")
+        key = ("fcpe", os.path.abspath(weights_path)) if state is None else ("fcpe", "state", _fingerprint(state),
+                                                                             repr(config))
+        self.key = key  # what engine.loaded["fcpe"] holds while this checkpoint is the loaded one
+        if engine.loaded.get("fcpe") != key:
+            if state is None:
+                from ..weights import load_fcpe_weights
+                if not os.path.exists(weights_path):
+                    raise FileNotFoundError(f"FCPE weights not found. Expected at: {weights_path}")
+                state, config = load_fcpe_weights(weights_path)
+            engine.load_fcpe(state, config, key=key)
 
     def get_f0(self, audio, f0_min: float = 50.0, f0_max: float = 1100.0, threshold: float = 0.006, **kw):
-        return self.engine.host(self.engine.rmvpe(_np(audio).reshape(-1).astype(np.float32), threshold * 5))
+        a = _np(audio).reshape(-1).astype(np.float32)
+        if self.network:
+            return self.engine.host(self.engine.fcpe(a, threshold)).astype(np.float32)
+        return self.engine.host(self.engine.rmvpe(a, threshold * 5))
 
 
 class PitchExtractor:

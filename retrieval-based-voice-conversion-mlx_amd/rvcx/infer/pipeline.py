@@ -21,7 +21,7 @@ from typing import Optional
 
 import numpy as np
 
-from .models import CREPE, HubertModel, RMVPE0Predictor, Synthesizer, _np
+from .models import CREPE, FCPE, HubertModel, RMVPE0Predictor, Synthesizer, _np
 
 
 class Config:
@@ -42,13 +42,16 @@ class PipelineRVCX:
     # "crepe-tiny" run CREPE as each side defines it: semantics="mlx" as rvc_mlx/lib/mlx/crepe.py (reflect padding,
     # biased std, weighted-argmax decode), semantics="rvc" as rvc/lib/predictors/f0.py:31-55 (torchcrepe.predict:
     # zero padding, unbiased std, viterbi decode; its triangular dither of the decoded cents only with
-    # crepe_dither=True in get_f0, as it is random; pipeline() decodes without it). "fcpe" is the MLX stub's RMVPE with threshold 0.006 x 5
-    # (rvc_mlx/lib/mlx/fcpe.py:129-132) and needs semantics="mlx" (rvc/'s torchfcpe model is not available).
+    # crepe_dither=True in get_f0, as it is random; pipeline() decodes without it). "fcpe": with semantics="rvc" the FCPE
+    # network of rvc/lib/predictors/FCPE.py on device, from the checkpoint passed as fcpe_weights (rvc/'s FCPE.get_f0,
+    # rvc/lib/predictors/f0.py:59-89: the raw local_argmax track at fcpe_threshold, zeros where unvoiced; without
+    # fcpe_weights it raises: torchfcpe's bundled model is not readable here); with semantics="mlx" the MLX stub's RMVPE
+    # at threshold 0.006 x 5 (rvc_mlx/lib/mlx/fcpe.py:129-132), whatever weights are given.
     SUPPORTED_F0_METHODS = ("rmvpe", "crepe", "crepe-tiny", "fcpe")
 
     def __init__(self, tgt_sr, config, hubert_model: Optional[HubertModel] = None,
                  rmvpe_model: Optional[RMVPE0Predictor] = None, f0_method: str = "rmvpe", semantics: str = "rvc",
-                 crepe_weights=None, crepe_dither: bool = False):
+                 crepe_weights=None, crepe_dither: bool = False, fcpe_weights=None, fcpe_threshold: float = 0.006):
         if semantics not in ("rvc", "mlx"):
             raise ValueError("semantics must be 'rvc' or 'mlx'")
         self.x_pad, self.x_query, self.x_center, self.x_max = config.x_pad, config.x_query, config.x_center, \
@@ -73,6 +76,9 @@ class PipelineRVCX:
         # {"full": path-or-state, "tiny": ...} (or one path for "full"); None = $RVCX_CREPE_DIR/crepe_{model}.npz
         self.crepe_weights = crepe_weights if isinstance(crepe_weights, dict) or crepe_weights is None \
             else {"full": crepe_weights}
+        # a checkpoint path of rvc/lib/predictors/FCPE.py's format, or its (state, config) pair; None = no FCPE network
+        self.fcpe_weights = fcpe_weights
+        self.fcpe_threshold = float(fcpe_threshold)
         self._check_method(f0_method)
         self._f0_method = f0_method
         self.engine = (hubert_model or rmvpe_model).engine if (hubert_model or rmvpe_model) else None
@@ -82,9 +88,26 @@ class PipelineRVCX:
     def _check_method(self, m):
         if m not in self.SUPPORTED_F0_METHODS:
             raise ValueError(f"f0_method {m!r} is not supported on this path (supported: {self.SUPPORTED_F0_METHODS})")
-        if m == "fcpe" and self.semantics != "mlx":
-            raise ValueError("f0_method 'fcpe' needs torchfcpe's model on the rvc/ path (rvc/lib/predictors/f0.py:60-89); "
-                             "semantics='mlx' runs the MLX port's FCPE (its RMVPE fallback)")
+        if m == "fcpe" and self.semantics != "mlx" and self.fcpe_weights is None:
+            raise ValueError("f0_method 'fcpe' on the rvc/ path (rvc/lib/predictors/f0.py:59-89) runs the FCPE network: "
+                             "pass fcpe_weights= (a checkpoint of rvc/lib/predictors/FCPE.py's {'config', 'model'} "
+                             "format, or its (state, config) pair); semantics='mlx' runs the MLX port's FCPE (its RMVPE "
+                             "fallback)")
+
+    def _fcpe(self, eng):
+        """Load this pipeline's FCPE checkpoint into the engine (once per checkpoint). The handle is kept: while the
+        engine still holds this checkpoint a call costs one comparison, not a hash of the state dict (fcpe_weights
+        is read when it is first used; a state dict mutated in place afterwards is not noticed)."""
+        m = getattr(self, "_fcpe_model", None)
+        if m is not None and m.engine is eng and eng.loaded.get("fcpe") == m.key:
+            return m
+        src = self.fcpe_weights
+        if isinstance(src, (tuple, list)):
+            m = FCPE(eng, state=src[0], config=src[1])
+        else:
+            m = FCPE(eng, weights_path=src)
+        self._fcpe_model = m
+        return m
 
     def _crepe(self, eng, f0_method):
         """Load the CREPE weights f0_method names into the engine (once per model kind)."""
@@ -100,7 +123,10 @@ class PipelineRVCX:
             self._crepe(eng, f0_method)
             return (1 if self.semantics == "mlx" else 2), 0.03
         if f0_method == "fcpe":
-            return 0, 0.006 * 5
+            if self.semantics == "mlx":
+                return 0, 0.006 * 5
+            self._fcpe(eng)  # _check_method has made sure the weights were given
+            return 3, 0.03
         return 0, 0.03
 
     @staticmethod
@@ -150,6 +176,8 @@ class PipelineRVCX:
             if self.crepe_dither:  # torchcrepe.convert.dither: scipy.stats.triang(c=0.5, loc=-20, scale=40)
                 dither = np.random.default_rng().triangular(-20.0, 0.0, 20.0, size=1 + len(xa) // 160)
             f0 = eng.crepe(xa, self.f0_min, self.f0_max, 0.1, semantics="rvc", dither=dither).double()
+        elif method == 3:  # FCPE(...).get_f0(x, p_len, filter_radius=0.006) (rvc/lib/predictors/f0.py:71-89)
+            f0 = eng.fcpe(xa, self.fcpe_threshold)
         else:
             f0 = eng.rmvpe(xa, thr)
         shift = float(pitch)
@@ -207,7 +235,8 @@ class PipelineRVCX:
             f0_autotune_strength=float(f0_autotune_strength),
             proposed_pitch=int(bool(proposed_pitch) and not mlx),
             proposed_pitch_threshold=float(proposed_pitch_threshold), volume_envelope=float(volume_envelope),
-            mlx_semantics=int(mlx), index_rate=rate, f0_method=method, rmvpe_threshold=thr)
+            mlx_semantics=int(mlx), index_rate=rate, f0_method=method, rmvpe_threshold=thr,
+            fcpe_threshold=self.fcpe_threshold)
         y, f0 = eng.pipeline_ex(np.asarray(audio, dtype=np.float64).reshape(-1), opts, eps_z=eps_z,
                                 eps_src=eps_src, seed=seed, want_f0=True)
         self.last_f0 = f0

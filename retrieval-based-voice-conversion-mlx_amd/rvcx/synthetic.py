@@ -363,6 +363,90 @@ def crepe_state(kind: str = "full", seed: int = 11) -> Dict[str, np.ndarray]:
     return st
 
 
+# the legacy FCPE checkpoint's config (rvc/lib/predictors/FCPE.py:731-756 reads these sections; 16 kHz, 1024-point
+# STFT at hop 160, 128 mels over 0-8000 Hz; FCPE.__init__'s f0 range :584-585)
+FCPE_LEGACY_CFG = {
+    "mel": {"sampling_rate": 16000, "n_fft": 1024, "win_size": 1024, "hop_size": 160, "num_mels": 128, "fmin": 0,
+            "fmax": 8000},
+    "model": {"input_channel": 128, "out_dims": 360, "n_layers": 6, "n_chans": 512, "use_siren": False,
+              "use_full": False, "f0_max": 1975.5, "f0_min": 32.70, "confidence": False},
+    "loss": {"loss_mse_scale": 10, "loss_l2_regularization": False, "loss_l2_regularization_scale": 1,
+             "loss_grad1_mse": False, "loss_grad1_mse_scale": 1},
+}
+
+
+def fcpe_config(n_layers: int = 6, n_chans: int = 512) -> dict:
+    """FCPE_LEGACY_CFG with another depth / width."""
+    cfg = {k: dict(v) for k, v in FCPE_LEGACY_CFG.items()}
+    cfg["model"].update(n_layers=int(n_layers), n_chans=int(n_chans))
+    return cfg
+
+
+def fcpe_state(seed: int = 13, n_layers: int = 2, n_chans: int = 512) -> Dict[str, np.ndarray]:
+    """Random-init FCPE weights under the module's state-dict names (FCPE.py:570-647), dense_out as its weight-norm
+    parametrization pair. A default-initialised model gives an almost constant pitch track (three quarters of a
+    log-mel's energy is its time average, and the attention adds another time average), so the weights are shaped
+    until the peak bin moves with the input: stack.0 and the depthwise kernels sum to zero over their taps (temporal
+    high-passes: the time average does not pass), stack.0 weighs the well-conditioned mel bands, to_q / to_k are scaled up (the Performer's exponents spread over
+    tens of units, their maximum staying far below exp's overflow), to_out down, and the head's bias keeps the
+    sigmoid outputs off saturation (frame maxima 0.3 - 0.8 on speech-like audio)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    C, inner, mels, bins = int(n_chans), 8 * 64, 128, 360
+    f32 = np.float32
+
+    def nrm(shape, scale):
+        return (rng.standard_normal(shape) * scale).astype(f32)
+
+    st: Dict[str, np.ndarray] = {}
+    lo, hi = (f32(1200.0) * np.log2(f32(v) / f32(10.0)) for v in (32.70, 1975.5))
+    st["cent_table"] = np.linspace(lo, hi, bins).astype(f32)
+    w0 = nrm((C, mels, 3), 2.0 / np.sqrt(mels * 3))
+    # ... and read the mel bands around 22 (a gaussian window, energy kept): in the bands where a voiced frame sits at
+    # the STFT's rounding floor (below ~100 Hz, above ~1.5 kHz for the speech-like test signal) an fp32 FFT errs by
+    # 1e-3 in the log-mel, which would set the fp32-vs-fp64 gap of the salience instead of the network
+    band = np.exp(-((np.arange(mels) - 22.0) / 7.0) ** 2)
+    band *= np.sqrt(mels / (band ** 2).sum())
+    st["stack.0.weight"] = ((w0 - w0.mean(axis=2, keepdims=True)) * band[None, :, None]).astype(f32)
+    st["stack.0.bias"] = nrm((C,), 0.05)
+    st["stack.1.weight"] = (1.0 + 0.1 * rng.standard_normal(C)).astype(f32)
+    st["stack.1.bias"] = nrm((C,), 0.1)
+    st["stack.3.weight"] = nrm((C, C, 3), 1.0 / np.sqrt(C * 3))
+    st["stack.3.bias"] = nrm((C,), 0.05)
+    for i in range(n_layers):
+        p = f"decoder._layers.{i}."
+        st[p + "conformer.net.0.weight"] = (1.0 + 0.1 * rng.standard_normal(C)).astype(f32)
+        st[p + "conformer.net.0.bias"] = nrm((C,), 0.1)
+        st[p + "conformer.net.2.weight"] = nrm((4 * C, C, 1), 1.5 / np.sqrt(C))
+        st[p + "conformer.net.2.bias"] = nrm((4 * C,), 0.05)
+        dw = nrm((2 * C, 1, 31), 1.5 / np.sqrt(31))
+        st[p + "conformer.net.4.conv.weight"] = (dw - dw.mean(axis=2, keepdims=True)).astype(f32)
+        st[p + "conformer.net.4.conv.bias"] = nrm((2 * C,), 0.05)
+        st[p + "conformer.net.6.weight"] = nrm((C, 2 * C, 1), 1.0 / np.sqrt(2 * C))
+        st[p + "conformer.net.6.bias"] = nrm((C,), 0.05)
+        st[p + "norm.weight"] = (1.0 + 0.1 * rng.standard_normal(C)).astype(f32)
+        st[p + "norm.bias"] = nrm((C,), 0.1)
+        # gaussian_orthogonal_random_matrix (FCPE.py:366-396): orthogonal 64 x 64 blocks, rows scaled to chi(64) norms
+        blocks = []
+        for _ in range(5):
+            qm, _ = np.linalg.qr(rng.standard_normal((64, 64)))
+            blocks.append(qm.T)
+        pm = np.concatenate(blocks)[:266] * np.linalg.norm(rng.standard_normal((266, 64)), axis=1)[:, None]
+        st[p + "attn.fast_attention.projection_matrix"] = pm.astype(f32)
+        for n, sc in (("to_q", 1.6), ("to_k", 1.6), ("to_v", 1.0), ("to_out", 0.5)):
+            o, ii = (C, inner) if n == "to_out" else (inner, C)
+            st[p + f"attn.{n}.weight"] = nrm((o, ii), sc / np.sqrt(ii))
+            st[p + f"attn.{n}.bias"] = nrm((o,), 0.05)
+    st["norm.weight"] = (1.0 + 0.1 * rng.standard_normal(C)).astype(f32)
+    st["norm.bias"] = nrm((C,), 0.1)
+    v = nrm((bins, C), 1.0 / np.sqrt(C))
+    st["dense_out.bias"] = (rng.standard_normal(bins) * 0.06 - 3.0).astype(f32)
+    st["dense_out.parametrizations.weight.original0"] = (
+        np.linalg.norm(v.astype(np.float64), axis=1, keepdims=True) * (1.0 + 0.1 * rng.standard_normal((bins, 1)))
+    ).astype(f32)
+    st["dense_out.parametrizations.weight.original1"] = v
+    return st
+
+
 # --------------------------------------------------------------------------- inputs
 def speech_like(n: int, seed: int = 1, sr: int = 16000) -> np.ndarray:
     """Speech-like 16 kHz signal (SURVEY §8(d) C2 recipe): f0 contour 90-250 Hz with

@@ -257,3 +257,87 @@ def load_crepe_weights(path: str) -> Dict[str, np.ndarray]:
     import torch
 
     return crepe_torch_layout(torch.load(path, map_location="cpu", weights_only=True))
+
+
+# --------------------------------------------------------------------------- FCPE (rvc/lib/predictors/FCPE.py)
+FCPE_HEADS, FCPE_DIM_HEAD, FCPE_CONV_K = 8, 64, 31  # SelfAttention / ConformerConvModule defaults (:466-468, :329)
+
+
+def fcpe_sizes(config: Mapping) -> Dict[str, object]:
+    """The sizes FCPEInfer reads from a checkpoint's ``config`` (FCPE.py:734-756, :767-783), validated: the flat dict
+    rvcx_set_fcpe_config takes. Refuses what FCPE itself refuses (use_siren, use_full, :591-594) and an input width
+    that is not the mel's."""
+    try:
+        mel, model = config["mel"], config["model"]
+        z = {k: int(mel[k]) for k in ("sampling_rate", "n_fft", "win_size", "hop_size", "num_mels")}
+        z.update(fmin=float(mel["fmin"]), fmax=float(mel["fmax"]))
+        z.update({k: int(model[k]) for k in ("n_layers", "n_chans", "out_dims", "input_channel")})
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"FCPE config lacks {e}: expected config['mel'] / config['model'] of an FCPE checkpoint") from e
+    if model.get("use_siren") or model.get("use_full"):
+        raise ValueError("FCPE config: use_siren / use_full models are not supported (FCPE.py:591-594)")
+    if z["input_channel"] != z["num_mels"]:
+        raise ValueError(f"FCPE config: input_channel {z['input_channel']} != num_mels {z['num_mels']}")
+    if z["n_chans"] % 4:
+        raise ValueError(f"FCPE config: n_chans {z['n_chans']} is not divisible by GroupNorm's 4 groups")
+    return z
+
+
+def fcpe_shapes(z: Mapping, n_feat: int) -> Dict[str, tuple]:
+    """Every tensor of the FCPE module's state dict (weight-norm fused) with its shape."""
+    C, inner, m = z["n_chans"], FCPE_HEADS * FCPE_DIM_HEAD, z["num_mels"]
+    sh = {"stack.0.weight": (C, m, 3), "stack.0.bias": (C,), "stack.1.weight": (C,), "stack.1.bias": (C,),
+          "stack.3.weight": (C, C, 3), "stack.3.bias": (C,), "norm.weight": (C,), "norm.bias": (C,),
+          "dense_out.weight": (z["out_dims"], C), "dense_out.bias": (z["out_dims"],), "cent_table": (z["out_dims"],)}
+    for i in range(z["n_layers"]):
+        p = f"decoder._layers.{i}."
+        sh.update({p + "norm.weight": (C,), p + "norm.bias": (C,),
+                   p + "attn.fast_attention.projection_matrix": (n_feat, FCPE_DIM_HEAD),
+                   p + "attn.to_out.weight": (C, inner), p + "attn.to_out.bias": (C,),
+                   p + "conformer.net.0.weight": (C,), p + "conformer.net.0.bias": (C,),
+                   p + "conformer.net.2.weight": (4 * C, C, 1), p + "conformer.net.2.bias": (4 * C,),
+                   p + "conformer.net.4.conv.weight": (2 * C, 1, FCPE_CONV_K),
+                   p + "conformer.net.4.conv.bias": (2 * C,),
+                   p + "conformer.net.6.weight": (C, 2 * C, 1), p + "conformer.net.6.bias": (C,)})
+        for n in ("to_q", "to_k", "to_v"):
+            sh.update({p + f"attn.{n}.weight": (inner, C), p + f"attn.{n}.bias": (inner,)})
+    return sh
+
+
+def check_fcpe_state(state: Mapping[str, object], config: Mapping) -> Dict[str, np.ndarray]:
+    """Fuse dense_out's weight-norm (``weight_g/weight_v`` or ``parametrizations.weight.original0/1``) and check that
+    the state holds exactly the FCPE module's tensors in the config's shapes. Returns float32 arrays."""
+    z = fcpe_sizes(config)
+    st = normalize_state(state)
+    pm = st.get("decoder._layers.0.attn.fast_attention.projection_matrix")
+    if pm is None or pm.ndim != 2:
+        raise ValueError("FCPE state: no decoder._layers.0.attn.fast_attention.projection_matrix "
+                         "(not the state dict of rvc/lib/predictors/FCPE.py's FCPE module)")
+    want = fcpe_shapes(z, int(pm.shape[0]))
+    missing = sorted(set(want) - set(st))
+    extra = sorted(set(st) - set(want))
+    if missing or extra:
+        raise ValueError(f"FCPE state: missing {missing[:4]}{'...' if len(missing) > 4 else ''}, "
+                         f"unexpected {extra[:4]}{'...' if len(extra) > 4 else ''}")
+    bad = [(k, st[k].shape, want[k]) for k in want if tuple(st[k].shape) != tuple(want[k])]
+    if bad:
+        raise ValueError(f"FCPE state: {bad[0][0]} has shape {bad[0][1]}, the config gives {bad[0][2]}")
+    return st
+
+
+def load_fcpe_weights(path: str):
+    """An FCPE checkpoint as FCPEInfer loads it (FCPE.py:731-756): ``{"config": {...}, "model": state_dict}``, read
+    with the non-executing loader. Returns (state, config) for Engine.load_fcpe. torchfcpe's bundled-model format
+    (another container and another network class) is refused."""
+    import torch
+
+    cpt = torch.load(path, map_location="cpu", weights_only=True)
+    if not (isinstance(cpt, dict) and isinstance(cpt.get("config"), dict) and isinstance(cpt.get("model"), dict)):
+        raise ValueError(f"{path}: not an FCPE checkpoint of rvc/lib/predictors/FCPE.py ({{'config', 'model'}}); "
+                         "torchfcpe's bundled format is not supported")
+
+    def plain(d):
+        return {k: plain(v) if isinstance(v, dict) else v for k, v in d.items()}
+
+    config = plain(cpt["config"])
+    return check_fcpe_state(cpt["model"], config), config
