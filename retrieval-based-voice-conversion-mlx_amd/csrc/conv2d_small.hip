@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_conv2d_small(const ConvArgs a, const in
   }
   // ---- epilogue: lane holds rows (pixels) 4*kq + i of fragment p, column (channel) li of fragment t. The uniform
   // switches (alpha, act, residual) are tested once per 4-pixel group around the group-wide operation (per element
-  // they were ~10 scalar branches per output, as in store_tile16)
+  // they were ~10 scalar branches per output, as in conv_common.h's epi_math)
   float* Y = a.y + (long long)b * a.y_bs;
   const float* R = a.res ? a.res + (long long)b * a.res_bs : nullptr;
   const bool res = a.res_mode == RES_ADD_POST;

@@ -1,5 +1,6 @@
 // Shared pieces of the implicit-GEMM conv kernels (conv_gemm.hip: exact fp32 MFMA; conv_emu.hip: fp32 through
-// three bf16 planes): activations, the fused epilogue, and the accumulator -> HBM store of one block tile.
+// three bf16 planes; the streamed kernels): activations, the fused epilogue, the accumulator -> HBM store of one block
+// tile, and what the conv translation units declare to each other.
 #pragma once
 #include "rvcx_kernels.h"
 
@@ -40,63 +41,114 @@ static __device__ __forceinline__ float pre_fn(float v, int act, float slope) {
 }
 static inline int pre_mode(int act) { return act == ACT_NONE ? PA_NONE : (act == ACT_LRELU ? PA_LRELU : PA_ANY); }
 
+// The fused epilogue, defined once for every kernel that takes its switches at run time:
+//   bias -> pre-residual -> alpha -> activation -> post-residual / reverse-subtract -> accumulate (/ div)  [epi_math]
+//   -> noise conv [epi_noise] -> mask [epi_mask] -> store.
+// A caller decides which accumulator element is which output (row, column), gathers the residual / accumulate / mask
+// operands (always before its first store: the stores may alias them, an in-place residual reads the very element it
+// writes, so the compiler cannot hoist the loads itself) and stores. conv_wst16_kernel and the fused ResBlock pair
+// keep epilogues of their own with compile-time switches, in this order of operations.
+
+// the batch entry's (outer b, inner bi) epilogue operands and output
+struct EpiPtrs {
+  const float *bias, *R, *MK;
+  float* Y;
+};
+__device__ __forceinline__ EpiPtrs epi_ptrs(const ConvArgs& a, int b, int bi) {
+  return {a.bias ? a.bias + (long long)b * a.bias_bs + (long long)bi * a.bias_bs2 : nullptr,
+          a.res ? a.res + (long long)b * a.res_bs + (long long)bi * a.res_bs2 : nullptr,
+          a.mask ? a.mask + (long long)b * a.mask_bs : nullptr, a.y + (long long)b * a.y_bs + (long long)bi * a.y_bs2};
+}
+
+// element r of a group's operand: one float for the whole group, or one per element (a vector, an array, a pointer)
+__device__ __forceinline__ float epi_at(float x, int) { return x; }
+template <class T>
+__device__ __forceinline__ float epi_at(const T& x, int r) {
+  return x[r];
+}
+
+// bias .. accumulate on a group of W values v (bn: the bias, rv: the residual, dv: the destination's old value; each
+// a float or indexable by element). The switches are uniform and tested once per group, each around its group-wide
+// operation: tested per element they cost ~25 scalar branches per output, as much as a short tile's MMA loop. Cheap
+// activations inline, the transcendental ones out of line (act_fn).
+template <int W, class V, class BN, class RV, class DV>
+__device__ __forceinline__ void epi_math(const ConvArgs& a, V& v, const BN& bn, const RV& rv, const DV& dv) {
+  const int act = a.act;
+  if (a.bias) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] += epi_at(bn, r);
+  }
+  if (a.res_mode == RES_ADD_PRE) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = v[r] + epi_at(rv, r);
+  }
+  if (a.alpha != 1.f) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] *= a.alpha;
+  }
+  if (act == ACT_LRELU) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
+  } else if (act == ACT_RELU) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
+  } else if (act != ACT_NONE) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = act_fn_slow(v[r], act, a.slope);
+  }
+  if (a.res_mode == RES_ADD_POST) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = v[r] + epi_at(rv, r);
+  } else if (a.res_mode == RES_RSUB_POST) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = epi_at(rv, r) - v[r];
+  }
+  if (a.acc_mode == ACC_ADD) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = epi_at(dv, r) + v[r];
+  } else if (a.acc_mode == ACC_ADD_DIV) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] = (epi_at(dv, r) + v[r]) / a.acc_div;
+  }
+}
+
+// the NSF noise conv's term (ConvArgs::nz_*, one tap: the dispatcher admits nz_kk = 1 only) of output row m, column n
+// of batch entry b: k_noise_add's arithmetic, y + (w x + b) with the product an fma onto 0
+__device__ __forceinline__ float epi_noise(const ConvArgs& a, int b, long long m, int n) {
+  const int p = n / a.nz_C, c = n - p * a.nz_C;
+  const float x = a.nz_har[(long long)b * a.nz_bs + (m * a.nz_u + p) * a.nz_stride];
+  return fmaf(a.nz_w[(long long)c * a.nz_stride], x, 0.f) + a.nz_b[c];
+}
+
+// the output-row mask, after the noise conv
+template <int W, class V, class MV>
+__device__ __forceinline__ void epi_mask(const float* MK, V& v, const MV& mv) {
+  if (MK) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] *= epi_at(mv, r);
+  }
+}
+
+// one output element (m, n), 2-D pixel (oh, ow): the epilogue and the store (the OUT_UPSAMPLE2D scatter included)
 static __device__ __forceinline__ void epilogue_store(const ConvArgs& a, float v, float bn, long long m, int n, int oh,
-                                                      int ow, const float* R, const float* MK, float* Y) {
-  if (a.bias) v += bn;
-  if (a.res_mode == RES_ADD_PRE) v = v + R[m * a.ldr + n];
-  if (a.alpha != 1.f) v *= a.alpha;
-  v = act_fn(v, a.act, a.slope);
-  if (a.res_mode == RES_ADD_POST) v = v + R[m * a.ldr + n];
-  else if (a.res_mode == RES_RSUB_POST) v = R[m * a.ldr + n] - v;
+                                                      int ow, const EpiPtrs& e) {
   float* dst;
   if (a.out_map == OUT_UPSAMPLE2D) {
     const int cv = a.out_cv;
     const int ph = n / (2 * cv), pw = (n / cv) & 1, co = n % cv;
-    dst = Y + ((long long)(2 * oh + ph) * (2 * a.W_out) + (2 * ow + pw)) * a.ldy + co;
+    dst = e.Y + ((long long)(2 * oh + ph) * (2 * a.W_out) + (2 * ow + pw)) * a.ldy + co;
   } else {
-    dst = Y + m * a.ldy + n;
+    dst = e.Y + m * a.ldy + n;
   }
-  if (a.acc_mode == ACC_ADD) v = *dst + v;
-  else if (a.acc_mode == ACC_ADD_DIV) v = (*dst + v) / a.acc_div;
-  if (MK) v *= MK[m];
-  *dst = v;
+  // one element has nothing to gather: the operands go in as pointers, read where a switch asks for them
+  float v1[1] = {v};
+  epi_math<1>(a, v1, bn, e.R + (m * a.ldr + n), dst);
+  epi_mask<1>(e.MK, v1, e.MK + m);
+  *dst = v1[0];
 }
 
 // The 16x16 accumulator tiles of a wave (v_mfma_f32_16x16x32 C layout: lane l holds column l % 16, rows 4 (l / 16) + r)
-// -> HBM or the split-K slab, with the shared epilogue (epilogue_store's order of operations, bit-identical). The
-// epilogue switches are uniform and tested once per 4-element group, each around its group-wide operation: tested
-// per element (as epilogue_store does) they cost ~25 scalar branches per output, as much as a short tile's MMA loop.
-// + the NSF noise conv (ConvArgs::nz_*) of output column n, rows mb .. mb + 3 (those with ok[r]): KK = nz_kk at
-// compile time. k_noise_add's order: an fma chain over q from 0, + bias, + v
-template <int KK>
-__device__ __forceinline__ void noise_rows(const ConvArgs& a, int b, long long mb, int n, const bool (&ok)[4],
-                                           f32x4& v) {
-  const int stride = a.nz_stride, C = a.nz_C;
-  const int p = n / C, c = n - p * C;
-  const float* hb = a.nz_har + (long long)b * a.nz_bs;
-  float wq[KK];
-  {
-    int tap = 0, j = 0;
-#pragma unroll
-    for (int q = 0; q < KK; ++q) {
-      wq[q] = a.nz_w[((long long)tap * C + c) * stride + j];
-      if (++j == stride) {
-        j = 0;
-        ++tap;
-      }
-    }
-  }
-  const float nb = a.nz_b[c];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float* x = hb + ((ok[r] ? mb + r : 0) * a.nz_u + p) * stride;
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < KK; ++q) acc = fmaf(wq[q], x[q], acc);
-    v[r] = v[r] + (acc + nb);
-  }
-}
-
+// -> HBM or the split-K slab, with the shared epilogue on the 4 rows of a column.
 // UP2D: the instantiation may see the ConvTranspose2d phase layout (OUT_UPSAMPLE2D: the 2-D gather-streamed kernel
 // only; compiled out elsewhere)
 template <int TM16, int TN16, int WM, int WN, bool UP2D = false>
@@ -119,18 +171,17 @@ __device__ __forceinline__ void store_tile16(const ConvArgs& a, int m0, int n0, 
     }
     return;
   }
-  const float* bias = a.bias ? a.bias + (long long)b * a.bias_bs : nullptr;
-  const float* R = a.res ? a.res + (long long)b * a.res_bs : nullptr;
-  const float* MK = a.mask ? a.mask + (long long)b * a.mask_bs : nullptr;
-  float* Y = a.y + (long long)b * a.y_bs;
+  const EpiPtrs e = epi_ptrs(a, b, 0);
+  const float* R = e.R;
+  const float* MK = e.MK;
+  float* Y = e.Y;
   const bool need_r = R && a.res_mode != RES_NONE;
   const bool need_d = a.acc_mode != ACC_STORE;
-  const int act = a.act;
 #pragma unroll
   for (int tn = 0; tn < TN16; ++tn) {
     const int n = n0 + wn * TN16 * 16 + tn * 16 + lc;
     const bool n_ok = n < a.N;
-    const float bn = (bias && n_ok) ? bias[n] : 0.f;
+    const float bn = (e.bias && n_ok) ? e.bias[n] : 0.f;
 #pragma unroll
     for (int tm = 0; tm < TM16; ++tm) {
       const long long mb = (long long)m0 + wm * TM16 * 16 + tm * 16 + 4 * lg;
@@ -139,7 +190,6 @@ __device__ __forceinline__ void store_tile16(const ConvArgs& a, int m0, int n0, 
       for (int r = 0; r < 4; ++r) ok[r] = n_ok && mb + r < Mtot;
       f32x4 v = acc[tm][tn];
       f32x4 rv = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f}, mv = {1.f, 1.f, 1.f, 1.f};
-      // gather first (residual / accumulate / mask operands), then the arithmetic, then the stores
       if (need_r) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) rv[r] = ok[r] ? R[(mb + r) * a.ldr + n] : 0.f;
@@ -152,51 +202,12 @@ __device__ __forceinline__ void store_tile16(const ConvArgs& a, int m0, int n0, 
 #pragma unroll
         for (int r = 0; r < 4; ++r) mv[r] = ok[r] ? MK[mb + r] : 1.f;
       }
-      if (bias) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += bn;
-      }
-      if (a.res_mode == RES_ADD_PRE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] + rv[r];
-      }
-      if (a.alpha != 1.f) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= a.alpha;
-      }
-      if (act == ACT_LRELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-      } else if (act == ACT_RELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
-      } else if (act != ACT_NONE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = act_fn_slow(v[r], act, a.slope);
-      }
-      if (a.res_mode == RES_ADD_POST) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] + rv[r];
-      } else if (a.res_mode == RES_RSUB_POST) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rv[r] - v[r];
-      }
-      if (a.acc_mode == ACC_ADD) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = dv[r] + v[r];
-      } else if (a.acc_mode == ACC_ADD_DIV) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = (dv[r] + v[r]) / a.acc_div;
-      }
+      epi_math<4>(a, v, bn, rv, dv);
       if (a.nz_har && n_ok) {
-        // the NSF noise conv of these 4 outputs (ConvArgs::nz_*): k_noise_add's arithmetic, y + (sum + b); one
-        // tap (the last stage's stride-1 noise conv: the dispatcher admits nz_kk = 1 only)
-        noise_rows<1>(a, b, mb, n, ok, v);
-      }
-      if (MK) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= mv[r];
+        for (int r = 0; r < 4; ++r) v[r] = v[r] + epi_noise(a, b, ok[r] ? mb + r : 0, n);
       }
+      epi_mask<4>(MK, v, mv);
       if (UP2D && a.out_map == OUT_UPSAMPLE2D) {
         // the 2x2-phase ConvTranspose2d (epilogue_store's mapping): virtual column n = (ph, pw, co) of input pixel m
         const int cv = a.out_cv;
@@ -220,8 +231,7 @@ __device__ __forceinline__ void store_tile16(const ConvArgs& a, int m0, int n0, 
 // store_tile16 for the transposed accumulator layout D = W X^T (conv_wsb.hip): lane (lc, lg) of a 16x16 tile holds
 // row lc, columns 4 lg + r, so the residual / accumulate operands and the outputs move as one 16-byte vector per lane
 // and tile where the rows are 16-byte aligned (vec: N, the row strides and the bases multiples of 4 floats) -- a
-// quarter of store_tile16's memory instructions, whose issue rate, not HBM, bounded the epilogue. Same per-element
-// order of operations (bit-identical results); 1-D OUT_ROWS only.
+// quarter of store_tile16's memory instructions, whose issue rate, not HBM, bounded the epilogue. 1-D OUT_ROWS only.
 template <int TM16, int TN16, int WM, int WN>
 __device__ __forceinline__ void store_tile16t(const ConvArgs& a, int m0, int n0, int b, int zsplit, int ksplit,
                                               long long Mtot, f32x4 (&acc)[TM16][TN16]) {
@@ -250,22 +260,21 @@ __device__ __forceinline__ void store_tile16t(const ConvArgs& a, int m0, int n0,
     }
     return;
   }
-  const float* bias = a.bias ? a.bias + (long long)b * a.bias_bs : nullptr;
-  const float* R = a.res ? a.res + (long long)b * a.res_bs : nullptr;
-  const float* MK = a.mask ? a.mask + (long long)b * a.mask_bs : nullptr;
-  float* Y = a.y + (long long)b * a.y_bs;
+  const EpiPtrs e = epi_ptrs(a, b, 0);
+  const float* R = e.R;
+  const float* MK = e.MK;
+  float* Y = e.Y;
   const bool need_r = R && a.res_mode != RES_NONE;
   const bool need_d = a.acc_mode != ACC_STORE;
-  const int act = a.act;
   const bool vec = nvec && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0) && (a.ldy & 3) == 0 &&
                    (!need_r || (((reinterpret_cast<uintptr_t>(R) & 15) == 0) && (a.ldr & 3) == 0));
 #pragma unroll
   for (int tn = 0; tn < TN16; ++tn) {
     const int n = n0 + wn * TN16 * 16 + tn * 16 + 4 * lg;
     f32x4 bn = {0.f, 0.f, 0.f, 0.f};
-    if (bias) {
+    if (e.bias) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) bn[r] = n + r < a.N ? bias[n + r] : 0.f;
+      for (int r = 0; r < 4; ++r) bn[r] = n + r < a.N ? e.bias[n + r] : 0.f;
     }
 #pragma unroll
     for (int tm = 0; tm < TM16; ++tm) {
@@ -278,7 +287,6 @@ __device__ __forceinline__ void store_tile16t(const ConvArgs& a, int m0, int n0,
       f32x4 v = acc[tm][tn];
       f32x4 rv = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f};
       float mv = 1.f;
-      // gather first (residual / accumulate / mask operands), then the arithmetic, then the stores
       if (need_r) {
         const float* src = R + m * a.ldr + n;
         if (vec && full) {
@@ -298,58 +306,13 @@ __device__ __forceinline__ void store_tile16t(const ConvArgs& a, int m0, int n0,
         }
       }
       if (MK) mv = m_ok ? MK[m] : 1.f;
-      if (bias) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += bn[r];
-      }
-      if (a.res_mode == RES_ADD_PRE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] + rv[r];
-      }
-      if (a.alpha != 1.f) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= a.alpha;
-      }
-      if (act == ACT_LRELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-      } else if (act == ACT_RELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
-      } else if (act != ACT_NONE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = act_fn_slow(v[r], act, a.slope);
-      }
-      if (a.res_mode == RES_ADD_POST) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] + rv[r];
-      } else if (a.res_mode == RES_RSUB_POST) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rv[r] - v[r];
-      }
-      if (a.acc_mode == ACC_ADD) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = dv[r] + v[r];
-      } else if (a.acc_mode == ACC_ADD_DIV) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = (dv[r] + v[r]) / a.acc_div;
-      }
+      epi_math<4>(a, v, bn, rv, dv);
       if (a.nz_har) {
-        // the NSF noise conv of these 4 outputs, one tap (the dispatcher admits nz_kk = 1 only): k_noise_add's
-        // arithmetic, y + (w x + b)
-        const float* hb = a.nz_har + (long long)b * a.nz_bs;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (!ok[r]) continue;
-          const int p = (n + r) / a.nz_C, c = n + r - p * a.nz_C;
-          const float x = hb[(m * a.nz_u + p) * a.nz_stride];
-          v[r] = v[r] + (fmaf(a.nz_w[(long long)c * a.nz_stride], x, 0.f) + a.nz_b[c]);
-        }
+        for (int r = 0; r < 4; ++r)
+          if (ok[r]) v[r] = v[r] + epi_noise(a, b, m, n + r);
       }
-      if (MK) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= mv;
-      }
+      epi_mask<4>(MK, v, mv);
       float* dst = Y + m * a.ldy + n;
       if (vec && full) {
         *reinterpret_cast<f32x4*>(dst) = v;
@@ -378,10 +341,9 @@ __device__ __forceinline__ void conv_store_tile(const ConvArgs& a, const TilePos
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int li = lane & 31, hk = lane >> 5;
-  const float* bias = a.bias ? a.bias + (long long)p.b * a.bias_bs + (long long)p.bi * a.bias_bs2 : nullptr;
-  const float* R = a.res ? a.res + (long long)p.b * a.res_bs + (long long)p.bi * a.res_bs2 : nullptr;
-  const float* MK = a.mask ? a.mask + (long long)p.b * a.mask_bs : nullptr;
-  float* Y = a.y + (long long)p.b * a.y_bs + (long long)p.bi * a.y_bs2;
+  const EpiPtrs e = epi_ptrs(a, p.b, p.bi);
+  const float *bias = e.bias, *R = e.R, *MK = e.MK;
+  float* Y = e.Y;
   auto emit = [&](float v, int ml, int n, bool n_ok, float bn) {
     long long m;
     int oh = 0, ow = 0;
@@ -399,7 +361,7 @@ __device__ __forceinline__ void conv_store_tile(const ConvArgs& a, const TilePos
       if (p.ksplit > 1) {
         a.ws[(((long long)p.zb * p.ksplit + p.zsplit) * a.ws_rows + m) * a.N + n] = v;
       } else {
-        epilogue_store(a, v, bn, m, n, oh, ow, R, MK, Y);
+        epilogue_store(a, v, bn, m, n, oh, ow, e);
       }
     }
   };
@@ -440,50 +402,11 @@ __device__ __forceinline__ void conv_store_tile(const ConvArgs& a, const TilePos
             dv[i] = (ok && need_d) ? Yl[ro * a.ldy] : 0.f;
             mv[i] = (ok && MK) ? Ml[ro] : 1.f;
           }
-          // the uniform switches once per 8-element half, each around its half-wide operation (store_tile16)
           float v[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = acc[tm][tn][8 * h + i];
-          if (a.bias) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] += bn;
-          }
-          if (a.res_mode == RES_ADD_PRE) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = v[i] + rv[i];
-          }
-          if (a.alpha != 1.f) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] *= a.alpha;
-          }
-          if (a.act == ACT_LRELU) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = v[i] > 0.f ? v[i] : v[i] * a.slope;
-          } else if (a.act == ACT_RELU) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
-          } else if (a.act != ACT_NONE) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = act_fn_slow(v[i], a.act, a.slope);
-          }
-          if (a.res_mode == RES_ADD_POST) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = v[i] + rv[i];
-          } else if (a.res_mode == RES_RSUB_POST) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = rv[i] - v[i];
-          }
-          if (a.acc_mode == ACC_ADD) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = dv[i] + v[i];
-          } else if (a.acc_mode == ACC_ADD_DIV) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = (dv[i] + v[i]) / a.acc_div;
-          }
-          if (MK) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] *= mv[i];
-          }
+          epi_math<8>(a, v, bn, rv, dv);
+          epi_mask<8>(MK, v, mv);
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const int r = 8 * h + i;
@@ -551,10 +474,19 @@ __device__ __forceinline__ void conv_block_coords(int ntn, int& bx, int& by, int
   }
 }
 
-// conv_emu.hip: fp32 convolution on bf16 MFMA through a 3-way operand split (defined there)
-// cfg: 10.. (cfg_tile_emu); returns hipErrorInvalidValue when the tile's LDS does not fit
-hipError_t conv_emu_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit, int ntn_enable,
-                           hipStream_t s);
+// One tile configuration of the LDS-staged kernels: conv_gemm.hip (native fp32 MFMA, cfg 0..9) and conv_emu.hip (fp32
+// through a 3-way bf16 operand split, cfg 10..16). pipe: the double-buffered GEMM form; a split launch (ksplit > 1)
+// writes the slab and leaves the combine to the caller. hipErrorInvalidValue: the tile's LDS does not fit, or the
+// tile has no such form
+hipError_t conv_gemm_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit, hipStream_t s);
+hipError_t conv_emu_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit, hipStream_t s);
 bool conv_emu_tile(int cfg, int& BM, int& BN);
+// conv_tiny.hip: the one-thread-per-output kernels, the shapes they take and their launches
+bool tiny_fits(const ConvArgs& a);
+bool rows1x1_fits(const ConvArgs& a, bool two_d);
+hipError_t launch_tiny(const ConvArgs& a, bool two_d, hipStream_t s);
+hipError_t launch_rows1x1(const ConvArgs& a, bool two_d, hipStream_t s);
+// conv_splitk.hip: the combine of a split launch (slab sum + the shared epilogue, the LayerNorm or the gate)
+hipError_t launch_splitk_reduce(const ConvArgs& a, int ksplit, bool two_d, hipStream_t s);
 
 }  // namespace rvcx

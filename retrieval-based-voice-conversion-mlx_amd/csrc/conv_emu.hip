@@ -456,7 +456,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_emu_kernel(const ConvArg
 }
 
 template <int BM, int BN, int WM, int WN, bool TWO_D, bool PIPE>
-hipError_t launch_emu(const ConvArgs& a, int ksplit, int ntn_enable, hipStream_t s) {
+hipError_t launch_emu(const ConvArgs& a, int ksplit, hipStream_t s) {
   int nrows_a, rw = 0, rh = 0, tiles_w = 1, mtiles;
   if (!TWO_D) {
     nrows_a = (BM - 1) * a.stride + (a.taps - 1) * a.dil + 1;
@@ -479,8 +479,8 @@ hipError_t launch_emu(const ConvArgs& a, int ksplit, int ntn_enable, hipStream_t
                     ((a.w_bs2 & 3) == 0) && ((a.w_ts & 3) == 0);
   if (a.batch_inner < 1) return hipErrorInvalidValue;
   const int ntiles = (a.N + BN - 1) / BN;
-  const int ntn = ntn_enable ? ntiles : 0;
-  dim3 grid(ntn ? mtiles * ntiles : mtiles, ntn ? 1 : ntiles, a.batch * a.batch_inner * ksplit);
+  const int ntn = ntiles;  // XCD-contiguous tile runs (conv_block_coords)
+  dim3 grid(mtiles * ntiles, 1, a.batch * a.batch_inner * ksplit);
   auto kern = conv_emu_kernel<BM, BN, WM, WN, TWO_D, PIPE>;
   static size_t smem_set = 64 * 1024;  // per instantiation: raise the dynamic-LDS limit once
   if (smem > smem_set) {
@@ -505,35 +505,35 @@ bool conv_emu_tile(int cfg, int& BM, int& BN) {
   return true;
 }
 
-hipError_t conv_emu_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit, int ntn_enable,
+hipError_t conv_emu_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit,
                            hipStream_t s) {
   if (two_d) {
     switch (cfg) {
-      case 10: return launch_emu<128, 64, 2, 2, true, false>(a, ksplit, ntn_enable, s);
-      case 12: return launch_emu<128, 32, 4, 1, true, false>(a, ksplit, ntn_enable, s);
-      case 13: return launch_emu<64, 64, 2, 2, true, false>(a, ksplit, ntn_enable, s);
-      case 14: return launch_emu<128, 128, 2, 2, true, false>(a, ksplit, ntn_enable, s);
+      case 10: return launch_emu<128, 64, 2, 2, true, false>(a, ksplit, s);
+      case 12: return launch_emu<128, 32, 4, 1, true, false>(a, ksplit, s);
+      case 13: return launch_emu<64, 64, 2, 2, true, false>(a, ksplit, s);
+      case 14: return launch_emu<128, 128, 2, 2, true, false>(a, ksplit, s);
       default: return hipErrorInvalidValue;
     }
   }
   if (pipe) {
     switch (cfg) {
-      case 10: return launch_emu<128, 64, 2, 2, false, true>(a, ksplit, ntn_enable, s);
-      case 12: return launch_emu<128, 32, 4, 1, false, true>(a, ksplit, ntn_enable, s);
-      case 13: return launch_emu<64, 64, 2, 2, false, true>(a, ksplit, ntn_enable, s);
-      case 14: return launch_emu<128, 128, 2, 2, false, true>(a, ksplit, ntn_enable, s);
-      case 15: return launch_emu<64, 128, 2, 2, false, true>(a, ksplit, ntn_enable, s);
+      case 10: return launch_emu<128, 64, 2, 2, false, true>(a, ksplit, s);
+      case 12: return launch_emu<128, 32, 4, 1, false, true>(a, ksplit, s);
+      case 13: return launch_emu<64, 64, 2, 2, false, true>(a, ksplit, s);
+      case 14: return launch_emu<128, 128, 2, 2, false, true>(a, ksplit, s);
+      case 15: return launch_emu<64, 128, 2, 2, false, true>(a, ksplit, s);
       default: return hipErrorInvalidValue;
     }
   }
   switch (cfg) {
-    case 10: return launch_emu<128, 64, 2, 2, false, false>(a, ksplit, ntn_enable, s);
-    case 11: return launch_emu<256, 32, 4, 1, false, false>(a, ksplit, ntn_enable, s);
-    case 12: return launch_emu<128, 32, 4, 1, false, false>(a, ksplit, ntn_enable, s);
-    case 13: return launch_emu<64, 64, 2, 2, false, false>(a, ksplit, ntn_enable, s);
-    case 14: return launch_emu<128, 128, 2, 2, false, false>(a, ksplit, ntn_enable, s);
-    case 15: return launch_emu<64, 128, 2, 2, false, false>(a, ksplit, ntn_enable, s);
-    case 16: return launch_emu<256, 64, 4, 1, false, false>(a, ksplit, ntn_enable, s);
+    case 10: return launch_emu<128, 64, 2, 2, false, false>(a, ksplit, s);
+    case 11: return launch_emu<256, 32, 4, 1, false, false>(a, ksplit, s);
+    case 12: return launch_emu<128, 32, 4, 1, false, false>(a, ksplit, s);
+    case 13: return launch_emu<64, 64, 2, 2, false, false>(a, ksplit, s);
+    case 14: return launch_emu<128, 128, 2, 2, false, false>(a, ksplit, s);
+    case 15: return launch_emu<64, 128, 2, 2, false, false>(a, ksplit, s);
+    case 16: return launch_emu<256, 64, 4, 1, false, false>(a, ksplit, s);
     default: return hipErrorInvalidValue;
   }
 }

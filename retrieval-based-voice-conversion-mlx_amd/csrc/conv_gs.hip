@@ -307,13 +307,13 @@ void launch_gs_mode(const ConvArgs& a, dim3 grid, size_t smem, int ntn, int kspl
 }
 
 template <int BM, int BN, int WM, int WN, bool TWO_D>
-hipError_t launch_gs(const ConvArgs& a, int ntn_enable, int ksplit, hipStream_t s) {
+hipError_t launch_gs(const ConvArgs& a, int ksplit, hipStream_t s) {
   const long long Mtot = TWO_D ? (long long)a.T_out * a.W_out : a.T_out;
   const long long mtiles = (Mtot + BM - 1) / BM;
   if (mtiles > INT32_MAX / 64 || a.wsplit_npad % BN != 0 || ksplit < 1 || (ksplit > 1 && !a.ws)) return hipErrorInvalidValue;
   const int ntiles = (a.N + BN - 1) / BN;
-  const int ntn = ntn_enable ? ntiles : 0;
-  dim3 grid((unsigned)(ntn ? mtiles * ntiles : mtiles), ntn ? 1 : ntiles, a.batch * ksplit);
+  const int ntn = ntiles;  // XCD-contiguous tile runs (conv_block_coords)
+  dim3 grid((unsigned)(mtiles * ntiles), 1, a.batch * ksplit);
   const bool h16 = a.wsplit_fmt == WSPLIT_H16;
   // the throttle pad (ConvArgs::lds_pad) is clamped to the CU's 160 KB: above 80 KB it means one workgroup per CU
   const size_t smem = std::min((size_t)2 * BM * (h16 ? ERS_H : ERS) + (size_t)std::max(0, a.lds_pad),
@@ -529,13 +529,13 @@ void launch_gsw_mode(const ConvArgs& a, dim3 grid, size_t smem, int ntn, int ksp
                      static_cast<const char*>(a.wsplit), a.wsplit_npad, ntn, ksplit, mfast);
 }
 
-hipError_t launch_gsw(const ConvArgs& a, int ntn_enable, int ksplit, hipStream_t s) {
+hipError_t launch_gsw(const ConvArgs& a, int ksplit, hipStream_t s) {
   const int W = a.W_out, rh = 64 / W;
   const long long mtiles = (a.T_out + rh - 1) / rh;
   if (a.wsplit_npad % 64 != 0 || ksplit < 1 || (ksplit > 1 && !a.ws) || mtiles > INT32_MAX / 64) return hipErrorInvalidValue;
   const int ntiles = (a.N + 63) / 64;
-  const int ntn = ntn_enable ? ntiles : 0;
-  dim3 grid((unsigned)(ntn ? mtiles * ntiles : mtiles), ntn ? 1 : ntiles, a.batch * ksplit);
+  const int ntn = ntiles;  // XCD-contiguous tile runs (conv_block_coords)
+  dim3 grid((unsigned)(mtiles * ntiles), 1, a.batch * ksplit);
   const bool h16 = a.wsplit_fmt == WSPLIT_H16;
   const size_t smem = (size_t)(rh + 2) * (W + 2) * (h16 ? ERS_H : ERS);
   const double wbytes = 6.0 * a.N * a.C_in * 9, abytes = 4.0 * (double)a.T_out * W * a.C_in * a.batch;
@@ -584,12 +584,12 @@ bool conv_gsw_eligible(const ConvArgs& a) {
          a.T_in == a.T_out && a.W_in == a.W_out && a.W_out <= GSW_MAXW && GSW_MAXW % a.W_out == 0 && a.W_out >= 4;
 }
 
-hipError_t conv_gs_launch(const ConvArgs& a, int cfg, int ntn_enable, hipStream_t s, bool two_d, int ksplit) {
+hipError_t conv_gs_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d, int ksplit) {
   if (!a.wsplit || !conv_gs_eligible(a, two_d) || a.lowp) return hipErrorInvalidValue;
   if (cfg != 30) return hipErrorInvalidValue;
-  if (two_d && conv_gsw_eligible(a)) return launch_gsw(a, ntn_enable, ksplit, s);
-  return two_d ? launch_gs<64, 64, 2, 2, true>(a, ntn_enable, ksplit, s)
-               : launch_gs<64, 64, 2, 2, false>(a, ntn_enable, ksplit, s);
+  if (two_d && conv_gsw_eligible(a)) return launch_gsw(a, ksplit, s);
+  return two_d ? launch_gs<64, 64, 2, 2, true>(a, ksplit, s)
+               : launch_gs<64, 64, 2, 2, false>(a, ksplit, s);
 }
 
 }  // namespace rvcx

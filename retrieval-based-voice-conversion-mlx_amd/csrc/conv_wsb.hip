@@ -307,7 +307,7 @@ __global__ __launch_bounds__(CONV_THREADS, (BM / WM) * (BN / WN) > 64 * 32 ? 2 :
 }
 
 template <int BM, int BN, int WM, int WN>
-hipError_t launch_wsb16(const ConvArgs& a, int ntn_enable, int ksplit, hipStream_t s) {
+hipError_t launch_wsb16(const ConvArgs& a, int ksplit, hipStream_t s) {
   const int nrows_a = BM + (a.taps - 1) * a.dil;
   const int mtiles = (a.T_out + BM - 1) / BM;
   const bool h16 = a.wsplit_fmt == WSPLIT_H16;
@@ -315,8 +315,8 @@ hipError_t launch_wsb16(const ConvArgs& a, int ntn_enable, int ksplit, hipStream
   if (a.wsplit_npad % BN != 0 || ksplit < 1 || (ksplit > 1 && !a.ws)) return hipErrorInvalidValue;
   if (a.lowp && !h16) return hipErrorInvalidValue;  // the reduced-precision mode reads the fp16 image's hi plane
   const int ntiles = (a.N + BN - 1) / BN;
-  const int ntn = ntn_enable ? ntiles : 0;
-  dim3 grid(ntn ? mtiles * ntiles : mtiles, ntn ? 1 : ntiles, a.batch * ksplit);
+  const int ntn = ntiles;  // XCD-contiguous tile runs (conv_block_coords)
+  dim3 grid(mtiles * ntiles, 1, a.batch * ksplit);
   // the reduced-precision opt-in only without a pre-mask (the generator's convs)
   const int mode = pre_mode(a.pre_act) | (a.pre_mask ? 4 : 0) | (h16 ? 16 : 0) | (h16 && a.lowp && !a.pre_mask ? 8 : 0);
   void (*kern)(const ConvArgs, const char*, int, int, int, int);
@@ -396,13 +396,13 @@ bool conv_wsb_tile(int cfg, int& BM, int& BN) {
   }
 }
 
-hipError_t conv_wsb_launch(const ConvArgs& a, int cfg, int ntn_enable, hipStream_t s, bool two_d, int ksplit) {
+hipError_t conv_wsb_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d, int ksplit) {
   if (!a.wsplit || !conv_wsb_eligible(a, two_d)) return hipErrorInvalidValue;
   switch (cfg) {
-    case 23: return launch_wsb16<128, 64, 2, 2>(a, ntn_enable, ksplit, s);
-    case 24: return launch_wsb16<256, 32, 4, 1>(a, ntn_enable, ksplit, s);
-    case 25: return launch_wsb16<128, 128, 2, 2>(a, ntn_enable, ksplit, s);
-    case 27: return launch_wsb16<128, 64, 1, 4>(a, ntn_enable, ksplit, s);
+    case 23: return launch_wsb16<128, 64, 2, 2>(a, ksplit, s);
+    case 24: return launch_wsb16<256, 32, 4, 1>(a, ksplit, s);
+    case 25: return launch_wsb16<128, 128, 2, 2>(a, ksplit, s);
+    case 27: return launch_wsb16<128, 64, 1, 4>(a, ksplit, s);
     default: return hipErrorInvalidValue;
   }
 }

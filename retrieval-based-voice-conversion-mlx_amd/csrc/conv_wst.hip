@@ -17,8 +17,8 @@
 //
 // Arithmetic: exactly conv_wsb16_kernel's (split_bf16.h put_h16x4 activations at 2^-4, the per-column-scaled
 // k_wsplit_h16 image, three v_mfma_f32_16x16x32_f16 products per (chunk, tap) step in the same order, acc + 2^-11 acc2
-// times the column's inverse scale, then store_tile16's epilogue order), with the MFMA operands swapped (D = W X^T, so
-// a lane's accumulators are four channels of one time row): the two kernels are bit-identical
+// times the column's inverse scale, then the shared epilogue's order, conv_common.h), with the MFMA operands swapped
+// (D = W X^T, so a lane's accumulators are four channels of one time row): the two kernels are bit-identical
 // (tests/test_gpu_conv_wst.py compares them element for element). Measured against the weight-streamed tile it
 // replaces (profiles/r06t_ab_wst.txt): bench_conv C128 k3 198 -> 262 TF, the up3 phase group 151 -> 224, C2 -0.2 ms.
 // What bounds it (r06v/w variants): the MFMA loop alone runs 43 us of the 70 us C128 k3 launch and the loads, split
@@ -193,8 +193,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_wst16_kernel(const ConvArgs a
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  // store_tile16's order of operations, per element: (acc + 2^-11 acc2) * inv, + bias, act, + residual, accumulate,
-  // + the fused noise conv (one tap: k_noise_add's y + (w x + b))
+  // the shared epilogue's order of operations (conv_common.h: epi_math, epi_noise), per element: (acc + 2^-11 acc2)
+  // * inv, + bias, act, + residual, accumulate, + the fused noise conv (one tap: k_noise_add's y + (w x + b))
   auto epilogue = [&](const Cur& c) __attribute__((always_inline)) {
     const int b = c.b;
     float* Yn = a.y + (long long)b * a.y_bs + n0;

@@ -184,7 +184,7 @@ hipError_t gate_tanh_sigmoid(const float* xin, int ldx, const float* g, long lon
 // (the NSF noise conv, hifigan_nsf.py:196-199, in its framed form); C % 4 == 0, taps*stride <= 16
 // weight-streamed split conv (conv_wsb.hip): eligibility (1-D, stride 1, C_in % 32 == 0, halo <= 64 rows, no
 // split-K), the pre-split weight image and its launch; conv_wsb_wants = eligible + split arithmetic + a grid
-// large enough to fill the chip (conv_gemm.hip policy)
+// large enough to fill the chip (conv_dispatch.hip policy)
 bool conv_wsb_eligible(const ConvArgs& a, bool two_d = false);
 bool conv_wsb_wants(const ConvArgs& a);
 // route a contraction with a static weight to the weight-streamed kernel (the big 1-D grids, conv_wsb_wants) or the
@@ -199,11 +199,11 @@ int conv_wsb_pick(const ConvArgs& a);  // the weight-streamed tile cfg the size 
 bool conv_gs_eligible(const ConvArgs& a, bool two_d);
 bool conv_gsw_eligible(const ConvArgs& a);  // the windowed 2-D form (split-K slices of whole 32-channel chunks)
 bool conv_gs_tile(int cfg, int& BM, int& BN);
-hipError_t conv_gs_launch(const ConvArgs& a, int cfg, int ntn_enable, hipStream_t s, bool two_d, int ksplit);
+hipError_t conv_gs_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d, int ksplit);
 int conv_wsplit_npad(int N);
 long long conv_wsplit_bytes(const ConvArgs& a);
 hipError_t conv_wsplit_build(const ConvArgs& a, void* out, hipStream_t s);
-hipError_t conv_wsb_launch(const ConvArgs& a, int cfg, int ntn_enable, hipStream_t s, bool two_d = false,
+hipError_t conv_wsb_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d = false,
                            int ksplit = 1);
 // weight-stationary form of the fp16-split conv (conv_wst.hip) for the short 64 / 128-channel convs (k = 3 ResBlock
 // convs, ConvTranspose phases): 1-D, C_in = N in {64, 128}, 2-3 taps, halo <= 16, no or leaky-ReLU pre-activation,
