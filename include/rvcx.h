@@ -155,6 +155,14 @@ int rvcx_set_fcpe_config(rvcx_ctx* ctx, const rvcx_fcpe_desc* desc);
  * d_salience (optional) fp32 [F][out_dims]. cap_frames >= the frames written, *frames_out = their count. */
 int rvcx_fcpe(rvcx_ctx* ctx, const float* d_audio, int64_t n, float threshold, int decoder_mode, int interp_uv,
               int64_t pad_to, double* d_f0, float* d_salience, int64_t cap_frames, int64_t* frames_out, void* stream);
+/* rvcx_fcpe's raw track for B streams of n samples each in one batched forward (one set of launches per layer for
+ * all streams, not a loop): row b at d_audio + b * ld (ld >= n). Per row the semantics of rvcx_fcpe with interp_uv = 0:
+ * F = n / hop + 1 frames, f0 = 0 where the frame maximum <= threshold. Everything the network pads or reduces over
+ * time (the mel's reflect / zero padding and repeated last frame, the convs' zero padding, the GroupNorm statistics,
+ * the attention's sums) is each stream's own. d_f0: fp64 [B][F]; d_salience (optional) fp32 [B][F][out_dims]. The
+ * interp_uv / pad_to tail stays with rvcx_fcpe. */
+int rvcx_fcpe_b(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld, int B, float threshold, int decoder_mode,
+                double* d_f0, float* d_salience, void* stream);
 /* The decode alone (the tail of rvcx_fcpe after the network: FCPE.py:683-714, :877-902) on caller-given salience
  * d_salience [F][out_dims], with the loaded model's cent table and hop / sampling rate. d_f0 fp64 [pad_to when
  * interp_uv and pad_to > 0, else F]. */
@@ -397,6 +405,9 @@ typedef struct {
   double cross_fade_overlap_size; /* seconds (default 0.1) */
   double extra_convert_size;      /* seconds (default 0.5) */
   double silent_threshold;        /* dB; hops with RMS below 10^(dB/20) output silence (core.py:58-59, :268-289) */
+  int f0_method;                  /* VoiceChanger's f0_method (pipeline.py:140-155): 0 "rmvpe" (a zero-initialised desc),
+                                   * 1 "fcpe": one batched FCPE forward per hop, the raw local_argmax track */
+  float fcpe_threshold;           /* f0_method 1: FCPE's voicing threshold; <= 0: 0.006 (pipeline.py:155) */
 } rvcx_rt_desc;
 
 typedef struct {                  /* per-hop options of VoiceChanger.on_request (core.py:453-484) */
@@ -417,7 +428,9 @@ typedef struct {                  /* per-hop options of VoiceChanger.on_request 
 
 int rvcx_rt_default_desc(rvcx_rt_desc* desc);
 int rvcx_rt_default_opts(rvcx_rt_opts* opts);
-/* Needs the synthesizer, HuBERT and RMVPE finalized. State lives in HBM, zero-initialised. */
+/* Needs the synthesizer and HuBERT finalized and, for a pitch-guided synthesizer, the f0 method's model: RMVPE
+ * (f0_method 0) or RVCX_MODEL_FCPE at 16 kHz / hop_size 160 (f0_method 1; RVCX_E_STATE / RVCX_E_SHAPE otherwise). Any
+ * other f0_method: RVCX_E_INVALID. State lives in HBM, zero-initialised. */
 int rvcx_rt_create(rvcx_ctx* ctx, const rvcx_rt_desc* desc, rvcx_rt** out);
 int rvcx_rt_destroy(rvcx_ctx* ctx, rvcx_rt* rt);
 /* geometry[12] = {n_streams, block48, block16, convert16, frames (p_len), skip_head, return_length,

@@ -19,6 +19,11 @@ extern "C" {
 int rvcx_performer_attention(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int H, int T,
                              const float* d_P, int M, float* d_out, void* stream);
 
+/* The same for B streams of one T in one set of launches: d_q, d_k, d_v, d_out [B][H][T][64]; every reduction over
+ * time (ksum, ctx, the row maximum, the denominator) is per (stream, head). */
+int rvcx_performer_attention_b(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int H,
+                               int T, const float* d_P, int M, float* d_out, void* stream);
+
 /* The FCPE network's input alone, as rvcx_fcpe forms it (rvc/lib/predictors/FCPE.py: Wav2Mel.extract_mel :790-813 over
  * STFT.get_mel :102-168): d_audio [n] fp32 at the loaded model's sampling rate -> d_mel [F][num_mels], the log-mel of
  * every band, F = n / hop + 1 frames (*frames_out; cap_frames >= F). Needs RVCX_MODEL_FCPE finalized. */

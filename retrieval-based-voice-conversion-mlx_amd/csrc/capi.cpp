@@ -505,6 +505,18 @@ int rvcx_fcpe(rvcx_ctx* ctx, const float* d_audio, int64_t n, float threshold, i
   });
 }
 
+int rvcx_fcpe_b(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld, int B, float threshold, int decoder_mode,
+                double* d_f0, float* d_salience, void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+    if (!d_audio || !d_f0 || n <= 0 || B < 1 || ld < n || decoder_mode < 0 || decoder_mode > 1)
+      throw Error(RVCX_E_INVALID, "rvcx_fcpe_b: bad arguments");
+    set_device(ctx);
+    fcpe_forward_b(*ctx, d_audio, n, ld, B, threshold, decoder_mode, d_f0, fcpe_frames(*ctx, n), d_salience,
+                   static_cast<hipStream_t>(stream));
+  });
+}
+
 int rvcx_fcpe_decode(rvcx_ctx* ctx, const float* d_salience, int64_t F, float threshold, int decoder_mode,
                      int interp_uv, int64_t pad_to, double* d_f0, void* stream) {
   return guard(ctx, [&] {
@@ -524,7 +536,7 @@ int rvcx_fcpe_mel(rvcx_ctx* ctx, const float* d_audio, int64_t n, float* d_mel, 
     if (!d_audio || !d_mel || n <= 0) throw Error(RVCX_E_INVALID, "rvcx_fcpe_mel: bad arguments");
     if (cap_frames < fcpe_frames(*ctx, n)) throw Error(RVCX_E_CAPACITY, "rvcx_fcpe_mel: output capacity too small");
     set_device(ctx);
-    const int F = fcpe_mel(*ctx, d_audio, n, d_mel, static_cast<hipStream_t>(stream));
+    const int F = fcpe_mel(*ctx, d_audio, n, n, 1, d_mel, static_cast<hipStream_t>(stream));
     if (frames_out) *frames_out = F;
   });
 }
@@ -540,6 +552,23 @@ int rvcx_performer_attention(rvcx_ctx* ctx, const float* d_q, const float* d_k, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* ws = ctx->buf<float>("perf.test.ws", (size_t)performer_ws_floats(H, T, M), s);
     check(performer_attention(d_q, d_k, d_v, (long long)T * 64, 64, H, T, d_P, M, ws, d_out, (long long)T * 64, 64, s),
+          "performer_attention");
+  });
+}
+
+int rvcx_performer_attention_b(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int H, int T,
+                               const float* d_P, int M, float* d_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_q || !d_k || !d_v || !d_P || !d_out || B <= 0 || H <= 0 || T <= 0 || M <= 0)
+      throw Error(RVCX_E_INVALID, "rvcx_performer_attention_b: bad argument");
+    if (M > PERFORMER_MAX_FEATURES || B > 4096 || (long long)B * H * T * 64 > INT32_MAX)
+      throw Error(RVCX_E_SHAPE, "rvcx_performer_attention_b: at most 512 features and 2^31 elements per operand");
+    set_device(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* ws = ctx->buf<float>("perf.test.ws", (size_t)performer_ws_floats(H, T, M, B), s);
+    const long long bs = (long long)H * T * 64;
+    check(performer_attention(d_q, d_k, d_v, (long long)T * 64, 64, H, T, d_P, M, ws, d_out, (long long)T * 64, 64, s, B,
+                              bs, bs),
           "performer_attention");
   });
 }
@@ -1367,6 +1396,8 @@ int rvcx_rt_default_desc(rvcx_rt_desc* d) {
   d->cross_fade_overlap_size = 0.1;
   d->extra_convert_size = 0.5;
   d->silent_threshold = -90.0;
+  d->f0_method = 0;
+  d->fcpe_threshold = 0.006f;  // rvc/realtime/pipeline.py:155
   return RVCX_OK;
 }
 

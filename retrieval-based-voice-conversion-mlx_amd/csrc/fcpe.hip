@@ -1,7 +1,9 @@
 // Non-GEMM kernels of the FCPE pitch network (rvc/lib/predictors/FCPE.py): the STFT magnitude of its mel, the input
 // stack's GroupNorm + LeakyReLU, the Conformer module's GLU + depthwise conv + Swish, the cents decoders and
 // FCPEF0Predictor.post_process. The Performer attention is performer_attn.hip; the convs and linears run on the
-// implicit-GEMM family.
+// implicit-GEMM family. The kernels that pad or reduce over time (GroupNorm, the depthwise conv, the mel's padding
+// and repeated last frame) take B streams of one length per launch, grid z (or y) = stream, each stream on its own
+// rows; the row-wise ones (magnitude, decoders) run on the B F rows of all streams.
 #include <algorithm>
 #include <cmath>
 
@@ -36,14 +38,33 @@ __global__ void k_fcpe_mag(const float* spec, int F, int nb, float* mag, int ldm
   }
 }
 
+// y[b][i] = x[b ldx + i - pad_l] for pad_l <= i < pad_l + n, else 0, i < ldy: the zero padding STFT.get_mel falls back
+// to when the reflection does not fit (FCPE.py:138), per stream
+__global__ void k_fcpe_zero_pad(const float* x, int n, int pad_l, long long ldx, float* y, long long ldy) {
+  x += blockIdx.y * ldx;
+  y += blockIdx.y * ldy;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < ldy; i += (long long)gridDim.x * blockDim.x)
+    y[i] = (i >= pad_l && i < (long long)pad_l + n) ? x[i - pad_l] : 0.f;
+}
+
+// mel [B][F][C]: row F - 1 of every stream = a copy of its own row F - 2 (Wav2Mel.extract_mel's appended frame,
+// FCPE.py:808-812)
+__global__ void k_fcpe_dup_last(float* mel, int F, int C) {
+  float* m = mel + (long long)blockIdx.x * F * C;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) m[(long long)(F - 1) * C + c] = m[(long long)(F - 2) * C + c];
+}
+
 // GroupNorm(G, C) over time-major x [T][C] in place, then LeakyReLU(slope) (FCPE.py:626-630: the statistics of a
 // group run over its C / G channels x T frames). Two launches: k_gn_stats sums each of GN_TCHUNKS time chunks of a
 // group in fp64 (a fixed tree over the workgroup) into ws [G][GN_TCHUNKS][2]; k_gn_apply adds the chunks in chunk
-// order (every thread the same sequence: no atomics, run-to-run bit identical) and normalises.
+// order (every thread the same sequence: no atomics, run-to-run bit identical) and normalises. grid z = stream: B
+// sequences of T rows back to back, the statistics per (stream, group), ws [B][G][GN_TCHUNKS][2].
 constexpr int GN_TCHUNKS = FCPE_GN_CHUNKS;
 __global__ __launch_bounds__(256) void k_gn_stats(const float* x, int T, int C, int G, double* ws) {
   __shared__ double s1[256], s2[256];
   const int g = blockIdx.y, cg = C / G, c0 = g * cg;
+  x += (long long)blockIdx.z * T * C;
+  ws += (long long)blockIdx.z * G * GN_TCHUNKS * 2;
   const int per = (T + GN_TCHUNKS - 1) / GN_TCHUNKS;
   const int t_lo = min(T, (int)blockIdx.x * per), t_hi = min(T, t_lo + per);
   const long long n = (long long)(t_hi - t_lo) * cg;
@@ -72,6 +93,8 @@ __global__ __launch_bounds__(256) void k_gn_apply(float* x, int T, int C, int G,
                                                   const float* beta, float eps, float slope) {
   const int g = blockIdx.y, cg = C / G, c0 = g * cg;
   const long long n = (long long)T * cg;
+  x += (long long)blockIdx.z * T * C;
+  ws += (long long)blockIdx.z * G * GN_TCHUNKS * 2;
   double a = 0.0, b = 0.0;
   for (int k = 0; k < GN_TCHUNKS; ++k) {
     a += ws[((long long)g * GN_TCHUNKS + k) * 2];
@@ -91,7 +114,8 @@ __global__ __launch_bounds__(256) void k_gn_apply(float* x, int T, int C, int G,
 // ConformerConvModule's middle (FCPE.py:339-344) as one kernel over the 1x1 conv's output x [T][2 C2]:
 //   g[t][c] = x[t][c] sigmoid(x[t][C2 + c])                         GLU (formed while the tile is loaded)
 //   y[t][c] = swish(b[c] + sum_k w[k][c] g[t + k - pad][c])         depthwise conv, zero padding, Swish
-// One workgroup per (64 channels, 32 output frames): the GLU'd rows t0 - pad .. t0 + 31 + K - 1 - pad sit in LDS.
+// One workgroup per (64 channels, 32 output frames, stream): the GLU'd rows t0 - pad .. t0 + 31 + K - 1 - pad sit in
+// LDS. grid z = stream (B sequences of T rows back to back): the zero padding is each stream's own, t outside [0, T).
 constexpr int DW_T = 32, DW_MAXK = 64;
 __global__ __launch_bounds__(256) void k_glu_dw_swish(const float* x, int T, int C2, const float* w, const float* b,
                                                        int K, int pad, float* y) {
@@ -100,6 +124,8 @@ __global__ __launch_bounds__(256) void k_glu_dw_swish(const float* x, int T, int
   const int c = blockIdx.x * 64 + cl;
   const int t0 = blockIdx.y * DW_T;
   const int rows = DW_T + K - 1;
+  x += (long long)blockIdx.z * T * 2 * C2;
+  y += (long long)blockIdx.z * T * C2;
   for (int i = tg; i < rows; i += 4) {
     const int t = t0 - pad + i;
     float v = 0.f;
@@ -243,20 +269,34 @@ hipError_t fcpe_magnitude(const float* spec, int F, int nbins, float* mag, int l
   return hipGetLastError();
 }
 
+hipError_t fcpe_zero_pad(const float* x, int n, int pad_l, long long ldx, float* y, long long ldy, int B,
+                         hipStream_t s) {
+  if (n < 1 || pad_l < 0 || ldy < (long long)pad_l + n || B < 1 || B > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_zero_pad, dim3(std::min(nblocks(ldy), 2048u), B), dim3(TB), 0, s, x, n, pad_l, ldx, y, ldy);
+  return hipGetLastError();
+}
+
+hipError_t fcpe_dup_last_frame(float* mel, int B, int F, int C, hipStream_t s) {
+  if (B < 1 || F < 2 || C < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_dup_last, dim3(B), dim3(TB), 0, s, mel, F, C);
+  return hipGetLastError();
+}
+
 hipError_t groupnorm_lrelu(float* x, int T, int C, int G, const float* gamma, const float* beta, float eps, float slope,
-                           double* ws, hipStream_t s) {
-  if (T < 1 || G < 1 || C % G || !ws) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_gn_stats, dim3(GN_TCHUNKS, G), dim3(256), 0, s, x, T, C, G, ws);
+                           double* ws, hipStream_t s, int B) {
+  if (T < 1 || G < 1 || C % G || !ws || B < 1 || B > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_gn_stats, dim3(GN_TCHUNKS, G, B), dim3(256), 0, s, x, T, C, G, ws);
   const long long n = (long long)T * (C / G);
-  hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), G), dim3(256), 0, s, x, T,
+  hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), G, B), dim3(256), 0, s, x, T,
                      C, G, ws, gamma, beta, eps, slope);
   return hipGetLastError();
 }
 
 hipError_t glu_dwconv_swish(const float* x, int T, int C2, const float* w, const float* b, int K, int pad, float* y,
-                            hipStream_t s) {
-  if (T < 1 || C2 % 64 || K < 1 || K > DW_MAXK || pad < 0 || pad >= K) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_glu_dw_swish, dim3(C2 / 64, (T + DW_T - 1) / DW_T), dim3(256), 0, s, x, T, C2, w, b, K, pad, y);
+                            hipStream_t s, int B) {
+  if (T < 1 || C2 % 64 || K < 1 || K > DW_MAXK || pad < 0 || pad >= K || B < 1 || B > 65535)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_glu_dw_swish, dim3(C2 / 64, (T + DW_T - 1) / DW_T, B), dim3(256), 0, s, x, T, C2, w, b, K, pad, y);
   return hipGetLastError();
 }
 

@@ -9,7 +9,7 @@
 //
 // Two passes, both on v_mfma_f32_16x16x4_f32 (an exact fp32 fma chain; the network is a few GFLOP per utterance,
 // far below what the split-bf16 planes would buy), no LDS, no barriers, no atomics:
-//   pass A (k_perf_kv)   one workgroup per (time slab of 128 rows, head); wave w owns the feature tiles w, w + 4, ...
+//   pass A (k_perf_kv)   one workgroup per (time slab of 128 rows, head, stream); wave w owns the feature tiles w, w + 4, ...
 //                        For a 16-row time tile it forms dash [t][j] (D layout: row t = 4 kq + r, column j = li),
 //                        turns it into k' in registers and feeds it straight back as the B operand of
 //                        ctx^T [d][j] += v^T [d][t] k' [t][j] (the k slot kq of step r is t = 4 kq + r). The slab's
@@ -24,6 +24,9 @@
 // exponential (exp(0) + eps is not zero), so they add exactly nothing to ksum, ctx, the denominator or the output.
 // Time rows t >= T get k' = 0 (pass A) and are not stored (pass B); their loads are clamped to row T - 1, so every
 // operand is finite.
+// Batch: B streams of one T per launch (grid z). Everything reduced over time -- ksum, ctx, the query's row maximum,
+// the denominator -- belongs to one (stream, head): the workspace holds ctx / ksum and the slabs' images per
+// (stream, head), and no load is clamped or reduced across a stream's rows. B = 1 is the single-utterance form.
 #include <cmath>
 
 #include "rvcx_kernels.h"
@@ -43,8 +46,8 @@ constexpr int PB_MAXJT = PERFORMER_MAX_FEATURES / 16;
 struct PerfArgs {
   const float* q;
   const float* k;
-  const float* v;  // element (h, t, d) at p + h hs + t ld + d
-  long long hs;
+  const float* v;  // element (b, h, t, d) at p + b bs + h hs + t ld + d
+  long long bs, hs;
   int ld;
   const float* P;  // [M][64]
   int M, T, H;
@@ -74,11 +77,11 @@ __device__ __forceinline__ float load_rows(const float* X, int ld, int t0, int T
 }
 
 __global__ __launch_bounds__(256) void k_perf_kv(PerfArgs a, float* part_ctx, float* part_ks) {
-  const int slab = blockIdx.x, h = blockIdx.y;
+  const int slab = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, kq = lane >> 4;
   const int njt = (a.M + 15) / 16;
-  const float* K = a.k + h * a.hs;
-  const float* V = a.v + h * a.hs;
+  const float* K = a.k + b * a.bs + h * a.hs;
+  const float* V = a.v + b * a.bs + h * a.hs;
   const int t_begin = slab * PA_SLAB, t_end = min(a.T, t_begin + PA_SLAB);
   f32x4 acc[PA_MAXJT][4];  // ctx^T tile (jj, dt): row d = 16 dt + 4 kq + r, column j = 16 (wave + 4 jj) + li
   float ks[PA_MAXJT];
@@ -127,8 +130,9 @@ __global__ __launch_bounds__(256) void k_perf_kv(PerfArgs a, float* part_ctx, fl
       }
     }
   }
-  float* pc = part_ctx + ((long long)slab * a.H + h) * a.M * PD;
-  float* pk = part_ks + ((long long)slab * a.H + h) * a.M;
+  const long long img = ((long long)slab * gridDim.z + b) * a.H + h;  // image (slab, stream, head)
+  float* pc = part_ctx + img * a.M * PD;
+  float* pk = part_ks + img * a.M;
 #pragma unroll
   for (int jj = 0; jj < PA_MAXJT; ++jj) {
     const int jt = wave + PA_WAVES * jj;
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(256) void k_perf_kv(PerfArgs a, float* part_ctx, fl
   }
 }
 
-// ctx / ksum = the slabs' partial images added in slab order
+// ctx / ksum = the slabs' partial images added in slab order (n_ctx / n_ks: the elements of all streams and heads)
 __global__ void k_perf_combine(const float* part_ctx, const float* part_ks, int nslab, long long n_ctx, long long n_ks,
                                float* ctx, float* ksum) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -161,14 +165,14 @@ __global__ void k_perf_combine(const float* part_ctx, const float* part_ks, int 
 }
 
 __global__ __launch_bounds__(256) void k_perf_out(PerfArgs a, const float* ctx, const float* ksum, float* out,
-                                                   long long out_hs, int out_ld) {
-  const int h = blockIdx.y;
+                                                   long long out_bs, long long out_hs, int out_ld) {
+  const int h = blockIdx.y, b = blockIdx.z;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, kq = lane >> 4;
   const int t0 = (blockIdx.x * 4 + wave) * 16;
   if (t0 >= a.T) return;
   const int njt = (a.M + 15) / 16;
   f32x4 xb[4];
-  const float diag = load_rows(a.q + h * a.hs, a.ld, t0, a.T, li, kq, a.c, a.c2, xb);  // row t0 + li
+  const float diag = load_rows(a.q + b * a.bs + h * a.hs, a.ld, t0, a.T, li, kq, a.c, a.c2, xb);  // row t0 + li
   f32x4 dsh[PB_MAXJT];  // dash^T tile jt: row j = 16 jt + 4 kq + r, column t = t0 + li
   float mx = -INFINITY;
 #pragma unroll
@@ -190,8 +194,8 @@ __global__ __launch_bounds__(256) void k_perf_out(PerfArgs a, const float* ctx, 
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float* C = ctx + (long long)h * a.M * PD;
-  const float* KS = ksum + (long long)h * a.M;
+  const float* C = ctx + ((long long)b * a.H + h) * a.M * PD;
+  const float* KS = ksum + ((long long)b * a.H + h) * a.M;
   float den = 0.f;
   f32x4 o[4];  // out^T tile dt: row d = 16 dt + 4 kq + r, column t = t0 + li
 #pragma unroll
@@ -213,7 +217,7 @@ __global__ __launch_bounds__(256) void k_perf_out(PerfArgs a, const float* ctx, 
   }
   const float dinv = 1.f / (xor_sum16(den) + 1e-8f);
   if (t0 + li < a.T) {
-    float* y = out + h * out_hs + (long long)(t0 + li) * out_ld + 4 * kq;
+    float* y = out + b * out_bs + h * out_hs + (long long)(t0 + li) * out_ld + 4 * kq;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(y + 16 * dt) = o[dt] * dinv;
   }
@@ -223,16 +227,17 @@ __global__ __launch_bounds__(256) void k_perf_out(PerfArgs a, const float* ctx, 
 
 int performer_slabs(int T) { return (T + PA_SLAB - 1) / PA_SLAB; }
 
-long long performer_ws_floats(int H, int T, int M) {
+long long performer_ws_floats(int H, int T, int M, int B) {
   const int ns = performer_slabs(T);
-  const long long one = (long long)H * M * (PD + 1);
+  const long long one = (long long)B * H * M * (PD + 1);
   return one + (ns > 1 ? ns * one : 0);
 }
 
 hipError_t performer_attention(const float* q, const float* k, const float* v, long long hs, int ld, int H, int T,
                                const float* P, int M, float* ws, float* out, long long out_hs, int out_ld,
-                               hipStream_t s) {
-  if (H < 1 || T < 1 || M < 1 || M > PERFORMER_MAX_FEATURES || (ld & 3) || (hs & 3) || (out_ld & 3) || (out_hs & 3))
+                               hipStream_t s, int B, long long bs, long long out_bs) {
+  if (H < 1 || T < 1 || M < 1 || M > PERFORMER_MAX_FEATURES || (ld & 3) || (hs & 3) || (out_ld & 3) || (out_hs & 3) ||
+      B < 1 || B > 65535 || (bs & 3) || (out_bs & 3))
     return hipErrorInvalidValue;
   for (const void* p : {(const void*)q, (const void*)k, (const void*)v, (const void*)P, (const void*)ws,
                         (const void*)out})
@@ -241,6 +246,7 @@ hipError_t performer_attention(const float* q, const float* k, const float* v, l
   a.q = q;
   a.k = k;
   a.v = v;
+  a.bs = bs;
   a.hs = hs;
   a.ld = ld;
   a.P = P;
@@ -251,17 +257,17 @@ hipError_t performer_attention(const float* q, const float* k, const float* v, l
   a.c2 = a.c * a.c;
   a.ratio = (float)(1.0 / std::sqrt((double)M));  // M^-0.5 (FCPE.py:188)
   const int ns = performer_slabs(T);
-  const long long n_ctx = (long long)H * M * PD, n_ks = (long long)H * M;
+  const long long n_ctx = (long long)B * H * M * PD, n_ks = (long long)B * H * M;
   // ws: ctx | the slabs' ctx images | ksum | the slabs' ksum images (the ctx images first: they take 16-byte stores)
   float* ctx = ws;
   float* part_ctx = ns > 1 ? ctx + n_ctx : ctx;  // one slab: pass A writes the final images
   float* ksum = ctx + (ns > 1 ? 1 + ns : 1) * n_ctx;
   float* part_ks = ns > 1 ? ksum + n_ks : ksum;
-  hipLaunchKernelGGL(k_perf_kv, dim3(ns, H), dim3(256), 0, s, a, part_ctx, part_ks);
+  hipLaunchKernelGGL(k_perf_kv, dim3(ns, H, B), dim3(256), 0, s, a, part_ctx, part_ks);
   if (ns > 1)
     hipLaunchKernelGGL(k_perf_combine, dim3((unsigned)((n_ctx + n_ks + 255) / 256)), dim3(256), 0, s, part_ctx,
                        part_ks, ns, n_ctx, n_ks, ctx, ksum);
-  hipLaunchKernelGGL(k_perf_out, dim3((T + 63) / 64, H), dim3(256), 0, s, a, ctx, ksum, out, out_hs, out_ld);
+  hipLaunchKernelGGL(k_perf_out, dim3((T + 63) / 64, H, B), dim3(256), 0, s, a, ctx, ksum, out, out_bs, out_hs, out_ld);
   return hipGetLastError();
 }
 

@@ -301,7 +301,13 @@ void finalize_fcpe(Ctx& c);
 // (F = n / hop + 1, or pad_to when interp_uv and pad_to > 0); cap = the capacity of f0 in frames.
 int64_t fcpe_frames(const Ctx& c, int64_t n);
 // the network's input alone: Wav2Mel.extract_mel (FCPE.py:790-813) -> mel [fcpe_frames(n)][n_mels]; returns the frames
-int fcpe_mel(Ctx& c, const float* audio, int64_t n, float* mel, hipStream_t s);
+// (B streams of n samples, row b at audio + b ld -> mel [B][frames][n_mels], each stream framed on its own)
+int fcpe_mel(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float* mel, hipStream_t s);
+// FCPEInfer.__call__ for B streams of n samples in one set of launches (row b at audio + b ld): the raw track f0
+// [B][F] fp64 (zeros where unvoiced; cap = the frames per stream f0 holds), salience [B][F][out_dims] optional.
+// Returns F = fcpe_frames(n). fcpe_forward is its B = 1 case plus the interp_uv / pad_to tail.
+int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float thr, int mode, double* f0,
+                       int64_t cap, float* sal_out, hipStream_t s);
 int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
                      double* f0, float* sal_out, int64_t cap, hipStream_t s);
 // the decoders + post_process alone on salience [F][out_dims]

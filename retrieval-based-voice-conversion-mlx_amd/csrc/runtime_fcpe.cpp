@@ -7,6 +7,9 @@
 //   convs    stack.0 / stack.3 (k 3) and every Linear / 1x1 conv on the implicit-GEMM family (launch_conv)
 //   attn     to_q | to_k | to_v as one GEMM into [F][3 x 512], then performer_attn.hip on the 8 heads in place
 //   conformer LN -> 1x1 (C -> 4C) -> GLU + depthwise k 31 + Swish (one kernel, fcpe.hip) -> 1x1 (2C -> C)
+//   batch    fcpe_forward_b runs B streams of one length in one set of launches per layer (a realtime hop's f0 with
+//            rvcx_rt_desc::f0_method 1, rvcx_fcpe_b): activations [B][F][C], row-wise ops on the B F rows, everything
+//            padded or reduced over time per stream. fcpe_forward is its B = 1 case plus the interp_uv / pad_to tail
 #include <cmath>
 
 #include "runtime.h"
@@ -201,94 +204,117 @@ int64_t fcpe_decode_run(Ctx& c, const float* sal, int64_t F, float thr, int mode
   return n;
 }
 
-// Wav2Mel.extract_mel (FCPE.py:790-813; STFT.get_mel :133-168) on audio [n]: the log-mel [F][n_mels] into `mel`
-// (F = fcpe_frames(n) rows). Returns F.
-int fcpe_mel(Ctx& c, const float* audio, int64_t n, float* mel, hipStream_t s) {
+// Wav2Mel.extract_mel (FCPE.py:790-813; STFT.get_mel :133-168) on B streams of n samples (row b at audio + b ld): the
+// log-mel [B][F][n_mels] into `mel` (F = fcpe_frames(n) rows per stream). Every stream is padded, framed and, when the
+// STFT gives one frame fewer than F, extended by a copy of its own last frame: the STFT conv runs in launch_conv's
+// batch form over the streams' own padded rows, so no frame reads across a stream boundary. Returns F.
+int fcpe_mel(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float* mel, hipStream_t s) {
   if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
   const FcpeCfg& g = c.fcfg;
   if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
+  if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
   const int nbin = g.n_fft / 2 + 1, ldm = nbin_padded(g.n_fft);
   const int64_t pl = (g.win - g.hop) / 2, pr = std::max<int64_t>((g.win - g.hop + 1) / 2, g.win - n - pl);
   const int64_t np = n + pl + pr, rows = (np + 31) / 32;
   const int Fs = (int)((np - g.win) / g.hop + 1);
   const int F = (int)fcpe_frames(c, n), Fm = std::min(Fs, F);
-  float* xp = c.buf<float>("fc.xp", (size_t)rows * 32, s);
+  if ((int64_t)B * F > INT32_MAX / std::max(4 * g.n_chans, 2 * nbin)) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  float* xp = c.buf<float>("fc.xp", (size_t)B * rows * 32, s);
   if (pr < n) {
-    check(reflect_pad_1d(audio, (int)n, (int)pl, (int)pr, xp, s, 1, n, rows * 32), "fcpe_pad");
+    check(reflect_pad_1d(audio, (int)n, (int)pl, (int)pr, xp, s, B, ld, rows * 32), "fcpe_pad");
   } else {  // torch pads with zeros when the reflection would not fit (:138)
-    RVCX_HIP(hipMemsetAsync(xp, 0, (size_t)rows * 32 * sizeof(float), s));
-    RVCX_HIP(hipMemcpyAsync(xp + pl, audio, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    check(fcpe_zero_pad(audio, (int)n, (int)pl, ld, xp, rows * 32, B, s), "fcpe_pad");
   }
-  float* spec = c.buf<float>("fc.spec", (size_t)Fm * 2 * nbin, s);
+  float* spec = c.buf<float>("fc.spec", (size_t)B * Fm * 2 * nbin, s);
   {
     ConvArgs a = lin(xp, 32, (int)rows, 32, c.W("fc.stft"), 2 * nbin, nullptr, spec, 2 * nbin);
     a.taps = g.win / 32;
     a.stride = g.hop / 32;
     a.w_ts = (long long)2 * nbin * 32;
     a.T_out = Fm;
+    a.batch = B;
+    a.x_bs = rows * 32;
+    a.y_bs = (long long)Fm * 2 * nbin;
     launch_conv(c, a, false, s, 0.0);
   }
-  float* mag = c.buf<float>("fc.mag", (size_t)Fm * ldm, s);
-  check(fcpe_magnitude(spec, Fm, nbin, mag, ldm, s), "fcpe_magnitude");
+  float* mag = c.buf<float>("fc.mag", (size_t)B * Fm * ldm, s);
+  check(fcpe_magnitude(spec, B * Fm, nbin, mag, ldm, s), "fcpe_magnitude");
   {
     ConvArgs a = lin(mag, ldm, Fm, ldm, c.W("fc.mel"), g.n_mels, nullptr, mel, g.n_mels);
     a.act = ACT_LOGCLAMP;
     a.slope = 1e-5f;
+    a.batch = B;  // Fm rows of each stream into its F rows of mel
+    a.x_bs = (long long)Fm * ldm;
+    a.y_bs = (long long)F * g.n_mels;
     launch_conv(c, a, false, s);
   }
-  if (F > Fm)
-    RVCX_HIP(hipMemcpyAsync(mel + (size_t)Fm * g.n_mels, mel + (size_t)(Fm - 1) * g.n_mels, g.n_mels * sizeof(float),
-                            hipMemcpyDeviceToDevice, s));
+  if (F > Fm) check(fcpe_dup_last_frame(mel, B, F, g.n_mels, s), "fcpe_dup_last_frame");
   return F;
 }
 
-int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
-                     double* f0, float* sal_out, int64_t cap, hipStream_t s) {
+// FCPEInfer.__call__ on B streams of n samples (row b at audio + b ld): f0 [B][F] (the raw track: zeros where
+// unvoiced), salience [B][F][out_dims] optional. Activations are [B][F][C] with the streams back to back, so
+// LayerNorm and every linear run once on the B F rows; what the network reduces or pads over time -- the mel's
+// framing, the k = 3 convs' zero padding (launch_conv's batch form), the GroupNorm statistics, the Performer's ctx /
+// ksum / row maximum / denominator, the depthwise conv's zero padding -- is per stream. B = 1 is fcpe_forward.
+int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float thr, int mode, double* f0,
+                       int64_t cap, float* sal_out, hipStream_t s) {
   if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
   const FcpeCfg& g = c.fcfg;
   if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
+  if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
   const int C = g.n_chans, inner = g.n_heads * g.dim_head;
   const int F = (int)fcpe_frames(c, n);
-  const int64_t n_out = interp_uv && pad_to > 0 ? pad_to : F;
-  if (n_out > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(n_out) + " frames");
-  float* mel = c.buf<float>("fc.mel", (size_t)F * g.n_mels, s);
-  fcpe_mel(c, audio, n, mel, s);
+  if (F > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(F) + " frames per stream");
+  const int R = B * F;  // rows of every row-wise op (fcpe_mel checks the range)
+  float* mel = c.buf<float>("fc.mel", (size_t)R * g.n_mels, s);
+  fcpe_mel(c, audio, n, ld, B, mel, s);
+  auto per_stream = [&](ConvArgs a, int Cin, int N) {  // a k = 3 conv over each stream's own F rows
+    a.batch = B;
+    a.x_bs = (long long)F * Cin;
+    a.y_bs = (long long)F * N;
+    return a;
+  };
   // ---- input stack (:624-631)
-  float* x = c.buf<float>("fc.x", (size_t)F * C, s);
-  float* x1 = c.buf<float>("fc.x1", (size_t)F * C, s);
-  float* ln = c.buf<float>("fc.ln", (size_t)F * C, s);
-  launch_conv(c, conv3(mel, F, g.n_mels, c.W("fc.stack0.w"), C, c.W("fc.stack0.b"), x1), false, s);
-  double* gnws = c.buf<double>("fc.gnws", (size_t)4 * FCPE_GN_CHUNKS * 2, s);
-  check(groupnorm_lrelu(x1, F, C, 4, c.W("fc.gn.g"), c.W("fc.gn.b"), 1e-5f, 0.01f, gnws, s), "fcpe_groupnorm");
-  launch_conv(c, conv3(x1, F, C, c.W("fc.stack3.w"), C, c.W("fc.stack3.b"), x), false, s);
+  float* x = c.buf<float>("fc.x", (size_t)R * C, s);
+  float* x1 = c.buf<float>("fc.x1", (size_t)R * C, s);
+  float* ln = c.buf<float>("fc.ln", (size_t)R * C, s);
+  launch_conv(c, per_stream(conv3(mel, F, g.n_mels, c.W("fc.stack0.w"), C, c.W("fc.stack0.b"), x1), g.n_mels, C), false,
+              s);
+  double* gnws = c.buf<double>("fc.gnws", (size_t)B * 4 * FCPE_GN_CHUNKS * 2, s);
+  check(groupnorm_lrelu(x1, F, C, 4, c.W("fc.gn.g"), c.W("fc.gn.b"), 1e-5f, 0.01f, gnws, s, B), "fcpe_groupnorm");
+  launch_conv(c, per_stream(conv3(x1, F, C, c.W("fc.stack3.w"), C, c.W("fc.stack3.b"), x), C, C), false, s);
   // ---- PCmer (:270-283)
-  float* qkv = c.buf<float>("fc.qkv", (size_t)F * 3 * inner, s);
-  float* att = c.buf<float>("fc.att", (size_t)F * inner, s);
-  float* h4 = c.buf<float>("fc.h4", (size_t)F * 4 * C, s);
-  float* dw = c.buf<float>("fc.dw", (size_t)F * 2 * C, s);
-  float* aws = c.buf<float>("fc.attws", (size_t)performer_ws_floats(g.n_heads, F, g.n_feat), s);
+  float* qkv = c.buf<float>("fc.qkv", (size_t)R * 3 * inner, s);
+  float* att = c.buf<float>("fc.att", (size_t)R * inner, s);
+  float* h4 = c.buf<float>("fc.h4", (size_t)R * 4 * C, s);
+  float* dw = c.buf<float>("fc.dw", (size_t)R * 2 * C, s);
+  float* aws = c.buf<float>("fc.attws", (size_t)performer_ws_floats(g.n_heads, F, g.n_feat, B), s);
   for (int i = 0; i < g.n_layers; ++i) {
     // x1 = x + to_out(attention(to_q, to_k, to_v of LN(x)))
-    check(layernorm_rows(x, nullptr, ln, c.W(dn(i, "ln.g")), c.W(dn(i, "ln.b")), F, C, 1e-5f, nullptr, s), "fcpe_ln");
-    launch_conv(c, lin(ln, C, F, C, c.W(dn(i, "qkv.w")), 3 * inner, c.W(dn(i, "qkv.b")), qkv, 3 * inner), false, s);
+    check(layernorm_rows(x, nullptr, ln, c.W(dn(i, "ln.g")), c.W(dn(i, "ln.b")), R, C, 1e-5f, nullptr, s), "fcpe_ln");
+    launch_conv(c, lin(ln, C, R, C, c.W(dn(i, "qkv.w")), 3 * inner, c.W(dn(i, "qkv.b")), qkv, 3 * inner), false, s);
     check(performer_attention(qkv, qkv + inner, qkv + 2 * inner, g.dim_head, 3 * inner, g.n_heads, F,
-                              c.W(dn(i, "proj")), g.n_feat, aws, att, g.dim_head, inner, s),
+                              c.W(dn(i, "proj")), g.n_feat, aws, att, g.dim_head, inner, s, B,
+                              (long long)F * 3 * inner, (long long)F * inner),
           "performer_attention");
     {
-      ConvArgs a = lin(att, inner, F, inner, c.W(dn(i, "out.w")), C, c.W(dn(i, "out.b")), x1, C);
+      ConvArgs a = lin(att, inner, R, inner, c.W(dn(i, "out.w")), C, c.W(dn(i, "out.b")), x1, C);
       a.res = x;
       a.ldr = C;
       a.res_mode = RES_ADD_POST;
       launch_conv(c, a, false, s);
     }
     // x = x1 + conformer(x1)
-    check(layernorm_rows(x1, nullptr, ln, c.W(dn(i, "cf.ln.g")), c.W(dn(i, "cf.ln.b")), F, C, 1e-5f, nullptr, s),
+    check(layernorm_rows(x1, nullptr, ln, c.W(dn(i, "cf.ln.g")), c.W(dn(i, "cf.ln.b")), R, C, 1e-5f, nullptr, s),
           "fcpe_ln");
-    launch_conv(c, lin(ln, C, F, C, c.W(dn(i, "cf.pw1.w")), 4 * C, c.W(dn(i, "cf.pw1.b")), h4, 4 * C), false, s);
-    check(glu_dwconv_swish(h4, F, 2 * C, c.W(dn(i, "cf.dw.w")), c.W(dn(i, "cf.dw.b")), g.conv_k, g.conv_k / 2, dw, s),
+    launch_conv(c, lin(ln, C, R, C, c.W(dn(i, "cf.pw1.w")), 4 * C, c.W(dn(i, "cf.pw1.b")), h4, 4 * C), false, s);
+    check(glu_dwconv_swish(h4, F, 2 * C, c.W(dn(i, "cf.dw.w")), c.W(dn(i, "cf.dw.b")), g.conv_k, g.conv_k / 2, dw, s,
+                           B),
           "fcpe_dwconv");
     {
-      ConvArgs a = lin(dw, 2 * C, F, 2 * C, c.W(dn(i, "cf.pw2.w")), C, c.W(dn(i, "cf.pw2.b")), x, C);
+      ConvArgs a = lin(dw, 2 * C, R, 2 * C, c.W(dn(i, "cf.pw2.w")), C, c.W(dn(i, "cf.pw2.b")), x, C);
       a.res = x1;
       a.ldr = C;
       a.res_mode = RES_ADD_POST;
@@ -296,14 +322,34 @@ int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode,
     }
   }
   // ---- head (:663-665)
-  check(layernorm_rows(x, nullptr, ln, c.W("fc.norm.g"), c.W("fc.norm.b"), F, C, 1e-5f, nullptr, s), "fcpe_ln");
-  float* sal = sal_out ? sal_out : c.buf<float>("fc.sal", (size_t)F * g.out_dims, s);
+  check(layernorm_rows(x, nullptr, ln, c.W("fc.norm.g"), c.W("fc.norm.b"), R, C, 1e-5f, nullptr, s), "fcpe_ln");
+  float* sal = sal_out ? sal_out : c.buf<float>("fc.sal", (size_t)R * g.out_dims, s);
   {
-    ConvArgs a = lin(ln, C, F, C, c.W("fc.dense.w"), g.out_dims, c.W("fc.dense.b"), sal, g.out_dims);
+    ConvArgs a = lin(ln, C, R, C, c.W("fc.dense.w"), g.out_dims, c.W("fc.dense.b"), sal, g.out_dims);
     a.act = ACT_SIGMOID;
     launch_conv(c, a, false, s);
   }
-  return fcpe_decode_run(c, sal, F, thr, mode, interp_uv, pad_to, f0, s);
+  // the decoders are row-wise: B F rows, f0 [B][F]
+  check(fcpe_decode(sal, R, g.out_dims, c.W("fc.cent"), thr, mode, f0, s), "fcpe_decode");
+  return F;
+}
+
+// One utterance: the B = 1 case of fcpe_forward_b, then FCPEF0Predictor.post_process when interp_uv.
+int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
+                     double* f0, float* sal_out, int64_t cap, hipStream_t s) {
+  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+  const FcpeCfg& g = c.fcfg;
+  if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
+  const int64_t F = fcpe_frames(c, n);
+  const int64_t n_out = interp_uv && pad_to > 0 ? pad_to : F;
+  if (n_out > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(n_out) + " frames");
+  if (!interp_uv) return fcpe_forward_b(c, audio, n, n, 1, thr, mode, f0, cap, sal_out, s);
+  if (n_out > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  double* raw = c.buf<double>("fc.f0raw", (size_t)F, s);
+  int* links = c.buf<int>("fc.links", (size_t)2 * n_out, s);
+  fcpe_forward_b(c, audio, n, n, 1, thr, mode, raw, F, sal_out, s);
+  check(fcpe_post_process(raw, (int)F, (int)n_out, g.hop, g.sr, links, f0, s), "fcpe_post_process");
+  return n_out;
 }
 
 }  // namespace rvcx

@@ -7,7 +7,8 @@
 // not functional, so the PyTorch semantics are followed.
 //
 // Per hop, all on device: 48k -> 16k resample (torchaudio sinc kernel), circular audio/convert buffers
-// and the RMS gate, RMVPE f0 + realtime quantisation into the circular pitch buffers, HuBERT (+ repeated
+// and the RMS gate, RMVPE or FCPE f0 (rvcx_rt_desc::f0_method; one batched forward over the B convert buffers either
+// way) + realtime quantisation into the circular pitch buffers, HuBERT (+ repeated
 // last frame), optional index retrieval from skip_head // 2, x2 upsample + protect, one batched
 // Synthesizer.infer over the B streams, clip, [volume envelope], * sqrt(vol), [tgt -> 48k resample],
 // SOLA offset search + crossfade. The host only plans (and syncs once per hop for proposed_pitch).
@@ -90,10 +91,20 @@ struct RtState {
   bool out_identity = true;
   DevBuf d_kin, d_kout, abuf[2], cbuf[2], pbuf[2], fbuf[2], sola, fade_in, offs, vol, volsq, gate, factor, meta;
   int cur = 0;
+  int f0_method = 0;  // 0 RMVPE, 1 FCPE (rvcx_rt_desc)
+  float fcpe_thr = 0.006f;
 };
 
 RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
-  if (!c.ready[0] || !c.ready[1] || !c.ready[2]) throw Error(RVCX_E_STATE, "stream: synth, hubert and rmvpe must be finalized");
+  if (!c.ready[0] || !c.ready[1]) throw Error(RVCX_E_STATE, "stream: synth and hubert must be finalized");
+  if (d.f0_method < 0 || d.f0_method > 1) throw Error(RVCX_E_INVALID, "stream: f0_method must be 0 (rmvpe) or 1 (fcpe)");
+  if (c.scfg.f0 && d.f0_method == 0 && !c.ready[2])
+    throw Error(RVCX_E_STATE, "stream: f0_method rmvpe but no RMVPE weights finalized");
+  if (c.scfg.f0 && d.f0_method == 1) {  // as the pipeline's f0_method 3 (runtime_pipeline.cpp check_f0_method)
+    if (!c.ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "stream: f0_method fcpe but no FCPE weights finalized");
+    if (c.fcfg.sr != 16000 || c.fcfg.hop != 160)  // the pitch frames are 160 samples at 16 kHz
+      throw Error(RVCX_E_SHAPE, "stream: the FCPE model must run at 16 kHz with hop_size 160");
+  }
   if (d.n_streams < 1 || d.n_streams > 4096) throw Error(RVCX_E_INVALID, "stream: n_streams out of range");
   if (d.read_chunk_size < 1) throw Error(RVCX_E_INVALID, "stream: read_chunk_size < 1");
   auto r = std::make_unique<RtState>();
@@ -101,6 +112,8 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   const double AUDIO_SR = 48000.0, SR = 16000.0;
   const int window = 160;
   s.B = d.n_streams;
+  s.f0_method = d.f0_method;
+  s.fcpe_thr = d.fcpe_threshold > 0 ? d.fcpe_threshold : 0.006f;  // the realtime filter_radius (pipeline.py:155)
   // VoiceChanger.__init__ (core.py:351-354)
   s.block48 = d.read_chunk_size * 128;
   s.cross48 = (int)(d.cross_fade_overlap_size * AUDIO_SR);
@@ -224,11 +237,18 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   double* f0 = c.buf<double>("rt.f0", (size_t)B * F, st);
   const int64_t L = hubert_frames(s.conv16);
   float* feats = c.buf<float>("rt.feats", (size_t)B * L * E, st);
-  hipStream_t ax = fork_aux(c, st);  // batched HuBERT beside batched RMVPE (pipeline.py:233-254)
+  hipStream_t ax = fork_aux(c, st);  // batched HuBERT beside the batched f0 network (pipeline.py:233-254)
   hubert_forward_b(c, conv, s.conv16, s.conv16, B, hubert_version_for(c), feats, L, ax);
   const bool guided = c.scfg.f0;  // no get_f0, pitch or protect without pitch guidance (pipeline.py:242-293)
   if (guided) {
-  rmvpe_forward_b(c, conv + s.silence_front, nf, s.conv16, B, 0.03f, f0, F, nullptr, st);
+  if (s.f0_method == 1) {  // the raw local_argmax track (pipeline.py:147-155), F = nf / 160 + 1 frames as RMVPE's
+    if (!c.ready[RVCX_MODEL_FCPE] || c.fcfg.sr != 16000 || c.fcfg.hop != 160)
+      throw Error(RVCX_E_STATE, "stream: the FCPE model this group was created with has been replaced");
+    if (fcpe_forward_b(c, conv + s.silence_front, nf, s.conv16, B, s.fcpe_thr, 0, f0, F, nullptr, st) != F)
+      throw Error(RVCX_E_SHAPE, "stream: FCPE frame count differs from the pitch track's");
+  } else {
+    rmvpe_forward_b(c, conv + s.silence_front, nf, s.conv16, B, 0.03f, f0, F, nullptr, st);
+  }
   std::vector<double> fac(B, std::pow(2.0, o.f0_up_key / 12.0));
   if (o.f0_autotune) {
     check(f0_autotune(f0, B * F, o.f0_autotune_strength, 0, st), "f0_autotune");

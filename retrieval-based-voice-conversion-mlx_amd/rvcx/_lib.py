@@ -31,10 +31,10 @@ EXPORTS = [
     "rvcx_pipeline_batch", "rvcx_set_highpass_sos", "rvcx_highpass_pad", "rvcx_device_status", "rvcx_index_parse",
     "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
-    "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode",
+    "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode", "rvcx_fcpe_b",
 ]
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
-TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_fcpe_mel"]
+TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel"]
 
 
 class RvcxLibraryError(ImportError):
@@ -88,7 +88,8 @@ class RtDesc(ctypes.Structure):
     """rvcx_rt_desc (include/rvcx.h)."""
     _fields_ = [("n_streams", ctypes.c_int), ("read_chunk_size", ctypes.c_int),
                 ("cross_fade_overlap_size", ctypes.c_double), ("extra_convert_size", ctypes.c_double),
-                ("silent_threshold", ctypes.c_double)]
+                ("silent_threshold", ctypes.c_double), ("f0_method", ctypes.c_int),
+                ("fcpe_threshold", ctypes.c_float)]
 
 
 class RtOpts(ctypes.Structure):
@@ -175,8 +176,10 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_set_fcpe_config": (i32, [vp, P(FcpeDesc)]),
         "rvcx_fcpe": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp, i64, P(i64), vp]),
         "rvcx_fcpe_decode": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp]),
+        "rvcx_fcpe_b": (i32, [vp, vp, i64, i64, i32, f32, i32, vp, vp, vp]),
         "rvcx_fcpe_mel": (i32, [vp, vp, i64, vp, i64, P(i64), vp]),
         "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
+        "rvcx_performer_attention_b": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
         "rvcx_split_audio": (i32, [vp, vp, i64, i32, f64, i32, P(i64), i64, P(i64), vp]),
         "rvcx_index_load": (i32, [vp, vp, i64]),
         "rvcx_index_unload": (i32, [vp]),

@@ -233,6 +233,26 @@ class Engine:
         assert fo.value == n_out, (fo.value, n_out)
         return (f0, sal) if want_salience else f0
 
+    def fcpe_batch(self, audio, threshold: float = 0.006, decoder: str = "local_argmax", want_salience: bool = False):
+        """rvcx_fcpe_b: FCPEInfer.__call__ for B streams in one batched forward. audio [B, n] at the model's sampling
+        rate -> the raw track f0 fp64 [B, n // hop + 1], zeros where a frame's maximum <= threshold (and the salience
+        [B, F, out_dims]). Each row is computed as rvcx_fcpe computes it alone: padding, statistics and the attention's
+        sums are per stream."""
+        if self.fcpe_cfg is None:
+            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        t = self.torch
+        a = self._dev(audio, t.float32)
+        if a.dim() != 2:
+            raise ValueError("fcpe_batch: audio [B, n]")
+        a = a.contiguous()
+        B, n = int(a.shape[0]), int(a.shape[1])
+        F = self._fcpe_frames(n)
+        f0 = t.empty((B, F), dtype=t.float64, device=self.device)
+        sal = t.empty((B, F, self.fcpe_cfg["out_dims"]), dtype=t.float32, device=self.device) if want_salience else None
+        self._check(self.lib.rvcx_fcpe_b(self.ctx, a.data_ptr(), n, n, B, float(threshold), self._FCPE_DECODERS[decoder],
+                                         f0.data_ptr(), _ptr(sal), self.stream()), "fcpe_b")
+        return (f0, sal) if want_salience else f0
+
     def fcpe_decode(self, salience, threshold: float = 0.006, decoder: str = "local_argmax", interp_uv: bool = False,
                     pad_to=None):
         """rvcx_fcpe_decode: the cents decoder (+ post_process) alone on salience [F][out_dims] -> f0 fp64."""
@@ -274,6 +294,20 @@ class Engine:
         self._check(self.lib.rvcx_performer_attention(self.ctx, q.data_ptr(), k.data_ptr(), v.data_ptr(), H, T,
                                                       pm.data_ptr(), int(pm.shape[0]), out.data_ptr(), self.stream()),
                     "performer_attention")
+        return out
+
+    def performer_attention_batch(self, q, k, v, proj):
+        """rvcx_performer_attention_b (include/rvcx_test.h): q, k, v [B][H][T][64], proj [M][64] -> [B][H][T][64], the
+        B streams in one set of launches."""
+        t = self.torch
+        q, k, v, pm = (self._dev(x, t.float32).contiguous() for x in (q, k, v, proj))
+        if q.dim() != 4 or q.shape[3] != 64 or k.shape != q.shape or v.shape != q.shape or pm.shape[1] != 64:
+            raise ValueError("performer_attention_batch: q, k, v [B][H][T][64] and proj [M][64]")
+        B, H, T, _ = (int(x) for x in q.shape)
+        out = t.empty_like(q)
+        self._check(self.lib.rvcx_performer_attention_b(self.ctx, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, H, T,
+                                                        pm.data_ptr(), int(pm.shape[0]), out.data_ptr(),
+                                                        self.stream()), "performer_attention_b")
         return out
 
     @property

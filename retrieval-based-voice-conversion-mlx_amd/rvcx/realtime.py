@@ -6,7 +6,7 @@ Mirrors rvc/realtime/core.py (``VoiceChanger`` :329-484 with ``process_audio`` /
 PyTorch path's behaviour is the contract.
 
 ``StreamGroup`` converts B concurrent streams of one geometry per hop in one device call
-(``rvcx_rt_process``: resample, circular buffers, RMS gate, RMVPE, HuBERT, retrieval, one batched
+(``rvcx_rt_process``: resample, circular buffers, RMS gate, RMVPE or FCPE (``f0_method``), HuBERT, retrieval, one batched
 Synthesizer.infer, SOLA crossfade -- all HIP kernels). ``VoiceChanger`` is the one-stream, numpy-in /
 numpy-out object of the reference. Audio I/O, VAD, noise gate and pedalboard effects are not part of
 this path.
@@ -22,6 +22,15 @@ import numpy as np
 from . import _lib
 from .engine import Engine
 
+F0_METHODS = ("rmvpe", "fcpe")  # VoiceChanger's f0_method (rvc/realtime/pipeline.py:140-155)
+
+
+def _f0_method_id(f0_method) -> int:
+    if f0_method not in F0_METHODS:
+        raise ValueError(f"f0_method {f0_method!r} is not supported in realtime streams: one of {F0_METHODS}")
+    return F0_METHODS.index(f0_method)
+
+
 GEOMETRY_FIELDS = ("n_streams", "block48", "block16", "convert16", "frames", "skip_head", "return_length",
                    "crossfade48", "sola_search48", "extra48", "resampled_block16", "silence_front")
 
@@ -31,18 +40,27 @@ def _ptr(t):
 
 
 class StreamGroup:
-    """B streams sharing one buffer geometry, converted together each hop on one Engine."""
+    """B streams sharing one buffer geometry, converted together each hop on one Engine.
+
+    f0_method "rmvpe" (the default) or "fcpe": the pitch network every hop runs, batched over the B convert buffers.
+    "fcpe" uses the checkpoint loaded with ``Engine.load_fcpe`` (16 kHz, hop 160) and needs no RMVPE weights; its raw
+    local_argmax track is voiced where the frame maximum exceeds fcpe_threshold (the reference's 0.006)."""
 
     def __init__(self, engine: Engine, n_streams: int = 1, read_chunk_size: int = 192,
                  cross_fade_overlap_size: float = 0.1, extra_convert_size: float = 0.5,
-                 silent_threshold: float = -90.0, sid=0):
+                 silent_threshold: float = -90.0, sid=0, f0_method: str = "rmvpe", fcpe_threshold: float = 0.006):
+        method = _f0_method_id(f0_method)
+        if f0_method == "fcpe" and getattr(engine, "fcpe_cfg", None) is None:
+            raise ValueError('f0_method "fcpe" needs an FCPE checkpoint on the Engine (Engine.load_fcpe)')
         self.engine = engine
+        self.f0_method = f0_method
         lib = engine.lib
         d = _lib.RtDesc()
         lib.rvcx_rt_default_desc(ctypes.byref(d))
         d.n_streams, d.read_chunk_size = int(n_streams), int(read_chunk_size)
         d.cross_fade_overlap_size, d.extra_convert_size = float(cross_fade_overlap_size), float(extra_convert_size)
         d.silent_threshold = float(silent_threshold)
+        d.f0_method, d.fcpe_threshold = method, float(fcpe_threshold)
         h = ctypes.c_void_p()
         engine._check(lib.rvcx_rt_create(engine.ctx, ctypes.byref(d), ctypes.byref(h)), "rt_create")
         self.handle = h
@@ -108,17 +126,21 @@ class VoiceChanger:
     """One realtime stream with the reference's API (rvc/realtime/core.py:329-484).
 
     ``VoiceChanger(read_chunk_size, cross_fade_overlap_size, extra_convert_size, engine=..., sid=0,
-    silent_threshold=0)`` then ``on_request(audio_input @48k) -> (audio_out np.float32 [block], vol, [0, ms, 0])``.
+    silent_threshold=0, f0_method="rmvpe")`` then ``on_request(audio_input @48k) -> (audio_out np.float32 [block], vol, [0, ms, 0])``.
     Models come from the Engine (``rvcx.infer.RVCX(...).engine`` or an Engine loaded by hand); an index
-    loaded on that Engine (``rvcx.infer.read_index``) is used when index_rate > 0.
+    loaded on that Engine (``rvcx.infer.read_index``) is used when index_rate > 0. f0_method is the reference's
+    "rmvpe" or "fcpe" (``Engine.load_fcpe``; fcpe_threshold as in StreamGroup); any other name raises ValueError.
     """
 
     def __init__(self, read_chunk_size: int, cross_fade_overlap_size: float, extra_convert_size: float,
-                 engine: Engine = None, silent_threshold: int = 0, sid: int = 0, **_unused):
+                 engine: Engine = None, silent_threshold: int = 0, sid: int = 0, f0_method: str = "rmvpe",
+                 fcpe_threshold: float = 0.006, **_unused):
+        _f0_method_id(f0_method)
         if engine is None:
-            raise ValueError("VoiceChanger needs an rvcx Engine with the synthesizer, HuBERT and RMVPE loaded")
+            raise ValueError("VoiceChanger needs an rvcx Engine with the synthesizer, HuBERT and the f0 method's "
+                             "model (RMVPE or FCPE) loaded")
         self.group = StreamGroup(engine, 1, read_chunk_size, cross_fade_overlap_size, extra_convert_size,
-                                 silent_threshold, sid)
+                                 silent_threshold, sid, f0_method, fcpe_threshold)
         g = self.group.geometry
         self.block_frame, self.crossfade_frame = g["block48"], g["crossfade48"]
         self.sola_search_frame, self.extra_frame = g["sola_search48"], g["extra48"]
