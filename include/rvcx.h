@@ -410,7 +410,8 @@ typedef struct {
   float fcpe_threshold;           /* f0_method 1: FCPE's voicing threshold; <= 0: 0.006 (pipeline.py:155) */
 } rvcx_rt_desc;
 
-typedef struct {                  /* per-hop options of VoiceChanger.on_request (core.py:453-484) */
+typedef struct {                  /* per-hop options of VoiceChanger.on_request (core.py:453-484); one for the group
+                                   * (rvcx_rt_process) or one per stream (rvcx_rt_process_v) */
   double f0_up_key;
   double index_rate;              /* > 0 needs rvcx_index_load; retrieval from skip_head // 2 */
   float protect;                  /* active when < 0.5 */
@@ -444,6 +445,30 @@ int rvcx_rt_reset(rvcx_ctx* ctx, rvcx_rt* rt, void* stream);
 int rvcx_rt_process(rvcx_ctx* ctx, rvcx_rt* rt, const float* d_in, const int32_t* sids, const rvcx_rt_opts* opts,
                     const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, float* d_vol,
                     int32_t* d_offs, void* stream);
+/* rvcx_rt_process with one rvcx_rt_opts per stream and an optional set of idle slots.
+ * opts: host [B]. active: host [B] (0 = idle this hop), NULL = all active. rvcx_rt_process(o) is this call with B
+ * copies of o and active = NULL.
+ * Per-stream options: each stream gets its own on_request arguments -- its own pitch factor (f0_up_key, and the
+ * proposed key when proposed_pitch is set and autotune is not; the host syncs once, and only on hops where an active
+ * stream asks), autotune on its own f0 row only (factor 1 there, the other rows' f0 bits untouched), protect, index_rate
+ * (one batched search over every stream that retrieves, each blended at its own (float)r / (float)(1 - r); streams at
+ * rate 0 are copied through) and volume_envelope (one batched change_rms; streams at exactly 1 untouched).
+ * gen_precision belongs to the hop: the active streams must agree (RVCX_E_INVALID). RVCX_E_STATE when an active
+ * stream has index_rate > 0 and no index is loaded. Nothing is launched and no state changes when the call fails so.
+ * Idle slots: for a slot with active[b] == 0 the hop did not happen -- its row of d_in is not read, none of its state
+ * changes, its d_out row is zeros, its d_vol 0 and its d_offs 0; its opts and sid are ignored. The networks run on the
+ * active streams only, compacted in slot order; with no active stream the call only writes the zero outputs.
+ * Noise: injected d_eps_z / d_eps_src are indexed by SLOT (row b belongs to slot b, idle rows are not read; with idle
+ * slots the injected source noise needs the HiFi-GAN-NSF layout, one [frames * upp] row per slot, else
+ * RVCX_E_INVALID). Drawn noise (Philox(seed)) is keyed by COMPACT ROW, the stream's position among the active ones:
+ * the draws of a hop are distinct across its active streams, and a stream's draws for one seed move when a
+ * lower-numbered slot goes idle -- vary the seed per hop, as VoiceChanger does. */
+int rvcx_rt_process_v(rvcx_ctx* ctx, rvcx_rt* rt, const float* d_in, const int32_t* sids, const rvcx_rt_opts* opts,
+                      const uint8_t* active, const float* d_eps_z, const float* d_eps_src, uint64_t seed,
+                      float* d_out, float* d_vol, int32_t* d_offs, void* stream);
+/* rvcx_rt_reset for one slot: its audio / convert / pitch / pitchf buffers and SOLA tail zeroed, asynchronous on
+ * `stream`, the other slots untouched. RVCX_E_INVALID when stream_index is not in [0, n_streams). */
+int rvcx_rt_reset_stream(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, void* stream);
 
 /* Contraction arithmetic of every convolution / linear / attention matmul of this context (replaces nothing in
  * the reference; torch's fp32 CPU conv is what every mode reproduces): 0 = default (3), 1 = fp32-input MFMA

@@ -1173,6 +1173,29 @@ hipError_t f0_autotune(double* f0, int F, double strength, int skip_unvoiced, hi
   hipLaunchKernelGGL(k_autotune, dim3(nblocks(F)), dim3(TB), 0, s, f0, F, strength, skip_unvoiced);
   return hipGetLastError();
 }
+// The same per row of f0 [B][F] (blockIdx.y = row) with each row's own strength; rows with on[b] == 0 are not touched.
+__global__ void k_autotune_rows(double* f0, int F, const double* __restrict__ strength, const int* __restrict__ on) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= F || !on[b]) return;
+  double* row = f0 + (long long)b * F;
+  const double f = row[i];
+  double best = c_notes[0], bd = fabs(c_notes[0] - f);
+  for (int j = 1; j < 54; ++j) {
+    const double d = fabs(c_notes[j] - f);
+    if (d < bd) {
+      bd = d;
+      best = c_notes[j];
+    }
+  }
+  row[i] = f + (best - f) * strength[b];
+}
+hipError_t f0_autotune_rows(double* f0, int F, const double* strength, const int* on, int B, hipStream_t s) {
+  if (F <= 0 || B < 1) return hipSuccess;
+  hipLaunchKernelGGL(k_autotune_rows, dim3(nblocks(F), B), dim3(TB), 0, s, f0, F, strength, on);
+  return hipGetLastError();
+}
 
 // ------------------------------------------------------------------ long-input split points
 // Pipeline.pipeline opt_ts search (rvc/infer/pipeline.py:440-452): with xp = reflect-pad(x, w/2),
@@ -1307,14 +1330,57 @@ hipError_t change_rms(const double* src, long long n_src, int sr_src, float* y, 
   hipLaunchKernelGGL(k_apply_rms, dim3(nblocks(n_y)), dim3(TB), 0, s, y, n_y, ws, n1, ws + n1, n2, rate);
   return hipGetLastError();
 }
-// change_rms with a float32 source (the streaming path's 16 kHz convert buffer, rvc/realtime/pipeline.py:303-310)
-hipError_t change_rms_f32src(const float* src, long long n_src, int sr_src, float* y, long long n_y, int sr_y,
-                             float rate, float* ws, hipStream_t s) {
+// change_rms with a float32 source (the streaming path's 16 kHz convert buffer, rvc/realtime/pipeline.py:303-310) over B
+// rows in one launch set (blockIdx.y = row): src rows of stride ld_src, y rows of stride ld_y, each row with its own
+// rate [B] and its own n1 + n2 floats of ws. Rows whose rate is exactly 1 are left untouched. The arithmetic per row
+// is k_rms_frames<float> / k_apply_rms.
+__global__ void k_rms_frames_rows(const float* x, long long ld, long long n, int frame, int hop, float* rms,
+                                  int ld_rms, const float* __restrict__ rate) {
+  const int b = blockIdx.y;
+  if (rate[b] == 1.f) return;
+  x += b * ld;
+  const long long start = (long long)blockIdx.x * hop - frame / 2;
+  double acc = 0.0;
+  for (int j = threadIdx.x; j < frame; j += blockDim.x) {
+    const long long q = start + j;
+    if (q >= 0 && q < n) {
+      const double v = (double)x[q];
+      acc += v * v;
+    }
+  }
+  __shared__ double red[TB];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = TB / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) rms[(long long)b * ld_rms + blockIdx.x] = (float)sqrt(red[0] / frame);
+}
+__global__ void k_apply_rms_rows(float* y, long long ld, long long n, const float* ws, int n1, int n2,
+                                 const float* __restrict__ rate_v) {
+  const int b = blockIdx.y;
+  const float rate = rate_v[b];
+  if (rate == 1.f) return;
+  y += b * ld;
+  const float* r1 = ws + (long long)b * (n1 + n2);
+  const float* r2 = r1 + n1;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float a = interp_linear(r1, n1, i, n);
+    const float c = fmaxf(interp_linear(r2, n2, i, n), 1e-6f);
+    y[i] = y[i] * (powf(a, 1.f - rate) * powf(c, rate - 1.f));
+  }
+}
+hipError_t change_rms_f32src_rows(const float* src, long long ld_src, long long n_src, int sr_src, float* y,
+                                  long long ld_y, long long n_y, int sr_y, const float* rate, float* ws, int B,
+                                  hipStream_t s) {
+  if (B < 1) return hipSuccess;
   const int n1 = rms_frame_count(n_src, sr_src), n2 = rms_frame_count(n_y, sr_y);
-  hipLaunchKernelGGL(k_rms_frames<float>, dim3(n1), dim3(TB), 0, s, src, n_src, sr_src / 2 * 2, sr_src / 2, ws);
-  hipLaunchKernelGGL(k_rms_frames<float>, dim3(n2), dim3(TB), 0, s, (const float*)y, n_y, sr_y / 2 * 2, sr_y / 2,
-                     ws + n1);
-  hipLaunchKernelGGL(k_apply_rms, dim3(nblocks(n_y)), dim3(TB), 0, s, y, n_y, ws, n1, ws + n1, n2, rate);
+  hipLaunchKernelGGL(k_rms_frames_rows, dim3(n1, B), dim3(TB), 0, s, src, ld_src, n_src, sr_src / 2 * 2, sr_src / 2, ws,
+                     n1 + n2, rate);
+  hipLaunchKernelGGL(k_rms_frames_rows, dim3(n2, B), dim3(TB), 0, s, (const float*)y, ld_y, n_y, sr_y / 2 * 2, sr_y / 2,
+                     ws + n1, n1 + n2, rate);
+  hipLaunchKernelGGL(k_apply_rms_rows, dim3(nblocks(n_y), B), dim3(TB), 0, s, y, ld_y, n_y, ws, n1, n2, rate);
   return hipGetLastError();
 }
 

@@ -1451,15 +1451,34 @@ int rvcx_rt_reset(rvcx_ctx* ctx, rvcx_rt* rt, void* stream) {
   });
 }
 
+int rvcx_rt_reset_stream(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, void* stream) {
+  return guard(ctx, [&] {
+    if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_reset_stream: null stream group");
+    set_device(ctx);
+    rt_reset_stream(*ctx, *rt->s, stream_index, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rvcx_rt_process_v(rvcx_ctx* ctx, rvcx_rt* rt, const float* d_in, const int32_t* sids, const rvcx_rt_opts* opts,
+                      const uint8_t* active, const float* d_eps_z, const float* d_eps_src, uint64_t seed,
+                      float* d_out, float* d_vol, int32_t* d_offs, void* stream) {
+  return guard(ctx, [&] {
+    if (!rt || !rt->s || !d_in || !sids || !opts || !d_out) throw Error(RVCX_E_INVALID, "rt_process_v: null argument");
+    set_device(ctx);
+    rt_process(*ctx, *rt->s, d_in, sids, opts, active, d_eps_z, d_eps_src, seed, d_out, d_vol, d_offs,
+               static_cast<hipStream_t>(stream));
+  });
+}
+
+// one rvcx_rt_opts for the whole group: rvcx_rt_process_v with B copies of it and every slot active
 int rvcx_rt_process(rvcx_ctx* ctx, rvcx_rt* rt, const float* d_in, const int32_t* sids, const rvcx_rt_opts* opts,
                     const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, float* d_vol,
                     int32_t* d_offs, void* stream) {
-  return guard(ctx, [&] {
-    if (!rt || !rt->s || !d_in || !sids || !opts || !d_out) throw Error(RVCX_E_INVALID, "rt_process: null argument");
-    set_device(ctx);
-    rt_process(*ctx, *rt->s, d_in, sids, *opts, d_eps_z, d_eps_src, seed, d_out, d_vol, d_offs,
-               static_cast<hipStream_t>(stream));
-  });
+  if (!rt || !rt->s || !opts) return rvcx_rt_process_v(ctx, rt, d_in, sids, nullptr, nullptr, d_eps_z, d_eps_src, seed,
+                                                       d_out, d_vol, d_offs, stream);
+  const std::vector<rvcx_rt_opts> each((size_t)rt_streams(*rt->s), *opts);
+  return rvcx_rt_process_v(ctx, rt, d_in, sids, each.data(), nullptr, d_eps_z, d_eps_src, seed, d_out, d_vol, d_offs,
+                           stream);
 }
 
 // ------------------------------------------------------------------ batched offline conversion (C4)

@@ -223,6 +223,22 @@ void index_retrieve(Ctx& c, const float* feats, int64_t L, int d, double index_r
         "ivf_retrieve");
 }
 
+void index_retrieve_rows(Ctx& c, const float* feats, int64_t L, int64_t off, int d, int n_seq, const int* seqs,
+                         const float* rate, const float* one_minus_rate, float* out, hipStream_t s) {
+  const IvfView& v = loaded(c);
+  if (d != v.d)
+    throw Error(RVCX_E_SHAPE, "index dimension " + std::to_string(v.d) + " != feature width " + std::to_string(d));
+  if (n_seq <= 0 || L - off <= 0) return;
+  float* ws = c.buf<float>("ivf.ws", ivf_ws_floats((long long)n_seq * (L - off), v.nlist, v.nprobe), s);
+  IvfRows R;
+  R.seqs = seqs;
+  R.rate = rate;
+  R.one_minus_rate = one_minus_rate;
+  R.L = (int)L;
+  R.off = (int)off;
+  check(ivf_retrieve_rows(v, feats, R, n_seq, out, ws, s), "ivf_retrieve_rows");
+}
+
 void index_reconstruct_n(Ctx& c, int64_t i0, int64_t ni, float* out, hipStream_t s) {
   const IvfView& v = loaded(c);
   if (i0 < 0 || ni < 0 || i0 + ni > v.ntotal) throw Error(RVCX_E_INVALID, "reconstruct_n: range out of bounds");

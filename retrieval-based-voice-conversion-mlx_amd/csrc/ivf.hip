@@ -38,6 +38,13 @@ __device__ __forceinline__ bool key_lt(float da, long long ta, float db, long lo
   return da < db || (da == db && ta < tb);
 }
 
+// row of x / out that query q reads and writes (IvfRows, rvcx_kernels.h)
+__device__ __forceinline__ long long query_row(const IvfRows& R, int q) {
+  if (!R.seqs) return q;
+  const int Lq = R.L - R.off;
+  return (long long)R.seqs[q / Lq] * R.L + R.off + q % Lq;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ coarse distances
@@ -46,13 +53,13 @@ __device__ __forceinline__ bool key_lt(float da, long long ta, float db, long lo
 constexpr int IVF_QB = 8;
 __global__ void __launch_bounds__(256) k_ivf_coarse(const float* __restrict__ x, int n, int d,
                                                     const float* __restrict__ cent, int nlist,
-                                                    float* __restrict__ cd) {
+                                                    float* __restrict__ cd, IvfRows R) {
   extern __shared__ float xs[];  // [IVF_QB][d]
   const int q0 = blockIdx.y * IVF_QB;
   const int nq = min(IVF_QB, n - q0);
   for (int i = threadIdx.x; i < IVF_QB * d; i += blockDim.x) {
     const int q = i / d;
-    xs[i] = q < nq ? x[(long long)(q0 + q) * d + (i % d)] : 0.f;
+    xs[i] = q < nq ? x[query_row(R, q0 + q) * d + (i % d)] : 0.f;
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -132,7 +139,7 @@ __global__ void __launch_bounds__(256) k_ivf_scan(const float* __restrict__ x, i
                                                   int nprobe, int k, float* __restrict__ dist_out,
                                                   long long* __restrict__ ids_out, const int* __restrict__ slot_of_id,
                                                   long long ntotal, float rate, float one_minus_rate,
-                                                  float* __restrict__ out) {
+                                                  float* __restrict__ out, IvfRows R) {
   extern __shared__ float sm[];
   float* xs = sm;                                   // [d]
   float* cd = xs + d;                               // [4*16] candidate dists
@@ -146,7 +153,13 @@ __global__ void __launch_bounds__(256) k_ivf_scan(const float* __restrict__ x, i
   __shared__ int sel_sh[64];
   const int q = blockIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const float* xq = x + (long long)q * d;
+  const long long row = query_row(R, q);
+  const float* xq = x + row * d;
+  if (R.seqs) {  // each sequence's own blend
+    const int sq = R.seqs[q / (R.L - R.off)];
+    rate = R.rate[sq];
+    one_minus_rate = R.one_minus_rate[sq];
+  }
   for (int i = threadIdx.x; i < d; i += blockDim.x) xs[i] = xq[i];
   __syncthreads();
 
@@ -260,7 +273,7 @@ __global__ void __launch_bounds__(256) k_ivf_scan(const float* __restrict__ x, i
   for (int c = threadIdx.x; c < d; c += blockDim.x) {
     float acc = vecs[rs[0] * d + c] * rw[0];
     for (int j = 1; j < k; ++j) acc = acc + vecs[rs[j] * d + c] * rw[j];
-    out[(long long)q * d + c] = acc * rate + one_minus_rate * xq[c];
+    out[row * d + c] = acc * rate + one_minus_rate * xq[c];
   }
 }
 #pragma clang fp contract(on)
@@ -270,20 +283,33 @@ size_t ivf_ws_floats(long long n, long long nlist, int nprobe) {
   return (size_t)n * nlist + (size_t)n * nprobe + 64;
 }
 
-hipError_t ivf_search(const IvfView& v, const float* x, long long n, int k, float* dist_out, long long* ids_out,
-                      float rate, float one_minus_rate, float* out, float* ws, hipStream_t s) {
+static hipError_t ivf_launch(const IvfView& v, const float* x, long long n, int k, float* dist_out,
+                             long long* ids_out, float rate, float one_minus_rate, float* out, float* ws,
+                             const IvfRows& R, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   float* cd = ws;
   int* probe = reinterpret_cast<int*>(ws + (size_t)n * v.nlist);
   const size_t lds_c = (size_t)IVF_QB * v.d * sizeof(float);
   hipLaunchKernelGGL(k_ivf_coarse, dim3((unsigned)((v.nlist + 63) / 64), (unsigned)((n + IVF_QB - 1) / IVF_QB)),
-                     dim3(256), lds_c, s, x, (int)n, v.d, v.cent, (int)v.nlist, cd);
+                     dim3(256), lds_c, s, x, (int)n, v.d, v.cent, (int)v.nlist, cd, R);
   hipLaunchKernelGGL(k_ivf_probe, dim3((unsigned)n), dim3(64), 0, s, cd, (int)n, (int)v.nlist, v.nprobe, probe);
   const size_t lds_s = (size_t)v.d * sizeof(float) + 64 * sizeof(float) + 128 * sizeof(long long) +
                        16 * (2 * sizeof(float) + 2 * sizeof(long long));
   hipLaunchKernelGGL(k_ivf_scan, dim3((unsigned)n), dim3(256), lds_s, s, x, (int)n, v.d, v.vecs, v.off, v.ids,
-                     probe, v.nprobe, k, dist_out, ids_out, v.slot_of_id, v.ntotal, rate, one_minus_rate, out);
+                     probe, v.nprobe, k, dist_out, ids_out, v.slot_of_id, v.ntotal, rate, one_minus_rate, out, R);
   return hipGetLastError();
+}
+
+hipError_t ivf_search(const IvfView& v, const float* x, long long n, int k, float* dist_out, long long* ids_out,
+                      float rate, float one_minus_rate, float* out, float* ws, hipStream_t s) {
+  return ivf_launch(v, x, n, k, dist_out, ids_out, rate, one_minus_rate, out, ws, IvfRows{}, s);
+}
+
+hipError_t ivf_retrieve_rows(const IvfView& v, const float* x, const IvfRows& rows, int n_seq, float* out, float* ws,
+                             hipStream_t s) {
+  if (!rows.seqs || !rows.rate || !rows.one_minus_rate || rows.off < 0 || rows.off >= rows.L || !out)
+    return hipErrorInvalidValue;
+  return ivf_launch(v, x, (long long)n_seq * (rows.L - rows.off), 8, nullptr, nullptr, 0.f, 0.f, out, ws, rows, s);
 }
 
 }  // namespace rvcx

@@ -374,9 +374,12 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d);
 void rt_destroy(RtState* s);
 void rt_geometry(const RtState& s, int64_t* g);
 void rt_reset(Ctx& c, RtState& s, hipStream_t st);
-void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts& o,
-                const float* eps_z, const float* eps_src, uint64_t seed, float* out48, float* vol_out, int* offs_out,
-                hipStream_t st);
+void rt_reset_stream(Ctx& c, RtState& s, int stream_index, hipStream_t st);
+int rt_streams(const RtState& s);
+// opts [B], one per slot; active [B] (0 = the slot sits this hop out) or null = every slot active
+void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts* opts,
+                const uint8_t* active, const float* eps_z, const float* eps_src, uint64_t seed, float* out48,
+                float* vol_out, int* offs_out, hipStream_t st);
 // index (index_ivf.cpp)
 struct ParsedIvf {  // a validated faiss IndexIVFFlat image on the host (lists in list order)
   int d = 0, nprobe = 1;
@@ -389,6 +392,10 @@ ParsedIvf parse_ivf(const uint8_t* bytes, int64_t nbytes);  // host only; throws
 void index_load(Ctx& c, const uint8_t* bytes, int64_t nbytes);
 void index_search(Ctx& c, const float* x, int64_t n, int k, float* dist, int64_t* ids, hipStream_t s);
 void index_retrieve(Ctx& c, const float* feats, int64_t L, int d, double index_rate, float* out, hipStream_t s);
+// the blend for n_seq sequences of feats / out [.][L][d] in one search: rows off.. of sequence seqs[i] at
+// rate[seqs[i]] / one_minus_rate[seqs[i]] (device arrays); no other row of out is written
+void index_retrieve_rows(Ctx& c, const float* feats, int64_t L, int64_t off, int d, int n_seq, const int* seqs,
+                         const float* rate, const float* one_minus_rate, float* out, hipStream_t s);
 void index_reconstruct_n(Ctx& c, int64_t i0, int64_t ni, float* out, hipStream_t s);
 int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
                             const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,

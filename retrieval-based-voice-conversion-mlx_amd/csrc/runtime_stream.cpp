@@ -12,6 +12,11 @@
 // last frame), optional index retrieval from skip_head // 2, x2 upsample + protect, one batched
 // Synthesizer.infer over the B streams, clip, [volume envelope], * sqrt(vol), [tgt -> 48k resample],
 // SOLA offset search + crossfade. The host only plans (and syncs once per hop for proposed_pitch).
+//
+// Every option is per slot (one rvcx_rt_opts each), and a slot may sit a hop out. The networks run on the B_act active
+// slots compacted to rows 0..B_act-1; the state kernels (rt_ingest, rt_pitch, rt_up2, rt_sola) map rows to slots with
+// the device slot map (stream.hip). The per-row options, the synthesizer's lengths / sids and the slot map travel in
+// one upload per hop (RowPlan). With every slot active the map is the identity and is not passed.
 #include <cmath>
 #include <cstring>
 
@@ -65,6 +70,34 @@ SincKernel sinc_kernel(int orig_freq, int new_freq) {
   return r;
 }
 
+// One hop's per-row plan as it lies in device memory (every array sized for the group's B slots, the first B_act
+// entries valid unless noted): uploaded once per hop, `factor` again after the proposed-pitch sync.
+struct RowPlan {
+  size_t factor, strength, protect, rate, one_minus_rate, rms, autotune, use_protect, seqs, meta, slot2row, row2slot;
+  size_t bytes;
+  explicit RowPlan(int B) {
+    size_t o = 0;
+    auto take = [&](size_t elem, size_t n) {
+      const size_t at = o;
+      o += elem * n * (size_t)B;
+      return at;
+    };
+    factor = take(sizeof(double), 1);    // 2^(key / 12), 1 under autotune
+    strength = take(sizeof(double), 1);  // autotune strength
+    protect = take(sizeof(float), 1);
+    rate = take(sizeof(float), 1);  // (float)index_rate and (float)(1 - index_rate)
+    one_minus_rate = take(sizeof(float), 1);
+    rms = take(sizeof(float), 1);  // volume_envelope
+    autotune = take(sizeof(int), 1);
+    use_protect = take(sizeof(int), 1);
+    seqs = take(sizeof(int), 1);       // the rows that retrieve (n_ret entries)
+    meta = take(sizeof(int32_t), 2);   // lengths [B_act] at 0, sids [B_act] at B
+    slot2row = take(sizeof(int), 1);   // [B], -1 = idle
+    row2slot = take(sizeof(int), 1);
+    bytes = o;
+  }
+};
+
 template <class T>
 void dev_alloc(DevBuf& b, size_t count) {
   const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
@@ -89,7 +122,7 @@ struct RtState {
   int tgt_sr = 48000;
   SincKernel kin, kout;
   bool out_identity = true;
-  DevBuf d_kin, d_kout, abuf[2], cbuf[2], pbuf[2], fbuf[2], sola, fade_in, offs, vol, volsq, gate, factor, meta;
+  DevBuf d_kin, d_kout, abuf[2], cbuf[2], pbuf[2], fbuf[2], sola, fade_in, offs, vol, volsq, gate, rows;
   int cur = 0;
   int f0_method = 0;  // 0 RMVPE, 1 FCPE (rvcx_rt_desc)
   float fcpe_thr = 0.006f;
@@ -184,8 +217,7 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   dev_alloc<float>(s.vol, s.B);
   dev_alloc<float>(s.volsq, s.B);
   dev_alloc<int>(s.gate, s.B);
-  dev_alloc<double>(s.factor, s.B);
-  dev_alloc<int32_t>(s.meta, 2 * (size_t)s.B);
+  dev_alloc<char>(s.rows, RowPlan(s.B).bytes);
   return r.release();
 }
 
@@ -209,115 +241,231 @@ void rt_reset(Ctx& c, RtState& s, hipStream_t st) {
   s.cur = 0;
 }
 
-void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts& o,
-                const float* eps_z, const float* eps_src, uint64_t seed, float* out48, float* vol_out, int* offs_out,
-                hipStream_t st) {
+int rt_streams(const RtState& s) { return s.B; }
+
+// One slot back to its created state. Both halves of each ping-pong pair are cleared, so the slot reads zeros
+// whichever half is current; no other slot's bytes are touched.
+void rt_reset_stream(Ctx& c, RtState& s, int b, hipStream_t st) {
+  (void)c;
+  if (b < 0 || b >= s.B) throw Error(RVCX_E_INVALID, "stream: stream_index out of range");
+  auto zero = [&](DevBuf& d, size_t row_bytes) {
+    RVCX_HIP(hipMemsetAsync(static_cast<char*>(d.p) + (size_t)b * row_bytes, 0, row_bytes, st));
+  };
+  for (int i = 0; i < 2; ++i) {
+    zero(s.abuf[i], sizeof(float) * s.abuf_n);
+    zero(s.cbuf[i], sizeof(float) * s.conv16);
+    zero(s.pbuf[i], sizeof(int) * s.pbuf_n);
+    zero(s.fbuf[i], sizeof(float) * s.pbuf_n);
+  }
+  if (s.cross48 > 0) zero(s.sola, sizeof(float) * s.cross48);
+}
+
+void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts* opts,
+                const uint8_t* active, const float* eps_z, const float* eps_src, uint64_t seed, float* out48,
+                float* vol_out, int* offs_out, hipStream_t st) {
   const int B = s.B, E = c.scfg.emb_dim, upp = c.scfg.upp(), I = c.scfg.I;
+  // the active slots in slot order are the compact rows
+  std::vector<int> slot2row(B, -1), row2slot;
   for (int b = 0; b < B; ++b)
+    if (!active || active[b]) {
+      slot2row[b] = (int)row2slot.size();
+      row2slot.push_back(b);
+    }
+  const int Ba = (int)row2slot.size();
+  const bool all = Ba == B;
+  const bool guided = c.scfg.f0;  // no get_f0, pitch or protect without pitch guidance (pipeline.py:242-293)
+  int n_ret = 0, n_prop = 0;
+  bool any_tune = false, any_rms = false;
+  for (int r = 0; r < Ba; ++r) {
+    const int b = row2slot[r];
+    const rvcx_rt_opts& o = opts[b];
     if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "stream: sid out of range");
-  if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "stream: index_rate > 0 but no feature index loaded");
-  if (o.gen_precision < 0 || o.gen_precision > 1)
-    throw Error(RVCX_E_INVALID, "stream: gen_precision must be 0 (fp32) or 1 (fp16 generator)");
-  if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "stream: index dimension mismatch");
+    if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "stream: index_rate > 0 but no feature index loaded");
+    if (o.gen_precision < 0 || o.gen_precision > 1)
+      throw Error(RVCX_E_INVALID, "stream: gen_precision must be 0 (fp32) or 1 (fp16 generator)");
+    if (o.gen_precision != opts[row2slot[0]].gen_precision)
+      throw Error(RVCX_E_INVALID, "stream: the active streams of one hop must agree on gen_precision");
+    if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "stream: index dimension mismatch");
+    n_ret += o.index_rate > 0 ? 1 : 0;
+    any_tune |= o.f0_autotune != 0;
+    n_prop += (!o.f0_autotune && o.proposed_pitch) ? 1 : 0;
+    any_rms |= o.volume_envelope != 1.0;
+  }
+  if (!all && eps_src && c.scfg.vocoder != 0)
+    throw Error(RVCX_E_INVALID, "stream: injected source noise with idle slots needs the HiFi-GAN-NSF noise layout");
+  if (Ba == 0) {  // nobody took part: zero outputs, no state touched
+    RVCX_HIP(hipMemsetAsync(out48, 0, sizeof(float) * (size_t)B * s.block48, st));
+    if (vol_out) RVCX_HIP(hipMemsetAsync(vol_out, 0, sizeof(float) * B, st));
+    if (offs_out) RVCX_HIP(hipMemsetAsync(offs_out, 0, sizeof(int) * B, st));
+    return;
+  }
+  const int gen_precision = opts[row2slot[0]].gen_precision;
+  const int T = s.feat;
+  // the hop's plan: per-row options, synthesizer lengths / sids, slot map -- one upload
+  const RowPlan P(B);
+  std::vector<char> plan(P.bytes, 0);
+  auto at = [&](size_t off) { return plan.data() + off; };
+  double* h_fac = reinterpret_cast<double*>(at(P.factor));
+  double* h_str = reinterpret_cast<double*>(at(P.strength));
+  float* h_prot = reinterpret_cast<float*>(at(P.protect));
+  float* h_rate = reinterpret_cast<float*>(at(P.rate));
+  float* h_omr = reinterpret_cast<float*>(at(P.one_minus_rate));
+  float* h_rms = reinterpret_cast<float*>(at(P.rms));
+  int* h_tune = reinterpret_cast<int*>(at(P.autotune));
+  int* h_usep = reinterpret_cast<int*>(at(P.use_protect));
+  int* h_seqs = reinterpret_cast<int*>(at(P.seqs));
+  int32_t* h_meta = reinterpret_cast<int32_t*>(at(P.meta));
+  std::memcpy(at(P.slot2row), slot2row.data(), sizeof(int) * B);
+  std::memcpy(at(P.row2slot), row2slot.data(), sizeof(int) * Ba);
+  for (int r = 0, k = 0; r < Ba; ++r) {
+    const int b = row2slot[r];
+    const rvcx_rt_opts& o = opts[b];
+    // autotune replaces the shift (pipeline.py:157-158); a proposed key is added after the sync below
+    h_fac[r] = o.f0_autotune ? 1.0 : std::pow(2.0, o.f0_up_key / 12.0);
+    h_str[r] = o.f0_autotune_strength;
+    h_tune[r] = o.f0_autotune ? 1 : 0;
+    h_prot[r] = o.protect;
+    h_usep[r] = (guided && o.protect < 0.5f) ? 1 : 0;
+    // torch: npy * index_rate + (1 - index_rate) * feats, python scalars cast to float32 (1 - r in double)
+    h_rate[r] = (float)o.index_rate;
+    h_omr[r] = (float)(1.0 - o.index_rate);
+    if (o.index_rate > 0) h_seqs[k++] = r;
+    h_rms[r] = (float)o.volume_envelope;
+    h_meta[r] = T;
+    h_meta[B + r] = sids[b];
+  }
+  char* dplan = static_cast<char*>(s.rows.p);
+  // A copy from pageable memory holds the host until it is staged. With idle slots the first kernel reads the slot
+  // map, so the plan goes first; with every slot active nothing reads it before the f0 network is queued, and the
+  // copy is issued behind that, where the device has work to do meanwhile.
+  auto upload_plan = [&] {
+    RVCX_HIP(hipMemcpyAsync(dplan, plan.data(), P.bytes, hipMemcpyHostToDevice, st));
+  };
+  if (!all) upload_plan();
+  const double* d_fac = reinterpret_cast<const double*>(dplan + P.factor);
+  const int32_t* dmeta = reinterpret_cast<const int32_t*>(dplan + P.meta);
+  const int* d_s2r = all ? nullptr : reinterpret_cast<const int*>(dplan + P.slot2row);
+  const int* d_r2s = all ? nullptr : reinterpret_cast<const int*>(dplan + P.row2slot);
   const int nxt = 1 - s.cur;
-  // 1. input resample 48k -> 16k, circular buffers, RMS gate (core.py:227-267)
+  // 1. input resample 48k -> 16k, circular buffers, RMS gate (core.py:227-267); idle slots carry their state over
   float* in16 = c.buf<float>("rt.in16", (size_t)B * s.n16, st);
   check(rt_resample(in48, s.block48, s.block48, static_cast<const float*>(s.d_kin.p), s.kin.K, s.kin.width, s.kin.orig,
-                    s.kin.nw, in16, s.n16, s.n16, nullptr, B, st),
+                    s.kin.nw, in16, s.n16, s.n16, nullptr, d_s2r, B, st),
         "rt_resample_in");
+  float* conv_rows = all ? nullptr : c.buf<float>("rt.conv", (size_t)Ba * s.conv16, st);
   check(rt_ingest(in16, s.n16, static_cast<float*>(s.abuf[s.cur].p), static_cast<float*>(s.abuf[nxt].p), s.abuf_n,
                   static_cast<float*>(s.cbuf[s.cur].p), static_cast<float*>(s.cbuf[nxt].p), s.conv16, s.sensitivity,
-                  static_cast<float*>(s.vol.p), static_cast<float*>(s.volsq.p), static_cast<int*>(s.gate.p), B, st),
+                  static_cast<float*>(s.vol.p), static_cast<float*>(s.volsq.p), static_cast<int*>(s.gate.p), d_s2r,
+                  conv_rows, B, st),
         "rt_ingest");
-  const float* conv = static_cast<const float*>(s.cbuf[nxt].p);
+  // the B_act convert buffers the networks see: the state itself when every slot is active
+  const float* conv = all ? static_cast<const float*>(s.cbuf[nxt].p) : conv_rows;
   // 2. f0 on the convert buffer (pipeline.py:233-245 -> get_f0 :122-212)
   const int nf = s.conv16 - s.silence_front;
   const int F = 1 + nf / 160;
   if (F > s.pbuf_n) throw Error(RVCX_E_SHAPE, "stream: f0 track longer than the pitch buffer");
-  double* f0 = c.buf<double>("rt.f0", (size_t)B * F, st);
+  double* f0 = c.buf<double>("rt.f0", (size_t)Ba * F, st);
   const int64_t L = hubert_frames(s.conv16);
-  float* feats = c.buf<float>("rt.feats", (size_t)B * L * E, st);
+  float* feats = c.buf<float>("rt.feats", (size_t)Ba * L * E, st);
   hipStream_t ax = fork_aux(c, st);  // batched HuBERT beside the batched f0 network (pipeline.py:233-254)
-  hubert_forward_b(c, conv, s.conv16, s.conv16, B, hubert_version_for(c), feats, L, ax);
-  const bool guided = c.scfg.f0;  // no get_f0, pitch or protect without pitch guidance (pipeline.py:242-293)
+  hubert_forward_b(c, conv, s.conv16, s.conv16, Ba, hubert_version_for(c), feats, L, ax);
   if (guided) {
   if (s.f0_method == 1) {  // the raw local_argmax track (pipeline.py:147-155), F = nf / 160 + 1 frames as RMVPE's
     if (!c.ready[RVCX_MODEL_FCPE] || c.fcfg.sr != 16000 || c.fcfg.hop != 160)
       throw Error(RVCX_E_STATE, "stream: the FCPE model this group was created with has been replaced");
-    if (fcpe_forward_b(c, conv + s.silence_front, nf, s.conv16, B, s.fcpe_thr, 0, f0, F, nullptr, st) != F)
+    if (fcpe_forward_b(c, conv + s.silence_front, nf, s.conv16, Ba, s.fcpe_thr, 0, f0, F, nullptr, st) != F)
       throw Error(RVCX_E_SHAPE, "stream: FCPE frame count differs from the pitch track's");
   } else {
-    rmvpe_forward_b(c, conv + s.silence_front, nf, s.conv16, B, 0.03f, f0, F, nullptr, st);
+    rmvpe_forward_b(c, conv + s.silence_front, nf, s.conv16, Ba, 0.03f, f0, F, nullptr, st);
   }
-  std::vector<double> fac(B, std::pow(2.0, o.f0_up_key / 12.0));
-  if (o.f0_autotune) {
-    check(f0_autotune(f0, B * F, o.f0_autotune_strength, 0, st), "f0_autotune");
-    std::fill(fac.begin(), fac.end(), 1.0);  // autotune replaces the shift (pipeline.py:157-158)
-  } else if (o.proposed_pitch) {
-    std::vector<double> h((size_t)B * F);
-    RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+  }
+  if (all) upload_plan();
+  if (guided) {
+  if (any_tune)  // rows without autotune keep their f0 bits
+    check(f0_autotune_rows(f0, F, reinterpret_cast<const double*>(dplan + P.strength),
+                           reinterpret_cast<const int*>(dplan + P.autotune), Ba, st),
+          "f0_autotune");
+  if (n_prop > 0) {  // the proposed key is a host median (pipeline.py:159-183): only the asking rows come back
+    std::vector<double> h((size_t)Ba * F);
+    for (int r = 0; r < Ba;) {
+      auto asks = [&](int q) { return !opts[row2slot[q]].f0_autotune && opts[row2slot[q]].proposed_pitch; };
+      if (!asks(r)) {
+        ++r;
+        continue;
+      }
+      int e = r + 1;
+      while (e < Ba && asks(e)) ++e;  // one copy per run of neighbouring rows
+      RVCX_HIP(hipMemcpyAsync(h.data() + (size_t)r * F, f0 + (size_t)r * F, sizeof(double) * (size_t)(e - r) * F,
+                              hipMemcpyDeviceToHost, st));
+      r = e;
+    }
     RVCX_HIP(hipStreamSynchronize(st));
     c.check_device_status();
-    for (int b = 0; b < B; ++b) {
-      std::vector<double> one(h.begin() + (size_t)b * F, h.begin() + (size_t)(b + 1) * F);
-      fac[b] = std::pow(2.0, (o.f0_up_key + proposed_key(one, o.proposed_pitch_threshold)) / 12.0);
+    for (int r = 0; r < Ba; ++r) {
+      const rvcx_rt_opts& o = opts[row2slot[r]];
+      if (o.f0_autotune || !o.proposed_pitch) continue;
+      std::vector<double> one(h.begin() + (size_t)r * F, h.begin() + (size_t)(r + 1) * F);
+      h_fac[r] = std::pow(2.0, (o.f0_up_key + proposed_key(one, o.proposed_pitch_threshold)) / 12.0);
     }
+    RVCX_HIP(hipMemcpyAsync(dplan + P.factor, h_fac, sizeof(double) * Ba, hipMemcpyHostToDevice, st));
   }
-  RVCX_HIP(hipMemcpyAsync(s.factor.p, fac.data(), sizeof(double) * B, hipMemcpyHostToDevice, st));
-  check(rt_pitch(f0, F, static_cast<const double*>(s.factor.p), static_cast<const int*>(s.pbuf[s.cur].p),
-                 static_cast<int*>(s.pbuf[nxt].p), static_cast<const float*>(s.fbuf[s.cur].p),
-                 static_cast<float*>(s.fbuf[nxt].p), s.pbuf_n, B, st),
+  check(rt_pitch(f0, F, d_fac, static_cast<const int*>(s.pbuf[s.cur].p), static_cast<int*>(s.pbuf[nxt].p),
+                 static_cast<const float*>(s.fbuf[s.cur].p), static_cast<float*>(s.fbuf[nxt].p), s.pbuf_n, d_s2r, B,
+                 st),
         "rt_pitch");
+  } else if (!all) {  // no pitch track to write, but an idle slot's (unused) pitch state still follows the flip
+    RVCX_HIP(hipMemcpyAsync(s.pbuf[nxt].p, s.pbuf[s.cur].p, s.pbuf[nxt].bytes, hipMemcpyDeviceToDevice, st));
+    RVCX_HIP(hipMemcpyAsync(s.fbuf[nxt].p, s.fbuf[s.cur].p, s.fbuf[nxt].bytes, hipMemcpyDeviceToDevice, st));
   }
-  // 3. HuBERT over the B convert buffers (pipeline.py:248-254), rows [B][L][E]
+  // 3. HuBERT over the B_act convert buffers (pipeline.py:248-254), rows [B_act][L][E]
   join_aux(c, st, ax);
-  // 4. index retrieval of rows skip_head // 2 .. (pipeline.py:264-268, :336-352)
+  // 4. index retrieval of rows skip_head // 2 .. (pipeline.py:264-268, :336-352): one search over every row that
+  // retrieves, each blended at its own rate; the rest of the features is a plain copy
   const float* fx = feats;
-  if (o.index_rate > 0) {
-    float* fr = c.buf<float>("rt.feats_idx", (size_t)B * L * E, st);
-    const int64_t off = s.skip_head / 2;
-    for (int b = 0; b < B; ++b) {
-      const float* src = feats + (size_t)b * L * E;
-      float* dst = fr + (size_t)b * L * E;
-      if (off > 0) RVCX_HIP(hipMemcpyAsync(dst, src, sizeof(float) * off * E, hipMemcpyDeviceToDevice, st));
-      index_retrieve(c, src + off * E, L - off, E, o.index_rate, dst + off * E, st);
-    }
+  if (n_ret > 0) {
+    float* fr = c.buf<float>("rt.feats_idx", (size_t)Ba * L * E, st);
+    RVCX_HIP(hipMemcpyAsync(fr, feats, sizeof(float) * (size_t)Ba * L * E, hipMemcpyDeviceToDevice, st));
+    index_retrieve_rows(c, feats, L, s.skip_head / 2, E, n_ret, reinterpret_cast<const int*>(dplan + P.seqs),
+                        reinterpret_cast<const float*>(dplan + P.rate),
+                        reinterpret_cast<const float*>(dplan + P.one_minus_rate), fr, st);
     fx = fr;
   }
   // 5. x2 upsample [:p_len] + protect; pitch tails (pipeline.py:270-293)
-  const int T = s.feat;
-  float* phone = c.buf<float>("rt.phone", (size_t)B * T * E, st);
-  int32_t* pitch = c.buf<int32_t>("rt.pitch", (size_t)B * T, st);
-  float* pitchf = c.buf<float>("rt.pitchf", (size_t)B * T, st);
+  float* phone = c.buf<float>("rt.phone", (size_t)Ba * T * E, st);
+  int32_t* pitch = c.buf<int32_t>("rt.pitch", (size_t)Ba * T, st);
+  float* pitchf = c.buf<float>("rt.pitchf", (size_t)Ba * T, st);
   const double formant = std::ceil(s.return_length * 1.0);
   const float pscale = (float)(formant / (double)s.return_length);
-  check(rt_up2(fx, feats, (int)L, E, phone, T, static_cast<const float*>(s.fbuf[nxt].p), s.pbuf_n, pscale, o.protect,
-               (guided && o.protect < 0.5f) ? 1 : 0, pitch, static_cast<const int*>(s.pbuf[nxt].p), pitchf, B, st),
+  check(rt_up2(fx, feats, (int)L, E, phone, T, static_cast<const float*>(s.fbuf[nxt].p), s.pbuf_n, pscale,
+               reinterpret_cast<const float*>(dplan + P.protect), reinterpret_cast<const int*>(dplan + P.use_protect),
+               pitch, static_cast<const int*>(s.pbuf[nxt].p), pitchf, d_r2s, Ba, st),
         "rt_up2");
-  // 6. one batched Synthesizer.infer over the B streams (pipeline.py:295-297), clip (:93)
-  std::vector<int32_t> meta(2 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    meta[b] = T;
-    meta[B + b] = sids[b];
-  }
-  int32_t* dmeta = static_cast<int32_t*>(s.meta.p);
-  RVCX_HIP(hipMemcpyAsync(dmeta, meta.data(), sizeof(int32_t) * meta.size(), hipMemcpyHostToDevice, st));
+  // 6. one batched Synthesizer.infer over the B_act rows (pipeline.py:295-297), clip (:93). Injected noise is
+  // indexed by slot, so with idle slots the active slots' rows are gathered first.
   const int64_t n_model = (int64_t)T * upp;
-  float* model = c.buf<float>("rt.model", (size_t)B * n_model, st);
+  if (!all && eps_z) {
+    float* ez = c.buf<float>("rt.eps_z", (size_t)Ba * I * T, st);
+    check(gather_rows(eps_z, I * T, d_r2s, ez, Ba, I * T, st), "rt_eps_z");
+    eps_z = ez;
+  }
+  if (!all && eps_src) {
+    float* es = c.buf<float>("rt.eps_src", (size_t)Ba * n_model, st);
+    check(gather_rows(eps_src, (int)n_model, d_r2s, es, Ba, (int)n_model, st), "rt_eps_src");
+    eps_src = es;
+  }
+  float* model = c.buf<float>("rt.model", (size_t)Ba * n_model, st);
   {
     ScopedFullLengths full(c);  // every stream's hop is T frames (meta above)
-    synth_forward(c, B, T, phone, dmeta, guided ? pitch : nullptr, guided ? pitchf : nullptr, dmeta + B, eps_z,
-                  eps_src, seed, model, nullptr, nullptr, st, o.gen_precision);
+    synth_forward(c, Ba, T, phone, dmeta, guided ? pitch : nullptr, guided ? pitchf : nullptr, dmeta + B, eps_z,
+                  eps_src, seed, model, nullptr, nullptr, st, gen_precision);
   }
-  (void)I;
-  check(rt_clip(model, n_model, (int)n_model, B, st), "rt_clip");
-  if (o.volume_envelope != 1.0) {  // pipeline.py:299-307 (source = the 16 kHz convert buffer)
+  check(rt_clip(model, n_model, (int)n_model, Ba, st), "rt_clip");
+  if (any_rms) {  // pipeline.py:299-307 (source = the 16 kHz convert buffer); rows at exactly 1 are skipped
     const int n1 = rms_frame_count(s.conv16, 16000), n2 = rms_frame_count(n_model, s.tgt_sr);
-    float* ws = c.buf<float>("rt.rms", (size_t)(n1 + n2), st);
-    for (int b = 0; b < B; ++b)
-      check(change_rms_f32src(conv + (size_t)b * s.conv16, s.conv16, 16000, model + (size_t)b * n_model, n_model,
-                              s.tgt_sr, (float)o.volume_envelope, ws, st),
-            "change_rms");
+    float* ws = c.buf<float>("rt.rms", (size_t)Ba * (n1 + n2), st);
+    check(change_rms_f32src_rows(conv, s.conv16, s.conv16, 16000, model, n_model, n_model, s.tgt_sr,
+                                 reinterpret_cast<const float*>(dplan + P.rms), ws, Ba, st),
+          "change_rms");
   }
   // 7. * sqrt(vol) [-> 48 kHz], SOLA crossfade (core.py:324, :404-451)
   const float* a48 = model;
@@ -325,9 +473,9 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   const float* scale = static_cast<const float*>(s.volsq.p);
   if (!s.out_identity) {
     const int64_t n48 = (int64_t)std::ceil((double)s.kout.nw * n_model / s.kout.orig);
-    float* r48 = c.buf<float>("rt.model48", (size_t)B * n48, st);
+    float* r48 = c.buf<float>("rt.model48", (size_t)Ba * n48, st);
     check(rt_resample(model, n_model, (int)n_model, static_cast<const float*>(s.d_kout.p), s.kout.K, s.kout.width,
-                      s.kout.orig, s.kout.nw, r48, n48, (int)n48, scale, B, st),
+                      s.kout.orig, s.kout.nw, r48, n48, (int)n48, scale, nullptr, Ba, st),
           "rt_resample_out");
     a48 = r48;
     lda = n48;
@@ -335,7 +483,7 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   }
   check(rt_sola(a48, lda, scale, static_cast<const int*>(s.gate.p), static_cast<float*>(s.sola.p), s.cross48,
                 s.sola48, static_cast<const float*>(s.fade_in.p), out48, s.block48,
-                offs_out ? offs_out : static_cast<int*>(s.offs.p), B, st),
+                offs_out ? offs_out : static_cast<int*>(s.offs.p), d_s2r, B, st),
         "rt_sola");
   if (vol_out) RVCX_HIP(hipMemcpyAsync(vol_out, s.vol.p, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
   s.cur = nxt;

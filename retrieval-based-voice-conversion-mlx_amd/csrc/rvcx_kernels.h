@@ -357,6 +357,8 @@ hipError_t peak_normalize(const float* src, float* dst, long long n, float* ws, 
 size_t peak_normalize_ws_floats(int B);
 // Pipeline.get_f0 / Pipeline.pipeline host DSP moved on device (aux_kernels.hip)
 hipError_t f0_autotune(double* f0, int F, double strength, int skip_unvoiced, hipStream_t s);
+// every frame of the rows of f0 [B][F] with on[b] != 0, each at its own strength[b]; the other rows are not written
+hipError_t f0_autotune_rows(double* f0, int F, const double* strength, const int* on, int B, hipStream_t s);
 hipError_t split_points(const double* x, long long n, int window, long long t_center, long long t_query,
                         double* sum_ws, long long* ts, int nts, hipStream_t s);
 int rms_frame_count(long long n, int sr);
@@ -380,23 +382,40 @@ size_t ivf_ws_floats(long long n, long long nlist, int nprobe);
 // dist_out/ids_out [n][k] (optional); out [n][d] = retrieval blend (optional)
 hipError_t ivf_search(const IvfView& v, const float* x, long long n, int k, float* dist_out, long long* ids_out,
                       float rate, float one_minus_rate, float* out, float* ws, hipStream_t s);
+// The retrieval blend for a chosen set of sequences of a batch x / out [B][L][d] in one search: query q is row
+// off + q % (L - off) of sequence seqs[q / (L - off)], blended at that sequence's own rate[seq] / one_minus_rate[seq]
+// (device arrays indexed by sequence). Rows that are no query are not written. n_seq * (L - off) queries.
+struct IvfRows {
+  const int* seqs = nullptr;  // null: query q is row q of x / out (ivf_search)
+  const float* rate = nullptr;
+  const float* one_minus_rate = nullptr;
+  int L = 0, off = 0;
+};
+hipError_t ivf_retrieve_rows(const IvfView& v, const float* x, const IvfRows& rows, int n_seq, float* out, float* ws,
+                             hipStream_t s);
 
-// streaming (stream.hip): B streams of one geometry per launch
+// streaming (stream.hip): B slots of one geometry per launch. slot2row [B] (-1 = idle this hop) / row2slot [B_act]
+// map a group's slots to the compact rows the networks run on; null = identity (stream.hip's header)
 hipError_t rt_resample(const float* x, long long ldx, int n_in, const float* ker, int K, int width, int orig, int nw,
-                       float* y, long long ldy, int n_out, const float* pre, int B, hipStream_t s);
+                       float* y, long long ldy, int n_out, const float* pre, const int* slot2row, int B,
+                       hipStream_t s);
 hipError_t rt_ingest(const float* in16, int n16, const float* abuf_old, float* abuf_new, int na, const float* cbuf_old,
-                     float* cbuf_new, int nc, double sensitivity, float* vol, float* volsq, int* gate, int B,
-                     hipStream_t s);
+                     float* cbuf_new, int nc, double sensitivity, float* vol, float* volsq, int* gate,
+                     const int* slot2row, float* cbuf_rows, int B, hipStream_t s);
 hipError_t rt_pitch(const double* f0, int F, const double* factor, const int* pold, int* pnew, const float* fold,
-                    float* fnew, int nbuf, int B, hipStream_t s);
+                    float* fnew, int nbuf, const int* slot2row, int B, hipStream_t s);
 hipError_t rt_up2(const float* feats, const float* feats0, int L, int D, float* phone, int T, const float* pitchf_buf,
-                  int nbuf, float pscale, float protect, int use_protect, int* pitch_out, const int* pitch_buf,
-                  float* pitchf_out, int B, hipStream_t s);
+                  int nbuf, float pscale, const float* protect, const int* use_protect, int* pitch_out,
+                  const int* pitch_buf, float* pitchf_out, const int* row2slot, int B, hipStream_t s);
 hipError_t rt_clip(float* x, long long ld, int n, int B, hipStream_t s);
 hipError_t rt_sola(const float* audio, long long lda, const float* volsq, const int* gate, float* sola_buf, int cf,
-                   int search, const float* fade_in, float* out, int block, int* offs, int B, hipStream_t s);
-hipError_t change_rms_f32src(const float* src, long long n_src, int sr_src, float* y, long long n_y, int sr_y,
-                             float rate, float* ws, hipStream_t s);
+                   int search, const float* fade_in, float* out, int block, int* offs, const int* slot2row, int B,
+                   hipStream_t s);
+// change_rms with a float32 source for B rows in one launch set: per-row rate [B] (exactly 1 = row untouched),
+// ws [B][n1 + n2] floats (n = rms_frame_count of either side)
+hipError_t change_rms_f32src_rows(const float* src, long long ld_src, long long n_src, int sr_src, float* y,
+                                  long long ld_y, long long n_y, int sr_y, const float* rate, float* ws, int B,
+                                  hipStream_t s);
 
 // second-order-section filtfilt (iir_scan.hip): per-section tables in one device buffer
 struct SosPlan {

@@ -27,7 +27,7 @@ EXPORTS = [
     "rvcx_f0_autotune", "rvcx_rmvpe_decode", "rvcx_profile", "rvcx_profile_read", "rvcx_profile_read_ex", "rvcx_index_load",
     "rvcx_index_unload", "rvcx_index_info", "rvcx_index_set_nprobe", "rvcx_index_search", "rvcx_index_reconstruct_n",
     "rvcx_index_retrieve", "rvcx_rt_default_desc", "rvcx_rt_default_opts", "rvcx_rt_create", "rvcx_rt_destroy",
-    "rvcx_rt_geometry", "rvcx_rt_reset", "rvcx_rt_process", "rvcx_hubert_batch", "rvcx_rmvpe_batch",
+    "rvcx_rt_geometry", "rvcx_rt_reset", "rvcx_rt_process", "rvcx_rt_process_v", "rvcx_rt_reset_stream", "rvcx_hubert_batch", "rvcx_rmvpe_batch",
     "rvcx_pipeline_batch", "rvcx_set_highpass_sos", "rvcx_highpass_pad", "rvcx_device_status", "rvcx_index_parse",
     "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
@@ -204,6 +204,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_rt_geometry": (i32, [vp, P(i64)]),
         "rvcx_rt_reset": (i32, [vp, vp, vp]),
         "rvcx_rt_process": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), vp, vp, u64, vp, vp, vp, vp]),
+        "rvcx_rt_process_v": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), P(ctypes.c_uint8), vp, vp, u64, vp, vp,
+                                    vp, vp]),
+        "rvcx_rt_reset_stream": (i32, [vp, vp, i32, vp]),
         "rvcx_device_status": (i32, [vp, vp]),
         "rvcx_index_parse": (i32, [vp, i64, P(i64), P(i64), P(i64), P(i64), ctypes.c_char_p, i64]),
         "rvcx_set_conv_math": (i32, [vp, i32]),

@@ -6,10 +6,14 @@ Mirrors rvc/realtime/core.py (``VoiceChanger`` :329-484 with ``process_audio`` /
 PyTorch path's behaviour is the contract.
 
 ``StreamGroup`` converts B concurrent streams of one geometry per hop in one device call
-(``rvcx_rt_process``: resample, circular buffers, RMS gate, RMVPE or FCPE (``f0_method``), HuBERT, retrieval, one batched
+(``rvcx_rt_process_v``: resample, circular buffers, RMS gate, RMVPE or FCPE (``f0_method``), HuBERT, retrieval, one batched
 Synthesizer.infer, SOLA crossfade -- all HIP kernels). ``VoiceChanger`` is the one-stream, numpy-in /
 numpy-out object of the reference. Audio I/O, VAD, noise gate and pedalboard effects are not part of
 this path.
+
+A group's B slots are independent users: every hop takes one ``RtOpts`` for all of them or one per slot (each slot its
+own ``on_request`` arguments), a set of slots may sit a hop out (``active``), and ``reset(stream=i)`` clears one slot
+for a newcomer without touching the others.
 """
 from __future__ import annotations
 
@@ -37,6 +41,40 @@ GEOMETRY_FIELDS = ("n_streams", "block48", "block16", "convert16", "frames", "sk
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def hop_arguments(n_streams: int, opts, active=None):
+    """The per-slot arguments of one hop, checked on the host: ``opts`` one ``RtOpts`` (every slot) or a sequence of
+    ``n_streams`` of them, ``active`` None (every slot) or a sequence of ``n_streams`` booleans. Returns (a ctypes
+    array of n_streams RtOpts, a ctypes uint8 array or None). ValueError for a wrong length or when the active slots
+    disagree on gen_precision (one hop runs one generator precision)."""
+    if isinstance(opts, _lib.RtOpts):
+        each = [opts] * n_streams
+    else:
+        each = list(opts)
+        if len(each) != n_streams:
+            raise ValueError(f"opts has {len(each)} entries for {n_streams} streams")
+        if not all(isinstance(o, _lib.RtOpts) for o in each):
+            raise ValueError("opts must be RtOpts (StreamGroup.opts) or a sequence of them")
+    act = None
+    if active is not None:
+        flags = [bool(a) for a in active]
+        if len(flags) != n_streams:
+            raise ValueError(f"active has {len(flags)} entries for {n_streams} streams")
+        act = (ctypes.c_uint8 * n_streams)(*[int(a) for a in flags])
+    else:
+        flags = [True] * n_streams
+    precisions = {int(o.gen_precision) for o, a in zip(each, flags) if a}
+    if len(precisions) > 1:
+        raise ValueError("the active streams of one hop must agree on gen_precision")
+    return (_lib.RtOpts * n_streams)(*each), act  # the array holds copies
+
+
+def check_slot(n_streams: int, stream) -> int:
+    """A slot index of a group of n_streams, or ValueError."""
+    if isinstance(stream, bool) or int(stream) != stream or not 0 <= int(stream) < n_streams:
+        raise ValueError(f"stream {stream!r} is not a slot of a {n_streams}-stream group")
+    return int(stream)
 
 
 class StreamGroup:
@@ -87,9 +125,16 @@ class StreamGroup:
         except Exception:
             pass
 
-    def reset(self):
-        self.engine._check(self.engine.lib.rvcx_rt_reset(self.engine.ctx, self.handle, self.engine.stream()),
-                           "rt_reset")
+    def reset(self, stream: Optional[int] = None):
+        """Clear the whole group (``stream=None``) or one slot: its audio / convert / pitch buffers and SOLA tail go
+        back to zeros, asynchronously on the current stream, and no other slot is touched -- for a user who takes over
+        a slot another one left."""
+        eng = self.engine
+        if stream is None:
+            eng._check(eng.lib.rvcx_rt_reset(eng.ctx, self.handle, eng.stream()), "rt_reset")
+            return
+        slot = check_slot(self.n_streams, stream)
+        eng._check(eng.lib.rvcx_rt_reset_stream(eng.ctx, self.handle, slot, eng.stream()), "rt_reset_stream")
 
     def opts(self, f0_up_key=0, index_rate=0.5, protect=0.5, volume_envelope=1.0, f0_autotune=False,
              f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0,
@@ -107,18 +152,24 @@ class StreamGroup:
         o.gen_precision = {"fp32": 0, "fp16": 1}[gen_precision]
         return o
 
-    def process(self, audio_in, opts: Optional[_lib.RtOpts] = None, eps_z=None, eps_src=None, seed: int = 0):
-        """One hop for every stream: audio_in [B, block48] @48 kHz (device tensor or numpy) ->
-        (out [B, block48] device tensor, vol [B] device tensor). Asynchronous on the current stream."""
+    def process(self, audio_in, opts=None, eps_z=None, eps_src=None, seed: int = 0, active=None):
+        """One hop: audio_in [B, block48] @48 kHz (device tensor or numpy) -> (out [B, block48] device tensor,
+        vol [B] device tensor). Asynchronous on the current stream.
+
+        opts: one ``RtOpts`` for every stream, or a sequence of B (each stream its own on_request arguments; only
+        gen_precision must agree among the active streams). active: a sequence of B booleans, None = all. For an idle
+        slot the hop did not happen: its input row is not read, its state is kept, and its out row, vol and SOLA offset
+        are zero. eps_z / eps_src rows are indexed by slot. ValueError for a wrong length or mixed gen_precision."""
         eng = self.engine
         t = eng.torch
+        arr, act = hop_arguments(self.n_streams, opts if opts is not None else self.opts(), active)
         x = eng._dev(audio_in, t.float32).reshape(self.n_streams, self.block_frame)
         ez = None if eps_z is None else eng._dev(eps_z, t.float32)
         es = None if eps_src is None else eng._dev(eps_src, t.float32)
-        o = opts if opts is not None else self.opts()
-        eng._check(eng.lib.rvcx_rt_process(eng.ctx, self.handle, x.data_ptr(), self.sids, ctypes.byref(o), _ptr(ez),
-                                           _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), self.out.data_ptr(),
-                                           self.vol.data_ptr(), self.offs.data_ptr(), eng.stream()), "rt_process")
+        eng._check(eng.lib.rvcx_rt_process_v(eng.ctx, self.handle, x.data_ptr(), self.sids, arr, act, _ptr(ez),
+                                             _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+                                             self.out.data_ptr(), self.vol.data_ptr(), self.offs.data_ptr(),
+                                             eng.stream()), "rt_process")
         return self.out, self.vol
 
 
