@@ -288,7 +288,9 @@ int rvcx_pipeline_default_opts(rvcx_pipeline_opts* opts);
  * ((n + 2 t_pad)/160 + n/t_center + 2) * upp is always enough). d_eps_z / d_eps_src (optional)
  * hold the injected noise of all chunks back to back ([192][T_i] then [T_i * upp] per chunk);
  * d_f0 (optional) receives the adjusted f0 [1 + (n + 2 t_pad)/160]. The host synchronises the
- * stream once to read the split points (long inputs only) and once for proposed_pitch. */
+ * stream once to read the split points (long inputs only) and once for proposed_pitch.
+ * The HiFi-GAN generator runs only over the frames whose samples the trim keeps, plus its receptive field: the
+ * output is unchanged bit for bit from a full-length run (the trimmed samples were never returned). */
 int rvcx_pipeline_ex(rvcx_ctx* ctx, const double* d_audio, int64_t n, const rvcx_pipeline_opts* opts,
                      const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, int64_t cap,
                      int64_t* n_out, double* d_f0, void* stream);
@@ -299,7 +301,8 @@ int rvcx_pipeline_ex(rvcx_ctx* ctx, const double* d_audio, int64_t n, const rvcx
  * output for utterance b, n_out samples. Noise when injected: d_eps_z [B][inter][T], d_eps_src [B][T*upp].
  * Optional outputs: d_f0 [B][F] the adjusted f0 of each row (as rvcx_pipeline_ex's d_f0), d_hidden [B][F][360] the
  * RMVPE salience each row's f0 was decoded from (RMVPE f0 method only), F = 1 + (n + 2 t_pad)/160. CREPE and FCPE
- * (f0_method 1-3) run per row. */
+ * (f0_method 1-3) run per row. As in rvcx_pipeline_ex the generator skips the frames the trim drops (one window for
+ * all rows); outputs are unchanged bit for bit. */
 int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t lda, int B,
                         const rvcx_pipeline_opts* opts, const int32_t* sids, const float* d_eps_z,
                         const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,

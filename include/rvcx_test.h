@@ -30,6 +30,17 @@ int rvcx_performer_attention_b(rvcx_ctx* ctx, const float* d_q, const float* d_k
 int rvcx_fcpe_mel(rvcx_ctx* ctx, const float* d_audio, int64_t n, float* d_mel, int64_t cap_frames,
                   int64_t* frames_out, void* stream);
 
+/* The generator's output window on (non-zero, the default) or off for this context. The offline pipelines trim
+ * t_pad_tgt samples per side of every chunk and the streaming hop reads only the start of the model's output; with
+ * the window on, the HiFi-GAN generator runs on the kept samples' frames plus its receptive field. Every output is
+ * the same bit for bit either way: the switch exists to show that, and for same-box timing comparisons.
+ * RVCX_DEC_WINDOW=0 (with RVCX_EXPERIMENTAL=1) sets the default off at rvcx_create. */
+int rvcx_set_dec_window(rvcx_ctx* ctx, int on);
+
+/* The generator's one-sided receptive field in input frames for a synthesizer configuration (the margin the output
+ * window keeps per cut side): *frames. Host only, no context. */
+int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames);
+
 #ifdef __cplusplus
 }
 #endif

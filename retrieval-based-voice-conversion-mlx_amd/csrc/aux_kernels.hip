@@ -458,7 +458,7 @@ hipError_t sine_source(const float* f0, int B, int L, int upp, float sr, const f
 constexpr int CP_T = 256, CP_IT = 24;  // C <= 92 at K = 7
 __global__ __launch_bounds__(CP_T) void k_conv_post(const float* __restrict__ x, int T, int C,
                                                     const float* __restrict__ wg, int K, float slope,
-                                                    float* __restrict__ y, float bias) {
+                                                    float* __restrict__ y, float bias, long long y_bs) {
   extern __shared__ float tile[];  // [(CP_T+K-1)][C+1], then w[C*K]
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * CP_T;
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(CP_T) void k_conv_post(const float* __restrict__ x,
   float acc = 0.f;
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < K; ++k) acc = fmaf(tile[(threadIdx.x + k) * ldt + c], w[c * K + k], acc);
-  y[(long long)b * T + t] = tanhf(acc + bias);  // + 0 for the bias-free HiFi-GAN / RefineGAN conv_post
+  y[(long long)b * y_bs + t] = tanhf(acc + bias);  // + 0 for the bias-free HiFi-GAN / RefineGAN conv_post
 }
 // The same conv_post at the HiFi-GAN-NSF / MRF shape (C = 32, K = 7: every RVC v2 rate): C and K at compile time,
 // the lrelu'd tile in LDS with a 36-float row stride (16 consecutive rows' float4 reads hit 64 distinct banks), the
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(CP_T) void k_conv_post(const float* __restrict__ x,
 constexpr int CPF_C = 32, CPF_K = 7, CPF_LD = 36, CPF_ROWS = CP_T + CPF_K - 1;
 __global__ __launch_bounds__(CP_T) void k_conv_post32(const float* __restrict__ x, int T,
                                                       const float* __restrict__ wg, float slope,
-                                                      float* __restrict__ y, float bias) {
+                                                      float* __restrict__ y, float bias, long long y_bs) {
   __shared__ __attribute__((aligned(16))) float tile[CPF_ROWS * CPF_LD];
   __shared__ __attribute__((aligned(16))) float w[CPF_K * CPF_C];  // [k][c]
   const int b = blockIdx.y;
@@ -554,13 +554,15 @@ __global__ __launch_bounds__(CP_T) void k_conv_post32(const float* __restrict__ 
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] = fmaf(xv[e], wv[e], acc[e]);
     }
-  y[(long long)b * T + t] = tanhf(((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias);
+  y[(long long)b * y_bs + t] = tanhf(((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias);
 }
 
 hipError_t conv_post_tanh(const float* x, int B, int T, int C, const float* w, int K, float slope, float* y,
-                          hipStream_t s, float bias) {
+                          hipStream_t s, float bias, long long y_bs) {
+  if (y_bs <= 0) y_bs = T;
   if (C == CPF_C && K == CPF_K && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-    hipLaunchKernelGGL(k_conv_post32, dim3((T + CP_T - 1) / CP_T, B), dim3(CP_T), 0, s, x, T, w, slope, y, bias);
+    hipLaunchKernelGGL(k_conv_post32, dim3((T + CP_T - 1) / CP_T, B), dim3(CP_T), 0, s, x, T, w, slope, y, bias,
+                       y_bs);
     return hipGetLastError();
   }
   // the staged fetch covers (CP_T + K - 1) rows of C / 4 float4 in CP_IT rounds of CP_T threads
@@ -568,7 +570,8 @@ hipError_t conv_post_tanh(const float* x, int B, int T, int C, const float* w, i
       (reinterpret_cast<uintptr_t>(x) & 15) != 0)
     return hipErrorInvalidValue;
   const size_t smem = ((size_t)(CP_T + K - 1) * (C + 1) + (size_t)C * K) * sizeof(float);
-  hipLaunchKernelGGL(k_conv_post, dim3((T + CP_T - 1) / CP_T, B), dim3(CP_T), smem, s, x, T, C, w, K, slope, y, bias);
+  hipLaunchKernelGGL(k_conv_post, dim3((T + CP_T - 1) / CP_T, B), dim3(CP_T), smem, s, x, T, C, w, K, slope, y, bias,
+                     y_bs);
   return hipGetLastError();
 }
 

@@ -290,6 +290,42 @@ void set_i32_once(Ctx& c, const std::string& name, int32_t* p, int32_t v, hipStr
 }
 }  // namespace rvcx
 
+namespace {
+// the synthesizer configuration a descriptor names (rvcx_set_synth_config, rvcx_dec_margin_frames)
+SynthCfg synth_cfg_of(const rvcx_synth_desc* d) {
+  if (!d) throw Error(RVCX_E_INVALID, "null desc");
+  SynthCfg g;
+  g.I = d->inter_channels;
+  g.H = d->hidden_channels;
+  g.F = d->filter_channels;
+  g.n_heads = d->n_heads;
+  g.n_layers = d->n_layers;
+  g.ksize = d->kernel_size;
+  if (d->n_resblocks < 1 || d->n_resblocks > 4 || d->n_dilations < 1 || d->n_dilations > 4)
+    throw Error(RVCX_E_INVALID, "resblock config out of range");
+  g.rb_k.assign(d->resblock_kernel_sizes, d->resblock_kernel_sizes + d->n_resblocks);
+  g.rb_d.clear();
+  for (int j = 0; j < d->n_resblocks; ++j)
+    g.rb_d.emplace_back(d->resblock_dilation_sizes[j], d->resblock_dilation_sizes[j] + d->n_dilations);
+  if (d->n_upsample < 1 || d->n_upsample > 8) throw Error(RVCX_E_INVALID, "n_upsample out of range");
+  g.ups.assign(d->upsample_rates, d->upsample_rates + d->n_upsample);
+  g.up_k.assign(d->upsample_kernel_sizes, d->upsample_kernel_sizes + d->n_upsample);
+  g.C0 = d->upsample_initial_channel;
+  g.n_spk = d->spk_embed_dim;
+  g.gin = d->gin_channels;
+  g.sr = d->sr;
+  g.emb_dim = d->text_enc_hidden_dim;
+  g.f0 = d->no_f0 == 0;
+  g.vocoder = d->vocoder;
+  if (g.vocoder < 0 || g.vocoder > 2) throw Error(RVCX_E_INVALID, "unsupported vocoder id");
+  if (!g.f0 && g.vocoder != 0)
+    throw Error(RVCX_E_INVALID, "models without pitch guidance use the HiFi-GAN decoder only (synthesizers.py:119-139)");
+  if (g.H % g.n_heads || g.I % 2 || g.C0 % (1 << g.ups.size()))
+    throw Error(RVCX_E_INVALID, "inconsistent synthesizer dimensions");
+  return g;
+}
+}  // namespace
+
 extern "C" {
 
 int rvcx_create(rvcx_ctx** out, int device) {
@@ -299,6 +335,7 @@ int rvcx_create(rvcx_ctx** out, int device) {
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return RVCX_E_HIP;
   auto* c = new rvcx_ctx();
   c->device = device;
+  if (const char* e = rvcx_knob("RVCX_DEC_WINDOW")) c->dec_window = std::atoi(e) != 0;  // A/B aid (rvcx_set_dec_window)
   *out = c;
   return RVCX_OK;
 }
@@ -315,36 +352,7 @@ const char* rvcx_last_error(const rvcx_ctx* ctx) { return ctx ? ctx->err.c_str()
 
 int rvcx_set_synth_config(rvcx_ctx* ctx, const rvcx_synth_desc* d) {
   return guard(ctx, [&] {
-    if (!d) throw Error(RVCX_E_INVALID, "null desc");
-    SynthCfg g;
-    g.I = d->inter_channels;
-    g.H = d->hidden_channels;
-    g.F = d->filter_channels;
-    g.n_heads = d->n_heads;
-    g.n_layers = d->n_layers;
-    g.ksize = d->kernel_size;
-    if (d->n_resblocks < 1 || d->n_resblocks > 4 || d->n_dilations < 1 || d->n_dilations > 4)
-      throw Error(RVCX_E_INVALID, "resblock config out of range");
-    g.rb_k.assign(d->resblock_kernel_sizes, d->resblock_kernel_sizes + d->n_resblocks);
-    g.rb_d.clear();
-    for (int j = 0; j < d->n_resblocks; ++j)
-      g.rb_d.emplace_back(d->resblock_dilation_sizes[j], d->resblock_dilation_sizes[j] + d->n_dilations);
-    if (d->n_upsample < 1 || d->n_upsample > 8) throw Error(RVCX_E_INVALID, "n_upsample out of range");
-    g.ups.assign(d->upsample_rates, d->upsample_rates + d->n_upsample);
-    g.up_k.assign(d->upsample_kernel_sizes, d->upsample_kernel_sizes + d->n_upsample);
-    g.C0 = d->upsample_initial_channel;
-    g.n_spk = d->spk_embed_dim;
-    g.gin = d->gin_channels;
-    g.sr = d->sr;
-    g.emb_dim = d->text_enc_hidden_dim;
-    g.f0 = d->no_f0 == 0;
-    g.vocoder = d->vocoder;
-    if (g.vocoder < 0 || g.vocoder > 2) throw Error(RVCX_E_INVALID, "unsupported vocoder id");
-    if (!g.f0 && g.vocoder != 0)
-      throw Error(RVCX_E_INVALID, "models without pitch guidance use the HiFi-GAN decoder only (synthesizers.py:119-139)");
-    if (g.H % g.n_heads || g.I % 2 || g.C0 % (1 << g.ups.size()))
-      throw Error(RVCX_E_INVALID, "inconsistent synthesizer dimensions");
-    ctx->scfg = g;
+    ctx->scfg = synth_cfg_of(d);
     ctx->synth_cfg_set = true;
     ctx->ready[0] = false;
   });
@@ -902,6 +910,7 @@ int rvcx_config_info(const rvcx_ctx* ctx, char* buf, int64_t cap, int64_t* len) 
   j += ", \"conv_math_default\": \"" + std::string(cm ? cm : "h16") + "\"";
   j += ", \"experimental\": " + std::string(experimental_on() ? "true" : "false");
   if (ctx) j += ", \"arena_bytes\": " + std::to_string(ctx->arena_bytes);
+  if (ctx) j += ", \"dec_window\": " + std::string(ctx->dec_window ? "true" : "false");
   j += ", \"env\": {";
   bool first = true;
   for (char** e = environ; e && *e; ++e) {
@@ -925,6 +934,22 @@ int rvcx_config_info(const rvcx_ctx* ctx, char* buf, int64_t cap, int64_t* len) 
     buf[n] = 0;
   }
   return (int64_t)j.size() < cap || !buf ? RVCX_OK : RVCX_E_CAPACITY;
+}
+
+int rvcx_set_dec_window(rvcx_ctx* ctx, int on) {
+  return guard(ctx, [&] { ctx->dec_window = on != 0; });
+}
+
+int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames) {
+  try {
+    if (!frames) return RVCX_E_INVALID;
+    *frames = dec_margin_frames(synth_cfg_of(d));
+    return RVCX_OK;
+  } catch (const Error& e) {
+    return e.code;
+  } catch (...) {
+    return RVCX_E_INVALID;
+  }
 }
 
 int rvcx_set_generator_precision(rvcx_ctx* ctx, int) {

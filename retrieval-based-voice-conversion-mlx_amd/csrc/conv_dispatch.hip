@@ -67,6 +67,10 @@ inline void cfg_tile(int cfg, int& BM, int& BN) {
   BN = t[cfg][1];
 }
 
+// the rows every policy decision below is made for: ConvArgs::plan_T where the caller launches a window of a longer
+// sequence and wants the full-length launch's kernel, tile and ksplit (1-D only), else the launch's own rows
+inline int plan_rows(const ConvArgs& a) { return (a.plan_T > 0 && a.W_out <= 0) ? a.plan_T : a.T_out; }
+
 // weight-streamed split kernel (conv_wsb.hip) tiles: 256x32 for N <= 32, else 128x64 (2 x 2 waves of 64 x 32;
 // RVCX_WCFG_* override). bench_conv on MI355X with the register epilogue (TF/s, vs the LDS-staged split kernel's
 // best tile): C256 k11 174 vs 142, C128 k11 204 vs 160, C128 k7 185 vs 144, C128 k3 124 vs 118, ConvTranspose
@@ -90,7 +94,7 @@ inline int pick_wsb(const ConvArgs& a) {
   if (a.N <= 32) return 24;
   // the wide ConvTranspose phase group of the second upsample (18600 rows x 1280 columns, 2 taps) on 128 x 128 tiles:
   // bench_conv r06a h25 254.6 vs h27 232.2 TF (the first one, 1550 rows x 3072, loses there: 189 vs 206)
-  if (a.taps <= 3 && a.N >= 1024 && a.T_out >= 8192 && a.C_in < 512 && c_long == 0) return 25;
+  if (a.taps <= 3 && a.N >= 1024 && plan_rows(a) >= 8192 && a.C_in < 512 && c_long == 0) return 25;
   if (a.taps <= 3) return 27;
   if (c_long > 0) return c_long;
   return (a.C_in < 256 && a.N >= 128) ? 25 : 23;
@@ -206,17 +210,21 @@ long long conv_plan_splitk(ConvArgs& a, bool two_d) {
   } else {
     cfg_tile(two_d ? pick_cfg<true>(a) : pick_cfg<false>(a), BM, BN);
   }
-  long long mtiles;
+  // the decisions (whether to split, ksplit) are made for plan_rows(a) rows, the slab for the launch's own T_out
+  const int T_plan = two_d ? a.T_out : plan_rows(a);
+  long long mtiles, mtiles_real;
   if (!two_d) {
-    mtiles = (a.T_out + BM - 1) / BM;
+    mtiles = (T_plan + BM - 1) / BM;
+    mtiles_real = (a.T_out + BM - 1) / BM;
   } else {
     const int rw = a.W_out < BM ? a.W_out : BM;
     const int rh = BM / rw;
-    mtiles = (long long)((a.T_out + rh - 1) / rh) * ((a.W_out + rw - 1) / rw);
+    mtiles = mtiles_real = (long long)((a.T_out + rh - 1) / rh) * ((a.W_out + rw - 1) / rw);
   }
   const long long tiles = mtiles * ((a.N + BN - 1) / BN) * a.batch * a.batch_inner;
+  const long long tiles_real = mtiles_real * ((a.N + BN - 1) / BN) * a.batch * a.batch_inner;
   const int iters = ((a.C_in + CK - 1) / CK) * a.taps;
-  const double M = two_d ? (double)a.T_out * a.W_out : (double)a.T_out;
+  const double M = two_d ? (double)a.T_out * a.W_out : (double)T_plan;
   const double flops = 2.0 * M * a.N * (double)a.C_in * a.taps * a.batch * a.batch_inner;
   // split only where the output grid leaves CUs idle AND the contraction is long enough to pay
   // for the extra combine launch (~5-10 us): a tile's (chunk, tap) steps are a serial chain of
@@ -247,7 +255,7 @@ long long conv_plan_splitk(ConvArgs& a, bool two_d) {
   if (ks < 2) return 0;
   a.ksplit = ks;
   a.ws_rows = two_d ? (long long)a.T_out * a.W_out : a.T_out;
-  return std::max((long long)ks * a.ws_rows * a.N * a.batch * a.batch_inner, tiles * ks * BM * BN);
+  return std::max((long long)ks * a.ws_rows * a.N * a.batch * a.batch_inner, tiles_real * ks * BM * BN);
 }
 
 bool conv_wsb_wants(const ConvArgs& a) {
@@ -258,7 +266,7 @@ bool conv_wsb_wants(const ConvArgs& a) {
   // the chip
   constexpr int min_taps = 2, min_tiles = 512, min_n = 64;
   if (a.N < min_n || a.taps < min_taps) return false;
-  const long long tiles = (long long)((a.T_out + 127) / 128) * ((a.N + 63) / 64) * a.batch;
+  const long long tiles = (long long)((plan_rows(a) + 127) / 128) * ((a.N + 63) / 64) * a.batch;
   return tiles >= min_tiles;
 }
 

@@ -148,6 +148,11 @@ struct Ctx {
   // set by the internal callers of synth_forward whose every row has the full length T (the pipeline, its batched form,
   // the streaming hop): the TextEncoder's attention then runs without the all-ones key mask (ScopedFullLengths)
   bool synth_full_lengths = false;
+  // the pipelines and the streaming hop hand the synthesizer the output window their trim keeps (DecWindow below);
+  // off: the generator runs full-length (rvcx_set_dec_window; RVCX_DEC_WINDOW=0 at context creation). Same outputs.
+  bool dec_window = true;
+  // the window a call site passes: none while the switch is off or the arena query plans its worst case
+  bool use_dec_window() const { return dec_window && !sizing_plan; }
   // set while HuBERT's feature encoder is being issued (runtime_pipeline.cpp issue_front): the launches RVCX_AUX_LDS
   // throttles
   bool aux_front = false;
@@ -340,10 +345,22 @@ int64_t hubert_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int
                          int64_t cap, hipStream_t s);
 int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
                         int64_t cap, float* hidden, hipStream_t s);
+// The output samples per row a caller of the synthesizer goes on to read, [s0, s1) (s1 < 0: all of them). The HiFi-GAN
+// generators (NSF and no-f0) then run on the window's frames plus their receptive field (dec_margin_frames) and write
+// the window's samples, bit-identical to the full-length run, at their usual place; the samples outside it are
+// unspecified. The TextEncoder and the flow run on every frame; MRF and RefineGAN ignore the window. Rows of a batch
+// share it.
+struct DecWindow {
+  long long s0 = 0, s1 = -1;
+};
+// the generator's one-sided receptive field in input frames, from the loaded configuration (runtime_synth.cpp)
+int dec_margin_frames(const SynthCfg& cf);
+// the frames [fa, fb) of T the generator runs on for a window ([0, T) without one, or where it would drop too few)
+void dec_window_frames(const SynthCfg& cf, int T, const DecWindow& win, int& fa, int& fb);
 void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* lengths, const int32_t* pitch,
                    const float* pitchf, const int32_t* sid, const float* eps_z, const float* eps_src, uint64_t seed,
                    float* out, float* zp_out, float* z_out, hipStream_t s, int gen_lowp = 0, int head = 0,
-                   float* mp_out = nullptr, float* logsp_out = nullptr);
+                   float* mp_out = nullptr, float* logsp_out = nullptr, const DecWindow& win = DecWindow());
 // head: Synthesizer.infer's rate (synthesizers.py:230-234) as the first kept frame -- the flow and the decoder run on
 // T - head frames (out [B][(T - head) upp], zp_out / z_out [B][T - head][I]); mp_out / logsp_out [B][T][I]
 // gen_lowp: the generator's weight-streamed convs and fused ResBlock pairs on fp16 operands (one MFMA product per
@@ -352,7 +369,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
 // B, T, f0, eps_src, seed), on a stream this one has joined since; the ConvTransposes add them as their residual
 void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, const float* f0, const float* g,
                  const float* eps_src, uint64_t seed, float* out, hipStream_t s, int gen_lowp = 0,
-                 bool noise_pre = false);
+                 bool noise_pre = false, const DecWindow& win = DecWindow());
 // the NSF harmonic source (SineGen) and every multi-tap noise conv (hifigan_nsf.py:196-199) into their own buffers:
 // the synthesizer issues it on the aux stream beside the TextEncoder and flow, which leave most of the GPU idle.
 // Returns false (nothing issued) for configurations without the NSF noise branch.
@@ -364,10 +381,12 @@ void set_highpass_sos(Ctx& c, const double* sos, int nsec);
 void highpass_pad(Ctx& c, const double* audio, int64_t n, int64_t t_pad, double* pad64, float* pad32, hipStream_t s);
 int hubert_version_for(const Ctx& c);
 // feats_pre (optional): HuBERT rows of this chunk computed ahead (e.g. on the aux stream), L_pre rows
+// trim: samples per side of the output the caller drops (the pipeline's t_pad_tgt): the generator gets the kept window
+// (DecWindow) while Ctx::use_dec_window(), and the trimmed samples of out are then unspecified
 int64_t vc_forward(Ctx& c, const float* audio, int64_t n, const int32_t* pitch, const float* pitchf,
                    int64_t pitch_len, int sid, float protect, double index_rate, const float* eps_z,
                    const float* eps_src, uint64_t seed, float* out, int64_t cap, hipStream_t s,
-                   const float* feats_pre = nullptr, int64_t L_pre = 0);
+                   const float* feats_pre = nullptr, int64_t L_pre = 0, int64_t trim = 0);
 // streaming (runtime_stream.cpp)
 struct RtState;
 RtState* rt_create(Ctx& c, const rvcx_rt_desc& d);

@@ -157,7 +157,7 @@ int hubert_version_for(const Ctx& c) { return c.scfg.emb_dim == 256 ? 1 : 2; }
 int64_t vc_forward(Ctx& c, const float* audio, int64_t n, const int32_t* pitch, const float* pitchf,
                    int64_t pitch_len, int sid, float protect, double index_rate, const float* eps_z,
                    const float* eps_src, uint64_t seed, float* out, int64_t cap, hipStream_t s,
-                   const float* feats_pre, int64_t L_pre) {
+                   const float* feats_pre, int64_t L_pre, int64_t trim) {
   if (sid < 0 || sid >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "sid out of range");
   const int E = c.scfg.emb_dim;
   const float* feats = feats_pre;
@@ -191,7 +191,10 @@ int64_t vc_forward(Ctx& c, const float* audio, int64_t n, const int32_t* pitch, 
   set_i32_once(c, "vc.len.sid", lens + 1, sid, s);
   {
     ScopedFullLengths full(c);
-    synth_forward(c, 1, T, phone, lens, pitch, pitchf, lens + 1, eps_z, eps_src, seed, out, nullptr, nullptr, s);
+    DecWindow win;
+    if (trim > 0 && c.use_dec_window()) win = {trim, (long long)T * upp - trim};
+    synth_forward(c, 1, T, phone, lens, pitch, pitchf, lens + 1, eps_z, eps_src, seed, out, nullptr, nullptr, s, 0, 0,
+                  nullptr, nullptr, win);
   }
   return (int64_t)T * upp;
 }
@@ -462,7 +465,8 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
     const int64_t nvc = vc_forward(c, pad32 + ch.a0, len, pitch ? pitch + ch.f_lo : nullptr,
                                    pitchf ? pitchf + ch.f_lo : nullptr, ch.f_hi - ch.f_lo, o.sid,
                                    o.protect, o.index_rate, eps_z ? eps_z + ez_off[i] : nullptr,
-                                   eps_src ? eps_src + es_off[i] : nullptr, cseed[i], vc, cap_vc, s, cfeats[i], cL[i]);
+                                   eps_src ? eps_src + es_off[i] : nullptr, cseed[i], vc, cap_vc, s, cfeats[i], cL[i],
+                                   o.t_pad_tgt);
     const int64_t keep = nvc - 2 * o.t_pad_tgt;
     if (keep <= 0) throw Error(RVCX_E_SHAPE, "pipeline: chunk too short for the padding");
     if (nch == 1) {
@@ -597,7 +601,10 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   float* vc = c.buf<float>("pb.vc", (size_t)B * nvc, s);
   {
     ScopedFullLengths full(c);  // every row Tv long (hm above)
-    synth_forward(c, B, (int)Tv, phone, meta, pc, pf, meta + B, eps_z, eps_src, seed, vc, nullptr, nullptr, s);
+    DecWindow win;  // the samples the trim below keeps, the same for every row
+    if (o.t_pad_tgt > 0 && c.use_dec_window()) win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
+    synth_forward(c, B, (int)Tv, phone, meta, pc, pf, meta + B, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
+                  nullptr, nullptr, win);
   }
   // 5. trim, volume envelope, peak normalisation per utterance (pipeline.py:545-552)
   const int64_t keep = nvc - 2 * o.t_pad_tgt;

@@ -420,10 +420,63 @@ bool dec_noise_prepare(Ctx& c, int B, int T, const float* f0, const float* eps_s
   return true;
 }
 
+// The generator's one-sided receptive field in input frames: how far from an output sample an input frame can lie and
+// still reach it. Walked back from the output, E = the reach in rows of the current stage:
+//   conv_post (7 taps)                      E = 3
+//   per stage, last to first:
+//     the ResBlocks (their mean: the widest)  E += max_j sum_m [(k_j - 1) d_jm / 2 + (k_j - 1) / 2]   (convs1 + convs2)
+//     ConvTranspose1d(k, stride u)            E = ceil(E / u) + max(1, ceil(k / u) - 1)
+//       (E output rows span ceil(E / u) input frames; the polyphase form (finalize_synth) reads frames q - pad ..
+//        q - pad + taps - 1 for output frame q, floor(k / 2u + 1/2 - 1/u) <= ceil(k / u) - 1 to either side: 1 for
+//        RVC's k = 2u, taps 3, pad 1)
+//   conv_pre (7 taps)                       E += 3
+// The noise convs read the source, which is always computed full-length and addressed by absolute sample, so they add
+// nothing. The 48 kHz v2 generator (rates 12 / 10 / 2 / 2, kernels 3 / 7 / 11, dilations 1 / 3 / 5): 3 + 60 = 63 ->
+// 33, + 60 = 93 -> 48, + 60 = 108 -> 12, + 60 = 72 -> 7, + 3 = 10 frames.
+int dec_margin_frames(const SynthCfg& cf) {
+  long long E = (7 - 1) / 2;
+  long long rb = 0;
+  for (size_t j = 0; j < cf.rb_k.size(); ++j) {
+    const int k = cf.rb_k[j];
+    long long r = 0;
+    for (int d : cf.rb_d[j]) r += (long long)(k - 1) * d / 2 + (k - 1) / 2;
+    rb = std::max(rb, r);
+  }
+  for (size_t i = cf.ups.size(); i-- > 0;) {
+    const int u = cf.ups[i], k = cf.up_k[i];
+    E += rb;
+    E = (E + u - 1) / u + std::max(1, (k + u - 1) / u - 1);
+  }
+  return (int)(E + (7 - 1) / 2);
+}
+
+// the frames [fa, fb) the generator has to run for the window's samples to be those of the full-length run: the
+// window's frames plus the margin per side, clamped to the sequence (no margin is needed past its true ends). A
+// window that would drop fewer than DEC_WINDOW_MIN_DROP frames is not worth a second set of shapes: the whole length.
+constexpr int DEC_WINDOW_MIN_DROP = 4;
+void dec_window_frames(const SynthCfg& cf, int T, const DecWindow& win, int& fa, int& fb) {
+  fa = 0;
+  fb = T;
+  if (win.s1 < 0 || cf.vocoder != 0) return;  // MRF and RefineGAN run full-length
+  const long long upp = cf.upp(), M = dec_margin_frames(cf);
+  const long long s0 = std::max<long long>(0, win.s0), s1 = std::min<long long>(win.s1, (long long)T * upp);
+  if (s1 <= s0) return;
+  const long long a = std::max<long long>(0, s0 / upp - M), b = std::min<long long>(T, (s1 + upp - 1) / upp + M);
+  if (T - (b - a) < DEC_WINDOW_MIN_DROP) return;
+  fa = (int)a;
+  fb = (int)b;
+}
+
 // ------------------------------------------------------------------ generator
 // HiFiGANNSFGenerator.forward (generators/hifigan_nsf.py:173-212); z_btc [B][T][I] time-major.
+// With an output window the generator runs on the frames dec_window_frames gives: its inputs are the full-length
+// buffers at an offset (z, mask, the source, the noise convs computed ahead), its own stage buffers hold the window
+// alone, and conv_post writes the samples at their usual place in out. Every launch is planned for the full stage
+// length (ConvArgs::plan_T), so each sample of the window gets the arithmetic of the full-length run, bit for bit;
+// the samples within the margin of a cut edge see zero padding where the full run sees neighbours and are unspecified.
 void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, const float* f0, const float* g,
-                 const float* eps_src, uint64_t seed, float* out, hipStream_t s, int gen_lowp, bool noise_pre) {
+                 const float* eps_src, uint64_t seed, float* out, hipStream_t s, int gen_lowp, bool noise_pre,
+                 const DecWindow& win) {
   const SynthCfg& cf = c.scfg;
   if (cf.f0 && cf.vocoder == 2) {
     refinegan_forward(c, B, T, z_btc, mask, f0, g, eps_src, seed, out, s);
@@ -431,6 +484,10 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
   }
   const int I = cf.I, C0 = cf.C0;
   const long long har_ld = (long long)T * cf.upp() + 2 * HAR_PAD;
+  int fa, fb;
+  dec_window_frames(cf, T, win, fa, fb);
+  const int Tc = fb - fa;                             // frames the generator runs on
+  const long long har_off = (long long)fa * cf.upp();  // the window's first sample in the source rows and in out
   float* har = nullptr;
   if (cf.f0) {
     if (noise_pre) {
@@ -443,9 +500,9 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
   float* cv = c.buf<float>("dec.cvec", (size_t)B * C0, s);
   run(c, lin(g, cf.gin, B, cf.gin, c.W("dec.cond.w"), C0, c.W("dec.cond.b"), cv, C0), s);
   // stage buffers sized for the largest stage
-  size_t maxe = (size_t)T * C0;
+  size_t maxe = (size_t)Tc * C0;
   {
-    long long t = T;
+    long long t = Tc;
     for (size_t i = 0; i < cf.ups.size(); ++i) {
       t *= cf.ups[i];
       maxe = std::max(maxe, (size_t)t * (C0 >> (i + 1)));
@@ -456,8 +513,11 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
   float* R = c.buf<float>("dec.r", (size_t)B * maxe, s);
   float* t1 = c.buf<float>("dec.t", (size_t)B * maxe, s);
   {
-    ConvArgs a = conv(z_btc, I, T, I, c.W("dec.pre.w"), C0, 7, 1, 3, c.W("dec.pre.b"), xin, C0, T, B);
-    a.pre_mask = mask;
+    ConvArgs a =
+        conv(z_btc + (size_t)fa * I, I, Tc, I, c.W("dec.pre.w"), C0, 7, 1, 3, c.W("dec.pre.b"), xin, C0, Tc, B);
+    a.x_bs = (long long)T * I;
+    a.plan_T = T;
+    a.pre_mask = mask + fa;
     a.pre_mask_bs = T;
     a.res = cv;
     a.ldr = 0;
@@ -466,13 +526,16 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     run(c, a, s);
   }
   float* cur = xin;
-  int curT = T, Cin = C0;
+  int curT = Tc, Cin = C0;
+  long long fullT = T, off = fa;  // the stage's full length, and the window's first row in it
   const int nk = (int)cf.rb_k.size();
   for (size_t i = 0; i < cf.ups.size(); ++i) {
     const UpsLayer& L = c.ups[i];
     const int C = L.cout, u = L.u, Ti = curT * u;
+    const long long fullTi = fullT * u, offi = off * u;
     // LeakyReLU(0.1) -> ConvTranspose1d (polyphase) ; output [B][curT][u*C] == [B][Ti][C]
     ConvArgs a = conv(cur, Cin, curT, Cin, L.w, u * C, L.taps, 1, L.pad, L.b, y, u * C, curT, B);
+    a.plan_T = (int)fullT;
     a.w_static = 1;
     a.lowp = gen_lowp;
     a.pre_act = ACT_LRELU;
@@ -497,13 +560,13 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
       if (noise_pre && kk > 1) {
         // computed ahead (dec_noise_prepare): y = ups(x) + nz, the residual of this ConvTranspose's epilogue -- the
         // same single addition as the accumulate pass after it (k_noise_add / the ACC_ADD conv), bit-identical
-        a.res = c.buf<float>("dec.nz" + std::to_string(i), (size_t)B * Ti * C, s);
+        a.res = c.buf<float>("dec.nz" + std::to_string(i), (size_t)B * fullTi * C, s) + (size_t)offi * C;
         a.ldr = u * C;
-        a.res_bs = (long long)Ti * C;
+        a.res_bs = fullTi * C;
         a.res_mode = RES_ADD_POST;
         nz_fused = true;
       } else if (kk == 1 && conv_routes_wsb16(c, a)) {
-        a.nz_har = har + HAR_PAD - npad;
+        a.nz_har = har + HAR_PAD - npad + har_off;
         a.nz_bs = har_ld;
         a.nz_stride = stride;
         a.nz_kk = ntap * stride;
@@ -516,13 +579,14 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     }
     run(c, a, s, 2.0 * B * curT * (double)Cin * C * L.k);
     if (cf.f0 && !nz_fused) {
-      if (noise_row_kernel(nf, B, Ti, C)) {
-        check(noise_conv_add(har + HAR_PAD - npad, har_ld, stride, ntap, c.W(nn + ".wf"), c.W(nn + ".b"), y, B, Ti,
-                             C, s),
+      const float* hsrc = har + HAR_PAD - npad + har_off;  // the window's first source sample of this framing
+      if (noise_row_kernel(nf, B, fullTi, C)) {
+        check(noise_conv_add(hsrc, har_ld, stride, ntap, c.W(nn + ".wf"), c.W(nn + ".b"), y, B, Ti, C, s),
               "noise_conv_add");
       } else {
-        ConvArgs an = conv(har + HAR_PAD - npad, stride, Ti + ntap - 1, stride, c.W(nn + ".wf"), C, ntap, 1, 0,
-                           c.W(nn + ".b"), y, C, Ti, B);
+        ConvArgs an = conv(hsrc, stride, Ti + ntap - 1, stride, c.W(nn + ".wf"), C, ntap, 1, 0, c.W(nn + ".b"), y, C, Ti,
+                           B);
+        an.plan_T = (int)fullTi;
         an.x_bs = har_ld;
         an.acc_mode = ACC_ADD;
         run(c, an, s, 2.0 * B * (double)Ti * C * kern);
@@ -582,6 +646,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
         const std::string n1 = rb + ".convs1." + std::to_string(m);
         const std::string n2 = rb + ".convs2." + std::to_string(m);
         ConvArgs a1 = conv(r_in, C, Ti, C, c.W(n1 + ".w"), C, k, d, (k * d - d) / 2, c.W(n1 + ".b"), T1, C, Ti, B);
+        a1.plan_T = (int)fullTi;
         a1.w_static = 1;
         a1.lowp = gen_lowp;
         a1.pre_act = ACT_LRELU;
@@ -591,6 +656,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
         const bool last = (m + 1 == dil.size());
         float* dst = last ? S : RR;
         ConvArgs a2 = conv(T1, C, Ti, C, c.W(n2 + ".w"), C, k, 1, (k - 1) / 2, c.W(n2 + ".b"), dst, C, Ti, B);
+        a2.plan_T = (int)fullTi;
         a2.w_static = 1;
         a2.lowp = gen_lowp;
         run(c, a1, s);
@@ -609,9 +675,12 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     cur = S;
     curT = Ti;
     Cin = C;
+    fullT = fullTi;
+    off = offi;
   }
   // LeakyReLU(0.01) -> conv_post (no bias) -> tanh
-  check(conv_post_tanh(cur, B, curT, Cin, c.W("dec.post.w"), 7, 0.01f, out, s, c.host[0].at("__post_b__").v[0]),
+  check(conv_post_tanh(cur, B, curT, Cin, c.W("dec.post.w"), 7, 0.01f, out + har_off, s,
+                       c.host[0].at("__post_b__").v[0], fullT),
         "conv_post");
 }
 
@@ -619,7 +688,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
 void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* lengths, const int32_t* pitch,
                    const float* pitchf, const int32_t* sid, const float* eps_z, const float* eps_src, uint64_t seed,
                    float* out, float* zp_out, float* z_out, hipStream_t s, int gen_lowp, int head, float* mp_out,
-                   float* logsp_out) {
+                   float* logsp_out, const DecWindow& win) {
   const SynthCfg& cf = c.scfg;
   const int H = cf.H, I = cf.I, F = cf.F, E = cf.emb_dim, nh = cf.n_heads, dk = H / nh;
   const long long BT = (long long)B * T;
@@ -803,7 +872,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
   if (z_out) RVCX_HIP(hipMemcpyAsync(z_out, z, BTf * I * sizeof(float), hipMemcpyDeviceToDevice, s));
   // ---- dec(z * mask, nsff0, g)
   join_aux(c, s, nax);
-  dec_forward(c, B, Tf, z, maskf, pitchff, g, eps_src, seed, out, s, gen_lowp, noise_pre);
+  dec_forward(c, B, Tf, z, maskf, pitchff, g, eps_src, seed, out, s, gen_lowp, noise_pre, win);
 }
 
 }  // namespace rvcx

@@ -124,6 +124,10 @@ struct ConvArgs {
                        // (conv_wsb16_kernel only: the two-plane fp16 arithmetic and the reduced-precision mode)
   int ksplit = 1;
   int no_splitk = 0;
+  // rows the dispatcher plans for (1-D; 0 = T_out): the kernel family, the tile and ksplit are chosen as for a launch
+  // of plan_T rows, so a launch over a window of a longer sequence (the decoder's output window, runtime_synth.cpp)
+  // gets the arithmetic of the full-length launch. Grids, workspaces and slabs are sized by T_out.
+  int plan_T = 0;
   // opt-in reduced precision (the generator's weight-streamed convs of a realtime hop, rvcx_rt_opts::gen_precision):
   // fp16 operands (the WSPLIT_H16 image's hi plane), one MFMA product per step. Never set on the parity path.
   int lowp = 0;
@@ -297,8 +301,9 @@ hipError_t upsample2_protect(const float* feats, const float* feats0, int L, int
                              hipStream_t s);
 hipError_t sine_source(const float* f0, int B, int L, int upp, float sr, const float* eps, uint64_t seed,
                        float lin_w, float lin_b, double* cum_ws, float* har, long long har_ld, hipStream_t s);
+// (y_bs: floats between the output rows of two batch entries, 0 = T)
 hipError_t conv_post_tanh(const float* x, int B, int T, int C, const float* w, int K, float slope, float* y,
-                          hipStream_t s, float bias = 0.f);
+                          hipStream_t s, float bias = 0.f, long long y_bs = 0);
 // per-sample harmonic source of the MRF HiFi-GAN / RefineGAN decoders (source_harm.hip): f0 [B][L] -> har row b
 // at har + b*har_ld, N = L*upp samples; eps [B][N][H] and ini [B][H] injected or drawn (Philox(seed))
 size_t harm_source_ws_doubles(int B, int L, int upp, int H);

@@ -34,7 +34,8 @@ EXPORTS = [
     "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode", "rvcx_fcpe_b",
 ]
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
-TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel"]
+TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
+                "rvcx_dec_margin_frames"]
 
 
 class RvcxLibraryError(ImportError):
@@ -178,6 +179,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_fcpe_decode": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp]),
         "rvcx_fcpe_b": (i32, [vp, vp, i64, i64, i32, f32, i32, vp, vp, vp]),
         "rvcx_fcpe_mel": (i32, [vp, vp, i64, vp, i64, P(i64), vp]),
+        "rvcx_set_dec_window": (i32, [vp, i32]),
+        "rvcx_dec_margin_frames": (i32, [P(SynthDesc), P(i32)]),
         "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
         "rvcx_performer_attention_b": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
         "rvcx_split_audio": (i32, [vp, vp, i64, i32, f64, i32, P(i64), i64, P(i64), vp]),

@@ -78,7 +78,8 @@ class Engine:
         return t.as_tensor(np.ascontiguousarray(x), dtype=dtype, device=self.device).contiguous()
 
     # ------------------------------------------------------------------ weights
-    def set_synth_config(self, cfg: SynthConfig = SYNTH_48K_V2):
+    @staticmethod
+    def _synth_desc(cfg: SynthConfig):
         d = _lib.SynthDesc()
         d.inter_channels, d.hidden_channels, d.filter_channels = cfg.inter_channels, cfg.hidden_channels, \
             cfg.filter_channels
@@ -100,8 +101,28 @@ class Engine:
         if cfg.vocoder not in _lib.VOCODERS:
             raise ValueError(f"unknown vocoder {cfg.vocoder!r}; expected one of {sorted(_lib.VOCODERS)}")
         d.vocoder = _lib.VOCODERS[cfg.vocoder]
+        return d
+
+    def set_synth_config(self, cfg: SynthConfig = SYNTH_48K_V2):
+        d = self._synth_desc(cfg)
         self._check(self.lib.rvcx_set_synth_config(self.ctx, ctypes.byref(d)), "set_synth_config")
         self.synth_cfg = cfg
+
+    def set_dec_window(self, on: bool):
+        """The generator's output window on (the default) or off (rvcx_set_dec_window, include/rvcx_test.h): with it
+        on, the pipelines and stream groups run the generator only over the frames their trim keeps. Outputs are
+        bit-identical either way."""
+        self._check(self.lib.rvcx_set_dec_window(self.ctx, 1 if on else 0), "set_dec_window")
+
+    def dec_margin_frames(self, cfg: SynthConfig = None) -> int:
+        """The generator's one-sided receptive field in frames for `cfg` (default: the loaded configuration): the
+        margin the output window keeps per cut side (rvcx_dec_margin_frames). Host only."""
+        d = self._synth_desc(cfg if cfg is not None else self.synth_cfg)
+        m = ctypes.c_int32(0)
+        rc = self.lib.rvcx_dec_margin_frames(ctypes.byref(d), ctypes.byref(m))
+        if rc != 0:
+            raise _lib.RvcxError(rc, "dec_margin_frames: bad synthesizer configuration")
+        return m.value
 
     def upload_state(self, model: int, state: Mapping[str, np.ndarray]):
         """Upload a fused fp32 state dict (reference names and layouts) and finalize it."""
