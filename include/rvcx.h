@@ -393,6 +393,36 @@ int rvcx_index_reconstruct_n(rvcx_ctx* ctx, int64_t i0, int64_t ni, float* d_out
 int rvcx_index_retrieve(rvcx_ctx* ctx, const float* d_feats, int64_t L, int d, double index_rate, float* d_out,
                         void* stream);
 
+/* ---------------------------------------------------------------- feature index: build and write
+ * Replaces faiss.index_factory(768, f"IVF{n_ivf},Flat") + train + add + faiss.write_index of
+ * rvc/train/process/extract_index.py:58-70 (faiss-cpu k-means + IndexIVF::add) on device. Unpinned against faiss
+ * itself (its random choices cannot be reproduced); the deviations are listed in csrc/index_build.cpp. */
+typedef struct {
+  int niter;                /* Lloyd iterations; 10 = faiss's cp.niter for the IVF coarse quantizer (train, :64) */
+  int64_t nprobe;           /* nprobe of the built index; 1 as extract_index.py:63 */
+  uint64_t seed;            /* seeds the choice of the initial centroids when init_rows is NULL */
+  const int64_t* init_rows; /* host, nlist distinct rows of d_x: the initial centroids; NULL = drawn from seed */
+} rvcx_index_build_opts;
+/* niter 10, nprobe 1, seed 0, init_rows NULL. Returns rvcx_status like every entry here (RVCX_E_INVALID for NULL). */
+int rvcx_index_default_build_opts(rvcx_index_build_opts* o);
+/* index.train(big_npy) + index.add(big_npy) (extract_index.py:64-68): k-means over d_x [n][d] fp32 (device, 16-byte
+ * aligned; d a multiple of 64 up to 1024, else RVCX_E_SHAPE) into nlist centroids, then every row, id = its row
+ * number, into the list of its nearest centroid. The result becomes the context's loaded index exactly as
+ * rvcx_index_load leaves it (a previously loaded index is replaced only when the build succeeds). Synchronises
+ * `stream` once per iteration. opts NULL = the defaults. RVCX_E_INVALID for nlist < 1, nlist > n, niter < 0,
+ * nprobe < 1 or duplicate / out-of-range init_rows. */
+int rvcx_index_build(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, int64_t nlist,
+                     const rvcx_index_build_opts* opts, void* stream);
+/* The loaded index's coarse centroids -> d_out [nlist][d] (faiss: index.quantizer.reconstruct_n(0, nlist)); the
+ * k-means reduction of extract_index.py:46-56 reads them back. RVCX_E_STATE when no index is loaded. */
+int rvcx_index_centroids(rvcx_ctx* ctx, float* d_out, void* stream);
+/* faiss.write_index(index, path) (extract_index.py:70) into host memory: the loaded index, built here or loaded
+ * from a file, as faiss 1.7.4 IndexIVFFlat bytes (direct map type 0; "full" list sizes when more than nlist / 2
+ * lists are non-empty, else "sprs"; an index loaded from a file keeps that file's choice of the two, so it saves
+ * back byte for byte). *nbytes = the size; bytes NULL reports only the size. RVCX_E_CAPACITY when cap is too
+ * small, RVCX_E_STATE when no index is loaded. Synchronises the device. */
+int rvcx_index_save(rvcx_ctx* ctx, void* bytes, int64_t cap, int64_t* nbytes);
+
 /* ---------------------------------------------------------------- streaming (config C5)
  * A group of n_streams concurrent realtime streams of one buffer geometry, converted together per hop.
  * Replaces VoiceChanger / Realtime / Realtime_Pipeline of rvc/realtime/core.py:329-484 and

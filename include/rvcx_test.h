@@ -41,6 +41,19 @@ int rvcx_set_dec_window(rvcx_ctx* ctx, int on);
  * window keeps per cut side): *frames. Host only, no context. */
 int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames);
 
+/* One nearest-centroid pass of the index build (csrc/kmeans.hip k_kmeans_assign; faiss IndexFlatL2::search with
+ * k = 1 inside Clustering::train): d_x [n][d], d_cent [nlist][d] fp32 -> d_assign [n] = argmin_l |x - c_l|^2, ties to
+ * the lowest l; d_dist [n] (optional) the squared distance to it. d % 32 == 0 and d <= 1024, else RVCX_E_SHAPE. */
+int rvcx_kmeans_assign(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const float* d_cent, int64_t nlist,
+                       int32_t* d_assign, float* d_dist, void* stream);
+
+/* One centroid update of the index build (k_kmeans_update after the stable counting sort): d_cent [nlist][d]
+ * (in-out) row l becomes the mean of the rows with d_assign == l (fp64 accumulation in ascending row order, one
+ * rounding); a list without rows keeps its centroid. d_sizes [nlist] (optional) = the list sizes. A row whose
+ * assignment is outside [0, nlist) belongs to no list and is left out. */
+int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const int32_t* d_assign, int64_t nlist,
+                       float* d_cent, int64_t* d_sizes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

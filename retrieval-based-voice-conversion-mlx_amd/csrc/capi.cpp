@@ -1413,6 +1413,57 @@ int rvcx_index_retrieve(rvcx_ctx* ctx, const float* d_feats, int64_t L, int d, d
   });
 }
 
+int rvcx_index_default_build_opts(rvcx_index_build_opts* o) {
+  if (!o) return RVCX_E_INVALID;
+  o->niter = 10;
+  o->nprobe = 1;
+  o->seed = 0;
+  o->init_rows = nullptr;
+  return RVCX_OK;
+}
+
+int rvcx_index_build(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, int64_t nlist,
+                     const rvcx_index_build_opts* opts, void* stream) {
+  return guard(ctx, [&] {
+    rvcx_index_build_opts o;
+    rvcx_index_default_build_opts(&o);
+    if (opts) o = *opts;
+    set_device(ctx);
+    index_build(*ctx, d_x, n, d, nlist, o, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rvcx_index_centroids(rvcx_ctx* ctx, float* d_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_out) throw Error(RVCX_E_INVALID, "index_centroids: null output");
+    set_device(ctx);
+    index_centroids(*ctx, d_out, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rvcx_index_save(rvcx_ctx* ctx, void* bytes, int64_t cap, int64_t* nbytes) {
+  return guard(ctx, [&] {
+    const int64_t nb = index_save(*ctx, bytes, cap);
+    if (nbytes) *nbytes = nb;
+  });
+}
+
+int rvcx_kmeans_assign(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const float* d_cent, int64_t nlist,
+                       int32_t* d_assign, float* d_dist, void* stream) {
+  return guard(ctx, [&] {
+    set_device(ctx);
+    kmeans_assign_run(*ctx, d_x, n, d, d_cent, nlist, d_assign, d_dist, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const int32_t* d_assign, int64_t nlist,
+                       float* d_cent, int64_t* d_sizes, void* stream) {
+  return guard(ctx, [&] {
+    set_device(ctx);
+    kmeans_update_run(*ctx, d_x, n, d, d_assign, nlist, d_cent, d_sizes, static_cast<hipStream_t>(stream));
+  });
+}
+
 // ------------------------------------------------------------------ streaming (C5)
 int rvcx_rt_default_desc(rvcx_rt_desc* d) {
   if (!d) return RVCX_E_INVALID;

@@ -174,6 +174,7 @@ ParsedIvf parse_ivf(const uint8_t* bytes, int64_t nbytes) {
   P.nlist = (long long)nlist;
   P.ntotal = ntotal;
   P.nprobe = (int)std::max<uint64_t>(1, std::min<uint64_t>(nprobe, nlist));
+  P.sparse_sizes = kind == "sprs";
   return P;
 }
 
@@ -186,6 +187,8 @@ void index_load(Ctx& c, const uint8_t* bytes, int64_t nbytes) {
   upload(ix->off, P.off.data(), P.off.size());
   upload(ix->ids, P.ids.data(), P.ids.size());
   upload(ix->slot_of_id, P.slot.data(), P.slot.size());
+  ix->off_host = P.off;
+  ix->size_enc = P.sparse_sizes ? 1 : 0;
   IvfView& v = ix->view;
   v.d = P.d;
   v.nlist = P.nlist;

@@ -96,6 +96,11 @@ struct UpsLayer {
 struct IvfIndex {
   IvfView view;
   DevBuf cent, vecs, off, ids, slot_of_id;
+  std::vector<long long> off_host;  // off [nlist + 1] on the host too: the list sizes index_save writes
+  // how index_save encodes the list sizes: -1 faiss's own choice ("full" when more than nlist / 2 lists are
+  // non-empty, else "sprs": a built index), 0 / 1 "full" / "sprs" as the loaded file had them, so that a loaded
+  // file saves back byte for byte whichever its writer chose
+  int size_enc = -1;
 };
 
 struct Ctx {
@@ -406,6 +411,7 @@ struct ParsedIvf {  // a validated faiss IndexIVFFlat image on the host (lists i
   std::vector<float> cent, vecs;
   std::vector<long long> off, ids;
   std::vector<int> slot;  // id -> slot
+  bool sparse_sizes = false;  // the file's list sizes were "sprs" pairs, not a "full" vector
 };
 ParsedIvf parse_ivf(const uint8_t* bytes, int64_t nbytes);  // host only; throws Error(RVCX_E_INVALID)
 void index_load(Ctx& c, const uint8_t* bytes, int64_t nbytes);
@@ -416,6 +422,18 @@ void index_retrieve(Ctx& c, const float* feats, int64_t L, int d, double index_r
 void index_retrieve_rows(Ctx& c, const float* feats, int64_t L, int64_t off, int d, int n_seq, const int* seqs,
                          const float* rate, const float* one_minus_rate, float* out, hipStream_t s);
 void index_reconstruct_n(Ctx& c, int64_t i0, int64_t ni, float* out, hipStream_t s);
+// index build and write (index_build.cpp): faiss train + add over x [n][d] (extract_index.py:58-68); the result
+// replaces the loaded index once the build has succeeded
+void index_build(Ctx& c, const float* x, int64_t n, int d, int64_t nlist, const rvcx_index_build_opts& o,
+                 hipStream_t s);
+void index_centroids(Ctx& c, float* out, hipStream_t s);  // the loaded index's centroids [nlist][d]
+// faiss.write_index of the loaded index (extract_index.py:70) -> the byte count; bytes == null: the count alone
+int64_t index_save(Ctx& c, void* bytes, int64_t cap);
+// the k-means kernels on their own (rvcx_test.h)
+void kmeans_assign_run(Ctx& c, const float* x, int64_t n, int d, const float* cent, int64_t nlist, int32_t* assign,
+                       float* dist, hipStream_t s);
+void kmeans_update_run(Ctx& c, const float* x, int64_t n, int d, const int32_t* assign, int64_t nlist, float* cent,
+                       int64_t* sizes, hipStream_t s);
 int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
                             const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
                             double* f0_out, hipStream_t s);

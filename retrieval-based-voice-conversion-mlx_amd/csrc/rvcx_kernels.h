@@ -399,6 +399,28 @@ struct IvfRows {
 hipError_t ivf_retrieve_rows(const IvfView& v, const float* x, const IvfRows& rows, int n_seq, float* out, float* ws,
                              hipStream_t s);
 
+// k-means for building an IndexIVFFlat (kmeans.hip; the Lloyd loop is index_build.cpp). x [n][d], cent [nlist][d]
+// fp32 row-major, 16-byte aligned; d % 32 == 0 and d <= 1024 (kmeans_shape_ok), n and nlist below 2^31.
+bool kmeans_shape_ok(int d);
+// assign[q] = argmin_l |x_q - c_l|^2, ties to the lowest l (fp32-input MFMA, no [n][nlist] store); dist [n]
+// (optional) = the squared distance to that centroid. cnorm [nlist] is scratch for the centroid norms.
+hipError_t kmeans_assign(const float* x, long long n, int d, const float* cent, long long nlist, float* cnorm,
+                         int* assign, float* dist, hipStream_t s);
+// Stable counting sort of the rows by list: sizes [nlist], off [nlist + 1], perm [n] = row ids grouped by list,
+// ascending inside each list (the order faiss's add fills a list in); identical run to run. hist is scratch of
+// kmeans_sort_blocks(n) * nlist ints. A row whose assign is outside [0, nlist) is left out of every list.
+int kmeans_sort_blocks(long long n);
+hipError_t kmeans_sort(const int* assign, long long n, long long nlist, int* hist, long long* sizes, long long* off,
+                       int* perm, hipStream_t s);
+// cent[l] <- the mean of its members (fp64 accumulation in perm order, one rounding); an empty list keeps its own
+hipError_t kmeans_update(const float* x, int d, const int* perm, const long long* off, long long nlist, float* cent,
+                         hipStream_t s);
+// faiss split_clusters for one pair: c_i = c_j scaled by 1 +- eps on even / odd components, c_j by the opposite
+hipError_t kmeans_split(float* cent, int d, long long i, long long j, float eps, hipStream_t s);
+// the IvfView arrays from perm: vecs [n][d] in list order, ids [n], slot_of_id [n]
+hipError_t kmeans_pack(const float* x, long long n, int d, const int* perm, float* vecs, long long* ids,
+                       int* slot_of_id, hipStream_t s);
+
 // streaming (stream.hip): B slots of one geometry per launch. slot2row [B] (-1 = idle this hop) / row2slot [B_act]
 // map a group's slots to the compact rows the networks run on; null = identity (stream.hip's header)
 hipError_t rt_resample(const float* x, long long ldx, int n_in, const float* ker, int K, int width, int orig, int nw,

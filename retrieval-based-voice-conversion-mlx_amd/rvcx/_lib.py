@@ -32,10 +32,11 @@ EXPORTS = [
     "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
     "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode", "rvcx_fcpe_b",
+    "rvcx_index_default_build_opts", "rvcx_index_build", "rvcx_index_centroids", "rvcx_index_save",
 ]
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
 TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
-                "rvcx_dec_margin_frames"]
+                "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update"]
 
 
 class RvcxLibraryError(ImportError):
@@ -127,6 +128,12 @@ class ConvTestDesc(ctypes.Structure):
     ]
 
 
+class IndexBuildOpts(ctypes.Structure):
+    """rvcx_index_build_opts (include/rvcx.h)."""
+    _fields_ = [("niter", ctypes.c_int), ("nprobe", ctypes.c_int64), ("seed", ctypes.c_uint64),
+                ("init_rows", ctypes.POINTER(ctypes.c_int64))]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -191,6 +198,12 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_index_search": (i32, [vp, vp, i64, i32, vp, vp, vp]),
         "rvcx_index_reconstruct_n": (i32, [vp, i64, i64, vp, vp]),
         "rvcx_index_retrieve": (i32, [vp, vp, i64, i32, f64, vp, vp]),
+        "rvcx_index_default_build_opts": (i32, [P(IndexBuildOpts)]),
+        "rvcx_index_build": (i32, [vp, vp, i64, i32, i64, P(IndexBuildOpts), vp]),
+        "rvcx_index_centroids": (i32, [vp, vp, vp]),
+        "rvcx_index_save": (i32, [vp, vp, i64, P(i64)]),
+        "rvcx_kmeans_assign": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
+        "rvcx_kmeans_update": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
         "rvcx_pipeline_batch": (i32, [vp, vp, i64, i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp, i64,
                                       P(i64), vp, vp, vp]),
         "rvcx_set_highpass_sos": (i32, [vp, vp, i32]),

@@ -710,6 +710,68 @@ class Engine:
                                                  out.data_ptr(), self.stream()), "index_retrieve")
         return out
 
+    # ------------------------------------------------------------------ feature index: build and write
+    def index_build(self, x, nlist: int, niter: int = 10, nprobe: int = 1, seed: int = 0, init_rows=None):
+        """index.train(x) + index.add(x) on device (extract_index.py:58-68): k-means over x [n, d] into nlist lists;
+        the result becomes this engine's loaded index. init_rows: nlist distinct rows of x as the initial centroids
+        (default: drawn from seed). -> index_info()."""
+        t = self.torch
+        xx = self._dev(x, t.float32)
+        xx = xx.reshape(-1, xx.shape[-1])
+        o = _lib.IndexBuildOpts()
+        self._check(self.lib.rvcx_index_default_build_opts(ctypes.byref(o)), "index_default_build_opts")
+        o.niter, o.nprobe, o.seed = int(niter), int(nprobe), int(seed)
+        rows = None
+        if init_rows is not None:
+            rows = np.ascontiguousarray(init_rows, dtype=np.int64).reshape(-1)
+            if rows.size != int(nlist):
+                raise _lib.RvcxError(-1, f"index_build: init_rows holds {rows.size} rows, nlist is {nlist}")
+            o.init_rows = rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        self._check(self.lib.rvcx_index_build(self.ctx, xx.data_ptr(), xx.shape[0], xx.shape[1], int(nlist),
+                                              ctypes.byref(o), self.stream()), "index_build")
+        return self.index_info()
+
+    def index_centroids(self):
+        """The loaded index's coarse centroids -> fp32 [nlist, d] device tensor."""
+        info = self.index_info()
+        if info is None:
+            raise _lib.RvcxError(-5, "no feature index loaded")
+        out = self.torch.empty((info["nlist"], info["d"]), dtype=self.torch.float32, device=self.device)
+        self._check(self.lib.rvcx_index_centroids(self.ctx, out.data_ptr(), self.stream()), "index_centroids")
+        return out
+
+    def index_save(self) -> bytes:
+        """faiss.write_index of the loaded index (extract_index.py:70) -> the file's bytes."""
+        nb = ctypes.c_int64(0)
+        self._check(self.lib.rvcx_index_save(self.ctx, None, 0, ctypes.byref(nb)), "index_save")
+        buf = ctypes.create_string_buffer(nb.value)
+        self._check(self.lib.rvcx_index_save(self.ctx, buf, nb.value, ctypes.byref(nb)), "index_save")
+        return buf.raw[:nb.value]
+
+    def kmeans_assign(self, x, cent, want_dist: bool = True):
+        """One nearest-centroid pass (rvcx_kmeans_assign): x [n, d], cent [nlist, d] -> (assign int32 [n],
+        dist fp32 [n] or None) device tensors."""
+        t = self.torch
+        xx, cc = self._dev(x, t.float32), self._dev(cent, t.float32)
+        n, d = xx.shape
+        assign = t.empty((n,), dtype=t.int32, device=self.device)
+        dist = t.empty((n,), dtype=t.float32, device=self.device) if want_dist else None
+        self._check(self.lib.rvcx_kmeans_assign(self.ctx, xx.data_ptr(), n, d, cc.data_ptr(), cc.shape[0],
+                                                assign.data_ptr(), _ptr(dist), self.stream()), "kmeans_assign")
+        return assign, dist
+
+    def kmeans_update(self, x, assign, cent):
+        """One centroid update (rvcx_kmeans_update): -> (new centroids fp32 [nlist, d], sizes int64 [nlist])
+        device tensors; cent is not modified."""
+        t = self.torch
+        xx, aa = self._dev(x, t.float32), self._dev(assign, t.int32)
+        cc = self._dev(cent, t.float32).clone()
+        n, d = xx.shape
+        sizes = t.empty((cc.shape[0],), dtype=t.int64, device=self.device)
+        self._check(self.lib.rvcx_kmeans_update(self.ctx, xx.data_ptr(), n, d, aa.data_ptr(), cc.shape[0],
+                                                cc.data_ptr(), sizes.data_ptr(), self.stream()), "kmeans_update")
+        return cc, sizes
+
     # ------------------------------------------------------------------ kernel timing
     def set_conv_math(self, mode: str):
         """Contraction arithmetic of this context: "h16" (the default: fp32 via three bf16 planes on bf16 MFMA, the

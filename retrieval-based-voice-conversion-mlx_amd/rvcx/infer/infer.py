@@ -187,6 +187,26 @@ class RVCX:
         wavfile.write(audio_output, self.tgt_sr, out.astype(np.float32))
         return out
 
+    def build_index(self, audio_paths_or_arrays, out_path: str, algorithm: str = "Auto", seed: int = 0, **kw):
+        """The .index file that index_rate > 0 needs, from the speaker's audio: the HuBERT features of every file or
+        16 kHz array, as rvc/train/extract/extract.py:133-139 saves them (files whose features hold NaN are skipped),
+        then rvc/train/process/extract_index.py:37-70 on device (rvcx.infer.index.build_index) and write. Returns
+        the built IndexIVFFlat, which is this engine's loaded index."""
+        from .index import build_index
+
+        feats = []
+        for a in audio_paths_or_arrays:
+            audio = load_audio(a) if isinstance(a, (str, os.PathLike)) else np.asarray(a)
+            f = self.engine.host(self.engine.hubert(audio, self.version))
+            if np.isnan(f).any():
+                continue
+            feats.append(f)
+        if not feats:
+            raise ValueError("build_index: no usable audio (every file's features held NaN, or none was given)")
+        index = build_index(self.engine, np.concatenate(feats, axis=0), algorithm=algorithm, seed=seed, **kw)
+        index.write(out_path)
+        return index
+
     def close(self):
         self.engine.close()
 
