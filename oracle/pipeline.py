@@ -135,9 +135,10 @@ class OraclePipeline:
 
     def pipeline(self, sid, audio, pitch=0, protect=0.33, volume_envelope=1.0, f0_autotune=False,
                  f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, index=None,
-                 index_rate=0.0):
-        """pipeline.py:390-558 with pitch_guidance=True; ``index`` = the parsed file_index (oracle.ivf)."""
-        vc_kw = dict(index=index, index_rate=index_rate)
+                 index_rate=0.0, version="v2"):
+        """pipeline.py:390-558 with pitch_guidance=True; ``index`` = the parsed file_index (oracle.ivf); ``version``
+        the embedder output the model takes ("v1": final_proj, 256-dim)."""
+        vc_kw = dict(index=index, index_rate=index_rate, version=version)
         audio = signal.filtfilt(BH, AH, audio)
         audio_pad = np.pad(audio, (self.window // 2, self.window // 2), mode="reflect")
         opt_ts = []

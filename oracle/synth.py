@@ -239,8 +239,11 @@ def harmonic_source(f0_up: Tensor, sr: int, harmonics: int, eps: Tensor, rand_in
                     lin_b: Optional[Tensor]) -> Tensor:
     """SineGenerator + merge of the MRF / RefineGAN decoders (generators/hifigan_mrf.py:120-230, refinegan.py:158-236)
     on the per-sample f0 [B, N, 1]; eps = randn_like(sine_waves) [B, N, H], rand_ini = torch.rand(B, H).
-    torch.cumsum of float32 on CPU accumulates in double: written so here."""
+    torch.cumsum of float32 on CPU accumulates in double: written so here. The source is built in float32 whatever the
+    dtype of the weights (its phase-wrap decisions are discrete and the reference's are float32's); its output is cast
+    to the weights' dtype before l_linear, so the rest of the generator follows the dtype (tests/parity_anchor.py)."""
     B, N, _ = f0_up.shape
+    f0_up, eps, rand_ini = f0_up.float(), eps.float(), rand_ini.float()
     f0_buf = torch.zeros(B, N, harmonics, dtype=torch.float32)
     f0_buf[:, :, 0] = f0_up[:, :, 0]
     for idx in range(harmonics - 1):
@@ -256,7 +259,7 @@ def harmonic_source(f0_up: Tensor, sr: int, harmonics: int, eps: Tensor, rand_in
     sines = torch.sin(torch.cumsum((rad + shift).double(), dim=1).float() * 2 * np.pi) * 0.1
     uv = (f0_up > 0).float()
     amp = uv * 0.003 + (1 - uv) * 0.1 / 3
-    sw = sines * uv + amp * eps
+    sw = (sines * uv + amp * eps).to(lin_w.dtype)
     return torch.tanh(F.linear(sw, lin_w, lin_b))  # [B, N, 1]
 
 

@@ -102,13 +102,17 @@ def check_each(points):
 SIDS = (3, 0, 108)  # the speaker gather beyond row 0, up to the table's last row (spk_embed_dim 109)
 
 
-def synth_case(lengths, seed, rate=None, upp=480, inter=192):
+def synth_case(lengths, seed, rate=None, upp=480, inter=192, cfg=None):
     """Synthesizer.infer inputs for B = len(lengths) rows of T = lengths[0] frames (PCG64): coarse pitch holding both
     1 and 255 (when there are two frames to hold them), f0 with a voiced/unvoiced/voiced run in row 0 and the last
-    row of a batch fully unvoiced, eps_src over the frames the decoder runs on."""
+    row of a batch fully unvoiced, eps_src over the frames the decoder runs on. With `cfg` (a SynthConfig) the phone
+    width, upp and the latent width are the configuration's."""
     rng = np.random.Generator(np.random.PCG64(seed))
     B, T = len(lengths), int(lengths[0])
-    phone = rng.standard_normal((B, T, 768)).astype(np.float32)
+    width = 768
+    if cfg is not None:
+        width, upp, inter = cfg.text_enc_hidden_dim, cfg.upp, cfg.inter_channels
+    phone = rng.standard_normal((B, T, width)).astype(np.float32)
     pitch = rng.integers(1, 256, size=(B, T)).astype(np.int64)
     pitch.reshape(-1)[-1] = 255
     if pitch.size > 1:
@@ -143,11 +147,13 @@ def rmvpe_fn(w, audio):
     return lambda dt: orm.mel2hidden(weights(w, dt), RMVPE_CFG, orm.mel_spectrogram(a.to(dt)))
 
 
-def synth_fn(w, phone, lengths, pitch, f0, sid, eps_z, eps_src, rate=None):
+def synth_fn(w, phone, lengths, pitch, f0, sid, eps_z, eps_src, rate=None, cfg=None):
     """fn(dtype) = Synthesizer.infer's {o [B, T' upp], z_p, z [B, T', I], m_p, logs_p [B, T, I]} in the device's
-    time-major layout."""
+    time-major layout, for the configuration `cfg` (default SYNTH_48K_V2)."""
     from oracle import synth as osynth
     from rvcx.config import SYNTH_48K_V2
+
+    cfg = SYNTH_48K_V2 if cfg is None else cfg
 
     f = lambda x: _t(np.asarray(x, np.float32))  # noqa: E731
     i = lambda x: _t(np.asarray(x, np.int64))  # noqa: E731
@@ -155,7 +161,7 @@ def synth_fn(w, phone, lengths, pitch, f0, sid, eps_z, eps_src, rate=None):
     lengths, pitch, sid = i(lengths), i(pitch), i(sid)
 
     def fn(dt):
-        o, _, (z, z_p, m_p, logs_p) = osynth.synth_infer(weights(w, dt), SYNTH_48K_V2, phone.to(dt), lengths, pitch,
+        o, _, (z, z_p, m_p, logs_p) = osynth.synth_infer(weights(w, dt), cfg, phone.to(dt), lengths, pitch,
                                                          f0.to(dt), sid, eps_z.to(dt), eps_src.to(dt), rate)
         tm = lambda x: x.transpose(1, 2)  # noqa: E731
         return {"o": o.reshape(o.shape[0], -1), "z_p": tm(z_p), "z": tm(z), "m_p": tm(m_p), "logs_p": tm(logs_p)}
@@ -163,16 +169,18 @@ def synth_fn(w, phone, lengths, pitch, f0, sid, eps_z, eps_src, rate=None):
     return fn
 
 
-def dec_fn(w, z, f0, sid, eps_src):
-    """z [B, I, T] float32 -> fn(dtype) = the generator's waveform [B, T upp]."""
+def dec_fn(w, z, f0, sid, eps_src, cfg=None):
+    """z [B, I, T] float32 -> fn(dtype) = the generator's waveform [B, T upp], for `cfg` (default SYNTH_48K_V2)."""
     from oracle import synth as osynth
     from rvcx.config import SYNTH_48K_V2
+
+    cfg = SYNTH_48K_V2 if cfg is None else cfg
 
     z, f0, eps_src = (_t(np.asarray(x, np.float32)) for x in (z, f0, eps_src))
     sid = _t(np.asarray(sid, np.int64))
 
     def fn(dt):
-        o = osynth.dec_only(weights(w, dt), SYNTH_48K_V2, z.to(dt), f0.to(dt), sid, eps_src.to(dt))
+        o = osynth.dec_only(weights(w, dt), cfg, z.to(dt), f0.to(dt), sid, eps_src.to(dt))
         return o.reshape(o.shape[0], -1)
 
     return fn

@@ -9,7 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+import parity_anchor as pa
 from conftest import golden
+from parity_anchor import K, anchor, check_each
+from test_gpu_models import anchored
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +55,18 @@ def test_nof0_synth_vs_reference(nof0_engine):
     assert rel_err(o, ref) < 2e-3, rel_err(o, ref)
     for b in range(o.shape[0]):
         assert spectrogram_correlation(o[b], ref[b]) > 0.999
+    # beside the fixed bars: the same inputs on the oracle in float64 (tests/parity_anchor.py). The device within
+    # K = 8 gaps of float64 and within (K + 1) of the stored fp32 output, as test_gpu_models.py holds the NSF fixtures.
+    # The no-f0 TextEncoder takes no pitch and the plain HiFiGANGenerator no f0 or source noise: zeros stand in.
+    B, T = g["phone"].shape[:2]
+    anc = anchor(pa.synth_fn(nof0_engine[1], g["phone"], g["lengths"], np.zeros((B, T), np.int64),
+                             np.zeros((B, T), np.float32), g["sid"], g["eps_z"], np.zeros(1, np.float32),
+                             cfg=nof0_engine[2]))
+    dev = {"z_p": zp.cpu().numpy(), "z": z.cpu().numpy(), "o": o}
+    check_each([(f"synth_nof0_b2 {k} device vs fp64", dev[k], *anc[k], K) for k in ("z_p", "z", "o")])
+    anchored("synth_nof0_b2 z_p", dev["z_p"], g["z_p"].transpose(0, 2, 1), *anc["z_p"], 1e-4)
+    anchored("synth_nof0_b2 z", dev["z"], g["z"].transpose(0, 2, 1), *anc["z"], 1e-4)
+    anchored("synth_nof0_b2 o", o, g["o"], *anc["o"], 2e-3)
 
 
 def test_nof0_pipeline_vs_oracle(nof0_engine, hubert_w, rmvpe_w):

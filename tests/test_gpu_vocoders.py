@@ -2,14 +2,19 @@
 (tests/golden/make_golden_vocoders.py) and the CPU oracle:
   * MRF HiFi-GAN (synthesizers.py:86-98, generators/hifigan_mrf.py): 9-harmonic per-sample source
     (source_harm.hip, exact double-accumulated phase scans), MRF blocks on the conv kernels, conv_post bias.
-Bars: latents rel <= 1e-4, waveform rel <= 2e-3 and spectrogram corr >= 0.999 (the NSF synth test's bar)."""
+Bars: latents rel <= 1e-4, waveform rel <= 2e-3 and spectrogram corr >= 0.999 (the NSF synth test's bar); the MRF
+fixture also on the float64 anchor (tests/parity_anchor.py). RefineGAN stays on its fixture bars: its oracle holds more
+fixed-dtype pieces (the kaiser-sinc resampling branch)."""
 import dataclasses
 
 import numpy as np
 import pytest
 import torch
 
+import parity_anchor as pa
 from conftest import golden
+from parity_anchor import K, anchor, check_each
+from test_gpu_models import anchored
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +56,16 @@ def test_mrf_synth_vs_reference(mrf_engine):
     assert rel_err(o, ref) < 2e-3, rel_err(o, ref)
     for b in range(o.shape[0]):
         assert spectrogram_correlation(o[b], ref[b]) > 0.999
+    # beside the fixed bars: the same inputs on the oracle in float64 (tests/parity_anchor.py; the 9-harmonic source
+    # stays float32 in both oracle runs, oracle.synth.harmonic_source). The device within K = 8 gaps of float64 and
+    # within (K + 1) of the stored fp32 output, as test_gpu_models.py holds the NSF fixtures.
+    anc = anchor(pa.synth_fn(mrf_engine[1], g["phone"], g["lengths"], g["pitch"], g["f0"], g["sid"], g["eps_z"],
+                             g["eps_src"], cfg=mrf_engine[2]))
+    dev = {"z_p": zp.cpu().numpy(), "z": z.cpu().numpy(), "o": o}
+    check_each([(f"synth_mrf_b2 {k} device vs fp64", dev[k], *anc[k], K) for k in ("z_p", "z", "o")])
+    anchored("synth_mrf_b2 z_p", dev["z_p"], g["z_p"].transpose(0, 2, 1), *anc["z_p"], 1e-4)
+    anchored("synth_mrf_b2 z", dev["z"], g["z"].transpose(0, 2, 1), *anc["z"], 1e-4)
+    anchored("synth_mrf_b2 o", o, g["o"], *anc["o"], 2e-3)
 
 
 def test_mrf_generated_noise_is_seeded(mrf_engine):
