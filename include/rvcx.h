@@ -499,6 +499,36 @@ int rvcx_rt_process(rvcx_ctx* ctx, rvcx_rt* rt, const float* d_in, const int32_t
 int rvcx_rt_process_v(rvcx_ctx* ctx, rvcx_rt* rt, const float* d_in, const int32_t* sids, const rvcx_rt_opts* opts,
                       const uint8_t* active, const float* d_eps_z, const float* d_eps_src, uint64_t seed,
                       float* d_out, float* d_vol, int32_t* d_offs, void* stream);
+/* Realtime(..., clean_audio, clean_strength) (rvc/realtime/core.py:86-94: arguments of the constructor, not of
+ * on_request) for one stream of the group, or for all of them with stream_index = -1: clean_audio != 0 sends that
+ * stream's model output through the noise gate (rvcx_spectral_gate at the model's sampling rate, prop_decrease =
+ * clean_strength) on every hop from now on, 0 (the state a group is created in) turns it off. A setting of the slot,
+ * like its sid: rvcx_rt_reset and rvcx_rt_reset_stream leave it, and rvcx_rt_opts keeps its layout.
+ * The rows that clean are gated after the clip and the volume envelope and before the sqrt(vol) scale, the output
+ * resample and SOLA, as pipeline.py:326-327 does; the other rows and idle slots are untouched. The gate's statistics
+ * run over the whole model row, so on a hop where an active stream cleans the generator runs full-length (no output
+ * window). gen_precision is independent of it.
+ * RVCX_E_INVALID, with no stream's setting changed and nothing launched, for a stream_index outside [-1, n_streams),
+ * a clean_strength outside [0, 1], a model row (frames * upp) shorter than 2048 samples, or a geometry in which a
+ * sample SOLA reads (through the output resampler's kernel when the model does not run at 48 kHz) would come from the
+ * gate's zeroed tail [256 * (n_model / 256), n_model): a hop therefore never meets a setting it has to refuse. */
+int rvcx_rt_set_clean(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, int clean_audio, double clean_strength);
+
+/* The noise gate on its own: noisereduce.torchgate.TorchGate(sr, nonstationary=False, prop_decrease=strength) as
+ * rvc/realtime/core.py:86-94 builds it and rvc/realtime/pipeline.py:326-327 calls it (no separate noise clip):
+ * STFT (n_fft = win = 1024, hop 256, periodic Hann, centred with zero padding), per (row, bin) a threshold of
+ * mean + 1.5 std (unbiased) over the frames of 20 log10(|X| + eps) clamped to its maximum - 40 dB, the mask
+ * smoothed by the 500 Hz x 50 ms triangle filter, inverse STFT.
+ * d_x [B][n] (rows ldx apart) -> d_y [B][n] (rows ldy apart): samples [0, n_out), n_out = 256 * (n / 256), are the
+ * gate's output (torch.istft's length) and samples [n_out, n) are written as zeros. strength: host [B], each row's
+ * prop_decrease in [0, 1]; a negative entry copies that row through unchanged (all n samples). d_mask (optional):
+ * [B][513][1 + n / 256] bytes, 1 where a bin is above its threshold (rows copied through are not written).
+ * All rows share each launch (four launches whatever B is); the overlap-add is a fixed-order gather, so a call gives
+ * the same bits every time. RVCX_E_SHAPE for n < 2048 or an sr whose smoothing filter is empty (int(500 / (sr / 512))
+ * < 1 or int(50 / (256 / sr * 1000)) < 1), RVCX_E_INVALID for a strength above 1; nothing is launched then. */
+int rvcx_spectral_gate(rvcx_ctx* ctx, const float* d_x, int B, int64_t n, int64_t ldx, int sr, const float* strength,
+                       float* d_y, int64_t ldy, uint8_t* d_mask, void* stream);
+
 /* rvcx_rt_reset for one slot: its audio / convert / pitch / pitchf buffers and SOLA tail zeroed, asynchronous on
  * `stream`, the other slots untouched. RVCX_E_INVALID when stream_index is not in [0, n_streams). */
 int rvcx_rt_reset_stream(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, void* stream);

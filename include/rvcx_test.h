@@ -54,6 +54,12 @@ int rvcx_kmeans_assign(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const 
 int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const int32_t* d_assign, int64_t nlist,
                        float* d_cent, int64_t* d_sizes, void* stream);
 
+/* The model rows of the group's last hop, [B_act][frames * upp] (the active streams in slot order), copied to d_dst
+ * (rows ld >= frames * upp apart): gated = 0 the rows as the noise gate read them (after the clip and the volume
+ * envelope), gated = 1 as the * sqrt(vol) / resample / SOLA stage read them (the gate's output; the same rows on a hop
+ * where no stream cleans). Valid until the context's next compute call. RVCX_E_STATE before the first hop. */
+int rvcx_rt_model_rows(rvcx_ctx* ctx, rvcx_rt* rt, int gated, float* d_dst, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

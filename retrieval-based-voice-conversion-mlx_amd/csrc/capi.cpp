@@ -1488,6 +1488,40 @@ int rvcx_rt_default_opts(rvcx_rt_opts* o) {
   return RVCX_OK;
 }
 
+int rvcx_spectral_gate(rvcx_ctx* ctx, const float* d_x, int B, int64_t n, int64_t ldx, int sr, const float* strength,
+                       float* d_y, int64_t ldy, uint8_t* d_mask, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_x || !d_y || !strength || B < 1 || B > 65535 || n < 0 || ldx < n || ldy < n)
+      throw Error(RVCX_E_INVALID, "spectral_gate: bad arguments");
+    spectral_gate_check(n, sr);
+    std::vector<float> p((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      if (!(strength[b] <= 1.f)) throw Error(RVCX_E_INVALID, "spectral_gate: strength above 1 (or NaN)");
+      p[b] = strength[b] < 0.f ? -1.f : strength[b];
+    }
+    set_device(ctx);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float* dp = ctx->buf<float>("sg.strength", (size_t)B, st);
+    RVCX_HIP(hipMemcpyAsync(dp, p.data(), sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
+    spectral_gate_run(*ctx, d_x, B, n, ldx, sr, dp, d_y, ldy, d_mask, st);
+  });
+}
+
+int rvcx_rt_set_clean(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, int clean_audio, double clean_strength) {
+  return guard(ctx, [&] {
+    if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_set_clean: null stream group");
+    rt_set_clean(*ctx, *rt->s, stream_index, clean_audio, clean_strength);
+  });
+}
+
+int rvcx_rt_model_rows(rvcx_ctx* ctx, rvcx_rt* rt, int gated, float* d_dst, int64_t ld, void* stream) {
+  return guard(ctx, [&] {
+    if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_model_rows: null stream group");
+    RVCX_HIP(hipSetDevice(ctx->device));  // not a compute call: the pool the rows lie in is left as the hop left it
+    rt_model_rows(*rt->s, gated, d_dst, ld, static_cast<hipStream_t>(stream));
+  });
+}
+
 int rvcx_rt_create(rvcx_ctx* ctx, const rvcx_rt_desc* desc, rvcx_rt** out) {
   return guard(ctx, [&] {
     if (!desc || !out) throw Error(RVCX_E_INVALID, "rt_create: null argument");

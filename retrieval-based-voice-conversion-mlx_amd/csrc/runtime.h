@@ -404,6 +404,18 @@ int rt_streams(const RtState& s);
 void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts* opts,
                 const uint8_t* active, const float* eps_z, const float* eps_src, uint64_t seed, float* out48,
                 float* vol_out, int* offs_out, hipStream_t st);
+// The noise gate of the realtime path (TorchGate's stationary mode; kernels in spectral_gate.hip) over x [B][n] ->
+// y [B][n], samples [256 (n / 256), n) zeros; d_strength [B] on the device, negative = the row is copied through;
+// mask_out (optional) [B][513][1 + n / 256]. spectral_gate_check throws RVCX_E_SHAPE for n < 2048 or a sampling rate
+// whose smoothing filter is empty, and launches nothing.
+void spectral_gate_check(int64_t n, int sr);
+void spectral_gate_run(Ctx& c, const float* x, int B, int64_t n, int64_t ldx, int sr, const float* d_strength,
+                       float* y, int64_t ldy, uint8_t* mask_out, hipStream_t st);
+// the noise gate of one slot (b = -1: every slot) on or off; throws RVCX_E_INVALID and changes nothing for a strength
+// outside [0, 1] or a geometry the gate cannot serve (runtime_stream.cpp)
+void rt_set_clean(Ctx& c, RtState& s, int b, int clean_audio, double clean_strength);
+// the last hop's model rows [B_act][frames * upp] before (gated = 0) or after (1) the noise gate -> dst (rows ld apart)
+void rt_model_rows(const RtState& s, int gated, float* dst, int64_t ld, hipStream_t st);
 // index (index_ivf.cpp)
 struct ParsedIvf {  // a validated faiss IndexIVFFlat image on the host (lists in list order)
   int d = 0, nprobe = 1;

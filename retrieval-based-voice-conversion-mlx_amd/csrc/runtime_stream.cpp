@@ -10,7 +10,7 @@
 // and the RMS gate, RMVPE or FCPE f0 (rvcx_rt_desc::f0_method; one batched forward over the B convert buffers either
 // way) + realtime quantisation into the circular pitch buffers, HuBERT (+ repeated
 // last frame), optional index retrieval from skip_head // 2, x2 upsample + protect, one batched
-// Synthesizer.infer over the B streams, clip, [volume envelope], * sqrt(vol), [tgt -> 48k resample],
+// Synthesizer.infer over the B streams, clip, [volume envelope], [noise gate], * sqrt(vol), [tgt -> 48k resample],
 // SOLA offset search + crossfade. The host only plans (and syncs once per hop for proposed_pitch).
 //
 // Every option is per slot (one rvcx_rt_opts each), and a slot may sit a hop out. The networks run on the B_act active
@@ -74,6 +74,7 @@ SincKernel sinc_kernel(int orig_freq, int new_freq) {
 // entries valid unless noted): uploaded once per hop, `factor` again after the proposed-pitch sync.
 struct RowPlan {
   size_t factor, strength, protect, rate, one_minus_rate, rms, autotune, use_protect, seqs, meta, slot2row, row2slot;
+  size_t clean;
   size_t bytes;
   explicit RowPlan(int B) {
     size_t o = 0;
@@ -94,6 +95,7 @@ struct RowPlan {
     meta = take(sizeof(int32_t), 2);   // lengths [B_act] at 0, sids [B_act] at B
     slot2row = take(sizeof(int), 1);   // [B], -1 = idle
     row2slot = take(sizeof(int), 1);
+    clean = take(sizeof(float), 1);    // clean_strength where clean_audio is set, else -1 (the gate copies the row)
     bytes = o;
   }
 };
@@ -126,7 +128,87 @@ struct RtState {
   int cur = 0;
   int f0_method = 0;  // 0 RMVPE, 1 FCPE (rvcx_rt_desc)
   float fcpe_thr = 0.006f;
+  // the last hop's model rows [last_rows][last_n] as the noise gate read them and as it left them (the same buffer on
+  // a hop without a cleaning stream): pool buffers of the context, valid until its next call (rvcx_rt_model_rows)
+  const float *last_model = nullptr, *last_gated = nullptr;
+  int last_rows = 0;
+  int64_t last_n = 0;
+  // per slot: the noise gate's strength (rt_set_clean), negative = the slot does not clean. A setting of the slot like
+  // its sid, not hop state: rt_reset / rt_reset_stream leave it.
+  std::vector<float> clean;
 };
+
+// TorchGate's filter half widths as Python's double arithmetic gives them: n_grad_freq = int(500 / (sr / (n_fft / 2))),
+// n_grad_time = int(50 / ((hop / sr) * 1000)) bins / frames
+static void sg_filter_sizes(int sr, int& nf, int& nt) {
+  nf = (int)(500.0 / ((double)sr / 512.0));
+  nt = (int)(50.0 / ((256.0 / (double)sr) * 1000.0));
+}
+
+void spectral_gate_check(int64_t n, int sr) {
+  if (n < 2 * SG_NFFT) throw Error(RVCX_E_SHAPE, "spectral_gate: needs at least 2048 samples per row");
+  int nf = 0, nt = 0;
+  if (sr > 0) sg_filter_sizes(sr, nf, nt);
+  if (sr <= 0 || nf < 1 || nt < 1 || nf > SG_MAX_HALF || nt > SG_MAX_HALF)
+    throw Error(RVCX_E_SHAPE, "spectral_gate: the sampling rate gives an empty smoothing filter");
+}
+
+void spectral_gate_run(Ctx& c, const float* x, int B, int64_t n, int64_t ldx, int sr, const float* d_strength,
+                       float* y, int64_t ldy, uint8_t* mask_out, hipStream_t st) {
+  spectral_gate_check(n, sr);
+  int nf = 0, nt = 0;
+  sg_filter_sizes(sr, nf, nt);
+  if (!c.dev.count("sg.tables")) {  // the twiddles and the window, once per context
+    std::vector<float> tab(SG_TAB_FLOATS);
+    sg_tables(tab.data());
+    c.alloc_weight("sg.tables", tab);
+  }
+  const float* tab = static_cast<const float*>(c.dev["sg.tables"]->p);
+  const size_t cells = (size_t)B * (size_t)sg_frames(n) * SG_BINS;
+  float* X = c.buf<float>("sg.X", 2 * cells, st);
+  float* db = c.buf<float>("sg.db", cells, st);
+  uint8_t* mask = c.buf<uint8_t>("sg.mask", cells, st);
+  float* frames = c.buf<float>("sg.frames", (size_t)B * (size_t)sg_frames(n) * SG_NFFT, st);
+  check(spectral_gate(x, ldx, n, d_strength, nf, nt, tab, X, db, mask, frames, y, ldy, mask_out, B, st),
+        "spectral_gate");
+}
+
+// Realtime(..., clean_audio, clean_strength) of one slot (core.py:86-94), or of every slot (b = -1). Refused, with no
+// slot changed: a strength outside [0, 1] (TorchGate asserts it), a model row shorter than the gate's 2048 samples, and
+// a geometry in which a sample SOLA reads (a[off + j], off <= sola48, j < block48 + cross48) would come from the tail
+// [256 * (n_model / 256), n_model) that the gate writes as zeros -- for tgt_sr != 48000 through the output resampler,
+// whose sample j reads the model's samples up to (j / nw) * orig + width + orig - 1 (k_rt_resample).
+void rt_set_clean(Ctx& c, RtState& s, int b, int clean_audio, double clean_strength) {
+  if (b < -1 || b >= s.B) throw Error(RVCX_E_INVALID, "stream: stream_index out of range");
+  float v = -1.f;
+  if (clean_audio) {
+    if (!(clean_strength >= 0.0 && clean_strength <= 1.0))
+      throw Error(RVCX_E_INVALID, "stream: clean_strength must lie in [0, 1]");
+    const int64_t n_model = (int64_t)s.feat * c.scfg.upp();
+    if (n_model < 2 * SG_NFFT) throw Error(RVCX_E_INVALID, "stream: clean_audio needs a model row of 2048 samples");
+    try {
+      spectral_gate_check(n_model, s.tgt_sr);
+    } catch (const Error& e) {
+      throw Error(RVCX_E_INVALID, std::string("stream: clean_audio: ") + e.what());
+    }
+    const int64_t last48 = (int64_t)s.sola48 + s.block48 + s.cross48 - 1;
+    const int64_t last_model =
+        s.out_identity ? last48 : (last48 / s.kout.nw) * s.kout.orig + s.kout.width + s.kout.orig - 1;
+    if (last_model >= sg_n_out(n_model))
+      throw Error(RVCX_E_INVALID, "stream: clean_audio: SOLA would read the gate's zeroed tail in this geometry");
+    v = (float)clean_strength;
+  }
+  for (int i = 0; i < s.B; ++i)
+    if (b < 0 || i == b) s.clean[(size_t)i] = v;
+}
+
+void rt_model_rows(const RtState& s, int gated, float* dst, int64_t ld, hipStream_t st) {
+  if (!s.last_model || s.last_rows < 1) throw Error(RVCX_E_STATE, "rt_model_rows: no hop with an active stream yet");
+  if (!dst || ld < s.last_n) throw Error(RVCX_E_INVALID, "rt_model_rows: null destination or ld below the row length");
+  RVCX_HIP(hipMemcpy2DAsync(dst, sizeof(float) * (size_t)ld, gated ? s.last_gated : s.last_model,
+                            sizeof(float) * (size_t)s.last_n, sizeof(float) * (size_t)s.last_n, (size_t)s.last_rows,
+                            hipMemcpyDeviceToDevice, st));
+}
 
 RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   if (!c.ready[0] || !c.ready[1]) throw Error(RVCX_E_STATE, "stream: synth and hubert must be finalized");
@@ -145,6 +227,7 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   const double AUDIO_SR = 48000.0, SR = 16000.0;
   const int window = 160;
   s.B = d.n_streams;
+  s.clean.assign((size_t)s.B, -1.f);
   s.f0_method = d.f0_method;
   s.fcpe_thr = d.fcpe_threshold > 0 ? d.fcpe_threshold : 0.006f;  // the realtime filter_radius (pipeline.py:155)
   // VoiceChanger.__init__ (core.py:351-354)
@@ -275,7 +358,8 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   const bool all = Ba == B;
   const bool guided = c.scfg.f0;  // no get_f0, pitch or protect without pitch guidance (pipeline.py:242-293)
   int n_ret = 0, n_prop = 0;
-  bool any_tune = false, any_rms = false;
+  bool any_tune = false, any_rms = false, any_clean = false;
+  const int64_t n_model = (int64_t)s.feat * upp;
   for (int r = 0; r < Ba; ++r) {
     const int b = row2slot[r];
     const rvcx_rt_opts& o = opts[b];
@@ -290,6 +374,7 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
     any_tune |= o.f0_autotune != 0;
     n_prop += (!o.f0_autotune && o.proposed_pitch) ? 1 : 0;
     any_rms |= o.volume_envelope != 1.0;
+    any_clean |= s.clean[b] >= 0.f;  // validated when it was set (rt_set_clean)
   }
   if (!all && eps_src && c.scfg.vocoder != 0)
     throw Error(RVCX_E_INVALID, "stream: injected source noise with idle slots needs the HiFi-GAN-NSF noise layout");
@@ -331,6 +416,7 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
     h_omr[r] = (float)(1.0 - o.index_rate);
     if (o.index_rate > 0) h_seqs[k++] = r;
     h_rms[r] = (float)o.volume_envelope;
+    reinterpret_cast<float*>(at(P.clean))[r] = s.clean[b];
     h_meta[r] = T;
     h_meta[B + r] = sids[b];
   }
@@ -442,7 +528,6 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
         "rt_up2");
   // 6. one batched Synthesizer.infer over the B_act rows (pipeline.py:295-297), clip (:93). Injected noise is
   // indexed by slot, so with idle slots the active slots' rows are gathered first.
-  const int64_t n_model = (int64_t)T * upp;
   if (!all && eps_z) {
     float* ez = c.buf<float>("rt.eps_z", (size_t)Ba * I * T, st);
     check(gather_rows(eps_z, I * T, d_r2s, ez, Ba, I * T, st), "rt_eps_z");
@@ -459,9 +544,10 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   {
     ScopedFullLengths full(c);  // every stream's hop is T frames (meta above)
     // k_rt_sola reads a[off + j], off <= sola48, j < block48 + cross48: the only reader of the model's output where
-    // it is neither resampled nor RMS-adjusted, so the generator runs on that window alone
+    // it is neither resampled nor RMS-adjusted nor gated (the gate's statistics run over the whole row), so the
+    // generator runs on that window alone
     DecWindow win;
-    if (s.out_identity && !any_rms && c.use_dec_window()) win = {0, n_need};
+    if (s.out_identity && !any_rms && !any_clean && c.use_dec_window()) win = {0, n_need};
     synth_forward(c, Ba, T, phone, dmeta, guided ? pitch : nullptr, guided ? pitchf : nullptr, dmeta + B, eps_z,
                   eps_src, seed, model, nullptr, nullptr, st, gen_precision, 0, nullptr, nullptr, win);
     if (win.s1 >= 0) n_clip = n_need;
@@ -473,6 +559,18 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
     check(change_rms_f32src_rows(conv, s.conv16, s.conv16, 16000, model, n_model, n_model, s.tgt_sr,
                                  reinterpret_cast<const float*>(dplan + P.rms), ws, Ba, st),
           "change_rms");
+  }
+  // the noise gate on the rows that ask for it (pipeline.py:326-327: after the volume envelope, before * sqrt(vol)),
+  // out of place; the other rows are copied through
+  s.last_model = s.last_gated = model;
+  s.last_rows = Ba;
+  s.last_n = n_model;
+  if (any_clean) {
+    float* gated = c.buf<float>("rt.model_clean", (size_t)Ba * n_model, st);
+    spectral_gate_run(c, model, Ba, n_model, n_model, s.tgt_sr, reinterpret_cast<const float*>(dplan + P.clean), gated,
+                      n_model, nullptr, st);
+    model = gated;
+    s.last_gated = gated;
   }
   // 7. * sqrt(vol) [-> 48 kHz], SOLA crossfade (core.py:324, :404-451)
   const float* a48 = model;

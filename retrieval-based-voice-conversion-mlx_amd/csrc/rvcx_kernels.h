@@ -444,6 +444,22 @@ hipError_t change_rms_f32src_rows(const float* src, long long ld_src, long long 
                                   long long ld_y, long long n_y, int sr_y, const float* rate, float* ws, int B,
                                   hipStream_t s);
 
+// The realtime noise gate (spectral_gate.hip: TorchGate's stationary mode, core.py:86-94 / pipeline.py:326-327) over
+// x [B][n] (rows ldx apart) -> y [B][n] (rows ldy apart): samples [0, sg_n_out(n)) gated, the rest zeros. strength
+// [B] on the device: prop_decrease per row, negative = the row is copied through. nf / nt: the smoothing filter's half
+// widths in bins / frames (1..SG_MAX_HALF). tab: sg_tables' floats on the device. Scratch per call: X [B][F][513][2],
+// db [B][F][513] floats, mask [B][F][513] bytes, frames [B][F][1024] floats, F = sg_frames(n). mask_out (optional)
+// [B][513][F]. Four launches whatever B is; needs n >= 2 * SG_NFFT.
+constexpr int SG_NFFT = 1024, SG_HOP = 256, SG_BINS = SG_NFFT / 2 + 1, SG_MAX_HALF = 64;
+constexpr int SG_TAB_FLOATS = 3 * SG_NFFT;
+inline long long sg_frames(long long n) { return 1 + n / SG_HOP; }
+inline long long sg_n_out(long long n) { return SG_HOP * (n / SG_HOP); }
+// twiddles exp(-2 pi i m / 1024) as [1024][2], then the periodic Hann window [1024]; computed in double (host)
+void sg_tables(float* tab);
+hipError_t spectral_gate(const float* x, long long ldx, long long n, const float* strength, int nf, int nt,
+                         const float* tab, float* X, float* db, unsigned char* mask, float* frames, float* y,
+                         long long ldy, unsigned char* mask_out, int B, hipStream_t s);
+
 // second-order-section filtfilt (iir_scan.hip): per-section tables in one device buffer
 struct SosPlan {
   int nsec = 0, L = 256;

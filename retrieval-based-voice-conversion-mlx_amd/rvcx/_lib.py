@@ -33,10 +33,11 @@ EXPORTS = [
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
     "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode", "rvcx_fcpe_b",
     "rvcx_index_default_build_opts", "rvcx_index_build", "rvcx_index_centroids", "rvcx_index_save",
+    "rvcx_spectral_gate", "rvcx_rt_set_clean",
 ]
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
 TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
-                "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update"]
+                "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update", "rvcx_rt_model_rows"]
 
 
 class RvcxLibraryError(ImportError):
@@ -223,6 +224,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_rt_process_v": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), P(ctypes.c_uint8), vp, vp, u64, vp, vp,
                                     vp, vp]),
         "rvcx_rt_reset_stream": (i32, [vp, vp, i32, vp]),
+        "rvcx_spectral_gate": (i32, [vp, vp, i32, i64, i64, i32, P(f32), vp, i64, vp, vp]),
+        "rvcx_rt_set_clean": (i32, [vp, vp, i32, i32, f64]),
+        "rvcx_rt_model_rows": (i32, [vp, vp, i32, vp, i64, vp]),
         "rvcx_device_status": (i32, [vp, vp]),
         "rvcx_index_parse": (i32, [vp, i64, P(i64), P(i64), P(i64), P(i64), ctypes.c_char_p, i64]),
         "rvcx_set_conv_math": (i32, [vp, i32]),

@@ -657,6 +657,37 @@ class Engine:
                                               1 if skip_unvoiced else 0, self.stream()), "f0_autotune")
         return f
 
+    def spectral_gate(self, x, sr: int, prop_decrease, return_mask: bool = False):
+        """The realtime path's noise gate (rvc/realtime/core.py:86-94: TorchGate(sr, prop_decrease=...), stationary,
+        no noise clip) on device: x [B, n] or [n] fp32 -> [B, 256 * (n // 256)], the length torch.istft returns, as the
+        reference's module does. prop_decrease: one strength in [0, 1] for every row, or one per row where a negative
+        entry copies that row through (its first n_out samples are returned). return_mask: also the bins above their
+        threshold, bool [B, 513, 1 + n // 256]. ValueError for a strength above 1."""
+        t = self.torch
+        xx = self._dev(x, t.float32)
+        xx = xx.reshape(1, -1) if xx.dim() == 1 else xx.reshape(-1, xx.shape[-1])
+        B, n = xx.shape
+        p = np.broadcast_to(np.asarray(prop_decrease, dtype=np.float64), (B,))
+        if not np.all(p <= 1.0):
+            raise ValueError(f"prop_decrease must lie in [0, 1], got {prop_decrease!r}")
+        strength = (ctypes.c_float * B)(*[float(v) for v in p])
+        y = t.empty((B, n), dtype=t.float32, device=self.device)
+        mask = t.zeros((B, 513, 1 + n // 256), dtype=t.uint8, device=self.device) if return_mask else None
+        self._check(self.lib.rvcx_spectral_gate(self.ctx, xx.data_ptr(), B, n, xx.stride(0), int(sr), strength,
+                                                y.data_ptr(), y.stride(0), _ptr(mask), self.stream()), "spectral_gate")
+        y = y[:, : 256 * (n // 256)]
+        return (y, mask.bool()) if return_mask else y
+
+    def rt_model_rows(self, group, rows: int, gated: bool):
+        """The model rows [rows, frames * upp] of a StreamGroup's last hop before (gated False) or after the noise
+        gate (rvcx_rt_model_rows, include/rvcx_test.h); rows = that hop's active streams."""
+        t = self.torch
+        n = group.geometry["frames"] * self.upp
+        out = t.empty((int(rows), n), dtype=t.float32, device=self.device)
+        self._check(self.lib.rvcx_rt_model_rows(self.ctx, group.handle, 1 if gated else 0, out.data_ptr(), n,
+                                                self.stream()), "rt_model_rows")
+        return out
+
     # ------------------------------------------------------------------ feature index (FAISS IVFFlat)
     def index_load(self, data: bytes):
         """Parse a faiss IndexIVFFlat file image and keep it in HBM (faiss.read_index, pipeline.py:430-434)."""

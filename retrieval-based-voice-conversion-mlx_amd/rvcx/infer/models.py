@@ -192,3 +192,22 @@ class PitchExtractor:
         if self.method == "fcpe":
             return self._model.get_f0(audio, f0_min=f0_min, f0_max=f0_max, threshold=kwargs.get("threshold", 0.006))
         return self._model.get_f0(audio, f0_min=f0_min, f0_max=f0_max, **kwargs)
+
+
+class SpectralGate:
+    """noisereduce.torchgate.TorchGate as rvc/realtime/core.py:86-94 constructs it -- TorchGate(sr,
+    prop_decrease=clean_strength): stationary, no noise clip -- on device: SpectralGate(sr, prop_decrease,
+    engine=...)(x [B, n]) -> a device tensor [B, 256 * (n // 256)], the length torch.istft gives the module.
+    prop_decrease outside [0, 1] raises ValueError (TorchGate asserts it)."""
+
+    def __init__(self, sr: int, prop_decrease: float = 1.0, engine: Engine = None):
+        if engine is None:
+            raise TypeError("SpectralGate needs the rvcx Engine it runs on (engine=...)")
+        if not 0.0 <= float(prop_decrease) <= 1.0:
+            raise ValueError(f"prop_decrease must lie in [0, 1], got {prop_decrease!r}")
+        self.sr, self.prop_decrease, self.engine = int(sr), float(prop_decrease), engine
+
+    def __call__(self, x):
+        return self.engine.spectral_gate(x, self.sr, self.prop_decrease)
+
+    forward = __call__

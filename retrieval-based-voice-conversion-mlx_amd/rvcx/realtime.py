@@ -8,8 +8,9 @@ PyTorch path's behaviour is the contract.
 ``StreamGroup`` converts B concurrent streams of one geometry per hop in one device call
 (``rvcx_rt_process_v``: resample, circular buffers, RMS gate, RMVPE or FCPE (``f0_method``), HuBERT, retrieval, one batched
 Synthesizer.infer, SOLA crossfade -- all HIP kernels). ``VoiceChanger`` is the one-stream, numpy-in /
-numpy-out object of the reference. Audio I/O, VAD, noise gate and pedalboard effects are not part of
-this path.
+numpy-out object of the reference. The noise gate of ``Realtime(..., clean_audio=True, clean_strength=...)``
+(core.py:86-94, pipeline.py:326-327) is a setting of each stream (``rvcx_rt_set_clean``), carried here by the options. Audio I/O, VAD and pedalboard effects are CPU
+libraries and not part of this path: ``vad_enabled=True`` / ``post_process=True`` raise instead of being dropped.
 
 A group's B slots are independent users: every hop takes one ``RtOpts`` for all of them or one per slot (each slot its
 own ``on_request`` arguments), a set of slots may sit a hop out (``active``), and ``reset(stream=i)`` clears one slot
@@ -70,6 +71,14 @@ def hop_arguments(n_streams: int, opts, active=None):
     return (_lib.RtOpts * n_streams)(*each), act  # the array holds copies
 
 
+def check_clean_strength(clean_strength) -> float:
+    """clean_strength as TorchGate's prop_decrease: a float in [0, 1], or ValueError (TorchGate asserts it)."""
+    v = float(clean_strength)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"clean_strength must lie in [0, 1], got {clean_strength!r}")
+    return v
+
+
 def check_slot(n_streams: int, stream) -> int:
     """A slot index of a group of n_streams, or ValueError."""
     if isinstance(stream, bool) or int(stream) != stream or not 0 <= int(stream) < n_streams:
@@ -82,12 +91,18 @@ class StreamGroup:
 
     f0_method "rmvpe" (the default) or "fcpe": the pitch network every hop runs, batched over the B convert buffers.
     "fcpe" uses the checkpoint loaded with ``Engine.load_fcpe`` (16 kHz, hop 160) and needs no RMVPE weights; its raw
-    local_argmax track is voiced where the frame maximum exceeds fcpe_threshold (the reference's 0.006)."""
+    local_argmax track is voiced where the frame maximum exceeds fcpe_threshold (the reference's 0.006).
+
+    clean_audio / clean_strength: the defaults ``opts()`` fills in -- the noise gate of Realtime(..., clean_audio=True,
+    clean_strength=0.5) on each stream's model output; ``opts(clean_audio=..., clean_strength=...)`` overrides them per
+    stream."""
 
     def __init__(self, engine: Engine, n_streams: int = 1, read_chunk_size: int = 192,
                  cross_fade_overlap_size: float = 0.1, extra_convert_size: float = 0.5,
-                 silent_threshold: float = -90.0, sid=0, f0_method: str = "rmvpe", fcpe_threshold: float = 0.006):
+                 silent_threshold: float = -90.0, sid=0, f0_method: str = "rmvpe", fcpe_threshold: float = 0.006,
+                 clean_audio: bool = False, clean_strength: float = 0.5):
         method = _f0_method_id(f0_method)
+        self.clean_audio, self.clean_strength = bool(clean_audio), check_clean_strength(clean_strength)
         if f0_method == "fcpe" and getattr(engine, "fcpe_cfg", None) is None:
             raise ValueError('f0_method "fcpe" needs an FCPE checkpoint on the Engine (Engine.load_fcpe)')
         self.engine = engine
@@ -112,6 +127,7 @@ class StreamGroup:
         t = engine.torch
         self.out = t.empty((self.n_streams, self.block_frame), dtype=t.float32, device=engine.device)
         self.vol = t.empty((self.n_streams,), dtype=t.float32, device=engine.device)
+        self._clean = [(0, 0.5)] * self.n_streams  # what the library holds per slot (rvcx_rt_set_clean); created off
         self.offs = t.empty((self.n_streams,), dtype=t.int32, device=engine.device)
 
     def close(self):
@@ -138,9 +154,13 @@ class StreamGroup:
 
     def opts(self, f0_up_key=0, index_rate=0.5, protect=0.5, volume_envelope=1.0, f0_autotune=False,
              f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0,
-             gen_precision: str = "fp32") -> _lib.RtOpts:
+             gen_precision: str = "fp32", clean_audio=None, clean_strength=None) -> _lib.RtOpts:
         """Per-hop options (rvcx_rt_opts). gen_precision "fp16" runs this hop's generator on fp16 operands (BASELINE
-        C5's half precision); the f0 / feature front end, TextEncoder and flow stay fp32-accurate either way."""
+        C5's half precision); the f0 / feature front end, TextEncoder and flow stay fp32-accurate either way.
+        clean_audio / clean_strength: None = the group's defaults; a strength outside [0, 1] raises ValueError. They
+        are not fields of rvcx_rt_opts (in the reference they are constructor arguments, and the struct keeps its
+        layout) but attributes of the returned object, which ``process`` hands to ``rvcx_rt_set_clean`` for the slots
+        whose setting changes; an RtOpts without them means the group's defaults."""
         o = _lib.RtOpts()
         self.engine.lib.rvcx_rt_default_opts(ctypes.byref(o))
         # rvc/realtime only retrieves when an index is loaded (pipeline.py:264); index_rate alone does not
@@ -150,7 +170,22 @@ class StreamGroup:
         o.f0_autotune_strength, o.proposed_pitch = float(f0_autotune_strength), int(bool(proposed_pitch))
         o.proposed_pitch_threshold = float(proposed_pitch_threshold)
         o.gen_precision = {"fp32": 0, "fp16": 1}[gen_precision]
+        o.clean_audio = int(self.clean_audio if clean_audio is None else bool(clean_audio))
+        o.clean_strength = self.clean_strength if clean_strength is None else check_clean_strength(clean_strength)
         return o
+
+    def _apply_clean(self, opts, active):
+        """Bring each active slot's noise gate setting to what its options ask for (no device work)."""
+        eng = self.engine
+        for b in range(self.n_streams):
+            if active is not None and not active[b]:
+                continue
+            o = opts if isinstance(opts, _lib.RtOpts) else opts[b]
+            want = (int(bool(getattr(o, "clean_audio", self.clean_audio))),
+                    check_clean_strength(getattr(o, "clean_strength", self.clean_strength)))
+            if want != self._clean[b]:
+                eng._check(eng.lib.rvcx_rt_set_clean(eng.ctx, self.handle, b, want[0], want[1]), "rt_set_clean")
+                self._clean[b] = want
 
     def process(self, audio_in, opts=None, eps_z=None, eps_src=None, seed: int = 0, active=None):
         """One hop: audio_in [B, block48] @48 kHz (device tensor or numpy) -> (out [B, block48] device tensor,
@@ -162,7 +197,9 @@ class StreamGroup:
         are zero. eps_z / eps_src rows are indexed by slot. ValueError for a wrong length or mixed gen_precision."""
         eng = self.engine
         t = eng.torch
-        arr, act = hop_arguments(self.n_streams, opts if opts is not None else self.opts(), active)
+        opts = self.opts() if opts is None else opts if isinstance(opts, _lib.RtOpts) else list(opts)
+        arr, act = hop_arguments(self.n_streams, opts, active)
+        self._apply_clean(opts, act)
         x = eng._dev(audio_in, t.float32).reshape(self.n_streams, self.block_frame)
         ez = None if eps_z is None else eng._dev(eps_z, t.float32)
         es = None if eps_src is None else eng._dev(eps_src, t.float32)
@@ -177,21 +214,27 @@ class VoiceChanger:
     """One realtime stream with the reference's API (rvc/realtime/core.py:329-484).
 
     ``VoiceChanger(read_chunk_size, cross_fade_overlap_size, extra_convert_size, engine=..., sid=0,
-    silent_threshold=0, f0_method="rmvpe")`` then ``on_request(audio_input @48k) -> (audio_out np.float32 [block], vol, [0, ms, 0])``.
+    silent_threshold=0, f0_method="rmvpe", clean_audio=False, clean_strength=0.5)`` then ``on_request(audio_input @48k) -> (audio_out np.float32 [block], vol, [0, ms, 0])``.
     Models come from the Engine (``rvcx.infer.RVCX(...).engine`` or an Engine loaded by hand); an index
     loaded on that Engine (``rvcx.infer.read_index``) is used when index_rate > 0. f0_method is the reference's
     "rmvpe" or "fcpe" (``Engine.load_fcpe``; fcpe_threshold as in StreamGroup); any other name raises ValueError.
+    clean_audio / clean_strength are the reference's (core.py:339-350): the noise gate on every hop's model output.
+    post_process=True and vad_enabled=True (pedalboard, webrtcvad: CPU libraries outside this path) raise ValueError;
+    the reference's remaining keywords are accepted and ignored.
     """
 
     def __init__(self, read_chunk_size: int, cross_fade_overlap_size: float, extra_convert_size: float,
                  engine: Engine = None, silent_threshold: int = 0, sid: int = 0, f0_method: str = "rmvpe",
-                 fcpe_threshold: float = 0.006, **_unused):
+                 fcpe_threshold: float = 0.006, clean_audio: bool = False, clean_strength: float = 0.5, **_unused):
         _f0_method_id(f0_method)
+        for name in ("post_process", "vad_enabled"):
+            if _unused.get(name):
+                raise ValueError(f"{name}=True is not supported: this path runs no CPU-side effects or VAD")
         if engine is None:
             raise ValueError("VoiceChanger needs an rvcx Engine with the synthesizer, HuBERT and the f0 method's "
                              "model (RMVPE or FCPE) loaded")
         self.group = StreamGroup(engine, 1, read_chunk_size, cross_fade_overlap_size, extra_convert_size,
-                                 silent_threshold, sid, f0_method, fcpe_threshold)
+                                 silent_threshold, sid, f0_method, fcpe_threshold, clean_audio, clean_strength)
         g = self.group.geometry
         self.block_frame, self.crossfade_frame = g["block48"], g["crossfade48"]
         self.sola_search_frame, self.extra_frame = g["sola_search48"], g["extra48"]
