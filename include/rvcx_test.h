@@ -41,6 +41,26 @@ int rvcx_set_dec_window(rvcx_ctx* ctx, int on);
  * window keeps per cut side): *frames. Host only, no context. */
 int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames);
 
+/* What the conv planner (csrc/conv_dispatch.hip conv_plan) decides for one contraction: the kernel family (*kind, a
+ * ConvKind as rvcx_profile_kind_name names them; the last one, "other": no family admits the form), its tile id
+ * (*tile, -1: the family has one form), the split over K (*ksplit) and the weight image the family reads
+ * (*wsplit_fmt: 0 three bf16 planes, 1 two fp16 planes, 2 the 3x3 small-channel image, -1 none). Host only: no
+ * context, no GPU; the descriptor's pointers are read for nullness and 16-byte alignment alone and its `route` is not
+ * read. form: the fields of the dispatcher's record a 1-D descriptor lacks (NULL = a plain 1-D form; for a 2-D
+ * contraction T_in / T_out are the image heights). static_weight: the weight is a constant tensor (the streamed
+ * kernels take only those). math: the context's arithmetic (rvcx_set_conv_math; 0 the default, 3 the fp16 split).
+ * plan_T: the rows the launch is planned for (0 = T_out). force_kind / force_tile: a forced family / tile, -1 the
+ * size policy's. */
+typedef struct rvcx_conv_plan_form {
+  int W_in, W_out, KH, KW, padh, padw; /* 2-D geometry (taps = KH * KW) */
+  int out_map, out_cv;                 /* 1: the 2x2-phase ConvTranspose2d scatter with out_cv real channels */
+  int b_kn, lowp;                      /* weights stored [C_in][N]; the reduced-precision opt-in */
+  int ldw;                             /* weight row stride, 0 = C_in */
+  int64_t w_ts, w_bs, bias_bs;         /* weight tap stride (0 = N * C_in), per-batch weight and bias strides */
+} rvcx_conv_plan_form;
+int rvcx_conv_plan(const rvcx_conv_test_desc* d, const rvcx_conv_plan_form* form, int two_d, int static_weight, int math,
+                   int plan_T, int force_kind, int force_tile, int* kind, int* tile, int* ksplit, int* wsplit_fmt);
+
 /* One nearest-centroid pass of the index build (csrc/kmeans.hip k_kmeans_assign; faiss IndexFlatL2::search with
  * k = 1 inside Clustering::train): d_x [n][d], d_cent [nlist][d] fp32 -> d_assign [n] = argmin_l |x - c_l|^2, ties to
  * the lowest l; d_dist [n] (optional) the squared distance to it. d % 32 == 0 and d <= 1024, else RVCX_E_SHAPE. */

@@ -44,6 +44,14 @@ static void fill_rand(std::vector<float>& v, unsigned seed) {
   for (auto& x : v) x = (float)rand() / RAND_MAX * 2.f - 1.f;
 }
 
+// the config numbers of the command line and the output: -1 the size policy, 0-9 the native fp32 tiles, 10-16 the
+// bf16-split tiles, 20-29 the weight-streamed tiles, 30-39 the gather-streamed ones, 40 the weight-stationary kernel
+static ConvForce force_of(int cfg, int pipe) {
+  if (cfg < 0) return ConvForce{-1, TILE_NONE, pipe};
+  const int kind = cfg < 10 ? CK_GEMM : (cfg < 20 ? CK_EMU : (cfg < 30 ? CK_WSB16 : (cfg < 40 ? CK_GS : CK_WST)));
+  return ConvForce{kind, cfg < 40 ? cfg : TILE_NONE, pipe};
+}
+
 struct Case {
   const char* name;
   int T, Cin, N, taps, dil;
@@ -92,17 +100,22 @@ int main(int argc, char** argv) {
         a.w = w; a.ldw = C; a.w_ts = (long long)N * C; a.taps = taps; a.dil = dil; a.pad = pad;
         a.y = y; a.ldy = N; a.T_out = T; a.N = N; a.bias = b;
         a.pre_act = ACT_LRELU; a.pre_slope = 0.1f;
-        a.force_cfg = cfg; a.pipe = pipe;
-        void* wsb = nullptr;
-        if (cfg >= 20) {  // weight-streamed split kernel: pre-split weight image
-          a.wsplit_fmt = fmt ? WSPLIT_H16 : WSPLIT_BF16;
+        a.no_splitk = 1;
+        if (cfg >= 20) {  // weight-streamed split kernel
+          a.math = fmt ? 3 : 2;
           a.lowp = fmt == 2;
+        }
+        const ConvForce force = force_of(cfg, pipe);
+        const ConvPlan plan = conv_plan(a, false, cfg >= 20, force);
+        void* wsb = nullptr;
+        if (plan.wsplit_fmt >= 0) {  // pre-split weight image
+          a.wsplit_fmt = plan.wsplit_fmt;
           CK_(hipMalloc(&wsb, conv_wsplit_bytes(a)));
           CK_(conv_wsplit_build(a, wsb, 0));
-          a.wsplit = wsb; a.wsplit_npad = conv_wsplit_npad(a.N); a.math = fmt ? 3 : 2; a.wsb = 1;
+          a.wsplit = wsb;
         }
         CK_(hipMemset(y, 0, (size_t)T * N * 4));
-        CK_(conv1d(a, 0));
+        CK_(conv_run(plan, a, false, 0, true));
         if (wsb) (void)hipFree(wsb);
         CK_(hipDeviceSynchronize());
         CK_(hipMemcpy(out.data(), y, out.size() * 4, hipMemcpyDeviceToHost));
@@ -147,12 +160,12 @@ int main(int argc, char** argv) {
       a.x = x; a.ldx = C; a.T_in = T; a.C_in = C;
       a.w = w; a.ldw = C; a.w_ts = (long long)N * C; a.taps = taps; a.dil = dil; a.pad = pad;
       a.y = y; a.ldy = N; a.T_out = T; a.N = N; a.bias = b;
-      a.pre_act = ACT_LRELU; a.pre_slope = 0.1f; a.pipe = pipe;
-      const long long need = conv_plan_splitk(a, false);
-      CK_(hipMalloc(&ws, (need > 0 ? need : 1) * 4));
+      a.pre_act = ACT_LRELU; a.pre_slope = 0.1f;
+      const ConvPlan plan = conv_plan(a, false, false, force_of(-1, pipe));
+      CK_(hipMalloc(&ws, (plan.slab_floats > 0 ? plan.slab_floats : 1) * 4));
       a.ws = ws;
       CK_(hipMemset(y, 0, (size_t)T * N * 4));
-      CK_(conv1d(a, 0));
+      CK_(conv_run(plan, a, false, 0));
       CK_(hipDeviceSynchronize());
       CK_(hipMemcpy(out.data(), y, out.size() * 4, hipMemcpyDeviceToHost));
       double md = 0, mr = 0;
@@ -160,7 +173,7 @@ int main(int argc, char** argv) {
         md = std::max(md, (double)fabsf(out[i] - ref[i]));
         mr = std::max(mr, (double)fabsf(ref[i]));
       }
-      printf("check splitk math=%d ksplit=%d pipe=%d max|diff|/max|ref| = %.3e %s\n", math, a.ksplit, pipe, md / mr,
+      printf("check splitk math=%d ksplit=%d pipe=%d max|diff|/max|ref| = %.3e %s\n", math, plan.ksplit, pipe, md / mr,
              md / mr < 1e-5 ? "OK" : "FAIL");
       (void)hipFree(ws);
     }
@@ -225,41 +238,44 @@ int main(int argc, char** argv) {
           a.act = ACT_NONE;
           a.res = rb; a.ldr = cs.N; a.res_mode = RES_ADD_POST; a.acc_mode = ACC_ADD;
         }
-        a.force_cfg = vv.cfg; a.pipe = vv.pipe; a.math = vv.math == 4 ? 3 : vv.math;
-        a.wsplit_fmt = vv.math >= 3 ? WSPLIT_H16 : WSPLIT_BF16;
+        a.math = vv.math == 4 ? 3 : vv.math;
         a.lowp = vv.math == 4;
+        a.no_splitk = vv.cfg >= 0;  // forced tiles run unsplit
         float* wsp = nullptr;
         void* wsb = nullptr;
-        if (vv.cfg >= 20) {
-          if (!conv_wsb_eligible(a)) break;
+        if (vv.cfg >= 20 && !conv_wsb_eligible(a)) break;
+        ConvForce force = force_of(vv.cfg, vv.pipe);
+        // a shape the weight-stationary kernel does not take: the weight-streamed tile of the size policy
+        if (force.kind == CK_WST && !conv_wst_fits(a, false)) force.kind = CK_WSB16;
+        const bool forced = force.kind >= 0;
+        const ConvPlan plan = conv_plan(a, false, vv.cfg >= 20, force);
+        if (plan.wsplit_fmt >= 0) {
+          a.wsplit_fmt = plan.wsplit_fmt;
           CK_(hipMalloc(&wsb, conv_wsplit_bytes(a)));
           CK_(conv_wsplit_build(a, wsb, 0));
-          a.wsplit = wsb; a.wsplit_npad = conv_wsplit_npad(a.N); a.wsb = 1;
+          a.wsplit = wsb;
         }
-        if (vv.cfg < 0) {
-          const long long need = conv_plan_splitk(a, false);
-          if (need > 0) { CK_(hipMalloc(&wsp, need * 4)); a.ws = wsp; }
-        }
-        if (conv1d(a, 0) != hipSuccess) {
+        if (plan.ksplit > 1) { CK_(hipMalloc(&wsp, plan.slab_floats * 4)); a.ws = wsp; }
+        if (conv_run(plan, a, false, 0, forced) != hipSuccess) {
           (void)hipGetLastError();
           if (wsp) (void)hipFree(wsp);
           if (wsb) (void)hipFree(wsb);
           break;
         }
-        for (int i = 0; i < 3; ++i) CK_(conv1d(a, 0));
+        for (int i = 0; i < 3; ++i) CK_(conv_run(plan, a, false, 0, forced));
         CK_(hipDeviceSynchronize());
         hipEvent_t e0, e1;
         CK_(hipEventCreate(&e0));
         CK_(hipEventCreate(&e1));
         CK_(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; ++i) CK_(conv1d(a, 0));
+        for (int i = 0; i < iters; ++i) CK_(conv_run(plan, a, false, 0, forced));
         CK_(hipEventRecord(e1, 0));
         CK_(hipEventSynchronize(e1));
         float ms = 0;
         CK_(hipEventElapsedTime(&ms, e0, e1));
         ms /= iters;
         best = std::max(best, flops / ms / 1e9);
-        ksp = a.ksplit;
+        ksp = plan.ksplit;
         if (wsp) (void)hipFree(wsp);
         if (wsb) (void)hipFree(wsb);
       }

@@ -79,19 +79,19 @@ int main(int argc, char** argv) {
       } else {
         a.T_in = sh.H; a.T_out = sh.H; a.pad = (sh.taps - 1) / 2;
       }
-      a.math = 2; a.w_static = 1; a.wsb = 2;
-      a.force_cfg = 30;
+      a.math = 2;
+      ConvPlan plan = conv_plan(a, sh.two_d != 0, true, ConvForce{CK_GS});
       void* wsb = nullptr;
+      a.wsplit_fmt = plan.wsplit_fmt;
       CK_(hipMalloc(&wsb, conv_wsplit_bytes(a)));
       CK_(conv_wsplit_build(a, wsb, 0));
-      a.wsplit = wsb; a.wsplit_npad = conv_wsplit_npad(a.N);
-      long long need = conv_plan_splitk(a, sh.two_d != 0);
-      const int plan_ks = a.ksplit;
+      a.wsplit = wsb;
+      long long need = plan.slab_floats;
+      const int plan_ks = plan.ksplit;
       if (ks > 0) {  // forced split count
         const int steps = (sh.C / 32) * sh.taps;
         if (ks > steps) { printf("  ks%-2d:   -   ", ks); (void)hipFree(wsb); continue; }
-        a.ksplit = ks;
-        a.ws_rows = rows;
+        plan.ksplit = ks;
         need = ks > 1 ? (long long)ks * rows * sh.N : 0;
       }
       float* ws = nullptr;
@@ -99,7 +99,7 @@ int main(int argc, char** argv) {
         CK_(hipMalloc(&ws, need * 4));
         a.ws = ws;
       }
-      auto run = [&]() { return sh.two_d ? conv2d(a, 0) : conv1d(a, 0); };
+      auto run = [&]() { return conv_run(plan, a, sh.two_d != 0, 0, true); };
       CK_(run());
       CK_(hipDeviceSynchronize());
       // warm: back to back

@@ -58,238 +58,6 @@ void set_device(rvcx_ctx* c) {
 
 }  // namespace
 
-namespace rvcx {
-hipStream_t Ctx::aux_stream() {
-  if (!aux) {
-    RVCX_HIP(hipSetDevice(device));
-    // (the aux stream at the device's least priority measured neutral: 18.22 vs 18.19 ms, round 3)
-    RVCX_HIP(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-    RVCX_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    RVCX_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-    RVCX_HIP(hipEventCreateWithFlags(&ev_gate, hipEventDisableTiming));
-  }
-  return aux;
-}
-
-unsigned* Ctx::device_status() {
-  if (!status_host) {
-    RVCX_HIP(hipSetDevice(device));
-    void* h = nullptr;
-    RVCX_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
-    std::memset(h, 0, 64);
-    status_host = static_cast<unsigned*>(h);
-    void* d = nullptr;
-    RVCX_HIP(hipHostGetDevicePointer(&d, h, 0));
-    status_dev = static_cast<unsigned*>(d);
-  }
-  return status_dev;
-}
-
-void Ctx::check_device_status() {
-  if (!status_host) return;
-  const unsigned v = __atomic_load_n(status_host, __ATOMIC_ACQUIRE);
-  if (v == 0) return;
-  __atomic_store_n(status_host, 0u, __ATOMIC_RELEASE);
-  std::string what;
-  if (v & 1u) what += "gru: partner hand-off timed out (the RMVPE BiGRU's workgroups were not co-resident); ";
-  throw Error(RVCX_E_HIP, what + "the outputs of the call that raised this flag are invalid");
-}
-
-Ctx::~Ctx() {
-  if (status_host) (void)hipHostFree(status_host);
-  for (auto& kv : call_ev)
-    if (kv.second) (void)hipEventDestroy(kv.second);
-  if (aux) {
-    (void)hipStreamSynchronize(aux);
-    (void)hipEventDestroy(ev_fork);
-    (void)hipEventDestroy(ev_join);
-    (void)hipEventDestroy(ev_gate);
-    (void)hipStreamDestroy(aux);
-  }
-}
-
-hipStream_t fork_aux(Ctx& c, hipStream_t s) {
-  static const bool no_overlap = [] {
-    const char* e = rvcx_knob("RVCX_NO_OVERLAP");
-    return e && std::atoi(e) != 0;
-  }();
-  if (c.prof || no_overlap) return s;
-  hipStream_t ax = c.aux_stream();
-  RVCX_HIP(hipEventRecord(c.ev_fork, s));
-  RVCX_HIP(hipStreamWaitEvent(ax, c.ev_fork, 0));
-  return ax;
-}
-
-void join_aux(Ctx& c, hipStream_t s, hipStream_t ax) {
-  if (ax == s) return;
-  RVCX_HIP(hipEventRecord(c.ev_join, ax));
-  RVCX_HIP(hipStreamWaitEvent(s, c.ev_join, 0));
-}
-
-// the weight tensor's pre-split image (built once on first use; the stream then synchronises so a later use on
-// another stream never races the build)
-const void* Ctx::wsplit_for(const ConvArgs& a, hipStream_t s) {
-  const auto key = std::make_tuple(static_cast<const void*>(a.w), a.ldw, a.w_ts, a.N, a.C_in, a.taps, a.wsplit_fmt);
-  auto& slot = wsplit_cache[key];
-  if (!slot) {
-    std::unique_ptr<DevBuf> b(new DevBuf());
-    const size_t bytes = (size_t)conv_wsplit_bytes(a);
-    if (hipMalloc(&b->p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      throw Error(RVCX_E_OOM, "split-weight allocation failed");
-    }
-    b->bytes = bytes;
-    check(conv_wsplit_build(a, b->p, s), "conv_wsplit_build");
-    RVCX_HIP(hipStreamSynchronize(s));
-    slot = std::move(b);
-  }
-  return slot->p;
-}
-
-const void* Ctx::rb_wsplit_for(const float* w, int C, int k, int wfmt, hipStream_t s) {
-  auto& slot = rb_wsplit_cache[{static_cast<const void*>(w), wfmt}];
-  if (!slot) {
-    std::unique_ptr<DevBuf> b(new DevBuf());
-    const size_t bytes = (size_t)rb_wsplit_bytes(C, k, wfmt);
-    if (hipMalloc(&b->p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      throw Error(RVCX_E_OOM, "split-weight allocation failed");
-    }
-    b->bytes = bytes;
-    check(rb_wsplit_build(w, C, k, b->p, s, wfmt), "rb_wsplit_build");
-    RVCX_HIP(hipStreamSynchronize(s));
-    slot = std::move(b);
-  }
-  return slot->p;
-}
-
-void launch_rb_pair(Ctx& c, const RbPairArgs& a, hipStream_t s) {
-  constexpr int cfg = 0;
-  if (!c.prof) {
-    check(rb_pair(a, cfg, s), "rb_pair");
-    return;
-  }
-  hipEvent_t ev[2];
-  for (auto& e : ev) {
-    if (!c.prof_pool.empty()) {
-      e = c.prof_pool.back();
-      c.prof_pool.pop_back();
-    } else {
-      RVCX_HIP(hipEventCreate(&e));
-    }
-  }
-  // algorithmic work: the two convs over the valid rows
-  const double flops = 2.0 * 2.0 * a.B * (double)a.T * a.C * a.C * a.k;
-  // x read, y written (+ read when accumulating), both weight tensors
-  const double bytes = 4.0 * ((double)a.B * a.T * a.C * (2 + (a.acc_mode != ACC_STORE ? 1 : 0)) + 2.0 * a.k * a.C * a.C);
-  Ctx::ProfRec r{ev[0], ev[1], flops, 0, a.T, a.C, a.C, -a.k, a.B, 1, bytes,
-                 a.wfmt == RB_WF16 ? (a.lowp ? Ctx::PEAK_F16 : Ctx::PEAK_F16X2) : Ctx::PEAK_SPLIT};
-  r.kind = CK_RBPAIR;
-  RVCX_HIP(hipEventRecord(r.a, s));
-  check(rb_pair(a, cfg, s), "rb_pair");
-  RVCX_HIP(hipEventRecord(r.b, s));
-  c.prof_recs.push_back(r);
-}
-
-bool conv_routes_wsb16(Ctx& c, const ConvArgs& a_in) {
-  ConvArgs b = a_in;
-  if (c.conv_math > 0 && b.math == 0) b.math = c.conv_math;
-  if (!(b.w_static || c.is_weight(b.w)) || b.force_cfg >= 0) return false;
-  if (!(conv_math_of(b) == 3 || b.lowp)) return false;  // the fp16 image (launch_conv below)
-  if (conv_wsb_route(b, false) != 1) return false;
-  b.wsb = 1;
-  return conv_plan_splitk(b, false) == 0 && conv_wsb_pick(b) >= 23;
-}
-
-void launch_conv(Ctx& c, const ConvArgs& a_in, bool two_d, hipStream_t s, double flops) {
-  ConvArgs a = a_in;
-  if (c.conv_math > 0 && a.math == 0) a.math = c.conv_math;
-  // weight-streamed kernel: forced (numerics tests / benchmarks: force_cfg >= 20 on a w_static weight) or routed by
-  // the policy for a packed (static) weight; decided before the split-K plan, whose geometry depends on it
-  const bool stat = a.w_static || c.is_weight(a.w);
-  a.wsb = !stat ? 0
-          : (a.force_cfg >= 30 && a.force_cfg < 40 ? 2
-             : (a.force_cfg >= 20 && !two_d) ? 1 : (a.force_cfg < 0 ? conv_wsb_route(a, two_d) : 0));
-  if (a.force_cfg == 40 && !two_d && stat) a.wsb = 1;  // the weight-stationary kernel (conv_wst.hip), forced
-  const long long need = conv_plan_splitk(a, two_d);
-  // the few-channel 3x3 convs' fp16-split form reads a pre-split image (conv2d_small.hip)
-  if (two_d && !a.wsb && stat && !a.wsplit && conv_math_of(a) == 3 && conv2d_small_fits(a)) {
-    a.wsplit_fmt = WSPLIT_S2D;
-    a.wsplit = c.wsplit_for(a, s);
-  }
-  if (a.wsb) {
-    // the weight-streamed kernel's fp16 image: the two-plane fp16 arithmetic (math 3) or the reduced-precision mode
-    if (!a.wsplit)
-      a.wsplit_fmt = ((a.wsb == 1 && a.lowp) || conv_math_of(a) == 3) ? WSPLIT_H16 : WSPLIT_BF16;
-    if (!a.wsplit) a.wsplit = c.wsplit_for(a, s);  // a caller-built image (rvcx_conv1d) is used as given
-    a.wsplit_npad = conv_wsplit_npad(a.N);
-  }
-  // split-K slabs are per stream: the aux stream's convs run concurrently with the caller's
-  // HuBERT's feature-encoder contractions (issued on the aux stream beside the U-Net, with ~1.5 ms of slack before the
-  // BiGRU) take 64 KB more LDS per workgroup: one or two of them per CU at most, so the U-Net's latency-bound chain
-  // finds free workgroup slots instead of waiting out ~50 us feature-conv workgroups. Same-box A/B (ms/step): r05ac
-  // none 13.53 / 13.47, 64 KB 13.28 / 13.35, 88 KB 13.25 / 13.27, 40 KB 13.39 / 13.51; r05ae none 13.53 / 13.54 /
-  // 13.48 / 13.51, 64 KB 13.39 / 13.16 / 13.37 / 13.33, 88 KB 13.48 / 13.29. Throttling HuBERT's transformer too
-  // (r05aa) costs +0.3-0.5 ms: it runs beside the BiGRU with little slack. RVCX_AUX_LDS=KB overrides (0: off)
-  static const int aux_lds = [] {
-    const char* e = rvcx_knob("RVCX_AUX_LDS");
-    return e ? std::max(0, std::atoi(e)) : 64;
-  }();
-  if (aux_lds > 0 && c.aux_front) a.lds_pad = aux_lds * 1024;
-  if (need > 0) {
-    a.ws = c.buf<float>(c.aux && s == c.aux ? "conv.splitk.aux" : "conv.splitk", (size_t)need, s);
-  }
-  if (flops < 0) {
-    const double M = two_d ? (double)a.T_out * a.W_out : (double)a.T_out;
-    flops = 2.0 * M * a.N * (double)a.C_in * a.taps * a.batch * a.batch_inner;
-  }
-  if (!c.prof) {
-    check(two_d ? conv2d(a, s) : conv1d(a, s), two_d ? "conv2d" : "conv1d");
-    return;
-  }
-  auto get_ev = [&]() {
-    hipEvent_t e;
-    if (!c.prof_pool.empty()) {
-      e = c.prof_pool.back();
-      c.prof_pool.pop_back();
-    } else {
-      RVCX_HIP(hipEventCreate(&e));
-    }
-    return e;
-  };
-  // input rows read once, weights once, output written once (+ read again for a residual / accumulate)
-  const double in_rows = two_d ? (double)a.T_in * a.W_in : (double)a.T_in;
-  const double out_el = (two_d ? (double)a.T_out * a.W_out : (double)a.T_out) * a.N * a.batch * a.batch_inner;
-  const double alg_bytes = 4.0 * (in_rows * a.C_in * a.batch * a.batch_inner + (double)a.taps * a.N * a.C_in +
-                                  out_el * (1 + (a.res && a.res_mode != RES_NONE ? 1 : 0) +
-                                            (a.acc_mode != ACC_STORE ? 1 : 0)));
-  // the launch's arithmetic ceiling (the rest of the family is priced at the bf16 split's, a lower bound for the few
-  // launches on the fp32-input MFMA)
-  const double peak = (a.wsb && a.wsplit_fmt == WSPLIT_H16) ? ((a.lowp && a.wsb == 1) ? Ctx::PEAK_F16 : Ctx::PEAK_F16X2)
-                      : (a.wsplit && a.wsplit_fmt == WSPLIT_S2D) ? Ctx::PEAK_F16X2
-                                                                  : Ctx::PEAK_SPLIT;
-  Ctx::ProfRec r{get_ev(), get_ev(), flops, two_d ? 1 : 0, two_d ? a.T_out * a.W_out : a.T_out, a.N, a.C_in,
-                 a.taps, a.batch * a.batch_inner, a.ksplit, alg_bytes, peak};
-  RVCX_HIP(hipEventRecord(r.a, s));
-  check(two_d ? conv2d(a, s) : conv1d(a, s), two_d ? "conv2d" : "conv1d");
-  r.kind = conv_last_kind();
-  RVCX_HIP(hipEventRecord(r.b, s));
-  c.prof_recs.push_back(r);
-}
-
-__global__ void k_set_i32(int32_t* p, int32_t v) { p[0] = v; }
-void set_i32(int32_t* p, int32_t v, hipStream_t s) {
-  hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, s, p, v);
-  check(hipGetLastError(), "set_i32");
-}
-void set_i32_once(Ctx& c, const std::string& name, int32_t* p, int32_t v, hipStream_t s) {
-  auto it = c.i32_marks.find(name);
-  if (it != c.i32_marks.end() && it->second.first == p && it->second.second == v) return;
-  set_i32(p, v, s);
-  c.i32_marks[name] = {p, v};
-}
-}  // namespace rvcx
-
 namespace {
 // the synthesizer configuration a descriptor names (rvcx_set_synth_config, rvcx_dec_margin_frames)
 SynthCfg synth_cfg_of(const rvcx_synth_desc* d) {
@@ -323,6 +91,26 @@ SynthCfg synth_cfg_of(const rvcx_synth_desc* d) {
   if (g.H % g.n_heads || g.I % 2 || g.C0 % (1 << g.ups.size()))
     throw Error(RVCX_E_INVALID, "inconsistent synthesizer dimensions");
   return g;
+}
+
+// the dispatcher's record of a 1-D test descriptor (rvcx_conv1d_ex, rvcx_conv_plan)
+ConvArgs conv_args_of(const rvcx_conv_test_desc* d) {
+  ConvArgs a;
+  a.x = d->x; a.x_bs = d->x_bs; a.x_bs2 = d->x_bs2; a.ldx = d->ldx; a.T_in = d->T_in; a.C_in = d->C_in;
+  a.pre_act = d->pre_act; a.pre_slope = d->pre_slope; a.pre_mask = d->pre_mask; a.pre_mask_bs = d->pre_mask_bs;
+  a.w = d->w; a.ldw = d->C_in; a.w_ts = (long long)d->N * d->C_in; a.w_bs2 = d->w_bs2;
+  a.taps = d->taps; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
+  a.y = d->y; a.y_bs = d->y_bs; a.y_bs2 = d->y_bs2; a.ldy = d->ldy; a.T_out = d->T_out; a.N = d->N;
+  a.bias = d->bias; a.bias_bs2 = d->bias_bs2; a.alpha = d->alpha; a.act = d->act; a.slope = d->slope;
+  a.res = d->res; a.res_bs = d->res_bs; a.res_bs2 = d->res_bs2; a.ldr = d->ldr; a.res_mode = d->res_mode;
+  a.mask = d->mask; a.mask_bs = d->mask_bs; a.acc_mode = d->acc_mode; a.acc_div = d->acc_div;
+  a.gate_h = d->gate_h; a.gate_g = d->gate_g; a.gate_g_bs = d->gate_g_bs;
+  a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps;
+  a.batch = d->batch; a.batch_inner = d->batch_inner;
+  a.nz_har = d->nz_har; a.nz_bs = d->nz_bs; a.nz_stride = d->nz_stride; a.nz_kk = d->nz_kk; a.nz_u = d->nz_u;
+  a.nz_C = d->nz_C; a.nz_w = d->nz_w; a.nz_b = d->nz_b;
+  a.no_splitk = d->no_splitk ? 1 : 0;
+  return a;
 }
 }  // namespace
 
@@ -952,6 +740,24 @@ int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames) {
   }
 }
 
+int rvcx_conv_plan(const rvcx_conv_test_desc* d, const rvcx_conv_plan_form* f, int two_d, int static_weight, int math,
+                   int plan_T, int force_kind, int force_tile, int* kind, int* tile, int* ksplit, int* wsplit_fmt) {
+  if (!d || !kind || !tile || !ksplit || !wsplit_fmt || math < 0 || math > 3 || (two_d && !f)) return RVCX_E_INVALID;
+  ConvArgs a = conv_args_of(d);
+  a.math = math;
+  a.plan_T = plan_T;
+  if (f) {
+    a.W_in = f->W_in; a.W_out = f->W_out; a.KH = f->KH; a.KW = f->KW; a.padh = f->padh; a.padw = f->padw;
+    a.out_map = f->out_map; a.out_cv = f->out_cv; a.b_kn = f->b_kn; a.lowp = f->lowp;
+    if (f->ldw > 0) a.ldw = f->ldw;
+    if (f->w_ts > 0) a.w_ts = f->w_ts;
+    a.w_bs = f->w_bs; a.bias_bs = f->bias_bs;
+  }
+  const ConvPlan p = conv_plan(a, two_d != 0, static_weight != 0, ConvForce{force_kind, force_tile});
+  *kind = p.kind, *tile = p.tile, *ksplit = p.ksplit, *wsplit_fmt = p.wsplit_fmt;
+  return RVCX_OK;
+}
+
 int rvcx_set_generator_precision(rvcx_ctx* ctx, int) {
   return guard(ctx, [&] {
     throw Error(RVCX_E_INVALID,
@@ -976,32 +782,16 @@ int rvcx_conv1d(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const floa
     a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = taps; a.dil = dilation; a.pad = pad;
     a.stride = stride;
     a.y = d_y; a.ldy = N; a.T_out = (int)T_out; a.N = N; a.bias = d_bias;
-    a.math = math >= 5 ? 3 : (math >= 3 ? 2 : math);
-    if (math == 7) a.wsplit_fmt = WSPLIT_H16;  // the two-plane fp16 arithmetic on the gather-streamed kernel
-    if (math == 5 || math == 6) {  // the two-plane fp16 arithmetic / its hi plane alone on the weight-streamed kernel
-      a.wsplit_fmt = WSPLIT_H16;
-      a.lowp = math == 6;
-    }
-    if (math == 3 || math == 5 || math == 6) {  // the weight-streamed split kernel (conv_wsb.hip) whatever the size policy would pick
-      if (!conv_wsb_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv1d: shape not eligible for the weight-streamed kernel");
-      a.w_static = 1;
-      a.force_cfg = conv_wsb_pick(a);  // the tile the pipeline's policy picks for this shape
-      a.no_splitk = 1;
-      // a fresh split image every call, never the address-keyed cache: the caller may reuse d_w (or torch's
-      // allocator may hand the address back) with new weights of the same shape
-      void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), static_cast<hipStream_t>(stream));
-      check(conv_wsplit_build(a, img, static_cast<hipStream_t>(stream)), "conv_wsplit_build");
-      a.wsplit = img;
-    }
-    if (math == 4 || math == 7) {  // the gather-streamed split kernel (conv_gs.hip), split-K by the size policy
-      if (!conv_gs_eligible(a, false)) throw Error(RVCX_E_SHAPE, "rvcx_conv1d: shape not eligible for the gather-streamed kernel");
-      a.w_static = 1;
-      a.force_cfg = 30;
-      void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), static_cast<hipStream_t>(stream));
-      check(conv_wsplit_build(a, img, static_cast<hipStream_t>(stream)), "conv_wsplit_build");
-      a.wsplit = img;
-    }
-    launch_conv(*ctx, a, false, static_cast<hipStream_t>(stream), -1.0);
+    // math -> the arithmetic, the forced family, the reduced-precision mode. 3 / 5 / 6: the weight-streamed kernel on
+    // the tile the size policy picks, unsplit (5: the two-plane fp16 arithmetic, 6: its hi plane alone); 4 / 7: the
+    // gather-streamed kernel, split-K by the size policy (7: fp16)
+    static const struct { int math, kind, lowp; } route[8] = {{0, -1, 0}, {1, -1, 0}, {2, -1, 0}, {2, CK_WSB16, 0},
+                                                              {2, CK_GS, 0}, {3, CK_WSB16, 0}, {3, CK_WSB16, 1}, {3, CK_GS, 0}};
+    a.math = route[math].math;
+    a.lowp = route[math].lowp;
+    a.no_splitk = route[math].kind == CK_WSB16;
+    const ConvForce force{route[math].kind};
+    launch_conv_test(*ctx, a, false, force.kind >= 0, force, -1, "rvcx_conv1d", static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1033,22 +823,11 @@ int rvcx_conv1d_gen(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const 
     a.acc_mode = acc_mode == 0 ? ACC_STORE : (acc_mode == 1 ? ACC_ADD : ACC_ADD_DIV);
     a.acc_div = acc_div;
     a.math = 3;
-    a.wsplit_fmt = WSPLIT_H16;
-    a.w_static = 1;
     a.no_splitk = 1;
     if (!conv_wsb_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_gen: shape not eligible for the weight-streamed kernel");
     // 0: the size policy's route, 1: the weight-streamed tile the policy would pick, 2: the weight-stationary kernel
-    a.force_cfg = kernel == 1 ? conv_wsb_pick(a) : (kernel == 2 ? 40 : -1);
-    // a fresh image every call (rvcx_conv1d's reason)
-    a.wsplit_npad = conv_wsplit_npad(a.N);
-    void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), static_cast<hipStream_t>(stream));
-    check(conv_wsplit_build(a, img, static_cast<hipStream_t>(stream)), "conv_wsplit_build");
-    a.wsplit = img;
-    ConvArgs b = a;
-    b.wsb = 1;
-    if (kernel == 2 && !conv_wst_fits(b, false))
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_gen: shape not eligible for the weight-stationary kernel");
-    launch_conv(*ctx, a, false, static_cast<hipStream_t>(stream), -1.0);
+    const ConvForce force{kernel == 1 ? CK_WSB16 : (kernel == 2 ? CK_WST : -1)};
+    launch_conv_test(*ctx, a, false, true, force, -1, "rvcx_conv1d_gen", static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1070,21 +849,7 @@ int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* d, int* kind_out, i
     if ((int64_t)(d->T_out - 1) * d->stride + (int64_t)(d->taps - 1) * d->dil + 1 > d->T_in + 2 * (int64_t)d->pad)
       throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: T_out exceeds the padded input");
     if ((int64_t)d->taps * d->N * d->C_in > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: size out of range");
-    ConvArgs a;
-    a.x = d->x; a.x_bs = d->x_bs; a.x_bs2 = d->x_bs2; a.ldx = d->ldx; a.T_in = d->T_in; a.C_in = d->C_in;
-    a.pre_act = d->pre_act; a.pre_slope = d->pre_slope; a.pre_mask = d->pre_mask; a.pre_mask_bs = d->pre_mask_bs;
-    a.w = d->w; a.ldw = d->C_in; a.w_ts = (long long)d->N * d->C_in; a.w_bs2 = d->w_bs2;
-    a.taps = d->taps; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
-    a.y = d->y; a.y_bs = d->y_bs; a.y_bs2 = d->y_bs2; a.ldy = d->ldy; a.T_out = d->T_out; a.N = d->N;
-    a.bias = d->bias; a.bias_bs2 = d->bias_bs2; a.alpha = d->alpha; a.act = d->act; a.slope = d->slope;
-    a.res = d->res; a.res_bs = d->res_bs; a.res_bs2 = d->res_bs2; a.ldr = d->ldr; a.res_mode = d->res_mode;
-    a.mask = d->mask; a.mask_bs = d->mask_bs; a.acc_mode = d->acc_mode; a.acc_div = d->acc_div;
-    a.gate_h = d->gate_h; a.gate_g = d->gate_g; a.gate_g_bs = d->gate_g_bs;
-    a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps;
-    a.batch = d->batch; a.batch_inner = d->batch_inner;
-    a.nz_har = d->nz_har; a.nz_bs = d->nz_bs; a.nz_stride = d->nz_stride; a.nz_kk = d->nz_kk; a.nz_u = d->nz_u;
-    a.nz_C = d->nz_C; a.nz_w = d->nz_w; a.nz_b = d->nz_b;
-    a.no_splitk = d->no_splitk ? 1 : 0;
+    ConvArgs a = conv_args_of(d);
     // the combine-time epilogues as their kernels take them (launch_splitk_reduce's conditions)
     if (a.ln_g && (a.N > 1024 || a.batch_inner != 1 || a.res_mode != RES_NONE || a.acc_mode != ACC_STORE || a.gate_h > 0))
       throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the combine's LayerNorm takes N <= 1024, one group, no other residual");
@@ -1093,58 +858,15 @@ int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* d, int* kind_out, i
       throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the combine's gate takes N = 2 gate_h and no other epilogue field");
     if (a.nz_har && (a.nz_kk != 1 || a.N != a.nz_u * a.nz_C || a.gate_h > 0 || a.ln_g))
       throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the fused noise conv takes one tap and N = nz_u nz_C");
-    // the route: what launch_conv will decide (a.wsb) is fixed here, so the family is known before the launch
-    int wsb = 0, expect = -1;
-    if (d->route == 1 || d->route == 2) {
-      a.math = d->route;
-      expect = d->route == 1 ? CK_GEMM : CK_EMU;
-    } else {
-      a.w_static = 1;
-      if (ctx->conv_math > 0) a.math = ctx->conv_math;
-      if (d->route == 0) {
-        wsb = conv_wsb_route(a, false);
-      } else {
-        a.math = 3;
-        if (d->route == 3) {
-          if (!conv_wsb_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: form not eligible for the weight-streamed kernel");
-          a.force_cfg = conv_wsb_pick(a);
-          wsb = 1;
-          expect = CK_WSB16;
-        } else if (d->route == 4) {
-          if (!conv_gs_eligible(a, false) || a.nz_har)
-            throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: form not eligible for the gather-streamed kernel");
-          a.force_cfg = 30;
-          wsb = 2;
-          expect = CK_GS;
-        } else {
-          a.force_cfg = 40;
-          wsb = 1;
-          expect = CK_WST;
-        }
-      }
-      if (wsb) {
-        // a fresh image every call (rvcx_conv1d's reason), in the format launch_conv would build
-        a.wsplit_fmt = conv_math_of(a) == 3 ? WSPLIT_H16 : WSPLIT_BF16;
-        a.wsplit_npad = conv_wsplit_npad(a.N);
-        void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), s);
-        check(conv_wsplit_build(a, img, s), "conv_wsplit_build");
-        a.wsplit = img;
-      }
-    }
-    ConvArgs p = a;
-    p.wsb = wsb;
-    conv_plan_splitk(p, false);
-    if (d->route == 5 && !conv_wst_fits(p, false))
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: form not eligible for the weight-stationary kernel");
-    if (!wsb && expect >= 0 && conv_unstreamed_kind(p) != expect)
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the dispatcher gives this shape to another kernel family");
-    if ((a.gate_h > 0 || a.ln_g) && p.ksplit < 2)
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the gate / LayerNorm need a contraction that splits (two steps, no_splitk off)");
-    if (a.nz_har && (wsb != 1 || p.ksplit > 1))
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the fused noise conv needs an unsplit weight-streamed / weight-stationary launch");
+    // route -> the arithmetic, a static weight, the forced family and the family the launch has to get
+    static const struct { int math, stat, force, expect; } route[6] = {{0, 1, -1, -1},       {1, 0, -1, CK_GEMM},
+                                                                       {2, 0, -1, CK_EMU},   {3, 1, CK_WSB16, -1},
+                                                                       {3, 1, CK_GS, -1},    {3, 1, CK_WST, -1}};
+    const auto& r = route[d->route];
+    a.math = r.math;
+    const ConvPlan p = launch_conv_test(*ctx, a, false, r.stat != 0, ConvForce{r.force}, r.expect, "rvcx_conv1d_ex", s);
     if (ksplit_out) *ksplit_out = p.ksplit;
-    launch_conv(*ctx, a, false, s, -1.0);
-    if (kind_out) *kind_out = conv_last_kind();
+    if (kind_out) *kind_out = p.kind;
   });
 }
 
@@ -1161,28 +883,14 @@ int rvcx_conv2d3x3(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, cons
     a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = 9; a.KH = 3; a.KW = 3; a.padh = 1; a.padw = 1;
     a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = N; a.bias = d_bias;
     a.act = act ? ACT_RELU : ACT_NONE;
-    a.math = math == 1 ? 1 : (math >= 2 ? 3 : 0);
-    if (a.math == 0 && ctx->conv_math > 0) a.math = ctx->conv_math;
-    if (math == 2) {
-      // the windowed gather-streamed kernel of the U-Net's deep levels in the two-plane fp16 split (64 x 64 tiles, K
-      // split over workgroups by the size policy); a fresh image every call
-      a.wsb = 2;
-      a.wsplit_fmt = WSPLIT_H16;
-      if (!conv_gsw_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv2d3x3: shape not eligible for the windowed kernel");
-      a.w_static = 1;
-      a.force_cfg = 30;
-      void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), static_cast<hipStream_t>(stream));
-      check(conv_wsplit_build(a, img, static_cast<hipStream_t>(stream)), "conv_wsplit_build");
-      a.wsplit = img;
-      a.wsplit_npad = conv_wsplit_npad(a.N);
-    } else if (conv_math_of(a) == 3 && conv2d_small_fits(a)) {
-      // a fresh image every call, never the address-keyed cache (the caller may reuse d_w with new weights)
-      a.wsplit_fmt = WSPLIT_S2D;
-      void* img = ctx->buf<char>("conv.test.s2d", (size_t)small2d_wsplit_bytes(a), static_cast<hipStream_t>(stream));
-      check(small2d_wsplit_build(a, img, static_cast<hipStream_t>(stream)), "small2d_wsplit_build");
-      a.wsplit = img;
-    }
-    launch_conv(*ctx, a, true, static_cast<hipStream_t>(stream), -1.0);
+    // math 2: the windowed gather-streamed kernel of the U-Net's deep levels in the two-plane fp16 split (64 x 64 tiles,
+    // K split over workgroups by the size policy); else the policy for a weight that is not static (the 3x3
+    // small-channel form reads a fresh fp16 image under the fp16-split arithmetic)
+    static const struct { int math, kind; } route[3] = {{0, -1}, {1, -1}, {3, CK_GSW}};
+    a.math = route[math].math;
+    const ConvForce force{route[math].kind};
+    if (math == 2 && !conv_gsw_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv2d3x3: shape not eligible for the windowed kernel");
+    launch_conv_test(*ctx, a, true, math == 2, force, -1, "rvcx_conv2d3x3", static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1213,21 +921,11 @@ int rvcx_convtranspose2d_s2(rvcx_ctx* ctx, const float* d_x, int H, int W, int C
     a.out_cv = N;
     a.bias = bp;
     a.act = act ? ACT_RELU : ACT_NONE;
+    // math 0: the gather-streamed kernel the pipeline's policy routes the up-convs to (under a split arithmetic); 1: the
+    // native fp32 kernel
     a.math = math == 1 ? 1 : 0;
-    if (a.math == 0 && ctx->conv_math > 0) a.math = ctx->conv_math;
-    if (math == 0 && conv_math_of(a) >= 2) {
-      // the gather-streamed kernel the pipeline's policy routes the up-convs to, with a fresh image every call
-      a.wsb = 2;
-      a.wsplit_fmt = conv_math_of(a) == 3 ? WSPLIT_H16 : WSPLIT_BF16;
-      if (!conv_gs_eligible(a, true)) throw Error(RVCX_E_SHAPE, "rvcx_convtranspose2d_s2: shape not eligible");
-      a.w_static = 1;
-      a.force_cfg = 30;
-      void* img = ctx->buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), s);
-      check(conv_wsplit_build(a, img, s), "conv_wsplit_build");
-      a.wsplit = img;
-      a.wsplit_npad = conv_wsplit_npad(a.N);
-    }
-    launch_conv(*ctx, a, true, s, -1.0);
+    const ConvForce force{math == 0 && conv_math(ctx->conv_math) >= 2 ? CK_GS : -1};
+    launch_conv_test(*ctx, a, true, force.kind >= 0, force, -1, "rvcx_convtranspose2d_s2", s);
   });
 }
 

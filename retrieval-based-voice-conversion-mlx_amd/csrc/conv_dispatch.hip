@@ -1,6 +1,6 @@
-// The conv dispatcher: which kernel family and tile a contraction gets (pick_*, conv_wsb_route), when it is split over
-// K (conv_plan_splitk), and conv1d / conv2d, which try the families in order. Every policy number below carries the
-// measurement that set it.
+// The conv dispatcher. conv_plan decides, once and on the host alone, which kernel family and tile a contraction gets,
+// whether it is split over K and which weight image it reads; conv_run launches exactly that plan. Every policy number
+// below carries the measurement that set it.
 #include <algorithm>
 #include <cstdlib>
 #include <string>
@@ -26,45 +26,46 @@ inline int env_cfg(const char* name, int dflt) {
 // which take the two-plane fp16 split (the WSPLIT_H16 / RB_WF16 images: three MFMA products per step instead of six,
 // measured as accurate as native fp32, bench_conv / tests/test_gpu_conv_math.py); ConvArgs::math overrides
 // RVCX_CONV_MATH (f32 | split | h16)
-inline int conv_math(const ConvArgs& a) {
+}  // namespace
+int conv_math(int requested) {
   static const int env = [] {
     const char* e = rvcx_knob("RVCX_CONV_MATH");
     if (e && (std::string(e) == "f32" || std::string(e) == "1")) return 1;
     if (e && (std::string(e) == "split" || std::string(e) == "2")) return 2;
     return 3;
   }();
-  return a.math > 0 ? a.math : env;
+  return requested > 0 ? requested : env;
 }
+namespace {
 
 // Tile per shape class in split mode, from build/bench_conv on MI355X (TF/s, split vs the native fp32 kernel):
 // long-tap convs 128x32 (C128 k11 155 vs 114, C256 k11 138 vs 106), short taps and GEMMs 64x64 (C128 k3 + residual
 // 101 vs 78, HuBERT qkv 52 vs 38), narrow short convs (N <= 32, taps < 5: the 32-channel ResBlock k=3, latency
 // bound) stay on the native kernel (53 vs 47): both arithmetics are fp32 accurate, so the choice is per shape. The
 // U-Net's 3x3 convs: 64x64 (C2 26.7 -> 25.9 ms vs 128x64)
-template <bool TWO_D>
-int pick_emu(const ConvArgs& a) {
-  if (TWO_D) return a.N <= 32 ? 12 : 13;
-  if (a.N <= 32) return a.taps >= 5 ? 12 : 1;
-  if (a.taps >= 5) return 12;
-  return 13;
+int pick_emu(const ConvArgs& a, bool two_d) {
+  if (two_d) return a.N <= 32 ? TILE_EMU_128x32 : TILE_EMU_64x64;
+  if (a.N <= 32) return a.taps >= 5 ? TILE_EMU_128x32 : TILE_F32_128x32;
+  if (a.taps >= 5) return TILE_EMU_128x32;
+  return TILE_EMU_64x64;
 }
 
-template <bool TWO_D>
-int pick_cfg(const ConvArgs& a) {
-  if (a.force_cfg >= 0) return a.force_cfg;
-  if (conv_math(a) >= 2) return pick_emu<TWO_D>(a);
+int pick_cfg(const ConvArgs& a, bool two_d) {
+  if (conv_math(a.math) >= 2) return pick_emu(a, two_d);
   // N <= 32 and the 1-D convs with taps >= 5 (A/B: 32.8 vs 33.6 ms): 128 x 32; everything else 64 x 64
-  if (a.N <= 32) return 1;
-  if (!TWO_D && a.taps >= 5) return 1;
-  return 3;
+  if (a.N <= 32) return TILE_F32_128x32;
+  if (!two_d && a.taps >= 5) return TILE_F32_128x32;
+  return TILE_F32_64x64;
 }
 
-inline void cfg_tile(int cfg, int& BM, int& BN) {
-  if (conv_emu_tile(cfg, BM, BN)) return;
+inline bool cfg_tile(int cfg, int& BM, int& BN) {
+  if (conv_emu_tile(cfg, BM, BN)) return true;
+  if (cfg < 0 || cfg >= 10) return false;
   static const int t[10][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 128}, {64, 128}, {256, 64},
                                {64, 64}, {128, 32}, {128, 128}};
   BM = t[cfg][0];
   BN = t[cfg][1];
+  return true;
 }
 
 // the rows every policy decision below is made for: ConvArgs::plan_T where the caller launches a window of a longer
@@ -90,23 +91,15 @@ inline int plan_rows(const ConvArgs& a) { return (a.plan_T > 0 && a.W_out <= 0) 
 // for every long conv (A/B aid)
 inline int pick_wsb(const ConvArgs& a) {
   static const int c_long = env_cfg("RVCX_WCFG_LONG", 0);
-  if (a.wsb == 2) return 30;  // gather-streamed (conv_gs.hip): the short contractions
-  if (a.N <= 32) return 24;
+  if (a.N <= 32) return TILE_WSB_256x32;
   // the wide ConvTranspose phase group of the second upsample (18600 rows x 1280 columns, 2 taps) on 128 x 128 tiles:
   // bench_conv r06a h25 254.6 vs h27 232.2 TF (the first one, 1550 rows x 3072, loses there: 189 vs 206)
-  if (a.taps <= 3 && a.N >= 1024 && plan_rows(a) >= 8192 && a.C_in < 512 && c_long == 0) return 25;
-  if (a.taps <= 3) return 27;
+  if (a.taps <= 3 && a.N >= 1024 && plan_rows(a) >= 8192 && a.C_in < 512 && c_long == 0) return TILE_WSB_128x128;
+  if (a.taps <= 3) return TILE_WSB_128x64_1x4;
   if (c_long > 0) return c_long;
-  return (a.C_in < 256 && a.N >= 128) ? 25 : 23;
+  return (a.C_in < 256 && a.N >= 128) ? TILE_WSB_128x128 : TILE_WSB_128x64;
 }
 }  // namespace
-int conv_wsb_pick(const ConvArgs& a) {
-  ConvArgs b = a;
-  b.wsb = 1;
-  return pick_wsb(b);
-}
-thread_local int g_conv_kind = CK_OTHER;
-int conv_last_kind() { return g_conv_kind; }
 const char* conv_kind_name(int k) {
   static const char* const names[CK_COUNT] = {"conv_wsb16_kernel", "conv_wsb_kernel", "conv_gs16_kernel",
                                               "conv_gsw16_kernel", "k_rb_pair", "k_conv2d_h16/k_conv2d_small",
@@ -117,99 +110,11 @@ const char* conv_kind_name(int k) {
 
 namespace {
 
-template <bool TWO_D>
-hipError_t dispatch(const ConvArgs& a_in, hipStream_t s) {
-  const ConvArgs& a = a_in;
-  if (a.N <= 0 || a.T_out <= 0 || a.batch <= 0) return hipSuccess;
-  if (a.C_in <= 0 || a.taps <= 0) return hipErrorInvalidValue;
-  // the fused noise conv lives in the 16x16 tile stores' unsplit epilogue only (the caller routes it to such a kernel)
-  const bool nz = a.nz_har != nullptr;
-  if (nz && (TWO_D || (a.ws && a.ksplit > 1) || a.nz_C <= 0 || a.nz_stride <= 0 ||
-             a.nz_kk != 1 ||
-             a.N != a.nz_u * a.nz_C || a.out_map != OUT_ROWS))
-    return hipErrorInvalidValue;
-  // the gate and the LayerNorm are applied by the combine
-  if ((a.gate_h > 0 || a.ln_g) && !(a.ws && a.ksplit > 1)) return hipErrorInvalidValue;
-  if (tiny_fits(a)) {
-    if (nz) return hipErrorInvalidValue;
-    g_conv_kind = CK_TINY;
-    return launch_tiny(a, TWO_D, s);
-  }
-  if (!nz && !(a.ws && a.ksplit > 1) && rows1x1_fits(a, TWO_D)) {
-    g_conv_kind = CK_TINY;
-    return launch_rows1x1(a, TWO_D, s);
-  }
-  if (a.wsb == 2 && a.wsplit && conv_math(a) >= 2 && conv_gs_eligible(a, TWO_D)) {
-    const int ks = (a.ws && a.ksplit > 1) ? a.ksplit : 1;
-    const int cfg = a.force_cfg >= 30 ? a.force_cfg : pick_wsb(a);
-    g_conv_kind = (TWO_D && cfg == 30 && conv_gsw_eligible(a)) ? CK_GSW : CK_GS;
-    hipError_t e = conv_gs_launch(a, cfg, s, TWO_D, ks);
-    if (e == hipSuccess && ks > 1) e = launch_splitk_reduce(a, ks, TWO_D, s);
-    if (e != hipErrorInvalidValue) return e;
-  }
-  if (a.wsb == 1 && a.wsplit && conv_math(a) >= 2 && conv_wsb_eligible(a, TWO_D)) {
-    const int ks = (a.ws && a.ksplit > 1) ? a.ksplit : 1;
-    // the short 64 / 128-channel convs on the weight-stationary kernel (conv_wst.hip; force_cfg 20..39 keeps a
-    // weight-streamed tile for comparisons)
-    if (ks == 1 && (a.force_cfg < 20 || a.force_cfg == 40) && conv_wst_fits(a, TWO_D)) {
-      g_conv_kind = CK_WST;
-      hipError_t e = conv_wst_launch(a, s);
-      if (e != hipErrorInvalidValue) return e;
-    }
-    const int cfg = a.force_cfg >= 20 && a.force_cfg < 40 ? a.force_cfg : pick_wsb(a);
-    g_conv_kind = CK_WSB16;
-    hipError_t e = conv_wsb_launch(a, cfg, s, TWO_D, ks);
-    if (e == hipSuccess && ks > 1) e = launch_splitk_reduce(a, ks, TWO_D, s);
-    if (e != hipErrorInvalidValue) return e;
-  }
-  if (nz) return hipErrorInvalidValue;  // no kernel with a 16x16 tile store took it
-  // 3x3 convs with 16/32 channels: 16x16x4 MFMA fragments (conv2d_small.hip)
-  if (TWO_D && a.force_cfg < 0 && conv2d_small_fits(a)) {
-    g_conv_kind = CK_SMALL2D;
-    return conv2d_small(a, s);
-  }
-  const int cfg = pick_cfg<TWO_D>(a);
-  const bool emu = cfg >= 10;  // the arithmetic: fp32 through bf16 planes (conv_emu.hip) or native fp32 (conv_gemm.hip)
-  g_conv_kind = emu ? CK_EMU : CK_GEMM;
-  // plain GEMMs (1-D, one tap, stride 1) take the double-buffered pipeline unless a.pipe < 0; a.pipe > 0 forces it
-  // (benchmarks)
-  const bool gemm = !TWO_D && a.taps == 1 && a.stride == 1;
-  const bool pipe = gemm && a.pipe >= 0;
-  const int ksplit = (a.ws && a.ksplit > 1) ? a.ksplit : 1;
-  auto run = [&](int c, bool p) -> hipError_t {
-    hipError_t e = emu ? conv_emu_launch(a, c, TWO_D, p, ksplit, s) : conv_gemm_launch(a, c, TWO_D, p, ksplit, s);
-    if (e != hipSuccess || ksplit == 1) return e;
-    return launch_splitk_reduce(a, ksplit, TWO_D, s);
-  };
-  hipError_t e = run(cfg, pipe);
-  if (e == hipErrorInvalidValue && pipe) e = run(cfg, false);  // tile without a GEMM-pipeline instantiation
-  if (e == hipErrorInvalidValue && a.force_cfg < 0) {
-    // the tile's halo does not fit in LDS (long strided taps) or the shape class has no such instantiation: the two
-    // fallback tiles of that arithmetic, 64 x 64 then 128 x 32
-    for (int alt : {emu ? 13 : 3, emu ? 12 : 1}) {
-      if (alt == cfg) continue;
-      e = run(alt, false);
-      if (e != hipErrorInvalidValue) break;
-    }
-  }
-  return e;
-}
-
-}  // namespace
-
-long long conv_plan_splitk(ConvArgs& a, bool two_d) {
-  a.ksplit = 1;
-  if (a.N <= 0 || a.T_out <= 0 || a.no_splitk) return 0;
-  if (tiny_fits(a)) return 0;
-  if (two_d && a.force_cfg < 0 && conv2d_small_fits(a)) return 0;
-  int BM, BN;
-  if (a.wsb == 2) {  // the gather-streamed tile
-    conv_gs_tile(a.force_cfg >= 30 ? a.force_cfg : pick_wsb(a), BM, BN);
-  } else if (a.wsb) {  // the weight-streamed tile (pick_wsb)
-    if (!conv_wsb_tile(a.force_cfg >= 20 ? a.force_cfg : pick_wsb(a), BM, BN)) return 0;
-  } else {
-    cfg_tile(two_d ? pick_cfg<true>(a) : pick_cfg<false>(a), BM, BN);
-  }
+// Split-K for a launch on BM x BN tiles (gs: the gather-streamed kernels' rules): ksplit, and through slab the floats
+// of the partial-tile workspace a split needs
+int plan_splitk(const ConvArgs& a, bool two_d, int BM, int BN, bool gs, long long& slab) {
+  slab = 0;
+  if (a.no_splitk) return 1;
   // the decisions (whether to split, ksplit) are made for plan_rows(a) rows, the slab for the launch's own T_out
   const int T_plan = two_d ? a.T_out : plan_rows(a);
   long long mtiles, mtiles_real;
@@ -238,28 +143,28 @@ long long conv_plan_splitk(ConvArgs& a, bool two_d) {
   constexpr int min_iters = 4;    // shortest contraction worth a split
   // a gated WaveNet in_layer always splits: its gate lives in the combine (ConvArgs::gate_h)
   const bool combine_epi = a.gate_h > 0 || a.ln_g;  // an epilogue only the combine applies: always split
-  if (!combine_epi && (tiles >= min_tiles || iters < min_iters || (flops < 1.0e8 && iters < 16))) return 0;
+  if (!combine_epi && (tiles >= min_tiles || iters < min_iters || (flops < 1.0e8 && iters < 16))) return 1;
   int ks = (int)((target + tiles - 1) / tiles);
   // the gather-streamed kernels keep >= 8 (chunk, tap) steps per slice: below that a slice is all prologue and
   // epilogue and the extra slab + combine launch cost more than the parallelism gains (bench_gs r03s, cold: HuBERT
   // 768 -> 768 ks 1 22.1 us vs ks 4 27.6, TextEncoder 1x1 ks 1 11.6 vs ks 3 14.4, U-Net 196 px ks 8 19.8 vs ks 16
   // 21.8, 3136 px ks 2 20.2 vs ks 6 27.3; the 3072 -> 768 linear keeps ks 4: 48.6 vs 62.8 unsplit)
   constexpr int gs_min_steps = 8;  // same-box C2: 2 17.73, 8 17.72, 16 17.86, 24 17.97 ms
-  ks = std::min(ks, a.wsb == 2 ? iters / gs_min_steps : iters / 2);
+  ks = std::min(ks, gs ? iters / gs_min_steps : iters / 2);
   ks = std::min(ks, 32);
   // the windowed 2-D gather-streamed kernel splits by whole 32-channel chunks (bench_gs: U-Net 784 px ks 8 and 3136 px
   // ks 4 beat the 10 and 6 the step count would give)
-  if (a.wsb == 2 && two_d && (a.force_cfg < 0 || a.force_cfg == 30) && conv_gsw_eligible(a))
-    ks = std::min(ks, (a.C_in + CK - 1) / CK);
+  if (gs && two_d && conv_gsw_eligible(a)) ks = std::min(ks, (a.C_in + CK - 1) / CK);
   if (combine_epi && iters >= 2) ks = std::max(ks, 2);
-  if (ks < 2) return 0;
-  a.ksplit = ks;
-  a.ws_rows = two_d ? (long long)a.T_out * a.W_out : a.T_out;
-  return std::max((long long)ks * a.ws_rows * a.N * a.batch * a.batch_inner, tiles_real * ks * BM * BN);
+  if (ks < 2) return 1;
+  const long long rows = two_d ? (long long)a.T_out * a.W_out : a.T_out;
+  slab = std::max((long long)ks * rows * a.N * a.batch * a.batch_inner, tiles_real * ks * BM * BN);
+  return ks;
 }
 
-bool conv_wsb_wants(const ConvArgs& a) {
-  if (conv_math(a) < 2 || !conv_wsb_eligible(a)) return false;
+// a static weight on the weight-streamed kernel
+bool wsb_wants(const ConvArgs& a) {
+  if (!conv_wsb_eligible(a)) return false;
   // where it measured faster (bench_conv, profiles/r02i_bench_conv.txt: 128 x 64 tiles of 2 x 2 waves of 64 x 32
   // with the register epilogue; C2 A/B): N >= 64 with >= 2 taps (ResBlock convs at 64-256 channels incl. k = 3, the
   // polyphase ConvTranspose phases; the 64-channel stage on 128x64 tiles beat the fused pair), on a grid that fills
@@ -270,24 +175,155 @@ bool conv_wsb_wants(const ConvArgs& a) {
   return tiles >= min_tiles;
 }
 
-int conv_wsb_route(const ConvArgs& a, bool two_d) {
-  if (conv_math(a) < 2 || tiny_fits(a)) return 0;
-  if (two_d && conv2d_small_fits(a)) return 0;
-  // the weight-streamed kernel on small grids (split-K) and on the U-Net's 3x3 convs measured slower than the
-  // gather-streamed one (HuBERT / TextEncoder GEMMs +0.7 ms, U-Net +0.8 ms: with few M tiles every wave re-streams its
-  // B fragments from L2)
-  if (!two_d && conv_wsb_wants(a)) return 1;
-  // everything else with a static weight, 32-channel chunks and >= 64 outputs: the short contractions
-  if (a.N >= 64 && conv_gs_eligible(a, two_d)) return 2;
-  return 0;
+constexpr ConvPlan refused{CK_OTHER, TILE_NONE, 1, 0, -1, false, false};
+constexpr ConvPlan tiny_plan{CK_TINY, TILE_NONE, 1, 0, -1, false, false};
+
+// the plan of a launch on the weight-streamed tile `tile` (pick_wsb's unless forced); wst: the weight-stationary
+// kernel may take it
+ConvPlan plan_wsb(const ConvArgs& a, int tile, bool wst) {
+  const int math = conv_math(a.math);
+  int BM, BN;
+  if (!conv_wsb_tile(tile, BM, BN)) return refused;
+  ConvPlan p{CK_WSB16, tile, 1, 0, (a.lowp || math == 3) ? WSPLIT_H16 : WSPLIT_BF16, true, false};
+  p.ksplit = plan_splitk(a, false, BM, BN, false, p.slab_floats);
+  // the short 64 / 128-channel convs on the weight-stationary kernel (conv_wst.hip), which reads the fp16 image
+  if (wst && p.ksplit == 1 && p.wsplit_fmt == WSPLIT_H16 && conv_wst_fits(a, false)) {
+    p.kind = CK_WST;
+    p.tile = TILE_NONE;
+  }
+  return p;
 }
 
-int conv_math_of(const ConvArgs& a) { return conv_math(a); }
-int conv_unstreamed_kind(const ConvArgs& a) {
-  if (tiny_fits(a) || (!(a.ws && a.ksplit > 1) && rows1x1_fits(a, false))) return CK_TINY;
-  return pick_cfg<false>(a) >= 10 ? CK_EMU : CK_GEMM;
+ConvPlan plan_gs(const ConvArgs& a, bool two_d) {
+  ConvPlan p{(two_d && conv_gsw_eligible(a)) ? CK_GSW : CK_GS, TILE_GS_64x64, 1, 0,
+             conv_math(a.math) == 3 ? WSPLIT_H16 : WSPLIT_BF16, true, false};
+  p.ksplit = plan_splitk(a, two_d, 64, 64, true, p.slab_floats);
+  return p;
 }
-hipError_t conv1d(const ConvArgs& a, hipStream_t s) { return dispatch<false>(a, s); }
-hipError_t conv2d(const ConvArgs& a, hipStream_t s) { return dispatch<true>(a, s); }
+
+// the LDS-staged families on tile `tile`; split_as_gs: the split is the gather-streamed tile's (below)
+ConvPlan plan_lds(const ConvArgs& a, bool two_d, int tile, int pipe, bool split_as_gs) {
+  int BM, BN;
+  if (!cfg_tile(tile, BM, BN) || a.nz_har) return refused;  // no kernel with a 16x16 tile store took the noise conv
+  // the arithmetic: fp32 through bf16 planes (conv_emu.hip) or native fp32 (conv_gemm.hip)
+  ConvPlan p{tile >= 10 ? CK_EMU : CK_GEMM, tile, 1, 0, -1, false, false};
+  // plain GEMMs (1-D, one tap, stride 1) take the double-buffered pipeline unless pipe < 0; pipe > 0 forces it
+  // (benchmarks)
+  p.pipe = !two_d && a.taps == 1 && a.stride == 1 && pipe >= 0;
+  if (split_as_gs) BM = BN = 64;
+  p.ksplit = plan_splitk(a, two_d, BM, BN, split_as_gs, p.slab_floats);
+  return p;
+}
+
+// one LDS-staged launch: the planned tile; where its halo does not fit in LDS (long strided taps) or the shape class
+// has no such instantiation, the two fallback tiles of that arithmetic, 64 x 64 then 128 x 32 (policy launches only)
+hipError_t run_lds(const ConvPlan& p, const ConvArgs& a, bool two_d, bool fallback, hipStream_t s) {
+  const bool emu = p.kind == CK_EMU;
+  auto run = [&](int c, bool pipe) {
+    return emu ? conv_emu_launch(a, c, two_d, pipe, p.ksplit, s) : conv_gemm_launch(a, c, two_d, pipe, p.ksplit, s);
+  };
+  hipError_t e = run(p.tile, p.pipe);
+  if (e == hipErrorInvalidValue && p.pipe) e = run(p.tile, false);  // tile without a GEMM-pipeline instantiation
+  if (e == hipErrorInvalidValue && fallback) {
+    for (int alt : {emu ? TILE_EMU_64x64 : TILE_F32_64x64, emu ? TILE_EMU_128x32 : TILE_F32_128x32}) {
+      if (alt == p.tile) continue;
+      e = run(alt, false);
+      if (e != hipErrorInvalidValue) break;
+    }
+  }
+  return e;
+}
+
+}  // namespace
+
+ConvPlan conv_plan(const ConvArgs& a, bool two_d, bool static_weight, const ConvForce& force) {
+  if (a.N <= 0 || a.T_out <= 0 || a.batch <= 0 || a.C_in <= 0 || a.taps <= 0) return refused;
+  const int math = conv_math(a.math);
+  // the fused noise conv lives in the 16x16 tile stores' unsplit epilogue only (the caller routes it to such a kernel)
+  const bool nz = a.nz_har != nullptr;
+  if (nz && (two_d || a.nz_C <= 0 || a.nz_stride <= 0 || a.nz_kk != 1 || a.N != a.nz_u * a.nz_C ||
+             a.out_map != OUT_ROWS))
+    return refused;
+  const bool streamed = static_weight && math >= 2;  // only a constant weight has a pre-split image
+  ConvPlan p = refused;
+  if (force.kind >= 0) {
+    // a forced family (numerics tests, benchmarks): it admits the form or the launch is refused
+    switch (force.kind) {
+      case CK_WSB16:
+        if (streamed && conv_wsb_eligible(a, two_d)) p = plan_wsb(a, force.tile >= 0 ? force.tile : pick_wsb(a), false);
+        break;
+      case CK_WST:
+        if (streamed && math == 3 && !a.lowp && conv_wst_fits(a, two_d))
+          p = ConvPlan{CK_WST, TILE_NONE, 1, 0, WSPLIT_H16, true, false};
+        break;
+      case CK_GS:
+      case CK_GSW:
+        if (streamed && (force.tile < 0 || force.tile == TILE_GS_64x64) && conv_gs_eligible(a, two_d))
+          p = plan_gs(a, two_d);
+        break;
+      case CK_GEMM:
+      case CK_EMU:
+        if ((force.tile >= 10) == (force.kind == CK_EMU)) p = plan_lds(a, two_d, force.tile, force.pipe, false);
+        break;
+      default: break;
+    }
+  } else if (tiny_fits(a)) {
+    if (!nz) p = tiny_plan;
+  } else if (two_d && conv2d_small_fits(a)) {
+    // 3x3 convs with 16/32 channels: 16x16x4 MFMA fragments (conv2d_small.hip); the fp16-split form reads a pre-split
+    // image
+    p = ConvPlan{CK_SMALL2D, TILE_NONE, 1, 0, math == 3 ? WSPLIT_S2D : -1, math == 3 && static_weight, false};
+  } else {
+    // a static weight: the weight-streamed kernel (the big 1-D grids, wsb_wants) or the gather-streamed one (the rest
+    // with 32-channel chunks and >= 64 outputs)
+    // the weight-streamed kernel on small grids (split-K) and on the U-Net's 3x3 convs measured slower than the
+    // gather-streamed one (HuBERT / TextEncoder GEMMs +0.7 ms, U-Net +0.8 ms: with few M tiles every wave re-streams its
+    // B fragments from L2)
+    const bool wsb = streamed && !two_d && wsb_wants(a);
+    // everything else with a static weight, 32-channel chunks and >= 64 outputs: the short contractions
+    const bool gs = streamed && !wsb && a.N >= 64 && conv_gs_form(a, two_d);
+    if (wsb) {
+      p = plan_wsb(a, pick_wsb(a), true);
+    } else if (gs && !a.lowp) {
+      p = plan_gs(a, two_d);
+    } else {
+      // (a reduced-precision launch of a gather-streamed shape -- those kernels have no such mode -- runs here, split
+      // as the gather-streamed tile would be: a short hop's ConvTranspose phases)
+      p = plan_lds(a, two_d, pick_cfg(a, two_d), force.pipe, gs);
+      if (p.kind != CK_OTHER && p.ksplit == 1 && rows1x1_fits(a, two_d)) p = tiny_plan;
+    }
+  }
+  // the noise conv needs an unsplit launch; the gate and the LayerNorm are applied by the combine
+  if ((nz && p.ksplit > 1) || ((a.gate_h > 0 || a.ln_g) && p.ksplit < 2)) return refused;
+  return p;
+}
+
+hipError_t conv_run(const ConvPlan& p, const ConvArgs& a_in, bool two_d, hipStream_t s, bool forced) {
+  if (a_in.N <= 0 || a_in.T_out <= 0 || a_in.batch <= 0) return hipSuccess;
+  if (p.kind == CK_OTHER || p.ksplit < 1 || (p.ksplit > 1 && !a_in.ws) ||
+      (p.wsplit_fmt >= 0 && p.kind != CK_SMALL2D && !a_in.wsplit))
+    return hipErrorInvalidValue;
+  // the fields the kernels read from their kernarg copy of the record
+  ConvArgs a = a_in;
+  a.ksplit = p.ksplit;
+  a.ws_rows = two_d ? (long long)a.T_out * a.W_out : a.T_out;
+  a.wsplit_fmt = p.wsplit_fmt >= 0 ? p.wsplit_fmt : 0;
+  if (p.wsplit_fmt < 0) a.wsplit = nullptr;
+  else if (p.kind != CK_SMALL2D) a.wsplit_npad = conv_wsplit_npad(a.N);
+  hipError_t e;
+  switch (p.kind) {
+    case CK_TINY: return tiny_fits(a) ? launch_tiny(a, two_d, s) : launch_rows1x1(a, two_d, s);
+    case CK_SMALL2D: return conv2d_small(a, s);
+    case CK_WST: return conv_wst_launch(a, s);
+    case CK_GS:
+    case CK_GSW: e = conv_gs_launch(a, p.tile, s, two_d, p.ksplit); break;
+    case CK_WSB16: e = conv_wsb_launch(a, p.tile, s, two_d, p.ksplit); break;
+    case CK_EMU:
+    case CK_GEMM: e = run_lds(p, a, two_d, !forced, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  if (e == hipSuccess && p.ksplit > 1) e = launch_splitk_reduce(a, p.ksplit, two_d, s);
+  return e;
+}
 
 }  // namespace rvcx

@@ -553,7 +553,9 @@ hipError_t launch_gsw(const ConvArgs& a, int ksplit, hipStream_t s) {
 
 }  // namespace
 
-bool conv_gs_eligible(const ConvArgs& a, bool two_d) {
+bool conv_gs_eligible(const ConvArgs& a, bool two_d) { return !a.lowp && conv_gs_form(a, two_d); }
+
+bool conv_gs_form(const ConvArgs& a, bool two_d) {
   const bool vec_a = ((a.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && ((a.x_bs & 3) == 0);
   // the 2x2-phase ConvTranspose2d output (OUT_UPSAMPLE2D, the U-Net decoder's up-convs, round 5) with the plain epilogue
   // (store_tile16 maps it; a split launch's combine does, as for the LDS-staged kernel)
@@ -566,16 +568,9 @@ bool conv_gs_eligible(const ConvArgs& a, bool two_d) {
   const long long rows_in = two_d ? (long long)a.T_in * a.W_in : a.T_in;
   if (rows_in * a.ldx + a.C_in >= INT32_MAX) return false;
   if (!two_d) return (long long)a.T_out * a.stride < INT32_MAX / 2 && a.T_in < INT32_MAX / 2;
-  return a.taps == a.KH * a.KW && !a.pre_mask && a.stride == 1 && a.W_out >= 1 && a.W_in >= 1;
-}
-
-// cfg 30: 64 x 64 (2 x 2 waves of 32 x 32). Round 5's 64 x 32 tiles with the K walk split over the 4 waves of a
-// workgroup (the windowed form, cfg 33) and the 128 x 64 / 64 x 128 tiles (31, 32) measured no faster and are gone
-bool conv_gs_tile(int cfg, int& BM, int& BN) {
-  if (cfg != 30) return false;
-  BM = 64;
-  BN = 64;
-  return true;
+  // (and the 32-bit tile count of the grid)
+  return a.taps == a.KH * a.KW && !a.pre_mask && a.stride == 1 && a.W_out >= 1 && a.W_in >= 1 &&
+         ((long long)a.T_out * a.W_out + 63) / 64 <= INT32_MAX / 64;
 }
 
 // the windowed 2-D kernel: 3x3 / pad 1 / stride 1, same-size images at most 32 pixels wide with 32 % W == 0
@@ -584,8 +579,10 @@ bool conv_gsw_eligible(const ConvArgs& a) {
          a.T_in == a.T_out && a.W_in == a.W_out && a.W_out <= GSW_MAXW && GSW_MAXW % a.W_out == 0 && a.W_out >= 4;
 }
 
+// cfg 30: 64 x 64 (2 x 2 waves of 32 x 32). Round 5's 64 x 32 tiles with the K walk split over the 4 waves of a
+// workgroup (the windowed form, cfg 33) and the 128 x 64 / 64 x 128 tiles (31, 32) measured no faster and are gone
 hipError_t conv_gs_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d, int ksplit) {
-  if (!a.wsplit || !conv_gs_eligible(a, two_d) || a.lowp) return hipErrorInvalidValue;
+  if (!a.wsplit || !conv_gs_eligible(a, two_d)) return hipErrorInvalidValue;
   if (cfg != 30) return hipErrorInvalidValue;
   if (two_d && conv_gsw_eligible(a)) return launch_gsw(a, ksplit, s);
   return two_d ? launch_gs<64, 64, 2, 2, true>(a, ksplit, s)

@@ -188,14 +188,14 @@ inline bool tiny_rows_fits(const ConvArgs& a) {
 constexpr int TINY_MAX_CIN = 4;
 bool tiny_fits(const ConvArgs& a) {
   const long long rows = a.W_out > 0 ? (long long)a.T_out * a.W_out : a.T_out;
-  return a.C_in <= TINY_MAX_CIN && a.C_in * a.taps <= 16 && a.force_cfg < 0 &&
+  return a.C_in <= TINY_MAX_CIN && a.C_in * a.taps <= 16 &&
          rows * a.N * a.batch * a.batch_inner < (1LL << 30);
 }
 
 // conv_rows1x1_kernel's shapes: a 1x1 / stride-1 conv (1-D or 2-D) with C_in a multiple of 4 up to 64, 16-B aligned
 // input rows, and conv_tiny_rows_kernel's epilogue conditions
 bool rows1x1_fits(const ConvArgs& a, bool two_d) {
-  if (a.taps != 1 || a.stride != 1 || a.dil != 1 || a.pad != 0 || a.force_cfg >= 0) return false;
+  if (a.taps != 1 || a.stride != 1 || a.dil != 1 || a.pad != 0) return false;
   if (two_d && (a.KH != 1 || a.KW != 1 || a.padh != 0 || a.padw != 0 || a.T_in != a.T_out || a.W_in != a.W_out))
     return false;
   const long long rows = two_d ? (long long)a.T_out * a.W_out : a.T_out;

@@ -328,21 +328,21 @@ bool conv_wst_fits(const ConvArgs& a, bool two_d) {
                      (!a.nz_har || (a.nz_C % 4 == 0 && a.nz_kk == 1));
   const bool shape = (a.C_in == 128 && a.N == 128 && (a.taps == 3 || a.taps == 2)) ||
                      (a.C_in == 64 && a.N == 64 && (a.taps == 3 || a.taps == 2));
-  return !two_d && shape && vec_a && vec_y && a.wsb == 1 && a.wsplit && a.wsplit_fmt == WSPLIT_H16 && !a.lowp &&
-         a.wsplit_npad >= a.N && a.batch_inner == 1 && !a.b_kn && a.out_map == OUT_ROWS && a.stride == 1 &&
-         a.dil >= 1 && (a.taps - 1) * a.dil <= WST_HMAX && (a.pre_act == ACT_LRELU || a.pre_act == ACT_NONE) &&
-         !a.pre_mask && a.alpha == 1.f &&
-         !a.mask && (a.act == ACT_NONE || a.act == ACT_LRELU) &&
+  return !two_d && shape && vec_a && vec_y && !a.lowp && a.batch_inner == 1 && !a.b_kn && a.out_map == OUT_ROWS &&
+         a.stride == 1 && a.dil >= 1 && (a.taps - 1) * a.dil <= WST_HMAX &&
+         (a.pre_act == ACT_LRELU || a.pre_act == ACT_NONE) && !a.pre_mask && a.alpha == 1.f && !a.mask && (a.act == ACT_NONE || a.act == ACT_LRELU) &&
          (a.res_mode == RES_NONE || (a.res_mode == RES_ADD_POST && a.res)) && a.bias_bs == 0 && a.gate_h == 0 &&
-         !a.ln_g && !(a.ws && a.ksplit > 1) && a.T_out > 0 && a.T_in > 0 && a.batch > 0 &&
+         !a.ln_g && a.T_out > 0 && a.T_in > 0 && a.batch > 0 &&
          // 32-bit element offsets on 24-bit multiplies inside a batch entry (the kernel's cursors)
          a.T_in < (1 << 24) && a.T_out + WST_BM < (1 << 24) && a.ldx < (1 << 24) && a.ldy < (1 << 24) &&
          a.ldr < (1 << 24) && (long long)a.T_in * a.ldx < (1LL << 31) && (long long)a.T_out * a.ldy < (1LL << 31) &&
-         (long long)a.T_out * a.ldr < (1LL << 31);
+         (long long)a.T_out * a.ldr < (1LL << 31) &&
+         (long long)((a.T_out + WST_BM - 1) / WST_BM) * a.batch < (1LL << 31);  // the persistent grid's tile count
 }
 
 hipError_t conv_wst_launch(const ConvArgs& a, hipStream_t s) {
-  if (!conv_wst_fits(a, false)) return hipErrorInvalidValue;
+  if (!a.wsplit || a.wsplit_fmt != WSPLIT_H16 || a.wsplit_npad < a.N || a.ksplit > 1 || !conv_wst_fits(a, false))
+    return hipErrorInvalidValue;
   if (a.C_in == 128) return a.taps == 3 ? launch_wst_epi<4, 3, 8>(a, s) : launch_wst_epi<4, 2, 8>(a, s);
   return a.taps == 3 ? launch_wst_epi<2, 3, 4>(a, s) : launch_wst_epi<2, 2, 4>(a, s);
 }

@@ -127,9 +127,7 @@ struct Ctx {
   int conv_math = 0;  // ConvArgs::math of every conv launch (rvcx_set_conv_math): 0 default, 1 fp32 MFMA, 2 split
   // the arithmetic a launch without ConvArgs::math gets: rvcx_set_conv_math, else RVCX_CONV_MATH
   int conv_math_default() const {
-    ConvArgs a;
-    a.math = conv_math;
-    return conv_math_of(a);
+    return rvcx::conv_math(conv_math);
   }
   static constexpr double PEAK_SPLIT = 2500.0 / 6.0, PEAK_F16X2 = 2500.0 / 3.0, PEAK_F16 = 2500.0;
   struct ProfRec {
@@ -461,8 +459,8 @@ void set_i32_once(Ctx& c, const std::string& name, int32_t* p, int32_t v, hipStr
 // far (or s itself when overlap is off: kernel timing on, or RVCX_NO_OVERLAP=1); join_aux makes s wait for
 // everything queued on the aux stream so far.
 hipStream_t fork_aux(Ctx& c, hipStream_t s);
-// whether launch_conv would run this 1-D contraction on the weight-streamed fp16 kernel without split-K (the kernels
-// whose epilogue takes the fused NSF noise conv, ConvArgs::nz_*)
+// whether launch_conv's plan runs this 1-D contraction on the weight-streamed fp16 or the weight-stationary kernel
+// without split-K (the kernels whose epilogue takes the fused NSF noise conv, ConvArgs::nz_*)
 bool conv_routes_wsb16(Ctx& c, const ConvArgs& a);
 // marks a synth_forward call whose rows all have the full length T (Ctx::synth_full_lengths) for its lifetime
 struct ScopedFullLengths {
@@ -471,8 +469,14 @@ struct ScopedFullLengths {
   ~ScopedFullLengths() { c.synth_full_lengths = false; }
 };
 void join_aux(Ctx& c, hipStream_t s, hipStream_t ax);
-// launch one implicit-GEMM conv (1-D or 2-D) with optional event timing; flops = algorithmic FLOPs
+// launch one implicit-GEMM conv (1-D or 2-D) as conv_plan routes it, with optional event timing; flops = algorithmic
+// FLOPs (runtime_conv.cpp)
 void launch_conv(Ctx& c, const ConvArgs& a_in, bool two_d, hipStream_t s, double flops = -1.0);
+// launch_conv for the kernel-level test entries: the plan under `force`, refused with RVCX_E_SHAPE before any launch
+// where the forced family does not admit the form, the family is not expect_kind (>= 0) or the combine's epilogues get
+// no split; a fresh weight image built per call. Returns the plan it ran.
+ConvPlan launch_conv_test(Ctx& c, const ConvArgs& a_in, bool two_d, bool static_weight, const ConvForce& force,
+                          int expect_kind, const char* who, hipStream_t s);
 // one fused ResBlock pair (resblock_fused.hip) with optional event timing (counted with the conv family)
 void launch_rb_pair(Ctx& c, const RbPairArgs& a, hipStream_t s);
 inline void check(hipError_t e, const char* what) {

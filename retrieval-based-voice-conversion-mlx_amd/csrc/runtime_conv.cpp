@@ -1,0 +1,255 @@
+// The runtime's side of a conv launch: plan (conv_dispatch.hip), weight image, split-K slab, run, with optional event
+// timing; the fused ResBlock pair's launch; and the context's streams, events and device-status word.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "runtime.h"
+
+namespace rvcx {
+hipStream_t Ctx::aux_stream() {
+  if (!aux) {
+    RVCX_HIP(hipSetDevice(device));
+    // (the aux stream at the device's least priority measured neutral: 18.22 vs 18.19 ms, round 3)
+    RVCX_HIP(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
+    RVCX_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    RVCX_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    RVCX_HIP(hipEventCreateWithFlags(&ev_gate, hipEventDisableTiming));
+  }
+  return aux;
+}
+
+unsigned* Ctx::device_status() {
+  if (!status_host) {
+    RVCX_HIP(hipSetDevice(device));
+    void* h = nullptr;
+    RVCX_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
+    std::memset(h, 0, 64);
+    status_host = static_cast<unsigned*>(h);
+    void* d = nullptr;
+    RVCX_HIP(hipHostGetDevicePointer(&d, h, 0));
+    status_dev = static_cast<unsigned*>(d);
+  }
+  return status_dev;
+}
+
+void Ctx::check_device_status() {
+  if (!status_host) return;
+  const unsigned v = __atomic_load_n(status_host, __ATOMIC_ACQUIRE);
+  if (v == 0) return;
+  __atomic_store_n(status_host, 0u, __ATOMIC_RELEASE);
+  std::string what;
+  if (v & 1u) what += "gru: partner hand-off timed out (the RMVPE BiGRU's workgroups were not co-resident); ";
+  throw Error(RVCX_E_HIP, what + "the outputs of the call that raised this flag are invalid");
+}
+
+Ctx::~Ctx() {
+  if (status_host) (void)hipHostFree(status_host);
+  for (auto& kv : call_ev)
+    if (kv.second) (void)hipEventDestroy(kv.second);
+  if (aux) {
+    (void)hipStreamSynchronize(aux);
+    (void)hipEventDestroy(ev_fork);
+    (void)hipEventDestroy(ev_join);
+    (void)hipEventDestroy(ev_gate);
+    (void)hipStreamDestroy(aux);
+  }
+}
+
+hipStream_t fork_aux(Ctx& c, hipStream_t s) {
+  static const bool no_overlap = [] {
+    const char* e = rvcx_knob("RVCX_NO_OVERLAP");
+    return e && std::atoi(e) != 0;
+  }();
+  if (c.prof || no_overlap) return s;
+  hipStream_t ax = c.aux_stream();
+  RVCX_HIP(hipEventRecord(c.ev_fork, s));
+  RVCX_HIP(hipStreamWaitEvent(ax, c.ev_fork, 0));
+  return ax;
+}
+
+void join_aux(Ctx& c, hipStream_t s, hipStream_t ax) {
+  if (ax == s) return;
+  RVCX_HIP(hipEventRecord(c.ev_join, ax));
+  RVCX_HIP(hipStreamWaitEvent(s, c.ev_join, 0));
+}
+
+// the weight tensor's pre-split image (built once on first use; the stream then synchronises so a later use on
+// another stream never races the build)
+const void* Ctx::wsplit_for(const ConvArgs& a, hipStream_t s) {
+  const auto key = std::make_tuple(static_cast<const void*>(a.w), a.ldw, a.w_ts, a.N, a.C_in, a.taps, a.wsplit_fmt);
+  auto& slot = wsplit_cache[key];
+  if (!slot) {
+    std::unique_ptr<DevBuf> b(new DevBuf());
+    const size_t bytes = (size_t)conv_wsplit_bytes(a);
+    if (hipMalloc(&b->p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      throw Error(RVCX_E_OOM, "split-weight allocation failed");
+    }
+    b->bytes = bytes;
+    check(conv_wsplit_build(a, b->p, s), "conv_wsplit_build");
+    RVCX_HIP(hipStreamSynchronize(s));
+    slot = std::move(b);
+  }
+  return slot->p;
+}
+
+const void* Ctx::rb_wsplit_for(const float* w, int C, int k, int wfmt, hipStream_t s) {
+  auto& slot = rb_wsplit_cache[{static_cast<const void*>(w), wfmt}];
+  if (!slot) {
+    std::unique_ptr<DevBuf> b(new DevBuf());
+    const size_t bytes = (size_t)rb_wsplit_bytes(C, k, wfmt);
+    if (hipMalloc(&b->p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      throw Error(RVCX_E_OOM, "split-weight allocation failed");
+    }
+    b->bytes = bytes;
+    check(rb_wsplit_build(w, C, k, b->p, s, wfmt), "rb_wsplit_build");
+    RVCX_HIP(hipStreamSynchronize(s));
+    slot = std::move(b);
+  }
+  return slot->p;
+}
+
+// a timing event from the context's pool (rvcx_profile_read* hands them back)
+static hipEvent_t take_event(Ctx& c) {
+  hipEvent_t e;
+  if (!c.prof_pool.empty()) {
+    e = c.prof_pool.back();
+    c.prof_pool.pop_back();
+  } else {
+    RVCX_HIP(hipEventCreate(&e));
+  }
+  return e;
+}
+
+void launch_rb_pair(Ctx& c, const RbPairArgs& a, hipStream_t s) {
+  constexpr int cfg = 0;
+  if (!c.prof) {
+    check(rb_pair(a, cfg, s), "rb_pair");
+    return;
+  }
+  // algorithmic work: the two convs over the valid rows
+  const double flops = 2.0 * 2.0 * a.B * (double)a.T * a.C * a.C * a.k;
+  // x read, y written (+ read when accumulating), both weight tensors
+  const double bytes = 4.0 * ((double)a.B * a.T * a.C * (2 + (a.acc_mode != ACC_STORE ? 1 : 0)) + 2.0 * a.k * a.C * a.C);
+  Ctx::ProfRec r{take_event(c), take_event(c), flops, 0, a.T, a.C, a.C, -a.k, a.B, 1, bytes,
+                 a.wfmt == RB_WF16 ? (a.lowp ? Ctx::PEAK_F16 : Ctx::PEAK_F16X2) : Ctx::PEAK_SPLIT};
+  r.kind = CK_RBPAIR;
+  RVCX_HIP(hipEventRecord(r.a, s));
+  check(rb_pair(a, cfg, s), "rb_pair");
+  RVCX_HIP(hipEventRecord(r.b, s));
+  c.prof_recs.push_back(r);
+}
+
+bool conv_routes_wsb16(Ctx& c, const ConvArgs& a_in) {
+  ConvArgs a = a_in;
+  if (c.conv_math > 0 && a.math == 0) a.math = c.conv_math;
+  const ConvPlan p = conv_plan(a, false, a.w_static || c.is_weight(a.w));
+  return (p.kind == CK_WSB16 || p.kind == CK_WST) && p.wsplit_fmt == WSPLIT_H16 && p.ksplit == 1;
+}
+
+namespace {
+// the planned launch: the slab, the aux-stream throttle, conv_run and, with kernel timing on, its record
+void run_planned(Ctx& c, const ConvPlan& p, ConvArgs& a, bool two_d, bool forced, hipStream_t s, double flops) {
+  // split-K slabs are per stream: the aux stream's convs run concurrently with the caller's
+  // HuBERT's feature-encoder contractions (issued on the aux stream beside the U-Net, with ~1.5 ms of slack before the
+  // BiGRU) take 64 KB more LDS per workgroup: one or two of them per CU at most, so the U-Net's latency-bound chain
+  // finds free workgroup slots instead of waiting out ~50 us feature-conv workgroups. Same-box A/B (ms/step): r05ac
+  // none 13.53 / 13.47, 64 KB 13.28 / 13.35, 88 KB 13.25 / 13.27, 40 KB 13.39 / 13.51; r05ae none 13.53 / 13.54 /
+  // 13.48 / 13.51, 64 KB 13.39 / 13.16 / 13.37 / 13.33, 88 KB 13.48 / 13.29. Throttling HuBERT's transformer too
+  // (r05aa) costs +0.3-0.5 ms: it runs beside the BiGRU with little slack. RVCX_AUX_LDS=KB overrides (0: off)
+  static const int aux_lds = [] {
+    const char* e = rvcx_knob("RVCX_AUX_LDS");
+    return e ? std::max(0, std::atoi(e)) : 64;
+  }();
+  if (aux_lds > 0 && c.aux_front) a.lds_pad = aux_lds * 1024;
+  if (p.ksplit > 1)
+    a.ws = c.buf<float>(c.aux && s == c.aux ? "conv.splitk.aux" : "conv.splitk", (size_t)p.slab_floats, s);
+  auto run = [&] {
+    const hipError_t e = conv_run(p, a, two_d, s, forced);
+    if (e == hipSuccess) return;
+    // planned launches are not retried on another family: a refusal is a bug in the plan or a bad record
+    auto n = [](long long v) { return std::to_string(v); };
+    throw Error(RVCX_E_HIP, std::string(two_d ? "conv2d: " : "conv1d: ") + conv_kind_name(p.kind) + " tile " + n(p.tile) +
+                                " ksplit " + n(p.ksplit) + " refused " + n(a.T_out) + " x " + n(a.W_out) + " rows, N " +
+                                n(a.N) + ", C_in " + n(a.C_in) + ", " + n(a.taps) + " taps: " + hipGetErrorString(e));
+  };
+  if (!c.prof) return run();
+  if (flops < 0) {
+    const double M = two_d ? (double)a.T_out * a.W_out : (double)a.T_out;
+    flops = 2.0 * M * a.N * (double)a.C_in * a.taps * a.batch * a.batch_inner;
+  }
+  // input rows read once, weights once, output written once (+ read again for a residual / accumulate)
+  const double in_rows = two_d ? (double)a.T_in * a.W_in : (double)a.T_in;
+  const double out_el = (two_d ? (double)a.T_out * a.W_out : (double)a.T_out) * a.N * a.batch * a.batch_inner;
+  const double alg_bytes = 4.0 * (in_rows * a.C_in * a.batch * a.batch_inner + (double)a.taps * a.N * a.C_in +
+                                  out_el * (1 + (a.res && a.res_mode != RES_NONE ? 1 : 0) +
+                                            (a.acc_mode != ACC_STORE ? 1 : 0)));
+  // the launch's arithmetic ceiling (the rest of the family is priced at the bf16 split's, a lower bound for the few
+  // launches on the fp32-input MFMA)
+  const bool wsb = p.kind == CK_WSB16 || p.kind == CK_WST;
+  const double peak = p.wsplit_fmt == WSPLIT_H16 ? ((a.lowp && wsb) ? Ctx::PEAK_F16 : Ctx::PEAK_F16X2)
+                      : (p.wsplit_fmt == WSPLIT_S2D && a.wsplit) ? Ctx::PEAK_F16X2
+                                                                 : Ctx::PEAK_SPLIT;
+  Ctx::ProfRec r{take_event(c), take_event(c), flops, two_d ? 1 : 0, two_d ? a.T_out * a.W_out : a.T_out, a.N, a.C_in,
+                 a.taps, a.batch * a.batch_inner, p.ksplit, alg_bytes, peak};
+  r.kind = p.kind;
+  RVCX_HIP(hipEventRecord(r.a, s));
+  run();
+  RVCX_HIP(hipEventRecord(r.b, s));
+  c.prof_recs.push_back(r);
+}
+}  // namespace
+
+// plan, image, slab, run
+void launch_conv(Ctx& c, const ConvArgs& a_in, bool two_d, hipStream_t s, double flops) {
+  ConvArgs a = a_in;
+  if (c.conv_math > 0 && a.math == 0) a.math = c.conv_math;
+  const ConvPlan p = conv_plan(a, two_d, a.w_static || c.is_weight(a.w));
+  if (p.needs_image) {
+    a.wsplit_fmt = p.wsplit_fmt;  // the cache key and the builder read it
+    a.wsplit = c.wsplit_for(a, s);
+  }
+  run_planned(c, p, a, two_d, false, s, flops);
+}
+
+ConvPlan launch_conv_test(Ctx& c, const ConvArgs& a_in, bool two_d, bool static_weight, const ConvForce& force,
+                          int expect_kind, const char* who, hipStream_t s) {
+  ConvArgs a = a_in;
+  if (c.conv_math > 0 && a.math == 0) a.math = c.conv_math;
+  const ConvPlan p = conv_plan(a, two_d, static_weight, force);
+  const std::string w(who);
+  const int want = force.kind >= 0 ? force.kind : expect_kind;
+  if (p.kind == CK_OTHER || (expect_kind >= 0 && p.kind != expect_kind))
+    throw Error(RVCX_E_SHAPE, w + ": " + (want >= 0 ? conv_kind_name(want) : "the size policy's family") + " does not "
+                                  "admit this form, or its gate / LayerNorm get no split (two steps, no_splitk off)");
+  // (the runtime fuses the noise conv only where conv_routes_wsb16 holds)
+  if (a.nz_har && !((p.kind == CK_WSB16 || p.kind == CK_WST) && p.ksplit == 1))
+    throw Error(RVCX_E_SHAPE, w + ": the fused noise conv needs an unsplit weight-streamed / weight-stationary launch");
+  if (p.wsplit_fmt >= 0) {
+    // a fresh image every call, never the address-keyed cache: the caller may reuse the weight's address (or torch's
+    // allocator may hand it back) with new weights of the same shape
+    a.wsplit_fmt = p.wsplit_fmt;
+    void* img = c.buf<char>("conv.test.wsplit", (size_t)conv_wsplit_bytes(a), s);
+    check(conv_wsplit_build(a, img, s), "conv_wsplit_build");
+    a.wsplit = img;
+  }
+  run_planned(c, p, a, two_d, force.kind >= 0, s, -1.0);
+  return p;
+}
+
+__global__ void k_set_i32(int32_t* p, int32_t v) { p[0] = v; }
+void set_i32(int32_t* p, int32_t v, hipStream_t s) {
+  hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, s, p, v);
+  check(hipGetLastError(), "set_i32");
+}
+void set_i32_once(Ctx& c, const std::string& name, int32_t* p, int32_t v, hipStream_t s) {
+  auto it = c.i32_marks.find(name);
+  if (it != c.i32_marks.end() && it->second.first == p && it->second.second == v) return;
+  set_i32(p, v, s);
+  c.i32_marks[name] = {p, v};
+}
+}  // namespace rvcx
+

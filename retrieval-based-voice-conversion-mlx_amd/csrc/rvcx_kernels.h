@@ -109,17 +109,15 @@ struct ConvArgs {
   int batch = 1;
   int batch_inner = 1;
   long long x_bs2 = 0, w_bs2 = 0, y_bs2 = 0, res_bs2 = 0, bias_bs2 = 0;
-  // tuning / benchmarking: force a tile configuration and the software pipeline on/off
-  int force_cfg = -1;
-  int pipe = 0;
   int astage = 0;  // A-tile staging batch: 0 = default (1), 1 = serial, 4 = 4 loads in flight
   int math = 0;    // contraction arithmetic: 0 = default (RVCX_CONV_MATH), 1 = native fp32 MFMA, 2 = fp32 via 3 bf16 planes
-  // split-K: set by conv_plan_splitk; ws holds ksplit partial [rows][N] tiles per batch entry
-  // weight-streamed split kernel (conv_wsb.hip): w pre-split into bf16 planes, set by the runtime for static weights
   int w_static = 0;             // the B operand is a constant weight tensor (callers set it; enables the cache)
+  // the pre-split weight image of the streamed kernels, in the format the plan names (ConvPlan::wsplit_fmt): the
+  // runtime's cache for static weights, or the caller's own
   const void* wsplit = nullptr;  // ((chunk * taps + tap) * wsplit_npad + n) rows of [hi|mid|lo] x 32 bf16
+  // read by the kernels from their kernarg copy; written by conv_run alone, from the plan. ws (the caller's allocation
+  // of ConvPlan::slab_floats) holds ksplit partial [rows][N] tiles per batch entry
   int wsplit_npad = 0;
-  int wsb = 0;  // set by the runtime (conv_wsb_route on a static weight): 1 weight-streamed kernel, 2 gather-streamed
   int wsplit_fmt = 0;  // WSPLIT_BF16: three bf16 planes (every streamed kernel); WSPLIT_H16: two fp16 planes + scale tail
                        // (conv_wsb16_kernel only: the two-plane fp16 arithmetic and the reduced-precision mode)
   int ksplit = 1;
@@ -148,26 +146,50 @@ struct ConvArgs {
   int lds_pad = 0;
 };
 
-hipError_t conv1d(const ConvArgs& a, hipStream_t s);
-// the kernel family the last conv1d / conv2d on this host thread launched (kernel-timing records, rvcx_profile)
+// the kernel families (the plan's, and the kernel-timing records' of rvcx_profile)
 enum ConvKind : int { CK_WSB16 = 0, CK_WSB, CK_GS, CK_GSW, CK_RBPAIR, CK_SMALL2D, CK_EMU, CK_GEMM, CK_TINY, CK_WST,
                       CK_OTHER, CK_COUNT };
-int conv_last_kind();
 const char* conv_kind_name(int k);
+// Tile ids, by the numbers DESIGN.md, profiles/ and bench_conv's command line know them by: the LDS-staged kernels'
+// native fp32 tiles 0..9 (conv_gemm.hip) and bf16-split tiles 10..16 (conv_emu.hip), the weight-streamed 23..27
+// (conv_wsb.hip), the gather-streamed 30 (conv_gs.hip)
+enum ConvTile : int {
+  TILE_NONE = -1,  // the family has one form (tiny, 3x3 small-channel, weight-stationary)
+  TILE_F32_128x32 = 1, TILE_F32_64x64 = 3, TILE_EMU_128x32 = 12, TILE_EMU_64x64 = 13,
+  TILE_WSB_128x64 = 23, TILE_WSB_256x32 = 24, TILE_WSB_128x128 = 25, TILE_WSB_128x64_1x4 = 27, TILE_GS_64x64 = 30,
+};
+// a numerics test's or a benchmark's override of the policy: the family (a ConvKind, -1 = the policy's), its tile
+// (-1 = the policy's for that family) and the GEMM pipeline (0 = the policy: on for plain GEMMs, < 0 off, > 0 on)
+struct ConvForce {
+  int kind = -1, tile = TILE_NONE, pipe = 0;
+};
+// What one launch runs: the family, its tile, the split over K with the floats of slab it needs (ConvArgs::ws), the
+// weight image the family reads (a WsplitFmt, -1 = none) and whether the runtime's cache is to supply it
+// (needs_image), and the LDS-staged families' GEMM-pipeline form. kind CK_OTHER: no family admits the form.
+struct ConvPlan {
+  ConvKind kind;
+  int tile, ksplit;
+  long long slab_floats;
+  int wsplit_fmt;
+  bool needs_image, pipe;
+};
+// The one place a contraction's route is decided (conv_dispatch.hip). Pure host code: it reads the record's form --
+// shape, strides, epilogue fields, arithmetic -- and its pointers for nullness and alignment only; no field conv_run
+// writes. static_weight: the B operand is a constant tensor (only those take the streamed kernels).
+ConvPlan conv_plan(const ConvArgs& a, bool two_d, bool static_weight, const ConvForce& force = ConvForce());
+// launch the plan: that family's launcher and, for a split, the combine. a.ws holds plan.slab_floats floats when
+// plan.ksplit > 1, a.wsplit the image when plan.wsplit_fmt >= 0. A launcher that refuses is an error
+// (hipErrorInvalidValue), never another family; forced: not even another tile of the LDS-staged families
+hipError_t conv_run(const ConvPlan& plan, const ConvArgs& a, bool two_d, hipStream_t s, bool forced = false);
 // the contraction arithmetic a launch gets: ConvArgs::math, else RVCX_CONV_MATH (1 fp32 MFMA, 2 bf16 split, 3 fp16 split)
-int conv_math_of(const ConvArgs& a);
-// the family conv1d gives a 1-D launch that no streamed kernel takes (a.wsb == 0): CK_TINY, CK_EMU or CK_GEMM
-int conv_unstreamed_kind(const ConvArgs& a);
-hipError_t conv2d(const ConvArgs& a, hipStream_t s);
-// 3x3/pad-1 2-D convs with C_in, N in {16, 32} on 16x16x4 MFMA fragments (conv2d_small.hip); conv2d routes
+int conv_math(int requested);
+// 3x3/pad-1 2-D convs with C_in, N in {16, 32} on 16x16x4 MFMA fragments (conv2d_small.hip); the planner routes
 // the shapes conv2d_small_fits accepts there
 bool conv2d_small_fits(const ConvArgs& a);
 hipError_t conv2d_small(const ConvArgs& a, hipStream_t s);
 // their WSPLIT_S2D image (the fp16-split form reads it; built by conv_wsplit_build for that format)
 long long small2d_wsplit_bytes(const ConvArgs& a);
 hipError_t small2d_wsplit_build(const ConvArgs& a, void* out, hipStream_t s);
-// choose split-K for small output grids; returns the workspace floats needed (0 = no split)
-long long conv_plan_splitk(ConvArgs& a, bool two_d);
 
 // ---------------------------------------------------------------- misc kernels
 hipError_t fill(float* p, float v, long long n, hipStream_t s);
@@ -186,23 +208,18 @@ hipError_t gate_tanh_sigmoid(const float* xin, int ldx, const float* g, long lon
                              int T, int H, hipStream_t s);
 // y[b][t][c] += nb[c] + sum_{q < taps*stride} wf[(q / stride) * C + c][q % stride] * har[b*har_bs + t*stride + q]
 // (the NSF noise conv, hifigan_nsf.py:196-199, in its framed form); C % 4 == 0, taps*stride <= 16
-// weight-streamed split conv (conv_wsb.hip): eligibility (1-D, stride 1, C_in % 32 == 0, halo <= 64 rows, no
-// split-K), the pre-split weight image and its launch; conv_wsb_wants = eligible + split arithmetic + a grid
-// large enough to fill the chip (conv_dispatch.hip policy)
+// The admission predicates (*_eligible, *_fits) are questions about the caller's form alone: admitted means that
+// family's launcher takes the launch.
+// weight-streamed split conv (conv_wsb.hip): eligibility (1-D, stride 1, C_in % 32 == 0, halo <= 64 rows), the
+// pre-split weight image and its launch
 bool conv_wsb_eligible(const ConvArgs& a, bool two_d = false);
-bool conv_wsb_wants(const ConvArgs& a);
-// route a contraction with a static weight to the weight-streamed kernel (the big 1-D grids, conv_wsb_wants) or the
-// gather-streamed one (the rest with 32-channel chunks and >= 64 outputs)
-// 0: not routed (conv_emu / conv_gemm), 1: conv_wsb.hip, 2: conv_gs.hip
-int conv_wsb_route(const ConvArgs& a, bool two_d);
 bool conv_wsb_tile(int cfg, int& BM, int& BN);  // cfg 23, 24, 25, 27 -> tile
-int conv_wsb_pick(const ConvArgs& a);  // the weight-streamed tile cfg the size policy picks for a
 // gather-streamed split conv (conv_gs.hip) for the short contractions: pre-split weights (the conv_wsb image) in a
 // register ring, A gathered per (chunk, tap) step; 1-D (any stride / dilation) and 2-D (stride 1, OUT_ROWS), C_in % 32
 // == 0, split-K capable. cfg 30 -> its 64 x 64 tile
 bool conv_gs_eligible(const ConvArgs& a, bool two_d);
+bool conv_gs_form(const ConvArgs& a, bool two_d);  // eligible but for ConvArgs::lowp (these kernels have no such mode)
 bool conv_gsw_eligible(const ConvArgs& a);  // the windowed 2-D form (split-K slices of whole 32-channel chunks)
-bool conv_gs_tile(int cfg, int& BM, int& BN);
 hipError_t conv_gs_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d, int ksplit);
 int conv_wsplit_npad(int N);
 long long conv_wsplit_bytes(const ConvArgs& a);
@@ -211,8 +228,8 @@ hipError_t conv_wsb_launch(const ConvArgs& a, int cfg, hipStream_t s, bool two_d
                            int ksplit = 1);
 // weight-stationary form of the fp16-split conv (conv_wst.hip) for the short 64 / 128-channel convs (k = 3 ResBlock
 // convs, ConvTranspose phases): 1-D, C_in = N in {64, 128}, 2-3 taps, halo <= 16, no or leaky-ReLU pre-activation,
-// the WSPLIT_H16 image, bias / leaky-ReLU / RES_ADD_POST / acc modes / the fused noise conv; bit-identical to
-// conv_wsb16_kernel. The dispatcher takes it ahead of the weight-streamed tiles
+// the WSPLIT_H16 image, unsplit, bias / leaky-ReLU / RES_ADD_POST / acc modes / the fused noise conv; bit-identical to
+// conv_wsb16_kernel. The planner takes it ahead of the weight-streamed tiles
 bool conv_wst_fits(const ConvArgs& a, bool two_d);
 hipError_t conv_wst_launch(const ConvArgs& a, hipStream_t s);
 // fused ResBlock dilation pair (resblock_fused.hip): y (acc_mode) <- conv2(lrelu(conv1_d(lrelu(x)) + b1)) + b2 + x,

@@ -37,7 +37,8 @@ EXPORTS = [
 ]
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
 TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
-                "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update", "rvcx_rt_model_rows"]
+                "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update", "rvcx_rt_model_rows",
+                "rvcx_conv_plan"]
 
 
 class RvcxLibraryError(ImportError):
@@ -127,6 +128,14 @@ class ConvTestDesc(ctypes.Structure):
         ("nz_w", ctypes.c_void_p), ("nz_b", ctypes.c_void_p),
         ("route", ctypes.c_int), ("no_splitk", ctypes.c_int),
     ]
+
+
+class ConvPlanForm(ctypes.Structure):
+    """rvcx_conv_plan_form (include/rvcx_test.h): the record's fields a 1-D ConvTestDesc lacks."""
+    _fields_ = [("W_in", ctypes.c_int), ("W_out", ctypes.c_int), ("KH", ctypes.c_int), ("KW", ctypes.c_int),
+                ("padh", ctypes.c_int), ("padw", ctypes.c_int), ("out_map", ctypes.c_int), ("out_cv", ctypes.c_int),
+                ("b_kn", ctypes.c_int), ("lowp", ctypes.c_int), ("ldw", ctypes.c_int), ("w_ts", ctypes.c_int64),
+                ("w_bs", ctypes.c_int64), ("bias_bs", ctypes.c_int64)]
 
 
 class IndexBuildOpts(ctypes.Structure):
@@ -239,6 +248,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_conv1d_gen": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, i32, f32, i32,
                                   vp, vp]),
         "rvcx_conv1d_ex": (i32, [vp, P(ConvTestDesc), P(i32), P(i32), vp]),
+        "rvcx_conv_plan": (i32, [P(ConvTestDesc), P(ConvPlanForm), i32, i32, i32, i32, i32, i32, P(i32), P(i32), P(i32),
+                                 P(i32)]),
         "rvcx_conv2d3x3": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
         "rvcx_convtranspose2d_s2": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
         "rvcx_flash_attention": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, vp, vp, vp]),

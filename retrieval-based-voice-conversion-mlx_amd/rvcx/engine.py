@@ -810,6 +810,7 @@ class Engine:
         everywhere) or "f32" (fp32-input MFMA) (rvcx_set_conv_math)."""
         m = {"default": 0, "f32": 1, "split": 2, "h16": 3}[mode]
         self._check(self.lib.rvcx_set_conv_math(self.ctx, m), "set_conv_math")
+        self.conv_math = m
 
     def conv1d(self, x, w, bias=None, dilation: int = 1, padding: int = 0, stride: int = 1, math: str = "default"):
         """torch.nn.functional.conv1d(x.T[None], w, bias, stride, padding, dilation)[0].T on the device kernel:
@@ -912,11 +913,24 @@ class Engine:
                                                               float(acc_div), float(ln_eps))
         d.route = self.ROUTES[route] if isinstance(route, str) else int(route)
         d.no_splitk = 1 if no_splitk else 0
+        self.last_conv_desc = d  # what conv_plan() queries the planner with
         kind, ksplit = ctypes.c_int(-1), ctypes.c_int(0)
         self._check(self.lib.rvcx_conv1d_ex(self.ctx, ctypes.byref(d), ctypes.byref(kind), ctypes.byref(ksplit),
                                             self.stream()), "conv1d_ex")
         name = self.lib.rvcx_profile_kind_name(kind.value)
         return y, (name.decode() if name else "other"), int(ksplit.value)
+
+    def conv_plan(self, desc=None, static_weight: bool = True):
+        """What the planner decides under the size policy for a conv1d_ex descriptor (the last one launched unless given)
+        in this context's arithmetic: (kernel family name, tile id, split count, weight image format). Host only
+        (rvcx_conv_plan, include/rvcx_test.h)."""
+        out = [ctypes.c_int(-1) for _ in range(4)]
+        d = self.last_conv_desc if desc is None else desc
+        self._check(self.lib.rvcx_conv_plan(ctypes.byref(d), None, 0, 1 if static_weight else 0,
+                                            getattr(self, "conv_math", 0), 0, -1, -1, *[ctypes.byref(o) for o in out]),
+                    "conv_plan")
+        name = self.lib.rvcx_profile_kind_name(out[0].value)
+        return (name.decode() if name else "other"), out[1].value, out[2].value, out[3].value
 
     def conv2d3x3(self, x, w, bias=None, relu: bool = False, math: str = "default"):
         """torch.nn.functional.conv2d(x.permute(2, 0, 1)[None], w, bias, padding=1)[0].permute(1, 2, 0) on the device

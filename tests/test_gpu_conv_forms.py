@@ -160,6 +160,9 @@ def test_form(engine, name, route, nsk):
     after, kind, ksplit = _run(engine, name, route, nsk)
     if route != "policy":
         assert kind == KIND[route], (kind, route)
+    else:  # the launch ran what the planner, asked on the host alone, says it decides for this descriptor
+        pk, _, pks, _ = engine.conv_plan()
+        assert (kind, ksplit) == (pk, pks), (kind, ksplit, pk, pks)
     assert kind in FAMILIES, kind
     assert ksplit >= 1 and (ksplit == 1 or not nsk)
     if c["gate"] or c["ln"]:
