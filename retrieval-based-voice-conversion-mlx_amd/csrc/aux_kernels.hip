@@ -347,8 +347,6 @@ hipError_t noise_conv_add(const float* har, long long har_bs, int stride, int ta
 }
 
 // ------------------------------------------------------------------ feature x2 upsample + protect blend
-// pipeline.py:344-362: feats = interpolate(x2, nearest); pitchff = 1 if pitchf > 0 else protect;
-// feats = feats * pitchff + feats0 * (1 - pitchff)   (feats0 == feats without index retrieval).
 // x2 nearest upsample + protect blend (pipeline.py:344-362): feats = retrieved (or raw) features,
 // feats0 = raw features; v = feats * p + feats0 * (1 - p) with each product and the sum rounded (torch).
 #pragma clang fp contract(off)
@@ -377,8 +375,6 @@ hipError_t upsample2_protect(const float* feats, const float* feats0, int L, int
 }
 
 // ------------------------------------------------------------------ NSF harmonic source (SineGen, harmonic_num=0)
-// generators/hifigan.py:156-228 + hifigan_nsf.py:48-52. Phase carry: rem[l] = fmod(f0[l]/sr*upp + .5, 1) - .5,
-// cumsum accumulated in fp64 and rounded per element (torch CPU cumsum acc_type<float> = double), then fmod 1.
 // SineGen phase prefix (generators/hifigan.py:156-228): rem[l] = fmod(f0[l]/sr*upp + 0.5, 1) - 0.5,
 // cum = fmod(cumsum(rem), 1) with the cumsum accumulated in double (torch CPU acc type).
 // Parallel scan, bit-identical to torch's sequential double loop: for f0 >= 0, inc + 0.5 >= 0.5 so every
@@ -810,8 +806,10 @@ hipError_t reflect_pad_rows(const float* x, int rows, int C, int pad_r, float* y
                      s, x, rows, C, pad_r, y);
   return hipGetLastError();
 }
-// |STFT| rows of ldm floats: bins 0 .. nb - 1, then zeros up to ldm (the mel GEMM's contraction runs over whole
-// 32-bin chunks)
+// sqrt(re^2 + im^2 + eps) in rows of ldm floats: bins 0 .. nb - 1, then zeros up to ldm (the mel GEMM's contraction
+// runs over whole 32-bin chunks). eps is 0 (RMVPE) or 1e-9 (FCPE.py:154), one instantiation each, so that each caller
+// keeps the arithmetic its own kernel had: RMVPE's sum contracted to one FMA, FCPE's with every product and sum rounded
+template <bool EPS>
 __global__ void k_stftmag(const float* spec, int F, int nb, float* mag, int ldm) {
   const long long n = (long long)F * ldm;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -820,14 +818,15 @@ __global__ void k_stftmag(const float* spec, int F, int nb, float* mag, int ldm)
     if (k < nb) {
       const float re = spec[(long long)f * 2 * nb + k];
       const float im = spec[(long long)f * 2 * nb + nb + k];
-      v = sqrtf(re * re + im * im);
+      v = EPS ? sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)), 1e-9f)) : sqrtf(re * re + im * im);
     }
     mag[i] = v;
   }
 }
-hipError_t stft_magnitude(const float* spec, int F, int nbins, float* mag, int ldm, hipStream_t s) {
-  if (ldm < nbins) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_stftmag, dim3(nblocks((long long)F * ldm)), dim3(TB), 0, s, spec, F, nbins, mag, ldm);
+hipError_t stft_magnitude(const float* spec, int F, int nbins, float eps, float* mag, int ldm, hipStream_t s) {
+  if (ldm < nbins || (eps != 0.f && eps != 1e-9f)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(eps != 0.f ? k_stftmag<true> : k_stftmag<false>, dim3(nblocks((long long)F * ldm)), dim3(TB), 0, s,
+                     spec, F, nbins, mag, ldm);
   return hipGetLastError();
 }
 

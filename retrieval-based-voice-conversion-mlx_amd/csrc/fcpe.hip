@@ -1,9 +1,9 @@
-// Non-GEMM kernels of the FCPE pitch network (rvc/lib/predictors/FCPE.py): the STFT magnitude of its mel, the input
-// stack's GroupNorm + LeakyReLU, the Conformer module's GLU + depthwise conv + Swish, the cents decoders and
-// FCPEF0Predictor.post_process. The Performer attention is performer_attn.hip; the convs and linears run on the
+// Non-GEMM kernels of the FCPE pitch network (rvc/lib/predictors/FCPE.py): the input stack's GroupNorm + LeakyReLU,
+// the Conformer module's GLU + depthwise conv + Swish, the cents decoders and FCPEF0Predictor.post_process (the STFT
+// magnitude of its mel is aux_kernels.hip's, shared with RMVPE). The Performer attention is performer_attn.hip; the convs and linears run on the
 // implicit-GEMM family. The kernels that pad or reduce over time (GroupNorm, the depthwise conv, the mel's padding
 // and repeated last frame) take B streams of one length per launch, grid z (or y) = stream, each stream on its own
-// rows; the row-wise ones (magnitude, decoders) run on the B F rows of all streams.
+// rows; the row-wise ones (the decoders) run on the B F rows of all streams.
 #include <algorithm>
 #include <cmath>
 
@@ -22,21 +22,6 @@ inline unsigned nblocks(long long n, int per = TB) {
 }
 
 __device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
-
-// sqrt(re^2 + im^2 + 1e-9) (FCPE.py:154) in rows of ldm floats: bins 0 .. nb - 1, then zeros up to ldm
-__global__ void k_fcpe_mag(const float* spec, int F, int nb, float* mag, int ldm) {
-  const long long n = (long long)F * ldm;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int f = (int)(i / ldm), k = (int)(i % ldm);
-    float v = 0.f;
-    if (k < nb) {
-      const float re = spec[(long long)f * 2 * nb + k];
-      const float im = spec[(long long)f * 2 * nb + nb + k];
-      v = sqrtf(re * re + im * im + 1e-9f);
-    }
-    mag[i] = v;
-  }
-}
 
 // y[b][i] = x[b ldx + i - pad_l] for pad_l <= i < pad_l + n, else 0, i < ldy: the zero padding STFT.get_mel falls back
 // to when the reflection does not fit (FCPE.py:138), per stream
@@ -262,12 +247,6 @@ __global__ void k_fcpe_interp(const double* f0, int F, int n, const int* prev, c
 }
 
 }  // namespace
-
-hipError_t fcpe_magnitude(const float* spec, int F, int nbins, float* mag, int ldm, hipStream_t s) {
-  if (ldm < nbins) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_fcpe_mag, dim3(nblocks((long long)F * ldm)), dim3(TB), 0, s, spec, F, nbins, mag, ldm);
-  return hipGetLastError();
-}
 
 hipError_t fcpe_zero_pad(const float* x, int n, int pad_l, long long ldx, float* y, long long ldy, int B,
                          hipStream_t s) {

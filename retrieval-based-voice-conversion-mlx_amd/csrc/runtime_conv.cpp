@@ -1,5 +1,5 @@
 // The runtime's side of a conv launch: plan (conv_dispatch.hip), weight image, split-K slab, run, with optional event
-// timing; the fused ResBlock pair's launch; and the context's streams, events and device-status word.
+// timing; the fused ResBlock pair's launch; and the context's streams, events, device-status word and packed weights.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +73,55 @@ void join_aux(Ctx& c, hipStream_t s, hipStream_t ax) {
   if (ax == s) return;
   RVCX_HIP(hipEventRecord(c.ev_join, ax));
   RVCX_HIP(hipStreamWaitEvent(s, c.ev_join, 0));
+}
+
+float* Ctx::W(const std::string& name) const {
+  auto it = dev.find(name);
+  if (it == dev.end()) throw Error(RVCX_E_STATE, "packed weight not found: " + name);
+  return static_cast<float*>(it->second->p);
+}
+
+float* Ctx::alloc_weight(const std::string& name, const std::vector<float>& data) {
+  std::unique_ptr<DevBuf> b(new DevBuf());
+  size_t bytes = data.size() * sizeof(float);
+  if (bytes == 0) bytes = 16;
+  if (hipMalloc(&b->p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    throw Error(RVCX_E_OOM, "weight allocation failed: " + name);
+  }
+  b->bytes = bytes;
+  RVCX_HIP(hipMemcpy(b->p, data.data(), data.size() * sizeof(float), hipMemcpyHostToDevice));
+  float* p = static_cast<float*>(b->p);
+  auto old = dev.find(name);
+  if (old != dev.end()) {
+    const uintptr_t o = reinterpret_cast<uintptr_t>(old->second->p);
+    wranges.erase(o);
+    drop_splits(o, o + old->second->bytes);  // the replaced tensor's split images
+  }
+  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+  drop_splits(u, u + bytes);  // images cached for an earlier tensor at a reused address
+  wranges[u] = u + bytes;
+  dev[name] = std::move(b);
+  return p;
+}
+
+void Ctx::drop_splits(uintptr_t lo, uintptr_t hi) {
+  for (auto it = wsplit_cache.begin(); it != wsplit_cache.end();) {
+    const uintptr_t u = reinterpret_cast<uintptr_t>(std::get<0>(it->first));
+    it = (u >= lo && u < hi) ? wsplit_cache.erase(it) : std::next(it);
+  }
+  for (auto it = rb_wsplit_cache.begin(); it != rb_wsplit_cache.end();) {
+    const uintptr_t u = reinterpret_cast<uintptr_t>(it->first.first);
+    it = (u >= lo && u < hi) ? rb_wsplit_cache.erase(it) : std::next(it);
+  }
+}
+
+bool Ctx::is_weight(const void* q) const {
+  const uintptr_t u = reinterpret_cast<uintptr_t>(q);
+  auto it = wranges.upper_bound(u);
+  if (it == wranges.begin()) return false;
+  --it;
+  return u < it->second;
 }
 
 // the weight tensor's pre-split image (built once on first use; the stream then synchronises so a later use on

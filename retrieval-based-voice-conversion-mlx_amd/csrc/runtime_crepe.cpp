@@ -9,7 +9,7 @@
 // The classifier (Linear + sigmoid) gives the [F][360] probabilities; decode + median/mean filters finish.
 #include <cmath>
 
-#include "runtime.h"
+#include "model_build.h"
 
 namespace rvcx {
 
@@ -20,43 +20,7 @@ constexpr int CHUNK = 256;  // frames per pass: bounds conv1's [CHUNK][256][C1] 
 constexpr int KC = 64;      // conv2..6 kernel
 constexpr double BN_EPS = 1e-3;
 
-const HostTensor& getc(Ctx& c, const std::string& n, std::vector<int64_t> shape) {
-  auto it = c.host[M].find(n);
-  if (it == c.host[M].end()) throw Error(RVCX_E_STATE, "missing weight: " + n);
-  if (it->second.shape != shape) {
-    std::string got, want;
-    for (auto s : it->second.shape) got += std::to_string(s) + ",";
-    for (auto s : shape) want += std::to_string(s) + ",";
-    throw Error(RVCX_E_SHAPE, "weight " + n + " has shape (" + got + ") expected (" + want + ")");
-  }
-  return it->second;
-}
-
 int crepe_cap(const Ctx& c, int i) { return (int)c.host[M].at("__cap__").v[i]; }
-
-ConvArgs conv1d_args(const float* x, int ldx, int Tin, int Cin, const float* w, int N, int taps, int dil, int pad,
-                     const float* bias, float* y, int Tout, int B) {
-  ConvArgs a;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = Tin;
-  a.C_in = Cin;
-  a.x_bs = (long long)Tin * ldx;
-  a.w = w;
-  a.ldw = Cin;
-  a.w_ts = (long long)N * Cin;
-  a.taps = taps;
-  a.dil = dil;
-  a.pad = pad;
-  a.y = y;
-  a.ldy = N;
-  a.y_bs = (long long)Tout * N;
-  a.T_out = Tout;
-  a.N = N;
-  a.bias = bias;
-  a.batch = B;
-  return a;
-}
 }  // namespace
 
 // Validates torchcrepe-named weights (conv{i}.weight [O][I][K][1], conv{i}.bias, conv{i}_BN.*, classifier.*),
@@ -79,23 +43,22 @@ void finalize_crepe(Ctx& c) {
   for (int i = 0; i < 6; ++i) {
     const std::string p = "conv" + std::to_string(i + 1);
     const int O = cap[i], I = i == 0 ? 1 : cap[i - 1], K = i == 0 ? K1 : KC;
-    const auto& w = getc(c, p + ".weight", {O, I, K, 1}).v;
-    std::vector<float> pk((size_t)O * I * K);
+    const HostTensor& wt = host_weight(c, M, p + ".weight", {O, I, K, 1});
+    std::vector<float> pk;
     if (i == 0) {  // [tap t][o][ch j] = w[o][0][32 t + j]
+      pk.resize(wt.v.size());
       for (int t = 0; t < K1 / 32; ++t)
         for (int o = 0; o < O; ++o)
-          for (int j = 0; j < 32; ++j) pk[((size_t)t * O + o) * 32 + j] = w[(size_t)o * K1 + 32 * t + j];
+          for (int j = 0; j < 32; ++j) pk[((size_t)t * O + o) * 32 + j] = wt.v[(size_t)o * K1 + 32 * t + j];
     } else {
-      for (int o = 0; o < O; ++o)
-        for (int ci = 0; ci < I; ++ci)
-          for (int k = 0; k < K; ++k) pk[((size_t)k * O + o) * I + ci] = w[((size_t)o * I + ci) * K + k];
+      pk = pack_conv1d(wt);  // [O][I][K][1] -> [K][O][I]
     }
     c.alloc_weight("cr." + p + ".w", pk);
-    c.alloc_weight("cr." + p + ".b", getc(c, p + ".bias", {O}).v);
-    const auto& mu = getc(c, p + "_BN.running_mean", {O}).v;
-    const auto& var = getc(c, p + "_BN.running_var", {O}).v;
-    const auto& gam = getc(c, p + "_BN.weight", {O}).v;
-    const auto& bet = getc(c, p + "_BN.bias", {O}).v;
+    c.alloc_weight("cr." + p + ".b", host_weight(c, M, p + ".bias", {O}).v);
+    const auto& mu = host_weight(c, M, p + "_BN.running_mean", {O}).v;
+    const auto& var = host_weight(c, M, p + "_BN.running_var", {O}).v;
+    const auto& gam = host_weight(c, M, p + "_BN.weight", {O}).v;
+    const auto& bet = host_weight(c, M, p + "_BN.bias", {O}).v;
     std::vector<float> bn((size_t)4 * O);
     for (int o = 0; o < O; ++o) {
       bn[o] = mu[o];
@@ -106,8 +69,8 @@ void finalize_crepe(Ctx& c) {
     c.alloc_weight("cr." + p + ".bn", bn);
   }
   const int feat = 4 * cap[5];  // 1024 / 4 / 2^6 = 4 rows x C6 (crepe.py:70, :76)
-  c.alloc_weight("cr.fc.w", getc(c, "classifier.weight", {BINS, feat}).v);
-  c.alloc_weight("cr.fc.b", getc(c, "classifier.bias", {BINS}).v);
+  c.alloc_weight("cr.fc.w", host_weight(c, M, "classifier.weight", {BINS, feat}).v);
+  c.alloc_weight("cr.fc.b", host_weight(c, M, "classifier.bias", {BINS}).v);
   std::vector<float> capv(cap, cap + 6);
   c.host[M]["__cap__"] = HostTensor{capv, {6}};
 }
@@ -138,8 +101,8 @@ int64_t crepe_forward(Ctx& c, const float* audio, int64_t n, double f0_min, doub
     const int B = (int)std::min<int64_t>(nb, F - f0i);
     check(crepe_frames(audio, n, f0i, B, fr, FRAME_LD, s, sem), "crepe_frames");
     {  // conv1: rows of 32 samples every 4 (376 rows cover the 1532-sample padded frame), 16 taps at dilation 8
-      ConvArgs a = conv1d_args(fr, 4, (FRAME_LD - 32) / 4 + 1, 32, c.W("cr.conv1.w"), cap[0], K1 / 32, 8, 0,
-                               c.W("cr.conv1.b"), hc, 256, B);
+      ConvArgs a = conv1d(fr, 4, (FRAME_LD - 32) / 4 + 1, 32, c.W("cr.conv1.w"), cap[0], K1 / 32, 8, 0,
+                          c.W("cr.conv1.b"), hc, cap[0], 256, B);
       a.x_bs = FRAME_LD;
       launch_conv(c, a, false, s, 2.0 * B * 256.0 * cap[0] * K1);
     }
@@ -147,25 +110,14 @@ int64_t crepe_forward(Ctx& c, const float* audio, int64_t n, double f0_min, doub
     int H = 128;
     for (int i = 1; i < 6; ++i) {
       const std::string p = "cr.conv" + std::to_string(i + 1);
-      ConvArgs a = conv1d_args(hp, cap[i - 1], H, cap[i - 1], c.W(p + ".w"), cap[i], KC, 1, KC / 2 - 1, c.W(p + ".b"),
-                               hc, H, B);
-      launch_conv(c, a, false, s);
+      launch_conv(c, conv1d(hp, cap[i - 1], H, cap[i - 1], c.W(p + ".w"), cap[i], KC, 1, KC / 2 - 1, c.W(p + ".b"), hc,
+                            cap[i], H, B),
+                  false, s);
       check(crepe_relu_bn_pool(hc, (long long)B * H, cap[i], c.W(p + ".bn"), hp, s), "crepe_bn");
       H /= 2;
     }
     // classifier over the flattened [4][C6] rows (H-major then channel, crepe.py:214-220) + sigmoid
-    ConvArgs a;
-    a.x = hp;
-    a.ldx = feat;
-    a.T_in = B;
-    a.C_in = feat;
-    a.w = c.W("cr.fc.w");
-    a.ldw = feat;
-    a.y = probs + (size_t)f0i * BINS;
-    a.ldy = BINS;
-    a.T_out = B;
-    a.N = BINS;
-    a.bias = c.W("cr.fc.b");
+    ConvArgs a = lin(hp, feat, B, feat, c.W("cr.fc.w"), BINS, c.W("cr.fc.b"), probs + (size_t)f0i * BINS, BINS);
     a.act = ACT_SIGMOID;
     launch_conv(c, a, false, s);
   }

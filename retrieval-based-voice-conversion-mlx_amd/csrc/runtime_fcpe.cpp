@@ -12,102 +12,15 @@
 //            padded or reduced over time per stream. fcpe_forward is its B = 1 case plus the interp_uv / pad_to tail
 #include <cmath>
 
-#include "runtime.h"
+#include "model_build.h"
 
 namespace rvcx {
 
 namespace {
 constexpr int M = RVCX_MODEL_FCPE;  // model slot
 
-const HostTensor& getf(Ctx& c, const std::string& n, std::vector<int64_t> shape) {
-  auto it = c.host[M].find(n);
-  if (it == c.host[M].end()) throw Error(RVCX_E_STATE, "missing weight: " + n);
-  if (it->second.shape != shape) {
-    std::string got, want;
-    for (auto s : it->second.shape) got += std::to_string(s) + ",";
-    for (auto s : shape) want += std::to_string(s) + ",";
-    throw Error(RVCX_E_SHAPE, "weight " + n + " has shape (" + got + ") expected (" + want + ")");
-  }
-  return it->second;
-}
-
-std::vector<float> pack_k(const HostTensor& t) {  // Conv1d [O][I][K] -> [K][O][I]
-  const int64_t O = t.shape[0], I = t.shape[1], K = t.shape[2];
-  std::vector<float> out(t.v.size());
-  for (int64_t o = 0; o < O; ++o)
-    for (int64_t i = 0; i < I; ++i)
-      for (int64_t k = 0; k < K; ++k) out[(k * O + o) * I + i] = t.v[(o * I + i) * K + k];
-  return out;
-}
-
-// y [rows][N] = x [rows][K] W^T + bias, W [N][K]
-ConvArgs lin(const float* x, int ldx, int rows, int K, const float* w, int N, const float* bias, float* y, int ldy) {
-  ConvArgs a;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = rows;
-  a.C_in = K;
-  a.w = w;
-  a.ldw = K;
-  a.taps = 1;
-  a.y = y;
-  a.ldy = ldy;
-  a.T_out = rows;
-  a.N = N;
-  a.bias = bias;
-  return a;
-}
-
-ConvArgs conv3(const float* x, int rows, int Cin, const float* w, int N, const float* bias, float* y) {
-  ConvArgs a = lin(x, Cin, rows, Cin, w, N, bias, y, N);
-  a.w_ts = (long long)N * Cin;
-  a.taps = 3;
-  a.pad = 1;
-  return a;
-}
-
-int nbin_padded(int n_fft) { return (n_fft / 2 + 1 + 31) / 32 * 32; }
-
-// librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) with its defaults htk=False, norm='slaney' (FCPE.py:123-126),
-// rows of nbin_padded floats (bins past n_fft / 2 zero)
-std::vector<float> mel_basis(const FcpeCfg& g) {
-  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
-  auto hz2mel = [&](double f) { return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp; };
-  auto mel2hz = [&](double m) { return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m; };
-  const int n = g.n_mels + 2, nbin = g.n_fft / 2 + 1, ld = nbin_padded(g.n_fft);
-  const double lo = hz2mel(g.fmin), hi = hz2mel(g.fmax), step = (hi - lo) / (n - 1);
-  std::vector<double> mel_f(n);
-  for (int i = 0; i < n; ++i) mel_f[i] = mel2hz(i == n - 1 ? hi : lo + i * step);
-  std::vector<float> w((size_t)g.n_mels * ld, 0.f);
-  for (int i = 0; i < g.n_mels; ++i) {
-    const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
-    const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-    for (int k = 0; k < nbin; ++k) {
-      const double f = k * ((double)g.sr / g.n_fft);
-      const float tri = (float)std::max(0.0, std::min(-(mel_f[i] - f) / fd0, (mel_f[i + 2] - f) / fd1));
-      w[(size_t)i * ld + k] = (float)((double)tri * enorm);
-    }
-  }
-  return w;
-}
-
-// the STFT (periodic Hann window of `win`, center = False) as a conv over 32-sample rows: W[tap][n][c], sample
-// 32 tap + c; n < nbin real, else imaginary
-std::vector<float> stft_weights(int win) {
-  const int nbin = win / 2 + 1, taps = win / 32;
-  std::vector<float> w((size_t)taps * 2 * nbin * 32);
-  const double pi = 3.14159265358979323846;
-  for (int t = 0; t < taps; ++t)
-    for (int nn = 0; nn < 2 * nbin; ++nn)
-      for (int cc = 0; cc < 32; ++cc) {
-        const int k = 32 * t + cc;
-        const double wn = 0.5 - 0.5 * std::cos(2.0 * pi * k / win);
-        const int f = nn < nbin ? nn : nn - nbin;
-        const double ang = 2.0 * pi * (double)((long long)k * f % win) / win;
-        w[((size_t)t * 2 * nbin + nn) * 32 + cc] = (float)(wn * (nn < nbin ? std::cos(ang) : -std::sin(ang)));
-      }
-  return w;
-}
+// STFT.get_mel (FCPE.py:123-126, :154): librosa's default (Slaney) basis, sqrt(re^2 + im^2 + 1e-9); n_fft == win
+MelSpec mel_spec(const FcpeCfg& g) { return {g.sr, g.win, g.hop, g.n_mels, g.fmin, g.fmax, false, 1e-9f}; }
 
 std::string lp(int i) { return "decoder._layers." + std::to_string(i) + "."; }
 std::string dn(int i, const char* what) { return "fc.l" + std::to_string(i) + "." + what; }
@@ -134,47 +47,48 @@ void finalize_fcpe(Ctx& c) {
   if (g.n_feat < 1 || g.n_feat > PERFORMER_MAX_FEATURES)
     throw Error(RVCX_E_SHAPE, "fcpe: projection_matrix rows (nb_features) must be in [1, 512]");
   c.alloc_weight("fc.stft", stft_weights(g.win));
-  c.alloc_weight("fc.mel", mel_basis(g));
-  c.alloc_weight("fc.stack0.w", pack_k(getf(c, "stack.0.weight", {C, g.n_mels, 3})));
-  c.alloc_weight("fc.stack0.b", getf(c, "stack.0.bias", {C}).v);
-  c.alloc_weight("fc.gn.g", getf(c, "stack.1.weight", {C}).v);
-  c.alloc_weight("fc.gn.b", getf(c, "stack.1.bias", {C}).v);
-  c.alloc_weight("fc.stack3.w", pack_k(getf(c, "stack.3.weight", {C, C, 3})));
-  c.alloc_weight("fc.stack3.b", getf(c, "stack.3.bias", {C}).v);
+  c.alloc_weight("fc.mel", mel_basis(mel_spec(g)));
+  c.alloc_weight("fc.stack0.w", pack_conv1d(host_weight(c, M, "stack.0.weight", {C, g.n_mels, 3})));
+  c.alloc_weight("fc.stack0.b", host_weight(c, M, "stack.0.bias", {C}).v);
+  c.alloc_weight("fc.gn.g", host_weight(c, M, "stack.1.weight", {C}).v);
+  c.alloc_weight("fc.gn.b", host_weight(c, M, "stack.1.bias", {C}).v);
+  c.alloc_weight("fc.stack3.w", pack_conv1d(host_weight(c, M, "stack.3.weight", {C, C, 3})));
+  c.alloc_weight("fc.stack3.b", host_weight(c, M, "stack.3.bias", {C}).v);
   for (int i = 0; i < g.n_layers; ++i) {
     const std::string p = lp(i);
-    c.alloc_weight(dn(i, "ln.g"), getf(c, p + "norm.weight", {C}).v);
-    c.alloc_weight(dn(i, "ln.b"), getf(c, p + "norm.bias", {C}).v);
+    c.alloc_weight(dn(i, "ln.g"), host_weight(c, M, p + "norm.weight", {C}).v);
+    c.alloc_weight(dn(i, "ln.b"), host_weight(c, M, p + "norm.bias", {C}).v);
     std::vector<float> w, b;
     for (const char* n : {"to_q", "to_k", "to_v"}) {
-      const auto& wv = getf(c, p + "attn." + n + ".weight", {inner, C}).v;
-      const auto& bv = getf(c, p + "attn." + n + ".bias", {inner}).v;
+      const auto& wv = host_weight(c, M, p + "attn." + n + ".weight", {inner, C}).v;
+      const auto& bv = host_weight(c, M, p + "attn." + n + ".bias", {inner}).v;
       w.insert(w.end(), wv.begin(), wv.end());
       b.insert(b.end(), bv.begin(), bv.end());
     }
     c.alloc_weight(dn(i, "qkv.w"), w);
     c.alloc_weight(dn(i, "qkv.b"), b);
-    c.alloc_weight(dn(i, "proj"), getf(c, p + "attn.fast_attention.projection_matrix", {g.n_feat, g.dim_head}).v);
-    c.alloc_weight(dn(i, "out.w"), getf(c, p + "attn.to_out.weight", {C, inner}).v);
-    c.alloc_weight(dn(i, "out.b"), getf(c, p + "attn.to_out.bias", {C}).v);
-    c.alloc_weight(dn(i, "cf.ln.g"), getf(c, p + "conformer.net.0.weight", {C}).v);
-    c.alloc_weight(dn(i, "cf.ln.b"), getf(c, p + "conformer.net.0.bias", {C}).v);
-    c.alloc_weight(dn(i, "cf.pw1.w"), getf(c, p + "conformer.net.2.weight", {4 * C, C, 1}).v);
-    c.alloc_weight(dn(i, "cf.pw1.b"), getf(c, p + "conformer.net.2.bias", {4 * C}).v);
-    const auto& dw = getf(c, p + "conformer.net.4.conv.weight", {2 * C, 1, K}).v;
+    c.alloc_weight(dn(i, "proj"),
+                   host_weight(c, M, p + "attn.fast_attention.projection_matrix", {g.n_feat, g.dim_head}).v);
+    c.alloc_weight(dn(i, "out.w"), host_weight(c, M, p + "attn.to_out.weight", {C, inner}).v);
+    c.alloc_weight(dn(i, "out.b"), host_weight(c, M, p + "attn.to_out.bias", {C}).v);
+    c.alloc_weight(dn(i, "cf.ln.g"), host_weight(c, M, p + "conformer.net.0.weight", {C}).v);
+    c.alloc_weight(dn(i, "cf.ln.b"), host_weight(c, M, p + "conformer.net.0.bias", {C}).v);
+    c.alloc_weight(dn(i, "cf.pw1.w"), host_weight(c, M, p + "conformer.net.2.weight", {4 * C, C, 1}).v);
+    c.alloc_weight(dn(i, "cf.pw1.b"), host_weight(c, M, p + "conformer.net.2.bias", {4 * C}).v);
+    const auto& dw = host_weight(c, M, p + "conformer.net.4.conv.weight", {2 * C, 1, K}).v;
     std::vector<float> dwt((size_t)K * 2 * C);
     for (int ch = 0; ch < 2 * C; ++ch)
       for (int k = 0; k < K; ++k) dwt[(size_t)k * 2 * C + ch] = dw[(size_t)ch * K + k];
     c.alloc_weight(dn(i, "cf.dw.w"), dwt);
-    c.alloc_weight(dn(i, "cf.dw.b"), getf(c, p + "conformer.net.4.conv.bias", {2 * C}).v);
-    c.alloc_weight(dn(i, "cf.pw2.w"), getf(c, p + "conformer.net.6.weight", {C, 2 * C, 1}).v);
-    c.alloc_weight(dn(i, "cf.pw2.b"), getf(c, p + "conformer.net.6.bias", {C}).v);
+    c.alloc_weight(dn(i, "cf.dw.b"), host_weight(c, M, p + "conformer.net.4.conv.bias", {2 * C}).v);
+    c.alloc_weight(dn(i, "cf.pw2.w"), host_weight(c, M, p + "conformer.net.6.weight", {C, 2 * C, 1}).v);
+    c.alloc_weight(dn(i, "cf.pw2.b"), host_weight(c, M, p + "conformer.net.6.bias", {C}).v);
   }
-  c.alloc_weight("fc.norm.g", getf(c, "norm.weight", {C}).v);
-  c.alloc_weight("fc.norm.b", getf(c, "norm.bias", {C}).v);
-  c.alloc_weight("fc.dense.w", getf(c, "dense_out.weight", {g.out_dims, C}).v);
-  c.alloc_weight("fc.dense.b", getf(c, "dense_out.bias", {g.out_dims}).v);
-  c.alloc_weight("fc.cent", getf(c, "cent_table", {g.out_dims}).v);
+  c.alloc_weight("fc.norm.g", host_weight(c, M, "norm.weight", {C}).v);
+  c.alloc_weight("fc.norm.b", host_weight(c, M, "norm.bias", {C}).v);
+  c.alloc_weight("fc.dense.w", host_weight(c, M, "dense_out.weight", {g.out_dims, C}).v);
+  c.alloc_weight("fc.dense.b", host_weight(c, M, "dense_out.bias", {g.out_dims}).v);
+  c.alloc_weight("fc.cent", host_weight(c, M, "cent_table", {g.out_dims}).v);
 }
 
 // the frames FCPEInfer gives for n samples: n / hop + 1, or one more than the STFT's when that is fewer
@@ -213,41 +127,14 @@ int fcpe_mel(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float* me
   const FcpeCfg& g = c.fcfg;
   if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
   if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
-  const int nbin = g.n_fft / 2 + 1, ldm = nbin_padded(g.n_fft);
+  const MelSpec ms = mel_spec(g);
   const int64_t pl = (g.win - g.hop) / 2, pr = std::max<int64_t>((g.win - g.hop + 1) / 2, g.win - n - pl);
-  const int64_t np = n + pl + pr, rows = (np + 31) / 32;
-  const int Fs = (int)((np - g.win) / g.hop + 1);
+  const int Fs = (int)((n + pl + pr - g.win) / g.hop + 1);
   const int F = (int)fcpe_frames(c, n), Fm = std::min(Fs, F);
-  if ((int64_t)B * F > INT32_MAX / std::max(4 * g.n_chans, 2 * nbin)) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
-  float* xp = c.buf<float>("fc.xp", (size_t)B * rows * 32, s);
-  if (pr < n) {
-    check(reflect_pad_1d(audio, (int)n, (int)pl, (int)pr, xp, s, B, ld, rows * 32), "fcpe_pad");
-  } else {  // torch pads with zeros when the reflection would not fit (:138)
-    check(fcpe_zero_pad(audio, (int)n, (int)pl, ld, xp, rows * 32, B, s), "fcpe_pad");
-  }
-  float* spec = c.buf<float>("fc.spec", (size_t)B * Fm * 2 * nbin, s);
-  {
-    ConvArgs a = lin(xp, 32, (int)rows, 32, c.W("fc.stft"), 2 * nbin, nullptr, spec, 2 * nbin);
-    a.taps = g.win / 32;
-    a.stride = g.hop / 32;
-    a.w_ts = (long long)2 * nbin * 32;
-    a.T_out = Fm;
-    a.batch = B;
-    a.x_bs = rows * 32;
-    a.y_bs = (long long)Fm * 2 * nbin;
-    launch_conv(c, a, false, s, 0.0);
-  }
-  float* mag = c.buf<float>("fc.mag", (size_t)B * Fm * ldm, s);
-  check(fcpe_magnitude(spec, B * Fm, nbin, mag, ldm, s), "fcpe_magnitude");
-  {
-    ConvArgs a = lin(mag, ldm, Fm, ldm, c.W("fc.mel"), g.n_mels, nullptr, mel, g.n_mels);
-    a.act = ACT_LOGCLAMP;
-    a.slope = 1e-5f;
-    a.batch = B;  // Fm rows of each stream into its F rows of mel
-    a.x_bs = (long long)Fm * ldm;
-    a.y_bs = (long long)F * g.n_mels;
-    launch_conv(c, a, false, s);
-  }
+  if ((int64_t)B * F > INT32_MAX / std::max(4 * g.n_chans, 2 * ms.nbin()))
+    throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  // torch pads with zeros when the reflection would not fit (:138)
+  mel_forward(c, ms, "fc.", audio, n, ld, B, MelFrames{pl, pr, pr >= n, Fm, F, true}, mel, s);
   if (F > Fm) check(fcpe_dup_last_frame(mel, B, F, g.n_mels, s), "fcpe_dup_last_frame");
   return F;
 }
@@ -270,21 +157,15 @@ int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B,
   const int R = B * F;  // rows of every row-wise op (fcpe_mel checks the range)
   float* mel = c.buf<float>("fc.mel", (size_t)R * g.n_mels, s);
   fcpe_mel(c, audio, n, ld, B, mel, s);
-  auto per_stream = [&](ConvArgs a, int Cin, int N) {  // a k = 3 conv over each stream's own F rows
-    a.batch = B;
-    a.x_bs = (long long)F * Cin;
-    a.y_bs = (long long)F * N;
-    return a;
-  };
-  // ---- input stack (:624-631)
+  // ---- input stack (:624-631): the k = 3 convs (zero pad 1) over each stream's own F rows
   float* x = c.buf<float>("fc.x", (size_t)R * C, s);
   float* x1 = c.buf<float>("fc.x1", (size_t)R * C, s);
   float* ln = c.buf<float>("fc.ln", (size_t)R * C, s);
-  launch_conv(c, per_stream(conv3(mel, F, g.n_mels, c.W("fc.stack0.w"), C, c.W("fc.stack0.b"), x1), g.n_mels, C), false,
-              s);
+  launch_conv(c, conv1d(mel, g.n_mels, F, g.n_mels, c.W("fc.stack0.w"), C, 3, 1, 1, c.W("fc.stack0.b"), x1, C, F, B),
+              false, s);
   double* gnws = c.buf<double>("fc.gnws", (size_t)B * 4 * FCPE_GN_CHUNKS * 2, s);
   check(groupnorm_lrelu(x1, F, C, 4, c.W("fc.gn.g"), c.W("fc.gn.b"), 1e-5f, 0.01f, gnws, s, B), "fcpe_groupnorm");
-  launch_conv(c, per_stream(conv3(x1, F, C, c.W("fc.stack3.w"), C, c.W("fc.stack3.b"), x), C, C), false, s);
+  launch_conv(c, conv1d(x1, C, F, C, c.W("fc.stack3.w"), C, 3, 1, 1, c.W("fc.stack3.b"), x, C, F, B), false, s);
   // ---- PCmer (:270-283)
   float* qkv = c.buf<float>("fc.qkv", (size_t)R * 3 * inner, s);
   float* att = c.buf<float>("fc.att", (size_t)R * inner, s);

@@ -5,53 +5,11 @@
 //           MLX rvc_mlx/lib/mlx/rmvpe.py.
 #include <cmath>
 
-#include "runtime.h"
+#include "model_build.h"
 
 namespace rvcx {
 
 namespace {
-
-const HostTensor& getw(Ctx& c, int model, const std::string& n, std::vector<int64_t> shape) {
-  auto it = c.host[model].find(n);
-  if (it == c.host[model].end()) throw Error(RVCX_E_STATE, "missing weight: " + n);
-  if (it->second.shape != shape) {
-    std::string got, want;
-    for (auto s : it->second.shape) got += std::to_string(s) + ",";
-    for (auto s : shape) want += std::to_string(s) + ",";
-    throw Error(RVCX_E_SHAPE, "weight " + n + " has shape (" + got + ") expected (" + want + ")");
-  }
-  return it->second;
-}
-
-std::vector<float> pack_conv1d(const HostTensor& t) {
-  const int64_t O = t.shape[0], I = t.shape[1], K = t.shape[2];
-  std::vector<float> out(t.v.size());
-  for (int64_t o = 0; o < O; ++o)
-    for (int64_t i = 0; i < I; ++i)
-      for (int64_t k = 0; k < K; ++k) out[(k * O + o) * I + i] = t.v[(o * I + i) * K + k];
-  return out;
-}
-
-ConvArgs lin(const float* x, int ldx, int rows, int K, const float* w, int N, const float* bias, float* y, int ldy) {
-  ConvArgs a;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = rows;
-  a.C_in = K;
-  a.w = w;
-  a.ldw = K;
-  a.taps = 1;
-  a.y = y;
-  a.ldy = ldy;
-  a.T_out = rows;
-  a.N = N;
-  a.bias = bias;
-  return a;
-}
-
-
-void run1(Ctx& c, const ConvArgs& a, hipStream_t s, double flops = -1.0) { launch_conv(c, a, false, s, flops); }
-void run2(Ctx& c, const ConvArgs& a, hipStream_t s, double flops = -1.0) { launch_conv(c, a, true, s, flops); }
 
 constexpr int HD = 768, HHEADS = 12, HFF = 3072, HCONV = 512;
 const int HK[7] = {10, 3, 3, 3, 3, 2, 2};
@@ -64,20 +22,20 @@ constexpr int POS_K = 128, POS_G = 16;
 void finalize_hubert(Ctx& c) {
   const int M = 1;
   // conv0 (C_in 1, k 10, s 5): [512][1][10] as is, the fused conv + GroupNorm + GELU kernel's [c][k] layout
-  c.alloc_weight("hb.conv0", getw(c, M, "feature_extractor.conv_layers.0.conv.weight", {HCONV, 1, HK[0]}).v);
+  c.alloc_weight("hb.conv0", host_weight(c, M, "feature_extractor.conv_layers.0.conv.weight", {HCONV, 1, HK[0]}).v);
   for (int i = 1; i < 7; ++i)
     c.alloc_weight("hb.conv" + std::to_string(i),
-                   pack_conv1d(getw(c, M, "feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight",
+                   pack_conv1d(host_weight(c, M, "feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight",
                                     {HCONV, HCONV, HK[i]})));
-  c.alloc_weight("hb.gn.g", getw(c, M, "feature_extractor.conv_layers.0.layer_norm.weight", {HCONV}).v);
-  c.alloc_weight("hb.gn.b", getw(c, M, "feature_extractor.conv_layers.0.layer_norm.bias", {HCONV}).v);
-  c.alloc_weight("hb.fp.ln.g", getw(c, M, "feature_projection.layer_norm.weight", {HCONV}).v);
-  c.alloc_weight("hb.fp.ln.b", getw(c, M, "feature_projection.layer_norm.bias", {HCONV}).v);
-  c.alloc_weight("hb.fp.w", getw(c, M, "feature_projection.projection.weight", {HD, HCONV}).v);
-  c.alloc_weight("hb.fp.b", getw(c, M, "feature_projection.projection.bias", {HD}).v);
+  c.alloc_weight("hb.gn.g", host_weight(c, M, "feature_extractor.conv_layers.0.layer_norm.weight", {HCONV}).v);
+  c.alloc_weight("hb.gn.b", host_weight(c, M, "feature_extractor.conv_layers.0.layer_norm.bias", {HCONV}).v);
+  c.alloc_weight("hb.fp.ln.g", host_weight(c, M, "feature_projection.layer_norm.weight", {HCONV}).v);
+  c.alloc_weight("hb.fp.ln.b", host_weight(c, M, "feature_projection.layer_norm.bias", {HCONV}).v);
+  c.alloc_weight("hb.fp.w", host_weight(c, M, "feature_projection.projection.weight", {HD, HCONV}).v);
+  c.alloc_weight("hb.fp.b", host_weight(c, M, "feature_projection.projection.bias", {HD}).v);
   {  // grouped positional conv: [768][48][128] -> [group][tap][48 out][48 in]
     const int cg = HD / POS_G;
-    auto& w = getw(c, M, "encoder.pos_conv_embed.conv.weight", {HD, cg, POS_K});
+    auto& w = host_weight(c, M, "encoder.pos_conv_embed.conv.weight", {HD, cg, POS_K});
     std::vector<float> v((size_t)POS_G * POS_K * cg * cg);
     for (int g = 0; g < POS_G; ++g)
       for (int t = 0; t < POS_K; ++t)
@@ -85,36 +43,36 @@ void finalize_hubert(Ctx& c) {
           for (int i = 0; i < cg; ++i)
             v[(((size_t)g * POS_K + t) * cg + o) * cg + i] = w.v[((size_t)(g * cg + o) * cg + i) * POS_K + t];
     c.alloc_weight("hb.pos.w", v);
-    c.alloc_weight("hb.pos.b", getw(c, M, "encoder.pos_conv_embed.conv.bias", {HD}).v);
+    c.alloc_weight("hb.pos.b", host_weight(c, M, "encoder.pos_conv_embed.conv.bias", {HD}).v);
   }
-  c.alloc_weight("hb.enc.ln.g", getw(c, M, "encoder.layer_norm.weight", {HD}).v);
-  c.alloc_weight("hb.enc.ln.b", getw(c, M, "encoder.layer_norm.bias", {HD}).v);
+  c.alloc_weight("hb.enc.ln.g", host_weight(c, M, "encoder.layer_norm.weight", {HD}).v);
+  c.alloc_weight("hb.enc.ln.b", host_weight(c, M, "encoder.layer_norm.bias", {HD}).v);
   for (int i = 0; i < 12; ++i) {
     const std::string p = "encoder.layers." + std::to_string(i);
     const std::string q = "hb." + std::to_string(i);
     std::vector<float> w, b;
     for (const char* n : {"q_proj", "k_proj", "v_proj"}) {
-      auto& tw = getw(c, M, p + ".attention." + n + ".weight", {HD, HD}).v;
-      auto& tb = getw(c, M, p + ".attention." + n + ".bias", {HD}).v;
+      auto& tw = host_weight(c, M, p + ".attention." + n + ".weight", {HD, HD}).v;
+      auto& tb = host_weight(c, M, p + ".attention." + n + ".bias", {HD}).v;
       w.insert(w.end(), tw.begin(), tw.end());
       b.insert(b.end(), tb.begin(), tb.end());
     }
     c.alloc_weight(q + ".qkv.w", w);
     c.alloc_weight(q + ".qkv.b", b);
-    c.alloc_weight(q + ".o.w", getw(c, M, p + ".attention.out_proj.weight", {HD, HD}).v);
-    c.alloc_weight(q + ".o.b", getw(c, M, p + ".attention.out_proj.bias", {HD}).v);
-    c.alloc_weight(q + ".ln1.g", getw(c, M, p + ".layer_norm.weight", {HD}).v);
-    c.alloc_weight(q + ".ln1.b", getw(c, M, p + ".layer_norm.bias", {HD}).v);
-    c.alloc_weight(q + ".ff1.w", getw(c, M, p + ".feed_forward.intermediate_dense.weight", {HFF, HD}).v);
-    c.alloc_weight(q + ".ff1.b", getw(c, M, p + ".feed_forward.intermediate_dense.bias", {HFF}).v);
-    c.alloc_weight(q + ".ff2.w", getw(c, M, p + ".feed_forward.output_dense.weight", {HD, HFF}).v);
-    c.alloc_weight(q + ".ff2.b", getw(c, M, p + ".feed_forward.output_dense.bias", {HD}).v);
-    c.alloc_weight(q + ".ln2.g", getw(c, M, p + ".final_layer_norm.weight", {HD}).v);
-    c.alloc_weight(q + ".ln2.b", getw(c, M, p + ".final_layer_norm.bias", {HD}).v);
+    c.alloc_weight(q + ".o.w", host_weight(c, M, p + ".attention.out_proj.weight", {HD, HD}).v);
+    c.alloc_weight(q + ".o.b", host_weight(c, M, p + ".attention.out_proj.bias", {HD}).v);
+    c.alloc_weight(q + ".ln1.g", host_weight(c, M, p + ".layer_norm.weight", {HD}).v);
+    c.alloc_weight(q + ".ln1.b", host_weight(c, M, p + ".layer_norm.bias", {HD}).v);
+    c.alloc_weight(q + ".ff1.w", host_weight(c, M, p + ".feed_forward.intermediate_dense.weight", {HFF, HD}).v);
+    c.alloc_weight(q + ".ff1.b", host_weight(c, M, p + ".feed_forward.intermediate_dense.bias", {HFF}).v);
+    c.alloc_weight(q + ".ff2.w", host_weight(c, M, p + ".feed_forward.output_dense.weight", {HD, HFF}).v);
+    c.alloc_weight(q + ".ff2.b", host_weight(c, M, p + ".feed_forward.output_dense.bias", {HD}).v);
+    c.alloc_weight(q + ".ln2.g", host_weight(c, M, p + ".final_layer_norm.weight", {HD}).v);
+    c.alloc_weight(q + ".ln2.b", host_weight(c, M, p + ".final_layer_norm.bias", {HD}).v);
   }
   if (c.host[M].count("final_proj.weight")) {
-    c.alloc_weight("hb.final_proj.w", getw(c, M, "final_proj.weight", {256, HD}).v);
-    c.alloc_weight("hb.final_proj.b", getw(c, M, "final_proj.bias", {256}).v);
+    c.alloc_weight("hb.final_proj.w", host_weight(c, M, "final_proj.weight", {256, HD}).v);
+    c.alloc_weight("hb.final_proj.b", host_weight(c, M, "final_proj.bias", {256}).v);
   }
 }
 
@@ -280,56 +238,18 @@ constexpr int NMEL = 128, NFFT = 1024, HOP = 160, NBIN = NFFT / 2 + 1, NCLS = 36
 // the streamed fp16 kernels (the three-plane LDS kernel + a split-K combine: 60 + 16 us at C2, r05i)
 constexpr int NBIN_P = 544;
 constexpr int LEVELS = 5, INTER = 4, NBLK = 4, C_BASE = 16, GRU_H = 256;
-
-// librosa.filters.mel(sr=16000, n_fft=1024, n_mels=128, fmin=30, fmax=8000, htk=True, norm='slaney')
-std::vector<float> mel_basis() {
-  const int n = NMEL + 2;
-  auto hz2mel = [](double f) { return 2595.0 * std::log10(1.0 + f / 700.0); };
-  auto mel2hz = [](double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); };
-  const double lo = hz2mel(30.0), hi = hz2mel(8000.0);
-  const double step = (hi - lo) / (n - 1);
-  std::vector<double> mel_f(n);
-  for (int i = 0; i < n; ++i) mel_f[i] = mel2hz(i == n - 1 ? hi : lo + i * step);
-  std::vector<float> w((size_t)NMEL * NBIN_P, 0.f);  // [mel][bin], rows of NBIN_P (bins >= NBIN zero)
-  for (int i = 0; i < NMEL; ++i) {
-    const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
-    const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-    for (int k = 0; k < NBIN; ++k) {
-      const double f = k * (16000.0 / NFFT);
-      const double lower = -(mel_f[i] - f) / fd0;
-      const double upper = (mel_f[i + 2] - f) / fd1;
-      const float tri = (float)std::max(0.0, std::min(lower, upper));
-      w[(size_t)i * NBIN_P + k] = (float)((double)tri * enorm);
-    }
-  }
-  return w;
-}
-
-// STFT as a conv over 32-sample rows: W[tap][n][c], sample k = 32*tap + c; n < 513 real, else imag.
-std::vector<float> stft_weights() {
-  std::vector<float> w((size_t)32 * 2 * NBIN * 32);
-  const double pi = 3.14159265358979323846;
-  for (int t = 0; t < 32; ++t)
-    for (int nn = 0; nn < 2 * NBIN; ++nn)
-      for (int cc = 0; cc < 32; ++cc) {
-        const int k = 32 * t + cc;
-        const double win = 0.5 - 0.5 * std::cos(2.0 * pi * k / NFFT);
-        const int f = nn < NBIN ? nn : nn - NBIN;
-        const double ang = 2.0 * pi * (double)((long long)k * f % NFFT) / NFFT;
-        const double v = nn < NBIN ? std::cos(ang) : -std::sin(ang);
-        w[((size_t)t * 2 * NBIN + nn) * 32 + cc] = (float)(win * v);
-      }
-  return w;
-}
+// MelSpectrogram (RMVPE.py:388-417): librosa's htk=True basis from 30 Hz to 8 kHz, plain |STFT|
+constexpr MelSpec MEL{16000, NFFT, HOP, NMEL, 30.0, 8000.0, true, 0.f};
+static_assert(MEL.nbin() == NBIN && MEL.ld() == NBIN_P, "the mel rows are NBIN_P floats");
 
 struct BN {
   std::vector<double> a, b;
 };
 BN bn_fold(Ctx& c, const std::string& p, int C) {
-  auto& g = getw(c, 2, p + ".weight", {C}).v;
-  auto& bb = getw(c, 2, p + ".bias", {C}).v;
-  auto& m = getw(c, 2, p + ".running_mean", {C}).v;
-  auto& v = getw(c, 2, p + ".running_var", {C}).v;
+  auto& g = host_weight(c, 2, p + ".weight", {C}).v;
+  auto& bb = host_weight(c, 2, p + ".bias", {C}).v;
+  auto& m = host_weight(c, 2, p + ".running_mean", {C}).v;
+  auto& v = host_weight(c, 2, p + ".running_var", {C}).v;
   BN r;
   r.a.resize(C);
   r.b.resize(C);
@@ -343,7 +263,7 @@ BN bn_fold(Ctx& c, const std::string& p, int C) {
 
 // Conv2d [O][I][3][3] + BN -> [9][O][I], bias [O]
 void conv_bn(Ctx& c, const std::string& wname, const std::string& bnname, int O, int I, const std::string& dst) {
-  auto& w = getw(c, 2, wname, {O, I, 3, 3}).v;
+  auto& w = host_weight(c, 2, wname, {O, I, 3, 3}).v;
   BN bn = bn_fold(c, bnname, O);
   std::vector<float> v((size_t)9 * O * I), bias(O);
   for (int o = 0; o < O; ++o) {
@@ -359,36 +279,22 @@ void block_weights(Ctx& c, const std::string& p, const std::string& q, int cin, 
   conv_bn(c, p + ".conv.0.weight", p + ".conv.1", cout, cin, q + ".c1");
   conv_bn(c, p + ".conv.3.weight", p + ".conv.4", cout, cout, q + ".c2");
   if (cin != cout) {
-    c.alloc_weight(q + ".sc.w", getw(c, 2, p + ".shortcut.weight", {cout, cin, 1, 1}).v);
-    c.alloc_weight(q + ".sc.b", getw(c, 2, p + ".shortcut.bias", {cout}).v);
+    c.alloc_weight(q + ".sc.w", host_weight(c, 2, p + ".shortcut.weight", {cout, cin, 1, 1}).v);
+    c.alloc_weight(q + ".sc.b", host_weight(c, 2, p + ".shortcut.bias", {cout}).v);
   }
 }
 
 ConvArgs c2d(const float* x, int ldx, int H, int W, int Cin, const float* w, int N, const float* bias, float* y,
              int ldy, int B = 1) {
-  ConvArgs a;
+  ConvArgs a = lin(x, ldx, H, Cin, w, N, bias, y, ldy);  // rows = image rows
   a.batch = B;  // B images of H x W pixels back to back
   a.x_bs = (long long)H * W * ldx;
   a.y_bs = (long long)H * W * ldy;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = H;
-  a.W_in = W;
-  a.C_in = Cin;
-  a.w = w;
-  a.ldw = Cin;
+  a.W_in = a.W_out = W;
   a.w_ts = (long long)N * Cin;
   a.taps = 9;
-  a.KH = 3;
-  a.KW = 3;
-  a.padh = 1;
-  a.padw = 1;
-  a.y = y;
-  a.ldy = ldy;
-  a.T_out = H;
-  a.W_out = W;
-  a.N = N;
-  a.bias = bias;
+  a.KH = a.KW = 3;
+  a.padh = a.padw = 1;
   return a;
 }
 
@@ -421,8 +327,8 @@ void conv_block(Ctx& c, const std::string& q, const float* x, int ldx, int H, in
 }  // namespace
 
 void finalize_rmvpe(Ctx& c) {
-  c.alloc_weight("rm.stft", stft_weights());
-  c.alloc_weight("rm.mel", mel_basis());
+  c.alloc_weight("rm.stft", stft_weights(MEL.win));
+  c.alloc_weight("rm.mel", mel_basis(MEL));
   {
     BN bn = bn_fold(c, "unet.encoder.bn", 1);
     c.host[2]["__bn0__"] = HostTensor{{(float)bn.a[0], (float)bn.b[0]}, {2}};
@@ -449,7 +355,7 @@ void finalize_rmvpe(Ctx& c) {
     const std::string p = "unet.decoder.layers." + std::to_string(i);
     const std::string q = "rm.dec" + std::to_string(i);
     {  // ConvTranspose2d 3x3 s2 p1 op1 + BN as a 2x2-tap phase conv with 4*co virtual outputs
-      auto& w = getw(c, 2, p + ".conv1.0.weight", {C, co, 3, 3}).v;
+      auto& w = host_weight(c, 2, p + ".conv1.0.weight", {C, co, 3, 3}).v;
       BN bn = bn_fold(c, p + ".conv1.1", co);
       std::vector<float> v((size_t)4 * 4 * co * C, 0.f), bias((size_t)4 * co);
       const int kmap[2][2] = {{1, -1}, {2, 0}};  // [phase][input offset] -> kernel index
@@ -477,33 +383,29 @@ void finalize_rmvpe(Ctx& c) {
     C = co;
   }
   c.alloc_weight("rm.cnn.w", [&] {
-    auto& w = getw(c, 2, "cnn.weight", {3, C_BASE, 3, 3}).v;
+    auto& w = host_weight(c, 2, "cnn.weight", {3, C_BASE, 3, 3}).v;
     std::vector<float> v((size_t)9 * 3 * C_BASE);
     for (int o = 0; o < 3; ++o)
       for (int i = 0; i < C_BASE; ++i)
         for (int t = 0; t < 9; ++t) v[((size_t)t * 3 + o) * C_BASE + i] = w[((size_t)o * C_BASE + i) * 9 + t];
     return v;
   }());
-  c.alloc_weight("rm.cnn.b", getw(c, 2, "cnn.bias", {3}).v);
+  c.alloc_weight("rm.cnn.b", host_weight(c, 2, "cnn.bias", {3}).v);
   {
     const int nin = 3 * NMEL;
-    auto& wf = getw(c, 2, "fc.0.gru.weight_ih_l0", {3 * GRU_H, nin}).v;
-    auto& wb = getw(c, 2, "fc.0.gru.weight_ih_l0_reverse", {3 * GRU_H, nin}).v;
-    std::vector<float> w(wf);
-    w.insert(w.end(), wb.begin(), wb.end());
-    c.alloc_weight("rm.gru.wih", w);
-    auto& bf = getw(c, 2, "fc.0.gru.bias_ih_l0", {3 * GRU_H}).v;
-    auto& bb = getw(c, 2, "fc.0.gru.bias_ih_l0_reverse", {3 * GRU_H}).v;
-    std::vector<float> b(bf);
-    b.insert(b.end(), bb.begin(), bb.end());
-    c.alloc_weight("rm.gru.bih", b);
-    c.alloc_weight("rm.gru.whh_f", getw(c, 2, "fc.0.gru.weight_hh_l0", {3 * GRU_H, GRU_H}).v);
-    c.alloc_weight("rm.gru.whh_b", getw(c, 2, "fc.0.gru.weight_hh_l0_reverse", {3 * GRU_H, GRU_H}).v);
-    c.alloc_weight("rm.gru.bhh_f", getw(c, 2, "fc.0.gru.bias_hh_l0", {3 * GRU_H}).v);
-    c.alloc_weight("rm.gru.bhh_b", getw(c, 2, "fc.0.gru.bias_hh_l0_reverse", {3 * GRU_H}).v);
+    auto& wf = host_weight(c, 2, "fc.0.gru.weight_ih_l0", {3 * GRU_H, nin}).v;
+    auto& wb = host_weight(c, 2, "fc.0.gru.weight_ih_l0_reverse", {3 * GRU_H, nin}).v;
+    c.alloc_weight("rm.gru.wih", cat({&wf, &wb}));
+    auto& bf = host_weight(c, 2, "fc.0.gru.bias_ih_l0", {3 * GRU_H}).v;
+    auto& bb = host_weight(c, 2, "fc.0.gru.bias_ih_l0_reverse", {3 * GRU_H}).v;
+    c.alloc_weight("rm.gru.bih", cat({&bf, &bb}));
+    c.alloc_weight("rm.gru.whh_f", host_weight(c, 2, "fc.0.gru.weight_hh_l0", {3 * GRU_H, GRU_H}).v);
+    c.alloc_weight("rm.gru.whh_b", host_weight(c, 2, "fc.0.gru.weight_hh_l0_reverse", {3 * GRU_H, GRU_H}).v);
+    c.alloc_weight("rm.gru.bhh_f", host_weight(c, 2, "fc.0.gru.bias_hh_l0", {3 * GRU_H}).v);
+    c.alloc_weight("rm.gru.bhh_b", host_weight(c, 2, "fc.0.gru.bias_hh_l0_reverse", {3 * GRU_H}).v);
   }
-  c.alloc_weight("rm.fc.w", getw(c, 2, "fc.1.weight", {NCLS, 2 * GRU_H}).v);
-  c.alloc_weight("rm.fc.b", getw(c, 2, "fc.1.bias", {NCLS}).v);
+  c.alloc_weight("rm.fc.w", host_weight(c, 2, "fc.1.weight", {NCLS, 2 * GRU_H}).v);
+  c.alloc_weight("rm.fc.b", host_weight(c, 2, "fc.1.bias", {NCLS}).v);
 }
 
 // E2E on B mel chunk images [B][Fc][128] (already padded to a multiple of 32 frames) -> sal [B][Fc][360].
@@ -646,33 +548,9 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
   if (n < NFFT / 2 + 1) throw Error(RVCX_E_SHAPE, "rmvpe: input shorter than 513 samples");
   const int F = (int)(1 + n / HOP);
   if (F > cap) throw Error(RVCX_E_CAPACITY, "rmvpe: output needs " + std::to_string(F) + " frames");
-  // MelSpectrogram (RMVPE.py:388-417): reflect pad 512, |STFT| (Hann 1024, hop 160), mel, log(clamp(1e-5))
-  const int64_t np = n + NFFT;
-  const int64_t rows = (np + 31) / 32;
-  float* xp = c.buf<float>("rm.xp", (size_t)B * rows * 32, s);
-  check(reflect_pad_1d(audio, (int)n, NFFT / 2, NFFT / 2, xp, s, B, lda, rows * 32), "reflect_pad");
-  float* spec = c.buf<float>("rm.spec", (size_t)B * F * 2 * NBIN, s);
-  {
-    ConvArgs a = lin(xp, 32, (int)rows, 32, c.W("rm.stft"), 2 * NBIN, nullptr, spec, 2 * NBIN);
-    a.taps = 32;
-    a.stride = 5;
-    a.w_ts = (long long)2 * NBIN * 32;
-    a.T_out = F;
-    a.batch = B;
-    a.x_bs = rows * 32;
-    a.y_bs = (long long)F * 2 * NBIN;
-    run1(c, a, s, 0.0);
-  }
-  const int ldm = NBIN_P;
-  float* mag = c.buf<float>("rm.mag", (size_t)B * F * ldm, s);
-  check(stft_magnitude(spec, B * F, NBIN, mag, ldm, s), "stft_mag");
+  // MelSpectrogram (RMVPE.py:388-417): centre reflect pad 512, F frames, the mel GEMM over all B F rows at once
   float* mel = c.buf<float>("rm.melout", (size_t)B * F * NMEL, s);
-  {
-    ConvArgs a = lin(mag, ldm, B * F, NBIN_P, c.W("rm.mel"), NMEL, nullptr, mel, NMEL);
-    a.act = ACT_LOGCLAMP;
-    a.slope = 1e-5f;
-    run1(c, a, s);
-  }
+  mel_forward(c, MEL, "rm.", audio, n, lda, B, MelFrames{NFFT / 2, NFFT / 2, false, F, F, false}, mel, s);
   // mel2hidden (RMVPE.py:445-482): reflect-pad frames to a multiple of 32, E2E per 32000-frame chunk
   const int Fp = 32 * ((F - 1) / 32 + 1);
   float* img = c.buf<float>("rm.img", (size_t)B * Fp * NMEL, s);

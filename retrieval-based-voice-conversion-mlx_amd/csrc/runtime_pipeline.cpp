@@ -242,19 +242,61 @@ static void check_f0_method(const Ctx& c, const rvcx_pipeline_opts& o) {
       throw Error(RVCX_E_SHAPE, "pipeline: the FCPE model must run at 16 kHz with hop_size 160");
   }
 }
-static float fcpe_thr(const rvcx_pipeline_opts& o) { return o.fcpe_threshold > 0 ? o.fcpe_threshold : 0.006f; }
 
-int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
-                            const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
-                            double* f0_out, hipStream_t s) {
+// the option checks of both pipeline forms, for utterances of n samples
+static void check_pipeline_opts(const Ctx& c, const rvcx_pipeline_opts& o, int64_t n) {
   if (c.hp_order == 0) throw Error(RVCX_E_STATE, "pipeline: high-pass filter not configured");
   if (o.t_pad < 0 || o.t_pad_tgt < 0 || o.t_pad >= n) throw Error(RVCX_E_INVALID, "pipeline: bad t_pad");
   check_f0_method(c, o);
   if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "pipeline: index_rate > 0 but no feature index loaded");
-  if (o.index_rate > 0 && c.ivf->view.d != c.scfg.emb_dim)
-    throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension does not match the model's feature width");
   if (o.version != 0 && o.version != hubert_version_for(c))
     throw Error(RVCX_E_INVALID, "pipeline: version does not match the synthesizer's embedding width");
+}
+
+// One row's f0 [F] over its padded input of m samples for the methods that run per row. CREPE: PitchExtractor.extract
+// (rvc_mlx/lib/mlx/pitch_extractors.py:155-156) with PipelineMLX's f0_min 50 / f0_max 1100 and CREPE.get_f0's threshold
+// 0.1; f0_method 2: rvc/'s CREPE.get_f0 (pipeline.py:223-234), viterbi decode without its dither. FCPE (f0_method 3):
+// FCPE.get_f0 (rvc/lib/predictors/f0.py:71-89), the raw local_argmax track. f0f names CREPE's fp32 work buffer.
+static void f0_row(Ctx& c, const rvcx_pipeline_opts& o, const float* audio, int64_t m, double* f0, int64_t F,
+                   const char* f0f, hipStream_t s) {
+  if (o.f0_method == 3) {
+    fcpe_forward(c, audio, m, o.fcpe_threshold > 0 ? o.fcpe_threshold : 0.006f, 0, 0, 0, f0, nullptr, F, s);
+  } else {
+    crepe_forward(c, audio, m, 50.0, 1100.0, 0.1f, c.buf<float>(f0f, (size_t)F, s), f0, nullptr, nullptr, s,
+                  o.f0_method == 2 ? 1 : 0);
+  }
+}
+
+// get_f0's adjustments (pipeline.py:248-291) of f0 [B][F] in place, then the coarse / fine pitch per row: autotune, or
+// the proposed-pitch key of each row (one device -> host copy and sync), then f0_post with the row's shift
+static void pitch_from_f0(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B, int64_t F, int32_t* pitch,
+                          float* pitchf, double* f0_out, hipStream_t s) {
+  std::vector<double> shift(B, o.pitch);
+  if (o.f0_autotune) {
+    check(f0_autotune(f0, (int)(B * F), o.f0_autotune_strength, o.mlx_semantics ? 1 : 0, s), "f0_autotune");
+    if (!o.mlx_semantics) std::fill(shift.begin(), shift.end(), 0.0);  // rvc/: autotune replaces the shift (:248-279)
+  } else if (o.proposed_pitch) {
+    std::vector<double> h((size_t)B * F);
+    RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    RVCX_HIP(hipStreamSynchronize(s));
+    c.check_device_status();
+    for (int b = 0; b < B; ++b) {
+      std::vector<double> one(h.begin() + (size_t)b * F, h.begin() + (size_t)(b + 1) * F);
+      shift[b] = o.pitch + proposed_key(one, o.proposed_pitch_threshold);
+    }
+  }
+  for (int b = 0; b < B; ++b)
+    check(f0_post(f0 + (size_t)b * F, (int)F, std::pow(2.0, shift[b] / 12.0), pitch + (size_t)b * F,
+                  pitchf + (size_t)b * F, f0_out ? f0_out + (size_t)b * F : nullptr, s),
+          "f0_post");
+}
+
+int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
+                            const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
+                            double* f0_out, hipStream_t s) {
+  check_pipeline_opts(c, o, n);
+  if (o.index_rate > 0 && c.ivf->view.d != c.scfg.emb_dim)
+    throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension does not match the model's feature width");
   const int64_t W = 160;  // Pipeline.window
   const int64_t m = n + 2 * o.t_pad;
   // 1. zero-phase high-pass, reflect pad t_pad (pipeline.py:439, :459); fp64 copy kept for the split
@@ -375,24 +417,15 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
   if (guided) {
   double* f0 = c.buf<double>("pl.f0", (size_t)F, s);
   if (o.f0_method >= 1) {
-    // CREPE (PitchExtractor.extract, rvc_mlx/lib/mlx/pitch_extractors.py:155-156, with PipelineMLX's f0_min 50 /
-    // f0_max 1100 and CREPE.get_f0's threshold 0.1; f0_method 2: rvc/'s CREPE.get_f0, pipeline.py:223-234, viterbi
-    // decode without its dither): no BiGRU, so HuBERT's remaining layers go out first and overlap the CREPE convs on
-    // the aux stream
+    // CREPE / FCPE over the whole padded input: no BiGRU, so HuBERT's remaining layers go out first and overlap the
+    // pitch network's convs on the aux stream
     if (c.before_gru) {
       auto rest = std::move(c.before_gru);
       c.before_gru = nullptr;
       gate_here(s);
       rest(s);
     }
-    if (o.f0_method == 3) {
-      // FCPE.get_f0 (rvc/lib/predictors/f0.py:71-89; pipeline.py's "fcpe" branch): the raw local_argmax track over
-      // the whole padded input, F = 1 + m / 160 frames
-      fcpe_forward(c, pad32, m, fcpe_thr(o), 0, 0, 0, f0, nullptr, F, s);
-    } else {
-      float* f0f = c.buf<float>("pl.f0f", (size_t)F, s);
-      crepe_forward(c, pad32, m, 50.0, 1100.0, 0.1f, f0f, f0, nullptr, nullptr, s, o.f0_method == 2 ? 1 : 0);
-    }
+    f0_row(c, o, pad32, m, f0, F, "pl.f0f", s);
   } else {
     rmvpe_forward(c, pad32, m, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, nullptr, s);
   }
@@ -402,20 +435,9 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
     gate_here(s);
     rest(s);
   }
-  double shift_semitones = o.pitch;
-  if (o.f0_autotune) {
-    check(f0_autotune(f0, (int)F, o.f0_autotune_strength, o.mlx_semantics ? 1 : 0, s), "f0_autotune");
-    if (!o.mlx_semantics) shift_semitones = 0.0;  // rvc/: autotune replaces the shift (pipeline.py:248-279)
-  } else if (o.proposed_pitch) {
-    std::vector<double> h(F);
-    RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * F, hipMemcpyDeviceToHost, s));
-    RVCX_HIP(hipStreamSynchronize(s));
-    c.check_device_status();
-    shift_semitones = o.pitch + proposed_key(h, o.proposed_pitch_threshold);
-  }
   pitch = c.buf<int32_t>("pl.pitch", (size_t)F, s);
   pitchf = c.buf<float>("pl.pitchf", (size_t)F, s);
-  check(f0_post(f0, (int)F, std::pow(2.0, shift_semitones / 12.0), pitch, pitchf, f0_out, s), "f0_post");
+  pitch_from_f0(c, o, f0, 1, F, pitch, pitchf, f0_out, s);
   } else {
     auto rest = std::move(c.before_gru);
     c.before_gru = nullptr;
@@ -499,14 +521,9 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
                                const int32_t* sids, const float* eps_z, const float* eps_src, uint64_t seed,
                                float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s) {
   if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
-  if (c.hp_order == 0) throw Error(RVCX_E_STATE, "pipeline: high-pass filter not configured");
-  if (o.t_pad < 0 || o.t_pad_tgt < 0 || o.t_pad >= n) throw Error(RVCX_E_INVALID, "pipeline: bad t_pad");
-  check_f0_method(c, o);
+  check_pipeline_opts(c, o, n);
   if (o.t_max > 0 && n + 160 > o.t_max)
     throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
-  if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "pipeline: index_rate > 0 but no feature index loaded");
-  if (o.version != 0 && o.version != hubert_version_for(c))
-    throw Error(RVCX_E_INVALID, "pipeline: version does not match the synthesizer's embedding width");
   for (int b = 0; b < B; ++b)
     if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
   const int64_t W = 160;
@@ -529,37 +546,14 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   int32_t* pitch = nullptr;
   float* pitchf = nullptr;
   if (guided) {
-  if (o.f0_method == 3) {  // FCPE per utterance, as CREPE below
-    for (int b = 0; b < B; ++b)
-      fcpe_forward(c, pad32 + (size_t)b * ldm, m, fcpe_thr(o), 0, 0, 0, f0 + (size_t)b * F, nullptr, F, s);
-  } else if (o.f0_method >= 1) {  // CREPE per utterance (frames of all rows would not batch any better: B x F frames)
-    float* f0f = c.buf<float>("pb.f0f", (size_t)F, s);
-    for (int b = 0; b < B; ++b)
-      crepe_forward(c, pad32 + (size_t)b * ldm, m, 50.0, 1100.0, 0.1f, f0f, f0 + (size_t)b * F, nullptr, nullptr, s,
-                    o.f0_method == 2 ? 1 : 0);
+  if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
+    for (int b = 0; b < B; ++b) f0_row(c, o, pad32 + (size_t)b * ldm, m, f0 + (size_t)b * F, F, "pb.f0f", s);
   } else {
     rmvpe_forward_b(c, pad32, m, ldm, B, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, hidden_out, s);
   }
-  std::vector<double> shift(B, o.pitch);
-  if (o.f0_autotune) {
-    check(f0_autotune(f0, (int)(B * F), o.f0_autotune_strength, o.mlx_semantics ? 1 : 0, s), "f0_autotune");
-    if (!o.mlx_semantics) std::fill(shift.begin(), shift.end(), 0.0);
-  } else if (o.proposed_pitch) {
-    std::vector<double> h((size_t)B * F);
-    RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
-    RVCX_HIP(hipStreamSynchronize(s));
-    c.check_device_status();
-    for (int b = 0; b < B; ++b) {
-      std::vector<double> one(h.begin() + (size_t)b * F, h.begin() + (size_t)(b + 1) * F);
-      shift[b] = o.pitch + proposed_key(one, o.proposed_pitch_threshold);
-    }
-  }
   pitch = c.buf<int32_t>("pb.pitch", (size_t)B * F, s);
   pitchf = c.buf<float>("pb.pitchf", (size_t)B * F, s);
-  for (int b = 0; b < B; ++b)
-    check(f0_post(f0 + (size_t)b * F, (int)F, std::pow(2.0, shift[b] / 12.0), pitch + (size_t)b * F,
-                  pitchf + (size_t)b * F, f0_out ? f0_out + (size_t)b * F : nullptr, s),
-          "f0_post");
+  pitch_from_f0(c, o, f0, B, F, pitch, pitchf, f0_out, s);
   } else if (f0_out) {
     RVCX_HIP(hipMemsetAsync(f0_out, 0, sizeof(double) * (size_t)B * F, s));
   }

@@ -7,7 +7,7 @@
 // upsample+concat and AdaIN kernels; source_harm.hip the source.
 #include <cmath>
 
-#include "runtime.h"
+#include "model_build.h"
 
 namespace rvcx {
 
@@ -19,105 +19,55 @@ constexpr float RG_SLOPE = 0.2f;
 constexpr int RG_K[3] = {3, 7, 11};
 constexpr int RG_D[3] = {1, 3, 5};
 
-const HostTensor& rg_get(Ctx& c, const std::string& n, std::vector<int64_t> shape) {
-  auto it = c.host[0].find(n);
-  if (it == c.host[0].end()) throw Error(RVCX_E_STATE, "missing weight: " + n);
-  if (it->second.shape != shape) throw Error(RVCX_E_SHAPE, "weight " + n + " has an unexpected shape");
-  return it->second;
-}
-
-std::vector<float> rg_pack(const HostTensor& t) {  // [O][I][K] -> [K][O][I]
-  const int64_t O = t.shape[0], I = t.shape[1], K = t.shape[2];
-  std::vector<float> out(t.v.size());
-  for (int64_t o = 0; o < O; ++o)
-    for (int64_t i = 0; i < I; ++i)
-      for (int64_t k = 0; k < K; ++k) out[(k * O + o) * I + i] = t.v[(o * I + i) * K + k];
-  return out;
-}
-
-// modified Bessel function of the first kind, order 0 (series; the kernel is computed once at finalize)
-double bessel_i0(double x) {
-  double sum = 1.0, term = 1.0;
-  const double q = 0.25 * x * x;
-  for (int k = 1; k < 200; ++k) {
-    term *= q / ((double)k * k);
-    sum += term;
-    if (term < 1e-17 * sum) break;
-  }
-  return sum;
-}
-
-// torchaudio.functional._get_sinc_resample_kernel(orig, 1, ..., lowpass_filter_width 64, rolloff 0.9475937167399596,
-// "sinc_interp_kaiser", beta 14.769656459379492) in float32 as the waveform dtype requests (refinegan.py:410-419)
-std::vector<float> kaiser_kernel(int orig, int& width) {
-  const double lw = 64.0, rolloff = 0.9475937167399596, beta = 14.769656459379492;
-  const double base = 1.0 * rolloff;
-  width = (int)std::ceil(lw * orig / base);
-  const int K = 2 * width + orig;
-  std::vector<float> k(K);
-  const float bf = (float)base, pi = (float)M_PI, fbeta = (float)beta;
-  const float i0b = (float)bessel_i0((double)fbeta);
-  for (int j = 0; j < K; ++j) {
-    float t = (float)(j - width) / (float)orig;  // idx (float32 arange / orig) + 0 / new
-    t = t * bf;
-    t = std::fmin(std::fmax(t, -(float)lw), (float)lw);
-    const float r = t / (float)lw;
-    const float win = (float)bessel_i0((double)(fbeta * std::sqrt(1.f - r * r))) / i0b;
-    t = t * pi;
-    const float sc = (float)(base / orig);
-    const float sinc = t == 0.f ? 1.f : std::sin(t) / t;
-    k[j] = sinc * (win * sc);
-  }
-  return k;
-}
-
 }  // namespace
 
 void finalize_refinegan(Ctx& c) {
   const SynthCfg& g = c.scfg;
   const int nu = (int)g.ups.size();
-  c.alloc_weight("rg.merge", rg_get(c, "dec.m_source.merge.0.weight", {1, 1}).v);
-  c.alloc_weight("rg.pre.w", rg_pack(rg_get(c, "dec.pre_conv.weight", {RG_START, 1, 7})));
-  c.alloc_weight("rg.pre.b", rg_get(c, "dec.pre_conv.bias", {RG_START}).v);
+  c.alloc_weight("rg.merge", host_weight(c, 0, "dec.m_source.merge.0.weight", {1, 1}).v);
+  c.alloc_weight("rg.pre.w", pack_conv1d(host_weight(c, 0, "dec.pre_conv.weight", {RG_START, 1, 7})));
+  c.alloc_weight("rg.pre.b", host_weight(c, 0, "dec.pre_conv.bias", {RG_START}).v);
   int ch = RG_START;
   for (int i = 0; i < nu; ++i) {
     const std::string n = "dec.downsample_blocks." + std::to_string(i);
-    c.alloc_weight("rg.down" + std::to_string(i) + ".w", rg_pack(rg_get(c, n + ".weight", {2 * ch, ch, 7})));
-    c.alloc_weight("rg.down" + std::to_string(i) + ".b", rg_get(c, n + ".bias", {2 * ch}).v);
-    int width = 0;
-    const int r = g.ups[nu - 1 - i];
-    c.alloc_weight("rg.rs" + std::to_string(i), kaiser_kernel(r, width));
-    c.host[0]["__rg_rs_width" + std::to_string(i) + "__"] = HostTensor{{(float)width}, {1}};
+    const std::string q = "rg.down" + std::to_string(i);
+    c.alloc_weight(q + ".w", pack_conv1d(host_weight(c, 0, n + ".weight", {2 * ch, ch, 7})));
+    c.alloc_weight(q + ".b", host_weight(c, 0, n + ".bias", {2 * ch}).v);
+    // torchaudio's resample(orig = r, new = 1, lowpass_filter_width 64, "sinc_interp_kaiser") (refinegan.py:410-419)
+    const SincKernel rs =
+        sinc_resample_kernel(g.ups[nu - 1 - i], 1, 64.0, 0.9475937167399596, SINC_KAISER, 14.769656459379492);
+    c.alloc_weight("rg.rs" + std::to_string(i), rs.k);
+    c.host[0]["__rg_rs_width" + std::to_string(i) + "__"] = HostTensor{{(float)rs.width}, {1}};
     ch *= 2;
   }
   if (ch != RG_C0 / 2) throw Error(RVCX_E_SHAPE, "RefineGAN: the source branch must end at 256 channels");
-  c.alloc_weight("rg.mel.w", rg_pack(rg_get(c, "dec.mel_conv.weight", {RG_C0 / 2, g.I, 7})));
-  c.alloc_weight("rg.mel.b", rg_get(c, "dec.mel_conv.bias", {RG_C0 / 2}).v);
-  c.alloc_weight("rg.cond.w", rg_get(c, "dec.cond.weight", {RG_C0 / 2, g.gin, 1}).v);
-  c.alloc_weight("rg.cond.b", rg_get(c, "dec.cond.bias", {RG_C0 / 2}).v);
+  c.alloc_weight("rg.mel.w", pack_conv1d(host_weight(c, 0, "dec.mel_conv.weight", {RG_C0 / 2, g.I, 7})));
+  c.alloc_weight("rg.mel.b", host_weight(c, 0, "dec.mel_conv.bias", {RG_C0 / 2}).v);
+  c.alloc_weight("rg.cond.w", host_weight(c, 0, "dec.cond.weight", {RG_C0 / 2, g.gin, 1}).v);
+  c.alloc_weight("rg.cond.b", host_weight(c, 0, "dec.cond.bias", {RG_C0 / 2}).v);
   int C = RG_C0;
   for (int i = 0; i < nu; ++i) {
     const int out = C / 2, cin = C + C / 4;
     const std::string p = "dec.upsample_conv_blocks." + std::to_string(i);
     const std::string q = "rg.up" + std::to_string(i);
-    c.alloc_weight(q + ".in.w", rg_pack(rg_get(c, p + ".input_conv.weight", {out, cin, 7})));
-    c.alloc_weight(q + ".in.b", rg_get(c, p + ".input_conv.bias", {out}).v);
+    c.alloc_weight(q + ".in.w", pack_conv1d(host_weight(c, 0, p + ".input_conv.weight", {out, cin, 7})));
+    c.alloc_weight(q + ".in.b", host_weight(c, 0, p + ".input_conv.bias", {out}).v);
     for (int j = 0; j < 3; ++j) {
       const std::string b = p + ".blocks." + std::to_string(j);
       const std::string d = q + ".b" + std::to_string(j);
-      c.alloc_weight(d + ".ain", rg_get(c, b + ".0.weight", {out}).v);
-      c.alloc_weight(d + ".aout", rg_get(c, b + ".2.weight", {out}).v);
+      c.alloc_weight(d + ".ain", host_weight(c, 0, b + ".0.weight", {out}).v);
+      c.alloc_weight(d + ".aout", host_weight(c, 0, b + ".2.weight", {out}).v);
       for (int m = 0; m < 3; ++m)
         for (int v = 1; v <= 2; ++v) {
           const std::string n = b + ".1.convs" + std::to_string(v) + "." + std::to_string(m);
           const std::string e = d + ".c" + std::to_string(v) + "." + std::to_string(m);
-          c.alloc_weight(e + ".w", rg_pack(rg_get(c, n + ".weight", {out, out, RG_K[j]})));
-          c.alloc_weight(e + ".b", rg_get(c, n + ".bias", {out}).v);
+          c.alloc_weight(e + ".w", pack_conv1d(host_weight(c, 0, n + ".weight", {out, out, RG_K[j]})));
+          c.alloc_weight(e + ".b", host_weight(c, 0, n + ".bias", {out}).v);
         }
     }
     C = out;
   }
-  c.alloc_weight("rg.post.w", rg_get(c, "dec.conv_post.weight", {1, C, 7}).v);
+  c.alloc_weight("rg.post.w", host_weight(c, 0, "dec.conv_post.weight", {1, C, 7}).v);
 }
 
 long long SynthCfg::src_noise_total(int B, long long T) const {
@@ -139,26 +89,7 @@ long long refinegan_noise_floats(const SynthCfg& g, int B, long long T) {
 
 static ConvArgs rg_conv(const float* x, int ldx, int Tin, int Cin, const float* w, int N, int taps, int pad,
                         const float* bias, float* y, int ldy, int Tout, int B, int dil = 1) {
-  ConvArgs a;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = Tin;
-  a.C_in = Cin;
-  a.x_bs = (long long)Tin * ldx;
-  a.w = w;
-  a.ldw = Cin;
-  a.w_ts = (long long)N * Cin;
-  a.taps = taps;
-  a.dil = dil;
-  a.pad = pad;
-  a.y = y;
-  a.ldy = ldy;
-  a.y_bs = (long long)Tout * ldy;
-  a.T_out = Tout;
-  a.N = N;
-  a.bias = bias;
-  a.batch = B;
-  return a;
+  return conv1d(x, ldx, Tin, Cin, w, N, taps, dil, pad, bias, y, ldy, Tout, B);
 }
 
 void refinegan_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, const float* f0, const float* g,

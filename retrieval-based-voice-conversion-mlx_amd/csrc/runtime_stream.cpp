@@ -20,54 +20,16 @@
 #include <cmath>
 #include <cstring>
 
-#include "runtime.h"
+#include "model_build.h"
 
 namespace rvcx {
 
 namespace {
 
-// torchaudio.functional.functional._get_sinc_resample_kernel (sinc_interp_hann, width 6, rolloff 0.99),
-// evaluated in float32 like Resample(..., dtype=torch.float32) (core.py:99-108).
-struct SincKernel {
-  int orig = 1, nw = 1, width = 0, K = 0;
-  std::vector<float> k;  // [nw][K]
-};
-
+// torchaudio's Resample(..., dtype=torch.float32) with its defaults (sinc_interp_hann, width 6, rolloff 0.99;
+// core.py:99-108)
 SincKernel sinc_kernel(int orig_freq, int new_freq) {
-  auto gcd = [](int a, int b) {
-    while (b) {
-      const int t = a % b;
-      a = b;
-      b = t;
-    }
-    return a;
-  };
-  const int g = gcd(orig_freq, new_freq);
-  SincKernel r;
-  r.orig = orig_freq / g;
-  r.nw = new_freq / g;
-  const float lpw = 6.0f;
-  const double base_d = (double)std::min(r.orig, r.nw) * 0.99;
-  r.width = (int)std::ceil(6.0 * r.orig / base_d);
-  r.K = 2 * r.width + r.orig;
-  r.k.resize((size_t)r.nw * r.K);
-  const float base = (float)base_d;
-  const float pi = (float)M_PI;
-  for (int p = 0; p < r.nw; ++p) {
-    for (int i = 0; i < r.K; ++i) {
-      const float idx = (float)(i - r.width) / (float)r.orig;
-      float t = (-(float)p) / (float)r.nw + idx;
-      t = t * base;
-      t = std::min(std::max(t, -lpw), lpw);
-      const float c = std::cos(t * pi / lpw / 2.0f);
-      const float window = c * c;
-      t = t * pi;
-      const float scale = (float)(base_d / r.orig);
-      const float kv = t == 0.0f ? 1.0f : std::sin(t) / t;
-      r.k[(size_t)p * r.K + i] = kv * (window * scale);
-    }
-  }
-  return r;
+  return sinc_resample_kernel(orig_freq, new_freq, 6.0, 0.99, SINC_HANN, 0.0);
 }
 
 // One hop's per-row plan as it lies in device memory (every array sized for the group's B slots, the first B_act

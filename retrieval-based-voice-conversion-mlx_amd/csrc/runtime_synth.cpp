@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "runtime.h"
+#include "model_build.h"
 
 namespace rvcx {
 
@@ -20,132 +20,7 @@ uint64_t splitmix(uint64_t x) {
   return x ^ (x >> 31);
 }
 
-const HostTensor& get(Ctx& c, int model, const std::string& n, std::vector<int64_t> shape) {
-  auto it = c.host[model].find(n);
-  if (it == c.host[model].end()) throw Error(RVCX_E_STATE, "missing weight: " + n);
-  if (it->second.shape != shape) {
-    std::string got, want;
-    for (auto s : it->second.shape) got += std::to_string(s) + ",";
-    for (auto s : shape) want += std::to_string(s) + ",";
-    throw Error(RVCX_E_SHAPE, "weight " + n + " has shape (" + got + ") expected (" + want + ")");
-  }
-  return it->second;
-}
-
-// torch Conv1d weight [O][I][K] -> [K][O][I]
-std::vector<float> pack_conv1d(const HostTensor& t) {
-  const int64_t O = t.shape[0], I = t.shape[1], K = t.shape[2];
-  std::vector<float> out(t.v.size());
-  for (int64_t o = 0; o < O; ++o)
-    for (int64_t i = 0; i < I; ++i)
-      for (int64_t k = 0; k < K; ++k) out[(k * O + o) * I + i] = t.v[(o * I + i) * K + k];
-  return out;
-}
-
-std::vector<float> cat(std::initializer_list<const std::vector<float>*> parts) {
-  std::vector<float> out;
-  for (auto* p : parts) out.insert(out.end(), p->begin(), p->end());
-  return out;
-}
-
-ConvArgs lin(const float* x, int ldx, int rows, int K, const float* w, int N, const float* bias, float* y, int ldy) {
-  ConvArgs a;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = rows;
-  a.C_in = K;
-  a.w = w;
-  a.ldw = K;
-  a.taps = 1;
-  a.y = y;
-  a.ldy = ldy;
-  a.T_out = rows;
-  a.N = N;
-  a.bias = bias;
-  return a;
-}
-
-// 1-D conv over B independent sequences of T rows ([B][T][ld]); weights packed [taps][N][Cin].
-ConvArgs conv(const float* x, int ldx, int Tin, int Cin, const float* w, int N, int taps, int dil, int pad,
-              const float* bias, float* y, int ldy, int Tout, int B) {
-  ConvArgs a;
-  a.x = x;
-  a.ldx = ldx;
-  a.T_in = Tin;
-  a.C_in = Cin;
-  a.x_bs = (long long)Tin * ldx;
-  a.w = w;
-  a.ldw = Cin;
-  a.w_ts = (long long)N * Cin;
-  a.taps = taps;
-  a.dil = dil;
-  a.pad = pad;
-  a.stride = 1;
-  a.y = y;
-  a.ldy = ldy;
-  a.y_bs = (long long)Tout * ldy;
-  a.T_out = Tout;
-  a.N = N;
-  a.bias = bias;
-  a.batch = B;
-  return a;
-}
-
-
 }  // namespace
-
-static void run(Ctx& c, const ConvArgs& a, hipStream_t s, double flops = -1.0) {
-  launch_conv(c, a, false, s, flops);
-}
-
-float* Ctx::W(const std::string& name) const {
-  auto it = dev.find(name);
-  if (it == dev.end()) throw Error(RVCX_E_STATE, "packed weight not found: " + name);
-  return static_cast<float*>(it->second->p);
-}
-
-float* Ctx::alloc_weight(const std::string& name, const std::vector<float>& data) {
-  std::unique_ptr<DevBuf> b(new DevBuf());
-  size_t bytes = data.size() * sizeof(float);
-  if (bytes == 0) bytes = 16;
-  if (hipMalloc(&b->p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    throw Error(RVCX_E_OOM, "weight allocation failed: " + name);
-  }
-  b->bytes = bytes;
-  RVCX_HIP(hipMemcpy(b->p, data.data(), data.size() * sizeof(float), hipMemcpyHostToDevice));
-  float* p = static_cast<float*>(b->p);
-  auto old = dev.find(name);
-  if (old != dev.end()) {
-    const uintptr_t o = reinterpret_cast<uintptr_t>(old->second->p);
-    wranges.erase(o);
-    drop_splits(o, o + old->second->bytes);  // the replaced tensor's split images
-  }
-  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
-  drop_splits(u, u + bytes);  // images cached for an earlier tensor at a reused address
-  wranges[u] = u + bytes;
-  dev[name] = std::move(b);
-  return p;
-}
-
-void Ctx::drop_splits(uintptr_t lo, uintptr_t hi) {
-  for (auto it = wsplit_cache.begin(); it != wsplit_cache.end();) {
-    const uintptr_t u = reinterpret_cast<uintptr_t>(std::get<0>(it->first));
-    it = (u >= lo && u < hi) ? wsplit_cache.erase(it) : std::next(it);
-  }
-  for (auto it = rb_wsplit_cache.begin(); it != rb_wsplit_cache.end();) {
-    const uintptr_t u = reinterpret_cast<uintptr_t>(it->first.first);
-    it = (u >= lo && u < hi) ? rb_wsplit_cache.erase(it) : std::next(it);
-  }
-}
-
-bool Ctx::is_weight(const void* q) const {
-  const uintptr_t u = reinterpret_cast<uintptr_t>(q);
-  auto it = wranges.upper_bound(u);
-  if (it == wranges.begin()) return false;
-  --it;
-  return u < it->second;
-}
 
 // ------------------------------------------------------------------ weight repacking
 void finalize_synth(Ctx& c) {
@@ -153,38 +28,38 @@ void finalize_synth(Ctx& c) {
   const int H = g.H, I = g.I, F = g.F, E = g.emb_dim, dk = H / g.n_heads, nw = 2 * g.window + 1;
   const int M = 0;
   // TextEncoder (encoders.py:88-144)
-  c.alloc_weight("te.emb_phone.w", get(c, M, "enc_p.emb_phone.weight", {H, E}).v);
-  c.alloc_weight("te.emb_phone.b", get(c, M, "enc_p.emb_phone.bias", {H}).v);
-  if (g.f0) c.alloc_weight("te.emb_pitch", get(c, M, "enc_p.emb_pitch.weight", {256, H}).v);
+  c.alloc_weight("te.emb_phone.w", host_weight(c, M, "enc_p.emb_phone.weight", {H, E}).v);
+  c.alloc_weight("te.emb_phone.b", host_weight(c, M, "enc_p.emb_phone.bias", {H}).v);
+  if (g.f0) c.alloc_weight("te.emb_pitch", host_weight(c, M, "enc_p.emb_pitch.weight", {256, H}).v);
   for (int i = 0; i < g.n_layers; ++i) {
     const std::string p = "enc_p.encoder.attn_layers." + std::to_string(i);
     const std::string q = "te." + std::to_string(i);
-    auto& wq = get(c, M, p + ".conv_q.weight", {H, H, 1}).v;
-    auto& wk = get(c, M, p + ".conv_k.weight", {H, H, 1}).v;
-    auto& wv = get(c, M, p + ".conv_v.weight", {H, H, 1}).v;
+    auto& wq = host_weight(c, M, p + ".conv_q.weight", {H, H, 1}).v;
+    auto& wk = host_weight(c, M, p + ".conv_k.weight", {H, H, 1}).v;
+    auto& wv = host_weight(c, M, p + ".conv_v.weight", {H, H, 1}).v;
     c.alloc_weight(q + ".qkv.w", cat({&wq, &wk, &wv}));
-    auto& bq = get(c, M, p + ".conv_q.bias", {H}).v;
-    auto& bk = get(c, M, p + ".conv_k.bias", {H}).v;
-    auto& bv = get(c, M, p + ".conv_v.bias", {H}).v;
+    auto& bq = host_weight(c, M, p + ".conv_q.bias", {H}).v;
+    auto& bk = host_weight(c, M, p + ".conv_k.bias", {H}).v;
+    auto& bv = host_weight(c, M, p + ".conv_v.bias", {H}).v;
     c.alloc_weight(q + ".qkv.b", cat({&bq, &bk, &bv}));
-    c.alloc_weight(q + ".o.w", get(c, M, p + ".conv_o.weight", {H, H, 1}).v);
-    c.alloc_weight(q + ".o.b", get(c, M, p + ".conv_o.bias", {H}).v);
-    c.alloc_weight(q + ".rel_k", get(c, M, p + ".emb_rel_k", {1, nw, dk}).v);
-    c.alloc_weight(q + ".rel_v", get(c, M, p + ".emb_rel_v", {1, nw, dk}).v);
+    c.alloc_weight(q + ".o.w", host_weight(c, M, p + ".conv_o.weight", {H, H, 1}).v);
+    c.alloc_weight(q + ".o.b", host_weight(c, M, p + ".conv_o.bias", {H}).v);
+    c.alloc_weight(q + ".rel_k", host_weight(c, M, p + ".emb_rel_k", {1, nw, dk}).v);
+    c.alloc_weight(q + ".rel_v", host_weight(c, M, p + ".emb_rel_v", {1, nw, dk}).v);
     const std::string n1 = "enc_p.encoder.norm_layers_1." + std::to_string(i);
     const std::string n2 = "enc_p.encoder.norm_layers_2." + std::to_string(i);
-    c.alloc_weight(q + ".ln1.g", get(c, M, n1 + ".gamma", {H}).v);
-    c.alloc_weight(q + ".ln1.b", get(c, M, n1 + ".beta", {H}).v);
-    c.alloc_weight(q + ".ln2.g", get(c, M, n2 + ".gamma", {H}).v);
-    c.alloc_weight(q + ".ln2.b", get(c, M, n2 + ".beta", {H}).v);
+    c.alloc_weight(q + ".ln1.g", host_weight(c, M, n1 + ".gamma", {H}).v);
+    c.alloc_weight(q + ".ln1.b", host_weight(c, M, n1 + ".beta", {H}).v);
+    c.alloc_weight(q + ".ln2.g", host_weight(c, M, n2 + ".gamma", {H}).v);
+    c.alloc_weight(q + ".ln2.b", host_weight(c, M, n2 + ".beta", {H}).v);
     const std::string f = "enc_p.encoder.ffn_layers." + std::to_string(i);
-    c.alloc_weight(q + ".ffn1.w", pack_conv1d(get(c, M, f + ".conv_1.weight", {F, H, g.ksize})));
-    c.alloc_weight(q + ".ffn1.b", get(c, M, f + ".conv_1.bias", {F}).v);
-    c.alloc_weight(q + ".ffn2.w", pack_conv1d(get(c, M, f + ".conv_2.weight", {H, F, g.ksize})));
-    c.alloc_weight(q + ".ffn2.b", get(c, M, f + ".conv_2.bias", {H}).v);
+    c.alloc_weight(q + ".ffn1.w", pack_conv1d(host_weight(c, M, f + ".conv_1.weight", {F, H, g.ksize})));
+    c.alloc_weight(q + ".ffn1.b", host_weight(c, M, f + ".conv_1.bias", {F}).v);
+    c.alloc_weight(q + ".ffn2.w", pack_conv1d(host_weight(c, M, f + ".conv_2.weight", {H, F, g.ksize})));
+    c.alloc_weight(q + ".ffn2.b", host_weight(c, M, f + ".conv_2.bias", {H}).v);
   }
-  c.alloc_weight("te.proj.w", get(c, M, "enc_p.proj.weight", {2 * I, H, 1}).v);
-  c.alloc_weight("te.proj.b", get(c, M, "enc_p.proj.bias", {2 * I}).v);
+  c.alloc_weight("te.proj.w", host_weight(c, M, "enc_p.proj.weight", {2 * I, H, 1}).v);
+  c.alloc_weight("te.proj.b", host_weight(c, M, "enc_p.proj.bias", {2 * I}).v);
   // flow (residuals.py:103-258, modules.py:5-117). A coupling's WaveNet state lives in one [T][2H] buffer: the
   // residual stream h in columns [0, H), the skip sum in [H, 2H). `pre` is packed with H zero rows appended, so its
   // launch also clears the skip sum; the cond layers of all couplings are one [flow_n * cl][gin] GEMM.
@@ -197,7 +72,8 @@ void finalize_synth(Ctx& c) {
     const std::string p = "flow.flows." + std::to_string(2 * f);
     const std::string q = "flow." + std::to_string(f);
     const bool rev = g.flow_n % 2 == 0 && (g.flow_n - 1 - f) % 2 == 0;
-    std::vector<float> prew = get(c, M, p + ".pre.weight", {H, I / 2, 1}).v, preb = get(c, M, p + ".pre.bias", {H}).v;
+    std::vector<float> prew = host_weight(c, M, p + ".pre.weight", {H, I / 2, 1}).v;
+    std::vector<float> preb = host_weight(c, M, p + ".pre.bias", {H}).v;
     if (rev)
       for (int o = 0; o < H; ++o) std::reverse(prew.begin() + (size_t)o * (I / 2), prew.begin() + (size_t)(o + 1) * (I / 2));
     prew.resize((size_t)2 * H * (I / 2), 0.f);
@@ -205,20 +81,22 @@ void finalize_synth(Ctx& c) {
     c.alloc_weight(q + ".pre.w", prew);
     c.alloc_weight(q + ".pre.b", preb);
     const int cl = 2 * H * g.flow_layers;
-    const auto& cw = get(c, M, p + ".enc.cond_layer.weight", {cl, g.gin, 1}).v;
-    const auto& cb = get(c, M, p + ".enc.cond_layer.bias", {cl}).v;
+    const auto& cw = host_weight(c, M, p + ".enc.cond_layer.weight", {cl, g.gin, 1}).v;
+    const auto& cb = host_weight(c, M, p + ".enc.cond_layer.bias", {cl}).v;
     condw.insert(condw.end(), cw.begin(), cw.end());
     condb.insert(condb.end(), cb.begin(), cb.end());
     for (int L = 0; L < g.flow_layers; ++L) {
       const std::string l = std::to_string(L);
       c.alloc_weight(q + ".in" + l + ".w",
-                     pack_conv1d(get(c, M, p + ".enc.in_layers." + l + ".weight", {2 * H, H, g.flow_k})));
-      c.alloc_weight(q + ".in" + l + ".b", get(c, M, p + ".enc.in_layers." + l + ".bias", {2 * H}).v);
+                     pack_conv1d(host_weight(c, M, p + ".enc.in_layers." + l + ".weight", {2 * H, H, g.flow_k})));
+      c.alloc_weight(q + ".in" + l + ".b", host_weight(c, M, p + ".enc.in_layers." + l + ".bias", {2 * H}).v);
       const int rs = (L == g.flow_layers - 1) ? H : 2 * H;
-      c.alloc_weight(q + ".rs" + l + ".w", get(c, M, p + ".enc.res_skip_layers." + l + ".weight", {rs, H, 1}).v);
-      c.alloc_weight(q + ".rs" + l + ".b", get(c, M, p + ".enc.res_skip_layers." + l + ".bias", {rs}).v);
+      c.alloc_weight(q + ".rs" + l + ".w",
+                     host_weight(c, M, p + ".enc.res_skip_layers." + l + ".weight", {rs, H, 1}).v);
+      c.alloc_weight(q + ".rs" + l + ".b", host_weight(c, M, p + ".enc.res_skip_layers." + l + ".bias", {rs}).v);
     }
-    std::vector<float> postw = get(c, M, p + ".post.weight", {I / 2, H, 1}).v, postb = get(c, M, p + ".post.bias", {I / 2}).v;
+    std::vector<float> postw = host_weight(c, M, p + ".post.weight", {I / 2, H, 1}).v;
+    std::vector<float> postb = host_weight(c, M, p + ".post.bias", {I / 2}).v;
     if (rev) {
       for (int o = 0; o < I / 4; ++o)
         std::swap_ranges(postw.begin() + (size_t)o * H, postw.begin() + (size_t)(o + 1) * H,
@@ -230,7 +108,7 @@ void finalize_synth(Ctx& c) {
   }
   c.alloc_weight("flow.cond.w", condw);
   c.alloc_weight("flow.cond.b", condb);
-  c.alloc_weight("emb_g", get(c, M, "emb_g.weight", {g.n_spk, g.gin}).v);
+  c.alloc_weight("emb_g", host_weight(c, M, "emb_g.weight", {g.n_spk, g.gin}).v);
   if (g.f0 && g.vocoder == 2) {  // RefineGAN (generators/refinegan.py), its own weight tree
     finalize_refinegan(c);
     return;
@@ -238,18 +116,18 @@ void finalize_synth(Ctx& c) {
   // HiFiGAN-NSF (generators/hifigan_nsf.py:55-171); without pitch guidance the plain HiFiGANGenerator
   // (generators/hifigan.py:9-104): the same conv_pre / cond / ups / resblocks / conv_post, no source module
   const int C0 = g.C0;
-  c.alloc_weight("dec.pre.w", pack_conv1d(get(c, M, "dec.conv_pre.weight", {C0, I, 7})));
-  c.alloc_weight("dec.pre.b", get(c, M, "dec.conv_pre.bias", {C0}).v);
-  c.alloc_weight("dec.cond.w", get(c, M, "dec.cond.weight", {C0, g.gin, 1}).v);
-  c.alloc_weight("dec.cond.b", get(c, M, "dec.cond.bias", {C0}).v);
+  c.alloc_weight("dec.pre.w", pack_conv1d(host_weight(c, M, "dec.conv_pre.weight", {C0, I, 7})));
+  c.alloc_weight("dec.pre.b", host_weight(c, M, "dec.conv_pre.bias", {C0}).v);
+  c.alloc_weight("dec.cond.w", host_weight(c, M, "dec.cond.weight", {C0, g.gin, 1}).v);
+  c.alloc_weight("dec.cond.b", host_weight(c, M, "dec.cond.bias", {C0}).v);
   // MRF HiFi-GAN (generators/hifigan_mrf.py:234-330) has the same dataflow under other names: upsamples.i for
   // ups.i, mrfs.i.j.layers.m.conv1/conv2 for resblocks.(i*nk+j).convs1/convs2.m, a 9-harmonic source and a
   // conv_post bias; its weights are packed under the NSF decoder's device names
   const bool mrf = g.vocoder == 1;
   const int Hs = g.src_harmonics();
   if (g.f0) {
-    auto& lw = get(c, M, "dec.m_source.l_linear.weight", {1, Hs}).v;
-    auto& lb = get(c, M, "dec.m_source.l_linear.bias", {1}).v;
+    auto& lw = host_weight(c, M, "dec.m_source.l_linear.weight", {1, Hs}).v;
+    auto& lb = host_weight(c, M, "dec.m_source.l_linear.bias", {1}).v;
     c.alloc_weight("dec.src.w", lw);
     c.host[M]["__src_lin__"] = HostTensor{{lw[0], lb[0]}, {2}};
   }
@@ -265,8 +143,8 @@ void finalize_synth(Ctx& c) {
       throw Error(RVCX_E_SHAPE, "ConvTranspose1d stage " + std::to_string(i) + ": output length != T*u unsupported");
     const std::string n = "dec.ups." + std::to_string(i);
     const std::string nref = (mrf ? "dec.upsamples." : "dec.ups.") + std::to_string(i);
-    auto& w = get(c, M, nref + ".weight", {cin, cout, k});
-    auto& b = get(c, M, nref + ".bias", {cout});
+    auto& w = host_weight(c, M, nref + ".weight", {cin, cout, k});
+    auto& b = host_weight(c, M, nref + ".bias", {cout});
     auto fdiv = [](int a, int bb) { return (a >= 0) ? a / bb : -((-a + bb - 1) / bb); };
     int smin = 1 << 30, smax = -(1 << 30);
     for (int r = 0; r < u; ++r) {
@@ -307,7 +185,7 @@ void finalize_synth(Ctx& c) {
     // framed form for the implicit GEMM: the source is read as rows of `stride` samples, so the
     // kern = 2*stride conv becomes 2 taps x stride channels: wf[tap][co][ci] = w[co][0][tap*stride + ci]
     // (kern = 1 when stride = 1: one tap, one channel)
-    const HostTensor& wn = get(c, M, nn + ".weight", {cout, 1, kern});
+    const HostTensor& wn = host_weight(c, M, nn + ".weight", {cout, 1, kern});
     const int ntap = kern == 1 ? 1 : 2;
     std::vector<float> wf((size_t)ntap * cout * stride, 0.f);
     for (int tp = 0; tp < ntap; ++tp)
@@ -317,7 +195,7 @@ void finalize_synth(Ctx& c) {
           if (kk < kern) wf[((size_t)tp * cout + co) * stride + ci] = wn.v[(size_t)co * kern + kk];
         }
     c.alloc_weight(nn + ".wf", wf);
-    c.alloc_weight(nn + ".b", get(c, M, nn + ".bias", {cout}).v);
+    c.alloc_weight(nn + ".b", host_weight(c, M, nn + ".bias", {cout}).v);
   }
   const int nk = (int)g.rb_k.size();
   for (int i = 0; i < nu; ++i) {
@@ -331,15 +209,15 @@ void finalize_synth(Ctx& c) {
           const std::string nref = mrf ? "dec.mrfs." + std::to_string(i) + "." + std::to_string(j) + ".layers." +
                                              std::to_string(m) + (q ? ".conv2" : ".conv1")
                                        : n;
-          c.alloc_weight(n + ".w", pack_conv1d(get(c, M, nref + ".weight", {C, C, k})));
-          c.alloc_weight(n + ".b", get(c, M, nref + ".bias", {C}).v);
+          c.alloc_weight(n + ".w", pack_conv1d(host_weight(c, M, nref + ".weight", {C, C, k})));
+          c.alloc_weight(n + ".b", host_weight(c, M, nref + ".bias", {C}).v);
         }
       }
     }
   }
   const int Cl = C0 >> nu;
-  c.alloc_weight("dec.post.w", get(c, M, "dec.conv_post.weight", {1, Cl, 7}).v);
-  const float post_b = mrf ? get(c, M, "dec.conv_post.bias", {1}).v[0] : 0.f;  // weight_norm(Conv1d(ch, 1, 7))
+  c.alloc_weight("dec.post.w", host_weight(c, M, "dec.conv_post.weight", {1, Cl, 7}).v);
+  const float post_b = mrf ? host_weight(c, M, "dec.conv_post.bias", {1}).v[0] : 0.f;  // weight_norm(Conv1d(ch, 1, 7))
   c.host[M]["__post_b__"] = HostTensor{{post_b}, {1}};
 }
 
@@ -410,11 +288,11 @@ bool dec_noise_prepare(Ctx& c, int B, int T, const float* f0, const float* eps_s
                            (int)Ti, C, s, true),
             "noise_conv");
     } else {
-      ConvArgs an = conv(har + HAR_PAD - f.npad, f.stride, (int)Ti + f.ntap - 1, f.stride, c.W(nn + ".wf"), C, f.ntap, 1,
-                         0, c.W(nn + ".b"), nz, C, (int)Ti, B);
+      ConvArgs an = conv1d(har + HAR_PAD - f.npad, f.stride, (int)Ti + f.ntap - 1, f.stride, c.W(nn + ".wf"), C, f.ntap,
+                           1, 0, c.W(nn + ".b"), nz, C, (int)Ti, B);
       an.x_bs = har_ld;
       an.lds_pad = 64 * 1024;  // beside the flow's latency-bound chain: at most two of its workgroups per CU
-      run(c, an, s, 2.0 * B * (double)Ti * C * f.kern);
+      run1(c, an, s, 2.0 * B * (double)Ti * C * f.kern);
     }
   }
   return true;
@@ -498,7 +376,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
   }
   // conv_pre + cond(g)
   float* cv = c.buf<float>("dec.cvec", (size_t)B * C0, s);
-  run(c, lin(g, cf.gin, B, cf.gin, c.W("dec.cond.w"), C0, c.W("dec.cond.b"), cv, C0), s);
+  run1(c, lin(g, cf.gin, B, cf.gin, c.W("dec.cond.w"), C0, c.W("dec.cond.b"), cv, C0), s);
   // stage buffers sized for the largest stage
   size_t maxe = (size_t)Tc * C0;
   {
@@ -514,7 +392,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
   float* t1 = c.buf<float>("dec.t", (size_t)B * maxe, s);
   {
     ConvArgs a =
-        conv(z_btc + (size_t)fa * I, I, Tc, I, c.W("dec.pre.w"), C0, 7, 1, 3, c.W("dec.pre.b"), xin, C0, Tc, B);
+        conv1d(z_btc + (size_t)fa * I, I, Tc, I, c.W("dec.pre.w"), C0, 7, 1, 3, c.W("dec.pre.b"), xin, C0, Tc, B);
     a.x_bs = (long long)T * I;
     a.plan_T = T;
     a.pre_mask = mask + fa;
@@ -523,7 +401,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     a.ldr = 0;
     a.res_bs = C0;
     a.res_mode = RES_ADD_PRE;
-    run(c, a, s);
+    run1(c, a, s);
   }
   float* cur = xin;
   int curT = Tc, Cin = C0;
@@ -534,7 +412,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     const int C = L.cout, u = L.u, Ti = curT * u;
     const long long fullTi = fullT * u, offi = off * u;
     // LeakyReLU(0.1) -> ConvTranspose1d (polyphase) ; output [B][curT][u*C] == [B][Ti][C]
-    ConvArgs a = conv(cur, Cin, curT, Cin, L.w, u * C, L.taps, 1, L.pad, L.b, y, u * C, curT, B);
+    ConvArgs a = conv1d(cur, Cin, curT, Cin, L.w, u * C, L.taps, 1, L.pad, L.b, y, u * C, curT, B);
     a.plan_T = (int)fullT;
     a.w_static = 1;
     a.lowp = gen_lowp;
@@ -577,19 +455,19 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
         nz_fused = true;
       }
     }
-    run(c, a, s, 2.0 * B * curT * (double)Cin * C * L.k);
+    run1(c, a, s, 2.0 * B * curT * (double)Cin * C * L.k);
     if (cf.f0 && !nz_fused) {
       const float* hsrc = har + HAR_PAD - npad + har_off;  // the window's first source sample of this framing
       if (noise_row_kernel(nf, B, fullTi, C)) {
         check(noise_conv_add(hsrc, har_ld, stride, ntap, c.W(nn + ".wf"), c.W(nn + ".b"), y, B, Ti, C, s),
               "noise_conv_add");
       } else {
-        ConvArgs an = conv(hsrc, stride, Ti + ntap - 1, stride, c.W(nn + ".wf"), C, ntap, 1, 0, c.W(nn + ".b"), y, C, Ti,
-                           B);
+        ConvArgs an =
+            conv1d(hsrc, stride, Ti + ntap - 1, stride, c.W(nn + ".wf"), C, ntap, 1, 0, c.W(nn + ".b"), y, C, Ti, B);
         an.plan_T = (int)fullTi;
         an.x_bs = har_ld;
         an.acc_mode = ACC_ADD;
-        run(c, an, s, 2.0 * B * (double)Ti * C * kern);
+        run1(c, an, s, 2.0 * B * (double)Ti * C * kern);
       }
     }
     // mean of the ResBlocks (residuals.py:71-80) accumulated into S. `cur` (= xin) is dead once the
@@ -645,7 +523,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
         const int d = dil[m];
         const std::string n1 = rb + ".convs1." + std::to_string(m);
         const std::string n2 = rb + ".convs2." + std::to_string(m);
-        ConvArgs a1 = conv(r_in, C, Ti, C, c.W(n1 + ".w"), C, k, d, (k * d - d) / 2, c.W(n1 + ".b"), T1, C, Ti, B);
+        ConvArgs a1 = conv1d(r_in, C, Ti, C, c.W(n1 + ".w"), C, k, d, (k * d - d) / 2, c.W(n1 + ".b"), T1, C, Ti, B);
         a1.plan_T = (int)fullTi;
         a1.w_static = 1;
         a1.lowp = gen_lowp;
@@ -655,11 +533,11 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
         a1.slope = 0.1f;
         const bool last = (m + 1 == dil.size());
         float* dst = last ? S : RR;
-        ConvArgs a2 = conv(T1, C, Ti, C, c.W(n2 + ".w"), C, k, 1, (k - 1) / 2, c.W(n2 + ".b"), dst, C, Ti, B);
+        ConvArgs a2 = conv1d(T1, C, Ti, C, c.W(n2 + ".w"), C, k, 1, (k - 1) / 2, c.W(n2 + ".b"), dst, C, Ti, B);
         a2.plan_T = (int)fullTi;
         a2.w_static = 1;
         a2.lowp = gen_lowp;
-        run(c, a1, s);
+        run1(c, a1, s);
         a2.res = r_in;
         a2.ldr = C;
         a2.res_bs = (long long)Ti * C;
@@ -668,7 +546,7 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
           a2.acc_mode = (j == 0) ? ACC_STORE : ((j + 1 == nk) ? ACC_ADD_DIV : ACC_ADD);
           a2.acc_div = (float)nk;
         }
-        run(c, a2, s);
+        run1(c, a2, s);
         r_in = RR;
       }
     }
@@ -713,7 +591,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     a.act = ACT_LRELU;
     a.slope = 0.1f;
     a.mask = mask;
-    run(c, a, s);
+    run1(c, a, s);
   }
   float* qkv = c.buf<float>("te.qkv", BT * 3 * H, s);
   const int nsplit = flash_attn_splits(B, nh, T);
@@ -724,7 +602,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
   const float qscale = (float)(1.0 / std::sqrt((double)dk));
   for (int i = 0; i < cf.n_layers; ++i) {
     const std::string q = "te." + std::to_string(i);
-    run(c, lin(x, H, (int)BT, H, c.W(q + ".qkv.w"), 3 * H, c.W(q + ".qkv.b"), qkv, 3 * H), s);
+    run1(c, lin(x, H, (int)BT, H, c.W(q + ".qkv.w"), 3 * H, c.W(q + ".qkv.b"), qkv, 3 * H), s);
     // attentions.py:79-185 in one pass per query block (flash_attn.hip): no [B][nh][T][T] scores. The key mask only
     // where a row is shorter than T: with every length T it is all ones, and its per-element loads in the key loop
     // cost the TextEncoder's attention ~1/3 of its time (the fill never fires: identical results)
@@ -738,18 +616,18 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
       a.ldr = H;
       a.ln_g = c.W(q + ".ln1.g");
       a.ln_b = c.W(q + ".ln1.b");
-      run(c, a, s);
+      run1(c, a, s);
     }
     {  // FFN (attentions.py:221-231): conv_1(pad(x*mask)) -> relu -> conv_2(pad(.*mask)) * mask
-      ConvArgs a = conv(x, H, T, H, c.W(q + ".ffn1.w"), F, cf.ksize, 1, (cf.ksize - 1) / 2, c.W(q + ".ffn1.b"), h1,
-                        F, T, B);
+      ConvArgs a = conv1d(x, H, T, H, c.W(q + ".ffn1.w"), F, cf.ksize, 1, (cf.ksize - 1) / 2, c.W(q + ".ffn1.b"), h1,
+                          F, T, B);
       a.pre_mask = mask;
       a.pre_mask_bs = T;
       a.act = ACT_RELU;
-      run(c, a, s);
+      run1(c, a, s);
       // x = LN(x + conv_2(.) * mask) in the split-K combine (norm_layers_2, attentions.py:63-66): no separate pass
-      ConvArgs b = conv(h1, F, T, F, c.W(q + ".ffn2.w"), H, cf.ksize, 1, (cf.ksize - 1) / 2, c.W(q + ".ffn2.b"), x,
-                        H, T, B);
+      ConvArgs b = conv1d(h1, F, T, F, c.W(q + ".ffn2.w"), H, cf.ksize, 1, (cf.ksize - 1) / 2, c.W(q + ".ffn2.b"), x,
+                          H, T, B);
       b.pre_mask = mask;
       b.pre_mask_bs = T;
       b.mask = mask;
@@ -759,7 +637,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
       b.res_bs = (long long)T * H;
       b.ln_g = c.W(q + ".ln2.g");
       b.ln_b = c.W(q + ".ln2.b");
-      run(c, b, s);
+      run1(c, b, s);
     }
   }
   float* stats = c.buf<float>("te.stats", BT * 2 * I, s);
@@ -767,7 +645,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     ConvArgs a = lin(x, H, (int)BT, H, c.W("te.proj.w"), 2 * I, c.W("te.proj.b"), stats, 2 * I);
     a.pre_mask = mask;
     a.mask = mask;
-    run(c, a, s);
+    run1(c, a, s);
   }
   // m_p / logs_p [B][T][I] for the caller (the return tuple of Synthesizer.infer, synthesizers.py:243)
   if (mp_out)
@@ -819,7 +697,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
   const int cl = 2 * H * cf.flow_layers;
   float* gc = c.buf<float>("flow.gc", (size_t)B * cf.flow_n * cl, s);
   // g -> every coupling's cond_layer(g) in one GEMM (modules.py:32-35, :92-93)
-  run(c, lin(g, cf.gin, B, cf.gin, c.W("flow.cond.w"), cf.flow_n * cl, c.W("flow.cond.b"), gc, cf.flow_n * cl), s);
+  run1(c, lin(g, cf.gin, B, cf.gin, c.W("flow.cond.w"), cf.flow_n * cl, c.W("flow.cond.b"), gc, cf.flow_n * cl), s);
   const bool fold = cf.flow_n % 2 == 0;  // the flips folded into the couplings' weights (finalize)
   for (int f = cf.flow_n - 1; f >= 0; --f) {
     const std::string q = "flow." + std::to_string(f);
@@ -836,18 +714,18 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     {  // h = pre(x0) * mask, and the skip sum cleared (the zero rows of the packed pre weight)
       ConvArgs a = lin(x0, I, (int)BTf, I / 2, c.W(q + ".pre.w"), 2 * H, c.W(q + ".pre.b"), hs, 2 * H);
       a.mask = maskf;
-      run(c, a, s);
+      run1(c, a, s);
     }
     for (int L = 0; L < cf.flow_layers; ++L) {
       const std::string l = std::to_string(L);
       {  // acts = tanh(in(h)[:H] + g_l[:H]) * sigmoid(in(h)[H:] + g_l[H:])  (commons.py:88-103), in the split-K combine
-        ConvArgs a = conv(hs, 2 * H, Tf, H, c.W(q + ".in" + l + ".w"), 2 * H, cf.flow_k, 1, (cf.flow_k - 1) / 2,
-                          c.W(q + ".in" + l + ".b"), acts, H, Tf, B);
+        ConvArgs a = conv1d(hs, 2 * H, Tf, H, c.W(q + ".in" + l + ".w"), 2 * H, cf.flow_k, 1, (cf.flow_k - 1) / 2,
+                            c.W(q + ".in" + l + ".b"), acts, H, Tf, B);
         a.x_bs = (long long)Tf * 2 * H;
         a.gate_h = H;
         a.gate_g = gc + (size_t)f * cl + (size_t)L * 2 * H;
         a.gate_g_bs = (long long)cf.flow_n * cl;
-        run(c, a, s);
+        run1(c, a, s);
       }
       const float* wrs = c.W(q + ".rs" + l + ".w");
       const float* brs = c.W(q + ".rs" + l + ".b");
@@ -857,7 +735,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
       ConvArgs a = lin(acts, H, (int)BTf, H, wrs, last ? H : 2 * H, brs, last ? hs + H : hs, 2 * H);
       a.acc_mode = ACC_ADD;
       a.mask = maskf;
-      run(c, a, s);
+      run1(c, a, s);
     }
     {  // x1 = (x1 - m) * mask, m = post(h) * mask
       ConvArgs a = lin(hs + H, 2 * H, (int)BTf, H, c.W(q + ".post.w"), I / 2, c.W(q + ".post.b"), x1, I);
@@ -865,7 +743,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
       a.ldr = I;
       a.res_mode = RES_RSUB_POST;
       a.mask = maskf;
-      run(c, a, s);
+      run1(c, a, s);
     }
     if (!fold) std::swap(z, xf);
   }

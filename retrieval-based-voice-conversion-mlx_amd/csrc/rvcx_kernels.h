@@ -291,14 +291,12 @@ long long performer_ws_floats(int H, int T, int M, int B = 1);
 hipError_t performer_attention(const float* q, const float* k, const float* v, long long hs, int ld, int H, int T,
                                const float* P, int M, float* ws, float* out, long long out_hs, int out_ld,
                                hipStream_t s, int B = 1, long long bs = 0, long long out_bs = 0);
-// FCPE (fcpe.hip): sqrt(re^2 + im^2 + 1e-9) of spec [F][2 nbins] into rows of ldm floats (zeros past nbins);
-// GroupNorm(G, C) + LeakyReLU over x [B][T][C] in place, the statistics per (stream, group) (ws: B * G *
-// FCPE_GN_CHUNKS * 2 doubles, the time chunks' sums); y [B][T][C2] = swish(b + depthwise_K(GLU(x [B][T][2 C2]))) with
+// FCPE (fcpe.hip): GroupNorm(G, C) + LeakyReLU over x [B][T][C] in place, the statistics per (stream, group) (ws: B *
+// G * FCPE_GN_CHUNKS * 2 doubles, the time chunks' sums); y [B][T][C2] = swish(b + depthwise_K(GLU(x [B][T][2 C2]))) with
 // zero padding `pad` at each stream's own ends (w [K][C2], C2 % 64 == 0, K <= 64); fcpe_zero_pad: y [B][ldy] = pad_l
 // zeros | x row b (n of ldx) | zeros; fcpe_dup_last_frame: row F - 1 of every stream of mel [B][F][C] = its row F - 2; the cents decoders (mode 0 local_argmax, 1 argmax) on salience
 // [F][nb] with the checkpoint's cent table -> f0 [F] (fp64 holding the fp32 value); FCPEF0Predictor.post_process:
 // nearest expansion of f0 [F] to n frames and linear interpolation through the unvoiced ones (links: 2 n ints)
-hipError_t fcpe_magnitude(const float* spec, int F, int nbins, float* mag, int ldm, hipStream_t s);
 constexpr int FCPE_GN_CHUNKS = 64;
 hipError_t groupnorm_lrelu(float* x, int T, int C, int G, const float* gamma, const float* beta, float eps, float slope,
                            double* ws, hipStream_t s, int B = 1);
@@ -351,7 +349,8 @@ hipError_t act_inplace(float* x, long long n, int act, float slope, hipStream_t 
 hipError_t reflect_pad_1d(const float* x, int n, int pad_l, int pad_r, float* y, hipStream_t s, int B = 1,
                           long long ldx = 0, long long ldy = 0);
 hipError_t reflect_pad_rows(const float* x, int rows, int C, int pad_r, float* y, hipStream_t s, int B = 1);
-hipError_t stft_magnitude(const float* spec, int F, int nbins, float* mag, int ldm, hipStream_t s);
+// sqrt(re^2 + im^2 + eps) of spec [F][2 nbins] into rows of ldm floats (zeros past nbins); eps 0 or 1e-9f
+hipError_t stft_magnitude(const float* spec, int F, int nbins, float eps, float* mag, int ldm, hipStream_t s);
 hipError_t affine_inplace(float* x, long long n, float a, float b, hipStream_t s);
 hipError_t avgpool2(const float* x, int H, int W, int C, int ldx, float* y, hipStream_t s);
 hipError_t nhwc_to_hcw(const float* x, int H, int W, int C, float* y, hipStream_t s);

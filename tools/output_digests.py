@@ -1,0 +1,97 @@
+"""sha256 of the raw output bytes of every model entry point on the seeded synthetic models (diagnostic, not product
+code): run it on two builds and diff the outputs to show that a host-side refactor left every result bit-identical.
+
+One line per output: RMVPE (single and batched, a frame count that is no multiple of 32), the FCPE mel and salience
+(a normal length, and one shorter than the window: zero padding and the duplicated last frame), HuBERT, CREPE, the
+synthesizer with each vocoder, a 6-hop stream group, and both pipeline forms for f0_method 0 / 2 / 3 under autotune
+and under proposed pitch.
+
+    python tools/output_digests.py > digests.txt
+"""
+import dataclasses
+import hashlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "retrieval-based-voice-conversion-mlx_amd"), ROOT]
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def show(name, *tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    print(f"{name:36s} {h.hexdigest()}", flush=True)
+
+
+def synth_inputs(cfg, B, T, seed):
+    from rvcx import synthetic
+
+    rng = np.random.Generator(np.random.PCG64(seed))
+    phone = rng.standard_normal((B, T, cfg.text_enc_hidden_dim)).astype(np.float32)
+    pitch = rng.integers(1, 256, size=(B, T)).astype(np.int64)
+    return phone, [T] * B, pitch, synthetic.f0_walk(B, T, seed=seed + 1), list(range(B))
+
+
+def main():
+    from rvcx import synthetic
+    from rvcx.config import SYNTH_48K_V2
+    from rvcx.engine import Engine
+    from rvcx.realtime import StreamGroup
+    from rvcx.weights import normalize_state
+
+    f32 = np.float32
+    eng = Engine(0)
+    eng.load_synth(normalize_state(synthetic.synth_state(2)), SYNTH_48K_V2)
+    eng.load_hubert(normalize_state(synthetic.hubert_state(4)))
+    eng.load_rmvpe(normalize_state(synthetic.rmvpe_state(5)))
+    eng.load_crepe(synthetic.crepe_state("tiny"))
+    eng.load_fcpe(synthetic.fcpe_state(13, 2, 512), synthetic.fcpe_config(2, 512))
+
+    a = synthetic.speech_like(10000, seed=21).astype(f32)  # 63 frames
+    show("rmvpe B=1", *eng.rmvpe(a, want_hidden=True))
+    show("rmvpe_batch B=2", *eng.rmvpe_batch(np.stack([a, 0.5 * a[::-1]]), want_hidden=True))
+    for n in (8000, 400):  # 400 < win: zero padding, 2 STFT frames of 3
+        x = synthetic.speech_like(n, seed=22).astype(f32)
+        show(f"fcpe_mel n={n}", eng.fcpe_mel(x))
+        show(f"fcpe n={n}", *eng.fcpe(x, want_salience=True))
+    show("fcpe_batch B=2", *eng.fcpe_batch(np.stack([a, 0.5 * a[::-1]]), want_salience=True))
+    show("hubert", eng.hubert(a))
+    show("crepe", *eng.crepe(a, want_periodicity=True, want_probs=True))
+    show("crepe rvc", *eng.crepe(a, want_probs=True, semantics="rvc"))
+
+    show("synth_infer HiFi-GAN", eng.synth_infer(*synth_inputs(SYNTH_48K_V2, 2, 40, 31), seed=7))
+    for voc in ("MRF HiFi-GAN", "RefineGAN"):
+        cfg = dataclasses.replace(SYNTH_48K_V2, vocoder=voc)
+        e2 = Engine(0)
+        e2.load_synth(normalize_state(synthetic.synth_state(2, cfg)), cfg)
+        show(f"synth_infer {voc}", e2.synth_infer(*synth_inputs(cfg, 2, 40, 31), seed=7))
+        e2.close()
+
+    B, hops = 2, 6
+    grp = StreamGroup(eng, B, read_chunk_size=96, cross_fade_overlap_size=0.1, extra_convert_size=0.5,
+                      silent_threshold=-90.0, sid=list(range(B)))
+    block = grp.geometry["block48"]
+    audio = np.stack([synthetic.speech_like(block * hops, seed=60 + b, sr=48000).astype(f32) for b in range(B)])
+    outs = [grp.process(audio[:, h * block:(h + 1) * block], grp.opts(index_rate=0.0), seed=h)[0].clone()
+            for h in range(hops)]
+    show(f"stream group B={B} {hops} hops", *outs)
+    grp.close()
+
+    eng.set_pipeline_highpass()
+    speech = synthetic.speech_like(24000, seed=7)
+    two = np.stack([speech, 0.7 * np.roll(speech, 4000)])
+    for method in (0, 2, 3):
+        for adj in ({"f0_autotune": 1}, {"proposed_pitch": 1}):
+            opts = eng.pipeline_opts(f0_method=method, pitch=2.0, **adj)
+            tag = f"f0_method={method} {next(iter(adj))}"
+            show(f"pipeline_ex {tag}", *eng.pipeline_ex(speech, opts, seed=3, want_f0=True))
+            show(f"pipeline_batch {tag}", *eng.pipeline_batch(two, opts, sids=[0, 1], seed=3, want_f0=True))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
