@@ -98,6 +98,17 @@ int rvcx_hubert_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld
 int rvcx_rmvpe_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t lda, int B, float thred, double* d_f0,
                      int64_t cap_frames, int64_t* frames_out, float* d_hidden, void* stream);
 
+/* HuBERT over B inputs of different lengths in one launch set: row b has n[b] samples (host array) at
+ * d_audio + b*lda (lda >= every n[b]; samples past n[b] are never read). Row b's features [L_b][D], L_b =
+ * frames of n[b] as rvcx_hubert counts them (written to L_out[b], host, optional), land at d_feats + b*ld_rows*D;
+ * ld_rows must hold the longest row's frames. The rows of a block past L_b, up to the longest row's count, are
+ * overwritten with unspecified finite values. Every valid frame equals rvcx_hubert's on that input alone up to
+ * summation order: the GroupNorm statistics are over the row's own frames, the positional conv sees zeros past
+ * its end and attention masks its pad keys. Equal lengths take rvcx_hubert_batch's path. A row too short for
+ * one frame (n[b] < 400) fails with RVCX_E_SHAPE. */
+int rvcx_hubert_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, int version,
+                        float* d_feats, int64_t ld_rows, int64_t* L_out, void* stream);
+
 /* CREPE (f0 methods "crepe" / "crepe-tiny"): CREPE.get_f0(audio, f0_min, f0_max, threshold) of
  * rvc_mlx/lib/mlx/crepe.py:282-325 (the torchcrepe network of rvc/lib/predictors/f0.py:25-57; MLX dispatch
  * rvc_mlx/lib/mlx/pitch_extractors.py:155-156). Weights: RVCX_MODEL_CREPE under torchcrepe's names (conv1..6 +
@@ -307,6 +318,29 @@ int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t
                         const rvcx_pipeline_opts* opts, const int32_t* sids, const float* d_eps_z,
                         const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
                         double* d_f0, float* d_hidden, void* stream);
+
+/* rvcx_pipeline_batch for utterances of different lengths: row b has n[b] samples (host array; every n[b] + 160 <=
+ * t_max, lda >= every n[b]); row b of d_out (stride ldo) receives Pipeline.pipeline's output for utterance b, n_out[b]
+ * samples (host array; samples of a row past n_out[b], up to the longest row's count, may be overwritten). One ragged
+ * HuBERT pass (rvcx_hubert_batch_v), one Synthesizer.infer with per-row lengths, and one launch set per stage for the
+ * upsample + protect, the pitch packing, the trim, the volume envelope and the peak normalisation, whatever B is.
+ * The pitch network runs per row (RMVPE's padding, its U-Net's zero padding and the BiGRU's reverse pass all start at
+ * a row's own end); rows of equal length inside the batch share one batched RMVPE pass.
+ * Noise when injected uses rvcx_pipeline_batch's layouts with T the longest row's frame count T_max = max_b
+ * min((n[b] + 2 t_pad) / 160, 2 L_b): d_eps_z [B][inter][T_max], d_eps_src [B][T_max*upp]; row b consumes
+ * d_eps_z[b][:, :T_b] and the first T_b*upp source draws, the draws a B = 1 call on that row consumes.
+ * d_f0 (optional): row b's adjusted f0, 1 + (n[b] + 2 t_pad)/160 values at d_f0 + b*ldf.
+ * The generator runs over the window common to all rows on z * mask, as the reference's batched Synthesizer.infer
+ * does, so the last frames of a shorter row within the generator's receptive field (10 frames for the 48 kHz v2
+ * model) differ from a run of that row alone; the trim removes them when t_pad_tgt covers that field. Rows of
+ * different lengths with a smaller t_pad_tgt fail with RVCX_E_INVALID. Equal lengths take rvcx_pipeline_batch's
+ * stages. rvcx_workspace_bytes(B, n_max, opts) sizes an arena for a ragged batch of B rows with every n[b] <= n_max:
+ * it also runs this call on B rows of n_max as a ragged batch, and adds room for the shared split-K slab to be regrown
+ * once per row. */
+int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n, int64_t lda, int B,
+                          const rvcx_pipeline_opts* opts, const int32_t* sids, const float* d_eps_z,
+                          const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
+                          double* d_f0, int64_t ldf, void* stream);
 
 /* Single-chunk shorthand of rvcx_pipeline_ex (t_max = 0, defaults otherwise). */
 int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, double semitones, float protect,

@@ -392,6 +392,19 @@ int rvcx_hubert_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld
   });
 }
 
+int rvcx_hubert_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, int version,
+                        float* d_feats, int64_t ld_rows, int64_t* L_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[1]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
+    if (!d_audio || !d_feats || !n || B < 1 || ld_rows < 1) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch_v: bad arguments");
+    for (int b = 0; b < B; ++b)
+      if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch_v: bad row length");
+    set_device(ctx);
+    hubert_forward_v(*ctx, d_audio, n, lda, B, version == 1 ? 1 : 2, d_feats, ld_rows, L_out,
+                     static_cast<hipStream_t>(stream));
+  });
+}
+
 int rvcx_rmvpe_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t lda, int B, float thred, double* d_f0,
                      int64_t cap_frames, int64_t* frames_out, float* d_hidden, void* stream) {
   return guard(ctx, [&] {
@@ -621,9 +634,21 @@ int rvcx_workspace_bytes(rvcx_ctx* ctx, int B, int64_t n, const rvcx_pipeline_op
           std::vector<int32_t> sids((size_t)B, o.sid);
           pipeline_forward_batch(*ctx, static_cast<const double*>(audio.p), n, n, B, o, sids.data(), nullptr, nullptr, 0,
                                  static_cast<float*>(out.p), cap, nullptr, nullptr, s);
+          // rvcx_pipeline_batch_v on B rows of n samples, run as a ragged batch (masks, the row-length arrays, the
+          // gathered RMVPE group and one single-row RMVPE forward): the regions it takes beyond the call above
+          std::vector<int64_t> nv((size_t)B, n), no((size_t)B);
+          pipeline_forward_batch_v(*ctx, static_cast<const double*>(audio.p), nv.data(), n, B, o, sids.data(), nullptr,
+                                   nullptr, 0, static_cast<float*>(out.p), cap, no.data(), nullptr, 0, s);
         }
         RVCX_HIP(hipStreamSynchronize(s));
-        return (int64_t)ctx->carved;
+        int64_t carved = (int64_t)ctx->carved;
+        if (B > 1) {
+          // a ragged batch walks its rows' front ends in another order than the calls above, and the split-K slab all
+          // convs share is regrown whenever a later conv needs a larger one: room for one regrowth per row and stream
+          for (const char* slab : {"conv.splitk", "conv.splitk.aux"})
+            if (ctx->ws.count(slab) && ctx->ws[slab]) carved += (int64_t)B * (int64_t)ctx->ws[slab]->bytes;
+        }
+        return carved;
       };
       need = measure(*opts);
       if (opts->f0_method == 3) {
@@ -1304,5 +1329,19 @@ int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t
     const int64_t no = pipeline_forward_batch(*ctx, d_audio, n, lda, B, *opts, sids, d_eps_z, d_eps_src, seed, d_out,
                                               ldo, d_f0, d_hidden, static_cast<hipStream_t>(stream));
     if (n_out) *n_out = no;
+  });
+}
+
+int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n, int64_t lda, int B,
+                          const rvcx_pipeline_opts* opts, const int32_t* sids, const float* d_eps_z,
+                          const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
+                          double* d_f0, int64_t ldf, void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[0] || !ctx->ready[1] || !ctx->ready[2]) throw Error(RVCX_E_STATE, "models not finalized");
+    if (!d_audio || !n || !opts || !sids || !d_out || !n_out || B < 1)
+      throw Error(RVCX_E_INVALID, "rvcx_pipeline_batch_v: bad arguments");
+    set_device(ctx);
+    pipeline_forward_batch_v(*ctx, d_audio, n, lda, B, *opts, sids, d_eps_z, d_eps_src, seed, d_out, ldo, n_out, d_f0,
+                             ldf, static_cast<hipStream_t>(stream));
   });
 }

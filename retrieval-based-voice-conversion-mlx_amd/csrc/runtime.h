@@ -336,6 +336,7 @@ constexpr int HUBERT_LAYERS = 12;
 struct HubertRun {
   int B = 0, L = 0, version = 0;
   float* feats = nullptr;
+  const float* mask = nullptr;  // ragged batches: [B][L], 1 on a sequence's own frames (the attention's key mask)
 };
 HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
                        int64_t cap, hipStream_t s);
@@ -348,6 +349,9 @@ int64_t hubert_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int
                          int64_t cap, hipStream_t s);
 int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
                         int64_t cap, float* hidden, hipStream_t s);
+// batched over B inputs of nv[b] samples (host array): sequence b's hubert_frames(nv[b]) rows at feats + b*ld_rows*D
+int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
+                         int64_t ld_rows, int64_t* rows_out, hipStream_t s);
 // The output samples per row a caller of the synthesizer goes on to read, [s0, s1) (s1 < 0: all of them). The HiFi-GAN
 // generators (NSF and no-f0) then run on the window's frames plus their receptive field (dec_margin_frames) and write
 // the window's samples, bit-identical to the full-length run, at their usual place; the samples outside it are
@@ -450,6 +454,11 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
 int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t lda, int B, const rvcx_pipeline_opts& o,
                                const int32_t* sids, const float* eps_z, const float* eps_src, uint64_t seed,
                                float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s);
+// B utterances of nv[b] samples (host array), rows of stride lda: out row b n_out[b] samples, f0_out row b at stride ldf
+void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
+                              const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
+                              uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
+                              hipStream_t s);
 rvcx_pipeline_opts default_pipeline_opts();
 int proposed_key(const std::vector<double>& f0, double threshold);
 int64_t hubert_frames(int64_t n);  // HuBERT output rows for n samples (0 when too short)

@@ -85,11 +85,19 @@ int64_t hubert_frames(int64_t n) {
   return t;
 }
 
-// B equal-length sequences: audio row b at audio + b*lda; feats row block b at feats + b*L*outD.
+// B sequences: audio row b at audio + b*lda; feats row block b at feats + b*L*outD.
 // Row-wise ops (LayerNorm, Linear, FFN) run over all B*L rows at once; convolutions, GroupNorm and
 // attention take the sequence as their batch index.
-HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
-                       int64_t cap, hipStream_t s) {
+// nv == nullptr: B equal-length sequences of n samples. nv[B] (host): sequence b has nv[b] <= n samples and L is the
+// longest one's frame count. A sequence's frames are then those of a run on it alone, up to summation order:
+//   - conv0's GroupNorm statistics are over the sequence's own frames, and its frames past them are written as zero;
+//   - the strided convs are valid convolutions, so a sequence's valid frames read only its valid inputs (its pad
+//     frames read zeros and the tail of the valid ones: finite, and never read by a valid frame);
+//   - the feature projection writes pad frames as zero, which is the zero padding the positional conv (k 128, pad 64)
+//     reads past a sequence's end;
+//   - attention masks the pad keys (run.mask); every other op is row-wise.
+static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv, int64_t lda, int B, int version,
+                       float* feats, int64_t cap, hipStream_t s) {
   if (B < 1) throw Error(RVCX_E_INVALID, "hubert: batch < 1");
   int64_t T[8];
   T[0] = n;
@@ -103,10 +111,30 @@ HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B
   float* a = c.buf<float>("hb.a", (size_t)B * T[1] * HCONV, s);
   float* b = c.buf<float>("hb.b", (size_t)B * T[2] * HCONV, s);
   double* gnws = c.buf<double>("hb.gnws", groupnorm_ws_doubles(HCONV, B), s);
-  // conv0 -> GroupNorm(512, 512) -> GELU in three launches (statistics, finalize, apply), the conv recomputed by each
-  check(hubert_conv0_gn_gelu(audio, lda, c.W("hb.conv0"), (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"), 1e-5f, gnws,
-                             a, s, B),
-        "hubert_conv0");
+  float* mask = nullptr;
+  if (nv) {
+    // per-sequence conv0 frames | output frames on device, and the [B][L] mask of valid output frames
+    std::vector<int32_t> hl(2 * (size_t)B);
+    for (int r = 0; r < B; ++r) {
+      if (nv[r] > n) throw Error(RVCX_E_INVALID, "hubert: a row is longer than the batch's longest");
+      const int64_t Lr = hubert_frames(nv[r]);
+      if (Lr < 1) throw Error(RVCX_E_SHAPE, "hubert: input too short (" + std::to_string(nv[r]) + " samples)");
+      hl[r] = (int32_t)((nv[r] - HK[0]) / HS[0] + 1);
+      hl[B + r] = (int32_t)Lr;
+    }
+    int32_t* dl = c.buf<int32_t>("hb.lens", 2 * (size_t)B, s);
+    RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
+    mask = c.buf<float>("hb.mask", (size_t)BL, s);
+    check(seq_mask(dl + B, mask, B, L, s), "hubert_mask");
+    check(hubert_conv0_gn_gelu_v(audio, lda, c.W("hb.conv0"), dl, (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"),
+                                 1e-5f, gnws, a, s, B),
+          "hubert_conv0_v");
+  } else {
+    // conv0 -> GroupNorm(512, 512) -> GELU in three launches (statistics, finalize, apply), the conv recomputed by each
+    check(hubert_conv0_gn_gelu(audio, lda, c.W("hb.conv0"), (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"), 1e-5f,
+                               gnws, a, s, B),
+          "hubert_conv0");
+  }
   float* cur = a;
   float* nxt = b;
   for (int i = 1; i < 7; ++i) {
@@ -127,7 +155,11 @@ HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B
   float* hs2 = c.buf<float>("hb.hs2", (size_t)BL * HD, s);
   check(layernorm_rows(cur, nullptr, nxt, c.W("hb.fp.ln.g"), c.W("hb.fp.ln.b"), BL, HCONV, 1e-5f, nullptr, s),
         "fp_ln");
-  run1(c, lin(nxt, HCONV, BL, HCONV, c.W("hb.fp.w"), HD, c.W("hb.fp.b"), hs, HD), s);
+  {
+    ConvArgs fp = lin(nxt, HCONV, BL, HCONV, c.W("hb.fp.w"), HD, c.W("hb.fp.b"), hs, HD);
+    fp.mask = mask;  // ragged: pad frames become the positional conv's zero padding
+    run1(c, fp, s);
+  }
   {  // hs + gelu(pos_conv(hs)) (groups as inner batch, sequences as outer batch), then encoder LayerNorm
     const int cg = HD / POS_G;
     ConvArgs p = lin(hs, HD, L, cg, c.W("hb.pos.w"), cg, c.W("hb.pos.b"), hs2, HD);
@@ -156,7 +188,13 @@ HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B
   r.L = L;
   r.version = version;
   r.feats = feats;
+  r.mask = mask;
   return r;
+}
+
+HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
+                       int64_t cap, hipStream_t s) {
+  return front(c, audio, n, nullptr, lda, B, version, feats, cap, s);
 }
 
 // encoder layers [l0, l1) on the hidden states the front end left in "hb.hs" (modeling_hubert.py
@@ -174,8 +212,10 @@ void hubert_layers(Ctx& c, const HubertRun& run, int l0, int l1, hipStream_t s) 
   for (int i = l0; i < l1; ++i) {
     const std::string q = "hb." + std::to_string(i);
     run1(c, lin(hs, HD, BL, HD, c.W(q + ".qkv.w"), 3 * HD, c.W(q + ".qkv.b"), qkv, 3 * HD), s);
-    // softmax((q * hd^-0.5) k^T) v per head in one pass (flash_attn.hip): no [B][12][L][L] scores
-    check(flash_attn(qkv, 3 * HD, B, L, HHEADS, hd, (float)std::pow((double)hd, -0.5), nullptr, nullptr, 0, nullptr,
+    // softmax((q * hd^-0.5) k^T) v per head in one pass (flash_attn.hip): no [B][12][L][L] scores. Ragged batches
+    // (run.mask): a pad key's score is -1e4, which is exp(-1e4 - max) == 0 in fp32 beside any valid key's (the scores
+    // of LayerNormed rows are far inside +-9e3), so it adds exactly 0 to a valid query's sums
+    check(flash_attn(qkv, 3 * HD, B, L, HHEADS, hd, (float)std::pow((double)hd, -0.5), nullptr, nullptr, 0, run.mask,
                      part_o, part_ml, nsplit, att, HD, s),
           "flash_attn");
     {  // hs = LN(hs + out_proj(att)) (layer_norm) in the split-K combine, in place: one combine block per row reads
@@ -228,6 +268,36 @@ int64_t hubert_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int
 int64_t hubert_forward(Ctx& c, const float* audio, int64_t n, int version, float* feats, int64_t cap,
                        hipStream_t s) {
   return hubert_forward_b(c, audio, n, n, 1, version, feats, cap, s);
+}
+
+// B sequences of nv[b] samples (host array): sequence b's L_b = hubert_frames(nv[b]) feature rows at
+// feats + b*ld_rows*outD, one launch set for all rows. Returns the longest sequence's row count; rows_out[b] = L_b.
+// The rows of a sequence past L_b (up to the longest's) are written and hold no meaning.
+int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
+                         int64_t ld_rows, int64_t* rows_out, hipStream_t s) {
+  if (B < 1) throw Error(RVCX_E_INVALID, "hubert: batch < 1");
+  int64_t n_max = 0;
+  bool equal = true;
+  for (int b = 0; b < B; ++b) {
+    n_max = std::max(n_max, nv[b]);
+    equal = equal && nv[b] == nv[0];
+  }
+  if (lda < n_max && B > 1) throw Error(RVCX_E_INVALID, "hubert: row stride shorter than the longest row");
+  const int64_t L = hubert_frames(n_max);
+  if (L > ld_rows) throw Error(RVCX_E_CAPACITY, "hubert: output needs " + std::to_string(L) + " rows per sequence");
+  const int outD = version == 1 ? 256 : HD;
+  // the layers write [B][L][outD] back to back: straight into the caller's rows when their stride is L
+  float* dst = (ld_rows == L || B == 1) ? feats : c.buf<float>("hb.featv", (size_t)B * L * outD, s);
+  // equal lengths need no masks: the equal-length form, bit for bit (rvcx_workspace_bytes sizes the ragged form)
+  const HubertRun r = front(c, audio, n_max, equal && !c.sizing_plan ? nullptr : nv, lda, B, version, dst, L, s);
+  hubert_layers(c, r, 0, HUBERT_LAYERS, s);
+  hubert_tail(c, r, s);
+  if (dst != feats)
+    RVCX_HIP(hipMemcpy2DAsync(feats, (size_t)ld_rows * outD * sizeof(float), dst, (size_t)L * outD * sizeof(float),
+                              (size_t)L * outD * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+  if (rows_out)
+    for (int b = 0; b < B; ++b) rows_out[b] = hubert_frames(nv[b]);
+  return L;
 }
 
 // ================================================================== RMVPE

@@ -622,6 +622,209 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   return keep;
 }
 
+// pitch_from_f0 for rows of Fv[b] frames at stride ld (f0, pitch, pitchf); f0_out rows at stride ldf
+static void pitch_from_f0_v(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B, const std::vector<int64_t>& Fv,
+                            int64_t ld, int32_t* pitch, float* pitchf, double* f0_out, int64_t ldf, hipStream_t s) {
+  std::vector<double> shift(B, o.pitch);
+  if (o.f0_autotune) {
+    for (int b = 0; b < B; ++b)
+      check(f0_autotune(f0 + (size_t)b * ld, (int)Fv[b], o.f0_autotune_strength, o.mlx_semantics ? 1 : 0, s),
+            "f0_autotune");
+    if (!o.mlx_semantics) std::fill(shift.begin(), shift.end(), 0.0);
+  } else if (o.proposed_pitch) {
+    std::vector<double> h((size_t)B * ld);
+    RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    RVCX_HIP(hipStreamSynchronize(s));
+    c.check_device_status();
+    for (int b = 0; b < B; ++b) {
+      std::vector<double> one(h.begin() + (size_t)b * ld, h.begin() + (size_t)b * ld + Fv[b]);
+      shift[b] = o.pitch + proposed_key(one, o.proposed_pitch_threshold);
+    }
+  }
+  for (int b = 0; b < B; ++b)
+    check(f0_post(f0 + (size_t)b * ld, (int)Fv[b], std::pow(2.0, shift[b] / 12.0), pitch + (size_t)b * ld,
+                  pitchf + (size_t)b * ld, f0_out ? f0_out + (size_t)b * ldf : nullptr, s),
+          "f0_post");
+}
+
+// Batched offline conversion of B utterances of different lengths nv[b] (each one chunk: nv[b] + 160 <= t_max): one
+// batched HuBERT over the ragged rows (hubert_forward_v), one Synthesizer.infer with per-row lengths, and the per-row
+// stages around them (upsample + protect, pitch packing, trim, volume envelope, peak normalisation) as one launch set
+// each, driven by device arrays of the rows' lengths. Per utterance the result is Pipeline.pipeline's, n_out[b] samples.
+//   - f0: RMVPE cannot take ragged rows exactly: its mel is reflect-padded at a row's own end and zero-padded to a
+//     multiple of 32 frames there, every 3x3 conv of the U-Net zero-pads at the image's own last frame, and the BiGRU's
+//     reverse recurrence starts there. Rows therefore run through the single-row forward, rows of equal length inside
+//     the batch together through the batched one.
+//   - the generator runs over the common window [t_pad_tgt, Tv_max upp - t_pad_tgt) on z * mask, as the reference's
+//     own batched Synthesizer.infer does: a shorter row's last frames, within the generator's receptive field of its
+//     end, see the zeroed pad frames' activations where a run of that row alone sees the conv's zero padding. The trim
+//     removes them only if t_pad_tgt covers the receptive field, so differing lengths with a smaller t_pad_tgt are refused.
+void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
+                              const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
+                              uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
+                              hipStream_t s) {
+  if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch_v: B < 1");
+  int64_t n_max = 0;
+  bool equal = true;
+  for (int b = 0; b < B; ++b) {
+    if (nv[b] <= 0 || (B > 1 && nv[b] > lda)) throw Error(RVCX_E_INVALID, "pipeline_batch_v: bad row length");
+    check_pipeline_opts(c, o, nv[b]);
+    if (o.t_max > 0 && nv[b] + 160 > o.t_max)
+      throw Error(RVCX_E_INVALID, "pipeline_batch_v: utterances longer than t_max take the single-utterance path");
+    if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch_v: sid out of range");
+    n_max = std::max(n_max, nv[b]);
+    equal = equal && nv[b] == nv[0];
+  }
+  const int E = c.scfg.emb_dim, upp = c.scfg.upp();
+  if (!equal && o.t_pad_tgt < (int64_t)dec_margin_frames(c.scfg) * upp)
+    throw Error(RVCX_E_INVALID, "pipeline_batch_v: rows of different lengths need t_pad_tgt >= " +
+                                    std::to_string((int64_t)dec_margin_frames(c.scfg) * upp) +
+                                    " samples (the generator's receptive field): a shorter row's last frames differ from "
+                                    "a run of that row alone, and only the trim removes them");
+  if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension mismatch");
+  const int64_t W = 160;
+  const int64_t m_max = n_max + 2 * o.t_pad;
+  const int64_t ldm = (m_max + 7) & ~int64_t(7);
+  std::vector<int64_t> mv(B), Fv(B), Lv(B), Tvv(B), keep(B);
+  int64_t Tv_max = 0, keep_max = 0;
+  for (int b = 0; b < B; ++b) {
+    mv[b] = nv[b] + 2 * o.t_pad;
+    Fv[b] = 1 + mv[b] / W;
+    Lv[b] = hubert_frames(mv[b]);
+    Tvv[b] = std::min<int64_t>(mv[b] / W, 2 * Lv[b]);
+    if (Tvv[b] <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch_v: input shorter than one frame");
+    keep[b] = Tvv[b] * upp - 2 * o.t_pad_tgt;
+    if (keep[b] <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch_v: utterance too short for the padding");
+    Tv_max = std::max(Tv_max, Tvv[b]);
+    keep_max = std::max(keep_max, keep[b]);
+  }
+  if (keep_max > ldo) throw Error(RVCX_E_CAPACITY, "pipeline_batch_v: output rows need " + std::to_string(keep_max));
+  const int64_t F_max = 1 + m_max / W, L_max = hubert_frames(m_max);
+  if (f0_out && ldf < F_max) throw Error(RVCX_E_CAPACITY, "pipeline_batch_v: f0 rows need " + std::to_string(F_max));
+  // per-row lengths on device: L | Tv | sid | n | keep
+  int32_t* meta = c.buf<int32_t>("pv.meta", 5 * (size_t)B, s);
+  {
+    std::vector<int32_t> hm(5 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+      hm[b] = (int32_t)Lv[b];
+      hm[B + b] = (int32_t)Tvv[b];
+      hm[2 * B + b] = sids[b];
+      hm[3 * B + b] = (int32_t)nv[b];
+      hm[4 * B + b] = (int32_t)keep[b];
+    }
+    RVCX_HIP(hipMemcpyAsync(meta, hm.data(), sizeof(int32_t) * hm.size(), hipMemcpyHostToDevice, s));
+  }
+  const int32_t *dL = meta, *dTv = meta + B, *dsid = meta + 2 * B, *dn = meta + 3 * B, *dkeep = meta + 4 * B;
+  // 1. zero-phase high-pass + reflect pad per utterance, each with its own length (pipeline.py:439, :459)
+  float* pad32 = c.buf<float>("pb.pad32", (size_t)B * ldm, s);
+  double* pad64 = c.buf<double>("pb.pad64", (size_t)B * m_max, s);
+  // (rows longest first here and in the per-row f0 below: the work buffers the rows share are then never regrown)
+  std::vector<int> order(B);
+  for (int b = 0; b < B; ++b) order[b] = b;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nv[x] > nv[y]; });
+  for (int b : order)
+    highpass_pad(c, audio + (size_t)b * lda, nv[b], o.t_pad, pad64 + (size_t)b * m_max, pad32 + (size_t)b * ldm, s);
+  // 2. ragged HuBERT on the aux stream beside the f0 of every row
+  double* f0 = c.buf<double>("pb.f0", (size_t)B * F_max, s);
+  float* feats = c.buf<float>("pb.feats", (size_t)B * L_max * E, s);
+  hipStream_t ax = fork_aux(c, s);
+  hubert_forward_v(c, pad32, mv.data(), ldm, B, hubert_version_for(c), feats, L_max, nullptr, ax);
+  const bool guided = c.scfg.f0;
+  int32_t* pitch = nullptr;
+  float* pitchf = nullptr;
+  if (guided) {
+    if (o.f0_method >= 1) {
+      for (int b : order)
+        f0_row(c, o, pad32 + (size_t)b * ldm, mv[b], f0 + (size_t)b * F_max, Fv[b], "pb.f0f", s);
+    } else {
+      const float thr = o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f;
+      // rows of equal length together; the groups largest first (rows x frames), so the work buffers a group shares
+      // with the next are not regrown
+      std::vector<std::vector<int>> groups;
+      for (int b = 0; b < B; ++b) {
+        bool placed = false;
+        for (auto& g : groups)
+          if (mv[g[0]] == mv[b]) g.push_back(b), placed = true;
+        if (!placed) groups.push_back({b});
+      }
+      if (c.sizing_plan) groups.push_back({0});  // rvcx_workspace_bytes: the single-row forward's regions too
+      std::stable_sort(groups.begin(), groups.end(), [&](const std::vector<int>& x, const std::vector<int>& y) {
+        return (int64_t)x.size() * Fv[x[0]] > (int64_t)y.size() * Fv[y[0]];
+      });
+      for (const auto& g : groups) {
+        const int b0 = g[0], ng = (int)g.size();
+        if (ng == 1) {
+          rmvpe_forward(c, pad32 + (size_t)b0 * ldm, mv[b0], thr, f0 + (size_t)b0 * F_max, Fv[b0], nullptr, s);
+          continue;
+        }
+        float* ga = c.buf<float>("pv.grp", (size_t)ng * ldm, s);
+        double* gf = c.buf<double>("pv.grpf0", (size_t)ng * F_max, s);
+        for (int k = 0; k < ng; ++k)
+          RVCX_HIP(hipMemcpyAsync(ga + (size_t)k * ldm, pad32 + (size_t)g[k] * ldm, sizeof(float) * (size_t)mv[b0],
+                                  hipMemcpyDeviceToDevice, s));
+        rmvpe_forward_b(c, ga, mv[b0], ldm, ng, thr, gf, Fv[b0], nullptr, s);
+        for (int k = 0; k < ng; ++k)
+          RVCX_HIP(hipMemcpyAsync(f0 + (size_t)g[k] * F_max, gf + (size_t)k * Fv[b0], sizeof(double) * (size_t)Fv[b0],
+                                  hipMemcpyDeviceToDevice, s));
+      }
+    }
+    pitch = c.buf<int32_t>("pb.pitch", (size_t)B * F_max, s);
+    pitchf = c.buf<float>("pb.pitchf", (size_t)B * F_max, s);
+    pitch_from_f0_v(c, o, f0, B, Fv, F_max, pitch, pitchf, f0_out, ldf, s);
+  } else if (f0_out) {
+    for (int b = 0; b < B; ++b) RVCX_HIP(hipMemsetAsync(f0_out + (size_t)b * ldf, 0, sizeof(double) * (size_t)Fv[b], s));
+  }
+  // 3. retrieval over all B*L_max rows (row-wise: a pad row's result is never read), upsample + protect, pitch packing
+  join_aux(c, s, ax);
+  const float* fx = feats;
+  if (o.index_rate > 0) {
+    float* fr = c.buf<float>("pb.feats_idx", (size_t)B * L_max * E, s);
+    index_retrieve(c, feats, B * L_max, E, o.index_rate, fr, s);
+    fx = fr;
+  }
+  float* phone = c.buf<float>("pb.phone", (size_t)B * Tv_max * E, s);
+  int32_t* pc = nullptr;
+  float* pf = nullptr;
+  if (guided) {
+    pc = c.buf<int32_t>("pb.pc", (size_t)B * Tv_max, s);
+    pf = c.buf<float>("pb.pf", (size_t)B * Tv_max, s);
+    check(pack_pitch_v(pitch, pitchf, F_max, dTv, (int)Tv_max, pc, pf, B, s), "pack_pitch");
+  }
+  check(upsample2_protect_v(fx, feats, dL, (int)L_max, E, phone, dTv, (int)Tv_max,
+                            (guided && o.protect < 0.5f) ? pitchf : nullptr, F_max, o.protect, B, s),
+        "upsample");
+  // 4. one Synthesizer.infer with per-row lengths (pipeline.py:365-372), the generator over the common window
+  const int64_t nvc = Tv_max * upp;
+  float* vc = c.buf<float>("pb.vc", (size_t)B * nvc, s);
+  {
+    DecWindow win;
+    if (o.t_pad_tgt > 0 && c.use_dec_window()) win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
+    if (equal && !c.sizing_plan) {
+      ScopedFullLengths full(c);
+      synth_forward(c, B, (int)Tv_max, phone, dTv, pc, pf, dsid, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
+                    nullptr, nullptr, win);
+    } else {
+      synth_forward(c, B, (int)Tv_max, phone, dTv, pc, pf, dsid, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
+                    nullptr, nullptr, win);
+    }
+  }
+  // 5. trim, volume envelope, peak normalisation of every row in one launch set each (pipeline.py:545-552)
+  float* mx = c.buf<float>("pb.max", peak_normalize_ws_floats(B), s);
+  if (o.volume_envelope == 1.0) {
+    check(peak_normalize_v(vc + o.t_pad_tgt, nvc, out, ldo, dkeep, keep_max, mx, B, s), "peak_normalize");
+  } else {
+    RVCX_HIP(hipMemcpy2DAsync(out, ldo * sizeof(float), vc + o.t_pad_tgt, nvc * sizeof(float), keep_max * sizeof(float),
+                              B, hipMemcpyDeviceToDevice, s));
+    float* rws = c.buf<float>("pv.rms", (size_t)B * (rms_frame_count(n_max, 16000) + rms_frame_count(keep_max, c.scfg.sr)),
+                              s);
+    check(change_rms_v(pad64 + o.t_pad, m_max, dn, n_max, 16000, out, ldo, dkeep, keep_max, c.scfg.sr,
+                       (float)o.volume_envelope, rws, B, s),
+          "change_rms");
+    check(peak_normalize_v(out, ldo, out, ldo, dkeep, keep_max, mx, B, s), "peak_normalize");
+  }
+  for (int b = 0; b < B; ++b) n_out[b] = keep[b];
+}
+
 rvcx_pipeline_opts default_pipeline_opts() {
   rvcx_pipeline_opts o;
   std::memset(&o, 0, sizeof(o));

@@ -345,6 +345,11 @@ hipError_t groupnorm_time_gelu(float* x, int T, int C, const float* gamma, const
 // C <= 1024, y 16-byte aligned; ws as above (aux_kernels.hip)
 hipError_t hubert_conv0_gn_gelu(const float* x, long long ldx, const float* w10, int T, int C, const float* gamma,
                                 const float* beta, float eps, double* ws, float* y, hipStream_t s, int B = 1);
+// The same over B sequences of different lengths: sequence b has Tv[b] rows (device array, 1 <= Tv[b] <= T_max) and its
+// statistics are over those rows alone; y is [B][T_max][C], rows from Tv[b] on written as zero
+hipError_t hubert_conv0_gn_gelu_v(const float* x, long long ldx, const float* w10, const int* Tv, int T_max, int C,
+                                  const float* gamma, const float* beta, float eps, double* ws, float* y, hipStream_t s,
+                                  int B);
 hipError_t act_inplace(float* x, long long n, int act, float slope, hipStream_t s);
 hipError_t reflect_pad_1d(const float* x, int n, int pad_l, int pad_r, float* y, hipStream_t s, int B = 1,
                           long long ldx = 0, long long ldy = 0);
@@ -454,6 +459,24 @@ hipError_t rt_clip(float* x, long long ld, int n, int B, hipStream_t s);
 hipError_t rt_sola(const float* audio, long long lda, const float* volsq, const int* gate, float* sola_buf, int cf,
                    int search, const float* fade_in, float* out, int block, int* offs, const int* slot2row, int B,
                    hipStream_t s);
+// The batched pipeline's per-row tail stages for rows of different lengths (aux_kernels.hip "ragged batches"): one
+// launch set for all B rows, lengths in device int arrays, each row's valid elements the single-row kernel's.
+// upsample2_protect: feats / feats0 [B][L_max][D], Lv[b] valid -> out [B][T_max][D], Tv[b] valid, the rest zero;
+// pitchf (optional) rows of stride ldp
+hipError_t upsample2_protect_v(const float* feats, const float* feats0, const int* Lv, int L_max, int D, float* out,
+                               const int* Tv, int T_max, const float* pitchf, long long ldp, float protect, int B,
+                               hipStream_t s);
+// pitch / pitchf rows of stride ldp -> pc / pf [B][T_max], zero from Tv[b] on
+hipError_t pack_pitch_v(const int32_t* pitch, const float* pitchf, long long ldp, const int* Tv, int T_max, int32_t* pc,
+                        float* pf, int B, hipStream_t s);
+// peak_normalize of row b's first nv[b] samples (n_max >= every nv[b]); ws peak_normalize_ws_floats(B)
+hipError_t peak_normalize_v(const float* src, long long lds, float* dst, long long ldd, const int* nv, long long n_max,
+                            float* ws, int B, hipStream_t s);
+// change_rms of row b: source n_src[b] fp64 samples (stride ld_src), target n_y[b] samples (stride ld_y); ws
+// [B][rms_frame_count(n_src_max, sr_src) + rms_frame_count(n_y_max, sr_y)] floats
+hipError_t change_rms_v(const double* src, long long ld_src, const int* n_src, long long n_src_max, int sr_src, float* y,
+                        long long ld_y, const int* n_y, long long n_y_max, int sr_y, float rate, float* ws, int B,
+                        hipStream_t s);
 // change_rms with a float32 source for B rows in one launch set: per-row rate [B] (exactly 1 = row untouched),
 // ws [B][n1 + n2] floats (n = rms_frame_count of either side)
 hipError_t change_rms_f32src_rows(const float* src, long long ld_src, long long n_src, int sr_src, float* y,

@@ -33,7 +33,7 @@ EXPORTS = [
     "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
     "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode", "rvcx_fcpe_b",
     "rvcx_index_default_build_opts", "rvcx_index_build", "rvcx_index_centroids", "rvcx_index_save",
-    "rvcx_spectral_gate", "rvcx_rt_set_clean",
+    "rvcx_spectral_gate", "rvcx_rt_set_clean", "rvcx_hubert_batch_v", "rvcx_pipeline_batch_v",
 ]
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
 TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
@@ -216,12 +216,15 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_kmeans_update": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
         "rvcx_pipeline_batch": (i32, [vp, vp, i64, i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp, i64,
                                       P(i64), vp, vp, vp]),
+        "rvcx_pipeline_batch_v": (i32, [vp, vp, P(i64), i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp,
+                                        i64, P(i64), vp, i64, vp]),
         "rvcx_set_highpass_sos": (i32, [vp, vp, i32]),
         "rvcx_workspace_bytes": (i32, [vp, i32, i64, P(PipelineOpts), P(i64), vp]),
         "rvcx_set_workspace": (i32, [vp, vp, i64]),
         "rvcx_workspace_info": (i32, [vp, P(i64), P(i64), P(i64)]),
         "rvcx_highpass_pad": (i32, [vp, vp, i64, i64, vp, vp, vp]),
         "rvcx_hubert_batch": (i32, [vp, vp, i64, i64, i32, i32, vp, i64, P(i64), vp]),
+        "rvcx_hubert_batch_v": (i32, [vp, vp, P(i64), i64, i32, i32, vp, i64, P(i64), vp]),
         "rvcx_rmvpe_batch": (i32, [vp, vp, i64, i64, i32, f32, vp, i64, P(i64), vp, vp]),
         "rvcx_rt_default_desc": (i32, [P(RtDesc)]),
         "rvcx_rt_default_opts": (i32, [P(RtOpts)]),

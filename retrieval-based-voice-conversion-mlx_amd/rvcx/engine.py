@@ -15,6 +15,15 @@ from .config import SYNTH_48K_V2, SynthConfig
 from .weights import normalize_state
 
 
+def hubert_frames(n: int) -> int:
+    """HuBERT feature rows for n samples at 16 kHz (the seven valid convs of its feature encoder); 0 when too short."""
+    for k, s in ((10, 5), (3, 2), (3, 2), (3, 2), (3, 2), (2, 2), (2, 2)):
+        if n < k:
+            return 0
+        n = (n - k) // s + 1
+    return n
+
+
 def _ptr(t) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -376,6 +385,29 @@ class Engine:
         L = rows.value
         return out.reshape(-1)[: B * L * D].reshape(B, L, D)
 
+    def hubert_batch_v(self, audios, version: str = "v2", ld_rows: Optional[int] = None):
+        """audios: a list of [N_b] arrays (16 kHz) of any lengths -> a list of feats [L_b, D] on device, from one
+        batched pass over all rows (each row's frames are `hubert`'s on that row alone, up to summation order).
+        ld_rows: frames between two rows' blocks in the output buffer (default: the longest row's frame count)."""
+        t = self.torch
+        rows = [self._dev(a, t.float32).reshape(-1) for a in audios]
+        B = len(rows)
+        if B < 1:
+            return []
+        ns = [int(r.numel()) for r in rows]
+        lda = max(ns)
+        a = t.zeros((B, lda), dtype=t.float32, device=self.device)
+        for b, r in enumerate(rows):
+            a[b, : ns[b]] = r
+        D = 256 if version == "v1" else 768
+        cap = max(1, hubert_frames(lda)) if ld_rows is None else int(ld_rows)
+        out = t.empty((B, cap, D), dtype=t.float32, device=self.device)
+        n_arr = (ctypes.c_int64 * B)(*ns)
+        L_arr = (ctypes.c_int64 * B)()
+        self._check(self.lib.rvcx_hubert_batch_v(self.ctx, a.data_ptr(), n_arr, lda, B, 1 if version == "v1" else 2,
+                                                 out.data_ptr(), cap, L_arr, self.stream()), "hubert_batch_v")
+        return [out[b, : int(L_arr[b])] for b in range(B)]
+
     def rmvpe_batch(self, audio, thred: float = 0.03, want_hidden: bool = False):
         """audio [B, N] (16 kHz, equal lengths) -> f0 fp64 [B, 1 + N//160] (and salience [B, F, 360])."""
         t = self.torch
@@ -648,6 +680,48 @@ class Engine:
         y = out.reshape(-1)[: B * ldo].reshape(B, ldo)[:, : no.value]
         extra = [v for v, w in ((f0, want_f0), (hid, want_hidden)) if w]
         return (y, *extra) if extra else y
+
+    def pipeline_frames(self, n: int, opts: "_lib.PipelineOpts") -> int:
+        """Synthesizer frames of an utterance of n samples under opts: min((n + 2 t_pad) / 160, 2 L)."""
+        m = int(n) + 2 * int(opts.t_pad)
+        return min(m // 160, 2 * hubert_frames(m))
+
+    def pipeline_batch_v(self, audios, opts: "_lib.PipelineOpts", sids=0, eps_z=None, eps_src=None, seed: int = 0,
+                         want_f0: bool = False):
+        """Utterances of different lengths (a list of fp64 [n_b] arrays @16 kHz, each within t_max) through one
+        batched pass (rvcx_pipeline_batch_v). Returns a list of fp32 [n_out_b] device tensors (row b =
+        Pipeline.pipeline of utterance b); with want_f0 also the list of the rows' adjusted f0 (fp64 [F_b]).
+        eps_z [B, inter, T_max] / eps_src [B, T_max * upp] with T_max = max pipeline_frames(n_b): row b consumes
+        eps_z[b, :, :T_b] and eps_src[b, :T_b * upp]."""
+        t = self.torch
+        rows = [self._dev(a, t.float64).reshape(-1) for a in audios]
+        B = len(rows)
+        if B < 1:
+            return ([], []) if want_f0 else []
+        ns = [int(r.numel()) for r in rows]
+        lda = max(ns)
+        a = t.zeros((B, lda), dtype=t.float64, device=self.device)
+        for b, r in enumerate(rows):
+            a[b, : ns[b]] = r
+        m = lda + 2 * int(opts.t_pad)
+        ldo = (m // 160) * self.upp
+        out = t.empty((B, ldo), dtype=t.float32, device=self.device)
+        sid = np.broadcast_to(np.asarray(sids, dtype=np.int32), (B,))
+        sarr = (ctypes.c_int32 * B)(*[int(v) for v in sid])
+        n_arr = (ctypes.c_int64 * B)(*ns)
+        no = (ctypes.c_int64 * B)()
+        ez = None if eps_z is None else self._dev(eps_z, t.float32)
+        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        F = 1 + m // 160
+        f0 = t.empty((B, F), dtype=t.float64, device=self.device) if want_f0 else None
+        self._check(self.lib.rvcx_pipeline_batch_v(self.ctx, a.data_ptr(), n_arr, lda, B, ctypes.byref(opts), sarr,
+                                                   _ptr(ez), _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+                                                   out.data_ptr(), ldo, no, _ptr(f0), F, self.stream()),
+                    "pipeline_batch_v")
+        ys = [out[b, : int(no[b])] for b in range(B)]
+        if not want_f0:
+            return ys
+        return ys, [f0[b, : 1 + (ns[b] + 2 * int(opts.t_pad)) // 160] for b in range(B)]
 
     def f0_autotune(self, f0, strength: float = 1.0, skip_unvoiced: bool = False):
         """Autotune.autotune_f0 on device; returns a new fp64 tensor."""

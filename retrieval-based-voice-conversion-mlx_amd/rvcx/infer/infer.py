@@ -177,6 +177,35 @@ class RVCX:
                 for c in chunks]
         return merge_audio(chunks, outs, intervals, 16000, self.tgt_sr) if split_audio else outs[0]
 
+    def convert_many(self, audios, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75, volume_envelope=1.0,
+                     protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, sid=0, proposed_pitch=False,
+                     proposed_pitch_threshold=155.0, seed: int = 0, batch: Optional[int] = None,
+                     max_pad: Optional[float] = None, noise_fn=None):
+        """`convert` over a list of 16 kHz utterances of any lengths -> the outputs in input order. Utterances of
+        similar length share one batched pass (PipelineRVCX.pipeline_many: sorted by length, a batch filled while its
+        shortest row is at least (1 - max_pad) of its longest, inputs above t_max converted alone)."""
+        from .pipeline import DEFAULT_BATCH, DEFAULT_MAX_PAD
+
+        return self.pipeline.pipeline_many(
+            self.hubert_model, self.net_g, sid, audios, pitch, f0_method, index_path, index_rate, self.use_f0,
+            volume_envelope, self.version, protect, f0_autotune, f0_autotune_strength, proposed_pitch,
+            proposed_pitch_threshold, seed=seed, batch=DEFAULT_BATCH if batch is None else batch,
+            max_pad=DEFAULT_MAX_PAD if max_pad is None else max_pad, noise_fn=noise_fn)
+
+    def infer_batch(self, input_dir, output_dir, **kw):
+        """convert_audio_batch (rvc/infer/infer.py:350-414) over the WAV files of input_dir: every file converted with
+        the options of `convert_many` and written under the same name to output_dir. Returns the output paths."""
+        from scipy.io import wavfile
+
+        names = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".wav"))
+        outs = self.convert_many([load_audio(os.path.join(input_dir, f)) for f in names], **kw)
+        os.makedirs(output_dir, exist_ok=True)
+        paths = []
+        for f, y in zip(names, outs):
+            paths.append(os.path.join(output_dir, f))
+            wavfile.write(paths[-1], self.tgt_sr, np.asarray(y, dtype=np.float32))
+        return paths
+
     def infer(self, audio_input, audio_output, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75,
               volume_envelope=1.0, protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, split_audio=False):
         from scipy.io import wavfile

@@ -37,6 +37,12 @@ class Config:
         return self.x_pad, self.x_query, self.x_center, self.x_max
 
 
+# pipeline_many's defaults: the best setting measured on a 64-utterance job of 2-30 s clips
+# (profiles/ragged_batch_times.txt: 829.5 ms against 850.1 ms, 848.0 .. 850.8, for the per-utterance loop)
+DEFAULT_BATCH = 8
+DEFAULT_MAX_PAD = 0.125
+
+
 class PipelineRVCX:
     # pipeline_mlx.py:82 / pitch_extractors.py:44 minus the pyworld CPU methods (dio, pm, harvest). "crepe" and
     # "crepe-tiny" run CREPE as each side defines it: semantics="mlx" as rvc_mlx/lib/mlx/crepe.py (reflect padding,
@@ -214,6 +220,17 @@ class PipelineRVCX:
                  f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, eps_z=None,
                  eps_src=None, seed: int = 0):
         """Whole utterance -> float32 [N_out] @tgt_sr (pipeline.py:390-558)."""
+        eng, opts = self._pipeline_opts(model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance,
+                                        volume_envelope, version, protect, f0_autotune, f0_autotune_strength,
+                                        proposed_pitch, proposed_pitch_threshold)
+        y, f0 = eng.pipeline_ex(np.asarray(audio, dtype=np.float64).reshape(-1), opts, eps_z=eps_z,
+                                eps_src=eps_src, seed=seed, want_f0=True)
+        self.last_f0 = f0
+        return eng.host(y)
+
+    def _pipeline_opts(self, model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance, volume_envelope,
+                       version, protect, f0_autotune, f0_autotune_strength, proposed_pitch, proposed_pitch_threshold):
+        """The checks and the rvcx_pipeline_opts of one `pipeline` call -> (engine, opts)."""
         self._check_method(f0_method)
         eng = self._engine(model)
         self._check_guidance(eng, bool(pitch_guidance))
@@ -237,10 +254,55 @@ class PipelineRVCX:
             proposed_pitch_threshold=float(proposed_pitch_threshold), volume_envelope=float(volume_envelope),
             mlx_semantics=int(mlx), index_rate=rate, f0_method=method, rmvpe_threshold=thr,
             fcpe_threshold=self.fcpe_threshold)
-        y, f0 = eng.pipeline_ex(np.asarray(audio, dtype=np.float64).reshape(-1), opts, eps_z=eps_z,
-                                eps_src=eps_src, seed=seed, want_f0=True)
-        self.last_f0 = f0
-        return eng.host(y)
+        return eng, opts
+
+    def pipeline_many(self, model, net_g, sid, audios, pitch=0, f0_method="rmvpe", file_index=None, index_rate=0.0,
+                      pitch_guidance=True, volume_envelope=1.0, version="v2", protect=0.33, f0_autotune=False,
+                      f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, seed: int = 0,
+                      batch: int = DEFAULT_BATCH, max_pad: float = DEFAULT_MAX_PAD, noise_fn=None):
+        """`pipeline` over a list of utterances of any lengths -> the list of float32 outputs in input order.
+        The utterances are grouped longest first into batches of up to `batch` rows whose shortest is at least
+        (1 - max_pad) of the longest (rvcx.offline.bucket) and every batch is one rvcx_pipeline_batch_v pass; an
+        utterance above t_max goes through `pipeline` alone (the batched pass takes single-chunk rows). batch = 1 is
+        the per-utterance loop. Batch k draws its noise from seed + k; noise_fn(i, T) -> (eps_z [inter, T], eps_src
+        [T * upp]) injects utterance i's noise instead (T its synthesizer frames), as the tests do."""
+        from ..offline import bucket
+
+        eng, opts = self._pipeline_opts(model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance,
+                                        volume_envelope, version, protect, f0_autotune, f0_autotune_strength,
+                                        proposed_pitch, proposed_pitch_threshold)
+        audios = [np.asarray(a, dtype=np.float64).reshape(-1) for a in audios]
+        outs = [None] * len(audios)
+        upp = eng.upp
+
+        def noise(i):
+            return (None, None) if noise_fn is None else noise_fn(i, eng.pipeline_frames(len(audios[i]), opts))
+
+        t_max = int(opts.t_max)
+        short = [i for i, a in enumerate(audios) if not (t_max > 0 and len(a) + 160 > t_max)]
+        for i in sorted(set(range(len(audios))) - set(short)):  # long inputs: the split search and the chunk loop
+            outs[i] = eng.host(eng.pipeline_ex(audios[i], opts, seed=seed))
+        for k, g in enumerate(bucket([len(audios[i]) for i in short], max(1, int(batch)), float(max_pad))):
+            ids = [short[j] for j in g]
+            if len(ids) == 1:
+                ez, es = noise(ids[0])
+                outs[ids[0]] = eng.host(eng.pipeline_ex(audios[ids[0]], opts, eps_z=ez, eps_src=es, seed=seed + k))
+                continue
+            ez = es = None
+            if noise_fn is not None:
+                Ts = [eng.pipeline_frames(len(audios[i]), opts) for i in ids]
+                per = [noise(i) for i in ids]
+                ez = np.zeros((len(ids), per[0][0].shape[0], max(Ts)), np.float32)
+                es = np.zeros((len(ids), max(Ts) * upp), np.float32)
+                for r, (z, sct) in enumerate(per):
+                    ez[r, :, :Ts[r]] = z
+                    es[r, :Ts[r] * upp] = sct
+            ys = eng.pipeline_batch_v([audios[i] for i in ids], opts, sids=int(opts.sid), eps_z=ez, eps_src=es,
+                                      seed=seed + k)
+            eng.check_device_status()
+            for i, y in zip(ids, ys):
+                outs[i] = y.cpu().numpy()
+        return outs
 
 
 PipelineMLX = PipelineRVCX

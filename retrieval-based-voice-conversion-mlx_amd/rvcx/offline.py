@@ -6,7 +6,9 @@ The reference shards a file list over devices with one process per device and no
 * ``plan``: every rank builds the SAME job list and takes its shard by longest-processing-time-first
   assignment (``sharding.assign_lpt``; equal lengths reduce to the reference's ``i :: world``). Within a
   shard, utterances of equal length are grouped into batches of up to B: one batch = one
-  ``rvcx_pipeline_batch`` pass (batched RMVPE, HuBERT and Synthesizer.infer).
+  ``rvcx_pipeline_batch`` pass (batched RMVPE, HuBERT and Synthesizer.infer). With ``max_pad`` the batches may
+  hold rows of different lengths (``bucket``), for a converter that takes such rows (``Engine.pipeline_batch_v``,
+  ``Engine.hubert_batch_v``).
 * ``run``: converts the shard batch by batch through a caller-supplied ``convert(batch, step)`` that
   returns one record row per utterance (id, n_out, peak, rms) as a [b, 4] tensor -- kept where it was made
   (the GPU bench leaves them in HBM, so the loop never waits for the device) -- the GPU bench passes the
@@ -45,15 +47,39 @@ class Plan:
     world: int
     batch: int
     shard: List[int]                 # job indices of this rank (ascending)
-    batches: List[List[int]]         # job indices per batched pass, equal length within a batch
+    batches: List[List[int]]         # job indices per batched pass (equal length within a batch unless max_pad)
 
 
-def plan(job: Sequence[Utterance], world: int, rank: int, batch: int) -> Plan:
+def bucket(lengths: Sequence[int], batch: int, max_pad: float) -> List[List[int]]:
+    """Positions of ``lengths`` grouped into batches of rows of similar length: longest first (equal lengths keep
+    their order), a batch is filled while it has fewer than ``batch`` rows and the next row is at least
+    ``(1 - max_pad)`` of the batch's longest, so no row of a batch is padded by more than ``max_pad`` of the batch's
+    length. ``max_pad = 0`` groups equal lengths only."""
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    if not 0.0 <= max_pad < 1.0:
+        raise ValueError("max_pad must be in [0, 1)")
+    out: List[List[int]] = []
+    for i in sorted(range(len(lengths)), key=lambda k: -lengths[k]):
+        # the longest row of a batch is its first; an integer comparison would need max_pad as a fraction
+        if out and len(out[-1]) < batch and lengths[i] >= (1.0 - max_pad) * lengths[out[-1][0]]:
+            out[-1].append(i)
+        else:
+            out.append([i])
+    return out
+
+
+def plan(job: Sequence[Utterance], world: int, rank: int, batch: int, max_pad: Optional[float] = None) -> Plan:
+    """max_pad None: batches of equal length only. A value: ``bucket``'s rule inside the shard (the shards themselves
+    do not depend on it)."""
     if batch < 1:
         raise ValueError("batch must be >= 1")
     if not 0 <= rank < world:
         raise ValueError(f"rank {rank} outside world {world}")
     shard = assign_lpt([u.n for u in job], world)[rank]
+    if max_pad is not None:
+        groups = bucket([job[i].n for i in shard], batch, max_pad)
+        return Plan(rank, world, batch, shard, [[shard[k] for k in g] for g in groups])
     by_len: Dict[int, List[int]] = {}
     for i in shard:
         by_len.setdefault(job[i].n, []).append(i)

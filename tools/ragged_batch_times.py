@@ -1,0 +1,128 @@
+"""A folder-like job of utterances of different lengths: one pass per utterance against batched passes over rows of
+similar length, for the whole pipeline and for HuBERT alone (diagnostic, not product code).
+
+The job: 64 `synthetic.speech_like` utterances, lengths drawn uniformly from 2-30 s at 16 kHz (one seed, printed),
+resident in HBM. Every route is timed over the whole job with a host clock around work that ends in a device
+synchronise, after one untimed warm-up pass over the same shapes; --reps passes, median reported:
+  (a) loop of `Engine.pipeline_ex` per utterance, longest first: the only route for such a job before
+      rvcx_pipeline_batch_v. Its own min .. max over the repeats is the spread every comparison is held against.
+  (b) `Engine.pipeline_batch_v` per batch of `offline.bucket(lengths, batch, max_pad)`, batch in {4, 8, 16} and
+      max_pad in {0.05, 0.125, 0.25}, with the share of computed synthesizer frames that are padding.
+  (c) `Engine.hubert_batch_v` over the same batches against a loop of `Engine.hubert`.
+A batched setting is called faster (slower) only if its median lies below (above) the loop's own min .. max.
+
+    python tools/ragged_batch_times.py [--reps 5] [--loop-only] > profiles/ragged_batch_times.txt
+
+--loop-only times the two loops alone. It calls nothing the ragged entry points added, so with RVCX_LIB pointing at a
+library built from an older commit it measures that commit's route.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "retrieval-based-voice-conversion-mlx_amd"), ROOT]
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+SEED, N_UTT, SR = 2024, 64, 16000
+
+
+def job_lengths():
+    rng = np.random.Generator(np.random.PCG64(SEED))
+    return [int(n) for n in rng.integers(2 * SR, 30 * SR + 1, size=N_UTT)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--loop-only", action="store_true")
+    args = ap.parse_args()
+    from rvcx import _lib, offline, synthetic
+    from rvcx.config import SYNTH_48K_V2
+    from rvcx.engine import Engine, hubert_frames
+    from rvcx.weights import normalize_state
+
+    dev = torch.device("cuda:0")
+    eng = Engine(0)
+    eng.load_synth(normalize_state(synthetic.synth_state(2)), SYNTH_48K_V2)
+    eng.load_hubert(normalize_state(synthetic.hubert_state(4)))
+    eng.load_rmvpe(normalize_state(synthetic.rmvpe_state(5)))
+    eng.set_pipeline_highpass()
+    opts = eng.pipeline_opts(pitch=2.0, protect=0.33)
+    ns = job_lengths()
+    seconds = sum(ns) / SR
+    print(f"library: {os.path.relpath(_lib.LIB_PATH, ROOT)}")
+    print(f"job: {N_UTT} utterances, seed {SEED}, {min(ns) / SR:.2f} .. {max(ns) / SR:.2f} s, {seconds:.1f} s of audio")
+    clips64 = [torch.as_tensor(synthetic.speech_like(n, seed=3000 + i), dtype=torch.float64).to(dev)
+               for i, n in enumerate(ns)]
+    clips32 = [c.float() for c in clips64]
+    order = sorted(range(N_UTT), key=lambda i: -ns[i])
+
+    def timed(fn):
+        fn()  # warm-up: every shape of the timed pass
+        out = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            out.append(time.perf_counter() - t0)
+        return out
+
+    res = {}
+
+    def report(name, t, ref=None, extra=""):
+        med = statistics.median(t)
+        verdict = ""
+        if ref is not None:
+            verdict = "faster" if med < min(ref) else ("slower" if med > max(ref) else "inside the loop's spread")
+        res[name] = {"s": [round(x, 5) for x in t], "audio_s_per_s": round(seconds / med, 1)}
+        print(f"{name:44s} median {med * 1e3:9.2f} ms  min {min(t) * 1e3:9.2f}  max {max(t) * 1e3:9.2f}  "
+              f"{seconds / med:9.1f} audio-s/s {extra} {verdict}", flush=True)
+
+    def pipe_loop():
+        for i in order:
+            eng.pipeline_ex(clips64[i], opts, seed=i)
+
+    def hub_loop():
+        for i in order:
+            eng.hubert(clips32[i])
+
+    t_pipe = timed(pipe_loop)
+    report("(a) loop of pipeline_ex", t_pipe,
+           extra=f"(spread {100 * (max(t_pipe) - min(t_pipe)) / statistics.median(t_pipe):.1f} %)")
+    t_hub = timed(hub_loop)
+    report("(c) loop of hubert", t_hub, extra=f"(spread {100 * (max(t_hub) - min(t_hub)) / statistics.median(t_hub):.1f} %)")
+    if not args.loop_only:
+        frames = [eng.pipeline_frames(n, opts) for n in ns]
+        for batch in (4, 8, 16):
+            for max_pad in (0.05, 0.125, 0.25):
+                groups = offline.bucket(ns, batch, max_pad)
+                pad = 1 - sum(frames) / sum(len(g) * frames[g[0]] for g in groups)
+                hpad = 1 - sum(hubert_frames(n) for n in ns) / sum(len(g) * hubert_frames(ns[g[0]]) for g in groups)
+                key = f"batch={batch} max_pad={max_pad}"
+
+                def pipe_batched():
+                    for k, g in enumerate(groups):
+                        eng.pipeline_batch_v([clips64[i] for i in g], opts, seed=k)
+
+                def hub_batched():
+                    for g in groups:
+                        eng.hubert_batch_v([clips32[i] for i in g])
+
+                report(f"(b) pipeline_batch_v {key}", timed(pipe_batched), t_pipe,
+                       f"{len(groups):2d} passes  padded frames {100 * pad:5.2f} %")
+                res[f"(b) pipeline_batch_v {key}"].update(passes=len(groups), pad_share=round(pad, 4))
+                report(f"(c) hubert_batch_v {key}", timed(hub_batched), t_hub,
+                       f"{len(groups):2d} passes  padded frames {100 * hpad:5.2f} %")
+    print(json.dumps(res))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
