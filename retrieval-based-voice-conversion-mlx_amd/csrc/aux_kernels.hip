@@ -349,28 +349,56 @@ hipError_t noise_conv_add(const float* har, long long har_bs, int stride, int ta
 // ------------------------------------------------------------------ feature x2 upsample + protect blend
 // x2 nearest upsample + protect blend (pipeline.py:344-362): feats = retrieved (or raw) features,
 // feats0 = raw features; v = feats * p + feats0 * (1 - p) with each product and the sum rounded (torch).
+// One launch for all rows (blockIdx.y = row): row b has Lv[b] feature frames -> Tv[b] output frames in out
+// [B][T_max][D], frames from Tv[b] on written as zero. feats / feats0 rows of stride L_max frames, pitchf (optional)
+// rows of stride ldp.
 #pragma clang fp contract(off)
-__global__ void k_up2(const float* feats, const float* feats0, int L, int D, float* out, int T, const float* pitchf,
-                      float protect) {
-  const long long n = (long long)T * D;
+__global__ void k_up2(const float* feats, const float* feats0, Len Lv, int L_max, int D, float* out, Len Tv, int T_max,
+                      const float* pitchf, long long ldp, float protect) {
+  const int b = blockIdx.y;
+  const int L = Lv[b], T = Tv[b];
+  feats += (long long)b * L_max * D;
+  feats0 += (long long)b * L_max * D;
+  out += (long long)b * T_max * D;
+  const long long n = (long long)T_max * D;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int t = (int)(i / D), c = (int)(i % D);
-    const int src = t >> 1 < L ? t >> 1 : L - 1;
-    const float f = feats[(long long)src * D + c];
-    float v = f;
-    if (pitchf) {
-      const float pf = pitchf[t];
-      const float p = pf < 1.f ? protect : (pf > 0.f ? 1.f : pf);
-      v = f * p + feats0[(long long)src * D + c] * (1.f - p);
+    float v = 0.f;
+    if (t < T) {
+      const int src = t >> 1 < L ? t >> 1 : L - 1;
+      const float f = feats[(long long)src * D + c];
+      v = f;
+      if (pitchf) {
+        const float pf = pitchf[b * ldp + t];
+        const float p = pf < 1.f ? protect : (pf > 0.f ? 1.f : pf);
+        v = f * p + feats0[(long long)src * D + c] * (1.f - p);
+      }
     }
     out[i] = v;
   }
 }
 #pragma clang fp contract(on)
-hipError_t upsample2_protect(const float* feats, const float* feats0, int L, int D, float* out, int T,
-                             const float* pitchf, float protect, hipStream_t s) {
-  hipLaunchKernelGGL(k_up2, dim3(nblocks((long long)T * D)), dim3(TB), 0, s, feats, feats0, L, D, out, T, pitchf,
-                     protect);
+hipError_t upsample2_protect(const float* feats, const float* feats0, Len L, int L_max, int D, float* out, Len T,
+                             int T_max, const float* pitchf, long long ldp, float protect, hipStream_t s, int B) {
+  if (B < 1 || T_max < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_up2, dim3(std::min(nblocks((long long)T_max * D), 4096u), B), dim3(TB), 0, s, feats, feats0, L,
+                     L_max, D, out, T, T_max, pitchf, ldp, protect);
+  return hipGetLastError();
+}
+// pitch [B][ldp] / pitchf [B][ldp] -> pc / pf [B][T_max]: row b's first Tv[b] frames, zero from there on
+__global__ void k_pack_pitch(const int32_t* __restrict__ pitch, const float* __restrict__ pitchf, long long ldp,
+                             const int* __restrict__ Tv, int T_max, int32_t* __restrict__ pc, float* __restrict__ pf) {
+  const int b = blockIdx.y;
+  const int T = Tv[b];
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T_max; t += gridDim.x * blockDim.x) {
+    pc[(long long)b * T_max + t] = t < T ? pitch[b * ldp + t] : 0;
+    pf[(long long)b * T_max + t] = t < T ? pitchf[b * ldp + t] : 0.f;
+  }
+}
+hipError_t pack_pitch(const int32_t* pitch, const float* pitchf, long long ldp, const int* Tv, int T_max, int32_t* pc,
+                      float* pf, int B, hipStream_t s) {
+  if (B < 1 || T_max < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pack_pitch, dim3(nblocks(T_max), B), dim3(TB), 0, s, pitch, pitchf, ldp, Tv, T_max, pc, pf);
   return hipGetLastError();
 }
 
@@ -626,10 +654,12 @@ __global__ void k_gn_stats(const float* x, int T, int C, int chunk, double* ws) 
 // grid (C/256, B): sequence b's partials at ws + b*nchunks*C*2, its scale/shift at ss + b*2C
 // grid (C/64, B), block 256 = 64 channels x 4 chunk lanes: lane r sums chunks r, r + 4, ... (coalesced over the 64
 // channels), the 4 lane sums are added in order (one thread per channel looping over all 256 chunks took 66 us)
-__global__ void k_gn_finalize(const double* ws, int nchunks, int T, int C, const float* gamma, const float* beta,
+// (sequence blockIdx.y's statistics are over its own Tv[blockIdx.y] rows)
+__global__ void k_gn_finalize(const double* ws, int nchunks, Len Tv, int C, const float* gamma, const float* beta,
                               float eps, float* ss) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int rl = threadIdx.x >> 6;
+  const int T = Tv[blockIdx.y];
   ws += (long long)blockIdx.y * nchunks * C * 2;
   ss += (long long)blockIdx.y * 2 * C;
   double s = 0.0, q = 0.0;
@@ -678,7 +708,7 @@ hipError_t groupnorm_time_gelu(float* x, int T, int C, const float* gamma, const
   if (C % 4 || B < 1) return hipErrorInvalidValue;
   float* ss = reinterpret_cast<float*>(ws + (size_t)B * nchunks * C * 2);
   hipLaunchKernelGGL(k_gn_stats, dim3((C + 63) / 64, nchunks, B), dim3(256), 0, s, x, T, C, chunk, ws);
-  hipLaunchKernelGGL(k_gn_finalize, dim3((C + 63) / 64, B), dim3(256), 0, s, ws, nchunks, T, C, gamma, beta, eps,
+  hipLaunchKernelGGL(k_gn_finalize, dim3((C + 63) / 64, B), dim3(256), 0, s, ws, nchunks, Len(T), C, gamma, beta, eps,
                      ss);
   const long long n4p = (long long)T * C / 4;
   if (n4p * B >= (1LL << 31)) return hipErrorInvalidValue;
@@ -701,18 +731,14 @@ __device__ __forceinline__ float hconv0_at(const float* __restrict__ xr, const f
   return v;
 }
 // grid (C/64, nchunks, B), block 256 = 64 channels x 4 row lanes: k_gn_stats's partial-sum layout (k_gn_finalize reads it)
-// RAGGED: sequence b has Tv[b] rows of its own (T unused). Its chunks are those of a single-sequence call on it, so
-// its partial sums, and with them its statistics, are that call's bit for bit.
-template <bool RAGGED>
+// Sequence b has Tv[b] rows of its own. Its chunks are those of a single-sequence call on it, so its partial sums, and
+// with them its statistics, are that call's bit for bit.
 __global__ __launch_bounds__(256) void k_hconv0_stats(const float* __restrict__ x, long long ldx, const float* __restrict__ w,
-                                                      int T, const int* __restrict__ Tv, int C, int chunk,
-                                                      double* __restrict__ ws) {
+                                                      Len Tv, int C, double* __restrict__ ws) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int rl = threadIdx.x >> 6;
-  if constexpr (RAGGED) {
-    T = Tv[blockIdx.z];
-    chunk = (T + (int)gridDim.y - 1) / (int)gridDim.y;
-  }
+  const int T = Tv[blockIdx.z];
+  const int chunk = (T + (int)gridDim.y - 1) / (int)gridDim.y;
   const int t0 = blockIdx.y * chunk;
   const int t1 = min(T, t0 + chunk);
   x += (long long)blockIdx.z * ldx;
@@ -737,42 +763,11 @@ __global__ __launch_bounds__(256) void k_hconv0_stats(const float* __restrict__ 
     ws[((long long)blockIdx.y * C + c) * 2 + 1] = q;
   }
 }
-// k_gn_finalize with a divisor per sequence: sequence blockIdx.y's statistics are over its own Tv[blockIdx.y] rows
-__global__ void k_gn_finalize_v(const double* ws, int nchunks, const int* __restrict__ Tv, int C, const float* gamma,
-                                const float* beta, float eps, float* ss) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int rl = threadIdx.x >> 6;
-  const int T = Tv[blockIdx.y];
-  ws += (long long)blockIdx.y * nchunks * C * 2;
-  ss += (long long)blockIdx.y * 2 * C;
-  double s = 0.0, q = 0.0;
-  if (c < C) {
-    for (int k = rl; k < nchunks; k += 4) {
-      s += ws[((long long)k * C + c) * 2];
-      q += ws[((long long)k * C + c) * 2 + 1];
-    }
-  }
-  __shared__ double sp[4][64], qp[4][64];
-  sp[rl][threadIdx.x & 63] = s;
-  qp[rl][threadIdx.x & 63] = q;
-  __syncthreads();
-  if (rl != 0 || c >= C) return;
-  s = ((sp[0][threadIdx.x] + sp[1][threadIdx.x]) + sp[2][threadIdx.x]) + sp[3][threadIdx.x];
-  q = ((qp[0][threadIdx.x] + qp[1][threadIdx.x]) + qp[2][threadIdx.x]) + qp[3][threadIdx.x];
-  const double mean = s / T;
-  double var = q / T - mean * mean;
-  if (var < 0) var = 0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float scale = rstd * gamma[c];
-  ss[c] = scale;
-  ss[C + c] = beta[c] - (float)mean * scale;
-}
 // block C/4 threads (thread = 4 channels, its 40 weights in registers), grid (rows, B): rows t = blockIdx.x + k gridDim.x
-// RAGGED: y is [B][T][C] with T the longest sequence's rows; sequence b's rows from Tv[b] on are written as zero (they
-// read no audio), so every row of y is defined and the strided convs after it see zeros past a sequence's end
-template <bool RAGGED>
-__global__ void k_hconv0_apply(const float* __restrict__ x, long long ldx, const float* __restrict__ w, int T,
-                               const int* __restrict__ Tv, int C, const float* __restrict__ ss, float* __restrict__ y) {
+// y is [B][T][C] with T the longest sequence's rows; sequence b's rows from Tv[b] on are written as zero (they read no
+// audio), so every row of y is defined and the strided convs after it see zeros past a sequence's end
+__global__ void k_hconv0_apply(const float* __restrict__ x, long long ldx, const float* __restrict__ w, int T, Len Tv,
+                               int C, const float* __restrict__ ss, float* __restrict__ y) {
   const int c0 = threadIdx.x * 4;
   x += (long long)blockIdx.y * ldx;
   y += (long long)blockIdx.y * T * C;
@@ -784,10 +779,10 @@ __global__ void k_hconv0_apply(const float* __restrict__ x, long long ldx, const
     for (int k = 0; k < 10; ++k) wr[j][k] = w[(long long)(c0 + j) * 10 + k];
   const f32x4v sc = *reinterpret_cast<const f32x4v*>(ss + c0);
   const f32x4v sh = *reinterpret_cast<const f32x4v*>(ss + C + c0);
-  const int Tb = RAGGED ? Tv[blockIdx.y] : T;
+  const int Tb = Tv[blockIdx.y];
   for (int t = blockIdx.x; t < T; t += gridDim.x) {
     f32x4v v;
-    if (RAGGED && t >= Tb) {
+    if (t >= Tb) {
       v[0] = v[1] = v[2] = v[3] = 0.f;
     } else {
       const float* xr = x + 5LL * t;
@@ -800,32 +795,19 @@ __global__ void k_hconv0_apply(const float* __restrict__ x, long long ldx, const
     *reinterpret_cast<f32x4v*>(y + (long long)t * C + c0) = v;
   }
 }
-hipError_t hubert_conv0_gn_gelu(const float* x, long long ldx, const float* w10, int T, int C, const float* gamma,
-                                const float* beta, float eps, double* ws, float* y, hipStream_t s, int B) {
-  // ws: groupnorm_ws_doubles(C, B); x row b at x + b ldx holds >= 5 (T - 1) + 10 samples; y [B][T][C]
-  if (C % 64 || C > 1024 || B < 1 || B > 65535 || T < 1 || (reinterpret_cast<uintptr_t>(y) & 15)) return hipErrorInvalidValue;
-  const int nchunks = GN_CHUNKS;
-  const int chunk = (T + nchunks - 1) / nchunks;
-  float* ss = reinterpret_cast<float*>(ws + (size_t)B * nchunks * C * 2);
-  hipLaunchKernelGGL(k_hconv0_stats<false>, dim3(C / 64, nchunks, B), dim3(256), 0, s, x, ldx, w10, T, nullptr, C, chunk,
-                     ws);
-  hipLaunchKernelGGL(k_gn_finalize, dim3(C / 64, B), dim3(256), 0, s, ws, nchunks, T, C, gamma, beta, eps, ss);
-  hipLaunchKernelGGL(k_hconv0_apply<false>, dim3((unsigned)std::min(T, 2048), B), dim3(C / 4), 0, s, x, ldx, w10, T,
-                     nullptr, C, ss, y);
-  return hipGetLastError();
-}
-hipError_t hubert_conv0_gn_gelu_v(const float* x, long long ldx, const float* w10, const int* Tv, int T_max, int C,
-                                  const float* gamma, const float* beta, float eps, double* ws, float* y, hipStream_t s,
-                                  int B) {
-  // Tv [B] (device): 1 <= Tv[b] <= T_max, x row b holds >= 5 (Tv[b] - 1) + 10 samples; y [B][T_max][C], every row written
-  if (C % 64 || C > 1024 || B < 1 || B > 65535 || T_max < 1 || !Tv || (reinterpret_cast<uintptr_t>(y) & 15))
+hipError_t hubert_conv0_gn_gelu(const float* x, long long ldx, const float* w10, Len T, int T_max, int C,
+                                const float* gamma, const float* beta, float eps, double* ws, float* y, hipStream_t s,
+                                int B) {
+  // ws: groupnorm_ws_doubles(C, B); 1 <= T[b] <= T_max, x row b at x + b ldx holds >= 5 (T[b] - 1) + 10 samples;
+  // y [B][T_max][C], every row written
+  if (C % 64 || C > 1024 || B < 1 || B > 65535 || T_max < 1 || (reinterpret_cast<uintptr_t>(y) & 15))
     return hipErrorInvalidValue;
   const int nchunks = GN_CHUNKS;
   float* ss = reinterpret_cast<float*>(ws + (size_t)B * nchunks * C * 2);
-  hipLaunchKernelGGL(k_hconv0_stats<true>, dim3(C / 64, nchunks, B), dim3(256), 0, s, x, ldx, w10, 0, Tv, C, 0, ws);
-  hipLaunchKernelGGL(k_gn_finalize_v, dim3(C / 64, B), dim3(256), 0, s, ws, nchunks, Tv, C, gamma, beta, eps, ss);
-  hipLaunchKernelGGL(k_hconv0_apply<true>, dim3((unsigned)std::min(T_max, 2048), B), dim3(C / 4), 0, s, x, ldx, w10,
-                     T_max, Tv, C, ss, y);
+  hipLaunchKernelGGL(k_hconv0_stats, dim3(C / 64, nchunks, B), dim3(256), 0, s, x, ldx, w10, T, C, ws);
+  hipLaunchKernelGGL(k_gn_finalize, dim3(C / 64, B), dim3(256), 0, s, ws, nchunks, T, C, gamma, beta, eps, ss);
+  hipLaunchKernelGGL(k_hconv0_apply, dim3((unsigned)std::min(T_max, 2048), B), dim3(C / 4), 0, s, x, ldx, w10, T_max, T,
+                     C, ss, y);
   return hipGetLastError();
 }
 
@@ -1162,12 +1144,13 @@ size_t filtfilt_ws_doubles(long long n, int order) {
 
 // peak normalisation (pipeline.py:550-552): m = max|x| / 0.99 ; if m > 1: x /= m. Fused with the trim copy
 // (pipeline.py:494 audio_opt slices): dst = src / m read from the un-trimmed buffer. Two launches for all B rows
-// and no fill: each absmax block writes its own maximum to ws[row][block], the scale pass reduces those <= 256
-// partials per block before it scales (no atomics, nothing to zero between calls).
+// (row b's first nv[b] samples) and no fill: each absmax block writes its own maximum to ws[row][block], the scale
+// pass reduces those <= 256 partials per block before it scales (no atomics, nothing to zero between calls).
 constexpr int PEAK_BLOCKS = 256;
-__global__ void k_absmax(const float* x, long long n, long long ldx, float* part) {
+__global__ void k_absmax(const float* x, Len nv, long long ldx, float* part) {
   __shared__ float wm[TB / 64];
   x += blockIdx.y * ldx;
+  const long long n = nv[blockIdx.y];
   float m = 0.f;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     m = fmaxf(m, fabsf(x[i]));
@@ -1179,11 +1162,12 @@ __global__ void k_absmax(const float* x, long long n, long long ldx, float* part
     part[blockIdx.y * PEAK_BLOCKS + blockIdx.x] = m;
   }
 }
-__global__ void k_peak_scale(const float* src, long long lds, float* dst, long long ldd, long long n, const float* part,
+__global__ void k_peak_scale(const float* src, long long lds, float* dst, long long ldd, Len nv, const float* part,
                              int nparts) {
   __shared__ float wm[TB / 64];
   src += blockIdx.y * lds;
   dst += blockIdx.y * ldd;
+  const long long n = nv[blockIdx.y];
   float m = threadIdx.x < nparts ? part[blockIdx.y * PEAK_BLOCKS + threadIdx.x] : 0.f;
   m = warp_max(m);
   if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
@@ -1196,12 +1180,13 @@ __global__ void k_peak_scale(const float* src, long long lds, float* dst, long l
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     dst[i] = scale ? src[i] / m : src[i];
 }
-hipError_t peak_normalize(const float* src, float* dst, long long n, float* ws, hipStream_t s, int B, long long lds,
-                          long long ldd) {
-  if (n <= 0 || B < 1) return hipSuccess;
-  const int nparts = (int)std::min<long long>(PEAK_BLOCKS, (n + TB - 1) / TB);
+hipError_t peak_normalize(const float* src, long long lds, float* dst, long long ldd, Len n, long long n_max, float* ws,
+                          hipStream_t s, int B) {
+  if (n_max <= 0 || B < 1) return hipSuccess;
+  if (n_max >= (1LL << 31)) return hipErrorInvalidValue;
+  const int nparts = (int)std::min<long long>(PEAK_BLOCKS, (n_max + TB - 1) / TB);
   hipLaunchKernelGGL(k_absmax, dim3(nparts, B), dim3(TB), 0, s, src, n, lds, ws);
-  hipLaunchKernelGGL(k_peak_scale, dim3(std::min(nblocks(n), 4096u), B), dim3(TB), 0, s, src, lds, dst, ldd, n, ws,
+  hipLaunchKernelGGL(k_peak_scale, dim3(std::min(nblocks(n_max), 4096u), B), dim3(TB), 0, s, src, lds, dst, ldd, n, ws,
                      nparts);
   return hipGetLastError();
 }
@@ -1323,8 +1308,18 @@ hipError_t split_points(const double* x, long long n, int window, long long t_ce
 // frame/2, mean |x|^2 per frame, sqrt) of source and target, both linearly interpolated
 // (F.interpolate mode='linear', align_corners=False) to the target length, then
 // y *= rms1^(1-rate) * max(rms2, 1e-6)^(rate-1). One block per RMS frame, fp64 sums.
+// One launch set for all rows (blockIdx.y = row): row b of x (stride ld) has nv[b] samples and 1 + nv[b] / hop frames,
+// written at rms + b*ld_rms behind the row's 1 + n_before[b] / hop_before source frames (hop_before 0: none before).
+// rate (optional): a row whose rate is exactly 1 is skipped.
 template <class T>
-__global__ void k_rms_frames(const T* x, long long n, int frame, int hop, float* rms) {
+__global__ void k_rms_frames(const T* x, long long ld, Len nv, int frame, int hop, float* rms, long long ld_rms,
+                             Len n_before, int hop_before, const float* __restrict__ rate) {
+  const int b = blockIdx.y;
+  if (rate && rate[b] == 1.f) return;
+  const long long n = nv[b];
+  if ((long long)blockIdx.x >= 1 + n / hop) return;
+  x += b * ld;
+  rms += b * ld_rms + (hop_before ? 1 + n_before[b] / hop_before : 0);
   const long long start = (long long)blockIdx.x * hop - frame / 2;
   double acc = 0.0;
   for (int j = threadIdx.x; j < frame; j += blockDim.x) {
@@ -1377,208 +1372,13 @@ __device__ __forceinline__ float interp_linear(const float* r, int n_in, long lo
   l1 = fminf(fmaxf(l1, 0.f), 1.f);
   return (1.f - l1) * r[i0] + l1 * r[i1];
 }
-__global__ void k_apply_rms(float* y, long long n, const float* r1, int n1, const float* r2, int n2, float rate) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float a = interp_linear(r1, n1, i, n);
-    const float b = fmaxf(interp_linear(r2, n2, i, n), 1e-6f);
-    y[i] = y[i] * (powf(a, 1.f - rate) * powf(b, rate - 1.f));
-  }
-}
-int rms_frame_count(long long n, int sr) { return (int)(1 + n / (sr / 2)); }
-hipError_t change_rms(const double* src, long long n_src, int sr_src, float* y, long long n_y, int sr_y, float rate,
-                      float* ws, hipStream_t s) {
-  const int n1 = rms_frame_count(n_src, sr_src), n2 = rms_frame_count(n_y, sr_y);
-  hipLaunchKernelGGL(k_rms_frames<double>, dim3(n1), dim3(TB), 0, s, src, n_src, sr_src / 2 * 2, sr_src / 2, ws);
-  hipLaunchKernelGGL(k_rms_frames<float>, dim3(n2), dim3(TB), 0, s, (const float*)y, n_y, sr_y / 2 * 2, sr_y / 2,
-                     ws + n1);
-  hipLaunchKernelGGL(k_apply_rms, dim3(nblocks(n_y)), dim3(TB), 0, s, y, n_y, ws, n1, ws + n1, n2, rate);
-  return hipGetLastError();
-}
-// change_rms with a float32 source (the streaming path's 16 kHz convert buffer, rvc/realtime/pipeline.py:303-310) over B
-// rows in one launch set (blockIdx.y = row): src rows of stride ld_src, y rows of stride ld_y, each row with its own
-// rate [B] and its own n1 + n2 floats of ws. Rows whose rate is exactly 1 are left untouched. The arithmetic per row
-// is k_rms_frames<float> / k_apply_rms.
-__global__ void k_rms_frames_rows(const float* x, long long ld, long long n, int frame, int hop, float* rms,
-                                  int ld_rms, const float* __restrict__ rate) {
+// row b: its source frames at ws + b*ld_ws, then its target frames; rate_v (optional): the row's own rate, exactly 1 =
+// the row is left untouched
+__global__ void k_apply_rms(float* y, long long ld, Len n_y, const float* ws, long long ld_ws, Len n_src, int hop_src,
+                            int hop_y, float rate, const float* __restrict__ rate_v) {
   const int b = blockIdx.y;
-  if (rate[b] == 1.f) return;
-  x += b * ld;
-  const long long start = (long long)blockIdx.x * hop - frame / 2;
-  double acc = 0.0;
-  for (int j = threadIdx.x; j < frame; j += blockDim.x) {
-    const long long q = start + j;
-    if (q >= 0 && q < n) {
-      const double v = (double)x[q];
-      acc += v * v;
-    }
-  }
-  __shared__ double red[TB];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = TB / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) rms[(long long)b * ld_rms + blockIdx.x] = (float)sqrt(red[0] / frame);
-}
-__global__ void k_apply_rms_rows(float* y, long long ld, long long n, const float* ws, int n1, int n2,
-                                 const float* __restrict__ rate_v) {
-  const int b = blockIdx.y;
-  const float rate = rate_v[b];
-  if (rate == 1.f) return;
-  y += b * ld;
-  const float* r1 = ws + (long long)b * (n1 + n2);
-  const float* r2 = r1 + n1;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float a = interp_linear(r1, n1, i, n);
-    const float c = fmaxf(interp_linear(r2, n2, i, n), 1e-6f);
-    y[i] = y[i] * (powf(a, 1.f - rate) * powf(c, rate - 1.f));
-  }
-}
-hipError_t change_rms_f32src_rows(const float* src, long long ld_src, long long n_src, int sr_src, float* y,
-                                  long long ld_y, long long n_y, int sr_y, const float* rate, float* ws, int B,
-                                  hipStream_t s) {
-  if (B < 1) return hipSuccess;
-  const int n1 = rms_frame_count(n_src, sr_src), n2 = rms_frame_count(n_y, sr_y);
-  hipLaunchKernelGGL(k_rms_frames_rows, dim3(n1, B), dim3(TB), 0, s, src, ld_src, n_src, sr_src / 2 * 2, sr_src / 2, ws,
-                     n1 + n2, rate);
-  hipLaunchKernelGGL(k_rms_frames_rows, dim3(n2, B), dim3(TB), 0, s, (const float*)y, ld_y, n_y, sr_y / 2 * 2, sr_y / 2,
-                     ws + n1, n1 + n2, rate);
-  hipLaunchKernelGGL(k_apply_rms_rows, dim3(nblocks(n_y), B), dim3(TB), 0, s, y, ld_y, n_y, ws, n1, n2, rate);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ ragged batches: the per-row tail stages
-// The stages of the batched pipeline around the synthesizer for rows of different lengths: one launch set for all rows
-// (blockIdx.y = row), each row's length read from a device array. A row's arithmetic is the single-row kernel's
-// (k_up2, k_absmax / k_peak_scale, k_rms_frames / k_apply_rms), so its valid elements are that kernel's bit for bit.
-
-// k_up2 over rows of L[b] feature frames -> T[b] output frames in out [B][T_max][D]; frames from T[b] on are written
-// as zero. feats / feats0 rows of stride L_max frames, pitchf (optional) rows of stride ldp.
-#pragma clang fp contract(off)
-__global__ void k_up2_v(const float* feats, const float* feats0, const int* __restrict__ Lv, int L_max, int D, float* out,
-                        const int* __restrict__ Tv, int T_max, const float* pitchf, long long ldp, float protect) {
-  const int b = blockIdx.y;
-  const int L = Lv[b], T = Tv[b];
-  feats += (long long)b * L_max * D;
-  feats0 += (long long)b * L_max * D;
-  out += (long long)b * T_max * D;
-  const long long n = (long long)T_max * D;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int t = (int)(i / D), c = (int)(i % D);
-    float v = 0.f;
-    if (t < T) {
-      const int src = t >> 1 < L ? t >> 1 : L - 1;
-      const float f = feats[(long long)src * D + c];
-      v = f;
-      if (pitchf) {
-        const float pf = pitchf[b * ldp + t];
-        const float p = pf < 1.f ? protect : (pf > 0.f ? 1.f : pf);
-        v = f * p + feats0[(long long)src * D + c] * (1.f - p);
-      }
-    }
-    out[i] = v;
-  }
-}
-#pragma clang fp contract(on)
-hipError_t upsample2_protect_v(const float* feats, const float* feats0, const int* Lv, int L_max, int D, float* out,
-                               const int* Tv, int T_max, const float* pitchf, long long ldp, float protect, int B,
-                               hipStream_t s) {
-  if (B < 1 || T_max < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_up2_v, dim3(std::min(nblocks((long long)T_max * D), 4096u), B), dim3(TB), 0, s, feats, feats0, Lv,
-                     L_max, D, out, Tv, T_max, pitchf, ldp, protect);
-  return hipGetLastError();
-}
-// pitch [B][ldp] / pitchf [B][ldp] -> pc / pf [B][T_max]: row b's first Tv[b] frames, zero from there on
-__global__ void k_pack_pitch_v(const int32_t* __restrict__ pitch, const float* __restrict__ pitchf, long long ldp,
-                               const int* __restrict__ Tv, int T_max, int32_t* __restrict__ pc, float* __restrict__ pf) {
-  const int b = blockIdx.y;
-  const int T = Tv[b];
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T_max; t += gridDim.x * blockDim.x) {
-    pc[(long long)b * T_max + t] = t < T ? pitch[b * ldp + t] : 0;
-    pf[(long long)b * T_max + t] = t < T ? pitchf[b * ldp + t] : 0.f;
-  }
-}
-hipError_t pack_pitch_v(const int32_t* pitch, const float* pitchf, long long ldp, const int* Tv, int T_max, int32_t* pc,
-                        float* pf, int B, hipStream_t s) {
-  if (B < 1 || T_max < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_pack_pitch_v, dim3(nblocks(T_max), B), dim3(TB), 0, s, pitch, pitchf, ldp, Tv, T_max, pc, pf);
-  return hipGetLastError();
-}
-// peak_normalize over rows of nv[b] samples (n_max the longest): every row's PEAK_BLOCKS partials are written
-__global__ void k_absmax_v(const float* x, const int* __restrict__ nv, long long ldx, float* part) {
-  __shared__ float wm[TB / 64];
-  x += blockIdx.y * ldx;
-  const long long n = nv[blockIdx.y];
-  float m = 0.f;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf(x[i]));
-  m = warp_max(m);
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmaxf(m, wm[w]);
-    part[blockIdx.y * PEAK_BLOCKS + blockIdx.x] = m;
-  }
-}
-__global__ void k_peak_scale_v(const float* src, long long lds, float* dst, long long ldd, const int* __restrict__ nv,
-                               const float* part, int nparts) {
-  __shared__ float wm[TB / 64];
-  src += blockIdx.y * lds;
-  dst += blockIdx.y * ldd;
-  const long long n = nv[blockIdx.y];
-  float m = threadIdx.x < nparts ? part[blockIdx.y * PEAK_BLOCKS + threadIdx.x] : 0.f;
-  m = warp_max(m);
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = wm[0];
-  for (int w = 1; w < TB / 64; ++w) m = fmaxf(m, wm[w]);
-  m = m / 0.99f;
-  const bool scale = m > 1.f;
-  if (!scale && src == dst) return;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    dst[i] = scale ? src[i] / m : src[i];
-}
-hipError_t peak_normalize_v(const float* src, long long lds, float* dst, long long ldd, const int* nv, long long n_max,
-                            float* ws, int B, hipStream_t s) {
-  if (n_max <= 0 || B < 1) return hipSuccess;
-  const int nparts = (int)std::min<long long>(PEAK_BLOCKS, (n_max + TB - 1) / TB);
-  hipLaunchKernelGGL(k_absmax_v, dim3(nparts, B), dim3(TB), 0, s, src, nv, lds, ws);
-  hipLaunchKernelGGL(k_peak_scale_v, dim3(std::min(nblocks(n_max), 4096u), B), dim3(TB), 0, s, src, lds, dst, ldd, nv,
-                     ws, nparts);
-  return hipGetLastError();
-}
-// change_rms over rows: source row b (fp64, stride ld_src) of n_src[b] samples, target row b of n_y[b]; row b's RMS
-// frames (1 + n / (sr / 2) of either side, as rms_frame_count) at ws + b*ld_ws, the source's first, then the target's
-template <class T>
-__global__ void k_rms_frames_v(const T* x, long long ld, const int* __restrict__ nv, int frame, int hop, float* rms,
-                               long long ld_rms, const int* __restrict__ n_before, int hop_before) {
-  const int b = blockIdx.y;
-  const long long n = nv[b];
-  if ((long long)blockIdx.x >= 1 + n / hop) return;
-  x += b * ld;
-  rms += b * ld_rms + (n_before ? 1 + n_before[b] / hop_before : 0);
-  const long long start = (long long)blockIdx.x * hop - frame / 2;
-  double acc = 0.0;
-  for (int j = threadIdx.x; j < frame; j += blockDim.x) {
-    const long long q = start + j;
-    if (q >= 0 && q < n) {
-      const double v = (double)x[q];
-      acc += v * v;
-    }
-  }
-  __shared__ double red[TB];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = TB / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) rms[blockIdx.x] = (float)sqrt(red[0] / frame);
-}
-__global__ void k_apply_rms_v(float* y, long long ld, const int* __restrict__ n_y, const float* ws, long long ld_ws,
-                              const int* __restrict__ n_src, int hop_src, int hop_y, float rate) {
-  const int b = blockIdx.y;
+  if (rate_v) rate = rate_v[b];
+  if (rate_v && rate == 1.f) return;
   const long long n = n_y[b];
   const int n1 = 1 + n_src[b] / hop_src, n2 = (int)(1 + n / hop_y);
   y += b * ld;
@@ -1590,19 +1390,26 @@ __global__ void k_apply_rms_v(float* y, long long ld, const int* __restrict__ n_
     y[i] = y[i] * (powf(a, 1.f - rate) * powf(c, rate - 1.f));
   }
 }
-hipError_t change_rms_v(const double* src, long long ld_src, const int* n_src, long long n_src_max, int sr_src, float* y,
-                        long long ld_y, const int* n_y, long long n_y_max, int sr_y, float rate, float* ws, int B,
-                        hipStream_t s) {
+int rms_frame_count(long long n, int sr) { return (int)(1 + n / (sr / 2)); }
+template <class S>
+hipError_t change_rms(const S* src, long long ld_src, Len n_src, long long n_src_max, int sr_src, float* y,
+                      long long ld_y, Len n_y, long long n_y_max, int sr_y, float rate, const float* rate_v, float* ws,
+                      hipStream_t s, int B) {
   if (B < 1) return hipSuccess;
+  if (n_src_max >= (1LL << 31) || n_y_max >= (1LL << 31)) return hipErrorInvalidValue;
   const int n1 = rms_frame_count(n_src_max, sr_src), n2 = rms_frame_count(n_y_max, sr_y);
   const long long ld_ws = n1 + n2;
-  hipLaunchKernelGGL(k_rms_frames_v<double>, dim3(n1, B), dim3(TB), 0, s, src, ld_src, n_src, sr_src / 2 * 2, sr_src / 2,
-                     ws, ld_ws, nullptr, 1);
-  hipLaunchKernelGGL(k_rms_frames_v<float>, dim3(n2, B), dim3(TB), 0, s, (const float*)y, ld_y, n_y, sr_y / 2 * 2,
-                     sr_y / 2, ws, ld_ws, n_src, sr_src / 2);
-  hipLaunchKernelGGL(k_apply_rms_v, dim3(std::min(nblocks(n_y_max), 4096u), B), dim3(TB), 0, s, y, ld_y, n_y, ws, ld_ws,
-                     n_src, sr_src / 2, sr_y / 2, rate);
+  hipLaunchKernelGGL(k_rms_frames<S>, dim3(n1, B), dim3(TB), 0, s, src, ld_src, n_src, sr_src / 2 * 2, sr_src / 2, ws,
+                     ld_ws, Len(0), 0, rate_v);
+  hipLaunchKernelGGL(k_rms_frames<float>, dim3(n2, B), dim3(TB), 0, s, (const float*)y, ld_y, n_y, sr_y / 2 * 2,
+                     sr_y / 2, ws, ld_ws, n_src, sr_src / 2, rate_v);
+  hipLaunchKernelGGL(k_apply_rms, dim3(std::min(nblocks(n_y_max), 4096u), B), dim3(TB), 0, s, y, ld_y, n_y, ws, ld_ws,
+                     n_src, sr_src / 2, sr_y / 2, rate, rate_v);
   return hipGetLastError();
 }
+template hipError_t change_rms<double>(const double*, long long, Len, long long, int, float*, long long, Len, long long,
+                                       int, float, const float*, float*, hipStream_t, int);
+template hipError_t change_rms<float>(const float*, long long, Len, long long, int, float*, long long, Len, long long,
+                                      int, float, const float*, float*, hipStream_t, int);
 
 }  // namespace rvcx

@@ -631,19 +631,17 @@ int rvcx_workspace_bytes(rvcx_ctx* ctx, int B, int64_t n, const rvcx_pipeline_op
           pipeline_forward_ex(*ctx, static_cast<const double*>(audio.p), n, o, nullptr, nullptr, 0,
                               static_cast<float*>(out.p), cap, nullptr, s);
         } else {
+          // B rows of n samples in the batched pipeline's sizing form (Ctx::sizing_plan): run as a ragged batch (masks,
+          // the gathered RMVPE group and one single-row RMVPE forward), whose regions hold the equal-length routes too
           std::vector<int32_t> sids((size_t)B, o.sid);
-          pipeline_forward_batch(*ctx, static_cast<const double*>(audio.p), n, n, B, o, sids.data(), nullptr, nullptr, 0,
-                                 static_cast<float*>(out.p), cap, nullptr, nullptr, s);
-          // rvcx_pipeline_batch_v on B rows of n samples, run as a ragged batch (masks, the row-length arrays, the
-          // gathered RMVPE group and one single-row RMVPE forward): the regions it takes beyond the call above
           std::vector<int64_t> nv((size_t)B, n), no((size_t)B);
-          pipeline_forward_batch_v(*ctx, static_cast<const double*>(audio.p), nv.data(), n, B, o, sids.data(), nullptr,
-                                   nullptr, 0, static_cast<float*>(out.p), cap, no.data(), nullptr, 0, s);
+          pipeline_forward_rows(*ctx, static_cast<const double*>(audio.p), nv.data(), n, B, o, sids.data(), nullptr,
+                                nullptr, 0, static_cast<float*>(out.p), cap, no.data(), nullptr, 0, nullptr, s);
         }
         RVCX_HIP(hipStreamSynchronize(s));
         int64_t carved = (int64_t)ctx->carved;
         if (B > 1) {
-          // a ragged batch walks its rows' front ends in another order than the calls above, and the split-K slab all
+          // a ragged batch walks its rows' front ends in another order than the call above, and the split-K slab all
           // convs share is regrown whenever a later conv needs a larger one: room for one regrowth per row and stream
           for (const char* slab : {"conv.splitk", "conv.splitk.aux"})
             if (ctx->ws.count(slab) && ctx->ws[slab]) carved += (int64_t)B * (int64_t)ctx->ws[slab]->bytes;
@@ -1341,7 +1339,7 @@ int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n
     if (!d_audio || !n || !opts || !sids || !d_out || !n_out || B < 1)
       throw Error(RVCX_E_INVALID, "rvcx_pipeline_batch_v: bad arguments");
     set_device(ctx);
-    pipeline_forward_batch_v(*ctx, d_audio, n, lda, B, *opts, sids, d_eps_z, d_eps_src, seed, d_out, ldo, n_out, d_f0,
-                             ldf, static_cast<hipStream_t>(stream));
+    pipeline_forward_rows(*ctx, d_audio, n, lda, B, *opts, sids, d_eps_z, d_eps_src, seed, d_out, ldo, n_out, d_f0, ldf,
+                          nullptr, static_cast<hipStream_t>(stream));
   });
 }

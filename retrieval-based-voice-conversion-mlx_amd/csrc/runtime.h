@@ -454,11 +454,13 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
 int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t lda, int B, const rvcx_pipeline_opts& o,
                                const int32_t* sids, const float* eps_z, const float* eps_src, uint64_t seed,
                                float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s);
-// B utterances of nv[b] samples (host array), rows of stride lda: out row b n_out[b] samples, f0_out row b at stride ldf
-void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
-                              const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
-                              uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
-                              hipStream_t s);
+// The batched pipeline. B utterances of nv[b] samples (host array), rows of stride lda: out row b n_out[b] samples,
+// f0_out row b at stride ldf; hidden_out (RMVPE's salience) only for rows of one length. pipeline_forward_batch above
+// is this with every nv[b] = n.
+void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
+                           const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
+                           uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
+                           float* hidden_out, hipStream_t s);
 rvcx_pipeline_opts default_pipeline_opts();
 int proposed_key(const std::vector<double>& f0, double threshold);
 int64_t hubert_frames(int64_t n);  // HuBERT output rows for n samples (0 when too short)
@@ -474,7 +476,7 @@ bool conv_routes_wsb16(Ctx& c, const ConvArgs& a);
 // marks a synth_forward call whose rows all have the full length T (Ctx::synth_full_lengths) for its lifetime
 struct ScopedFullLengths {
   Ctx& c;
-  explicit ScopedFullLengths(Ctx& cc) : c(cc) { c.synth_full_lengths = true; }
+  explicit ScopedFullLengths(Ctx& cc, bool full = true) : c(cc) { c.synth_full_lengths = full; }
   ~ScopedFullLengths() { c.synth_full_lengths = false; }
 };
 void join_aux(Ctx& c, hipStream_t s, hipStream_t ax);

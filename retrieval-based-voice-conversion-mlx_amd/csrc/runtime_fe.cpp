@@ -112,6 +112,7 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
   float* b = c.buf<float>("hb.b", (size_t)B * T[2] * HCONV, s);
   double* gnws = c.buf<double>("hb.gnws", groupnorm_ws_doubles(HCONV, B), s);
   float* mask = nullptr;
+  Len T1((int)T[1]);  // conv0 frames per sequence
   if (nv) {
     // per-sequence conv0 frames | output frames on device, and the [B][L] mask of valid output frames
     std::vector<int32_t> hl(2 * (size_t)B);
@@ -126,15 +127,12 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
     RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
     mask = c.buf<float>("hb.mask", (size_t)BL, s);
     check(seq_mask(dl + B, mask, B, L, s), "hubert_mask");
-    check(hubert_conv0_gn_gelu_v(audio, lda, c.W("hb.conv0"), dl, (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"),
-                                 1e-5f, gnws, a, s, B),
-          "hubert_conv0_v");
-  } else {
-    // conv0 -> GroupNorm(512, 512) -> GELU in three launches (statistics, finalize, apply), the conv recomputed by each
-    check(hubert_conv0_gn_gelu(audio, lda, c.W("hb.conv0"), (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"), 1e-5f,
-                               gnws, a, s, B),
-          "hubert_conv0");
+    T1 = Len(dl);
   }
+  // conv0 -> GroupNorm(512, 512) -> GELU in three launches (statistics, finalize, apply), the conv recomputed by each
+  check(hubert_conv0_gn_gelu(audio, lda, c.W("hb.conv0"), T1, (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"), 1e-5f,
+                             gnws, a, s, B),
+        "hubert_conv0");
   float* cur = a;
   float* nxt = b;
   for (int i = 1; i < 7; ++i) {

@@ -184,7 +184,7 @@ int64_t vc_forward(Ctx& c, const float* audio, int64_t n, const int32_t* pitch, 
     fx = fr;
   }
   float* phone = c.buf<float>("vc.phone", (size_t)T * E, s);
-  check(upsample2_protect(fx, feats, (int)L, E, phone, T, protect < 0.5f ? pitchf : nullptr, protect, s),
+  check(upsample2_protect(fx, feats, (int)L, (int)L, E, phone, T, T, protect < 0.5f ? pitchf : nullptr, 0, protect, s),
         "upsample");
   int32_t* lens = c.buf<int32_t>("vc.len", 4, s);
   set_i32_once(c, "vc.len.T", lens, T, s);
@@ -267,27 +267,34 @@ static void f0_row(Ctx& c, const rvcx_pipeline_opts& o, const float* audio, int6
   }
 }
 
-// get_f0's adjustments (pipeline.py:248-291) of f0 [B][F] in place, then the coarse / fine pitch per row: autotune, or
-// the proposed-pitch key of each row (one device -> host copy and sync), then f0_post with the row's shift
-static void pitch_from_f0(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B, int64_t F, int32_t* pitch,
-                          float* pitchf, double* f0_out, hipStream_t s) {
+// get_f0's adjustments (pipeline.py:248-291) of f0 in place, then the coarse / fine pitch per row, for rows of Fv[b]
+// frames at stride ld (f0, pitch, pitchf; f0_out rows at stride ldf): autotune (one launch when the rows lie back to
+// back), or the proposed-pitch key of each row (one device -> host copy and sync), then f0_post with the row's shift
+static void pitch_from_f0(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B, const int64_t* Fv, int64_t ld,
+                          int32_t* pitch, float* pitchf, double* f0_out, int64_t ldf, hipStream_t s) {
   std::vector<double> shift(B, o.pitch);
   if (o.f0_autotune) {
-    check(f0_autotune(f0, (int)(B * F), o.f0_autotune_strength, o.mlx_semantics ? 1 : 0, s), "f0_autotune");
+    const int skip = o.mlx_semantics ? 1 : 0;
+    if (std::all_of(Fv, Fv + B, [&](int64_t F) { return F == ld; })) {
+      check(f0_autotune(f0, (int)(B * ld), o.f0_autotune_strength, skip, s), "f0_autotune");
+    } else {
+      for (int b = 0; b < B; ++b)
+        check(f0_autotune(f0 + (size_t)b * ld, (int)Fv[b], o.f0_autotune_strength, skip, s), "f0_autotune");
+    }
     if (!o.mlx_semantics) std::fill(shift.begin(), shift.end(), 0.0);  // rvc/: autotune replaces the shift (:248-279)
   } else if (o.proposed_pitch) {
-    std::vector<double> h((size_t)B * F);
+    std::vector<double> h((size_t)B * ld);
     RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
     RVCX_HIP(hipStreamSynchronize(s));
     c.check_device_status();
     for (int b = 0; b < B; ++b) {
-      std::vector<double> one(h.begin() + (size_t)b * F, h.begin() + (size_t)(b + 1) * F);
+      std::vector<double> one(h.begin() + (size_t)b * ld, h.begin() + (size_t)b * ld + Fv[b]);
       shift[b] = o.pitch + proposed_key(one, o.proposed_pitch_threshold);
     }
   }
   for (int b = 0; b < B; ++b)
-    check(f0_post(f0 + (size_t)b * F, (int)F, std::pow(2.0, shift[b] / 12.0), pitch + (size_t)b * F,
-                  pitchf + (size_t)b * F, f0_out ? f0_out + (size_t)b * F : nullptr, s),
+    check(f0_post(f0 + (size_t)b * ld, (int)Fv[b], std::pow(2.0, shift[b] / 12.0), pitch + (size_t)b * ld,
+                  pitchf + (size_t)b * ld, f0_out ? f0_out + (size_t)b * ldf : nullptr, s),
           "f0_post");
 }
 
@@ -437,7 +444,7 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
   }
   pitch = c.buf<int32_t>("pl.pitch", (size_t)F, s);
   pitchf = c.buf<float>("pl.pitchf", (size_t)F, s);
-  pitch_from_f0(c, o, f0, 1, F, pitch, pitchf, f0_out, s);
+  pitch_from_f0(c, o, f0, 1, &F, F, pitch, pitchf, f0_out, F, s);
   } else {
     auto rest = std::move(c.before_gru);
     c.before_gru = nullptr;
@@ -506,151 +513,23 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
   if (o.volume_envelope != 1.0) {
     const int n1 = rms_frame_count(n, 16000), n2 = rms_frame_count(written, c.scfg.sr);
     float* rws = c.buf<float>("pl.rms", (size_t)(n1 + n2), s);
-    check(change_rms(filtered, n, 16000, out, written, c.scfg.sr, (float)o.volume_envelope, rws, s), "change_rms");
+    check(change_rms(filtered, n, (int)n, n, 16000, out, written, (int)written, written, c.scfg.sr,
+                     (float)o.volume_envelope, nullptr, rws, s),
+          "change_rms");
   }
   float* mx = c.buf<float>("pl.max", peak_normalize_ws_floats(1), s);
-  check(peak_normalize(trimmed, out, written, mx, s), "peak_normalize");
+  check(peak_normalize(trimmed, written, out, written, (int)written, written, mx, s), "peak_normalize");
   return written;
 }
 
-// Batched offline conversion (config C4): B equal-length utterances, each no longer than t_max (one chunk
-// each, pipeline.py:486-512 with opt_ts empty), through one batched RMVPE, one batched HuBERT and one
-// batched Synthesizer.infer. Per utterance the result is Pipeline.pipeline's; the batch only widens
-// every GEMM (B x rows). audio row b at audio + b*lda (fp64); out row b at out + b*ldo, n_out samples each.
-int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t lda, int B, const rvcx_pipeline_opts& o,
-                               const int32_t* sids, const float* eps_z, const float* eps_src, uint64_t seed,
-                               float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s) {
-  if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
-  check_pipeline_opts(c, o, n);
-  if (o.t_max > 0 && n + 160 > o.t_max)
-    throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
-  for (int b = 0; b < B; ++b)
-    if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
-  const int64_t W = 160;
-  const int64_t m = n + 2 * o.t_pad;
-  const int64_t ldm = (m + 7) & ~int64_t(7);
-  const int E = c.scfg.emb_dim, upp = c.scfg.upp();
-  // 1. zero-phase high-pass + reflect pad per utterance (pipeline.py:439, :459)
-  float* pad32 = c.buf<float>("pb.pad32", (size_t)B * ldm, s);
-  double* pad64 = c.buf<double>("pb.pad64", (size_t)B * m, s);
-  for (int b = 0; b < B; ++b)
-    highpass_pad(c, audio + (size_t)b * lda, n, o.t_pad, pad64 + (size_t)b * m, pad32 + (size_t)b * ldm, s);
-  // 2. f0 (batched RMVPE) + get_f0 adjustments per utterance (pipeline.py:462-472, :248-291)
-  const int64_t F = 1 + m / W, T = m / W;
-  double* f0 = c.buf<double>("pb.f0", (size_t)B * F, s);
-  const int64_t L = hubert_frames(m);
-  float* feats = c.buf<float>("pb.feats", (size_t)B * L * E, s);
-  hipStream_t ax = fork_aux(c, s);  // batched HuBERT beside batched RMVPE
-  hubert_forward_b(c, pad32, m, ldm, B, hubert_version_for(c), feats, L, ax);
-  const bool guided = c.scfg.f0;  // no RMVPE, pitch or protect without pitch guidance (pipeline.py:324-365)
-  int32_t* pitch = nullptr;
-  float* pitchf = nullptr;
-  if (guided) {
-  if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
-    for (int b = 0; b < B; ++b) f0_row(c, o, pad32 + (size_t)b * ldm, m, f0 + (size_t)b * F, F, "pb.f0f", s);
-  } else {
-    rmvpe_forward_b(c, pad32, m, ldm, B, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, hidden_out, s);
-  }
-  pitch = c.buf<int32_t>("pb.pitch", (size_t)B * F, s);
-  pitchf = c.buf<float>("pb.pitchf", (size_t)B * F, s);
-  pitch_from_f0(c, o, f0, B, F, pitch, pitchf, f0_out, s);
-  } else if (f0_out) {
-    RVCX_HIP(hipMemsetAsync(f0_out, 0, sizeof(double) * (size_t)B * F, s));
-  }
-  // 3. batched HuBERT, retrieval, x2 upsample + protect (pipeline.py:327-362)
-  join_aux(c, s, ax);
-  const int64_t Tv = std::min<int64_t>(T, 2 * L);
-  if (Tv <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch: input shorter than one frame");
-  const float* fx = feats;
-  if (o.index_rate > 0) {
-    if (c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension mismatch");
-    float* fr = c.buf<float>("pb.feats_idx", (size_t)B * L * E, s);
-    index_retrieve(c, feats, B * L, E, o.index_rate, fr, s);  // row-wise: the B sequences stack
-    fx = fr;
-  }
-  float* phone = c.buf<float>("pb.phone", (size_t)B * Tv * E, s);
-  int32_t* pc = nullptr;
-  float* pf = nullptr;
-  if (guided) {
-    pc = c.buf<int32_t>("pb.pc", (size_t)B * Tv, s);
-    pf = c.buf<float>("pb.pf", (size_t)B * Tv, s);
-    RVCX_HIP(hipMemcpy2DAsync(pc, Tv * sizeof(int32_t), pitch, F * sizeof(int32_t), Tv * sizeof(int32_t), B,
-                              hipMemcpyDeviceToDevice, s));
-    RVCX_HIP(hipMemcpy2DAsync(pf, Tv * sizeof(float), pitchf, F * sizeof(float), Tv * sizeof(float), B,
-                              hipMemcpyDeviceToDevice, s));
-  }
-  for (int b = 0; b < B; ++b)
-    check(upsample2_protect(fx + (size_t)b * L * E, feats + (size_t)b * L * E, (int)L, E, phone + (size_t)b * Tv * E,
-                            (int)Tv, (guided && o.protect < 0.5f) ? pf + (size_t)b * Tv : nullptr, o.protect, s),
-          "upsample");
-  // 4. one batched Synthesizer.infer (pipeline.py:365-372)
-  int32_t* meta = c.buf<int32_t>("pb.meta", 2 * (size_t)B, s);
-  std::vector<int32_t> hm(2 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    hm[b] = (int32_t)Tv;
-    hm[B + b] = sids[b];
-  }
-  RVCX_HIP(hipMemcpyAsync(meta, hm.data(), sizeof(int32_t) * hm.size(), hipMemcpyHostToDevice, s));
-  const int64_t nvc = Tv * upp;
-  float* vc = c.buf<float>("pb.vc", (size_t)B * nvc, s);
-  {
-    ScopedFullLengths full(c);  // every row Tv long (hm above)
-    DecWindow win;  // the samples the trim below keeps, the same for every row
-    if (o.t_pad_tgt > 0 && c.use_dec_window()) win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
-    synth_forward(c, B, (int)Tv, phone, meta, pc, pf, meta + B, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
-                  nullptr, nullptr, win);
-  }
-  // 5. trim, volume envelope, peak normalisation per utterance (pipeline.py:545-552)
-  const int64_t keep = nvc - 2 * o.t_pad_tgt;
-  if (keep <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch: utterance too short for the padding");
-  if (keep > ldo) throw Error(RVCX_E_CAPACITY, "pipeline_batch: output rows need " + std::to_string(keep));
-  float* mx = c.buf<float>("pb.max", peak_normalize_ws_floats(B), s);
-  if (o.volume_envelope == 1.0) {  // trim + normalise in one pass over all rows
-    check(peak_normalize(vc + o.t_pad_tgt, out, keep, mx, s, B, nvc, ldo), "peak_normalize");
-    return keep;
-  }
-  RVCX_HIP(hipMemcpy2DAsync(out, ldo * sizeof(float), vc + o.t_pad_tgt, nvc * sizeof(float), keep * sizeof(float), B,
-                            hipMemcpyDeviceToDevice, s));
-  for (int b = 0; b < B; ++b) {
-    const int n1 = rms_frame_count(n, 16000), n2 = rms_frame_count(keep, c.scfg.sr);
-    float* rws = c.buf<float>("pl.rms", (size_t)(n1 + n2), s);
-    check(change_rms(pad64 + (size_t)b * m + o.t_pad, n, 16000, out + (size_t)b * ldo, keep, c.scfg.sr,
-                     (float)o.volume_envelope, rws, s),
-          "change_rms");
-  }
-  check(peak_normalize(out, out, keep, mx, s, B, ldo, ldo), "peak_normalize");
-  return keep;
-}
-
-// pitch_from_f0 for rows of Fv[b] frames at stride ld (f0, pitch, pitchf); f0_out rows at stride ldf
-static void pitch_from_f0_v(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B, const std::vector<int64_t>& Fv,
-                            int64_t ld, int32_t* pitch, float* pitchf, double* f0_out, int64_t ldf, hipStream_t s) {
-  std::vector<double> shift(B, o.pitch);
-  if (o.f0_autotune) {
-    for (int b = 0; b < B; ++b)
-      check(f0_autotune(f0 + (size_t)b * ld, (int)Fv[b], o.f0_autotune_strength, o.mlx_semantics ? 1 : 0, s),
-            "f0_autotune");
-    if (!o.mlx_semantics) std::fill(shift.begin(), shift.end(), 0.0);
-  } else if (o.proposed_pitch) {
-    std::vector<double> h((size_t)B * ld);
-    RVCX_HIP(hipMemcpyAsync(h.data(), f0, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
-    RVCX_HIP(hipStreamSynchronize(s));
-    c.check_device_status();
-    for (int b = 0; b < B; ++b) {
-      std::vector<double> one(h.begin() + (size_t)b * ld, h.begin() + (size_t)b * ld + Fv[b]);
-      shift[b] = o.pitch + proposed_key(one, o.proposed_pitch_threshold);
-    }
-  }
-  for (int b = 0; b < B; ++b)
-    check(f0_post(f0 + (size_t)b * ld, (int)Fv[b], std::pow(2.0, shift[b] / 12.0), pitch + (size_t)b * ld,
-                  pitchf + (size_t)b * ld, f0_out ? f0_out + (size_t)b * ldf : nullptr, s),
-          "f0_post");
-}
-
-// Batched offline conversion of B utterances of different lengths nv[b] (each one chunk: nv[b] + 160 <= t_max): one
-// batched HuBERT over the ragged rows (hubert_forward_v), one Synthesizer.infer with per-row lengths, and the per-row
-// stages around them (upsample + protect, pitch packing, trim, volume envelope, peak normalisation) as one launch set
-// each, driven by device arrays of the rows' lengths. Per utterance the result is Pipeline.pipeline's, n_out[b] samples.
+// Batched offline conversion (config C4) of B utterances of nv[b] samples (each one chunk: nv[b] + 160 <= t_max,
+// pipeline.py:486-512 with opt_ts empty): one batched HuBERT over the rows (hubert_forward_v), one Synthesizer.infer
+// with per-row lengths, and the per-row stages around them (upsample + protect, pitch packing, trim, volume envelope,
+// peak normalisation) as one launch set each, driven by device arrays of the rows' lengths. Per utterance the result is
+// Pipeline.pipeline's, n_out[b] samples; the batch only widens every GEMM. audio row b at audio + b*lda (fp64), out
+// row b at out + b*ldo, f0_out row b at f0_out + b*ldf.
+//   - rows of one length throughout (`plain` below) take the equal-length routes: HuBERT without masks, the synthesizer
+//     with full lengths, one batched RMVPE straight from the padded input (hidden_out, its salience, only then).
 //   - f0: RMVPE cannot take ragged rows exactly: its mel is reflect-padded at a row's own end and zero-padded to a
 //     multiple of 32 frames there, every 3x3 conv of the U-Net zero-pads at the image's own last frame, and the BiGRU's
 //     reverse recurrence starts there. Rows therefore run through the single-row forward, rows of equal length inside
@@ -659,29 +538,34 @@ static void pitch_from_f0_v(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int
 //     own batched Synthesizer.infer does: a shorter row's last frames, within the generator's receptive field of its
 //     end, see the zeroed pad frames' activations where a run of that row alone sees the conv's zero padding. The trim
 //     removes them only if t_pad_tgt covers the receptive field, so differing lengths with a smaller t_pad_tgt are refused.
-void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
-                              const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
-                              uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
-                              hipStream_t s) {
-  if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch_v: B < 1");
+void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
+                           const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
+                           uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
+                           float* hidden_out, hipStream_t s) {
+  if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
   int64_t n_max = 0;
   bool equal = true;
   for (int b = 0; b < B; ++b) {
-    if (nv[b] <= 0 || (B > 1 && nv[b] > lda)) throw Error(RVCX_E_INVALID, "pipeline_batch_v: bad row length");
+    if (nv[b] <= 0 || (B > 1 && nv[b] > lda)) throw Error(RVCX_E_INVALID, "pipeline_batch: bad row length");
     check_pipeline_opts(c, o, nv[b]);
     if (o.t_max > 0 && nv[b] + 160 > o.t_max)
-      throw Error(RVCX_E_INVALID, "pipeline_batch_v: utterances longer than t_max take the single-utterance path");
-    if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch_v: sid out of range");
+      throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
+    if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
     n_max = std::max(n_max, nv[b]);
     equal = equal && nv[b] == nv[0];
   }
   const int E = c.scfg.emb_dim, upp = c.scfg.upp();
   if (!equal && o.t_pad_tgt < (int64_t)dec_margin_frames(c.scfg) * upp)
-    throw Error(RVCX_E_INVALID, "pipeline_batch_v: rows of different lengths need t_pad_tgt >= " +
+    throw Error(RVCX_E_INVALID, "pipeline_batch: rows of different lengths need t_pad_tgt >= " +
                                     std::to_string((int64_t)dec_margin_frames(c.scfg) * upp) +
                                     " samples (the generator's receptive field): a shorter row's last frames differ from "
                                     "a run of that row alone, and only the trim removes them");
+  const bool guided = c.scfg.f0;  // no f0, pitch or protect without pitch guidance (pipeline.py:324-365)
+  if (hidden_out && !(equal && guided && o.f0_method == 0))
+    throw Error(RVCX_E_INVALID, "pipeline_batch: the salience needs equal lengths, RMVPE and a pitch-guided model");
   if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension mismatch");
+  // rvcx_workspace_bytes sizes the ragged form: masks, the gathered RMVPE group and one single-row RMVPE forward
+  const bool plain = equal && !c.sizing_plan;
   const int64_t W = 160;
   const int64_t m_max = n_max + 2 * o.t_pad;
   const int64_t ldm = (m_max + 7) & ~int64_t(7);
@@ -692,17 +576,17 @@ void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, in
     Fv[b] = 1 + mv[b] / W;
     Lv[b] = hubert_frames(mv[b]);
     Tvv[b] = std::min<int64_t>(mv[b] / W, 2 * Lv[b]);
-    if (Tvv[b] <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch_v: input shorter than one frame");
+    if (Tvv[b] <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch: input shorter than one frame");
     keep[b] = Tvv[b] * upp - 2 * o.t_pad_tgt;
-    if (keep[b] <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch_v: utterance too short for the padding");
+    if (keep[b] <= 0) throw Error(RVCX_E_SHAPE, "pipeline_batch: utterance too short for the padding");
     Tv_max = std::max(Tv_max, Tvv[b]);
     keep_max = std::max(keep_max, keep[b]);
   }
-  if (keep_max > ldo) throw Error(RVCX_E_CAPACITY, "pipeline_batch_v: output rows need " + std::to_string(keep_max));
+  if (keep_max > ldo) throw Error(RVCX_E_CAPACITY, "pipeline_batch: output rows need " + std::to_string(keep_max));
   const int64_t F_max = 1 + m_max / W, L_max = hubert_frames(m_max);
-  if (f0_out && ldf < F_max) throw Error(RVCX_E_CAPACITY, "pipeline_batch_v: f0 rows need " + std::to_string(F_max));
+  if (f0_out && ldf < F_max) throw Error(RVCX_E_CAPACITY, "pipeline_batch: f0 rows need " + std::to_string(F_max));
   // per-row lengths on device: L | Tv | sid | n | keep
-  int32_t* meta = c.buf<int32_t>("pv.meta", 5 * (size_t)B, s);
+  int32_t* meta = c.buf<int32_t>("pb.meta", 5 * (size_t)B, s);
   {
     std::vector<int32_t> hm(5 * (size_t)B);
     for (int b = 0; b < B; ++b) {
@@ -724,16 +608,16 @@ void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, in
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nv[x] > nv[y]; });
   for (int b : order)
     highpass_pad(c, audio + (size_t)b * lda, nv[b], o.t_pad, pad64 + (size_t)b * m_max, pad32 + (size_t)b * ldm, s);
-  // 2. ragged HuBERT on the aux stream beside the f0 of every row
+  // 2. batched HuBERT on the aux stream beside the f0 of every row, then get_f0's adjustments (pipeline.py:462-472,
+  //    :248-291)
   double* f0 = c.buf<double>("pb.f0", (size_t)B * F_max, s);
   float* feats = c.buf<float>("pb.feats", (size_t)B * L_max * E, s);
   hipStream_t ax = fork_aux(c, s);
   hubert_forward_v(c, pad32, mv.data(), ldm, B, hubert_version_for(c), feats, L_max, nullptr, ax);
-  const bool guided = c.scfg.f0;
   int32_t* pitch = nullptr;
   float* pitchf = nullptr;
   if (guided) {
-    if (o.f0_method >= 1) {
+    if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
       for (int b : order)
         f0_row(c, o, pad32 + (size_t)b * ldm, mv[b], f0 + (size_t)b * F_max, Fv[b], "pb.f0f", s);
     } else {
@@ -747,14 +631,15 @@ void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, in
           if (mv[g[0]] == mv[b]) g.push_back(b), placed = true;
         if (!placed) groups.push_back({b});
       }
-      if (c.sizing_plan) groups.push_back({0});  // rvcx_workspace_bytes: the single-row forward's regions too
+      if (c.sizing_plan) groups.push_back({0});
       std::stable_sort(groups.begin(), groups.end(), [&](const std::vector<int>& x, const std::vector<int>& y) {
         return (int64_t)x.size() * Fv[x[0]] > (int64_t)y.size() * Fv[y[0]];
       });
       for (const auto& g : groups) {
         const int b0 = g[0], ng = (int)g.size();
-        if (ng == 1) {
-          rmvpe_forward(c, pad32 + (size_t)b0 * ldm, mv[b0], thr, f0 + (size_t)b0 * F_max, Fv[b0], nullptr, s);
+        if (ng == 1 || (ng == B && plain)) {  // one row, or all of them: in place
+          rmvpe_forward_b(c, pad32 + (size_t)b0 * ldm, mv[b0], ldm, ng, thr, f0 + (size_t)b0 * F_max, Fv[b0],
+                          ng == B ? hidden_out : nullptr, s);
           continue;
         }
         float* ga = c.buf<float>("pv.grp", (size_t)ng * ldm, s);
@@ -770,11 +655,12 @@ void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, in
     }
     pitch = c.buf<int32_t>("pb.pitch", (size_t)B * F_max, s);
     pitchf = c.buf<float>("pb.pitchf", (size_t)B * F_max, s);
-    pitch_from_f0_v(c, o, f0, B, Fv, F_max, pitch, pitchf, f0_out, ldf, s);
+    pitch_from_f0(c, o, f0, B, Fv.data(), F_max, pitch, pitchf, f0_out, ldf, s);
   } else if (f0_out) {
     for (int b = 0; b < B; ++b) RVCX_HIP(hipMemsetAsync(f0_out + (size_t)b * ldf, 0, sizeof(double) * (size_t)Fv[b], s));
   }
   // 3. retrieval over all B*L_max rows (row-wise: a pad row's result is never read), upsample + protect, pitch packing
+  //    (pipeline.py:327-362)
   join_aux(c, s, ax);
   const float* fx = feats;
   if (o.index_rate > 0) {
@@ -788,41 +674,49 @@ void pipeline_forward_batch_v(Ctx& c, const double* audio, const int64_t* nv, in
   if (guided) {
     pc = c.buf<int32_t>("pb.pc", (size_t)B * Tv_max, s);
     pf = c.buf<float>("pb.pf", (size_t)B * Tv_max, s);
-    check(pack_pitch_v(pitch, pitchf, F_max, dTv, (int)Tv_max, pc, pf, B, s), "pack_pitch");
+    check(pack_pitch(pitch, pitchf, F_max, dTv, (int)Tv_max, pc, pf, B, s), "pack_pitch");
   }
-  check(upsample2_protect_v(fx, feats, dL, (int)L_max, E, phone, dTv, (int)Tv_max,
-                            (guided && o.protect < 0.5f) ? pitchf : nullptr, F_max, o.protect, B, s),
+  check(upsample2_protect(fx, feats, dL, (int)L_max, E, phone, dTv, (int)Tv_max,
+                          (guided && o.protect < 0.5f) ? pitchf : nullptr, F_max, o.protect, s, B),
         "upsample");
-  // 4. one Synthesizer.infer with per-row lengths (pipeline.py:365-372), the generator over the common window
+  // 4. one Synthesizer.infer with per-row lengths (pipeline.py:365-372), the generator over the common window: the
+  //    samples the trim below keeps
   const int64_t nvc = Tv_max * upp;
   float* vc = c.buf<float>("pb.vc", (size_t)B * nvc, s);
   {
+    ScopedFullLengths full(c, plain);
     DecWindow win;
     if (o.t_pad_tgt > 0 && c.use_dec_window()) win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
-    if (equal && !c.sizing_plan) {
-      ScopedFullLengths full(c);
-      synth_forward(c, B, (int)Tv_max, phone, dTv, pc, pf, dsid, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
-                    nullptr, nullptr, win);
-    } else {
-      synth_forward(c, B, (int)Tv_max, phone, dTv, pc, pf, dsid, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
-                    nullptr, nullptr, win);
-    }
+    synth_forward(c, B, (int)Tv_max, phone, dTv, pc, pf, dsid, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
+                  nullptr, nullptr, win);
   }
   // 5. trim, volume envelope, peak normalisation of every row in one launch set each (pipeline.py:545-552)
   float* mx = c.buf<float>("pb.max", peak_normalize_ws_floats(B), s);
-  if (o.volume_envelope == 1.0) {
-    check(peak_normalize_v(vc + o.t_pad_tgt, nvc, out, ldo, dkeep, keep_max, mx, B, s), "peak_normalize");
+  if (o.volume_envelope == 1.0) {  // trim + normalise in one pass over all rows
+    check(peak_normalize(vc + o.t_pad_tgt, nvc, out, ldo, dkeep, keep_max, mx, s, B), "peak_normalize");
   } else {
     RVCX_HIP(hipMemcpy2DAsync(out, ldo * sizeof(float), vc + o.t_pad_tgt, nvc * sizeof(float), keep_max * sizeof(float),
                               B, hipMemcpyDeviceToDevice, s));
-    float* rws = c.buf<float>("pv.rms", (size_t)B * (rms_frame_count(n_max, 16000) + rms_frame_count(keep_max, c.scfg.sr)),
-                              s);
-    check(change_rms_v(pad64 + o.t_pad, m_max, dn, n_max, 16000, out, ldo, dkeep, keep_max, c.scfg.sr,
-                       (float)o.volume_envelope, rws, B, s),
+    const int nrms = rms_frame_count(n_max, 16000) + rms_frame_count(keep_max, c.scfg.sr);
+    float* rws = c.buf<float>("pb.rms", (size_t)B * nrms, s);
+    check(change_rms(pad64 + o.t_pad, m_max, dn, n_max, 16000, out, ldo, dkeep, keep_max, c.scfg.sr,
+                     (float)o.volume_envelope, nullptr, rws, s, B),
           "change_rms");
-    check(peak_normalize_v(out, ldo, out, ldo, dkeep, keep_max, mx, B, s), "peak_normalize");
+    check(peak_normalize(out, ldo, out, ldo, dkeep, keep_max, mx, s, B), "peak_normalize");
   }
   for (int b = 0; b < B; ++b) n_out[b] = keep[b];
+}
+
+// B equal-length utterances of n samples: the rows above with one length; returns the rows' output length
+int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t lda, int B, const rvcx_pipeline_opts& o,
+                               const int32_t* sids, const float* eps_z, const float* eps_src, uint64_t seed,
+                               float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s) {
+  if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
+  const std::vector<int64_t> nv((size_t)B, n);
+  std::vector<int64_t> n_out((size_t)B);
+  pipeline_forward_rows(c, audio, nv.data(), lda, B, o, sids, eps_z, eps_src, seed, out, ldo, n_out.data(), f0_out,
+                        1 + (n + 2 * o.t_pad) / 160, hidden_out, s);
+  return n_out[0];
 }
 
 rvcx_pipeline_opts default_pipeline_opts() {

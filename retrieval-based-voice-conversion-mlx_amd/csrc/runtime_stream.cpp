@@ -518,8 +518,8 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   if (any_rms) {  // pipeline.py:299-307 (source = the 16 kHz convert buffer); rows at exactly 1 are skipped
     const int n1 = rms_frame_count(s.conv16, 16000), n2 = rms_frame_count(n_model, s.tgt_sr);
     float* ws = c.buf<float>("rt.rms", (size_t)Ba * (n1 + n2), st);
-    check(change_rms_f32src_rows(conv, s.conv16, s.conv16, 16000, model, n_model, n_model, s.tgt_sr,
-                                 reinterpret_cast<const float*>(dplan + P.rms), ws, Ba, st),
+    check(change_rms(conv, s.conv16, (int)s.conv16, s.conv16, 16000, model, n_model, (int)n_model, n_model, s.tgt_sr,
+                     1.f, reinterpret_cast<const float*>(dplan + P.rms), ws, st, Ba),
           "change_rms");
   }
   // the noise gate on the rows that ask for it (pipeline.py:326-327: after the volume envelope, before * sqrt(vol)),

@@ -15,6 +15,15 @@ namespace rvcx {
 // the opt-in and every RVCX_* variable present (honoured or ignored). Defined in capi.cpp.
 const char* rvcx_knob(const char* name);
 
+// A length per row of a batch: one value for every row, or a device array indexed by the row (read on the device only)
+struct Len {
+  const int* v = nullptr;
+  int n = 0;
+  Len(int all) : n(all) {}
+  Len(const int* rows) : v(rows) {}
+  __host__ __device__ int operator[](int b) const { return v ? v[b] : n; }
+};
+
 enum Act : int {
   ACT_NONE = 0,
   ACT_LRELU = 1,    // leaky relu with slope
@@ -311,9 +320,13 @@ hipError_t fcpe_post_process(const double* f0, int F, int n, int hop, int sr, in
 // (store: y = the noise conv itself, not accumulated)
 hipError_t noise_conv_add(const float* har, long long har_bs, int stride, int taps, const float* wf, const float* nb,
                           float* y, int B, int T, int C, hipStream_t s, bool store = false);
-hipError_t upsample2_protect(const float* feats, const float* feats0, int L, int D, float* out, int T, const float* pitchf,
-                             float protect,
-                             hipStream_t s);
+// x2 upsample + protect blend of B rows in one launch: feats / feats0 [B][L_max][D], L[b] valid -> out [B][T_max][D],
+// T[b] valid, the rest zero; pitchf (optional) rows of stride ldp
+hipError_t upsample2_protect(const float* feats, const float* feats0, Len L, int L_max, int D, float* out, Len T,
+                             int T_max, const float* pitchf, long long ldp, float protect, hipStream_t s, int B = 1);
+// pitch / pitchf rows of stride ldp -> pc / pf [B][T_max], zero from Tv[b] on
+hipError_t pack_pitch(const int32_t* pitch, const float* pitchf, long long ldp, const int* Tv, int T_max, int32_t* pc,
+                      float* pf, int B, hipStream_t s);
 hipError_t sine_source(const float* f0, int B, int L, int upp, float sr, const float* eps, uint64_t seed,
                        float lin_w, float lin_b, double* cum_ws, float* har, long long har_ld, hipStream_t s);
 // (y_bs: floats between the output rows of two batch entries, 0 = T)
@@ -341,15 +354,12 @@ constexpr int GN_CHUNKS = 256;
 inline size_t groupnorm_ws_doubles(int C, int B = 1) { return (size_t)B * (GN_CHUNKS * C * 2 + C); }
 hipError_t groupnorm_time_gelu(float* x, int T, int C, const float* gamma, const float* beta, float eps,
                                double* ws, hipStream_t s, int B = 1);
-// HuBERT conv_layers.0 fused: y[b][t][c] = GELU(GroupNorm_c(sum_k w10[c][k] x[b ldx + 5t + k])), T rows, C % 64 == 0,
-// C <= 1024, y 16-byte aligned; ws as above (aux_kernels.hip)
-hipError_t hubert_conv0_gn_gelu(const float* x, long long ldx, const float* w10, int T, int C, const float* gamma,
-                                const float* beta, float eps, double* ws, float* y, hipStream_t s, int B = 1);
-// The same over B sequences of different lengths: sequence b has Tv[b] rows (device array, 1 <= Tv[b] <= T_max) and its
-// statistics are over those rows alone; y is [B][T_max][C], rows from Tv[b] on written as zero
-hipError_t hubert_conv0_gn_gelu_v(const float* x, long long ldx, const float* w10, const int* Tv, int T_max, int C,
-                                  const float* gamma, const float* beta, float eps, double* ws, float* y, hipStream_t s,
-                                  int B);
+// HuBERT conv_layers.0 fused: y[b][t][c] = GELU(GroupNorm_c(sum_k w10[c][k] x[b ldx + 5t + k])), C % 64 == 0,
+// C <= 1024, y 16-byte aligned; ws as above (aux_kernels.hip). Sequence b has T[b] rows (1 <= T[b] <= T_max) and its
+// statistics are over those rows alone; y is [B][T_max][C], rows from T[b] on written as zero
+hipError_t hubert_conv0_gn_gelu(const float* x, long long ldx, const float* w10, Len T, int T_max, int C,
+                                const float* gamma, const float* beta, float eps, double* ws, float* y, hipStream_t s,
+                                int B = 1);
 hipError_t act_inplace(float* x, long long n, int act, float slope, hipStream_t s);
 hipError_t reflect_pad_1d(const float* x, int n, int pad_l, int pad_r, float* y, hipStream_t s, int B = 1,
                           long long ldx = 0, long long ldy = 0);
@@ -377,9 +387,10 @@ hipError_t filtfilt_pad(const double* x, long long n, const double* b, const dou
                         const double* FL, int order, long long t_pad, double* ws, double* pad64, float* pad32,
                         hipStream_t s);
 size_t filtfilt_ws_doubles(long long n, int order);
-// dst row b = src row b / (max|src row b| / 0.99) when that exceeds 1, else a copy (src == dst: in place)
-hipError_t peak_normalize(const float* src, float* dst, long long n, float* ws, hipStream_t s, int B = 1,
-                          long long lds = 0, long long ldd = 0);
+// dst row b = src row b / (max|src row b| / 0.99) when that exceeds 1, else a copy (src == dst: in place), over the
+// row's first n[b] samples (n_max >= every n[b]); ws peak_normalize_ws_floats(B)
+hipError_t peak_normalize(const float* src, long long lds, float* dst, long long ldd, Len n, long long n_max, float* ws,
+                          hipStream_t s, int B = 1);
 size_t peak_normalize_ws_floats(int B);
 // Pipeline.get_f0 / Pipeline.pipeline host DSP moved on device (aux_kernels.hip)
 hipError_t f0_autotune(double* f0, int F, double strength, int skip_unvoiced, hipStream_t s);
@@ -390,8 +401,14 @@ hipError_t split_points(const double* x, long long n, int window, long long t_ce
 int rms_frame_count(long long n, int sr);
 // fp64 frame RMS (librosa.feature.rms, center=True, constant pad): nframes = 1 + (n + 2*(frame/2) - frame)/hop
 hipError_t rms_frames_f64(const double* x, long long n, int frame, int hop, double* rms, int nframes, hipStream_t s);
-hipError_t change_rms(const double* src, long long n_src, int sr_src, float* y, long long n_y, int sr_y, float rate,
-                      float* ws, hipStream_t s);
+// AudioProcessor.change_rms of B rows in one launch set: source row b (fp64 or fp32, stride ld_src) of n_src[b]
+// samples, target row b (stride ld_y) of n_y[b]; rate_v (optional, device) is a rate per row in place of rate, and a
+// row whose entry is exactly 1 is left untouched. ws [B][rms_frame_count(n_src_max, sr_src) +
+// rms_frame_count(n_y_max, sr_y)] floats: a row's source frames, then its target frames
+template <class S>
+hipError_t change_rms(const S* src, long long ld_src, Len n_src, long long n_src_max, int sr_src, float* y,
+                      long long ld_y, Len n_y, long long n_y_max, int sr_y, float rate, const float* rate_v, float* ws,
+                      hipStream_t s, int B = 1);
 
 // FAISS IndexIVFFlat on device (ivf.hip): search + the retrieval blend of pipeline.py:378-388
 struct IvfView {
@@ -459,29 +476,6 @@ hipError_t rt_clip(float* x, long long ld, int n, int B, hipStream_t s);
 hipError_t rt_sola(const float* audio, long long lda, const float* volsq, const int* gate, float* sola_buf, int cf,
                    int search, const float* fade_in, float* out, int block, int* offs, const int* slot2row, int B,
                    hipStream_t s);
-// The batched pipeline's per-row tail stages for rows of different lengths (aux_kernels.hip "ragged batches"): one
-// launch set for all B rows, lengths in device int arrays, each row's valid elements the single-row kernel's.
-// upsample2_protect: feats / feats0 [B][L_max][D], Lv[b] valid -> out [B][T_max][D], Tv[b] valid, the rest zero;
-// pitchf (optional) rows of stride ldp
-hipError_t upsample2_protect_v(const float* feats, const float* feats0, const int* Lv, int L_max, int D, float* out,
-                               const int* Tv, int T_max, const float* pitchf, long long ldp, float protect, int B,
-                               hipStream_t s);
-// pitch / pitchf rows of stride ldp -> pc / pf [B][T_max], zero from Tv[b] on
-hipError_t pack_pitch_v(const int32_t* pitch, const float* pitchf, long long ldp, const int* Tv, int T_max, int32_t* pc,
-                        float* pf, int B, hipStream_t s);
-// peak_normalize of row b's first nv[b] samples (n_max >= every nv[b]); ws peak_normalize_ws_floats(B)
-hipError_t peak_normalize_v(const float* src, long long lds, float* dst, long long ldd, const int* nv, long long n_max,
-                            float* ws, int B, hipStream_t s);
-// change_rms of row b: source n_src[b] fp64 samples (stride ld_src), target n_y[b] samples (stride ld_y); ws
-// [B][rms_frame_count(n_src_max, sr_src) + rms_frame_count(n_y_max, sr_y)] floats
-hipError_t change_rms_v(const double* src, long long ld_src, const int* n_src, long long n_src_max, int sr_src, float* y,
-                        long long ld_y, const int* n_y, long long n_y_max, int sr_y, float rate, float* ws, int B,
-                        hipStream_t s);
-// change_rms with a float32 source for B rows in one launch set: per-row rate [B] (exactly 1 = row untouched),
-// ws [B][n1 + n2] floats (n = rms_frame_count of either side)
-hipError_t change_rms_f32src_rows(const float* src, long long ld_src, long long n_src, int sr_src, float* y,
-                                  long long ld_y, long long n_y, int sr_y, const float* rate, float* ws, int B,
-                                  hipStream_t s);
 
 // The realtime noise gate (spectral_gate.hip: TorchGate's stationary mode, core.py:86-94 / pipeline.py:326-327) over
 // x [B][n] (rows ldx apart) -> y [B][n] (rows ldy apart): samples [0, sg_n_out(n)) gated, the rest zeros. strength

@@ -652,32 +652,45 @@ class Engine:
         res = out[: no.value]
         return (res, f0) if want_f0 else res
 
-    def pipeline_batch(self, audio, opts: "_lib.PipelineOpts", sids=0, eps_z=None, eps_src=None, seed: int = 0,
-                       out=None, want_f0: bool = False, want_hidden: bool = False):
-        """B equal-length utterances (fp64 [B, n] @16 kHz, each within t_max) through one batched pass.
-        Returns fp32 [B, n_out] on device (row b = Pipeline.pipeline of utterance b); with want_f0 / want_hidden
-        also the rows' adjusted f0 fp64 [B, F] / RMVPE salience fp32 [B, F, 360]."""
+    def _pipeline_rows(self, a, ns, opts, sids, eps_z, eps_src, seed, out, want_f0, want_hidden):
+        """What rvcx_pipeline_batch and rvcx_pipeline_batch_v share: a [B, lda] fp64 on device, rows of ns samples
+        (an int: the equal-length entry). Returns (out [B, ldo], n_out per row, f0 [B, F] or None, salience or None)."""
         t = self.torch
-        a = self._dev(audio, t.float64)
-        B, n = int(a.shape[0]), int(a.shape[1])
-        m = n + 2 * int(opts.t_pad)
+        B, lda = int(a.shape[0]), int(a.shape[1])
+        m = lda + 2 * int(opts.t_pad)
         ldo = (m // 160) * self.upp
         if out is None or out.numel() < B * ldo:
             out = t.empty((B, ldo), dtype=t.float32, device=self.device)
+        out = out.reshape(-1)[: B * ldo].reshape(B, ldo)
         sid = np.broadcast_to(np.asarray(sids, dtype=np.int32), (B,))
         sarr = (ctypes.c_int32 * B)(*[int(v) for v in sid])
-        no = ctypes.c_int64(0)
         ez = None if eps_z is None else self._dev(eps_z, t.float32)
         es = None if eps_src is None else self._dev(eps_src, t.float32)
         F = 1 + m // 160
         f0 = t.empty((B, F), dtype=t.float64, device=self.device) if want_f0 else None
         hid = t.empty((B, F, 360), dtype=t.float32, device=self.device) if want_hidden else None
-        self._check(self.lib.rvcx_pipeline_batch(self.ctx, a.data_ptr(), n, n, B, ctypes.byref(opts), sarr, _ptr(ez),
-                                                 _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
-                                                 out.data_ptr(), ldo, ctypes.byref(no), _ptr(f0), _ptr(hid),
-                                                 self.stream()),
-                    "pipeline_batch")
-        y = out.reshape(-1)[: B * ldo].reshape(B, ldo)[:, : no.value]
+        head = (self.ctx, a.data_ptr())
+        mid = (lda, B, ctypes.byref(opts), sarr, _ptr(ez), _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+               out.data_ptr(), ldo)
+        if isinstance(ns, int):
+            no = ctypes.c_int64(0)
+            self._check(self.lib.rvcx_pipeline_batch(*head, ns, *mid, ctypes.byref(no), _ptr(f0), _ptr(hid),
+                                                     self.stream()), "pipeline_batch")
+            return out, [int(no.value)] * B, f0, hid
+        no = (ctypes.c_int64 * B)()
+        self._check(self.lib.rvcx_pipeline_batch_v(*head, (ctypes.c_int64 * B)(*ns), *mid, no, _ptr(f0), F,
+                                                   self.stream()), "pipeline_batch_v")
+        return out, [int(v) for v in no], f0, hid
+
+    def pipeline_batch(self, audio, opts: "_lib.PipelineOpts", sids=0, eps_z=None, eps_src=None, seed: int = 0,
+                       out=None, want_f0: bool = False, want_hidden: bool = False):
+        """B equal-length utterances (fp64 [B, n] @16 kHz, each within t_max) through one batched pass.
+        Returns fp32 [B, n_out] on device (row b = Pipeline.pipeline of utterance b); with want_f0 / want_hidden
+        also the rows' adjusted f0 fp64 [B, F] / RMVPE salience fp32 [B, F, 360]."""
+        a = self._dev(audio, self.torch.float64)
+        out, no, f0, hid = self._pipeline_rows(a, int(a.shape[1]), opts, sids, eps_z, eps_src, seed, out, want_f0,
+                                               want_hidden)
+        y = out[:, : no[0]]
         extra = [v for v, w in ((f0, want_f0), (hid, want_hidden)) if w]
         return (y, *extra) if extra else y
 
@@ -699,26 +712,11 @@ class Engine:
         if B < 1:
             return ([], []) if want_f0 else []
         ns = [int(r.numel()) for r in rows]
-        lda = max(ns)
-        a = t.zeros((B, lda), dtype=t.float64, device=self.device)
+        a = t.zeros((B, max(ns)), dtype=t.float64, device=self.device)
         for b, r in enumerate(rows):
             a[b, : ns[b]] = r
-        m = lda + 2 * int(opts.t_pad)
-        ldo = (m // 160) * self.upp
-        out = t.empty((B, ldo), dtype=t.float32, device=self.device)
-        sid = np.broadcast_to(np.asarray(sids, dtype=np.int32), (B,))
-        sarr = (ctypes.c_int32 * B)(*[int(v) for v in sid])
-        n_arr = (ctypes.c_int64 * B)(*ns)
-        no = (ctypes.c_int64 * B)()
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
-        F = 1 + m // 160
-        f0 = t.empty((B, F), dtype=t.float64, device=self.device) if want_f0 else None
-        self._check(self.lib.rvcx_pipeline_batch_v(self.ctx, a.data_ptr(), n_arr, lda, B, ctypes.byref(opts), sarr,
-                                                   _ptr(ez), _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
-                                                   out.data_ptr(), ldo, no, _ptr(f0), F, self.stream()),
-                    "pipeline_batch_v")
-        ys = [out[b, : int(no[b])] for b in range(B)]
+        out, no, f0, _ = self._pipeline_rows(a, ns, opts, sids, eps_z, eps_src, seed, None, want_f0, False)
+        ys = [out[b, : no[b]] for b in range(B)]
         if not want_f0:
             return ys
         return ys, [f0[b, : 1 + (ns[b] + 2 * int(opts.t_pad)) // 160] for b in range(B)]

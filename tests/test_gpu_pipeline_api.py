@@ -216,3 +216,55 @@ def test_pipeline_batch_vs_reference_and_oracle(engine, synth_w, hubert_w, rmvpe
         assert yb[b].shape == refs[b].shape
         assert spectrogram_correlation(yb[b], refs[b]) >= 0.999
         assert rel(yb[b], refs[b]) <= 2e-3, (b, rel(yb[b], refs[b]))
+
+
+@pytest.mark.parametrize("case", ["volume_envelope", "proposed_pitch"])
+def test_pipeline_batch_options_match_single(engine, case):
+    """The equal-length batch with a volume envelope (the batched RMS kernels) and with proposed pitch (one f0 readback
+    for all rows, a key per row) against rvcx_pipeline_ex per row with the row's slice of the injected noise:
+    test_pipeline_batch_matches_single's bars."""
+    from oracle.metrics import spectrogram_correlation
+    from rvcx import synthetic
+
+    engine.set_pipeline_highpass()
+    B, n = 3, 24000
+    audio = np.stack([synthetic.speech_like(n, seed=60 + b) * (1.0, 0.6, 0.8)[b] for b in range(B)])
+    kw = dict(pitch=2.0, protect=0.33, t_pad=4800, t_pad_tgt=14400,
+              **{"volume_envelope": dict(volume_envelope=0.5), "proposed_pitch": dict(proposed_pitch=1)}[case])
+    opts = engine.pipeline_opts(**kw)
+    upp, sids = engine.upp, [0, 3, 7]
+    T = engine.pipeline_frames(n, opts)
+    rng = np.random.default_rng(4)
+    ez = rng.standard_normal((B, 192, T)).astype(np.float32)
+    es = rng.standard_normal((B, T * upp)).astype(np.float32)
+    yb = engine.pipeline_batch(audio, opts, sids=sids, eps_z=ez, eps_src=es).cpu().numpy()
+    assert yb.shape == (B, T * upp - 2 * 14400)
+    for b in range(B):
+        y1 = engine.pipeline_ex(audio[b], engine.pipeline_opts(sid=sids[b], **kw), eps_z=ez[b], eps_src=es[b])
+        y1 = y1.cpu().numpy()
+        assert y1.shape == yb[b].shape  # equal n_out
+        corr = spectrogram_correlation(yb[b], y1)
+        diff = float(np.abs(yb[b] - y1).max()) / max(float(np.abs(y1).max()), 1e-6)
+        print(f"\n{case} row {b}: corr {corr:.6f} max diff {diff:.3e} of the peak")
+        assert corr > 0.999
+        assert diff < 5e-3
+
+
+def test_pipeline_batch_arena_holds_equal_lengths(engine):
+    """An arena of workspace_bytes(n, B, opts) holds the equal-length batch (no RVCX_E_OOM), and the result is the
+    internally allocated pool's, bit for bit."""
+    from rvcx import synthetic
+
+    t = engine.torch
+    engine.set_pipeline_highpass()
+    B, n = 3, 24000
+    audio = np.stack([synthetic.speech_like(n, seed=60 + b) for b in range(B)])
+    opts = engine.pipeline_opts(pitch=2.0, protect=0.33, t_pad=4800, t_pad_tgt=14400, volume_envelope=0.5)
+    ref = engine.host(engine.pipeline_batch(audio, opts, sids=[0, 3, 7], seed=11))
+    arena = t.empty(engine.workspace_bytes(n, B, opts), dtype=t.uint8, device=engine.device)
+    engine.set_workspace(arena)
+    try:
+        got = engine.host(engine.pipeline_batch(audio, opts, sids=[0, 3, 7], seed=11))
+    finally:
+        engine.set_workspace(None)
+    assert np.isfinite(got).all() and np.array_equal(got, ref)

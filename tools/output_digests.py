@@ -3,8 +3,10 @@ code): run it on two builds and diff the outputs to show that a host-side refact
 
 One line per output: RMVPE (single and batched, a frame count that is no multiple of 32), the FCPE mel and salience
 (a normal length, and one shorter than the window: zero padding and the duplicated last frame), HuBERT, CREPE, the
-synthesizer with each vocoder, a 6-hop stream group, and both pipeline forms for f0_method 0 / 2 / 3 under autotune
-and under proposed pitch.
+synthesizer with each vocoder, a 6-hop stream group (once more with a volume envelope on one of its streams), both
+pipeline forms for f0_method 0 / 2 / 3 under autotune and under proposed pitch and with a volume envelope, the batched
+pipeline's salience, and the ragged forms: HuBERT over rows of five lengths, the pipeline over rows of three lengths
+(plain and with a volume envelope) and over two equal rows.
 
     python tools/output_digests.py > digests.txt
 """
@@ -79,7 +81,12 @@ def main():
     outs = [grp.process(audio[:, h * block:(h + 1) * block], grp.opts(index_rate=0.0), seed=h)[0].clone()
             for h in range(hops)]
     show(f"stream group B={B} {hops} hops", *outs)
+    per_stream = [grp.opts(index_rate=0.0), grp.opts(index_rate=0.0, volume_envelope=0.4)]
+    outs = [grp.process(audio[:, h * block:(h + 1) * block], per_stream, seed=h)[0].clone() for h in range(hops)]
+    show(f"stream group B={B} envelope on 1", *outs)
     grp.close()
+    show("hubert_batch_v 5 rows", *eng.hubert_batch_v([synthetic.speech_like(n, seed=70 + i).astype(f32) for i, n in
+                                                       enumerate((40000, 400, 21000, 20700, 16000))]))
 
     eng.set_pipeline_highpass()
     speech = synthetic.speech_like(24000, seed=7)
@@ -90,6 +97,18 @@ def main():
             tag = f"f0_method={method} {next(iter(adj))}"
             show(f"pipeline_ex {tag}", *eng.pipeline_ex(speech, opts, seed=3, want_f0=True))
             show(f"pipeline_batch {tag}", *eng.pipeline_batch(two, opts, sids=[0, 1], seed=3, want_f0=True))
+    env = eng.pipeline_opts(pitch=2.0, volume_envelope=0.5)
+    show("pipeline_ex envelope", *eng.pipeline_ex(speech, env, seed=3, want_f0=True))
+    show("pipeline_batch envelope", *eng.pipeline_batch(two, env, sids=[0, 1], seed=3, want_f0=True))
+    show("pipeline_batch want_hidden", *eng.pipeline_batch(two, eng.pipeline_opts(pitch=2.0), sids=[0, 1], seed=3,
+                                                           want_f0=True, want_hidden=True))
+    ys, f0s = eng.pipeline_batch_v(list(two), env, sids=[0, 1], seed=3, want_f0=True)
+    show("pipeline_batch_v equal rows envelope", *ys, *f0s)
+    ragged = [synthetic.speech_like(n, seed=90 + b) for b, n in enumerate((24000, 40000, 8000, 24000))]
+    for tag, kw in (("plain", {}), ("envelope", {"volume_envelope": 0.5})):
+        opts = eng.pipeline_opts(pitch=2.0, t_pad=4800, t_pad_tgt=14400, **kw)
+        ys, f0s = eng.pipeline_batch_v(ragged, opts, sids=[0, 3, 7, 0], seed=3, want_f0=True)
+        show(f"pipeline_batch_v ragged {tag}", *ys, *f0s)
     eng.close()
 
 

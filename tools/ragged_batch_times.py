@@ -11,10 +11,10 @@ synchronise, after one untimed warm-up pass over the same shapes; --reps passes,
   (c) `Engine.hubert_batch_v` over the same batches against a loop of `Engine.hubert`.
 A batched setting is called faster (slower) only if its median lies below (above) the loop's own min .. max.
 
-    python tools/ragged_batch_times.py [--reps 5] [--loop-only] > profiles/ragged_batch_times.txt
+    python tools/ragged_batch_times.py [--reps 5] [--loop-only] [--only BATCH MAX_PAD] > profiles/ragged_batch_times.txt
 
 --loop-only times the two loops alone. It calls nothing the ragged entry points added, so with RVCX_LIB pointing at a
-library built from an older commit it measures that commit's route.
+library built from an older commit it measures that commit's route. --only times one batched setting beside the loops.
 """
 import argparse
 import json
@@ -41,6 +41,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop-only", action="store_true")
+    ap.add_argument("--only", nargs=2, metavar=("BATCH", "MAX_PAD"), default=None)
     args = ap.parse_args()
     from rvcx import _lib, offline, synthetic
     from rvcx.config import SYNTH_48K_V2
@@ -100,8 +101,8 @@ def main():
     report("(c) loop of hubert", t_hub, extra=f"(spread {100 * (max(t_hub) - min(t_hub)) / statistics.median(t_hub):.1f} %)")
     if not args.loop_only:
         frames = [eng.pipeline_frames(n, opts) for n in ns]
-        for batch in (4, 8, 16):
-            for max_pad in (0.05, 0.125, 0.25):
+        for batch in (4, 8, 16) if args.only is None else (int(args.only[0]),):
+            for max_pad in (0.05, 0.125, 0.25) if args.only is None else (float(args.only[1]),):
                 groups = offline.bucket(ns, batch, max_pad)
                 pad = 1 - sum(frames) / sum(len(g) * frames[g[0]] for g in groups)
                 hpad = 1 - sum(hubert_frames(n) for n in ns) / sum(len(g) * hubert_frames(ns[g[0]]) for g in groups)
