@@ -80,6 +80,25 @@ int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const 
  * where no stream cleans). Valid until the context's next compute call. RVCX_E_STATE before the first hop. */
 int rvcx_rt_model_rows(rvcx_ctx* ctx, rvcx_rt* rt, int gated, float* d_dst, int64_t ld, void* stream);
 
+/* RMVPE's BiGRU recurrence alone (csrc/gru.hip k_gru_bidir_g; nn.GRU(384, 256, bidirectional), ATen cell order), given
+ * the input projections: d_gi [B][T][1536] (x W_ih^T + b_ih; forward r, z, n then backward r, z, n), W_hh [768][256]
+ * and b_hh [768] per direction -> d_out [B][T][512] (forward h then backward h per step). It runs the launches RMVPE
+ * runs: the context's hand-off buffer, 16 sequences per launch, one tag counter per 16-sequence slice. tag_start < 0:
+ * the counters run on from the earlier launches on the buffer; tag_start >= 0 (< 2^32): the buffer is zeroed and every
+ * slice's counter set to tag_start before the launch (0: a freshly zeroed buffer; a counter that T + 1 more tags would
+ * carry past 2^32 zeroes the slice and restarts at 1). Any B >= 1; 1 <= T <= 2^20 (32-bit row offsets in the kernel);
+ * the W_hh pointers 16-byte aligned; else RVCX_E_INVALID. */
+int rvcx_gru_bidir(rvcx_ctx* ctx, const float* d_gi, int B, int T, const float* d_whh_f, const float* d_bhh_f,
+                   const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream);
+
+/* The generator's harmonic source alone, as the decoder of the loaded configuration computes it: NSF SineGen +
+ * l_linear + tanh (k_sine_cum / k_sine, csrc/aux_kernels.hip) or the 9-harmonic MRF source (csrc/source_harm.hip).
+ * d_f0 [B][T] -> d_har [B][T * upp]. d_eps_src as rvcx_dec_only takes it (NSF: [B][T * upp] N(0, 1); MRF:
+ * [B][T * upp][9] N(0, 1) then [B][9] U(0, 1) initial phases; NULL: drawn from `seed`). RVCX_E_STATE without a
+ * finalized pitch-guided synthesizer with one of these two decoders. */
+int rvcx_dec_source(rvcx_ctx* ctx, int B, int T, const float* d_f0, const float* d_eps_src, uint64_t seed, float* d_har,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

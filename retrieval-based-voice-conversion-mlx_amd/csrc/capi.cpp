@@ -1185,6 +1185,32 @@ int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const 
   });
 }
 
+int rvcx_gru_bidir(rvcx_ctx* ctx, const float* d_gi, int B, int T, const float* d_whh_f, const float* d_bhh_f,
+                   const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream) {
+  return guard(ctx, [&] {
+    // T: the kernel's 32-bit row offsets (t * 1536); the weights are read as float4
+    if (!d_gi || !d_whh_f || !d_bhh_f || !d_whh_b || !d_bhh_b || !d_out || B < 1 || B > 65535 || T < 1 ||
+        T > (1 << 20) || tag_start > (int64_t)UINT32_MAX || (reinterpret_cast<uintptr_t>(d_whh_f) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_whh_b) & 15))
+      throw Error(RVCX_E_INVALID, "rvcx_gru_bidir: bad arguments");
+    set_device(ctx);
+    ctx->before_gru = nullptr;  // nothing is issued beside this launch
+    gru_bidir_run(*ctx, d_gi, B, T, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start < 0 ? -1 : (long long)tag_start,
+                  static_cast<hipStream_t>(stream));
+  });
+}
+
+int rvcx_dec_source(rvcx_ctx* ctx, int B, int T, const float* d_f0, const float* d_eps_src, uint64_t seed, float* d_har,
+                    void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[0] || !ctx->scfg.f0 || ctx->scfg.vocoder == 2)
+      throw Error(RVCX_E_STATE, "rvcx_dec_source: needs a finalized pitch-guided HiFi-GAN (NSF) or MRF synthesizer");
+    if (B < 1 || T < 1 || !d_f0 || !d_har) throw Error(RVCX_E_INVALID, "rvcx_dec_source: bad arguments");
+    set_device(ctx);
+    dec_source_rows(*ctx, B, T, d_f0, d_eps_src, seed, d_har, static_cast<hipStream_t>(stream));
+  });
+}
+
 // ------------------------------------------------------------------ streaming (C5)
 int rvcx_rt_default_desc(rvcx_rt_desc* d) {
   if (!d) return RVCX_E_INVALID;

@@ -34,8 +34,10 @@ constexpr unsigned SPIN_LIMIT = 1u << 22;  // default bound on the polls of one 
 
 // gate activations on the hardware exp/rcp (v_exp_f32, v_rcp_f32): the libm expf/tanhf and IEEE divisions
 // were 0.14 us of every 1.5 us step (and __frcp_rn, used until round 6, is still the IEEE division sequence: three
-// dependent 10-instruction chains per step on the hand-off path); error <= ~2e-6 relative on sigmoid, ~1e-7 absolute
-// on tanh
+// dependent 10-instruction chains per step on the hand-off path). Error budget (1 ulp each for v_exp_f32 / v_rcp_f32,
+// 0.5 |v| ulp for the rounding of the scaled exponent, 0.5 ulp for the addition): sigmoid (0.5 |v| + 2.5) 2^-23
+// relative, <= 2e-6 up to |v| = 16 where the gate has saturated; tanh_g about 2.5 ulp of the subtracted term near 1,
+// 3e-7 absolute near v = 0, held to 6e-7 (tests/test_gpu_gru.py checks the recurrence under this budget)
 __device__ __forceinline__ float rcp_hw(float v) { return __builtin_amdgcn_rcpf(v); }
 __device__ __forceinline__ float sigm(float v) { return rcp_hw(1.f + __expf(-v)); }
 __device__ __forceinline__ float tanh_g(float v) { return 1.f - 2.f * rcp_hw(1.f + __expf(2.f * v)); }

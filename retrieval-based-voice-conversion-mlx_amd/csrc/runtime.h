@@ -349,6 +349,11 @@ int64_t hubert_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int
                          int64_t cap, hipStream_t s);
 int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
                         int64_t cap, float* hidden, hipStream_t s);
+// RMVPE's BiGRU recurrence on the context's hand-off buffer (runtime_fe.cpp): gi [B][T][1536] -> out [B][T][512], 16
+// sequences per launch; tag_start < 0 continues the buffer's tag counters, >= 0 zeroes it and sets them (the tests).
+// Takes Ctx::before_gru and issues it right after the BiGRU's launches.
+void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
+                   const float* bhh_b, float* out, long long tag_start, hipStream_t s);
 // batched over B inputs of nv[b] samples (host array): sequence b's hubert_frames(nv[b]) rows at feats + b*ld_rows*D
 int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
                          int64_t ld_rows, int64_t* rows_out, hipStream_t s);
@@ -381,6 +386,10 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
 // the synthesizer issues it on the aux stream beside the TextEncoder and flow, which leave most of the GPU idle.
 // Returns false (nothing issued) for configurations without the NSF noise branch.
 bool dec_noise_prepare(Ctx& c, int B, int T, const float* f0, const float* eps_src, uint64_t seed, hipStream_t s);
+// the harmonic source alone, as dec_forward / dec_noise_prepare compute it (NSF SineGen or the MRF source of the loaded
+// configuration): the interior of the "dec.har" rows copied to out [B][T * upp] (rvcx_dec_source, the tests)
+void dec_source_rows(Ctx& c, int B, int T, const float* f0, const float* eps_src, uint64_t seed, float* out,
+                     hipStream_t s);
 
 void set_highpass(Ctx& c, const double* b, const double* a, const double* zi, int order);
 void set_highpass_sos(Ctx& c, const double* sos, int nsec);

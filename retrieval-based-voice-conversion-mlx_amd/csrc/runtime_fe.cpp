@@ -476,6 +476,35 @@ void finalize_rmvpe(Ctx& c) {
   c.alloc_weight("rm.fc.b", host_weight(c, 2, "fc.1.bias", {NCLS}).v);
 }
 
+// The BiGRU recurrence of B sequences of T steps on the context's hand-off buffer (gi [B][T][1536] -> out [B][T][512]):
+// the buffer and its zeroing, one tag counter per 16-sequence slice, and the launches. tag_start < 0: the counters run
+// on from the earlier launches on this buffer (RMVPE); tag_start >= 0 (rvcx_gru_bidir, the tests): the buffer is
+// zeroed and every slice's counter set to it first, so no granule left by an earlier launch can carry a tag this one
+// waits for. Work the caller registered to go out beside the BiGRU (Ctx::before_gru) is issued from here.
+void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
+                   const float* bhh_b, float* out, long long tag_start, hipStream_t s) {
+  unsigned long long* xchg = c.buf<unsigned long long>("rm.xchg", gru_xchg_words(B), s);
+  // a new (or regrown) allocation holds garbage tags: zeroed once, and the tag counters of its slices restart
+  if (c.zero_once("rm.xchg", xchg, sizeof(unsigned long long) * gru_xchg_words(B), (long long)B, s))
+    c.gru_tags.clear();
+  if (tag_start >= 0) {
+    if (tag_start > 0) RVCX_HIP(hipMemsetAsync(xchg, 0, sizeof(unsigned long long) * gru_xchg_words(B), s));
+    for (int g0 = 0; g0 < B; g0 += 16) c.gru_tags[xchg + gru_xchg_words(g0)] = (unsigned)tag_start;
+  }
+  unsigned* status = c.device_status();  // sticky until the host reads it (Ctx::check_device_status)
+  // work the caller wants issued beside the BiGRU (which occupies 4 CUs): the gate event marks this point of the
+  // stream, the BiGRU goes out first and the hook's (many) launches after it, so the host time spent issuing
+  // them overlaps the BiGRU instead of delaying its launch
+  std::function<void(hipStream_t)> hook = std::move(c.before_gru);
+  c.before_gru = nullptr;
+  if (hook && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, s));
+  for (int g0 = 0; g0 < B; g0 += 16)  // at most 16 sequences per launch (16 x 4 working workgroups co-resident)
+    check(gru_bidir(gi + (size_t)g0 * T * 6 * GRU_H, whh_f, bhh_f, whh_b, bhh_b, T, out + (size_t)g0 * T * 2 * GRU_H,
+                    xchg + gru_xchg_words(g0), status, &c.gru_tags[xchg + gru_xchg_words(g0)], s, std::min(16, B - g0)),
+          "gru");
+  if (hook) hook(s);
+}
+
 // E2E on B mel chunk images [B][Fc][128] (already padded to a multiple of 32 frames) -> sal [B][Fc][360].
 // Pooling and the per-row transforms run on the B images stacked along time (every level's height is
 // even, so no 2x2 window straddles two images); convolutions take the image as their batch index.
@@ -587,23 +616,8 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
   float* gi = c.buf<float>("rm.gi", (size_t)B * Fc * 6 * GRU_H, s);
   run1(c, lin(feat, 3 * NMEL, B * Fc, 3 * NMEL, c.W("rm.gru.wih"), 6 * GRU_H, c.W("rm.gru.bih"), gi, 6 * GRU_H), s);
   float* go = c.buf<float>("rm.gruout", (size_t)B * Fc * 2 * GRU_H, s);
-  unsigned long long* xchg = c.buf<unsigned long long>("rm.xchg", gru_xchg_words(B), s);
-  // a new (or regrown) allocation holds garbage tags: zeroed once, and the tag counters of its slices restart
-  if (c.zero_once("rm.xchg", xchg, sizeof(unsigned long long) * gru_xchg_words(B), (long long)B, s))
-    c.gru_tags.clear();
-  unsigned* status = c.device_status();  // sticky until the host reads it (Ctx::check_device_status)
-  // work the caller wants issued beside the BiGRU (which occupies 4 CUs): the gate event marks this point of the
-  // stream, the BiGRU goes out first and the hook's (many) launches after it, so the host time spent issuing
-  // them overlaps the BiGRU instead of delaying its launch
-  std::function<void(hipStream_t)> hook = std::move(c.before_gru);
-  c.before_gru = nullptr;
-  if (hook && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, s));
-  for (int g0 = 0; g0 < B; g0 += 16)  // at most 16 sequences per launch (16 x 4 working workgroups co-resident)
-    check(gru_bidir(gi + (size_t)g0 * Fc * 6 * GRU_H, c.W("rm.gru.whh_f"), c.W("rm.gru.bhh_f"), c.W("rm.gru.whh_b"),
-                    c.W("rm.gru.bhh_b"), Fc, go + (size_t)g0 * Fc * 2 * GRU_H, xchg + gru_xchg_words(g0), status,
-                    &c.gru_tags[xchg + gru_xchg_words(g0)], s, std::min(16, B - g0)),
-          "gru");
-  if (hook) hook(s);
+  gru_bidir_run(c, gi, B, Fc, c.W("rm.gru.whh_f"), c.W("rm.gru.bhh_f"), c.W("rm.gru.whh_b"), c.W("rm.gru.bhh_b"), go, -1,
+                s);
   ConvArgs f = lin(go, 2 * GRU_H, B * Fc, 2 * GRU_H, c.W("rm.fc.w"), NCLS, c.W("rm.fc.b"), sal, NCLS);
   f.act = ACT_SIGMOID;
   run1(c, f, s);

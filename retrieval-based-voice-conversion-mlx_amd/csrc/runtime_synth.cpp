@@ -270,6 +270,14 @@ float* dec_source(Ctx& c, int B, int T, const float* f0, const float* eps_src, u
 }
 }  // namespace
 
+void dec_source_rows(Ctx& c, int B, int T, const float* f0, const float* eps_src, uint64_t seed, float* out,
+                     hipStream_t s) {
+  const long long Nh = (long long)T * c.scfg.upp();
+  const float* har = dec_source(c, B, T, f0, eps_src, seed, s);
+  RVCX_HIP(hipMemcpy2DAsync(out, sizeof(float) * (size_t)Nh, har + HAR_PAD, sizeof(float) * (size_t)(Nh + 2 * HAR_PAD),
+                            sizeof(float) * (size_t)Nh, (size_t)B, hipMemcpyDeviceToDevice, s));
+}
+
 bool dec_noise_prepare(Ctx& c, int B, int T, const float* f0, const float* eps_src, uint64_t seed, hipStream_t s) {
   const SynthCfg& cf = c.scfg;
   if (!cf.f0 || cf.vocoder == 2 || !f0) return false;

@@ -38,7 +38,7 @@ EXPORTS = [
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
 TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
                 "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update", "rvcx_rt_model_rows",
-                "rvcx_conv_plan"]
+                "rvcx_conv_plan", "rvcx_gru_bidir", "rvcx_dec_source"]
 
 
 class RvcxLibraryError(ImportError):
@@ -214,6 +214,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "rvcx_index_save": (i32, [vp, vp, i64, P(i64)]),
         "rvcx_kmeans_assign": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
         "rvcx_kmeans_update": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
+        "rvcx_gru_bidir": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+        "rvcx_dec_source": (i32, [vp, i32, i32, vp, vp, u64, vp, vp]),
         "rvcx_pipeline_batch": (i32, [vp, vp, i64, i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp, i64,
                                       P(i64), vp, vp, vp]),
         "rvcx_pipeline_batch_v": (i32, [vp, vp, P(i64), i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp,

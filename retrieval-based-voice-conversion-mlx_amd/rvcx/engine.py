@@ -875,6 +875,35 @@ class Engine:
                                                 cc.data_ptr(), sizes.data_ptr(), self.stream()), "kmeans_update")
         return cc, sizes
 
+    def gru_bidir(self, gi, whh_f, bhh_f, whh_b, bhh_b, tag_start: int = 0):
+        """RMVPE's BiGRU recurrence alone (rvcx_gru_bidir, include/rvcx_test.h): gi [B, T, 1536], W_hh [768, 256] and
+        b_hh [768] per direction -> out [B, T, 512] (device). tag_start < 0 continues the hand-off tag counters of the
+        context's buffer, >= 0 zeroes the buffer and sets them."""
+        t = self.torch
+        g = self._dev(gi, t.float32)
+        B, T, _ = g.shape
+        assert g.shape[2] == 1536
+        w = [self._dev(x, t.float32) for x in (whh_f, bhh_f, whh_b, bhh_b)]
+        assert tuple(w[0].shape) == (768, 256) == tuple(w[2].shape) and w[1].numel() == 768 == w[3].numel()
+        out = t.empty((B, T, 512), dtype=t.float32, device=self.device)
+        self._check(self.lib.rvcx_gru_bidir(self.ctx, g.data_ptr(), B, T, w[0].data_ptr(), w[1].data_ptr(),
+                                            w[2].data_ptr(), w[3].data_ptr(), out.data_ptr(), int(tag_start),
+                                            self.stream()), "gru_bidir")
+        return out
+
+    def dec_source(self, f0, eps_src=None, seed: int = 0):
+        """The decoder's harmonic source alone (rvcx_dec_source, include/rvcx_test.h): f0 [B, T] -> har
+        [B, T * upp] (device), NSF SineGen or the MRF source of the loaded configuration; eps_src as dec_only's."""
+        t = self.torch
+        f = self._dev(f0, t.float32)
+        B, T = f.shape
+        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        out = t.empty((B, T * self.upp), dtype=t.float32, device=self.device)
+        self._check(self.lib.rvcx_dec_source(self.ctx, B, T, f.data_ptr(), _ptr(es),
+                                             ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(), self.stream()),
+                    "dec_source")
+        return out
+
     # ------------------------------------------------------------------ kernel timing
     def set_conv_math(self, mode: str):
         """Contraction arithmetic of this context: "h16" (the default: fp32 via three bf16 planes on bf16 MFMA, the

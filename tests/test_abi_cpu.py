@@ -30,6 +30,25 @@ def test_library_exports_every_header_symbol():
     assert set(_lib.EXPORTS) == set(header_symbols())
 
 
+def test_recurrence_test_entries_are_exported_and_bound():
+    """rvcx_gru_bidir and rvcx_dec_source (include/rvcx_test.h): declared there and not in rvcx.h, exported, bound with
+    their prototypes, an Engine method each, and refused without a context."""
+    from rvcx import _lib
+    from rvcx.engine import Engine
+
+    test_h = open(os.path.join(REPO, "include", "rvcx_test.h")).read()
+    declared = set(re.findall(r"^\s*int\s+(rvcx_[a-z0-9_]+)\s*\(", test_h, re.M))
+    lib = _lib.load()
+    for name, nargs in (("rvcx_gru_bidir", 11), ("rvcx_dec_source", 8)):
+        assert name in declared and name not in header_symbols() and name not in _lib.EXPORTS
+        assert name in _lib.TEST_EXPORTS and name in _lib.exported_symbols()
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == nargs
+        assert _lib.STATUS[fn(*([None] + [0] * (nargs - 1)))] == "RVCX_E_INVALID"
+    assert set(_lib.TEST_EXPORTS) <= declared
+    assert callable(Engine.gru_bidir) and callable(Engine.dec_source)
+
+
 def test_engine_refuses_without_gpu():
     import torch
 
