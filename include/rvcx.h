@@ -567,16 +567,6 @@ int rvcx_spectral_gate(rvcx_ctx* ctx, const float* d_x, int B, int64_t n, int64_
  * `stream`, the other slots untouched. RVCX_E_INVALID when stream_index is not in [0, n_streams). */
 int rvcx_rt_reset_stream(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, void* stream);
 
-/* Contraction arithmetic of every convolution / linear / attention matmul of this context (replaces nothing in
- * the reference; torch's fp32 CPU conv is what every mode reproduces): 0 = default (3), 1 = fp32-input MFMA
- * (v_mfma_f32_32x32x2_f32, an exact fp32 fma chain at 157 TF), 2 = fp32 through an exact 3-way bf16 split of both
- * operands with the six significant plane products on bf16 MFMA (error below fp32's own rounding, 2.67x the
- * MFMA rate), 3 = as 2, except that the generator's weight-streamed convs and fused ResBlock pairs split both
- * operands into two fp16 planes (x = h + 2^-11 l, 11 significand bits each) with three plane products into two
- * fp32 accumulators (csrc/split_bf16.h; error against fp64 measured at or below the fp32-input MFMA's, 5.3x the
- * fp32 MFMA rate). Env RVCX_CONV_MATH=f32 | split | h16 sets the process default when RVCX_EXPERIMENTAL=1. */
-int rvcx_set_conv_math(rvcx_ctx* ctx, int mode);
-
 /* The effective configuration as a NUL-terminated JSON object (cap bytes; *len, optional, gets its length): the
  * context's contraction arithmetic, whether developer knobs are enabled, and every RVCX_* environment variable of the
  * process with whether it is honoured. The RVCX_* tuning / A-B switches (tile and split-K policy, kernel-path and
@@ -584,121 +574,6 @@ int rvcx_set_conv_math(rvcx_ctx* ctx, int mode);
  * listed here as not honoured. RVCX_E_CAPACITY when cap is too small (the string is truncated). ctx may be NULL (the
  * process-wide fields only; no device is touched). */
 int rvcx_config_info(const rvcx_ctx* ctx, char* buf, int64_t cap, int64_t* len);
-
-/* Removed in round 4 (deprecated shim, kept so existing callers link): the reduced-precision generator is now a
- * per-hop setting, rvcx_rt_opts.gen_precision. Always returns RVCX_E_INVALID with a message saying so. */
-int rvcx_set_generator_precision(rvcx_ctx* ctx, int precision);
-
-/* One Conv1d forward, time-major: d_x [T][C_in], d_w [taps][N][C_in] (torch weight [N][C_in][taps] permuted),
- * d_bias [N] (optional), d_y [T_out][N]; y[t] = bias + sum_k W[k] x[t*stride - pad + k*dilation] (zero outside).
- * The kernel family behind every contraction of the path, exposed for numerics tests; replaces
- * torch.nn.Conv1d.forward as used throughout rvc/lib/algorithm (e.g. residuals.py:34-80). math as above, plus
- * 3 = the split arithmetic on the weight-streamed kernel (weights pre-split in HBM; 1-D stride-1 convs with
- * C_in % 32 == 0 and (taps - 1) * dilation <= 64, else RVCX_E_SHAPE), 4 = the split arithmetic on the gather-streamed
- * kernel (weights pre-split in HBM, A gathered per step, split-K by the size policy; C_in % 32 == 0), 5 = the
- * two-plane fp16 split on the weight-streamed kernel (rvcx_set_conv_math mode 3's generator arithmetic), 6 = its fp16
- * hi planes alone (the realtime reduced-precision mode); 5 and 6 take the shapes 3 does; 7 = the two-plane fp16 split
- * on the gather-streamed kernel (the shapes 4 takes). */
-int rvcx_conv1d(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const float* d_w, const float* d_bias, int N,
-                int taps, int dilation, int pad, int stride, int math, float* d_y, int64_t T_out, void* stream);
-
-/* The generator's fused conv form, time-major (rvcx_conv1d's layouts, stride 1, T_out = T + 2 pad - (taps - 1)
- * dilation): y = acc(act(conv(pre(x)) + bias) + res), pre = leaky ReLU(pre_slope) when pre_act = 1 (else identity),
- * act = leaky ReLU(slope) when act = 1, res
- * optional ([T_out][N]), acc_mode 0 store, 1 y + v, 2 (y + v) / acc_div -- one ResBlock conv (residuals.py:71-80:
- * convs1 with act, convs2 with the residual and the ResBlock mean on the last pair) or one ConvTranspose phase group
- * (hifigan_nsf.py:184-199) in the two-plane fp16 split. kernel 0 = the size policy's route, 1 = the weight-streamed
- * kernel (conv_wsb.hip, the tile the policy picks), 2 = the weight-stationary kernel (conv_wst.hip: C_in = N in {64,
- * 128}, 2-3 taps, (taps - 1) dilation <= 16, else RVCX_E_SHAPE). Exposed for numerics tests; C_in % 32 == 0. */
-int rvcx_conv1d_gen(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const float* d_w, const float* d_bias,
-                    int N, int taps, int dilation, int pad, int pre_act, float pre_slope, int act, float slope,
-                    const float* d_res, int acc_mode, float acc_div, int kernel, float* d_y, void* stream);
-
-/* One 1-D contraction in any form the runtime issues (csrc/runtime_synth.cpp, runtime_fe.cpp), described field by
- * field as the dispatcher's own record (ConvArgs, csrc/rvcx_kernels.h) takes it. All pointers are device pointers, all
- * strides in floats; w is [taps][N][C_in] per group (rvcx_conv1d's layout), bias [N] per group.
- *   input     pre(x[b][row][c]) * pre_mask[b][row], zero outside [0, T_in); row = m stride - pad + tap dil
- *   value     v = act(alpha (acc + bias [+ res: res_mode 1])); res_mode 2: v + res, 3: res - v; acc_mode 1: y + v,
- *             2: (y + v) / acc_div; then v * mask[b][m]. act / pre_act: 0 none, 1 leaky ReLU(slope), 2 ReLU, 3 erf GELU,
- *             4 tanh, 5 sigmoid, 6 log(max(v, slope))
- *   batch     entry (b, g) of batch x batch_inner reads / writes at b *_bs + g *_bs2 (the masks and gate_g: b only)
- *   gate_h    > 0: y[m][c] = tanh(v[c] + g[c]) sigmoid(v[c + gate_h] + g[c + gate_h]), v = acc + bias, N = 2 gate_h,
- *             g = gate_g + b gate_g_bs; no other epilogue field
- *   ln_g      set: y[m] = LN(res[m] + v[m]) ln_g + ln_b over the N <= 1024 columns (res_mode 0, acc_mode 0)
- *   nz_har    set: + nz_b[c] + nz_w[c nz_stride] har[b nz_bs + (m nz_u + p) nz_stride] at column n = p nz_C + c (the
- *             fused NSF noise conv: nz_kk = 1, N = nz_u nz_C, an unsplit weight-streamed or weight-stationary launch)
- * The gate and the LayerNorm live in the split-K combine: they need a contraction of at least two 32-channel steps.
- * route 0 = the size policy as the runtime applies it to a static weight, 1 = exact fp32 MFMA, 2 = the LDS-staged bf16
- * split (a non-static weight), 3 = the weight-streamed tile the policy picks, 4 = gather-streamed, 5 =
- * weight-stationary. A forced route that does not admit the form returns RVCX_E_SHAPE before anything is launched; it
- * never runs on another kernel. no_splitk keeps the contraction in one slice. *kind_out (optional) gets the kernel
- * family that ran (rvcx_profile_kind_name's index), *ksplit_out (optional) the planned split count. The caller owns
- * every extent: nothing is checked against an allocation. Exposed for numerics tests. */
-typedef struct {
-  const float* x; const float* w; const float* bias; const float* res; const float* mask; const float* pre_mask;
-  float* y;
-  int T_in, C_in, N, taps, dil, pad, stride, T_out;
-  int ldx, ldy, ldr;
-  int batch;
-  int64_t x_bs, y_bs, res_bs, mask_bs, pre_mask_bs;
-  int batch_inner;
-  int64_t x_bs2, w_bs2, y_bs2, res_bs2, bias_bs2;
-  int pre_act; float pre_slope;
-  int act; float slope; float alpha;
-  int res_mode, acc_mode; float acc_div;
-  int gate_h; const float* gate_g; int64_t gate_g_bs;
-  const float* ln_g; const float* ln_b; float ln_eps;
-  const float* nz_har; int64_t nz_bs;
-  int nz_stride, nz_kk, nz_u, nz_C;
-  const float* nz_w; const float* nz_b;
-  int route, no_splitk;
-} rvcx_conv_test_desc;
-int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* desc, int* kind_out, int* ksplit_out, void* stream);
-
-/* One 3x3 / pad-1 Conv2d forward, NHWC: d_x [H][W][C_in], d_w [9][N][C_in] (torch weight [N][C_in][3][3] permuted to
- * (kh * 3 + kw, N, C_in)), d_bias [N] (optional), d_y [H][W][N]; act 0 none, 1 ReLU. The RMVPE U-Net's conv
- * (RMVPE.py:13-57 ConvBlockRes, torch.nn.Conv2d(kernel 3, padding 1)), exposed for the numerics tests of its
- * few-channel kernels (C_in, N in {16, 32}: csrc/conv2d_small.hip) and deep levels: math 0 = the context's arithmetic
- * (the two-plane fp16 split by default), 1 = exact fp32 (v_mfma_f32_16x16x4_f32), 2 = the deep levels' windowed
- * gather-streamed kernel in the fp16 split (images at most 32 wide, C_in % 32 == 0, else RVCX_E_SHAPE). Other shapes
- * take the general 2-D path. */
-int rvcx_conv2d3x3(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w, const float* d_bias,
-                   int N, int act, int math, float* d_y, void* stream);
-
-/* One ConvTranspose2d(C_in, N, kernel 3, stride 2, padding 1, output_padding 1) forward, NHWC: d_x [H][W][C_in],
- * d_w [C_in][N][3][3] (the torch layout as stored), d_bias [N] (optional), d_y [2H][2W][N]; act 0 none, 1 ReLU. The
- * RMVPE U-Net decoder's up-conv (RMVPE.py ResDecoderBlock conv1, torch.nn.ConvTranspose2d), run as the pipeline runs
- * it: a 2x2-tap phase conv with 4 N virtual output columns whose epilogue scatters the phases. math 0 = the context's
- * arithmetic (the two-plane fp16 split on the gather-streamed kernel where it applies), 1 = exact fp32. Exposed for the
- * numerics tests. */
-int rvcx_convtranspose2d_s2(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w,
-                            const float* d_bias, int N, int act, int math, float* d_y, void* stream);
-
-/* Multi-head attention core on the fused kernel (csrc/flash_attn.hip), time-major: d_qkv [B][T][3 H] (q | k | v, head
- * h at columns h dk .. of each, H = n_heads dk), d_out [B][T][H]: per head softmax(qscale q k^T + band) v + band(p)
- * rel_v, where, with d_rel_k / d_rel_v [2 window + 1][dk] (both or neither), band adds qscale q . rel_k[j - i + window]
- * to the logit of key j of query i for |j - i| <= window and band(p) is the probabilities of those keys
- * (MultiHeadAttention.attention with window_size, rvc/lib/algorithm/attentions.py:79-185), and d_mask [B][T]
- * (optional) fills the logits of masked query-key pairs with -1e4 (:106-107). Without the relative tables it is
- * HuBERT's attention (modeling_hubert.py HubertAttention: softmax((q dk^-0.5) k^T) v). dk 64 or 96, window <= 15.
- * Exposed for the numerics tests. */
-int rvcx_flash_attention(rvcx_ctx* ctx, const float* d_qkv, int B, int T, int n_heads, int dk, float qscale,
-                         const float* d_rel_k, const float* d_rel_v, int window, const float* d_mask, float* d_out,
-                         void* stream);
-
-/* One ResBlock dilation pair as one fused kernel (csrc/resblock_fused.hip), time-major: d_x, d_y [B][T][C] (distinct
- * buffers), d_w1 / d_w2 [k][C][C] (torch weight [C][C][k] permuted), d_b1 / d_b2 [C]:
- *     out = conv2(lrelu(conv1_d(lrelu(x), 0.1) + b1, 0.1)) + b2 + x     (zero padding; conv2 dilation 1)
- *     acc_mode 0: y = out; 1: y = y + out; 2: y = (y + out) / acc_div
- * Replaces one iteration of ResBlock.forward (rvc/lib/algorithm/residuals.py:71-80) and MRFLayer.forward
- * (generators/hifigan_mrf.py:45-50), plus the ResBlock mean of HiFiGANNSFGenerator.forward (hifigan_nsf.py:190-207)
- * on the last pair. C in {32, 64}, odd k, (k - 1) / 2 * dilation <= 30, else RVCX_E_SHAPE. cfg bits 0-3: 0 the
- * default kernels (the k = 3, 32-channel fp16 pairs on the weight-resident form), 1 the streamed-weight kernel for
- * every shape (comparisons; bit-identical results); bits 4-5 the arithmetic: 0 the exact 3-plane bf16 split, 1 the two-plane
- * fp16 split, 2 fp16 hi planes alone (the realtime reduced-precision mode). Exposed for numerics tests and A/B timing. */
-int rvcx_resblock_pair(rvcx_ctx* ctx, const float* d_x, int B, int64_t T, int C, const float* d_w1, const float* d_b1,
-                       const float* d_w2, const float* d_b2, int k, int dilation, int acc_mode, float acc_div, int cfg,
-                       float* d_y, void* stream);
 
 /* Upsampling factor of the loaded synthesizer (prod(upsample_rates); net_g.dec.upp). */
 int rvcx_synth_upp(const rvcx_ctx* ctx);

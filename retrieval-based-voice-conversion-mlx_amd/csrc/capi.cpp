@@ -1,5 +1,6 @@
-// extern "C" boundary (include/rvcx.h). Every entry point converts C++ exceptions into an
-// rvcx_status and stores the message for rvcx_last_error.
+// extern "C" boundary of the product ABI (include/rvcx.h); the kernel-level test entries (include/rvcx_test.h) are
+// capi_test.cpp. Every entry point converts C++ exceptions into an rvcx_status and stores the message for
+// rvcx_last_error (guard, capi_common.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -9,8 +10,7 @@
 #include <unistd.h>
 #include <vector>
 
-#include "../../include/rvcx_test.h"
-#include "runtime.h"
+#include "capi_common.h"
 
 extern char** environ;
 
@@ -26,91 +26,10 @@ static bool experimental_on() {
 const char* rvcx_knob(const char* name) { return experimental_on() ? std::getenv(name) : nullptr; }
 }  // namespace rvcx
 
-struct rvcx_ctx : public Ctx {};
-struct rvcx_rt {
-  RtState* s = nullptr;
-};
-
 namespace {
-
-template <class F>
-int guard(rvcx_ctx* c, F&& f) {
-  if (!c) return RVCX_E_INVALID;
-  try {
-    c->err.clear();
-    f();
-    return RVCX_OK;
-  } catch (const Error& e) {
-    c->err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    c->err = e.what();
-    return RVCX_E_INVALID;
-  }
-}
-
-// every compute entry point: select the device and report device-side faults of earlier, completed calls
-void set_device(rvcx_ctx* c) {
-  RVCX_HIP(hipSetDevice(c->device));
-  c->check_device_status();
-  c->begin_call();
-}
-
-}  // namespace
-
-namespace {
-// the synthesizer configuration a descriptor names (rvcx_set_synth_config, rvcx_dec_margin_frames)
-SynthCfg synth_cfg_of(const rvcx_synth_desc* d) {
-  if (!d) throw Error(RVCX_E_INVALID, "null desc");
-  SynthCfg g;
-  g.I = d->inter_channels;
-  g.H = d->hidden_channels;
-  g.F = d->filter_channels;
-  g.n_heads = d->n_heads;
-  g.n_layers = d->n_layers;
-  g.ksize = d->kernel_size;
-  if (d->n_resblocks < 1 || d->n_resblocks > 4 || d->n_dilations < 1 || d->n_dilations > 4)
-    throw Error(RVCX_E_INVALID, "resblock config out of range");
-  g.rb_k.assign(d->resblock_kernel_sizes, d->resblock_kernel_sizes + d->n_resblocks);
-  g.rb_d.clear();
-  for (int j = 0; j < d->n_resblocks; ++j)
-    g.rb_d.emplace_back(d->resblock_dilation_sizes[j], d->resblock_dilation_sizes[j] + d->n_dilations);
-  if (d->n_upsample < 1 || d->n_upsample > 8) throw Error(RVCX_E_INVALID, "n_upsample out of range");
-  g.ups.assign(d->upsample_rates, d->upsample_rates + d->n_upsample);
-  g.up_k.assign(d->upsample_kernel_sizes, d->upsample_kernel_sizes + d->n_upsample);
-  g.C0 = d->upsample_initial_channel;
-  g.n_spk = d->spk_embed_dim;
-  g.gin = d->gin_channels;
-  g.sr = d->sr;
-  g.emb_dim = d->text_enc_hidden_dim;
-  g.f0 = d->no_f0 == 0;
-  g.vocoder = d->vocoder;
-  if (g.vocoder < 0 || g.vocoder > 2) throw Error(RVCX_E_INVALID, "unsupported vocoder id");
-  if (!g.f0 && g.vocoder != 0)
-    throw Error(RVCX_E_INVALID, "models without pitch guidance use the HiFi-GAN decoder only (synthesizers.py:119-139)");
-  if (g.H % g.n_heads || g.I % 2 || g.C0 % (1 << g.ups.size()))
-    throw Error(RVCX_E_INVALID, "inconsistent synthesizer dimensions");
-  return g;
-}
-
-// the dispatcher's record of a 1-D test descriptor (rvcx_conv1d_ex, rvcx_conv_plan)
-ConvArgs conv_args_of(const rvcx_conv_test_desc* d) {
-  ConvArgs a;
-  a.x = d->x; a.x_bs = d->x_bs; a.x_bs2 = d->x_bs2; a.ldx = d->ldx; a.T_in = d->T_in; a.C_in = d->C_in;
-  a.pre_act = d->pre_act; a.pre_slope = d->pre_slope; a.pre_mask = d->pre_mask; a.pre_mask_bs = d->pre_mask_bs;
-  a.w = d->w; a.ldw = d->C_in; a.w_ts = (long long)d->N * d->C_in; a.w_bs2 = d->w_bs2;
-  a.taps = d->taps; a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
-  a.y = d->y; a.y_bs = d->y_bs; a.y_bs2 = d->y_bs2; a.ldy = d->ldy; a.T_out = d->T_out; a.N = d->N;
-  a.bias = d->bias; a.bias_bs2 = d->bias_bs2; a.alpha = d->alpha; a.act = d->act; a.slope = d->slope;
-  a.res = d->res; a.res_bs = d->res_bs; a.res_bs2 = d->res_bs2; a.ldr = d->ldr; a.res_mode = d->res_mode;
-  a.mask = d->mask; a.mask_bs = d->mask_bs; a.acc_mode = d->acc_mode; a.acc_div = d->acc_div;
-  a.gate_h = d->gate_h; a.gate_g = d->gate_g; a.gate_g_bs = d->gate_g_bs;
-  a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps;
-  a.batch = d->batch; a.batch_inner = d->batch_inner;
-  a.nz_har = d->nz_har; a.nz_bs = d->nz_bs; a.nz_stride = d->nz_stride; a.nz_kk = d->nz_kk; a.nz_u = d->nz_u;
-  a.nz_C = d->nz_C; a.nz_w = d->nz_w; a.nz_b = d->nz_b;
-  a.no_splitk = d->no_splitk ? 1 : 0;
-  return a;
+// the three models every pipeline entry runs
+bool pipeline_ready(const rvcx_ctx* c) {
+  return c->ready[RVCX_MODEL_SYNTH] && c->ready[RVCX_MODEL_HUBERT] && c->ready[RVCX_MODEL_RMVPE];
 }
 }  // namespace
 
@@ -142,7 +61,7 @@ int rvcx_set_synth_config(rvcx_ctx* ctx, const rvcx_synth_desc* d) {
   return guard(ctx, [&] {
     ctx->scfg = synth_cfg_of(d);
     ctx->synth_cfg_set = true;
-    ctx->ready[0] = false;
+    ctx->ready[RVCX_MODEL_SYNTH] = false;
   });
 }
 
@@ -189,7 +108,7 @@ int rvcx_synth_upp(const rvcx_ctx* ctx) { return ctx ? ctx->scfg.upp() : 0; }
 int rvcx_hubert(rvcx_ctx* ctx, const float* d_audio, int64_t n, int version, float* d_feats, int64_t cap_rows,
                 int64_t* rows_out, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[1]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_HUBERT]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
     if (!d_audio || !d_feats || n <= 0) throw Error(RVCX_E_INVALID, "rvcx_hubert: bad arguments");
     set_device(ctx);
     const int64_t L = hubert_forward(*ctx, d_audio, n, version == 1 ? 1 : 2, d_feats, cap_rows,
@@ -201,7 +120,7 @@ int rvcx_hubert(rvcx_ctx* ctx, const float* d_audio, int64_t n, int version, flo
 int rvcx_rmvpe(rvcx_ctx* ctx, const float* d_audio, int64_t n, float thred, double* d_f0, int64_t cap_frames,
                int64_t* frames_out, float* d_hidden, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[2]) throw Error(RVCX_E_STATE, "rmvpe weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_RMVPE]) throw Error(RVCX_E_STATE, "rmvpe weights not finalized");
     if (!d_audio || !d_f0 || n <= 0) throw Error(RVCX_E_INVALID, "rvcx_rmvpe: bad arguments");
     set_device(ctx);
     const int64_t F = rmvpe_forward(*ctx, d_audio, n, thred, d_f0, cap_frames, d_hidden,
@@ -325,50 +244,6 @@ int rvcx_fcpe_decode(rvcx_ctx* ctx, const float* d_salience, int64_t F, float th
   });
 }
 
-int rvcx_fcpe_mel(rvcx_ctx* ctx, const float* d_audio, int64_t n, float* d_mel, int64_t cap_frames, int64_t* frames_out,
-                  void* stream) {
-  return guard(ctx, [&] {
-    if (!ctx->ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-    if (!d_audio || !d_mel || n <= 0) throw Error(RVCX_E_INVALID, "rvcx_fcpe_mel: bad arguments");
-    if (cap_frames < fcpe_frames(*ctx, n)) throw Error(RVCX_E_CAPACITY, "rvcx_fcpe_mel: output capacity too small");
-    set_device(ctx);
-    const int F = fcpe_mel(*ctx, d_audio, n, n, 1, d_mel, static_cast<hipStream_t>(stream));
-    if (frames_out) *frames_out = F;
-  });
-}
-
-int rvcx_performer_attention(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int H, int T,
-                             const float* d_P, int M, float* d_out, void* stream) {
-  return guard(ctx, [&] {
-    if (!d_q || !d_k || !d_v || !d_P || !d_out || H <= 0 || T <= 0 || M <= 0)
-      throw Error(RVCX_E_INVALID, "rvcx_performer_attention: bad argument");
-    if (M > PERFORMER_MAX_FEATURES || (long long)H * T * 64 > INT32_MAX)
-      throw Error(RVCX_E_SHAPE, "rvcx_performer_attention: at most 512 features and 2^31 elements per operand");
-    set_device(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* ws = ctx->buf<float>("perf.test.ws", (size_t)performer_ws_floats(H, T, M), s);
-    check(performer_attention(d_q, d_k, d_v, (long long)T * 64, 64, H, T, d_P, M, ws, d_out, (long long)T * 64, 64, s),
-          "performer_attention");
-  });
-}
-
-int rvcx_performer_attention_b(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int H, int T,
-                               const float* d_P, int M, float* d_out, void* stream) {
-  return guard(ctx, [&] {
-    if (!d_q || !d_k || !d_v || !d_P || !d_out || B <= 0 || H <= 0 || T <= 0 || M <= 0)
-      throw Error(RVCX_E_INVALID, "rvcx_performer_attention_b: bad argument");
-    if (M > PERFORMER_MAX_FEATURES || B > 4096 || (long long)B * H * T * 64 > INT32_MAX)
-      throw Error(RVCX_E_SHAPE, "rvcx_performer_attention_b: at most 512 features and 2^31 elements per operand");
-    set_device(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* ws = ctx->buf<float>("perf.test.ws", (size_t)performer_ws_floats(H, T, M, B), s);
-    const long long bs = (long long)H * T * 64;
-    check(performer_attention(d_q, d_k, d_v, (long long)T * 64, 64, H, T, d_P, M, ws, d_out, (long long)T * 64, 64, s, B,
-                              bs, bs),
-          "performer_attention");
-  });
-}
-
 int rvcx_split_audio(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sr, double silence_thresh_db,
                      int min_silence_len_ms, int64_t* intervals, int64_t cap, int64_t* count, void* stream) {
   return guard(ctx, [&] {
@@ -383,7 +258,7 @@ int rvcx_split_audio(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sr, do
 int rvcx_hubert_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t lda, int B, int version, float* d_feats,
                       int64_t cap_rows, int64_t* rows_out, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[1]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_HUBERT]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
     if (!d_audio || !d_feats || n <= 0 || B < 1 || lda < n) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch: bad arguments");
     set_device(ctx);
     const int64_t L = hubert_forward_b(*ctx, d_audio, n, lda, B, version == 1 ? 1 : 2, d_feats, cap_rows,
@@ -395,7 +270,7 @@ int rvcx_hubert_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld
 int rvcx_hubert_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, int version,
                         float* d_feats, int64_t ld_rows, int64_t* L_out, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[1]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_HUBERT]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
     if (!d_audio || !d_feats || !n || B < 1 || ld_rows < 1) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch_v: bad arguments");
     for (int b = 0; b < B; ++b)
       if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch_v: bad row length");
@@ -408,7 +283,7 @@ int rvcx_hubert_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, i
 int rvcx_rmvpe_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t lda, int B, float thred, double* d_f0,
                      int64_t cap_frames, int64_t* frames_out, float* d_hidden, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[2]) throw Error(RVCX_E_STATE, "rmvpe weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_RMVPE]) throw Error(RVCX_E_STATE, "rmvpe weights not finalized");
     if (!d_audio || !d_f0 || n <= 0 || B < 1 || lda < n) throw Error(RVCX_E_INVALID, "rvcx_rmvpe_batch: bad arguments");
     set_device(ctx);
     const int64_t F = rmvpe_forward_b(*ctx, d_audio, n, lda, B, thred, d_f0, cap_frames, d_hidden,
@@ -450,7 +325,7 @@ int rvcx_synth_infer(rvcx_ctx* ctx, int B, int T, const float* d_phone, const in
                      const int32_t* d_pitch, const float* d_pitchf, const int32_t* d_sid, const float* d_eps_z,
                      const float* d_eps_src, uint64_t seed, float* d_out, float* d_zp, float* d_z, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0]) throw Error(RVCX_E_STATE, "synthesizer weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_SYNTH]) throw Error(RVCX_E_STATE, "synthesizer weights not finalized");
     if (B <= 0 || T <= 0 || !d_phone || !d_lengths || !d_sid || !d_out)
       throw Error(RVCX_E_INVALID, "rvcx_synth_infer: bad arguments");
     if (ctx->scfg.f0 && (!d_pitch || !d_pitchf))
@@ -467,7 +342,7 @@ int rvcx_synth_infer_ex(rvcx_ctx* ctx, int B, int T, const float* d_phone, const
                         const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, float* d_zp,
                         float* d_z, float* d_m_p, float* d_logs_p, int* t_out, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0]) throw Error(RVCX_E_STATE, "synthesizer weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_SYNTH]) throw Error(RVCX_E_STATE, "synthesizer weights not finalized");
     if (B <= 0 || T <= 0 || !d_phone || !d_lengths || !d_sid || !d_out)
       throw Error(RVCX_E_INVALID, "rvcx_synth_infer_ex: bad arguments");
     if (ctx->scfg.f0 && (!d_pitch || !d_pitchf))
@@ -493,7 +368,7 @@ int rvcx_synth_infer_ex(rvcx_ctx* ctx, int B, int T, const float* d_phone, const
 int rvcx_dec_only(rvcx_ctx* ctx, int B, int T, const float* d_z, const float* d_f0, const int32_t* d_sid,
                   const float* d_eps_src, uint64_t seed, float* d_out, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0]) throw Error(RVCX_E_STATE, "synthesizer weights not finalized");
+    if (!ctx->ready[RVCX_MODEL_SYNTH]) throw Error(RVCX_E_STATE, "synthesizer weights not finalized");
     if (B <= 0 || T <= 0 || !d_z || !d_sid || !d_out || (ctx->scfg.f0 && !d_f0))
       throw Error(RVCX_E_INVALID, "rvcx_dec_only: bad arguments");
     set_device(ctx);
@@ -512,7 +387,8 @@ int rvcx_voice_conversion(rvcx_ctx* ctx, const float* d_audio, int64_t n, const 
                           const float* d_eps_src, uint64_t seed, float* d_out, int64_t cap, int64_t* n_out,
                           void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0] || !ctx->ready[1]) throw Error(RVCX_E_STATE, "synthesizer/hubert not finalized");
+    if (!ctx->ready[RVCX_MODEL_SYNTH] || !ctx->ready[RVCX_MODEL_HUBERT])
+      throw Error(RVCX_E_STATE, "synthesizer/hubert not finalized");
     if (!d_audio || !d_out || n <= 0 || (ctx->scfg.f0 && (!d_pitch || !d_pitchf)))
       throw Error(RVCX_E_INVALID, "bad arguments");
     set_device(ctx);
@@ -571,7 +447,7 @@ int rvcx_pipeline_ex(rvcx_ctx* ctx, const double* d_audio, int64_t n, const rvcx
                      const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, int64_t cap,
                      int64_t* n_out, double* d_f0, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0] || !ctx->ready[1] || !ctx->ready[2]) throw Error(RVCX_E_STATE, "models not finalized");
+    if (!pipeline_ready(ctx)) throw Error(RVCX_E_STATE, "models not finalized");
     if (!d_audio || !d_out || !opts || n <= 0) throw Error(RVCX_E_INVALID, "bad arguments");
     set_device(ctx);
     const int64_t no = pipeline_forward_ex(*ctx, d_audio, n, *opts, d_eps_z, d_eps_src, seed, d_out, cap, d_f0,
@@ -602,77 +478,10 @@ int rvcx_workspace_info(const rvcx_ctx* ctx, int64_t* held, int64_t* arena_bytes
 int rvcx_workspace_bytes(rvcx_ctx* ctx, int B, int64_t n, const rvcx_pipeline_opts* opts, int64_t* bytes,
                          void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0] || !ctx->ready[1] || !ctx->ready[2]) throw Error(RVCX_E_STATE, "models not finalized");
+    if (!pipeline_ready(ctx)) throw Error(RVCX_E_STATE, "models not finalized");
     if (!opts || !bytes || n <= 0 || B < 1) throw Error(RVCX_E_INVALID, "rvcx_workspace_bytes: bad arguments");
     set_device(ctx);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    // the call itself on zero audio, from an empty internally allocated pool; the pool is released again after, and
-    // a caller arena stays attached (its regions are carved anew by the next call)
-    char* const arena = ctx->arena;
-    const size_t arena_bytes = ctx->arena_bytes;
-    ctx->release_pool();
-    ctx->arena = nullptr;
-    ctx->arena_bytes = 0;
-    struct PlanScope {
-      Ctx& c;
-      ~PlanScope() { c.sizing_plan = false; }
-    } plan_scope{*ctx};
-    ctx->sizing_plan = true;
-    DevBuf audio, out;
-    const int64_t m = n + 2 * opts->t_pad;
-    const int64_t cap = (m / 160 + (opts->t_center > 0 ? n / opts->t_center : 0) + 2) * ctx->scfg.upp();
-    int64_t need = 0;
-    try {
-      RVCX_HIP(hipMalloc(&audio.p, sizeof(double) * (size_t)(B * n)));
-      RVCX_HIP(hipMalloc(&out.p, sizeof(float) * (size_t)(B * cap)));
-      RVCX_HIP(hipMemsetAsync(audio.p, 0, sizeof(double) * (size_t)(B * n), s));
-      auto measure = [&](const rvcx_pipeline_opts& o) {
-        if (B == 1) {
-          pipeline_forward_ex(*ctx, static_cast<const double*>(audio.p), n, o, nullptr, nullptr, 0,
-                              static_cast<float*>(out.p), cap, nullptr, s);
-        } else {
-          // B rows of n samples in the batched pipeline's sizing form (Ctx::sizing_plan): run as a ragged batch (masks,
-          // the gathered RMVPE group and one single-row RMVPE forward), whose regions hold the equal-length routes too
-          std::vector<int32_t> sids((size_t)B, o.sid);
-          std::vector<int64_t> nv((size_t)B, n), no((size_t)B);
-          pipeline_forward_rows(*ctx, static_cast<const double*>(audio.p), nv.data(), n, B, o, sids.data(), nullptr,
-                                nullptr, 0, static_cast<float*>(out.p), cap, no.data(), nullptr, 0, nullptr, s);
-        }
-        RVCX_HIP(hipStreamSynchronize(s));
-        int64_t carved = (int64_t)ctx->carved;
-        if (B > 1) {
-          // a ragged batch walks its rows' front ends in another order than the call above, and the split-K slab all
-          // convs share is regrown whenever a later conv needs a larger one: room for one regrowth per row and stream
-          for (const char* slab : {"conv.splitk", "conv.splitk.aux"})
-            if (ctx->ws.count(slab) && ctx->ws[slab]) carved += (int64_t)B * (int64_t)ctx->ws[slab]->bytes;
-        }
-        return carved;
-      };
-      need = measure(*opts);
-      if (opts->f0_method == 3) {
-        // FCPE's scratch is carved in place of RMVPE's, which can be the larger: the size also holds the same call
-        // with the default f0 method, so an arena sized for "fcpe" serves a caller that switches back
-        rvcx_pipeline_opts o0 = *opts;
-        o0.f0_method = 0;
-        ctx->release_pool();
-        need = std::max(need, measure(o0));
-      }
-      // the per-chunk HuBERT feature buffers (pl.hb<i>) sum to the same total over any split plan up to one row and
-      // the 256-B rounding per chunk
-      if (B == 1 && opts->t_max > 0 && n + 160 > opts->t_max && opts->t_center > 0) {
-        const int64_t nts = n > opts->t_center ? (n - 1 - opts->t_center) / opts->t_center + 1 : 0;
-        need += (nts + 1) * ((int64_t)ctx->scfg.emb_dim * 4 + 512);
-      }
-    } catch (...) {
-      ctx->release_pool();
-      ctx->arena = arena;
-      ctx->arena_bytes = arena_bytes;
-      throw;
-    }
-    ctx->release_pool();
-    ctx->arena = arena;
-    ctx->arena_bytes = arena_bytes;
-    *bytes = need;
+    *bytes = pipeline_workspace_bytes(*ctx, B, n, *opts, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -703,13 +512,6 @@ int rvcx_index_parse(const void* bytes, int64_t nbytes, int64_t* d, int64_t* nto
     if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.what());
     return RVCX_E_INVALID;
   }
-}
-
-int rvcx_set_conv_math(rvcx_ctx* ctx, int mode) {
-  return guard(ctx, [&] {
-    if (mode < 0 || mode > 3) throw Error(RVCX_E_INVALID, "conv math mode must be 0, 1, 2 or 3");
-    ctx->conv_math = mode;
-  });
 }
 
 int rvcx_config_info(const rvcx_ctx* ctx, char* buf, int64_t cap, int64_t* len) {
@@ -745,274 +547,6 @@ int rvcx_config_info(const rvcx_ctx* ctx, char* buf, int64_t cap, int64_t* len) 
     buf[n] = 0;
   }
   return (int64_t)j.size() < cap || !buf ? RVCX_OK : RVCX_E_CAPACITY;
-}
-
-int rvcx_set_dec_window(rvcx_ctx* ctx, int on) {
-  return guard(ctx, [&] { ctx->dec_window = on != 0; });
-}
-
-int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames) {
-  try {
-    if (!frames) return RVCX_E_INVALID;
-    *frames = dec_margin_frames(synth_cfg_of(d));
-    return RVCX_OK;
-  } catch (const Error& e) {
-    return e.code;
-  } catch (...) {
-    return RVCX_E_INVALID;
-  }
-}
-
-int rvcx_conv_plan(const rvcx_conv_test_desc* d, const rvcx_conv_plan_form* f, int two_d, int static_weight, int math,
-                   int plan_T, int force_kind, int force_tile, int* kind, int* tile, int* ksplit, int* wsplit_fmt) {
-  if (!d || !kind || !tile || !ksplit || !wsplit_fmt || math < 0 || math > 3 || (two_d && !f)) return RVCX_E_INVALID;
-  ConvArgs a = conv_args_of(d);
-  a.math = math;
-  a.plan_T = plan_T;
-  if (f) {
-    a.W_in = f->W_in; a.W_out = f->W_out; a.KH = f->KH; a.KW = f->KW; a.padh = f->padh; a.padw = f->padw;
-    a.out_map = f->out_map; a.out_cv = f->out_cv; a.b_kn = f->b_kn; a.lowp = f->lowp;
-    if (f->ldw > 0) a.ldw = f->ldw;
-    if (f->w_ts > 0) a.w_ts = f->w_ts;
-    a.w_bs = f->w_bs; a.bias_bs = f->bias_bs;
-  }
-  const ConvPlan p = conv_plan(a, two_d != 0, static_weight != 0, ConvForce{force_kind, force_tile});
-  *kind = p.kind, *tile = p.tile, *ksplit = p.ksplit, *wsplit_fmt = p.wsplit_fmt;
-  return RVCX_OK;
-}
-
-int rvcx_set_generator_precision(rvcx_ctx* ctx, int) {
-  return guard(ctx, [&] {
-    throw Error(RVCX_E_INVALID,
-                "rvcx_set_generator_precision was removed: set rvcx_rt_opts.gen_precision per streaming hop instead");
-  });
-}
-
-int rvcx_conv1d(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const float* d_w, const float* d_bias, int N,
-                int taps, int dilation, int pad, int stride, int math, float* d_y, int64_t T_out, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    if (!d_x || !d_w || !d_y || T <= 0 || C_in <= 0 || N <= 0 || taps <= 0 || dilation <= 0 || stride <= 0 ||
-        pad < 0 || T_out <= 0 || math < 0 || math > 7)
-      throw Error(RVCX_E_INVALID, "rvcx_conv1d: bad argument");
-    if ((T_out - 1) * stride + (int64_t)(taps - 1) * dilation + 1 > T + 2 * (int64_t)pad)
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d: T_out exceeds the padded input");
-    if (T > INT32_MAX || T_out > INT32_MAX || (int64_t)taps * N * C_in > INT32_MAX)
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d: size out of range");
-    ConvArgs a;
-    a.x = d_x; a.ldx = C_in; a.T_in = (int)T; a.C_in = C_in;
-    a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = taps; a.dil = dilation; a.pad = pad;
-    a.stride = stride;
-    a.y = d_y; a.ldy = N; a.T_out = (int)T_out; a.N = N; a.bias = d_bias;
-    // math -> the arithmetic, the forced family, the reduced-precision mode. 3 / 5 / 6: the weight-streamed kernel on
-    // the tile the size policy picks, unsplit (5: the two-plane fp16 arithmetic, 6: its hi plane alone); 4 / 7: the
-    // gather-streamed kernel, split-K by the size policy (7: fp16)
-    static const struct { int math, kind, lowp; } route[8] = {{0, -1, 0}, {1, -1, 0}, {2, -1, 0}, {2, CK_WSB16, 0},
-                                                              {2, CK_GS, 0}, {3, CK_WSB16, 0}, {3, CK_WSB16, 1}, {3, CK_GS, 0}};
-    a.math = route[math].math;
-    a.lowp = route[math].lowp;
-    a.no_splitk = route[math].kind == CK_WSB16;
-    const ConvForce force{route[math].kind};
-    launch_conv_test(*ctx, a, false, force.kind >= 0, force, -1, "rvcx_conv1d", static_cast<hipStream_t>(stream));
-  });
-}
-
-int rvcx_conv1d_gen(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const float* d_w, const float* d_bias,
-                    int N, int taps, int dilation, int pad, int pre_act, float pre_slope, int act, float slope,
-                    const float* d_res, int acc_mode, float acc_div, int kernel, float* d_y, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    if (!d_x || !d_w || !d_y || T <= 0 || C_in <= 0 || N <= 0 || taps <= 0 || dilation <= 0 || pad < 0 || act < 0 ||
-        act > 1 || pre_act < 0 || pre_act > 1 || acc_mode < 0 || acc_mode > 2 || kernel < 0 || kernel > 2 || (d_res && d_res == d_x))
-      throw Error(RVCX_E_INVALID, "rvcx_conv1d_gen: bad argument");
-    const int64_t T_out = T + 2 * (int64_t)pad - (int64_t)(taps - 1) * dilation;
-    if (T_out <= 0 || T > INT32_MAX || (int64_t)taps * N * C_in > INT32_MAX)
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_gen: size out of range");
-    ConvArgs a;
-    a.x = d_x; a.ldx = C_in; a.T_in = (int)T; a.C_in = C_in;
-    a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = taps; a.dil = dilation; a.pad = pad;
-    a.y = d_y; a.ldy = N; a.T_out = (int)T_out; a.N = N; a.bias = d_bias;
-    a.pre_act = pre_act ? ACT_LRELU : ACT_NONE;
-    a.pre_slope = pre_slope;
-    a.act = act ? ACT_LRELU : ACT_NONE;
-    a.slope = slope;
-    if (d_res) {
-      a.res = d_res;
-      a.ldr = N;
-      a.res_mode = RES_ADD_POST;
-    }
-    a.acc_mode = acc_mode == 0 ? ACC_STORE : (acc_mode == 1 ? ACC_ADD : ACC_ADD_DIV);
-    a.acc_div = acc_div;
-    a.math = 3;
-    a.no_splitk = 1;
-    if (!conv_wsb_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_gen: shape not eligible for the weight-streamed kernel");
-    // 0: the size policy's route, 1: the weight-streamed tile the policy would pick, 2: the weight-stationary kernel
-    const ConvForce force{kernel == 1 ? CK_WSB16 : (kernel == 2 ? CK_WST : -1)};
-    launch_conv_test(*ctx, a, false, true, force, -1, "rvcx_conv1d_gen", static_cast<hipStream_t>(stream));
-  });
-}
-
-int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* d, int* kind_out, int* ksplit_out, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!d || !d->x || !d->w || !d->y || d->T_in <= 0 || d->C_in <= 0 || d->N <= 0 || d->taps <= 0 || d->dil <= 0 ||
-        d->stride <= 0 || d->pad < 0 || d->T_out <= 0 || d->batch <= 0 || d->batch_inner <= 0 || d->ldx < d->C_in ||
-        d->ldy < (d->gate_h > 0 ? d->gate_h : d->N) || d->pre_act < 0 || d->pre_act > ACT_LOGCLAMP || d->act < 0 ||
-        d->act > ACT_LOGCLAMP || d->res_mode < RES_NONE || d->res_mode > RES_RSUB_POST || d->acc_mode < ACC_STORE ||
-        d->acc_mode > ACC_ADD_DIV || (d->res_mode != RES_NONE && !d->res) || (d->res && d->ldr != 0 && d->ldr < d->N) ||
-        d->route < 0 || d->route > 5 || d->gate_h < 0 || (d->gate_h > 0 && !d->gate_g) ||
-        (d->ln_g && (!d->ln_b || !d->res)) ||
-        (d->nz_har && (!d->nz_w || !d->nz_b || d->nz_C <= 0 || d->nz_u <= 0 || d->nz_stride <= 0)) ||
-        ctx->is_weight(d->w))
-      throw Error(RVCX_E_INVALID, "rvcx_conv1d_ex: bad argument");
-    if ((int64_t)(d->T_out - 1) * d->stride + (int64_t)(d->taps - 1) * d->dil + 1 > d->T_in + 2 * (int64_t)d->pad)
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: T_out exceeds the padded input");
-    if ((int64_t)d->taps * d->N * d->C_in > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: size out of range");
-    ConvArgs a = conv_args_of(d);
-    // the combine-time epilogues as their kernels take them (launch_splitk_reduce's conditions)
-    if (a.ln_g && (a.N > 1024 || a.batch_inner != 1 || a.res_mode != RES_NONE || a.acc_mode != ACC_STORE || a.gate_h > 0))
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the combine's LayerNorm takes N <= 1024, one group, no other residual");
-    if (a.gate_h > 0 && (a.N != 2 * a.gate_h || a.batch_inner != 1 || a.act != ACT_NONE || a.alpha != 1.f || a.res ||
-                         a.mask || a.acc_mode != ACC_STORE))
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the combine's gate takes N = 2 gate_h and no other epilogue field");
-    if (a.nz_har && (a.nz_kk != 1 || a.N != a.nz_u * a.nz_C || a.gate_h > 0 || a.ln_g))
-      throw Error(RVCX_E_SHAPE, "rvcx_conv1d_ex: the fused noise conv takes one tap and N = nz_u nz_C");
-    // route -> the arithmetic, a static weight, the forced family and the family the launch has to get
-    static const struct { int math, stat, force, expect; } route[6] = {{0, 1, -1, -1},       {1, 0, -1, CK_GEMM},
-                                                                       {2, 0, -1, CK_EMU},   {3, 1, CK_WSB16, -1},
-                                                                       {3, 1, CK_GS, -1},    {3, 1, CK_WST, -1}};
-    const auto& r = route[d->route];
-    a.math = r.math;
-    const ConvPlan p = launch_conv_test(*ctx, a, false, r.stat != 0, ConvForce{r.force}, r.expect, "rvcx_conv1d_ex", s);
-    if (ksplit_out) *ksplit_out = p.ksplit;
-    if (kind_out) *kind_out = p.kind;
-  });
-}
-
-int rvcx_conv2d3x3(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w, const float* d_bias,
-                   int N, int act, int math, float* d_y, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    if (!d_x || !d_w || !d_y || H <= 0 || W <= 0 || C_in <= 0 || N <= 0 || act < 0 || act > 1 || math < 0 || math > 2)
-      throw Error(RVCX_E_INVALID, "rvcx_conv2d3x3: bad argument");
-    if ((int64_t)H * W * (C_in > N ? C_in : N) > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_conv2d3x3: size out of range");
-    ConvArgs a;
-    a.x = d_x; a.ldx = C_in; a.T_in = H; a.W_in = W; a.C_in = C_in;
-    a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = 9; a.KH = 3; a.KW = 3; a.padh = 1; a.padw = 1;
-    a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = N; a.bias = d_bias;
-    a.act = act ? ACT_RELU : ACT_NONE;
-    // math 2: the windowed gather-streamed kernel of the U-Net's deep levels in the two-plane fp16 split (64 x 64 tiles,
-    // K split over workgroups by the size policy); else the policy for a weight that is not static (the 3x3
-    // small-channel form reads a fresh fp16 image under the fp16-split arithmetic)
-    static const struct { int math, kind; } route[3] = {{0, -1}, {1, -1}, {3, CK_GSW}};
-    a.math = route[math].math;
-    const ConvForce force{route[math].kind};
-    if (math == 2 && !conv_gsw_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv2d3x3: shape not eligible for the windowed kernel");
-    launch_conv_test(*ctx, a, true, math == 2, force, -1, "rvcx_conv2d3x3", static_cast<hipStream_t>(stream));
-  });
-}
-
-int rvcx_convtranspose2d_s2(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w,
-                            const float* d_bias, int N, int act, int math, float* d_y, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    if (!d_x || !d_w || !d_y || H <= 0 || W <= 0 || C_in <= 0 || N <= 0 || act < 0 || act > 1 || math < 0 || math > 1)
-      throw Error(RVCX_E_INVALID, "rvcx_convtranspose2d_s2: bad argument");
-    if ((int64_t)4 * H * W * (C_in > 4 * N ? C_in : 4 * N) > INT32_MAX)
-      throw Error(RVCX_E_SHAPE, "rvcx_convtranspose2d_s2: size out of range");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // the phase-conv weights (and its bias per virtual column) in test buffers, rebuilt every call
-    float* wp = ctx->buf<float>("conv.test.upw", (size_t)16 * N * C_in, s);
-    check(upconv_phase_pack(d_w, C_in, N, wp, s), "upconv_phase_pack");
-    float* bp = nullptr;
-    if (d_bias) {
-      bp = ctx->buf<float>("conv.test.upb", (size_t)4 * N, s);
-      for (int p = 0; p < 4; ++p)
-        RVCX_HIP(hipMemcpyAsync(bp + (size_t)p * N, d_bias, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
-    }
-    ConvArgs a;  // runtime_fe.cpp's decoder up-conv
-    a.x = d_x; a.ldx = C_in; a.T_in = H; a.W_in = W; a.C_in = C_in;
-    a.w = wp; a.ldw = C_in; a.w_ts = (long long)4 * N * C_in; a.taps = 4; a.KH = 2; a.KW = 2;
-    a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = 4 * N;
-    a.out_map = OUT_UPSAMPLE2D;
-    a.out_cv = N;
-    a.bias = bp;
-    a.act = act ? ACT_RELU : ACT_NONE;
-    // math 0: the gather-streamed kernel the pipeline's policy routes the up-convs to (under a split arithmetic); 1: the
-    // native fp32 kernel
-    a.math = math == 1 ? 1 : 0;
-    const ConvForce force{math == 0 && conv_math(ctx->conv_math) >= 2 ? CK_GS : -1};
-    launch_conv_test(*ctx, a, true, force.kind >= 0, force, -1, "rvcx_convtranspose2d_s2", s);
-  });
-}
-
-int rvcx_flash_attention(rvcx_ctx* ctx, const float* d_qkv, int B, int T, int n_heads, int dk, float qscale,
-                         const float* d_rel_k, const float* d_rel_v, int window, const float* d_mask, float* d_out,
-                         void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    if (!d_qkv || !d_out || B <= 0 || T <= 0 || n_heads <= 0 || (dk != 64 && dk != 96) || window < 0 ||
-        (d_rel_k != nullptr) != (d_rel_v != nullptr))
-      throw Error(RVCX_E_INVALID, "rvcx_flash_attention: bad argument");
-    if ((long long)B * T * 3 * n_heads * dk > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_flash_attention: too large");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nsplit = flash_attn_splits(B, n_heads, T);
-    float* po = ctx->buf<float>("att.test.o", (size_t)flash_attn_ws_floats(B, n_heads, T, dk, nsplit), s);
-    float* pml = ctx->buf<float>("att.test.ml", (size_t)nsplit * B * n_heads * T * 2, s);
-    check(flash_attn(d_qkv, 3 * n_heads * dk, B, T, n_heads, dk, qscale, d_rel_k, d_rel_v, window, d_mask, po, pml,
-                     nsplit, d_out, n_heads * dk, s),
-          "flash_attn");
-  });
-}
-
-int rvcx_resblock_pair(rvcx_ctx* ctx, const float* d_x, int B, int64_t T, int C, const float* d_w1, const float* d_b1,
-                       const float* d_w2, const float* d_b2, int k, int dilation, int acc_mode, float acc_div, int cfg,
-                       float* d_y, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    ctx->check_device_status();
-    if (!d_x || !d_y || !d_w1 || !d_w2 || !d_b1 || !d_b2 || B <= 0 || T <= 0 || acc_mode < 0 || acc_mode > 2 ||
-        d_x == d_y || cfg < 0)
-      throw Error(RVCX_E_INVALID, "rvcx_resblock_pair: bad argument");
-    if (!rb_pair_fits(C, k, dilation) || T > INT32_MAX / C)
-      throw Error(RVCX_E_SHAPE, "rvcx_resblock_pair: shape not supported by the fused kernel");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int fmt = (cfg >> 4) & 3;
-    if (fmt > 2) throw Error(RVCX_E_INVALID, "rvcx_resblock_pair: arithmetic (cfg bits 4-5) must be 0, 1 or 2");
-    cfg &= 15;
-    const int wfmt = fmt ? RB_WF16 : RB_WBF16;
-    // fresh split images every call (test entry: the weight pointers may be reused by the caller)
-    void* w1s = ctx->buf<char>("rb.test.w1s", (size_t)rb_wsplit_bytes(C, k, wfmt), s);
-    void* w2s = ctx->buf<char>("rb.test.w2s", (size_t)rb_wsplit_bytes(C, k, wfmt), s);
-    check(rb_wsplit_build(d_w1, C, k, w1s, s, wfmt), "rb_wsplit_build");
-    check(rb_wsplit_build(d_w2, C, k, w2s, s, wfmt), "rb_wsplit_build");
-    RbPairArgs a;
-    a.wfmt = wfmt;
-    a.lowp = fmt == 2;
-    a.x = d_x;
-    a.x_bs = T * C;
-    a.w1s = w1s;
-    a.b1 = d_b1;
-    a.w2s = w2s;
-    a.b2 = d_b2;
-    a.C = C;
-    a.k = k;
-    a.d = dilation;
-    a.T = (int)T;
-    a.B = B;
-    a.y = d_y;
-    a.y_bs = T * C;
-    a.acc_mode = acc_mode;
-    a.acc_div = acc_div;
-    check(rb_pair(a, cfg, s), "rb_pair");
-  });
 }
 
 int rvcx_profile(rvcx_ctx* ctx, int enable) {
@@ -1069,8 +603,6 @@ int rvcx_profile_read_kinds(rvcx_ctx* ctx, double* total_ms, double* total_flops
     ctx->prof_recs.clear();
   });
 }
-
-}  // extern "C"
 
 // ------------------------------------------------------------------ feature index (FAISS IVFFlat)
 int rvcx_index_load(rvcx_ctx* ctx, const void* bytes, int64_t nbytes) {
@@ -1169,48 +701,6 @@ int rvcx_index_save(rvcx_ctx* ctx, void* bytes, int64_t cap, int64_t* nbytes) {
   });
 }
 
-int rvcx_kmeans_assign(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const float* d_cent, int64_t nlist,
-                       int32_t* d_assign, float* d_dist, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    kmeans_assign_run(*ctx, d_x, n, d, d_cent, nlist, d_assign, d_dist, static_cast<hipStream_t>(stream));
-  });
-}
-
-int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const int32_t* d_assign, int64_t nlist,
-                       float* d_cent, int64_t* d_sizes, void* stream) {
-  return guard(ctx, [&] {
-    set_device(ctx);
-    kmeans_update_run(*ctx, d_x, n, d, d_assign, nlist, d_cent, d_sizes, static_cast<hipStream_t>(stream));
-  });
-}
-
-int rvcx_gru_bidir(rvcx_ctx* ctx, const float* d_gi, int B, int T, const float* d_whh_f, const float* d_bhh_f,
-                   const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream) {
-  return guard(ctx, [&] {
-    // T: the kernel's 32-bit row offsets (t * 1536); the weights are read as float4
-    if (!d_gi || !d_whh_f || !d_bhh_f || !d_whh_b || !d_bhh_b || !d_out || B < 1 || B > 65535 || T < 1 ||
-        T > (1 << 20) || tag_start > (int64_t)UINT32_MAX || (reinterpret_cast<uintptr_t>(d_whh_f) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_whh_b) & 15))
-      throw Error(RVCX_E_INVALID, "rvcx_gru_bidir: bad arguments");
-    set_device(ctx);
-    ctx->before_gru = nullptr;  // nothing is issued beside this launch
-    gru_bidir_run(*ctx, d_gi, B, T, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start < 0 ? -1 : (long long)tag_start,
-                  static_cast<hipStream_t>(stream));
-  });
-}
-
-int rvcx_dec_source(rvcx_ctx* ctx, int B, int T, const float* d_f0, const float* d_eps_src, uint64_t seed, float* d_har,
-                    void* stream) {
-  return guard(ctx, [&] {
-    if (!ctx->ready[0] || !ctx->scfg.f0 || ctx->scfg.vocoder == 2)
-      throw Error(RVCX_E_STATE, "rvcx_dec_source: needs a finalized pitch-guided HiFi-GAN (NSF) or MRF synthesizer");
-    if (B < 1 || T < 1 || !d_f0 || !d_har) throw Error(RVCX_E_INVALID, "rvcx_dec_source: bad arguments");
-    set_device(ctx);
-    dec_source_rows(*ctx, B, T, d_f0, d_eps_src, seed, d_har, static_cast<hipStream_t>(stream));
-  });
-}
-
 // ------------------------------------------------------------------ streaming (C5)
 int rvcx_rt_default_desc(rvcx_rt_desc* d) {
   if (!d) return RVCX_E_INVALID;
@@ -1258,14 +748,6 @@ int rvcx_rt_set_clean(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, int clean_au
   return guard(ctx, [&] {
     if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_set_clean: null stream group");
     rt_set_clean(*ctx, *rt->s, stream_index, clean_audio, clean_strength);
-  });
-}
-
-int rvcx_rt_model_rows(rvcx_ctx* ctx, rvcx_rt* rt, int gated, float* d_dst, int64_t ld, void* stream) {
-  return guard(ctx, [&] {
-    if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_model_rows: null stream group");
-    RVCX_HIP(hipSetDevice(ctx->device));  // not a compute call: the pool the rows lie in is left as the hop left it
-    rt_model_rows(*rt->s, gated, d_dst, ld, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1344,7 +826,7 @@ int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t
                         const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
                         double* d_f0, float* d_hidden, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0] || !ctx->ready[1] || !ctx->ready[2]) throw Error(RVCX_E_STATE, "models not finalized");
+    if (!pipeline_ready(ctx)) throw Error(RVCX_E_STATE, "models not finalized");
     if (!d_audio || !opts || !sids || !d_out || n <= 0 || B < 1 || lda < n)
       throw Error(RVCX_E_INVALID, "rvcx_pipeline_batch: bad arguments");
     set_device(ctx);
@@ -1361,7 +843,7 @@ int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n
                           const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
                           double* d_f0, int64_t ldf, void* stream) {
   return guard(ctx, [&] {
-    if (!ctx->ready[0] || !ctx->ready[1] || !ctx->ready[2]) throw Error(RVCX_E_STATE, "models not finalized");
+    if (!pipeline_ready(ctx)) throw Error(RVCX_E_STATE, "models not finalized");
     if (!d_audio || !n || !opts || !sids || !d_out || !n_out || B < 1)
       throw Error(RVCX_E_INVALID, "rvcx_pipeline_batch_v: bad arguments");
     set_device(ctx);
@@ -1369,3 +851,5 @@ int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n
                           nullptr, static_cast<hipStream_t>(stream));
   });
 }
+
+}  // extern "C"

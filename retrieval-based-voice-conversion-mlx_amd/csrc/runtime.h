@@ -237,7 +237,11 @@ struct Ctx {
   // begin_call's events. The marks describing buffer contents go with the regions (a caller that wrote into its arena
   // between calls cannot leave a stale zeroed buffer or memoised scalar behind).
   void arena_rewind() {
-    if (!arena) return;
+    if (arena) drop_pool();
+  }
+  // drop the named pool, with the marks that describe its contents (zeroed buffers, memoised scalars, BiGRU tag
+  // counters)
+  void drop_pool() {
     ws.clear();
     zero_marks.clear();
     i32_marks.clear();
@@ -245,16 +249,10 @@ struct Ctx {
     arena_used = 0;
     carved = 0;
   }
-  // synchronise the device and drop the named pool, with the marks that describe its contents (zeroed buffers,
-  // memoised scalars, BiGRU tag counters)
+  // synchronise the device, then drop the pool
   void release_pool() {
     RVCX_HIP(hipDeviceSynchronize());
-    ws.clear();
-    zero_marks.clear();
-    i32_marks.clear();
-    gru_tags.clear();
-    arena_used = 0;
-    carved = 0;
+    drop_pool();
   }
   size_t pool_bytes() const {
     size_t t = 0;
@@ -470,6 +468,10 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
                            const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
                            float* hidden_out, hipStream_t s);
+// rvcx_workspace_bytes: the pool a pipeline call of B utterances of n samples under o takes, measured by running it on
+// zero audio from an empty pool (B = 1 pipeline_forward_ex, B > 1 pipeline_forward_rows in its sizing form); a caller
+// arena is detached meanwhile and the pool is released again before it returns
+int64_t pipeline_workspace_bytes(Ctx& c, int B, int64_t n, const rvcx_pipeline_opts& o, hipStream_t s);
 rvcx_pipeline_opts default_pipeline_opts();
 int proposed_key(const std::vector<double>& f0, double threshold);
 int64_t hubert_frames(int64_t n);  // HuBERT output rows for n samples (0 when too short)

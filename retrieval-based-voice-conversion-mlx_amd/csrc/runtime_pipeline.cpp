@@ -719,6 +719,79 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   return n_out[0];
 }
 
+namespace {
+// rvcx_workspace_bytes plans from an empty, internally allocated pool: the caller's arena is detached for the scope and
+// attached again after (its regions are carved anew by the next call), the pool the plan took is dropped, and
+// Ctx::sizing_plan is set for the scope
+struct SizingScope {
+  Ctx& c;
+  char* const arena;
+  const size_t arena_bytes;
+  explicit SizingScope(Ctx& cc) : c(cc), arena(cc.arena), arena_bytes(cc.arena_bytes) {
+    c.release_pool();
+    c.arena = nullptr;
+    c.arena_bytes = 0;
+    c.sizing_plan = true;
+  }
+  ~SizingScope() {
+    (void)hipDeviceSynchronize();  // release_pool without its throw: every measurement has synchronised its stream
+    c.drop_pool();
+    c.arena = arena;
+    c.arena_bytes = arena_bytes;
+    c.sizing_plan = false;
+  }
+};
+}  // namespace
+
+int64_t pipeline_workspace_bytes(Ctx& c, int B, int64_t n, const rvcx_pipeline_opts& opts, hipStream_t s) {
+  // the call itself on zero audio; the buffers outlive the scope, which synchronises the device before they are freed
+  DevBuf audio, out;
+  SizingScope scope(c);
+  const int64_t m = n + 2 * opts.t_pad;
+  const int64_t cap = (m / 160 + (opts.t_center > 0 ? n / opts.t_center : 0) + 2) * c.scfg.upp();
+  RVCX_HIP(hipMalloc(&audio.p, sizeof(double) * (size_t)(B * n)));
+  RVCX_HIP(hipMalloc(&out.p, sizeof(float) * (size_t)(B * cap)));
+  RVCX_HIP(hipMemsetAsync(audio.p, 0, sizeof(double) * (size_t)(B * n), s));
+  auto measure = [&](const rvcx_pipeline_opts& o) {
+    if (B == 1) {
+      pipeline_forward_ex(c, static_cast<const double*>(audio.p), n, o, nullptr, nullptr, 0, static_cast<float*>(out.p),
+                          cap, nullptr, s);
+    } else {
+      // B rows of n samples in the batched pipeline's sizing form (Ctx::sizing_plan): run as a ragged batch (masks,
+      // the gathered RMVPE group and one single-row RMVPE forward), whose regions hold the equal-length routes too
+      std::vector<int32_t> sids((size_t)B, o.sid);
+      std::vector<int64_t> nv((size_t)B, n), no((size_t)B);
+      pipeline_forward_rows(c, static_cast<const double*>(audio.p), nv.data(), n, B, o, sids.data(), nullptr, nullptr, 0,
+                            static_cast<float*>(out.p), cap, no.data(), nullptr, 0, nullptr, s);
+    }
+    RVCX_HIP(hipStreamSynchronize(s));
+    int64_t carved = (int64_t)c.carved;
+    if (B > 1) {
+      // a ragged batch walks its rows' front ends in another order than the call above, and the split-K slab all
+      // convs share is regrown whenever a later conv needs a larger one: room for one regrowth per row and stream
+      for (const char* slab : {"conv.splitk", "conv.splitk.aux"})
+        if (c.ws.count(slab) && c.ws[slab]) carved += (int64_t)B * (int64_t)c.ws[slab]->bytes;
+    }
+    return carved;
+  };
+  int64_t need = measure(opts);
+  if (opts.f0_method == 3) {
+    // FCPE's scratch is carved in place of RMVPE's, which can be the larger: the size also holds the same call
+    // with the default f0 method, so an arena sized for "fcpe" serves a caller that switches back
+    rvcx_pipeline_opts o0 = opts;
+    o0.f0_method = 0;
+    c.release_pool();
+    need = std::max(need, measure(o0));
+  }
+  // the per-chunk HuBERT feature buffers (pl.hb<i>) sum to the same total over any split plan up to one row and
+  // the 256-B rounding per chunk
+  if (B == 1 && opts.t_max > 0 && n + 160 > opts.t_max && opts.t_center > 0) {
+    const int64_t nts = n > opts.t_center ? (n - 1 - opts.t_center) / opts.t_center + 1 : 0;
+    need += (nts + 1) * ((int64_t)c.scfg.emb_dim * 4 + 512);
+  }
+  return need;
+}
+
 rvcx_pipeline_opts default_pipeline_opts() {
   rvcx_pipeline_opts o;
   std::memset(&o, 0, sizeof(o));

@@ -173,9 +173,10 @@ void rt_model_rows(const RtState& s, int gated, float* dst, int64_t ld, hipStrea
 }
 
 RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
-  if (!c.ready[0] || !c.ready[1]) throw Error(RVCX_E_STATE, "stream: synth and hubert must be finalized");
+  if (!c.ready[RVCX_MODEL_SYNTH] || !c.ready[RVCX_MODEL_HUBERT])
+    throw Error(RVCX_E_STATE, "stream: synth and hubert must be finalized");
   if (d.f0_method < 0 || d.f0_method > 1) throw Error(RVCX_E_INVALID, "stream: f0_method must be 0 (rmvpe) or 1 (fcpe)");
-  if (c.scfg.f0 && d.f0_method == 0 && !c.ready[2])
+  if (c.scfg.f0 && d.f0_method == 0 && !c.ready[RVCX_MODEL_RMVPE])
     throw Error(RVCX_E_STATE, "stream: f0_method rmvpe but no RMVPE weights finalized");
   if (c.scfg.f0 && d.f0_method == 1) {  // as the pipeline's f0_method 3 (runtime_pipeline.cpp check_f0_method)
     if (!c.ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "stream: f0_method fcpe but no FCPE weights finalized");

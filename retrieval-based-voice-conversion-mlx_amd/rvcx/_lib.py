@@ -1,4 +1,5 @@
-"""ctypes binding of librvcx.so (the C-ABI declared in include/rvcx.h).
+"""ctypes binding of librvcx.so: the product C-ABI declared in include/rvcx.h (SIG) and the kernel-level test
+entries declared in include/rvcx_test.h (TEST_SIG).
 
 There is no CPU fallback: if the HIP library is missing or cannot be loaded, importing
 the compute path raises ``RvcxLibraryError``.
@@ -18,27 +19,6 @@ STATUS = {
     0: "RVCX_OK", -1: "RVCX_E_INVALID", -2: "RVCX_E_SHAPE", -3: "RVCX_E_HIP", -4: "RVCX_E_OOM",
     -5: "RVCX_E_STATE", -6: "RVCX_E_CAPACITY",
 }
-
-EXPORTS = [
-    "rvcx_create", "rvcx_destroy", "rvcx_set_generator_precision", "rvcx_config_info", "rvcx_profile_read_kinds",
-    "rvcx_profile_kind_name", "rvcx_synth_infer_ex", "rvcx_last_error", "rvcx_set_synth_config", "rvcx_upload", "rvcx_finalize",
-    "rvcx_hubert", "rvcx_rmvpe", "rvcx_f0_post", "rvcx_synth_infer", "rvcx_dec_only", "rvcx_voice_conversion",
-    "rvcx_synth_upp", "rvcx_set_highpass", "rvcx_pipeline", "rvcx_pipeline_default_opts", "rvcx_pipeline_ex",
-    "rvcx_f0_autotune", "rvcx_rmvpe_decode", "rvcx_profile", "rvcx_profile_read", "rvcx_profile_read_ex", "rvcx_index_load",
-    "rvcx_index_unload", "rvcx_index_info", "rvcx_index_set_nprobe", "rvcx_index_search", "rvcx_index_reconstruct_n",
-    "rvcx_index_retrieve", "rvcx_rt_default_desc", "rvcx_rt_default_opts", "rvcx_rt_create", "rvcx_rt_destroy",
-    "rvcx_rt_geometry", "rvcx_rt_reset", "rvcx_rt_process", "rvcx_rt_process_v", "rvcx_rt_reset_stream", "rvcx_hubert_batch", "rvcx_rmvpe_batch",
-    "rvcx_pipeline_batch", "rvcx_set_highpass_sos", "rvcx_highpass_pad", "rvcx_device_status", "rvcx_index_parse",
-    "rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3", "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair", "rvcx_crepe", "rvcx_split_audio",
-    "rvcx_workspace_bytes", "rvcx_set_workspace", "rvcx_workspace_info", "rvcx_crepe_ex",
-    "rvcx_crepe_decode", "rvcx_set_fcpe_config", "rvcx_fcpe", "rvcx_fcpe_decode", "rvcx_fcpe_b",
-    "rvcx_index_default_build_opts", "rvcx_index_build", "rvcx_index_centroids", "rvcx_index_save",
-    "rvcx_spectral_gate", "rvcx_rt_set_clean", "rvcx_hubert_batch_v", "rvcx_pipeline_batch_v",
-]
-# kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
-TEST_EXPORTS = ["rvcx_performer_attention", "rvcx_performer_attention_b", "rvcx_fcpe_mel", "rvcx_set_dec_window",
-                "rvcx_dec_margin_frames", "rvcx_kmeans_assign", "rvcx_kmeans_update", "rvcx_rt_model_rows",
-                "rvcx_conv_plan", "rvcx_gru_bidir", "rvcx_dec_source"]
 
 
 class RvcxLibraryError(ImportError):
@@ -105,7 +85,7 @@ class RtOpts(ctypes.Structure):
 
 
 class ConvTestDesc(ctypes.Structure):
-    """rvcx_conv_test_desc (include/rvcx.h): one 1-D contraction as the dispatcher's record takes it."""
+    """rvcx_conv_test_desc (include/rvcx_test.h): one 1-D contraction as the dispatcher's record takes it."""
     _fields_ = [
         ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p),
         ("mask", ctypes.c_void_p), ("pre_mask", ctypes.c_void_p), ("y", ctypes.c_void_p),
@@ -144,6 +124,118 @@ class IndexBuildOpts(ctypes.Structure):
                 ("init_rows", ctypes.POINTER(ctypes.c_int64))]
 
 
+vp, i64, i32, f32, f64, u64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double,
+                               ctypes.c_uint64)
+P = ctypes.POINTER
+
+# symbol -> (restype, argtypes): each entry point is listed once, under the header that declares it
+# (tests/test_abi_cpu.py holds both tables against the headers, name by name and parameter count by parameter count)
+
+# the product ABI (include/rvcx.h)
+SIG = {
+    "rvcx_create": (i32, [P(vp), i32]),
+    "rvcx_destroy": (i32, [vp]),
+    "rvcx_last_error": (ctypes.c_char_p, [vp]),
+    "rvcx_set_synth_config": (i32, [vp, P(SynthDesc)]),
+    "rvcx_upload": (i32, [vp, i32, ctypes.c_char_p, vp, P(i64), i32]),
+    "rvcx_finalize": (i32, [vp, i32]),
+    "rvcx_hubert": (i32, [vp, vp, i64, i32, vp, i64, P(i64), vp]),
+    "rvcx_rmvpe": (i32, [vp, vp, i64, f32, vp, i64, P(i64), vp, vp]),
+    "rvcx_f0_post": (i32, [vp, vp, i64, f64, vp, vp, vp, vp]),
+    "rvcx_synth_infer": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
+    "rvcx_synth_infer_ex": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, f64, vp, vp, u64, vp, vp, vp, vp, vp, P(i32),
+                                  vp]),
+    "rvcx_dec_only": (i32, [vp, i32, i32, vp, vp, vp, vp, u64, vp, vp]),
+    "rvcx_voice_conversion": (i32, [vp, vp, i64, vp, vp, i32, f32, f64, vp, vp, u64, vp, i64, P(i64), vp]),
+    "rvcx_synth_upp": (i32, [vp]),
+    "rvcx_set_highpass": (i32, [vp, vp, vp, vp, i32]),
+    "rvcx_profile": (i32, [vp, i32]),
+    "rvcx_profile_read": (i32, [vp, P(f64), P(f64), P(i64)]),
+    "rvcx_profile_read_ex": (i32, [vp, P(f64), P(f64), P(i64), P(f64)]),
+    "rvcx_pipeline": (i32, [vp, vp, i64, i32, f64, f32, i64, i64, vp, vp, u64, vp, i64, P(i64), vp, vp]),
+    "rvcx_pipeline_default_opts": (i32, [P(PipelineOpts)]),
+    "rvcx_pipeline_ex": (i32, [vp, vp, i64, P(PipelineOpts), vp, vp, u64, vp, i64, P(i64), vp, vp]),
+    "rvcx_f0_autotune": (i32, [vp, vp, i64, f64, i32, vp]),
+    "rvcx_rmvpe_decode": (i32, [vp, vp, i64, f32, vp, vp]),
+    "rvcx_crepe": (i32, [vp, vp, i64, f32, f32, f32, vp, vp, vp, i64, P(i64), vp]),
+    "rvcx_crepe_ex": (i32, [vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp, i64, P(i64), vp]),
+    "rvcx_crepe_decode": (i32, [vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp]),
+    "rvcx_set_fcpe_config": (i32, [vp, P(FcpeDesc)]),
+    "rvcx_fcpe": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp, i64, P(i64), vp]),
+    "rvcx_fcpe_decode": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp]),
+    "rvcx_fcpe_b": (i32, [vp, vp, i64, i64, i32, f32, i32, vp, vp, vp]),
+    "rvcx_split_audio": (i32, [vp, vp, i64, i32, f64, i32, P(i64), i64, P(i64), vp]),
+    "rvcx_index_load": (i32, [vp, vp, i64]),
+    "rvcx_index_unload": (i32, [vp]),
+    "rvcx_index_info": (i32, [vp, P(i64), P(i64), P(i64), P(i64)]),
+    "rvcx_index_set_nprobe": (i32, [vp, i64]),
+    "rvcx_index_search": (i32, [vp, vp, i64, i32, vp, vp, vp]),
+    "rvcx_index_reconstruct_n": (i32, [vp, i64, i64, vp, vp]),
+    "rvcx_index_retrieve": (i32, [vp, vp, i64, i32, f64, vp, vp]),
+    "rvcx_index_default_build_opts": (i32, [P(IndexBuildOpts)]),
+    "rvcx_index_build": (i32, [vp, vp, i64, i32, i64, P(IndexBuildOpts), vp]),
+    "rvcx_index_centroids": (i32, [vp, vp, vp]),
+    "rvcx_index_save": (i32, [vp, vp, i64, P(i64)]),
+    "rvcx_pipeline_batch": (i32, [vp, vp, i64, i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp, i64,
+                                  P(i64), vp, vp, vp]),
+    "rvcx_pipeline_batch_v": (i32, [vp, vp, P(i64), i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp,
+                                    i64, P(i64), vp, i64, vp]),
+    "rvcx_set_highpass_sos": (i32, [vp, vp, i32]),
+    "rvcx_workspace_bytes": (i32, [vp, i32, i64, P(PipelineOpts), P(i64), vp]),
+    "rvcx_set_workspace": (i32, [vp, vp, i64]),
+    "rvcx_workspace_info": (i32, [vp, P(i64), P(i64), P(i64)]),
+    "rvcx_highpass_pad": (i32, [vp, vp, i64, i64, vp, vp, vp]),
+    "rvcx_hubert_batch": (i32, [vp, vp, i64, i64, i32, i32, vp, i64, P(i64), vp]),
+    "rvcx_hubert_batch_v": (i32, [vp, vp, P(i64), i64, i32, i32, vp, i64, P(i64), vp]),
+    "rvcx_rmvpe_batch": (i32, [vp, vp, i64, i64, i32, f32, vp, i64, P(i64), vp, vp]),
+    "rvcx_rt_default_desc": (i32, [P(RtDesc)]),
+    "rvcx_rt_default_opts": (i32, [P(RtOpts)]),
+    "rvcx_rt_create": (i32, [vp, P(RtDesc), P(vp)]),
+    "rvcx_rt_destroy": (i32, [vp, vp]),
+    "rvcx_rt_geometry": (i32, [vp, P(i64)]),
+    "rvcx_rt_reset": (i32, [vp, vp, vp]),
+    "rvcx_rt_process": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), vp, vp, u64, vp, vp, vp, vp]),
+    "rvcx_rt_process_v": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), P(ctypes.c_uint8), vp, vp, u64, vp, vp,
+                                vp, vp]),
+    "rvcx_rt_reset_stream": (i32, [vp, vp, i32, vp]),
+    "rvcx_spectral_gate": (i32, [vp, vp, i32, i64, i64, i32, P(f32), vp, i64, vp, vp]),
+    "rvcx_rt_set_clean": (i32, [vp, vp, i32, i32, f64]),
+    "rvcx_device_status": (i32, [vp, vp]),
+    "rvcx_index_parse": (i32, [vp, i64, P(i64), P(i64), P(i64), P(i64), ctypes.c_char_p, i64]),
+    "rvcx_config_info": (i32, [vp, vp, i64, P(i64)]),
+    "rvcx_profile_read_kinds": (i32, [vp, P(f64), P(f64), P(i64), P(f64), i32, P(f64), P(f64), P(f64), P(f64),
+                                      P(i64)]),
+    "rvcx_profile_kind_name": (ctypes.c_char_p, [i32]),
+}
+
+# kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI
+TEST_SIG = {
+    "rvcx_set_conv_math": (i32, [vp, i32]),
+    "rvcx_conv1d": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
+    "rvcx_conv1d_gen": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, i32, f32, i32,
+                              vp, vp]),
+    "rvcx_conv1d_ex": (i32, [vp, P(ConvTestDesc), P(i32), P(i32), vp]),
+    "rvcx_conv2d3x3": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
+    "rvcx_convtranspose2d_s2": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
+    "rvcx_flash_attention": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp]),
+    "rvcx_resblock_pair": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
+    "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
+    "rvcx_performer_attention_b": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
+    "rvcx_fcpe_mel": (i32, [vp, vp, i64, vp, i64, P(i64), vp]),
+    "rvcx_set_dec_window": (i32, [vp, i32]),
+    "rvcx_dec_margin_frames": (i32, [P(SynthDesc), P(i32)]),
+    "rvcx_conv_plan": (i32, [P(ConvTestDesc), P(ConvPlanForm), i32, i32, i32, i32, i32, i32, P(i32), P(i32), P(i32),
+                             P(i32)]),
+    "rvcx_kmeans_assign": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
+    "rvcx_kmeans_update": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
+    "rvcx_rt_model_rows": (i32, [vp, vp, i32, vp, i64, vp]),
+    "rvcx_gru_bidir": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "rvcx_dec_source": (i32, [vp, i32, i32, vp, vp, u64, vp, vp]),
+}
+
+EXPORTS = list(SIG)
+TEST_EXPORTS = list(TEST_SIG)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -160,107 +252,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         lib = ctypes.CDLL(p)
     except OSError as e:
         raise RvcxLibraryError(f"cannot load {p}: {e}") from e
-    vp, i64, i32, f32, f64, u64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double,
-                                   ctypes.c_uint64)
-    P = ctypes.POINTER
-    sig = {
-        "rvcx_create": (i32, [P(vp), i32]),
-        "rvcx_destroy": (i32, [vp]),
-        "rvcx_last_error": (ctypes.c_char_p, [vp]),
-        "rvcx_set_synth_config": (i32, [vp, P(SynthDesc)]),
-        "rvcx_upload": (i32, [vp, i32, ctypes.c_char_p, vp, P(i64), i32]),
-        "rvcx_finalize": (i32, [vp, i32]),
-        "rvcx_hubert": (i32, [vp, vp, i64, i32, vp, i64, P(i64), vp]),
-        "rvcx_rmvpe": (i32, [vp, vp, i64, f32, vp, i64, P(i64), vp, vp]),
-        "rvcx_f0_post": (i32, [vp, vp, i64, f64, vp, vp, vp, vp]),
-        "rvcx_synth_infer": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
-        "rvcx_synth_infer_ex": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, f64, vp, vp, u64, vp, vp, vp, vp, vp, P(i32),
-                                      vp]),
-        "rvcx_dec_only": (i32, [vp, i32, i32, vp, vp, vp, vp, u64, vp, vp]),
-        "rvcx_voice_conversion": (i32, [vp, vp, i64, vp, vp, i32, f32, f64, vp, vp, u64, vp, i64, P(i64), vp]),
-        "rvcx_synth_upp": (i32, [vp]),
-        "rvcx_set_highpass": (i32, [vp, vp, vp, vp, i32]),
-        "rvcx_profile": (i32, [vp, i32]),
-        "rvcx_profile_read": (i32, [vp, P(f64), P(f64), P(i64)]),
-        "rvcx_profile_read_ex": (i32, [vp, P(f64), P(f64), P(i64), P(f64)]),
-        "rvcx_pipeline": (i32, [vp, vp, i64, i32, f64, f32, i64, i64, vp, vp, u64, vp, i64, P(i64), vp, vp]),
-        "rvcx_pipeline_default_opts": (i32, [P(PipelineOpts)]),
-        "rvcx_pipeline_ex": (i32, [vp, vp, i64, P(PipelineOpts), vp, vp, u64, vp, i64, P(i64), vp, vp]),
-        "rvcx_f0_autotune": (i32, [vp, vp, i64, f64, i32, vp]),
-        "rvcx_rmvpe_decode": (i32, [vp, vp, i64, f32, vp, vp]),
-        "rvcx_crepe": (i32, [vp, vp, i64, f32, f32, f32, vp, vp, vp, i64, P(i64), vp]),
-        "rvcx_crepe_ex": (i32, [vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp, i64, P(i64), vp]),
-        "rvcx_crepe_decode": (i32, [vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp]),
-        "rvcx_set_fcpe_config": (i32, [vp, P(FcpeDesc)]),
-        "rvcx_fcpe": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp, i64, P(i64), vp]),
-        "rvcx_fcpe_decode": (i32, [vp, vp, i64, f32, i32, i32, i64, vp, vp]),
-        "rvcx_fcpe_b": (i32, [vp, vp, i64, i64, i32, f32, i32, vp, vp, vp]),
-        "rvcx_fcpe_mel": (i32, [vp, vp, i64, vp, i64, P(i64), vp]),
-        "rvcx_set_dec_window": (i32, [vp, i32]),
-        "rvcx_dec_margin_frames": (i32, [P(SynthDesc), P(i32)]),
-        "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
-        "rvcx_performer_attention_b": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
-        "rvcx_split_audio": (i32, [vp, vp, i64, i32, f64, i32, P(i64), i64, P(i64), vp]),
-        "rvcx_index_load": (i32, [vp, vp, i64]),
-        "rvcx_index_unload": (i32, [vp]),
-        "rvcx_index_info": (i32, [vp, P(i64), P(i64), P(i64), P(i64)]),
-        "rvcx_index_set_nprobe": (i32, [vp, i64]),
-        "rvcx_index_search": (i32, [vp, vp, i64, i32, vp, vp, vp]),
-        "rvcx_index_reconstruct_n": (i32, [vp, i64, i64, vp, vp]),
-        "rvcx_index_retrieve": (i32, [vp, vp, i64, i32, f64, vp, vp]),
-        "rvcx_index_default_build_opts": (i32, [P(IndexBuildOpts)]),
-        "rvcx_index_build": (i32, [vp, vp, i64, i32, i64, P(IndexBuildOpts), vp]),
-        "rvcx_index_centroids": (i32, [vp, vp, vp]),
-        "rvcx_index_save": (i32, [vp, vp, i64, P(i64)]),
-        "rvcx_kmeans_assign": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
-        "rvcx_kmeans_update": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
-        "rvcx_gru_bidir": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
-        "rvcx_dec_source": (i32, [vp, i32, i32, vp, vp, u64, vp, vp]),
-        "rvcx_pipeline_batch": (i32, [vp, vp, i64, i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp, i64,
-                                      P(i64), vp, vp, vp]),
-        "rvcx_pipeline_batch_v": (i32, [vp, vp, P(i64), i64, i32, P(PipelineOpts), P(ctypes.c_int32), vp, vp, u64, vp,
-                                        i64, P(i64), vp, i64, vp]),
-        "rvcx_set_highpass_sos": (i32, [vp, vp, i32]),
-        "rvcx_workspace_bytes": (i32, [vp, i32, i64, P(PipelineOpts), P(i64), vp]),
-        "rvcx_set_workspace": (i32, [vp, vp, i64]),
-        "rvcx_workspace_info": (i32, [vp, P(i64), P(i64), P(i64)]),
-        "rvcx_highpass_pad": (i32, [vp, vp, i64, i64, vp, vp, vp]),
-        "rvcx_hubert_batch": (i32, [vp, vp, i64, i64, i32, i32, vp, i64, P(i64), vp]),
-        "rvcx_hubert_batch_v": (i32, [vp, vp, P(i64), i64, i32, i32, vp, i64, P(i64), vp]),
-        "rvcx_rmvpe_batch": (i32, [vp, vp, i64, i64, i32, f32, vp, i64, P(i64), vp, vp]),
-        "rvcx_rt_default_desc": (i32, [P(RtDesc)]),
-        "rvcx_rt_default_opts": (i32, [P(RtOpts)]),
-        "rvcx_rt_create": (i32, [vp, P(RtDesc), P(vp)]),
-        "rvcx_rt_destroy": (i32, [vp, vp]),
-        "rvcx_rt_geometry": (i32, [vp, P(i64)]),
-        "rvcx_rt_reset": (i32, [vp, vp, vp]),
-        "rvcx_rt_process": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), vp, vp, u64, vp, vp, vp, vp]),
-        "rvcx_rt_process_v": (i32, [vp, vp, vp, P(ctypes.c_int32), P(RtOpts), P(ctypes.c_uint8), vp, vp, u64, vp, vp,
-                                    vp, vp]),
-        "rvcx_rt_reset_stream": (i32, [vp, vp, i32, vp]),
-        "rvcx_spectral_gate": (i32, [vp, vp, i32, i64, i64, i32, P(f32), vp, i64, vp, vp]),
-        "rvcx_rt_set_clean": (i32, [vp, vp, i32, i32, f64]),
-        "rvcx_rt_model_rows": (i32, [vp, vp, i32, vp, i64, vp]),
-        "rvcx_device_status": (i32, [vp, vp]),
-        "rvcx_index_parse": (i32, [vp, i64, P(i64), P(i64), P(i64), P(i64), ctypes.c_char_p, i64]),
-        "rvcx_set_conv_math": (i32, [vp, i32]),
-        "rvcx_set_generator_precision": (i32, [vp, i32]),
-        "rvcx_config_info": (i32, [vp, vp, i64, P(i64)]),
-        "rvcx_profile_read_kinds": (i32, [vp, P(f64), P(f64), P(i64), P(f64), i32, P(f64), P(f64), P(f64), P(f64),
-                                          P(i64)]),
-        "rvcx_profile_kind_name": (ctypes.c_char_p, [i32]),
-        "rvcx_conv1d": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
-        "rvcx_conv1d_gen": (i32, [vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, i32, f32, i32,
-                                  vp, vp]),
-        "rvcx_conv1d_ex": (i32, [vp, P(ConvTestDesc), P(i32), P(i32), vp]),
-        "rvcx_conv_plan": (i32, [P(ConvTestDesc), P(ConvPlanForm), i32, i32, i32, i32, i32, i32, P(i32), P(i32), P(i32),
-                                 P(i32)]),
-        "rvcx_conv2d3x3": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
-        "rvcx_convtranspose2d_s2": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
-        "rvcx_flash_attention": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, vp, vp, vp]),
-        "rvcx_resblock_pair": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in {**SIG, **TEST_SIG}.items():
         if not hasattr(lib, name):  # reported by exported_symbols(); an older build lacks newer entry points
             continue
         fn = getattr(lib, name)

@@ -1,16 +1,38 @@
-"""CPU-side checks of the C-ABI library: it exists, loads, and exports every symbol the header
-declares (no compute calls: there is no GPU here)."""
+"""CPU-side checks of the C-ABI library: it exists, loads, exports every symbol the two headers declare (the product
+ABI include/rvcx.h, the kernel-level test entries include/rvcx_test.h), binds each with as many parameters as its
+prototype has, and keeps the two surfaces apart (no compute calls: there is no GPU here)."""
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# the kernel-level entries that used to sit in rvcx.h: test-only, so declared in rvcx_test.h alone
+MOVED_TO_TEST_HEADER = ["rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3",
+                        "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair"]
+
+
+def header_prototypes(name):
+    """{entry point: number of parameters} of include/<name>: comments stripped, then every `int` / `const char*`
+    function named rvcx_*, its parameters counted by the top-level commas of the parameter list."""
+    src = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", name)).read(), flags=re.S)
+    protos = {}
+    for m in re.finditer(r"^\s*(?:int|const char\*)\s+(rvcx_[a-z0-9_]+)\s*\(([^;{}]*)\)\s*;", src, re.M):
+        params, depth, commas = m.group(2).strip(), 0, 0
+        for ch in params:
+            depth += ch in "(["
+            depth -= ch in ")]"
+            commas += ch == "," and depth == 0
+        assert m.group(1) not in protos, f"{m.group(1)} declared twice in {name}"
+        protos[m.group(1)] = 0 if params in ("", "void") else commas + 1
+    return protos
+
 
 def header_symbols():
-    src = open(os.path.join(REPO, "include", "rvcx.h")).read()
-    return sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(rvcx_[a-z0-9_]+)\s*\(", src, re.M)))
+    return sorted(header_prototypes("rvcx.h"))
 
 
 def test_header_lists_entry_points():
@@ -24,10 +46,63 @@ def test_library_exports_every_header_symbol():
 
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail(f"{_lib.LIB_PATH} missing: run __graft_entry__.build()")
+    product, test = set(header_prototypes("rvcx.h")), set(header_prototypes("rvcx_test.h"))
     exported = set(_lib.exported_symbols())
-    missing = [s for s in header_symbols() if s not in exported]
+    missing = sorted((product | test) - exported)
     assert not missing, missing
-    assert set(_lib.EXPORTS) == set(header_symbols())
+    assert set(_lib.EXPORTS) == product
+    assert set(_lib.TEST_EXPORTS) == test
+    assert not product & test, sorted(product & test)
+    assert len(_lib.EXPORTS) == len(product) and len(_lib.TEST_EXPORTS) == len(test)  # each symbol listed once
+
+
+def test_bindings_take_as_many_parameters_as_the_prototypes():
+    """For every entry point of both headers: the parameter count of the declaration equals len(argtypes) of its
+    ctypes binding, in the table and on the loaded library."""
+    from rvcx import _lib
+
+    lib = _lib.load()
+    protos = {**header_prototypes("rvcx.h"), **header_prototypes("rvcx_test.h")}
+    table = {**_lib.SIG, **_lib.TEST_SIG}
+    assert len(protos) >= 87
+    wrong = {n: (k, len(table[n][1])) for n, k in protos.items() if len(table[n][1]) != k}
+    assert not wrong, f"(prototype, binding) parameter counts differ: {wrong}"
+    unbound = [n for n in protos if getattr(lib, n).argtypes is None or len(getattr(lib, n).argtypes) != protos[n]]
+    assert not unbound, unbound
+
+
+@pytest.mark.parametrize("header", ["rvcx.h", "rvcx_test.h"])
+def test_header_compiles_alone_as_c99(header, tmp_path):
+    """Each header is a C header a product can include on its own (rvcx_test.h includes rvcx.h itself)."""
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if cc is None:
+        pytest.skip("no C compiler (cc / gcc) on PATH")
+    src = tmp_path / "one.c"
+    src.write_text(f'#include "{header}"\n')
+    r = subprocess.run([cc, "-std=c99", "-pedantic", "-Wall", "-fsyntax-only",
+                        "-I" + os.path.join(REPO, "include"), str(src)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr
+
+
+def test_kernel_test_entries_are_declared_in_the_test_header_only():
+    """The product header holds no entry that exists for the numerics tests, and the shim
+    rvcx_set_generator_precision (an unconditional error since the per-hop rvcx_rt_opts.gen_precision) is gone from
+    both headers, the bindings and the library."""
+    import ctypes
+
+    from rvcx import _lib
+    from rvcx.engine import Engine
+
+    product, test = header_prototypes("rvcx.h"), header_prototypes("rvcx_test.h")
+    for name in MOVED_TO_TEST_HEADER:
+        assert name in test and name not in product, name
+        assert name in _lib.TEST_SIG and name not in _lib.SIG, name
+    assert "rvcx_conv_test_desc" not in open(os.path.join(REPO, "include", "rvcx.h")).read()
+    assert "} rvcx_conv_test_desc;" in open(os.path.join(REPO, "include", "rvcx_test.h")).read()
+    gone = "rvcx_set_generator_precision"
+    assert gone not in product and gone not in test and gone not in _lib.SIG and gone not in _lib.TEST_SIG
+    assert not hasattr(ctypes.CDLL(_lib.LIB_PATH), gone)
+    assert not hasattr(Engine, "set_generator_precision")
 
 
 def test_recurrence_test_entries_are_exported_and_bound():
