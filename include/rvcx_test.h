@@ -51,7 +51,7 @@ int rvcx_conv1d_gen(rvcx_ctx* ctx, const float* d_x, int64_t T, int C_in, const 
                     const float* d_res, int acc_mode, float acc_div, int kernel, float* d_y, void* stream);
 
 /* One 1-D contraction in any form the runtime issues (csrc/runtime_synth.cpp, runtime_fe.cpp), described field by
- * field as the dispatcher's own record (ConvArgs, csrc/rvcx_kernels.h) takes it. All pointers are device pointers, all
+ * field as the dispatcher's own record (ConvArgs, csrc/conv_kernels.h) takes it. All pointers are device pointers, all
  * strides in floats; w is [taps][N][C_in] per group (rvcx_conv1d's layout), bias [N] per group.
  *   input     pre(x[b][row][c]) * pre_mask[b][row], zero outside [0, T_in); row = m stride - pad + tap dil
  *   value     v = act(alpha (acc + bias [+ res: res_mode 1])); res_mode 2: v + res, 3: res - v; acc_mode 1: y + v,
@@ -216,7 +216,7 @@ int rvcx_gru_bidir(rvcx_ctx* ctx, const float* d_gi, int B, int T, const float* 
                    const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream);
 
 /* The generator's harmonic source alone, as the decoder of the loaded configuration computes it: NSF SineGen +
- * l_linear + tanh (k_sine_cum / k_sine, csrc/aux_kernels.hip) or the 9-harmonic MRF source (csrc/source_harm.hip).
+ * l_linear + tanh (k_sine_cum / k_sine, csrc/nsf_source.hip) or the 9-harmonic MRF source (csrc/source_harm.hip).
  * d_f0 [B][T] -> d_har [B][T * upp]. d_eps_src as rvcx_dec_only takes it (NSF: [B][T * upp] N(0, 1); MRF:
  * [B][T * upp][9] N(0, 1) then [B][9] U(0, 1) initial phases; NULL: drawn from `seed`). RVCX_E_STATE without a
  * finalized pitch-guided synthesizer with one of these two decoders. */

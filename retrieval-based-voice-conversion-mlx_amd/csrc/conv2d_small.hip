@@ -16,7 +16,6 @@
 
 #include <cstdlib>
 
-#include "rvcx_kernels.h"
 #include "split_bf16.h"
 
 namespace rvcx {

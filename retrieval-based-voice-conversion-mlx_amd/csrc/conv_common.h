@@ -2,7 +2,7 @@
 // three bf16 planes; the streamed kernels): activations, the fused epilogue, the accumulator -> HBM store of one block
 // tile, and what the conv translation units declare to each other.
 #pragma once
-#include "rvcx_kernels.h"
+#include "conv_kernels.h"
 
 namespace rvcx {
 

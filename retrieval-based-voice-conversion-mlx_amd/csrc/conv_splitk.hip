@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "conv_common.h"
+#include "device_util.h"
 
 namespace rvcx {
 
@@ -44,10 +45,6 @@ __global__ void splitk_reduce_kernel(const ConvArgs a, const int ksplit, const i
 // (a wave per row with the loads in a column loop measured 16 us against 5.6 + 7 for the two passes). The arithmetic
 // is splitk_reduce_kernel's epilogue followed by k_layernorm's on (res + v); the mean and variance sum the columns in
 // another order (block-wide), so the result equals the two passes to fp32 rounding of those sums.
-__device__ __forceinline__ float wave_sum64(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const ConvArgs a, const int ksplit) {
   __shared__ float red[2][4];
   const long long row = blockIdx.x;
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const ConvArgs a,
     v[j] = t;
     s += t;
   }
-  s = wave_sum64(s);
+  s = wave_sum(s);
   if (lane == 0) red[0][wave] = s;
   __syncthreads();
   const float mean = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)a.N;
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const ConvArgs a,
       q += d * d;
     }
   }
-  q = wave_sum64(q);
+  q = wave_sum(q);
   if (lane == 0) red[1][wave] = q;
   __syncthreads();
   const float var = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)a.N;
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const ConvArgs a,
 namespace {
 
 // the split-K combine of a gated WaveNet in_layer (ConvArgs::gate_h): the pair (c, c + H) of one output row per thread
-// (k_gate's arithmetic, aux_kernels.hip), acts [rows][ldy]
+// (tanh(u) * sigmoid(v), each with the conditioning added first), acts [rows][ldy]
 __global__ void splitk_reduce_gate_kernel(const ConvArgs a, const int ksplit) {
   const unsigned H = (unsigned)a.gate_h;
   const unsigned per_b = (unsigned)(a.ws_rows * a.N), per_o = (unsigned)a.ws_rows * H;

@@ -71,7 +71,7 @@ __global__ void k_wmax_col(const float* __restrict__ w, int ldw, long long w_ts,
   if (n < N)
     for (int tap = 0; tap < taps; ++tap)
       for (int c = lane; c < C_in; c += 64) m = fmaxf(m, fabsf(w[tap * w_ts + (long long)n * ldw + c]));
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if (lane == 0) colmax[n] = __float_as_uint(m);
 }
 __global__ void k_wsplit_h16(const float* __restrict__ w, int ldw, long long w_ts, int N, int C_in, int taps,

@@ -4,7 +4,8 @@
 // Reference: rvc_mlx/lib/mlx/crepe.py (CREPEModel :48-222, CREPE.get_f0 :282-325).
 #include <algorithm>
 
-#include "rvcx_kernels.h"
+#include "crepe_kernels.h"
+#include "device_util.h"
 
 namespace rvcx {
 
@@ -13,7 +14,7 @@ constexpr int CR_WIN = 1024, CR_HOP = 160, CR_PAD1 = 254, CR_BINS = 360;
 constexpr int CR_T = 256;
 
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();
   if (lane == 0) red[w] = v;
@@ -211,7 +212,7 @@ constexpr int VBAND = 11;               // the transition matrix max(12 - |i - j
 constexpr double V_TINY = 1.1754943508222875e-38;  // np.finfo(float32).tiny: librosa's epsilon for float32 probs
 
 __device__ __forceinline__ float block_max_f(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  v = wave_max(v);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();
   if (lane == 0) red[w] = v;
@@ -221,7 +222,7 @@ __device__ __forceinline__ float block_max_f(float v, float* red) {
   return r;
 }
 __device__ __forceinline__ float block_sum_f(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();
   if (lane == 0) red[w] = v;

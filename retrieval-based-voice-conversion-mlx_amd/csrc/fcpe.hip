@@ -1,25 +1,18 @@
 // Non-GEMM kernels of the FCPE pitch network (rvc/lib/predictors/FCPE.py): the input stack's GroupNorm + LeakyReLU,
 // the Conformer module's GLU + depthwise conv + Swish, the cents decoders and FCPEF0Predictor.post_process (the STFT
-// magnitude of its mel is aux_kernels.hip's, shared with RMVPE). The Performer attention is performer_attn.hip; the convs and linears run on the
-// implicit-GEMM family. The kernels that pad or reduce over time (GroupNorm, the depthwise conv, the mel's padding
+// magnitude of its mel is rmvpe_aux.hip's, shared with RMVPE). The Performer attention is performer_attn.hip; the convs
+// and linears run on the implicit-GEMM family. The kernels that pad or reduce over time (GroupNorm, the depthwise conv, the mel's padding
 // and repeated last frame) take B streams of one length per launch, grid z (or y) = stream, each stream on its own
 // rows; the row-wise ones (the decoders) run on the B F rows of all streams.
 #include <algorithm>
 #include <cmath>
 
-#include "rvcx_kernels.h"
+#include "device_util.h"
+#include "fcpe_kernels.h"
 
 namespace rvcx {
 
 namespace {
-
-constexpr int TB = 256;
-
-inline unsigned nblocks(long long n, int per = TB) {
-  long long b = (n + per - 1) / per;
-  if (b > 65535LL * 32) b = 65535LL * 32;
-  return (unsigned)(b < 1 ? 1 : b);
-}
 
 __device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
 
@@ -164,9 +157,9 @@ __global__ void k_fcpe_decode(const float* sal, int F, int nb, const float* cent
       best = ov;
       bi = oi;
     }
-    num += __shfl_xor(num, o, 64);
-    den += __shfl_xor(den, o, 64);
   }
+  num = wave_sum(num);
+  den = wave_sum(den);
   if (lane != 0) return;
   if (mode == 0) {
     num = 0.0;

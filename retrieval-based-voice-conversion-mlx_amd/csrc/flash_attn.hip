@@ -15,6 +15,7 @@
 #include <cmath>
 #include <string>
 
+#include "attention_kernels.h"
 #include "split_bf16.h"
 
 namespace rvcx {

@@ -20,7 +20,7 @@
 // n = tanh(ig_n + hg_n * r), h' = (h - n) * z + n, with hg = W_hh h + b_hh.
 #include <cstdlib>
 
-#include "rvcx_kernels.h"
+#include "fe_kernels.h"
 
 namespace rvcx {
 

@@ -17,7 +17,7 @@
 
 #include <algorithm>
 
-#include "rvcx_kernels.h"
+#include "pipeline_kernels.h"
 
 namespace rvcx {
 

@@ -19,7 +19,8 @@
 #include <cfloat>
 #include <climits>
 
-#include "rvcx_kernels.h"
+#include "device_util.h"
+#include "ivf_kernels.h"
 
 namespace rvcx {
 
@@ -27,18 +28,12 @@ namespace {
 
 constexpr int WAVE = 64;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-
 // (dist, tie) lexicographic "a strictly before b"
 __device__ __forceinline__ bool key_lt(float da, long long ta, float db, long long tb) {
   return da < db || (da == db && ta < tb);
 }
 
-// row of x / out that query q reads and writes (IvfRows, rvcx_kernels.h)
+// row of x / out that query q reads and writes (IvfRows, ivf_kernels.h)
 __device__ __forceinline__ long long query_row(const IvfRows& R, int q) {
   if (!R.seqs) return q;
   const int Lq = R.L - R.off;

@@ -19,7 +19,8 @@
 #include <cfloat>
 #include <climits>
 
-#include "rvcx_kernels.h"
+#include "device_util.h"
+#include "ivf_kernels.h"
 
 namespace rvcx {
 
@@ -54,8 +55,7 @@ __global__ void __launch_bounds__(256) k_kmeans_norms(const float* __restrict__ 
     const double v = p[i];
     acc += v * v;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum(acc);
   if (lane == 0) norms[r] = (float)acc;
 }
 
@@ -194,8 +194,7 @@ __global__ void __launch_bounds__(256) k_kmeans_dist(const float* __restrict__ x
     const float t = xp[i] - cp[i];
     acc = fmaf(t, t, acc);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum(acc);
   if (lane == 0) dist[q] = acc;
 }
 

@@ -29,7 +29,7 @@
 // (stream, head), and no load is clamped or reduced across a stream's rows. B = 1 is the single-utterance form.
 #include <cmath>
 
-#include "rvcx_kernels.h"
+#include "fcpe_kernels.h"
 
 namespace rvcx {
 

@@ -4,38 +4,14 @@
 // contractions (every Conv1d) run on the MFMA conv kernels. These are HBM / L2 bound.
 #include <cmath>
 
-#include "rvcx_kernels.h"
+#include "device_util.h"
+#include "vocoder_kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace rvcx {
 
 namespace {
-
-__device__ __forceinline__ void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-__device__ __forceinline__ float normal_at(uint64_t seed, uint64_t idx) {
-  uint32_t c[4] = {(uint32_t)(idx >> 1), (uint32_t)(idx >> 33), 0x41444149u, 2u};
-  philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float u1 = ((c[0] >> 8) + 1) * (1.0f / 16777217.0f);
-  const float u2 = (c[1] >> 8) * (1.0f / 16777216.0f);
-  const float r = sqrtf(-2.f * logf(u1));
-  const float th = 6.283185307179586f * u2;
-  return (idx & 1) ? r * sinf(th) : r * cosf(th);
-}
 
 __device__ __forceinline__ float lrelu(float v, float s) { return v > 0.f ? v : v * s; }
 
@@ -104,7 +80,7 @@ __global__ void k_adain(const float* __restrict__ x, int B, int T, int C, const 
     const long long bt = i / C;
     const int b = (int)(bt / T), t = (int)(bt % T);
     const long long ei = ((long long)b * C + c) * T + t;
-    const float e = eps ? eps[ei] : normal_at(seed, (uint64_t)ei);
+    const float e = eps ? eps[ei] : normal_at(seed, (uint64_t)ei, 0x41444149u, 2u);
     const float v = lrelu(x[i] + e * w[c], slope);
     if (mode == 0) y[i] = v;
     else if (mode == 1) y[i] = y[i] + v;

@@ -82,7 +82,7 @@ __global__ void k_rb_wmax(const float* __restrict__ w, int C, int k, unsigned* _
   float m = 0.f;
   for (int tap = 0; tap < k; ++tap)
     for (int c = lane; c < C; c += 64) m = fmaxf(m, fabsf(w[((long long)tap * C + o) * C + c]));
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  m = wave_max(m);
   if (lane == 0) chmax[o] = __float_as_uint(m);
 }
 __global__ void k_rb_wsplit_h16(const float* __restrict__ w, int C, int k, int NP, unsigned short* __restrict__ out,

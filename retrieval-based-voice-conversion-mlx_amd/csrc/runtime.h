@@ -44,8 +44,13 @@ struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
+  ~DevBuf() { reset(); }
+  // back to the empty state (frees an owned allocation)
+  void reset() {
     if (p && !borrowed) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    borrowed = false;
   }
 };
 

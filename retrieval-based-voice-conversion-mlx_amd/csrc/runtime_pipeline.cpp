@@ -28,60 +28,46 @@ void set_highpass(Ctx& c, const double* b, const double* a, const double* zi, in
   for (auto& v : c.hp_a) v /= a0;
 }
 
-// SOS plan (iir_scan.hip): per section the DF2T biquad, its steady state for a unit pass input (scipy
+// SOS plan (iir_scan.hip): per section the DF2T biquad and its steady state for a unit pass input (scipy
 // filtfilt's zi * x0: the whole cascade at rest on the constant x0, DC gains of the preceding sections
-// included), A^(L 2^s) for the carry scan and the rows C A^k of the chunk fix-up.
+// included); for the cascade as one system A^(L 2^s) for the carry scan and the rows C A^k of the chunk fix-up.
 void set_highpass_sos(Ctx& c, const double* sos, int nsec) {
   if (nsec < 1 || nsec > IIR_MAXO) throw Error(RVCX_E_INVALID, "highpass: bad section count");
   SosPlan p;
   p.nsec = nsec;
-  p.L = 256;
   if (nsec > 4) throw Error(RVCX_E_INVALID, "highpass: more than 4 sections");
-  std::vector<double> tab((size_t)nsec * p.stride(), 0.0);
+  // per section: b0 b1 b2 a1 a2, then its two steady-state values
+  struct Sec {
+    double t[5], w[2];
+  };
+  std::vector<Sec> sec(nsec);
   double gain = 1.0;  // DC gain of the sections before j
   for (int j = 0; j < nsec; ++j) {
     const double* q = sos + 6 * j;
     if (!(q[3] != 0.0)) throw Error(RVCX_E_INVALID, "highpass: section a0 == 0");
     const double b0 = q[0] / q[3], b1 = q[1] / q[3], b2 = q[2] / q[3], a1 = q[4] / q[3], a2 = q[5] / q[3];
-    double* t = tab.data() + (size_t)j * p.stride();
+    double* t = sec[j].t;
     t[0] = b0, t[1] = b1, t[2] = b2, t[3] = a1, t[4] = a2;
     // steady state z = (I - A)^-1 B u with A = [[-a1, 1], [-a2, 0]], B = [b1 - a1 b0, b2 - a2 b0], u = gain
     const double B0 = b1 - a1 * b0, B1 = b2 - a2 * b0;
     const double det = (1.0 + a1) * 1.0 + a2;  // det(I - A) = (1 + a1) * 1 - (-1) * (a2)
     if (!(std::fabs(det) > 1e-300)) throw Error(RVCX_E_INVALID, "highpass: section has a pole at z = 1");
     // (I - A) = [[1 + a1, -1], [a2, 1]] -> inverse = [[1, 1], [-a2, 1 + a1]] / det
-    t[8] = (B0 + B1) / det * gain;
-    t[9] = (-a2 * B0 + (1.0 + a1) * B1) / det * gain;
+    sec[j].w[0] = (B0 + B1) / det * gain;
+    sec[j].w[1] = (-a2 * B0 + (1.0 + a1) * B1) / det * gain;
     gain *= (b0 + b1 + b2) / (1.0 + a1 + a2);
-    // A^L then squarings: pow[s] = A^(L 2^s), s = 0..10
-    double M[4] = {1, 0, 0, 1};
-    double* ca = t + 64;
-    for (int k = 0; k < p.L; ++k) {
-      ca[2 * k] = M[0];
-      ca[2 * k + 1] = M[1];
-      const double n0 = -a1 * M[0] + M[2], n1 = -a1 * M[1] + M[3], n2 = -a2 * M[0], n3 = -a2 * M[1];
-      M[0] = n0, M[1] = n1, M[2] = n2, M[3] = n3;  // M <- A M
-    }
-    for (int sidx = 0; sidx < 11; ++sidx) {
-      double* P = t + 16 + 4 * sidx;
-      P[0] = M[0], P[1] = M[1], P[2] = M[2], P[3] = M[3];
-      const double n0 = M[0] * M[0] + M[1] * M[2], n1 = M[0] * M[1] + M[1] * M[3];
-      const double n2 = M[2] * M[0] + M[3] * M[2], n3 = M[2] * M[1] + M[3] * M[3];
-      M[0] = n0, M[1] = n1, M[2] = n2, M[3] = n3;
-    }
   }
   // the cascade as ONE system of NS = 2 nsec states (iir_scan.hip casc_filtfilt_pad): its A and C by stepping the
   // cascade from unit states with zero input, the steady state w = the per-section states above, A^(L 2^s) and
   // the rows C A^k of the chunk fix-up
   const int NS = 2 * nsec, L = p.casc_L;
-  const size_t casc_off = tab.size();
-  tab.resize(casc_off + 48 + 64 * 12 + 8 * (size_t)L, 0.0);
-  double* ct = tab.data() + casc_off;
+  std::vector<double> tab(48 + 64 * 12 + 8 * (size_t)L, 0.0);
+  double* ct = tab.data();
   std::vector<double> A((size_t)NS * NS), C(NS);
   auto step = [&](const double* z, double x, double* zo) {
     double u = x;
     for (int j = 0; j < nsec; ++j) {
-      const double* t = tab.data() + (size_t)j * p.stride();
+      const double* t = sec[j].t;
       const double y = t[0] * u + z[2 * j];
       zo[2 * j] = t[1] * u - t[3] * y + z[2 * j + 1];
       zo[2 * j + 1] = t[2] * u - t[4] * y;
@@ -96,10 +82,9 @@ void set_highpass_sos(Ctx& c, const double* sos, int nsec) {
     for (int r = 0; r < NS; ++r) A[(size_t)r * NS + i] = zo[r];
   }
   for (int j = 0; j < nsec; ++j) {
-    const double* t = tab.data() + (size_t)j * p.stride();
-    for (int q = 0; q < 5; ++q) ct[5 * j + q] = t[q];
-    ct[40 + 2 * j] = t[8];
-    ct[40 + 2 * j + 1] = t[9];
+    for (int q = 0; q < 5; ++q) ct[5 * j + q] = sec[j].t[q];
+    ct[40 + 2 * j] = sec[j].w[0];
+    ct[40 + 2 * j + 1] = sec[j].w[1];
   }
   auto mul = [&](const std::vector<double>& X, const std::vector<double>& Y) {
     std::vector<double> Z((size_t)NS * NS, 0.0);
@@ -125,8 +110,7 @@ void set_highpass_sos(Ctx& c, const double* sos, int nsec) {
     M = mul(M, M);
   }
   RVCX_HIP(hipSetDevice(c.device));
-  c.hp_sos_buf.~DevBuf();
-  new (&c.hp_sos_buf) DevBuf();
+  c.hp_sos_buf.reset();
   const size_t bytes = tab.size() * sizeof(double);
   if (hipMalloc(&c.hp_sos_buf.p, bytes) != hipSuccess) {
     (void)hipGetLastError();
@@ -134,21 +118,20 @@ void set_highpass_sos(Ctx& c, const double* sos, int nsec) {
   }
   c.hp_sos_buf.bytes = bytes;
   RVCX_HIP(hipMemcpy(c.hp_sos_buf.p, tab.data(), bytes, hipMemcpyHostToDevice));
-  p.dev = static_cast<const double*>(c.hp_sos_buf.p);
-  p.casc = p.dev + casc_off;
+  p.casc = static_cast<const double*>(c.hp_sos_buf.p);
   c.hp_sos = p;
 }
 
 void highpass_pad(Ctx& c, const double* audio, int64_t n, int64_t t_pad, double* pad64, float* pad32, hipStream_t s) {
   if (c.hp_order == 0) throw Error(RVCX_E_STATE, "pipeline: high-pass filter not configured");
   if (c.hp_sos.nsec > 0) {
-    double* ws = c.buf<double>("pl.sosws", filtfilt_sos_ws_doubles(n, c.hp_order, c.hp_sos.L), s);
+    double* ws = c.buf<double>("pl.sosws", filtfilt_sos_ws_doubles(n, c.hp_order), s);
     check(filtfilt_sos_pad(c.hp_sos, c.hp_order, audio, n, t_pad, ws, pad64, pad32, s), "filtfilt_sos");
     return;
   }
   double* ws = c.buf<double>("pl.iirws", filtfilt_ws_doubles(n, c.hp_order), s);
-  check(filtfilt_pad(audio, n, c.hp_b.data(), c.hp_a.data(), c.hp_zi.data(), nullptr, c.hp_order, t_pad, ws, pad64,
-                     pad32, s),
+  check(filtfilt_pad(audio, n, c.hp_b.data(), c.hp_a.data(), c.hp_zi.data(), c.hp_order, t_pad, ws, pad64, pad32,
+                     s),
         "filtfilt_pad");
 }
 

@@ -16,7 +16,8 @@
 // bit-identical to torch's sequential loop. Elementwise float ops keep torch's rounding (no FMA contraction).
 #include <cmath>
 
-#include "rvcx_kernels.h"
+#include "device_util.h"
+#include "vocoder_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -27,36 +28,6 @@ namespace {
 constexpr int SH_T = 256;   // threads per block
 constexpr int SH_V = 4;     // consecutive samples per thread
 constexpr int SH_CHUNK = SH_T * SH_V;
-
-__device__ __forceinline__ void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-__device__ __forceinline__ float normal_at(uint64_t seed, uint64_t idx) {
-  uint32_t c[4] = {(uint32_t)(idx >> 1), (uint32_t)(idx >> 33), 0x48524d53u, 0u};
-  philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float u1 = ((c[0] >> 8) + 1) * (1.0f / 16777217.0f);
-  const float u2 = (c[1] >> 8) * (1.0f / 16777216.0f);
-  const float r = sqrtf(-2.f * logf(u1));
-  const float th = 6.283185307179586f * u2;
-  return (idx & 1) ? r * sinf(th) : r * cosf(th);
-}
-__device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t idx) {
-  uint32_t c[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), 0x494e4954u, 1u};
-  philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  return (c[0] >> 8) * (1.0f / 16777216.0f);  // [0, 1)
-}
 
 struct Src {
   const float* f0;  // [B][L] frame f0
@@ -90,7 +61,7 @@ __device__ __forceinline__ float rad_at(const Src& s, const float* fb, long long
 
 __device__ __forceinline__ float ini_at(const Src& s, int b, int h) {
   if (h == 0) return 0.f;  // rand_ini[:, 0] = 0
-  return s.ini ? s.ini[b * s.H + h] : uniform_at(s.seed, (uint64_t)b * s.H + h);
+  return s.ini ? s.ini[b * s.H + h] : uniform_at(s.seed, (uint64_t)b * s.H + h, 0x494e4954u, 1u);
 }
 
 // exclusive block scan of one double per thread; returns this thread's exclusive prefix and the block total
@@ -224,7 +195,7 @@ __global__ __launch_bounds__(SH_T) void k_harm_emit(Src s, const double* pre1, c
       const float uv = uvv[v];
       const float amp = uv * amp_v + (1.f - uv) * 0.1f / 3.0f;
       const long long ei = ((long long)b * N + n0 + v) * s.H + h;
-      const float e = s.eps ? s.eps[ei] : normal_at(s.seed, (uint64_t)ei);
+      const float e = s.eps ? s.eps[ei] : normal_at(s.seed, (uint64_t)ei, 0x48524d53u, 0u);
       const float xv = sine * uv + amp * e;
       mix[v] = (h == 0) ? xv * w : mix[v] + xv * w;
     }

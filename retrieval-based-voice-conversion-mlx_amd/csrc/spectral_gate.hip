@@ -21,7 +21,7 @@
 
 #include <cmath>
 
-#include "rvcx_kernels.h"
+#include "stream_kernels.h"
 
 namespace rvcx {
 

@@ -3,6 +3,7 @@
 // [hi | mid | lo] x 32 channels + 16 B pad = ERS bytes (16 consecutive rows hit 16 distinct 4-bank groups).
 #pragma once
 #include "conv_common.h"
+#include "device_util.h"
 
 namespace rvcx {
 namespace splitbf16 {
@@ -76,7 +77,7 @@ __device__ __forceinline__ float f16hi_f(unsigned p) { return (float)__builtin_b
 // (non-negative floats order as their bit patterns: atomicMax on the bits, one per wave), then the split kernel turns
 // it into the power of two sc with max |w| sc in [128, 256) (small weights stay normal fp16).
 __device__ __forceinline__ void absmax_wave_publish(float m, unsigned* dst) {
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(dst, __float_as_uint(m));
 }
 __device__ __forceinline__ float h16_weight_scale(unsigned mbits) {

@@ -12,7 +12,8 @@
 
 #include <algorithm>
 
-#include "rvcx_kernels.h"
+#include "device_util.h"
+#include "stream_kernels.h"
 
 namespace rvcx {
 
@@ -20,8 +21,7 @@ namespace {
 constexpr int RT_TB = 256;
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 0) red[w] = v;
   __syncthreads();
@@ -234,11 +234,8 @@ __global__ void __launch_bounds__(RT_TB) k_rt_sola(const float* __restrict__ aud
       nom = fmaf(v, sb[i], nom);
       den = fmaf(v, v, den);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      nom += __shfl_xor(nom, o, 64);
-      den += __shfl_xor(den, o, 64);
-    }
+    nom = wave_sum(nom);
+    den = wave_sum(den);
     if (lane == 0) ratio[k] = nom / sqrtf(den + 1e-8f);
   }
   __syncthreads();

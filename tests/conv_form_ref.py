@@ -1,7 +1,7 @@
 """The 1-D contraction forms the runtime issues, stated in torch at any dtype (test helper, no GPU needed).
 
 `ref(d, dtype)` evaluates one form on logical arrays (no strides: x [B][G][T_in][C_in], w [G][taps][N][C_in], ...) with
-the semantics documented at ConvArgs (csrc/rvcx_kernels.h) and spelled out by epilogue_store (csrc/conv_common.h):
+the semantics documented at ConvArgs (csrc/conv_kernels.h) and spelled out by epilogue_store (csrc/conv_common.h):
 
     input   pre(x) * pre_mask, zero outside [0, T_in); row of output m, tap k: m stride - pad + k dil
     value   acc = sum x W; v = acc + bias; RES_ADD_PRE: v += R; v *= alpha; v = act(v);
@@ -22,7 +22,7 @@ import zlib
 import numpy as np
 import torch
 
-NONE, LRELU, RELU, GELU, TANH, SIGMOID, LOGCLAMP = range(7)  # Act (csrc/rvcx_kernels.h)
+NONE, LRELU, RELU, GELU, TANH, SIGMOID, LOGCLAMP = range(7)  # Act (csrc/kernel_base.h)
 RES_NONE, RES_ADD_PRE, RES_ADD_POST, RES_RSUB_POST = range(4)
 ACC_STORE, ACC_ADD, ACC_ADD_DIV = range(3)
 SENTINEL = np.array([0xDEADBEEF], np.uint32).view(np.float32)[0]  # finite, never a result

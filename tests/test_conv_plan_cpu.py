@@ -17,7 +17,7 @@ import pytest
 from rvcx import _lib
 
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_routes.json")
-# ConvKind (csrc/rvcx_kernels.h)
+# ConvKind (csrc/conv_kernels.h)
 CK_WSB16, CK_WSB, CK_GS, CK_GSW, CK_RBPAIR, CK_SMALL2D, CK_EMU, CK_GEMM, CK_TINY, CK_WST, CK_OTHER = range(11)
 # what a conv launch can produce: not the fused ResBlock pair (its own launcher), not "other", and not conv_wsb_kernel
 # (the bf16 32x32x16 form, which no longer exists)

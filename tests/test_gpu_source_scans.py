@@ -1,5 +1,5 @@
 """The generators' harmonic sources alone (rvcx_dec_source, include/rvcx_test.h): NSF SineGen (k_sine_cum / k_sine,
-csrc/aux_kernels.hip) and the 9-harmonic MRF source (csrc/source_harm.hip), whose phase scans claim to be bit-identical
+csrc/nsf_source.hip) and the 9-harmonic MRF source (csrc/source_harm.hip), whose phase scans claim to be bit-identical
 to torch's sequential double-accumulated loops. The noise and, for MRF, the initial phases are injected.
 
 Two checks per case:

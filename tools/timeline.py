@@ -15,7 +15,7 @@ def phase(name):
         return "rmvpe"
     if "gn_" in n:
         return "hubert"
-    if "sine" in n or "conv_post" in n or "k_zp" in n or "k_gate" in n or "flip" in n or "softmax_rel" in n:
+    if "sine" in n or "conv_post" in n or "k_zp" in n or "flip" in n or "softmax_rel" in n:
         return "synth"
     return "other"
 
