@@ -109,6 +109,21 @@ int rvcx_rmvpe_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t lda
 int rvcx_hubert_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, int version,
                         float* d_feats, int64_t ld_rows, int64_t* L_out, void* stream);
 
+/* RMVPE over B inputs of different lengths in one launch set: row b has n[b] samples (host array) at
+ * d_audio + b*lda (lda >= every n[b]; samples past n[b] are never read). Row b's f0 [F_b] fp64, F_b = 1 + n[b]/160
+ * (written to F_out[b], host, optional), lands at d_f0 + b*ldf, and its salience [F_b][360] (d_hidden, optional) at
+ * d_hidden + b*ld_hidden_frames*360; ldf (and ld_hidden_frames) must hold the longest row's frames, else
+ * RVCX_E_CAPACITY. Values of a row past F_b are not written. Every row equals rvcx_rmvpe's on that input alone up to
+ * summation order: the mel and the frame padding reflect about the row's own end, every 3x3 conv and up-conv of the
+ * U-Net reads zero past the row's own last padded frame, and the BiGRU's reverse pass starts there. Equal lengths
+ * take rvcx_rmvpe_batch's path, bit for bit, whatever their length (that path splits rows of more than 32000 padded
+ * frames, the reference's chunk of 320 s, as rvcx_rmvpe does). Among rows of different lengths a row of more than
+ * 32000 padded frames fails with RVCX_E_SHAPE: the ragged pass does not chunk. A row shorter than 513 samples fails
+ * with RVCX_E_SHAPE; any other row rvcx_rmvpe refuses fails with that call's status. */
+int rvcx_rmvpe_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, float thred,
+                       double* d_f0, int64_t ldf, int64_t* F_out, float* d_hidden, int64_t ld_hidden_frames,
+                       void* stream);
+
 /* CREPE (f0 methods "crepe" / "crepe-tiny"): CREPE.get_f0(audio, f0_min, f0_max, threshold) of
  * rvc_mlx/lib/mlx/crepe.py:282-325 (the torchcrepe network of rvc/lib/predictors/f0.py:25-57; MLX dispatch
  * rvc_mlx/lib/mlx/pitch_extractors.py:155-156). Weights: RVCX_MODEL_CREPE under torchcrepe's names (conv1..6 +
@@ -283,7 +298,10 @@ typedef struct {
                                        1100, threshold 0.1), 2 = CREPE as rvc/ runs it (pipeline.py:223-234;
                                        rvcx_crepe_ex semantics 1, without the dither), 3 = FCPE with the loaded
                                        RVCX_MODEL_FCPE weights (rvc/lib/predictors/f0.py:77-87: the raw track,
-                                       zeros where unvoiced; the model's hop must be 160 at 16 kHz) */
+                                       zeros where unvoiced; the model's hop must be 160 at 16 kHz), 4 = RMVPE with
+                                       the rows of a batch in one ragged pass (rvcx_rmvpe_batch_v; in
+                                       rvcx_pipeline_batch_v only: a row's f0 then equals method 0's up to summation
+                                       order, not bit for bit. One utterance and equal lengths run as method 0) */
   float fcpe_threshold;             /* FCPE's voicing threshold (FCPE.get_f0's filter_radius, f0.py:71); <= 0: 0.006 */
 } rvcx_pipeline_opts;
 
@@ -324,8 +342,9 @@ int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t
  * samples (host array; samples of a row past n_out[b], up to the longest row's count, may be overwritten). One ragged
  * HuBERT pass (rvcx_hubert_batch_v), one Synthesizer.infer with per-row lengths, and one launch set per stage for the
  * upsample + protect, the pitch packing, the trim, the volume envelope and the peak normalisation, whatever B is.
- * The pitch network runs per row (RMVPE's padding, its U-Net's zero padding and the BiGRU's reverse pass all start at
- * a row's own end); rows of equal length inside the batch share one batched RMVPE pass.
+ * The pitch network runs per row under f0_method 0 (the default: a row's f0 is then rvcx_pipeline_ex's bit for bit),
+ * rows of equal length inside the batch sharing one batched RMVPE pass; f0_method 4 runs all rows in one ragged RMVPE
+ * pass (rvcx_rmvpe_batch_v: equal to the per-row pass up to summation order).
  * Noise when injected uses rvcx_pipeline_batch's layouts with T the longest row's frame count T_max = max_b
  * min((n[b] + 2 t_pad) / 160, 2 L_b): d_eps_z [B][inter][T_max], d_eps_src [B][T_max*upp]; row b consumes
  * d_eps_z[b][:, :T_b] and the first T_b*upp source draws, the draws a B = 1 call on that row consumes.
@@ -359,6 +378,7 @@ int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, doub
  *   longest first, so the work buffers grow only inside the first chunk), so the size holds for any audio of n samples.
  *   With f0_method 3 the FCPE network's scratch (mel, activations, the attention's ctx / ksum slab images) is carved
  *   in place of RMVPE's; the call is then sized under f0_method 0 as well and the larger size is reported.
+ *   With f0_method 4 and B > 1 the ragged RMVPE pass is sized on B rows of n samples.
  * rvcx_set_workspace: hand the context a caller-owned device arena (e.g. a torch uint8 tensor's data_ptr(), 256-B
  *   aligned), valid until replaced or the context is destroyed: the pool is then carved from it and never allocated,
  *   and a call that would need more fails with RVCX_E_OOM. NULL, 0 returns to internal allocation. The current pool

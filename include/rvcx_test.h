@@ -110,6 +110,18 @@ int rvcx_conv2d3x3(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, cons
 int rvcx_convtranspose2d_s2(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w,
                             const float* d_bias, int N, int act, int math, float* d_y, void* stream);
 
+/* The two entries above on B images of different heights in one launch, as the ragged RMVPE pass issues them
+ * (rvcx_rmvpe_batch_v): d_x [B][H_max][W][C_in], H (host, [B]) each image's own height in [1, H_max], d_y
+ * [B][H_max][W][N] (the up-conv: [B][2 H_max][2 W][N]). Image b's output rows below H[b] (the up-conv: 2 H[b]) are
+ * those of the single-image entry on its first H[b] rows, up to summation order: a tap at a row from H[b] on reads
+ * zero whatever d_x holds there. Its output rows from there on are unspecified. math as the single-image entries; the
+ * kernel family and split are the planner's for B images of H_max rows. */
+int rvcx_conv2d3x3_v(rvcx_ctx* ctx, const float* d_x, int B, const int* H, int H_max, int W, int C_in,
+                     const float* d_w, const float* d_bias, int N, int act, int math, float* d_y, void* stream);
+int rvcx_convtranspose2d_s2_v(rvcx_ctx* ctx, const float* d_x, int B, const int* H, int H_max, int W, int C_in,
+                              const float* d_w, const float* d_bias, int N, int act, int math, float* d_y,
+                              void* stream);
+
 /* Multi-head attention core on the fused kernel (csrc/flash_attn.hip), time-major: d_qkv [B][T][3 H] (q | k | v, head
  * h at columns h dk .. of each, H = n_heads dk), d_out [B][T][H]: per head softmax(qscale q k^T + band) v + band(p)
  * rel_v, where, with d_rel_k / d_rel_v [2 window + 1][dk] (both or neither), band adds qscale q . rel_k[j - i + window]
@@ -214,6 +226,14 @@ int rvcx_rt_model_rows(rvcx_ctx* ctx, rvcx_rt* rt, int gated, float* d_dst, int6
  * the W_hh pointers 16-byte aligned; else RVCX_E_INVALID. */
 int rvcx_gru_bidir(rvcx_ctx* ctx, const float* d_gi, int B, int T, const float* d_whh_f, const float* d_bhh_f,
                    const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream);
+
+/* rvcx_gru_bidir for sequences of different lengths in the same launches: T (host, [B]) each sequence's step count
+ * (>= 1), d_gi [B][T_max][1536] and d_out [B][T_max][512] with T_max the longest. Sequence b's first T[b] output rows
+ * are rvcx_gru_bidir's on that sequence alone with T = T[b], bit for bit (the same arithmetic in the same order; its
+ * reverse direction starts at row T[b] - 1); its rows from T[b] on are not written. Every slice's tag counter advances
+ * by T_max + 1. */
+int rvcx_gru_bidir_v(rvcx_ctx* ctx, const float* d_gi, int B, const int* T, const float* d_whh_f, const float* d_bhh_f,
+                     const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream);
 
 /* The generator's harmonic source alone, as the decoder of the loaded configuration computes it: NSF SineGen +
  * l_linear + tanh (k_sine_cum / k_sine, csrc/nsf_source.hip) or the 9-harmonic MRF source (csrc/source_harm.hip).

@@ -292,6 +292,21 @@ int rvcx_rmvpe_batch(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t lda
   });
 }
 
+int rvcx_rmvpe_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, float thred,
+                       double* d_f0, int64_t ldf, int64_t* F_out, float* d_hidden, int64_t ld_hidden_frames,
+                       void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[RVCX_MODEL_RMVPE]) throw Error(RVCX_E_STATE, "rmvpe weights not finalized");
+    if (!d_audio || !d_f0 || !n || B < 1 || ldf < 1 || (d_hidden && ld_hidden_frames < 1))
+      throw Error(RVCX_E_INVALID, "rvcx_rmvpe_batch_v: bad arguments");
+    for (int b = 0; b < B; ++b)
+      if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_rmvpe_batch_v: bad row length");
+    set_device(ctx);
+    rmvpe_forward_v(*ctx, d_audio, n, lda, B, thred, d_f0, ldf, F_out, d_hidden, ld_hidden_frames,
+                    static_cast<hipStream_t>(stream));
+  });
+}
+
 int rvcx_rmvpe_decode(rvcx_ctx* ctx, const float* d_hidden, int64_t F, float thred, double* d_f0, void* stream) {
   return guard(ctx, [&] {
     if (!d_hidden || !d_f0 || F < 0) throw Error(RVCX_E_INVALID, "rvcx_rmvpe_decode: bad arguments");

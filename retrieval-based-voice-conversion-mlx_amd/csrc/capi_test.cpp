@@ -1,6 +1,7 @@
 // extern "C" boundary of the kernel-level test entries (include/rvcx_test.h): single kernels, the planner query and the
 // comparison switches, for the numerics tests and A/B timing. The product ABI (include/rvcx.h) is capi.cpp.
 #include <cstdint>
+#include <string>
 
 #include "../../include/rvcx_test.h"
 #include "capi_common.h"
@@ -174,60 +175,119 @@ int rvcx_conv1d_ex(rvcx_ctx* ctx, const rvcx_conv_test_desc* d, int* kind_out, i
   });
 }
 
+namespace {
+// the per-image heights of a *_v entry on device (host array H[B], each in [1, H_max]); nullptr without one
+const int* test_heights(Ctx& c, const int* H, int B, int H_max, const char* who, hipStream_t s) {
+  if (!H) return nullptr;
+  for (int b = 0; b < B; ++b)
+    if (H[b] < 1 || H[b] > H_max) throw Error(RVCX_E_INVALID, std::string(who) + ": a height outside [1, H_max]");
+  int* d = c.buf<int>("conv.test.h", (size_t)B, s);
+  RVCX_HIP(hipMemcpyAsync(d, H, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, s));
+  return d;
+}
+
+// rvcx_conv2d3x3 on B images of H rows back to back, image b's own height Hv[b] (host, optional)
+void conv2d3x3_run(rvcx_ctx* ctx, const float* d_x, int B, const int* Hv, int H, int W, int C_in, const float* d_w,
+                   const float* d_bias, int N, int act, int math, float* d_y, void* stream, const char* who) {
+  set_device(ctx);
+  if (!d_x || !d_w || !d_y || B <= 0 || H <= 0 || W <= 0 || C_in <= 0 || N <= 0 || act < 0 || act > 1 || math < 0 ||
+      math > 2)
+    throw Error(RVCX_E_INVALID, std::string(who) + ": bad argument");
+  if ((int64_t)B * H * W * (C_in > N ? C_in : N) > INT32_MAX) throw Error(RVCX_E_SHAPE, std::string(who) + ": size out of range");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ConvArgs a;
+  a.x = d_x; a.ldx = C_in; a.T_in = H; a.W_in = W; a.C_in = C_in;
+  a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = 9; a.KH = 3; a.KW = 3; a.padh = 1; a.padw = 1;
+  a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = N; a.bias = d_bias;
+  a.act = act ? ACT_RELU : ACT_NONE;
+  if (B > 1) {
+    a.batch = B;
+    a.x_bs = (long long)H * W * C_in;
+    a.y_bs = (long long)H * W * N;
+  }
+  a.h_in = test_heights(*ctx, Hv, B, H, who, s);
+  // math 2: the windowed gather-streamed kernel of the U-Net's deep levels in the two-plane fp16 split (64 x 64 tiles,
+  // K split over workgroups by the size policy); else the policy for a weight that is not static (the 3x3
+  // small-channel form reads a fresh fp16 image under the fp16-split arithmetic)
+  static const struct { int math, kind; } route[3] = {{0, -1}, {1, -1}, {3, CK_GSW}};
+  a.math = route[math].math;
+  const ConvForce force{route[math].kind};
+  if (math == 2 && !conv_gsw_eligible(a)) throw Error(RVCX_E_SHAPE, std::string(who) + ": shape not eligible for the windowed kernel");
+  launch_conv_test(*ctx, a, true, math == 2, force, -1, who, s);
+}
+
+// rvcx_convtranspose2d_s2 likewise
+void convtranspose2d_s2_run(rvcx_ctx* ctx, const float* d_x, int B, const int* Hv, int H, int W, int C_in,
+                            const float* d_w, const float* d_bias, int N, int act, int math, float* d_y, void* stream,
+                            const char* who) {
+  set_device(ctx);
+  if (!d_x || !d_w || !d_y || B <= 0 || H <= 0 || W <= 0 || C_in <= 0 || N <= 0 || act < 0 || act > 1 || math < 0 ||
+      math > 1)
+    throw Error(RVCX_E_INVALID, std::string(who) + ": bad argument");
+  if ((int64_t)4 * B * H * W * (C_in > 4 * N ? C_in : 4 * N) > INT32_MAX)
+    throw Error(RVCX_E_SHAPE, std::string(who) + ": size out of range");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the phase-conv weights (and its bias per virtual column) in test buffers, rebuilt every call
+  float* wp = ctx->buf<float>("conv.test.upw", (size_t)16 * N * C_in, s);
+  check(upconv_phase_pack(d_w, C_in, N, wp, s), "upconv_phase_pack");
+  float* bp = nullptr;
+  if (d_bias) {
+    bp = ctx->buf<float>("conv.test.upb", (size_t)4 * N, s);
+    for (int p = 0; p < 4; ++p)
+      RVCX_HIP(hipMemcpyAsync(bp + (size_t)p * N, d_bias, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+  }
+  ConvArgs a;  // runtime_fe.cpp's decoder up-conv
+  a.x = d_x; a.ldx = C_in; a.T_in = H; a.W_in = W; a.C_in = C_in;
+  a.w = wp; a.ldw = C_in; a.w_ts = (long long)4 * N * C_in; a.taps = 4; a.KH = 2; a.KW = 2;
+  a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = 4 * N;
+  a.out_map = OUT_UPSAMPLE2D;
+  a.out_cv = N;
+  a.bias = bp;
+  a.act = act ? ACT_RELU : ACT_NONE;
+  if (B > 1) {
+    a.batch = B;
+    a.x_bs = (long long)H * W * C_in;
+    a.y_bs = (long long)4 * H * W * N;
+  }
+  a.h_in = test_heights(*ctx, Hv, B, H, who, s);
+  // math 0: the gather-streamed kernel the pipeline's policy routes the up-convs to (under a split arithmetic); 1: the
+  // native fp32 kernel
+  a.math = math == 1 ? 1 : 0;
+  const ConvForce force{math == 0 && conv_math(ctx->conv_math) >= 2 ? CK_GS : -1};
+  launch_conv_test(*ctx, a, true, force.kind >= 0, force, -1, who, s);
+}
+}  // namespace
+
 int rvcx_conv2d3x3(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w, const float* d_bias,
                    int N, int act, int math, float* d_y, void* stream) {
   return guard(ctx, [&] {
-    set_device(ctx);
-    if (!d_x || !d_w || !d_y || H <= 0 || W <= 0 || C_in <= 0 || N <= 0 || act < 0 || act > 1 || math < 0 || math > 2)
-      throw Error(RVCX_E_INVALID, "rvcx_conv2d3x3: bad argument");
-    if ((int64_t)H * W * (C_in > N ? C_in : N) > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_conv2d3x3: size out of range");
-    ConvArgs a;
-    a.x = d_x; a.ldx = C_in; a.T_in = H; a.W_in = W; a.C_in = C_in;
-    a.w = d_w; a.ldw = C_in; a.w_ts = (long long)N * C_in; a.taps = 9; a.KH = 3; a.KW = 3; a.padh = 1; a.padw = 1;
-    a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = N; a.bias = d_bias;
-    a.act = act ? ACT_RELU : ACT_NONE;
-    // math 2: the windowed gather-streamed kernel of the U-Net's deep levels in the two-plane fp16 split (64 x 64 tiles,
-    // K split over workgroups by the size policy); else the policy for a weight that is not static (the 3x3
-    // small-channel form reads a fresh fp16 image under the fp16-split arithmetic)
-    static const struct { int math, kind; } route[3] = {{0, -1}, {1, -1}, {3, CK_GSW}};
-    a.math = route[math].math;
-    const ConvForce force{route[math].kind};
-    if (math == 2 && !conv_gsw_eligible(a)) throw Error(RVCX_E_SHAPE, "rvcx_conv2d3x3: shape not eligible for the windowed kernel");
-    launch_conv_test(*ctx, a, true, math == 2, force, -1, "rvcx_conv2d3x3", static_cast<hipStream_t>(stream));
+    conv2d3x3_run(ctx, d_x, 1, nullptr, H, W, C_in, d_w, d_bias, N, act, math, d_y, stream, "rvcx_conv2d3x3");
+  });
+}
+
+int rvcx_conv2d3x3_v(rvcx_ctx* ctx, const float* d_x, int B, const int* H, int H_max, int W, int C_in,
+                     const float* d_w, const float* d_bias, int N, int act, int math, float* d_y, void* stream) {
+  return guard(ctx, [&] {
+    if (!H) throw Error(RVCX_E_INVALID, "rvcx_conv2d3x3_v: bad argument");
+    conv2d3x3_run(ctx, d_x, B, H, H_max, W, C_in, d_w, d_bias, N, act, math, d_y, stream, "rvcx_conv2d3x3_v");
   });
 }
 
 int rvcx_convtranspose2d_s2(rvcx_ctx* ctx, const float* d_x, int H, int W, int C_in, const float* d_w,
                             const float* d_bias, int N, int act, int math, float* d_y, void* stream) {
   return guard(ctx, [&] {
-    set_device(ctx);
-    if (!d_x || !d_w || !d_y || H <= 0 || W <= 0 || C_in <= 0 || N <= 0 || act < 0 || act > 1 || math < 0 || math > 1)
-      throw Error(RVCX_E_INVALID, "rvcx_convtranspose2d_s2: bad argument");
-    if ((int64_t)4 * H * W * (C_in > 4 * N ? C_in : 4 * N) > INT32_MAX)
-      throw Error(RVCX_E_SHAPE, "rvcx_convtranspose2d_s2: size out of range");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // the phase-conv weights (and its bias per virtual column) in test buffers, rebuilt every call
-    float* wp = ctx->buf<float>("conv.test.upw", (size_t)16 * N * C_in, s);
-    check(upconv_phase_pack(d_w, C_in, N, wp, s), "upconv_phase_pack");
-    float* bp = nullptr;
-    if (d_bias) {
-      bp = ctx->buf<float>("conv.test.upb", (size_t)4 * N, s);
-      for (int p = 0; p < 4; ++p)
-        RVCX_HIP(hipMemcpyAsync(bp + (size_t)p * N, d_bias, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
-    }
-    ConvArgs a;  // runtime_fe.cpp's decoder up-conv
-    a.x = d_x; a.ldx = C_in; a.T_in = H; a.W_in = W; a.C_in = C_in;
-    a.w = wp; a.ldw = C_in; a.w_ts = (long long)4 * N * C_in; a.taps = 4; a.KH = 2; a.KW = 2;
-    a.y = d_y; a.ldy = N; a.T_out = H; a.W_out = W; a.N = 4 * N;
-    a.out_map = OUT_UPSAMPLE2D;
-    a.out_cv = N;
-    a.bias = bp;
-    a.act = act ? ACT_RELU : ACT_NONE;
-    // math 0: the gather-streamed kernel the pipeline's policy routes the up-convs to (under a split arithmetic); 1: the
-    // native fp32 kernel
-    a.math = math == 1 ? 1 : 0;
-    const ConvForce force{math == 0 && conv_math(ctx->conv_math) >= 2 ? CK_GS : -1};
-    launch_conv_test(*ctx, a, true, force.kind >= 0, force, -1, "rvcx_convtranspose2d_s2", s);
+    convtranspose2d_s2_run(ctx, d_x, 1, nullptr, H, W, C_in, d_w, d_bias, N, act, math, d_y, stream,
+                           "rvcx_convtranspose2d_s2");
+  });
+}
+
+int rvcx_convtranspose2d_s2_v(rvcx_ctx* ctx, const float* d_x, int B, const int* H, int H_max, int W, int C_in,
+                              const float* d_w, const float* d_bias, int N, int act, int math, float* d_y,
+                              void* stream) {
+  return guard(ctx, [&] {
+    if (!H) throw Error(RVCX_E_INVALID, "rvcx_convtranspose2d_s2_v: bad argument");
+    convtranspose2d_s2_run(ctx, d_x, B, H, H_max, W, C_in, d_w, d_bias, N, act, math, d_y, stream,
+                           "rvcx_convtranspose2d_s2_v");
   });
 }
 
@@ -352,18 +412,49 @@ int rvcx_kmeans_update(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const 
   });
 }
 
+namespace {
+// rvcx_gru_bidir with each sequence's own step count Tv[b] <= T (host, optional)
+void gru_bidir_test(rvcx_ctx* ctx, const float* d_gi, int B, int T, const int* Tv, const float* d_whh_f,
+                    const float* d_bhh_f, const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start,
+                    void* stream, const char* who) {
+  // T: the kernel's 32-bit row offsets (t * 1536); the weights are read as float4
+  if (!d_gi || !d_whh_f || !d_bhh_f || !d_whh_b || !d_bhh_b || !d_out || B < 1 || B > 65535 || T < 1 ||
+      T > (1 << 20) || tag_start > (int64_t)UINT32_MAX || (reinterpret_cast<uintptr_t>(d_whh_f) & 15) ||
+      (reinterpret_cast<uintptr_t>(d_whh_b) & 15))
+    throw Error(RVCX_E_INVALID, std::string(who) + ": bad arguments");
+  set_device(ctx);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int* d_T = nullptr;
+  if (Tv) {
+    int* d = ctx->buf<int>("gru.test.T", (size_t)B, s);
+    RVCX_HIP(hipMemcpyAsync(d, Tv, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, s));
+    d_T = d;
+  }
+  ctx->before_gru = nullptr;  // nothing is issued beside this launch
+  gru_bidir_run(*ctx, d_gi, B, T, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start < 0 ? -1 : (long long)tag_start,
+                s, d_T);
+}
+}  // namespace
+
 int rvcx_gru_bidir(rvcx_ctx* ctx, const float* d_gi, int B, int T, const float* d_whh_f, const float* d_bhh_f,
                    const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream) {
   return guard(ctx, [&] {
-    // T: the kernel's 32-bit row offsets (t * 1536); the weights are read as float4
-    if (!d_gi || !d_whh_f || !d_bhh_f || !d_whh_b || !d_bhh_b || !d_out || B < 1 || B > 65535 || T < 1 ||
-        T > (1 << 20) || tag_start > (int64_t)UINT32_MAX || (reinterpret_cast<uintptr_t>(d_whh_f) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_whh_b) & 15))
-      throw Error(RVCX_E_INVALID, "rvcx_gru_bidir: bad arguments");
-    set_device(ctx);
-    ctx->before_gru = nullptr;  // nothing is issued beside this launch
-    gru_bidir_run(*ctx, d_gi, B, T, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start < 0 ? -1 : (long long)tag_start,
-                  static_cast<hipStream_t>(stream));
+    gru_bidir_test(ctx, d_gi, B, T, nullptr, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start, stream,
+                   "rvcx_gru_bidir");
+  });
+}
+
+int rvcx_gru_bidir_v(rvcx_ctx* ctx, const float* d_gi, int B, const int* T, const float* d_whh_f, const float* d_bhh_f,
+                     const float* d_whh_b, const float* d_bhh_b, float* d_out, int64_t tag_start, void* stream) {
+  return guard(ctx, [&] {
+    if (!T || B < 1) throw Error(RVCX_E_INVALID, "rvcx_gru_bidir_v: bad arguments");
+    int T_max = 0;
+    for (int b = 0; b < B; ++b) {
+      if (T[b] < 1) throw Error(RVCX_E_INVALID, "rvcx_gru_bidir_v: a sequence of no steps");
+      T_max = T[b] > T_max ? T[b] : T_max;
+    }
+    gru_bidir_test(ctx, d_gi, B, T_max, T, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start, stream,
+                   "rvcx_gru_bidir_v");
   });
 }
 

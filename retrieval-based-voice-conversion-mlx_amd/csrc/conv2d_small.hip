@@ -39,6 +39,7 @@ __global__ __launch_bounds__(256) void k_conv2d_small(const ConvArgs a, const in
   float* As = sm;                                   // [RH + 2][W + 2][CP]
   float* Bs = sm + (size_t)(RH + 2) * AW * CP;      // [9][NOUT][CP]
   const int b = blockIdx.z;
+  const int Hi = conv_rows_in(a, b);  // the image's own rows: a halo row from there on stages as zero
   const int h0 = blockIdx.x * RH;
   const float* X = a.x + (long long)b * a.x_bs;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(256) void k_conv2d_small(const ConvArgs a, const in
       const int pix = idx / (CIN / 4);
       const int r = pix / AW, cc = pix - r * AW;
       const int gh = h0 - 1 + r, gw = cc - 1;
-      v[it] = (idx < na && gh >= 0 && gh < H && gw >= 0 && gw < W)
+      v[it] = (idx < na && gh >= 0 && gh < Hi && gw >= 0 && gw < W)
                   ? *reinterpret_cast<const f32x4*>(X + ((long long)gh * W + gw) * a.ldx + 4 * q)
                   : f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -208,6 +209,7 @@ __global__ __launch_bounds__(256) void k_conv2d_h16(const ConvArgs a, const int 
   char* As = smh;
   char* Bs = smh + (((size_t)(npix + 1) * PS + 15) & ~(size_t)15);  // [KS][NT][plane][64 lanes][16 B]
   const int b = blockIdx.z;
+  const int Hi = conv_rows_in(a, b);  // the image's own rows: a halo row from there on stages as zero
   const int h0 = blockIdx.x * RH;
   const float* X = a.x + (long long)b * a.x_bs;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(256) void k_conv2d_h16(const ConvArgs a, const int 
       const int pix = idx / (CIN / 4);
       const int r = pix / AW, cc = pix - r * AW;
       const int gh = h0 - 1 + r, gw = cc - 1;
-      const bool ok = idx < na && gh >= 0 && gh < H && gw >= 0 && gw < W;
+      const bool ok = idx < na && gh >= 0 && gh < Hi && gw >= 0 && gw < W;
       v[it] = *reinterpret_cast<const f32x4*>(X + ((long long)(ok ? gh : 0) * W + (ok ? gw : 0)) * a.ldx + 4 * q);
       if (!ok) v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
     }

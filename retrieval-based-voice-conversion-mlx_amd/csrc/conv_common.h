@@ -41,6 +41,16 @@ static __device__ __forceinline__ float pre_fn(float v, int act, float slope) {
 }
 static inline int pre_mode(int act) { return act == ACT_NONE ? PA_NONE : (act == ACT_LRELU ? PA_LRELU : PA_ANY); }
 
+// The valid input rows of outer batch entry b: its own height in a batch of images of different heights
+// (ConvArgs::h_in), else T_in. b has to be uniform over the wave (the block's batch index, or a readfirstlane): the
+// bound is then one scalar load, and every gather tests its row against it where it tested T_in.
+// The heights are written by the host before the launch and by no kernel: read through the constant address space, the
+// load is scalar (s_load_dword) also where it sits in a loop beside stores the compiler cannot tell apart from it.
+static __device__ __forceinline__ int conv_rows_in(const ConvArgs& a, int b) {
+  typedef const int __attribute__((address_space(4))) * const_ip;
+  return a.h_in ? ((const_ip)a.h_in)[b] : a.T_in;
+}
+
 // The fused epilogue, defined once for every kernel that takes its switches at run time:
 //   bias -> pre-residual -> alpha -> activation -> post-residual / reverse-subtract -> accumulate (/ div)  [epi_math]
 //   -> noise conv [epi_noise] -> mask [epi_mask] -> store.

@@ -303,6 +303,8 @@ hipError_t conv_run(const ConvPlan& p, const ConvArgs& a_in, bool two_d, hipStre
   if (p.kind == CK_OTHER || p.ksplit < 1 || (p.ksplit > 1 && !a_in.ws) ||
       (p.wsplit_fmt >= 0 && p.kind != CK_SMALL2D && !a_in.wsplit))
     return hipErrorInvalidValue;
+  // images of different heights (ConvArgs::h_in): a 2-D launch of a family whose gather tests the bound, or an error
+  if (a_in.h_in && (!two_d || p.kind == CK_WST || p.kind == CK_WSB16)) return hipErrorInvalidValue;
   // the fields the kernels read from their kernarg copy of the record
   ConvArgs a = a_in;
   a.ksplit = p.ksplit;

@@ -66,6 +66,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_emu_kernel(const ConvArg
   const float* X = a.x + (long long)b * a.x_bs + (long long)bi * a.x_bs2;
   const float* Wb = a.w + (long long)b * a.w_bs + (long long)bi * a.w_bs2;
   const float* PM = a.pre_mask ? a.pre_mask + (long long)b * a.pre_mask_bs : nullptr;
+  const int Hi = TWO_D ? conv_rows_in(a, b) : a.T_in;  // 2-D: the image's own rows (ConvArgs::h_in)
   const int aw = TWO_D ? rw + a.KW - 1 : 0;
   const int row0 = TWO_D ? 0 : m0 * a.stride - a.pad;
 
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_emu_kernel(const ConvArg
         const int c = c0 + c4;
         const int ah = r / aw, awi = r - ah * aw;
         const int gh = h0 - a.padh + ah, gw = w0 - a.padw + awi;
-        const bool valid = (gh >= 0) && (gh < a.T_in) && (gw >= 0) && (gw < a.W_in);
+        const bool valid = (gh >= 0) && (gh < Hi) && (gw >= 0) && (gw < a.W_in);
         const long long grow = (long long)gh * a.W_in + gw;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (valid && c < a.C_in) {
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_emu_kernel(const ConvArg
       } else {
         const int ah = r / aw, awi = r - ah * aw;
         const int gh = h0 - a.padh + ah, gw = w0 - a.padw + awi;
-        ok = r < nrows_a && gh >= 0 && gh < a.T_in && gw >= 0 && gw < a.W_in;
+        ok = r < nrows_a && gh >= 0 && gh < Hi && gw >= 0 && gw < a.W_in;
         g = (long long)gh * a.W_in + gw;
       }
       f32x4 val = {0.f, 0.f, 0.f, 0.f};

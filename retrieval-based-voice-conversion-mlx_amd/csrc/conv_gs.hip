@@ -105,6 +105,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_gs16_kernel(const ConvAr
   const long long Mtot = TWO_D ? (long long)a.T_out * a.W_out : a.T_out;
   const float* X = a.x + (long long)b * a.x_bs;
   const float* PM = PMASK ? a.pre_mask + (long long)b * a.pre_mask_bs : nullptr;
+  const int Hi = TWO_D ? conv_rows_in(a, b) : a.T_in;  // 2-D: the image's own rows (ConvArgs::h_in)
 
   // (chunk, tap) steps [it0, it1) of this split-K slice
   const int taps = a.taps;
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_gs16_kernel(const ConvAr
         ok = rok[v] && (unsigned)g < (unsigned)a.T_in;
       } else {
         const int ih = g0[v] + a_kh, iw = w0v[v] + a_kw;
-        ok = rok[v] && (unsigned)ih < (unsigned)a.T_in && (unsigned)iw < (unsigned)a.W_in;
+        ok = rok[v] && (unsigned)ih < (unsigned)Hi && (unsigned)iw < (unsigned)a.W_in;
         g = ih * a.W_in + iw;
       }
       const unsigned gc = ok ? (unsigned)g : 0u;
@@ -397,6 +398,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_gsw16_kernel(const ConvA
   const int h0 = bx * rh;
   const int nwin = (rh + 2) * aw;
   const float* X = a.x + (long long)b * a.x_bs;
+  const int Hi = conv_rows_in(a, b);  // the image's own rows: the window's rows from there on stage as zero
   const int nch = a.C_in / EK;
   const int pc = (nch + ksplit - 1) / ksplit;  // whole chunks per split-K slice
   const int c0 = zsplit * pc, c1 = min(nch, c0 + pc);
@@ -413,7 +415,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_gsw16_kernel(const ConvA
       const int r = v * (NT / EC4) + arow;
       const int wh = r / aw, wc = r - wh * aw;
       const int ih = h0 - 1 + wh, iw = wc - 1;
-      const bool ok = r < nwin && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
+      const bool ok = r < nwin && (unsigned)ih < (unsigned)Hi && (unsigned)iw < (unsigned)W;
       const unsigned g = ok ? (unsigned)(ih * W + iw) : 0u;
       wr_[v] = *reinterpret_cast<const f32x4*>(src + g * (unsigned)a.ldx);  // branch-free (conv_gs16_kernel)
       wok |= ok ? (1u << v) : 0u;

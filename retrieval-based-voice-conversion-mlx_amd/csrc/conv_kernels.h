@@ -124,6 +124,12 @@ struct ConvArgs {
   // extra dynamic LDS per workgroup (bytes): fewer of this launch's workgroups fit a CU beside the critical stream's
   // (an occupancy throttle for off-critical-path work; the gather-streamed and LDS-staged kernels honour it)
   int lds_pad = 0;
+  // 2-D, images of different heights in one batch (device array indexed by the outer batch entry, each <= T_in): image
+  // b has h_in[b] valid rows and a tap at a row from h_in[b] on reads zero, whatever the buffer holds there -- the
+  // padding a launch on that image alone has at its last row. Its output rows from h_in[b] on are written and hold no
+  // meaning. The planner does not read it: the route is the equal-height batch's (conv_run refuses a family without
+  // it). Last in the record: no other field's place in the kernels' argument copy moves.
+  const int* h_in = nullptr;
 };
 
 // the kernel families (the plan's, and the kernel-timing records' of rvcx_profile). CK_WSB is retired: no plan names

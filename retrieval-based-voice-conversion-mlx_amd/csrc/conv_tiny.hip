@@ -32,6 +32,8 @@ __global__ void conv_tiny_kernel(const ConvArgs a) {
       oh = m / a.W_out;
       ow = m - oh * a.W_out;
     }
+    // the image's own rows (ConvArgs::h_in; launch_tiny admits it where a wave's 64 outputs lie in one image)
+    const int Hi = (TWO_D && a.h_in) ? conv_rows_in(a, __builtin_amdgcn_readfirstlane(b)) : a.T_in;
     float acc = 0.f;
     for (int tap = 0; tap < a.taps; ++tap) {
       int g;
@@ -41,7 +43,7 @@ __global__ void conv_tiny_kernel(const ConvArgs a) {
       } else {
         const int kh = tap / a.KW;
         const int gh = oh - a.padh + kh, gw = ow - a.padw + (tap - kh * a.KW);
-        if (gh < 0 || gh >= a.T_in || gw < 0 || gw >= a.W_in) continue;
+        if (gh < 0 || gh >= Hi || gw < 0 || gw >= a.W_in) continue;
         g = gh * a.W_in + gw;
       }
       const float pm = (PM && !TWO_D) ? PM[g] : 1.f;
@@ -86,6 +88,7 @@ __global__ __launch_bounds__(256) void conv_tiny_rows_kernel(const ConvArgs a) {
       oh = m / a.W_out;
       ow = m - oh * a.W_out;
     }
+    const int Hi = (TWO_D && a.h_in) ? conv_rows_in(a, __builtin_amdgcn_readfirstlane(b)) : a.T_in;  // as conv_tiny_kernel
     for (int tap = 0; tap < a.taps; ++tap) {
       int g;
       if (!TWO_D) {
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(256) void conv_tiny_rows_kernel(const ConvArgs a) {
       } else {
         const int kh = tap / a.KW;
         const int gh = oh - a.padh + kh, gw = ow - a.padw + (tap - kh * a.KW);
-        if (gh < 0 || gh >= a.T_in || gw < 0 || gw >= a.W_in) continue;
+        if (gh < 0 || gh >= Hi || gw < 0 || gw >= a.W_in) continue;
         g = gh * a.W_in + gw;
       }
       for (int c = 0; c < a.C_in; ++c) {
@@ -220,6 +223,8 @@ hipError_t launch_tiny(const ConvArgs& a, bool two_d, hipStream_t s) {
   const long long rows = two_d ? (long long)a.T_out * a.W_out : a.T_out;
   const long long total = rows * a.N * a.batch * a.batch_inner;
   if (total >= (1LL << 31) - 65536LL * 256) return hipErrorInvalidValue;  // 32-bit indexing in the kernel
+  // per-image heights: the kernels read the bound of the wave's first output, so a wave may not straddle two images
+  if (a.h_in && (!two_d || (tiny_rows_fits(a) ? rows : rows * a.N) % 64 != 0)) return hipErrorInvalidValue;
   if (tiny_rows_fits(a)) {
     const long long nr = total / a.N;
     const unsigned nbr = (unsigned)std::min<long long>((nr + 255) / 256, 65536);

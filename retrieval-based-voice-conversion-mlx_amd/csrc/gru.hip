@@ -55,8 +55,9 @@ __device__ __forceinline__ float tanh_g(float v) { return 1.f - 2.f * rcp_hw(1.f
 template <int MODE>
 __global__ __launch_bounds__(NT, 1) void k_gru_bidir_g(const float* __restrict__ gi, const float* whh_f,
                                                        const float* bhh_f, const float* whh_b, const float* bhh_b,
-                                                       int T, float* out, unsigned long long* xchg,
-                                                       unsigned* status, unsigned spin_limit, unsigned tag0) {
+                                                       int T_max, const int* Tv, float* out,
+                                                       unsigned long long* xchg, unsigned* status,
+                                                       unsigned spin_limit, unsigned tag0) {
   constexpr int CG = 32;  // columns of each half per wave
   __shared__ __attribute__((aligned(16))) float h_own[UNITS];
   __shared__ __attribute__((aligned(16))) float h_pw[NT / 64][CG];  // per-wave copy of its partner columns
@@ -70,8 +71,13 @@ __global__ __launch_bounds__(NT, 1) void k_gru_bidir_g(const float* __restrict__
   const int d = w & 1;       // direction
   const int q = w >> 3;      // half
   const int seq = blockIdx.x >> 4;
-  gi += (long long)seq * T * 6 * H;
-  out += (long long)seq * T * 2 * H;
+  // Sequences of different lengths (Tv, one scalar load): sequence seq runs its own T steps in rows of stride T_max, its
+  // reverse direction from row T - 1. The four workgroups of a sequence all read the same T, so partners execute the
+  // same number of steps and no workgroup polls a partner that has already exited; different sequences never wait on
+  // each other. Output rows from T on are left as they were.
+  const int T = Tv ? Tv[seq] : T_max;
+  gi += (long long)seq * T_max * 6 * H;
+  out += (long long)seq * T_max * 2 * H;
   xchg += (long long)seq * 4 * 2 * UNITS;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -209,13 +215,14 @@ __global__ __launch_bounds__(NT, 1) void k_gru_bidir_g(const float* __restrict__
 
 hipError_t gru_bidir(const float* gi, const float* whh_f, const float* bhh_f, const float* whh_b,
                      const float* bhh_b, int T, float* out, unsigned long long* xchg, unsigned* status,
-                     unsigned* next_tag, hipStream_t s, int B) {
+                     unsigned* next_tag, hipStream_t s, int B, const int* Tv) {
   // the two halves of a direction spin on each other: all 4B working workgroups (1 per CU) must be co-resident;
   // the 12B idle ones exit at once
   if (B < 1 || B > 16 || !next_tag) return hipErrorInvalidValue;
   // granule tags run on across launches on the same buffer (tag0 advances by T + 1 per launch; *next_tag is the
   // caller's counter OF THIS BUFFER, starting at 0 for a zeroed one), so whatever the buffer holds from an earlier
-  // launch never matches a tag this launch waits for and no per-launch zeroing is needed. When the 32-bit tag space
+  // launch never matches a tag this launch waits for and no per-launch zeroing is needed (T is the longest sequence's
+  // step count when Tv gives each sequence its own: a shorter one uses the first of the launch's tags). When the 32-bit tag space
   // would wrap, the buffer is zeroed and the count restarts at 1: no stale tag can equal a new one.
   unsigned tag0 = *next_tag;
   if ((unsigned long long)tag0 + (unsigned)T + 1 >= (1ull << 32) || tag0 == 0) {
@@ -233,8 +240,8 @@ hipError_t gru_bidir(const float* gi, const float* whh_f, const float* bhh_f, co
     return e ? std::atoi(e) : 0;
   }();
   auto kern = mode == 1 ? k_gru_bidir_g<1> : (mode == 2 ? k_gru_bidir_g<2> : k_gru_bidir_g<0>);
-  hipLaunchKernelGGL(kern, dim3(16 * B), dim3(NT), 0, s, gi, whh_f, bhh_f, whh_b, bhh_b, T, out, xchg, status, spin,
-                     tag0);
+  hipLaunchKernelGGL(kern, dim3(16 * B), dim3(NT), 0, s, gi, whh_f, bhh_f, whh_b, bhh_b, T, Tv, out, xchg, status,
+                     spin, tag0);
   return hipGetLastError();
 }
 

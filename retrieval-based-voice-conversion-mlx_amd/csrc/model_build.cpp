@@ -79,14 +79,15 @@ std::vector<float> stft_weights(int win) {
 }
 
 void mel_forward(Ctx& c, const MelSpec& m, const std::string& pfx, const float* audio, int64_t n, int64_t ld, int B,
-                 const MelFrames& g, float* mel, hipStream_t s) {
+                 const MelFrames& g, float* mel, hipStream_t s, const int* nv) {
   const int nbin = m.nbin(), ldm = m.ld();
   const int64_t rows = (n + g.pl + g.pr + 31) / 32;
   float* xp = c.buf<float>(pfx + "xp", (size_t)B * rows * 32, s);
+  if (nv && g.zero_pad) throw Error(RVCX_E_INVALID, "mel: a length per stream takes the reflect pad");
   if (g.zero_pad) {
     check(fcpe_zero_pad(audio, (int)n, (int)g.pl, ld, xp, rows * 32, B, s), "mel_pad");
   } else {
-    check(reflect_pad_1d(audio, (int)n, (int)g.pl, (int)g.pr, xp, s, B, ld, rows * 32), "mel_pad");
+    check(reflect_pad_1d(audio, (int)n, (int)g.pl, (int)g.pr, xp, s, B, ld, rows * 32, nv), "mel_pad");
   }
   float* spec = c.buf<float>(pfx + "spec", (size_t)B * g.Fm * 2 * nbin, s);
   {

@@ -76,9 +76,10 @@ struct MelFrames {
   bool per_stream;
 };
 // B streams of n samples (row b at audio + b ld) -> mel [B][F][n_mels]. Weights `pfx`stft / `pfx`mel, work buffers
-// `pfx`xp / spec / mag.
+// `pfx`xp / spec / mag. nv (device, optional; reflect pad only): stream b has nv[b] <= n samples and is padded at its
+// own end; its frames past its own count are computed on the zeros after it (finite, for the caller to ignore).
 void mel_forward(Ctx& c, const MelSpec& m, const std::string& pfx, const float* audio, int64_t n, int64_t ld, int B,
-                 const MelFrames& g, float* mel, hipStream_t s);
+                 const MelFrames& g, float* mel, hipStream_t s, const int* nv = nullptr);
 
 // ---- torchaudio.functional._get_sinc_resample_kernel, evaluated in float32 as a float32 waveform requests
 struct SincKernel {

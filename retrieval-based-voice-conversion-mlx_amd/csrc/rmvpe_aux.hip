@@ -36,9 +36,11 @@ hipError_t upconv_phase_pack(const float* w, int C, int co, float* out, hipStrea
 #pragma clang fp contract(on)
 
 // ------------------------------------------------------------------ RMVPE front end
-// grid.y = sequence: x rows of stride ldx, y rows of stride ldy
+// grid.y = sequence: x rows of stride ldx, y rows of stride ldy; sequence b has n[b] samples and is reflected about
+// its own ends (samples past n[b] are never read)
 // (a row stride ldy past the padded length gets its tail zeroed here: no fill launch before)
-__global__ void k_reflect1d(const float* x, int n, int pl, int pr, float* y, long long ldx, long long ldy) {
+__global__ void k_reflect1d(const float* x, Len nv, int pl, int pr, float* y, long long ldx, long long ldy) {
+  const int n = nv[blockIdx.y];
   const int m = n + pl + pr;
   const int mz = ldy > m ? (int)ldy : m;
   x += blockIdx.y * ldx;
@@ -51,27 +53,37 @@ __global__ void k_reflect1d(const float* x, int n, int pl, int pr, float* y, lon
   }
 }
 hipError_t reflect_pad_1d(const float* x, int n, int pad_l, int pad_r, float* y, hipStream_t s, int B, long long ldx,
-                          long long ldy) {
-  if (pad_l >= n || pad_r >= n) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_reflect1d, dim3(std::min(nblocks(n + pad_l + pad_r), 2048u), B), dim3(TB), 0, s, x, n, pad_l,
-                     pad_r, y, ldx, ldy);
+                          long long ldy, const int* nv) {
+  if (pad_l >= n || pad_r >= n || (nv && ldy < (long long)n + pad_l + pad_r)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_reflect1d, dim3(std::min(nblocks(n + pad_l + pad_r), 2048u), B), dim3(TB), 0, s, x,
+                     nv ? Len(nv) : Len(n), pad_l, pad_r, y, ldx, ldy);
   return hipGetLastError();
 }
-// grid.y = image: x [B][rows][C] -> y [B][rows + pr][C]
-__global__ void k_reflect_rows(const float* x, int rows, int C, int pr, float* y) {
-  const long long n = (long long)(rows + pr) * C;
-  x += (long long)blockIdx.y * rows * C;
+// grid.y = image: x [B][ld_in][C] -> y [B][ld_out][C]; image b's rows[b] rows, then their reflection up to out[b]
+// rows, then zeros up to ld_out
+__global__ void k_reflect_rows(const float* x, Len rowsv, Len outv, int ld_in, int ld_out, int C, float* y) {
+  const int rows = rowsv[blockIdx.y], out = outv[blockIdx.y];
+  const long long n = (long long)ld_out * C;
+  x += (long long)blockIdx.y * ld_in * C;
   y += (long long)blockIdx.y * n;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(i / C), c = (int)(i % C);
     const int src = r < rows ? r : 2 * (rows - 1) - r;
-    y[i] = x[(long long)src * C + c];
+    y[i] = r < out ? x[(long long)src * C + c] : 0.f;
   }
 }
 hipError_t reflect_pad_rows(const float* x, int rows, int C, int pad_r, float* y, hipStream_t s, int B) {
   if (pad_r >= rows) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_reflect_rows, dim3(std::min(nblocks((long long)(rows + pad_r) * C), 2048u), B), dim3(TB), 0,
-                     s, x, rows, C, pad_r, y);
+                     s, x, Len(rows), Len(rows + pad_r), rows, rows + pad_r, C, y);
+  return hipGetLastError();
+}
+// images of different heights: rows[b] (device) of ld_in, padded to out[b] (device, out[b] - rows[b] < rows[b]: the
+// caller's check) of ld_out
+hipError_t reflect_pad_rows_v(const float* x, const int* rows, const int* out, int ld_in, int ld_out, int C, float* y,
+                              hipStream_t s, int B) {
+  hipLaunchKernelGGL(k_reflect_rows, dim3(std::min(nblocks((long long)ld_out * C), 2048u), B), dim3(TB), 0, s, x,
+                     Len(rows), Len(out), ld_in, ld_out, C, y);
   return hipGetLastError();
 }
 // sqrt(re^2 + im^2 + eps) in rows of ldm floats: bins 0 .. nb - 1, then zeros up to ldm (the mel GEMM's contraction
@@ -130,14 +142,16 @@ hipError_t nhwc_to_hcw(const float* x, int H, int W, int C, float* y, hipStream_
 }
 
 // ------------------------------------------------------------------ RMVPE decode (RMVPE.py:484-540), fp64 like numpy
-// rows of B sequences: frame f of sequence b reads sal[(b*Fs + f)][.] and writes f0[b*F + f]
-__global__ void k_decode(const float* sal, int F, int Fs, int nrows, int ncls, float thred, double* f0) {
+// rows of B sequences: frame f < F[b] of sequence b reads sal[(b*Fs + f)][.] and writes f0[b*ldf + f]
+__global__ void k_decode(const float* sal, Len Fv, int F, int Fs, int nrows, int ncls, float thred, double* f0,
+                         long long ldf) {
 #pragma clang fp contract(off)  // numpy rounds every product and sum separately
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= nrows) return;
-  const int f = row;
-  const float* s = sal + ((long long)(row / F) * Fs + row % F) * ncls;
+  const int b = row / F, f = row % F;
+  if (f >= Fv[b]) return;
+  const float* s = sal + ((long long)b * Fs + f) * ncls;
   float best = -INFINITY;
   int bi = 0x7fffffff;
   for (int k = lane; k < ncls; k += 64) {
@@ -176,13 +190,16 @@ __global__ void k_decode(const float* sal, int F, int Fs, int nrows, int ncls, f
     if ((double)best <= (double)thred) cents = 0.0;
     double v = 10.0 * pow(2.0, cents / 1200.0);
     if (v == 10.0) v = 0.0;
-    f0[f] = v;
+    f0[b * ldf + f] = v;
   }
 }
-hipError_t rmvpe_decode(const float* sal, int F, int ncls, float thred, double* f0, hipStream_t s, int B, int Fs) {
+hipError_t rmvpe_decode(const float* sal, int F, int ncls, float thred, double* f0, hipStream_t s, int B, int Fs,
+                        const int* Fv, long long ldf) {
   if (Fs <= 0) Fs = F;
+  if (ldf <= 0) ldf = F;
   const int nrows = B * F;
-  hipLaunchKernelGGL(k_decode, dim3((nrows + 3) / 4), dim3(256), 0, s, sal, F, Fs, nrows, ncls, thred, f0);
+  hipLaunchKernelGGL(k_decode, dim3((nrows + 3) / 4), dim3(256), 0, s, sal, Fv ? Len(Fv) : Len(F), F, Fs, nrows, ncls,
+                     thred, f0, ldf);
   return hipGetLastError();
 }
 

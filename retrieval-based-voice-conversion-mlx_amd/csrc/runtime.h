@@ -354,9 +354,15 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
                         int64_t cap, float* hidden, hipStream_t s);
 // RMVPE's BiGRU recurrence on the context's hand-off buffer (runtime_fe.cpp): gi [B][T][1536] -> out [B][T][512], 16
 // sequences per launch; tag_start < 0 continues the buffer's tag counters, >= 0 zeroes it and sets them (the tests).
-// Takes Ctx::before_gru and issues it right after the BiGRU's launches.
+// Takes Ctx::before_gru and issues it right after the BiGRU's launches. Tv (device, optional): sequence b runs its own
+// Tv[b] <= T steps in rows of stride T.
 void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
-                   const float* bhh_b, float* out, long long tag_start, hipStream_t s);
+                   const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv = nullptr);
+// batched over B inputs of nv[b] samples (host array) in one ragged pass: f0 row b (F_b = 1 + nv[b] / 160 frames) at
+// f0 + b*ldf, its salience (optional) at hidden + b*ld_hidden*360; F_out[b] = F_b (host, optional). Returns the longest
+// row's frames. Equal lengths are rmvpe_forward_b.
+int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, float thred, double* f0,
+                        int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s);
 // batched over B inputs of nv[b] samples (host array): sequence b's hubert_frames(nv[b]) rows at feats + b*ld_rows*D
 int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
                          int64_t ld_rows, int64_t* rows_out, hipStream_t s);

@@ -353,9 +353,10 @@ void block_weights(Ctx& c, const std::string& p, const std::string& q, int cin, 
 }
 
 ConvArgs c2d(const float* x, int ldx, int H, int W, int Cin, const float* w, int N, const float* bias, float* y,
-             int ldy, int B = 1) {
+             int ldy, int B = 1, const int* hv = nullptr) {
   ConvArgs a = lin(x, ldx, H, Cin, w, N, bias, y, ldy);  // rows = image rows
   a.batch = B;  // B images of H x W pixels back to back
+  a.h_in = hv;  // image b's own rows (device, optional): the conv zero-pads at its own last row
   a.x_bs = (long long)H * W * ldx;
   a.y_bs = (long long)H * W * ldy;
   a.W_in = a.W_out = W;
@@ -369,10 +370,10 @@ ConvArgs c2d(const float* x, int ldx, int H, int W, int Cin, const float* w, int
 // ConvBlockRes (RMVPE.py:13-57): relu(bn(conv)) x2 + shortcut(x) (or x)
 // B images back to back (NHWC, row stride ldx / ldy per pixel)
 void conv_block(Ctx& c, const std::string& q, const float* x, int ldx, int H, int W, int cin, int cout, float* y,
-                int ldy, hipStream_t s, int B = 1) {
+                int ldy, hipStream_t s, int B = 1, const int* hv = nullptr) {
   const size_t P = (size_t)H * W;
   float* t = c.buf<float>("rm.blk.t", (size_t)B * P * cout, s);
-  ConvArgs a = c2d(x, ldx, H, W, cin, c.W(q + ".c1.w"), cout, c.W(q + ".c1.b"), t, cout, B);
+  ConvArgs a = c2d(x, ldx, H, W, cin, c.W(q + ".c1.w"), cout, c.W(q + ".c1.b"), t, cout, B, hv);
   a.act = ACT_RELU;
   run2(c, a, s);
   const float* res = x;
@@ -383,7 +384,7 @@ void conv_block(Ctx& c, const std::string& q, const float* x, int ldx, int H, in
     res = sc;
     ldr = cout;
   }
-  ConvArgs b = c2d(t, cout, H, W, cout, c.W(q + ".c2.w"), cout, c.W(q + ".c2.b"), y, ldy, B);
+  ConvArgs b = c2d(t, cout, H, W, cout, c.W(q + ".c2.w"), cout, c.W(q + ".c2.b"), y, ldy, B, hv);
   b.act = ACT_RELU;
   b.res = res;
   b.ldr = ldr;
@@ -480,9 +481,9 @@ void finalize_rmvpe(Ctx& c) {
 // the buffer and its zeroing, one tag counter per 16-sequence slice, and the launches. tag_start < 0: the counters run
 // on from the earlier launches on this buffer (RMVPE); tag_start >= 0 (rvcx_gru_bidir, the tests): the buffer is
 // zeroed and every slice's counter set to it first, so no granule left by an earlier launch can carry a tag this one
-// waits for. Work the caller registered to go out beside the BiGRU (Ctx::before_gru) is issued from here.
+// waits for. Tv (device, optional): sequence b runs Tv[b] <= T steps in rows of stride T. Work the caller registered to go out beside the BiGRU (Ctx::before_gru) is issued from here.
 void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
-                   const float* bhh_b, float* out, long long tag_start, hipStream_t s) {
+                   const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv) {
   unsigned long long* xchg = c.buf<unsigned long long>("rm.xchg", gru_xchg_words(B), s);
   // a new (or regrown) allocation holds garbage tags: zeroed once, and the tag counters of its slices restart
   if (c.zero_once("rm.xchg", xchg, sizeof(unsigned long long) * gru_xchg_words(B), (long long)B, s))
@@ -500,7 +501,8 @@ void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, co
   if (hook && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, s));
   for (int g0 = 0; g0 < B; g0 += 16)  // at most 16 sequences per launch (16 x 4 working workgroups co-resident)
     check(gru_bidir(gi + (size_t)g0 * T * 6 * GRU_H, whh_f, bhh_f, whh_b, bhh_b, T, out + (size_t)g0 * T * 2 * GRU_H,
-                    xchg + gru_xchg_words(g0), status, &c.gru_tags[xchg + gru_xchg_words(g0)], s, std::min(16, B - g0)),
+                    xchg + gru_xchg_words(g0), status, &c.gru_tags[xchg + gru_xchg_words(g0)], s, std::min(16, B - g0),
+                    Tv ? Tv + g0 : nullptr),
           "gru");
   if (hook) hook(s);
 }
@@ -508,7 +510,14 @@ void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, co
 // E2E on B mel chunk images [B][Fc][128] (already padded to a multiple of 32 frames) -> sal [B][Fc][360].
 // Pooling and the per-row transforms run on the B images stacked along time (every level's height is
 // even, so no 2x2 window straddles two images); convolutions take the image as their batch index.
-static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int B = 1) {
+// hv (device, optional; row l of ldh ints: the images' own heights at level l, Fp_b >> l): images of different heights,
+// each a multiple of 32 frames of its Fc rows. Every 3x3 conv and up-conv then reads zero at an image's rows from its
+// own height on (ConvArgs::h_in), which is the zero padding a pass on that image alone has there, and the BiGRU runs
+// each sequence over its own frames; pooling, the 1x1 shortcuts, the layout change and the linears are row-wise. An
+// image's rows past its own height hold no meaning at any stage and no valid row reads them.
+static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int B = 1, const int* hv = nullptr,
+                      int ldh = 0) {
+  auto hl = [&](int level) { return hv ? hv + (size_t)level * ldh : nullptr; };
   int H = Fc, W = NMEL;
   // encoder: level outputs go to the second half of the decoder concat buffers
   float* catb[LEVELS];
@@ -525,7 +534,7 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
       const bool last = b == NBLK - 1;
       float* out = last ? catb[i] + cout : (b % 2 == 0 ? pa : pb);
       conv_block(c, "rm.enc" + std::to_string(i) + "." + std::to_string(b), in, ldi, H, W, ci, cout, out,
-                 last ? 2 * cout : cout, s, B);
+                 last ? 2 * cout : cout, s, B, hl(i));
       in = out;
       ldi = last ? 2 * cout : cout;
       ci = cout;
@@ -550,7 +559,7 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
       for (int b = 0; b < NBLK; ++b, ++k) {
         float* out = (k % 2 == 0) ? ia : ib;
         conv_block(c, "rm.int" + std::to_string(i) + "." + std::to_string(b), in, ldi, H, W, ci, top, out, top, s,
-                   B);
+                   B, hl(LEVELS));
         in = out;
         ci = top;
         ldi = top;
@@ -589,6 +598,7 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
       a.batch = B;
       a.x_bs = (long long)H * W * ldx;
       a.y_bs = (long long)(2 * H) * (2 * W) * 2 * co;
+      a.h_in = hl(LEVELS - i);  // the tap at h + 1 reads zero at an image's own last row
       run2(c, a, s, 2.0 * B * H * W * (double)C * co * 9);
     }
     H *= 2;
@@ -599,7 +609,7 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
     int ci = 2 * co, ldi = 2 * co;
     for (int b = 0; b < NBLK; ++b) {
       float* out = (b % 2 == 0) ? da : db;
-      conv_block(c, q + "." + std::to_string(b), in, ldi, H, W, ci, co, out, co, s, B);
+      conv_block(c, q + "." + std::to_string(b), in, ldi, H, W, ci, co, out, co, s, B, hl(LEVELS - 1 - i));
       in = out;
       ci = co;
       ldi = co;
@@ -610,14 +620,14 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
   }
   // cnn (16 -> 3, 3x3, bias) -> [Fc][3*128] (index c*128 + w) -> BiGRU -> Linear + sigmoid
   float* cn = c.buf<float>("rm.cnn", (size_t)B * Fc * NMEL * 3, s);
-  run2(c, c2d(x, ldx, H, W, C_BASE, c.W("rm.cnn.w"), 3, c.W("rm.cnn.b"), cn, 3, B), s);
+  run2(c, c2d(x, ldx, H, W, C_BASE, c.W("rm.cnn.w"), 3, c.W("rm.cnn.b"), cn, 3, B, hl(0)), s);
   float* feat = c.buf<float>("rm.feat", (size_t)B * Fc * 3 * NMEL, s);
   check(nhwc_to_hcw(cn, B * Fc, NMEL, 3, feat, s), "nhwc_to_hcw");
   float* gi = c.buf<float>("rm.gi", (size_t)B * Fc * 6 * GRU_H, s);
   run1(c, lin(feat, 3 * NMEL, B * Fc, 3 * NMEL, c.W("rm.gru.wih"), 6 * GRU_H, c.W("rm.gru.bih"), gi, 6 * GRU_H), s);
   float* go = c.buf<float>("rm.gruout", (size_t)B * Fc * 2 * GRU_H, s);
   gru_bidir_run(c, gi, B, Fc, c.W("rm.gru.whh_f"), c.W("rm.gru.bhh_f"), c.W("rm.gru.whh_b"), c.W("rm.gru.bhh_b"), go, -1,
-                s);
+                s, hl(0));
   ConvArgs f = lin(go, 2 * GRU_H, B * Fc, 2 * GRU_H, c.W("rm.fc.w"), NCLS, c.W("rm.fc.b"), sal, NCLS);
   f.act = ACT_SIGMOID;
   run1(c, f, s);
@@ -678,6 +688,83 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
 int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double* f0, int64_t cap, float* hidden,
                       hipStream_t s) {
   return rmvpe_forward_b(c, audio, n, n, 1, thred, f0, cap, hidden, s);
+}
+
+// B sequences of nv[b] samples in one launch set: row b has F_b = 1 + nv[b] / 160 frames and runs as an image of
+// Fp_b = 32 ceil(F_b / 32) frames inside [B][Fp_max][128]. In every stage a row's valid values are those of
+// rmvpe_forward on that row alone, up to summation order:
+//   - the mel reflect-pads each row at its own end (samples past nv[b] are never read); the STFT and mel GEMMs run over
+//     all B F_max frames, a row's frames past F_b on the zeros after it (finite, never read);
+//   - the frame padding reflects about each row's own F_b up to Fp_b, zeros after;
+//   - the U-Net and the BiGRU take the rows' heights (e2e_chunk);
+//   - the decode and the salience copy stop at F_b.
+// Rows go through 64 images at a time, as rmvpe_forward_b's. The reference's 32000-frame chunking is not taken in this
+// form: a row that long is refused. Equal lengths are rmvpe_forward_b, bit for bit (rvcx_workspace_bytes sizes the
+// ragged form).
+int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, float thred, double* f0,
+                        int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s) {
+  if (B < 1) throw Error(RVCX_E_INVALID, "rmvpe: batch < 1");
+  int64_t n_max = 0;
+  bool equal = true;
+  for (int b = 0; b < B; ++b) {
+    if (nv[b] < NFFT / 2 + 1) throw Error(RVCX_E_SHAPE, "rmvpe: input shorter than 513 samples");
+    n_max = std::max(n_max, nv[b]);
+    equal = equal && nv[b] == nv[0];
+  }
+  if (lda < n_max && B > 1) throw Error(RVCX_E_INVALID, "rmvpe: row stride shorter than the longest row");
+  const int64_t F_max64 = 1 + n_max / HOP;
+  if (F_max64 > ldf) throw Error(RVCX_E_CAPACITY, "rmvpe: output needs " + std::to_string(F_max64) + " frames per row");
+  if (hidden && F_max64 > ld_hidden)
+    throw Error(RVCX_E_CAPACITY, "rmvpe: salience needs " + std::to_string(F_max64) + " frames per row");
+  if (F_out)
+    for (int b = 0; b < B; ++b) F_out[b] = 1 + nv[b] / HOP;
+  if (equal && !c.sizing_plan) {
+    const int64_t F = F_max64;
+    const bool f0_tight = ldf == F || B == 1, hid_tight = !hidden || ld_hidden == F || B == 1;
+    double* f0b = f0_tight ? f0 : c.buf<double>("rm.f0v", (size_t)B * F, s);
+    float* hb = hid_tight ? hidden : c.buf<float>("rm.hidv", (size_t)B * F * NCLS, s);
+    rmvpe_forward_b(c, audio, n_max, lda, B, thred, f0b, F, hb, s);
+    if (!f0_tight)
+      RVCX_HIP(hipMemcpy2DAsync(f0, (size_t)ldf * sizeof(double), f0b, (size_t)F * sizeof(double),
+                                (size_t)F * sizeof(double), B, hipMemcpyDeviceToDevice, s));
+    if (!hid_tight)
+      RVCX_HIP(hipMemcpy2DAsync(hidden, (size_t)ld_hidden * NCLS * sizeof(float), hb, (size_t)F * NCLS * sizeof(float),
+                                (size_t)F * NCLS * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+    return F;
+  }
+  const int chunk = 32000;
+  if (32 * ((F_max64 - 1) / 32 + 1) > chunk)
+    throw Error(RVCX_E_SHAPE, "rmvpe: a row of more than 32000 padded frames takes the single-row call");
+  const int F_max = (int)F_max64, Fp_max = 32 * ((F_max - 1) / 32 + 1);
+  // per-row lengths on device: n | F | the image heights Fp >> level, level 0 .. LEVELS
+  std::vector<int32_t> hl((size_t)(3 + LEVELS) * B);
+  for (int b = 0; b < B; ++b) {
+    const int F = (int)(1 + nv[b] / HOP), Fp = 32 * ((F - 1) / 32 + 1);
+    if (Fp - F >= F) check(hipErrorInvalidValue, "pad_frames");  // reflect_pad_rows' refusal of that row alone
+    hl[b] = (int32_t)nv[b];
+    hl[B + b] = F;
+    for (int l = 0; l <= LEVELS; ++l) hl[(size_t)(2 + l) * B + b] = Fp >> l;
+  }
+  int32_t* dl = c.buf<int32_t>("rm.lens", hl.size(), s);
+  RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
+  const int32_t *dn = dl, *dF = dl + B, *dH = dl + 2 * (size_t)B;
+  float* mel = c.buf<float>("rm.melout", (size_t)B * F_max * NMEL, s);
+  mel_forward(c, MEL, "rm.", audio, n_max, lda, B, MelFrames{NFFT / 2, NFFT / 2, false, F_max, F_max, false}, mel, s, dn);
+  float* img = c.buf<float>("rm.img", (size_t)B * Fp_max * NMEL, s);
+  check(reflect_pad_rows_v(mel, dF, dH, F_max, Fp_max, NMEL, img, s, B), "pad_frames");
+  const auto& bn0 = c.host[2].at("__bn0__").v;
+  check(affine_inplace(img, (long long)B * Fp_max * NMEL, bn0[0], bn0[1], s), "bn0");
+  float* sal = c.buf<float>("rm.sal", (size_t)B * Fp_max * NCLS, s);
+  for (int b0 = 0; b0 < B; b0 += 64) {  // the BiGRU keeps 4 co-resident workgroups per sequence
+    const int nb = std::min(64, B - b0);
+    e2e_chunk(c, img + (size_t)b0 * Fp_max * NMEL, Fp_max, sal + (size_t)b0 * Fp_max * NCLS, s, nb, dH + b0, B);
+  }
+  if (hidden)
+    for (int b = 0; b < B; ++b)
+      RVCX_HIP(hipMemcpyAsync(hidden + (size_t)b * ld_hidden * NCLS, sal + (size_t)b * Fp_max * NCLS,
+                              (size_t)hl[B + b] * NCLS * sizeof(float), hipMemcpyDeviceToDevice, s));
+  check(rmvpe_decode(sal, F_max, NCLS, thred, f0, s, B, Fp_max, dF, ldf), "decode");
+  return F_max;
 }
 
 }  // namespace rvcx

@@ -214,8 +214,9 @@ int proposed_key(const std::vector<double>& f0, double threshold) {
 
 // f0_method of rvcx_pipeline_opts against the loaded models
 static void check_f0_method(const Ctx& c, const rvcx_pipeline_opts& o) {
-  if (o.f0_method < 0 || o.f0_method > 3)
-    throw Error(RVCX_E_INVALID, "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX), 2 (crepe, rvc/) or 3 (fcpe)");
+  if (o.f0_method < 0 || o.f0_method > 4)
+    throw Error(RVCX_E_INVALID,
+                "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX), 2 (crepe, rvc/), 3 (fcpe) or 4 (rmvpe, ragged)");
   if (!c.scfg.f0) return;
   if ((o.f0_method == 1 || o.f0_method == 2) && !c.ready[RVCX_MODEL_CREPE])
     throw Error(RVCX_E_STATE, "pipeline: f0_method crepe but no CREPE weights finalized");
@@ -281,10 +282,12 @@ static void pitch_from_f0(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B
           "f0_post");
 }
 
-int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
+int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& opts,
                             const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
                             double* f0_out, hipStream_t s) {
-  check_pipeline_opts(c, o, n);
+  check_pipeline_opts(c, opts, n);
+  rvcx_pipeline_opts o = opts;
+  if (o.f0_method == 4) o.f0_method = 0;  // one utterance: the ragged RMVPE pass is the single-row one
   if (o.index_rate > 0 && c.ivf->view.d != c.scfg.emb_dim)
     throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension does not match the model's feature width");
   const int64_t W = 160;  // Pipeline.window
@@ -513,16 +516,16 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
 // row b at out + b*ldo, f0_out row b at f0_out + b*ldf.
 //   - rows of one length throughout (`plain` below) take the equal-length routes: HuBERT without masks, the synthesizer
 //     with full lengths, one batched RMVPE straight from the padded input (hidden_out, its salience, only then).
-//   - f0: RMVPE cannot take ragged rows exactly: its mel is reflect-padded at a row's own end and zero-padded to a
-//     multiple of 32 frames there, every 3x3 conv of the U-Net zero-pads at the image's own last frame, and the BiGRU's
-//     reverse recurrence starts there. Rows therefore run through the single-row forward, rows of equal length inside
-//     the batch together through the batched one.
+//   - f0: under f0_method 0 rows run through RMVPE's single-row forward, rows of equal length inside the batch together
+//     through the batched one, so a row's f0 is the single run's bit for bit; f0_method 4 runs all rows in one ragged
+//     pass (rmvpe_forward_v: a length per row in the mel's and the frames' reflect pads, the U-Net's zero padding and
+//     the BiGRU), equal to it up to summation order.
 //   - the generator runs over the common window [t_pad_tgt, Tv_max upp - t_pad_tgt) on z * mask, as the reference's
 //     own batched Synthesizer.infer does: a shorter row's last frames, within the generator's receptive field of its
 //     end, see the zeroed pad frames' activations where a run of that row alone sees the conv's zero padding. The trim
 //     removes them only if t_pad_tgt covers the receptive field, so differing lengths with a smaller t_pad_tgt are refused.
 void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
-                           const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
+                           const rvcx_pipeline_opts& opts, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
                            float* hidden_out, hipStream_t s) {
   if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
@@ -530,13 +533,18 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   bool equal = true;
   for (int b = 0; b < B; ++b) {
     if (nv[b] <= 0 || (B > 1 && nv[b] > lda)) throw Error(RVCX_E_INVALID, "pipeline_batch: bad row length");
-    check_pipeline_opts(c, o, nv[b]);
-    if (o.t_max > 0 && nv[b] + 160 > o.t_max)
+    check_pipeline_opts(c, opts, nv[b]);
+    if (opts.t_max > 0 && nv[b] + 160 > opts.t_max)
       throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
     if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
     n_max = std::max(n_max, nv[b]);
     equal = equal && nv[b] == nv[0];
   }
+  // f0_method 4: all rows in one ragged RMVPE pass; equal lengths (outside the arena query, which sizes the ragged
+  // pass) and one row are method 0
+  rvcx_pipeline_opts o = opts;
+  const bool ragged_f0 = o.f0_method == 4 && B > 1 && (!equal || c.sizing_plan);
+  if (o.f0_method == 4) o.f0_method = 0;
   const int E = c.scfg.emb_dim, upp = c.scfg.upp();
   if (!equal && o.t_pad_tgt < (int64_t)dec_margin_frames(c.scfg) * upp)
     throw Error(RVCX_E_INVALID, "pipeline_batch: rows of different lengths need t_pad_tgt >= " +
@@ -603,6 +611,9 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
     if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
       for (int b : order)
         f0_row(c, o, pad32 + (size_t)b * ldm, mv[b], f0 + (size_t)b * F_max, Fv[b], "pb.f0f", s);
+    } else if (ragged_f0) {
+      rmvpe_forward_v(c, pad32, mv.data(), ldm, B, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F_max, nullptr,
+                      nullptr, 0, s);
     } else {
       const float thr = o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f;
       // rows of equal length together; the groups largest first (rows x frames), so the work buffers a group shares

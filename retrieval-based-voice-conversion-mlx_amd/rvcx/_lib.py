@@ -188,6 +188,7 @@ SIG = {
     "rvcx_hubert_batch": (i32, [vp, vp, i64, i64, i32, i32, vp, i64, P(i64), vp]),
     "rvcx_hubert_batch_v": (i32, [vp, vp, P(i64), i64, i32, i32, vp, i64, P(i64), vp]),
     "rvcx_rmvpe_batch": (i32, [vp, vp, i64, i64, i32, f32, vp, i64, P(i64), vp, vp]),
+    "rvcx_rmvpe_batch_v": (i32, [vp, vp, P(i64), i64, i32, f32, vp, i64, P(i64), vp, i64, vp]),
     "rvcx_rt_default_desc": (i32, [P(RtDesc)]),
     "rvcx_rt_default_opts": (i32, [P(RtOpts)]),
     "rvcx_rt_create": (i32, [vp, P(RtDesc), P(vp)]),
@@ -217,6 +218,8 @@ TEST_SIG = {
     "rvcx_conv1d_ex": (i32, [vp, P(ConvTestDesc), P(i32), P(i32), vp]),
     "rvcx_conv2d3x3": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "rvcx_convtranspose2d_s2": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
+    "rvcx_conv2d3x3_v": (i32, [vp, vp, i32, P(i32), i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
+    "rvcx_convtranspose2d_s2_v": (i32, [vp, vp, i32, P(i32), i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "rvcx_flash_attention": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp]),
     "rvcx_resblock_pair": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
@@ -230,6 +233,7 @@ TEST_SIG = {
     "rvcx_kmeans_update": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp]),
     "rvcx_rt_model_rows": (i32, [vp, vp, i32, vp, i64, vp]),
     "rvcx_gru_bidir": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "rvcx_gru_bidir_v": (i32, [vp, vp, i32, P(i32), vp, vp, vp, vp, vp, i64, vp]),
     "rvcx_dec_source": (i32, [vp, i32, i32, vp, vp, u64, vp, vp]),
 }
 

@@ -361,6 +361,31 @@ class Engine(KernelTestMixin):
                                               ctypes.byref(fo), _ptr(hid), self.stream()), "rmvpe_batch")
         return (f0, hid) if want_hidden else f0
 
+    def rmvpe_batch_v(self, audios, thred: float = 0.03, want_hidden: bool = False):
+        """audios: a list of [N_b] arrays (16 kHz) of any lengths -> a list of f0 fp64 [1 + N_b//160] on device (and
+        the list of saliences [F_b, 360]), from one ragged pass over all rows (rvcx_rmvpe_batch_v: each row is `rmvpe`'s
+        on that row alone, up to summation order)."""
+        t = self.torch
+        rows = [self._dev(a, t.float32).reshape(-1) for a in audios]
+        B = len(rows)
+        if B < 1:
+            return ([], []) if want_hidden else []
+        ns = [int(r.numel()) for r in rows]
+        lda = max(ns)
+        a = t.zeros((B, lda), dtype=t.float32, device=self.device)
+        for b, r in enumerate(rows):
+            a[b, : ns[b]] = r
+        F = 1 + lda // 160
+        f0 = t.empty((B, F), dtype=t.float64, device=self.device)
+        hid = t.empty((B, F, 360), dtype=t.float32, device=self.device) if want_hidden else None
+        F_arr = (ctypes.c_int64 * B)()
+        self._check(self.lib.rvcx_rmvpe_batch_v(self.ctx, a.data_ptr(), (ctypes.c_int64 * B)(*ns), lda, B, float(thred),
+                                                f0.data_ptr(), F, F_arr, _ptr(hid), F, self.stream()), "rmvpe_batch_v")
+        f0s = [f0[b, : int(F_arr[b])] for b in range(B)]
+        if not want_hidden:
+            return f0s
+        return f0s, [hid[b, : int(F_arr[b])] for b in range(B)]
+
     def rmvpe_decode(self, hidden, thred: float = 0.03):
         """RMVPE0Predictor.decode on device: salience [F, 360] -> f0 fp64 [F]."""
         t = self.torch

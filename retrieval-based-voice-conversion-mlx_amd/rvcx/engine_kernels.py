@@ -137,6 +137,22 @@ class KernelTestMixin:
                                             self.stream()), "gru_bidir")
         return out
 
+    def gru_bidir_v(self, gi, T, whh_f, bhh_f, whh_b, bhh_b, tag_start: int = 0):
+        """gru_bidir for sequences of different lengths in the same launches (rvcx_gru_bidir_v): gi [B, max(T), 1536],
+        T the B step counts -> out [B, max(T), 512] (device); sequence b's rows from T[b] on are not written (they hold
+        NaN here)."""
+        t = self.torch
+        g = self._dev(gi, t.float32)
+        B, Tm, _ = g.shape
+        Tv = (ctypes.c_int32 * B)(*[int(v) for v in T])
+        assert g.shape[2] == 1536 and len(T) == B and max(T) == Tm
+        w = [self._dev(x, t.float32) for x in (whh_f, bhh_f, whh_b, bhh_b)]
+        out = t.full((B, Tm, 512), float("nan"), dtype=t.float32, device=self.device)
+        self._check(self.lib.rvcx_gru_bidir_v(self.ctx, g.data_ptr(), B, Tv, w[0].data_ptr(), w[1].data_ptr(),
+                                              w[2].data_ptr(), w[3].data_ptr(), out.data_ptr(), int(tag_start),
+                                              self.stream()), "gru_bidir_v")
+        return out
+
     def dec_source(self, f0, eps_src=None, seed: int = 0):
         """The decoder's harmonic source alone (rvcx_dec_source, include/rvcx_test.h): f0 [B, T] -> har
         [B, T * upp] (device), NSF SineGen or the MRF source of the loaded configuration; eps_src as dec_only's."""
@@ -304,6 +320,42 @@ class KernelTestMixin:
         m = {"default": 0, "f32": 1}[math]
         self._check(self.lib.rvcx_convtranspose2d_s2(self.ctx, _ptr(x), H, W, C, _ptr(wd), _ptr(b), N,
                                                      1 if relu else 0, m, _ptr(y), self.stream()), "convtranspose2d_s2")
+        return y
+
+    def conv2d3x3_v(self, x, heights, w, bias=None, relu: bool = False, math: str = "default"):
+        """conv2d3x3 on B images of different heights in one launch (rvcx_conv2d3x3_v): x [B][H_max][W][C_in], heights
+        the B own heights -> [B][H_max][W][N]; image b's rows below heights[b] are conv2d3x3's on x[b, :heights[b]], a
+        tap from row heights[b] on reading zero whatever x holds there."""
+        torch = self.torch
+        x = self._dev(x, torch.float32).contiguous()
+        w = torch.as_tensor(w, dtype=torch.float32)
+        N, C = int(w.shape[0]), int(w.shape[1])
+        wk = self._dev(w.permute(2, 3, 0, 1).reshape(9, N, C).contiguous(), torch.float32)
+        b = self._dev(bias, torch.float32) if bias is not None else None
+        B, H, W = (int(v) for v in x.shape[:3])
+        hv = (ctypes.c_int32 * B)(*[int(v) for v in heights])
+        y = torch.empty((B, H, W, N), dtype=torch.float32, device=self.device)
+        m = {"default": 0, "f32": 1, "gsw": 2}[math]
+        self._check(self.lib.rvcx_conv2d3x3_v(self.ctx, _ptr(x), B, hv, H, W, C, _ptr(wk), _ptr(b), N,
+                                              1 if relu else 0, m, _ptr(y), self.stream()), "conv2d3x3_v")
+        return y
+
+    def convtranspose2d_s2_v(self, x, heights, w, bias=None, relu: bool = False, math: str = "default"):
+        """convtranspose2d_s2 on B images of different heights in one launch (rvcx_convtranspose2d_s2_v): x
+        [B][H_max][W][C_in] -> [B][2 H_max][2 W][N]; image b's rows below 2 heights[b] are convtranspose2d_s2's on
+        x[b, :heights[b]]."""
+        torch = self.torch
+        x = self._dev(x, torch.float32).contiguous()
+        wd = self._dev(torch.as_tensor(w, dtype=torch.float32).contiguous(), torch.float32)
+        C, N = int(wd.shape[0]), int(wd.shape[1])
+        b = self._dev(bias, torch.float32) if bias is not None else None
+        B, H, W = (int(v) for v in x.shape[:3])
+        hv = (ctypes.c_int32 * B)(*[int(v) for v in heights])
+        y = torch.empty((B, 2 * H, 2 * W, N), dtype=torch.float32, device=self.device)
+        m = {"default": 0, "f32": 1}[math]
+        self._check(self.lib.rvcx_convtranspose2d_s2_v(self.ctx, _ptr(x), B, hv, H, W, C, _ptr(wd), _ptr(b), N,
+                                                       1 if relu else 0, m, _ptr(y), self.stream()),
+                    "convtranspose2d_s2_v")
         return y
 
     def flash_attention(self, qkv, n_heads: int, qscale: float, rel_k=None, rel_v=None, window: int = 0, mask=None):

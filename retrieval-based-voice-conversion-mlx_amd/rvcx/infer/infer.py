@@ -180,17 +180,18 @@ class RVCX:
     def convert_many(self, audios, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75, volume_envelope=1.0,
                      protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, sid=0, proposed_pitch=False,
                      proposed_pitch_threshold=155.0, seed: int = 0, batch: Optional[int] = None,
-                     max_pad: Optional[float] = None, noise_fn=None):
+                     max_pad: Optional[float] = None, noise_fn=None, ragged_f0: bool = False):
         """`convert` over a list of 16 kHz utterances of any lengths -> the outputs in input order. Utterances of
         similar length share one batched pass (PipelineRVCX.pipeline_many: sorted by length, a batch filled while its
-        shortest row is at least (1 - max_pad) of its longest, inputs above t_max converted alone)."""
+        shortest row is at least (1 - max_pad) of its longest, inputs above t_max converted alone). ragged_f0
+        (f0_method "rmvpe" only): the rows of a batch also share one ragged RMVPE pass."""
         from .pipeline import DEFAULT_BATCH, DEFAULT_MAX_PAD
 
         return self.pipeline.pipeline_many(
             self.hubert_model, self.net_g, sid, audios, pitch, f0_method, index_path, index_rate, self.use_f0,
             volume_envelope, self.version, protect, f0_autotune, f0_autotune_strength, proposed_pitch,
             proposed_pitch_threshold, seed=seed, batch=DEFAULT_BATCH if batch is None else batch,
-            max_pad=DEFAULT_MAX_PAD if max_pad is None else max_pad, noise_fn=noise_fn)
+            max_pad=DEFAULT_MAX_PAD if max_pad is None else max_pad, noise_fn=noise_fn, ragged_f0=ragged_f0)
 
     def infer_batch(self, input_dir, output_dir, **kw):
         """convert_audio_batch (rvc/infer/infer.py:350-414) over the WAV files of input_dir: every file converted with

@@ -63,6 +63,11 @@ class RMVPE0Predictor:
         f0 = self.engine.rmvpe(_np(audio).reshape(-1), thred)
         return self.engine.host(f0)
 
+    def infer_from_audio_batch(self, audios, thred: float = 0.03):
+        """infer_from_audio over a list of utterances of any lengths in one ragged pass -> the list of f0 arrays."""
+        f0s = self.engine.rmvpe_batch_v([_np(a).reshape(-1) for a in audios], thred)
+        return [self.engine.host(f) for f in f0s]
+
     def infer_from_audio_with_hidden(self, audio, thred: float = 0.03):
         f0, hidden = self.engine.rmvpe(_np(audio).reshape(-1), thred, want_hidden=True)
         return self.engine.host(f0), self.engine.host(hidden)

@@ -259,18 +259,27 @@ class PipelineRVCX:
     def pipeline_many(self, model, net_g, sid, audios, pitch=0, f0_method="rmvpe", file_index=None, index_rate=0.0,
                       pitch_guidance=True, volume_envelope=1.0, version="v2", protect=0.33, f0_autotune=False,
                       f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, seed: int = 0,
-                      batch: int = DEFAULT_BATCH, max_pad: float = DEFAULT_MAX_PAD, noise_fn=None):
+                      batch: int = DEFAULT_BATCH, max_pad: float = DEFAULT_MAX_PAD, noise_fn=None,
+                      ragged_f0: bool = False):
         """`pipeline` over a list of utterances of any lengths -> the list of float32 outputs in input order.
         The utterances are grouped longest first into batches of up to `batch` rows whose shortest is at least
         (1 - max_pad) of the longest (rvcx.offline.bucket) and every batch is one rvcx_pipeline_batch_v pass; an
         utterance above t_max goes through `pipeline` alone (the batched pass takes single-chunk rows). batch = 1 is
         the per-utterance loop. Batch k draws its noise from seed + k; noise_fn(i, T) -> (eps_z [inter, T], eps_src
-        [T * upp]) injects utterance i's noise instead (T its synthesizer frames), as the tests do."""
+        [T * upp]) injects utterance i's noise instead (T its synthesizer frames), as the tests do.
+        ragged_f0 (f0_method "rmvpe" only, else ValueError): the rows of a batch share one ragged RMVPE pass
+        (rvcx_pipeline_opts.f0_method 4) instead of one pass per row; a row's f0 then equals the per-row pass up to
+        summation order, not bit for bit."""
         from ..offline import bucket
+
+        if ragged_f0 and f0_method != "rmvpe":
+            raise ValueError(f'ragged_f0 runs RMVPE: f0_method must be "rmvpe", not {f0_method!r}')
 
         eng, opts = self._pipeline_opts(model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance,
                                         volume_envelope, version, protect, f0_autotune, f0_autotune_strength,
                                         proposed_pitch, proposed_pitch_threshold)
+        if ragged_f0:
+            opts.f0_method = 4
         audios = [np.asarray(a, dtype=np.float64).reshape(-1) for a in audios]
         outs = [None] * len(audios)
         upp = eng.upp

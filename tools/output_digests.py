@@ -6,7 +6,8 @@ One line per output: RMVPE (single and batched, a frame count that is no multipl
 synthesizer with each vocoder, a 6-hop stream group (once more with a volume envelope on one of its streams), both
 pipeline forms for f0_method 0 / 2 / 3 under autotune and under proposed pitch and with a volume envelope, the batched
 pipeline's salience, and the ragged forms: HuBERT over rows of five lengths, the pipeline over rows of three lengths
-(plain and with a volume envelope) and over two equal rows.
+(plain and with a volume envelope) and over two equal rows, RMVPE over rows of five lengths in one ragged pass and the
+ragged pipeline with it (f0_method 4).
 
     python tools/output_digests.py > digests.txt
 """
@@ -39,7 +40,7 @@ def synth_inputs(cfg, B, T, seed):
 
 
 def main():
-    from rvcx import synthetic
+    from rvcx import _lib, synthetic
     from rvcx.config import SYNTH_48K_V2
     from rvcx.engine import Engine
     from rvcx.realtime import StreamGroup
@@ -109,6 +110,14 @@ def main():
         opts = eng.pipeline_opts(pitch=2.0, t_pad=4800, t_pad_tgt=14400, **kw)
         ys, f0s = eng.pipeline_batch_v(ragged, opts, sids=[0, 3, 7, 0], seed=3, want_f0=True)
         show(f"pipeline_batch_v ragged {tag}", *ys, *f0s)
+    if "rvcx_rmvpe_batch_v" in _lib.exported_symbols():  # a library from before the ragged RMVPE pass ends here
+        rows = [synthetic.speech_like(n, seed=70 + i).astype(f32) for i, n in
+                enumerate((2720, 4960, 5280, 10080, 16000))]
+        f0s, hids = eng.rmvpe_batch_v(rows, want_hidden=True)
+        show("rmvpe_batch_v 5 rows", *f0s, *hids)
+        opts = eng.pipeline_opts(pitch=2.0, t_pad=4800, t_pad_tgt=14400, f0_method=4)
+        ys, f0s = eng.pipeline_batch_v(ragged, opts, sids=[0, 3, 7, 0], seed=3, want_f0=True)
+        show("pipeline_batch_v ragged f0_method=4", *ys, *f0s)
     eng.close()
 
 

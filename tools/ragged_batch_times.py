@@ -9,7 +9,12 @@ synchronise, after one untimed warm-up pass over the same shapes; --reps passes,
   (b) `Engine.pipeline_batch_v` per batch of `offline.bucket(lengths, batch, max_pad)`, batch in {4, 8, 16} and
       max_pad in {0.05, 0.125, 0.25}, with the share of computed synthesizer frames that are padding.
   (c) `Engine.hubert_batch_v` over the same batches against a loop of `Engine.hubert`.
+  (d) (b) with f0_method 4: the rows of a batch in one ragged RMVPE pass instead of one pass per row. (b) and (d) of a
+      setting are timed alternately, pass by pass, in the same process; the ratio of their medians is printed and
+      called a gain (loss) only if it exceeds the spread of (b)'s own repeats.
+  (e) `Engine.rmvpe_batch_v` over the same batches against a loop of `Engine.rmvpe`.
 A batched setting is called faster (slower) only if its median lies below (above) the loop's own min .. max.
+(d) and (e) are skipped on a library without rvcx_rmvpe_batch_v (one built from an older commit through RVCX_LIB).
 
     python tools/ragged_batch_times.py [--reps 5] [--loop-only] [--only BATCH MAX_PAD] > profiles/ragged_batch_times.txt
 
@@ -64,16 +69,27 @@ def main():
     clips32 = [c.float() for c in clips64]
     order = sorted(range(N_UTT), key=lambda i: -ns[i])
 
-    def timed(fn):
-        fn()  # warm-up: every shape of the timed pass
-        out = []
-        for _ in range(args.reps):
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
+    def once(fn):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(dev)
+        return time.perf_counter() - t0
+
+    def timed(*fns):
+        """Each fn warmed up once (every shape of the timed pass), then --reps passes of each, alternating."""
+        for fn in fns:
             fn()
-            torch.cuda.synchronize(dev)
-            out.append(time.perf_counter() - t0)
-        return out
+        out = [[] for _ in fns]
+        for _ in range(args.reps):
+            for k, fn in enumerate(fns):
+                out[k].append(once(fn))
+        return out[0] if len(fns) == 1 else out
+
+    have_v = "rvcx_rmvpe_batch_v" in _lib.exported_symbols()
+    if not have_v:
+        print("no rvcx_rmvpe_batch_v in this library: (d) and (e) skipped")
+    opts4 = eng.pipeline_opts(pitch=2.0, protect=0.33, f0_method=4)
 
     res = {}
 
@@ -99,6 +115,13 @@ def main():
            extra=f"(spread {100 * (max(t_pipe) - min(t_pipe)) / statistics.median(t_pipe):.1f} %)")
     t_hub = timed(hub_loop)
     report("(c) loop of hubert", t_hub, extra=f"(spread {100 * (max(t_hub) - min(t_hub)) / statistics.median(t_hub):.1f} %)")
+
+    def rm_loop():
+        for i in order:
+            eng.rmvpe(clips32[i])
+
+    t_rm = timed(rm_loop)
+    report("(e) loop of rmvpe", t_rm, extra=f"(spread {100 * (max(t_rm) - min(t_rm)) / statistics.median(t_rm):.1f} %)")
     if not args.loop_only:
         frames = [eng.pipeline_frames(n, opts) for n in ns]
         for batch in (4, 8, 16) if args.only is None else (int(args.only[0]),):
@@ -116,11 +139,32 @@ def main():
                     for g in groups:
                         eng.hubert_batch_v([clips32[i] for i in g])
 
-                report(f"(b) pipeline_batch_v {key}", timed(pipe_batched), t_pipe,
+                def pipe_batched4():
+                    for k, g in enumerate(groups):
+                        eng.pipeline_batch_v([clips64[i] for i in g], opts4, seed=k)
+
+                def rm_batched():
+                    for g in groups:
+                        eng.rmvpe_batch_v([clips32[i] for i in g])
+
+                t_b, t_d = timed(pipe_batched, pipe_batched4) if have_v else (timed(pipe_batched), None)
+                report(f"(b) pipeline_batch_v {key}", t_b, t_pipe,
                        f"{len(groups):2d} passes  padded frames {100 * pad:5.2f} %")
                 res[f"(b) pipeline_batch_v {key}"].update(passes=len(groups), pad_share=round(pad, 4))
+                if have_v:
+                    report(f"(d) pipeline_batch_v f0_method=4 {key}", t_d, t_pipe)
+                    mb, md = statistics.median(t_b), statistics.median(t_d)
+                    spread = (max(t_b) - min(t_b)) / mb
+                    gain = mb / md - 1
+                    word = "gain" if gain > spread else ("loss" if -gain > spread else "inside (b)'s spread")
+                    print(f"    (d) against (b): {100 * gain:+.2f} % ((b)'s own spread {100 * spread:.2f} %): {word}",
+                          flush=True)
+                    res[f"(d) pipeline_batch_v f0_method=4 {key}"].update(gain_over_b=round(gain, 4),
+                                                                          b_spread=round(spread, 4))
                 report(f"(c) hubert_batch_v {key}", timed(hub_batched), t_hub,
                        f"{len(groups):2d} passes  padded frames {100 * hpad:5.2f} %")
+                if have_v:
+                    report(f"(e) rmvpe_batch_v {key}", timed(rm_batched), t_rm, f"{len(groups):2d} passes")
     print(json.dumps(res))
     eng.close()
 
