@@ -347,8 +347,12 @@ int rvcx_synth_infer(rvcx_ctx* ctx, int B, int T, const float* d_phone, const in
       throw Error(RVCX_E_INVALID, "rvcx_synth_infer: a pitch-guided model needs pitch and pitchf");
     if (!ctx->scfg.f0) d_pitch = nullptr, d_pitchf = nullptr;  // Synthesizer.infer ignores them (:233-239)
     set_device(ctx);
-    synth_forward(*ctx, B, T, d_phone, d_lengths, d_pitch, d_pitchf, d_sid, d_eps_z, d_eps_src, seed, d_out, d_zp,
-                  d_z, static_cast<hipStream_t>(stream));
+    SynthCall syn;
+    syn.B = B, syn.T = T;
+    syn.phone = d_phone, syn.lengths = d_lengths, syn.pitch = d_pitch, syn.pitchf = d_pitchf, syn.sid = d_sid;
+    syn.eps_z = d_eps_z, syn.eps_src = d_eps_src, syn.seed = seed;
+    syn.out = d_out, syn.zp_out = d_zp, syn.z_out = d_z;
+    synth_forward(*ctx, syn, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -374,8 +378,13 @@ int rvcx_synth_infer_ex(rvcx_ctx* ctx, int B, int T, const float* d_phone, const
       if (head >= T) throw Error(RVCX_E_SHAPE, "rvcx_synth_infer_ex: rate keeps no frame (the reference's slice is empty)");
     }
     set_device(ctx);
-    synth_forward(*ctx, B, T, d_phone, d_lengths, d_pitch, d_pitchf, d_sid, d_eps_z, d_eps_src, seed, d_out, d_zp,
-                  d_z, static_cast<hipStream_t>(stream), 0, head, d_m_p, d_logs_p);
+    SynthCall syn;
+    syn.B = B, syn.T = T;
+    syn.phone = d_phone, syn.lengths = d_lengths, syn.pitch = d_pitch, syn.pitchf = d_pitchf, syn.sid = d_sid;
+    syn.eps_z = d_eps_z, syn.eps_src = d_eps_src, syn.seed = seed;
+    syn.out = d_out, syn.zp_out = d_zp, syn.z_out = d_z, syn.mp_out = d_m_p, syn.logsp_out = d_logs_p;
+    syn.head = head;
+    synth_forward(*ctx, syn, static_cast<hipStream_t>(stream));
     if (t_out) *t_out = T - head;
   });
 }
@@ -393,7 +402,11 @@ int rvcx_dec_only(rvcx_ctx* ctx, int B, int T, const float* d_z, const float* d_
     check(transpose_bct_btc(d_z, zt, B, I, T, s), "transpose");
     float* g = ctx->buf<float>("dec_only.g", (size_t)B * ctx->scfg.gin, s);
     check(gather_rows(ctx->W("emb_g"), ctx->scfg.gin, d_sid, g, B, ctx->scfg.gin, s), "emb_g");
-    dec_forward(*ctx, B, T, zt, nullptr, d_f0, g, d_eps_src, seed, d_out, s);
+    DecCall dec;
+    dec.B = B, dec.T = T;
+    dec.z_btc = zt, dec.f0 = d_f0, dec.g = g, dec.eps_src = d_eps_src, dec.seed = seed;
+    dec.out = d_out;
+    dec_forward(*ctx, dec, s);
   });
 }
 
@@ -466,7 +479,7 @@ int rvcx_pipeline_ex(rvcx_ctx* ctx, const double* d_audio, int64_t n, const rvcx
     if (!d_audio || !d_out || !opts || n <= 0) throw Error(RVCX_E_INVALID, "bad arguments");
     set_device(ctx);
     const int64_t no = pipeline_forward_ex(*ctx, d_audio, n, *opts, d_eps_z, d_eps_src, seed, d_out, cap, d_f0,
-                                           static_cast<hipStream_t>(stream));
+                                           static_cast<hipStream_t>(stream), false);
     if (n_out) *n_out = no;
   });
 }
@@ -863,7 +876,7 @@ int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n
       throw Error(RVCX_E_INVALID, "rvcx_pipeline_batch_v: bad arguments");
     set_device(ctx);
     pipeline_forward_rows(*ctx, d_audio, n, lda, B, *opts, sids, d_eps_z, d_eps_src, seed, d_out, ldo, n_out, d_f0, ldf,
-                          nullptr, static_cast<hipStream_t>(stream));
+                          nullptr, static_cast<hipStream_t>(stream), false);
   });
 }
 

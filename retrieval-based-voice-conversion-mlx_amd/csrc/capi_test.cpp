@@ -430,7 +430,6 @@ void gru_bidir_test(rvcx_ctx* ctx, const float* d_gi, int B, int T, const int* T
     RVCX_HIP(hipMemcpyAsync(d, Tv, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, s));
     d_T = d;
   }
-  ctx->before_gru = nullptr;  // nothing is issued beside this launch
   gru_bidir_run(*ctx, d_gi, B, T, d_whh_f, d_bhh_f, d_whh_b, d_bhh_b, d_out, tag_start < 0 ? -1 : (long long)tag_start,
                 s, d_T);
 }

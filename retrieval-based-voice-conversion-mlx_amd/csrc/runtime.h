@@ -153,23 +153,14 @@ struct Ctx {
   // pre-split images of the fused ResBlock pair kernel (resblock_fused.hip), per weight tensor
   std::map<std::pair<const void*, int>, std::unique_ptr<DevBuf>> rb_wsplit_cache;
   const void* rb_wsplit_for(const float* w, int C, int k, int wfmt, hipStream_t s);
-  // set by the internal callers of synth_forward whose every row has the full length T (the pipeline, its batched form,
-  // the streaming hop): the TextEncoder's attention then runs without the all-ones key mask (ScopedFullLengths)
-  bool synth_full_lengths = false;
   // the pipelines and the streaming hop hand the synthesizer the output window their trim keeps (DecWindow below);
   // off: the generator runs full-length (rvcx_set_dec_window; RVCX_DEC_WINDOW=0 at context creation). Same outputs.
+  // The arena query (pipeline_workspace_bytes) passes no window either: it plans the worst case.
   bool dec_window = true;
-  // the window a call site passes: none while the switch is off or the arena query plans its worst case
-  bool use_dec_window() const { return dec_window && !sizing_plan; }
-  // set while HuBERT's feature encoder is being issued (runtime_pipeline.cpp issue_front): the launches RVCX_AUX_LDS
-  // throttles
-  bool aux_front = false;
   // second stream for work independent of the caller's stream (HuBERT beside RMVPE), created lazily
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_gate = nullptr;
   hipStream_t aux_stream();
-  // issued by RMVPE's E2E right before the BiGRU launch (host callback, cleared when taken)
-  std::function<void(hipStream_t)> before_gru;
   // device-side fault flags in pinned host-mapped memory (bit 0: a BiGRU partner hand-off timed out).
   // Kernels store into it; the host reads it after a synchronisation: every compute entry point checks
   // it on entry (faults of earlier, completed calls), the pipeline at its own sync points, and
@@ -210,7 +201,6 @@ struct Ctx {
   char* arena = nullptr;
   size_t arena_bytes = 0, arena_used = 0;
   size_t carved = 0;  // bytes the pool has taken since the last release (every region, regrown ones included)
-  bool sizing_plan = false;  // rvcx_workspace_bytes: long inputs take the worst-case chunk plan (runtime_pipeline.cpp)
   // Call-to-call ordering: every compute entry point starts with begin_call(), which records an event on
   // each stream the previous call took pool buffers on; the first pool buffer a call takes on a stream makes that
   // stream wait for the previous call's events on OTHER streams. A call on stream B therefore never overwrites a
@@ -340,32 +330,42 @@ struct HubertRun {
   int B = 0, L = 0, version = 0;
   float* feats = nullptr;
   const float* mask = nullptr;  // ragged batches: [B][L], 1 on a sequence's own frames (the attention's key mask)
+  // extra LDS bytes per workgroup on every conv launch of the run (ConvArgs::lds_pad): the occupancy throttle of a run
+  // issued beside latency-bound work on another stream. A caller may change it between the parts.
+  int lds_pad = 0;
 };
 HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
-                       int64_t cap, hipStream_t s);
+                       int64_t cap, hipStream_t s, int lds_pad = 0);
 void hubert_layers(Ctx& c, const HubertRun& run, int l0, int l1, hipStream_t s);
 int64_t hubert_tail(Ctx& c, const HubertRun& run, hipStream_t s);
+// Work a caller wants issued beside RMVPE's BiGRU, which occupies 4 CUs per sequence (the pipeline: the rest of HuBERT
+// on the aux stream). The RMVPE forwards issue it once, right after the launches of the first BiGRU group they reach;
+// Ctx::ev_gate is recorded on the stream before those launches, where the hook's work may start.
+using GruHook = std::function<void(hipStream_t)>;
 int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double* f0, int64_t cap, float* hidden,
-                      hipStream_t s);
+                      hipStream_t s, GruHook beside_gru = nullptr);
 // batched over B equal-length inputs (rows of stride lda); outputs back to back per sequence
 int64_t hubert_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
                          int64_t cap, hipStream_t s);
 int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
-                        int64_t cap, float* hidden, hipStream_t s);
+                        int64_t cap, float* hidden, hipStream_t s, GruHook beside_gru = nullptr);
 // RMVPE's BiGRU recurrence on the context's hand-off buffer (runtime_fe.cpp): gi [B][T][1536] -> out [B][T][512], 16
 // sequences per launch; tag_start < 0 continues the buffer's tag counters, >= 0 zeroes it and sets them (the tests).
-// Takes Ctx::before_gru and issues it right after the BiGRU's launches. Tv (device, optional): sequence b runs its own
-// Tv[b] <= T steps in rows of stride T.
+// Tv (device, optional): sequence b runs its own Tv[b] <= T steps in rows of stride T. beside_gru (optional) is issued
+// right after the BiGRU's launches.
 void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
-                   const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv = nullptr);
+                   const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv = nullptr,
+                   const GruHook& beside_gru = nullptr);
 // batched over B inputs of nv[b] samples (host array) in one ragged pass: f0 row b (F_b = 1 + nv[b] / 160 frames) at
 // f0 + b*ldf, its salience (optional) at hidden + b*ld_hidden*360; F_out[b] = F_b (host, optional). Returns the longest
-// row's frames. Equal lengths are rmvpe_forward_b.
+// row's frames. Equal lengths are rmvpe_forward_b, unless force_ragged (the arena query, which sizes the ragged form).
 int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, float thred, double* f0,
-                        int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s);
-// batched over B inputs of nv[b] samples (host array): sequence b's hubert_frames(nv[b]) rows at feats + b*ld_rows*D
+                        int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s,
+                        bool force_ragged = false);
+// batched over B inputs of nv[b] samples (host array): sequence b's hubert_frames(nv[b]) rows at feats + b*ld_rows*D.
+// Equal lengths run without masks, unless force_ragged.
 int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
-                         int64_t ld_rows, int64_t* rows_out, hipStream_t s);
+                         int64_t ld_rows, int64_t* rows_out, hipStream_t s, bool force_ragged = false);
 // The output samples per row a caller of the synthesizer goes on to read, [s0, s1) (s1 < 0: all of them). The HiFi-GAN
 // generators (NSF and no-f0) then run on the window's frames plus their receptive field (dec_margin_frames) and write
 // the window's samples, bit-identical to the full-length run, at their usual place; the samples outside it are
@@ -378,19 +378,49 @@ struct DecWindow {
 int dec_margin_frames(const SynthCfg& cf);
 // the frames [fa, fb) of T the generator runs on for a window ([0, T) without one, or where it would drop too few)
 void dec_window_frames(const SynthCfg& cf, int T, const DecWindow& win, int& fa, int& fb);
-void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* lengths, const int32_t* pitch,
-                   const float* pitchf, const int32_t* sid, const float* eps_z, const float* eps_src, uint64_t seed,
-                   float* out, float* zp_out, float* z_out, hipStream_t s, int gen_lowp = 0, int head = 0,
-                   float* mp_out = nullptr, float* logsp_out = nullptr, const DecWindow& win = DecWindow());
-// head: Synthesizer.infer's rate (synthesizers.py:230-234) as the first kept frame -- the flow and the decoder run on
-// T - head frames (out [B][(T - head) upp], zp_out / z_out [B][T - head][I]); mp_out / logsp_out [B][T][I]
-// gen_lowp: the generator's weight-streamed convs and fused ResBlock pairs on fp16 operands (one MFMA product per
-// step): the realtime hop's opt-in (rvcx_rt_opts::gen_precision), never set by an offline entry point
-// noise_pre: the NSF source and the noise convs of the multi-tap stages were computed ahead by dec_noise_prepare (same
-// B, T, f0, eps_src, seed), on a stream this one has joined since; the ConvTransposes add them as their residual
-void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, const float* f0, const float* g,
-                 const float* eps_src, uint64_t seed, float* out, hipStream_t s, int gen_lowp = 0,
-                 bool noise_pre = false, const DecWindow& win = DecWindow());
+// One Synthesizer.infer call (synthesizers.py:213-243) on B rows of T frames.
+struct SynthCall {
+  int B = 0, T = 0;
+  const float* phone = nullptr;      // [B][T][emb_dim]
+  const int32_t* lengths = nullptr;  // [B]
+  const int32_t* pitch = nullptr;    // [B][T], null without pitch guidance
+  const float* pitchf = nullptr;
+  const int32_t* sid = nullptr;  // [B]
+  const float* eps_z = nullptr;  // injected noise (optional; drawn from seed otherwise)
+  const float* eps_src = nullptr;
+  uint64_t seed = 0;
+  float* out = nullptr;  // [B][(T - head) upp]
+  // optional outputs: zp_out / z_out [B][T - head][I], mp_out / logsp_out [B][T][I]
+  float *zp_out = nullptr, *z_out = nullptr, *mp_out = nullptr, *logsp_out = nullptr;
+  // the generator's weight-streamed convs and fused ResBlock pairs on fp16 operands (one MFMA product per step): the
+  // realtime hop's opt-in (rvcx_rt_opts::gen_precision), never set by an offline entry point
+  int gen_lowp = 0;
+  // Synthesizer.infer's rate (synthesizers.py:230-234) as the first kept frame: the flow and the decoder run on
+  // T - head frames
+  int head = 0;
+  DecWindow win;
+  // every row has the full length T (the pipelines on rows of one length, the streaming hop): the TextEncoder's
+  // attention then runs without the all-ones key mask. Same results.
+  bool full_lengths = false;
+};
+void synth_forward(Ctx& c, const SynthCall& call, hipStream_t s);
+// One generator call on z_btc [B][T][I] (time-major), mask [B][T], f0 [B][T], g [B][gin] -> out [B][T upp].
+struct DecCall {
+  int B = 0, T = 0;
+  const float* z_btc = nullptr;
+  const float* mask = nullptr;
+  const float* f0 = nullptr;
+  const float* g = nullptr;
+  const float* eps_src = nullptr;
+  uint64_t seed = 0;
+  float* out = nullptr;
+  int gen_lowp = 0;  // as SynthCall's
+  // the NSF source and the noise convs of the multi-tap stages were computed ahead by dec_noise_prepare (same B, T,
+  // f0, eps_src, seed), on a stream this one has joined since; the ConvTransposes add them as their residual
+  bool noise_pre = false;
+  DecWindow win;
+};
+void dec_forward(Ctx& c, const DecCall& call, hipStream_t s);
 // the NSF harmonic source (SineGen) and every multi-tap noise conv (hifigan_nsf.py:196-199) into their own buffers:
 // the synthesizer issues it on the aux stream beside the TextEncoder and flow, which leave most of the GPU idle.
 // Returns false (nothing issued) for configurations without the NSF noise branch.
@@ -406,8 +436,8 @@ void set_highpass_sos(Ctx& c, const double* sos, int nsec);
 void highpass_pad(Ctx& c, const double* audio, int64_t n, int64_t t_pad, double* pad64, float* pad32, hipStream_t s);
 int hubert_version_for(const Ctx& c);
 // feats_pre (optional): HuBERT rows of this chunk computed ahead (e.g. on the aux stream), L_pre rows
-// trim: samples per side of the output the caller drops (the pipeline's t_pad_tgt): the generator gets the kept window
-// (DecWindow) while Ctx::use_dec_window(), and the trimmed samples of out are then unspecified
+// trim: samples per side of the output the caller drops (the pipeline's t_pad_tgt, or 0 while the window is off): for
+// trim > 0 the generator gets the kept window (DecWindow), and the trimmed samples of out are then unspecified
 int64_t vc_forward(Ctx& c, const float* audio, int64_t n, const int32_t* pitch, const float* pitchf,
                    int64_t pitch_len, int sid, float protect, double index_rate, const float* eps_z,
                    const float* eps_src, uint64_t seed, float* out, int64_t cap, hipStream_t s,
@@ -466,9 +496,12 @@ void kmeans_assign_run(Ctx& c, const float* x, int64_t n, int d, const float* ce
                        float* dist, hipStream_t s);
 void kmeans_update_run(Ctx& c, const float* x, int64_t n, int d, const int32_t* assign, int64_t nlist, float* cent,
                        int64_t* sizes, hipStream_t s);
+// sizing (here and in pipeline_forward_rows): the call is pipeline_workspace_bytes' measurement and takes the
+// worst-case routes, so that the pool it carves holds any real call of that size -- a long input the chunk plan with
+// the longest possible chunk, a batch the ragged form for equal rows too, and the generator no output window
 int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& o,
                             const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
-                            double* f0_out, hipStream_t s);
+                            double* f0_out, hipStream_t s, bool sizing);
 int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t lda, int B, const rvcx_pipeline_opts& o,
                                const int32_t* sids, const float* eps_z, const float* eps_src, uint64_t seed,
                                float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s);
@@ -478,7 +511,7 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
 void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
                            const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
-                           float* hidden_out, hipStream_t s);
+                           float* hidden_out, hipStream_t s, bool sizing);
 // rvcx_workspace_bytes: the pool a pipeline call of B utterances of n samples under o takes, measured by running it on
 // zero audio from an empty pool (B = 1 pipeline_forward_ex, B > 1 pipeline_forward_rows in its sizing form); a caller
 // arena is detached meanwhile and the pool is released again before it returns
@@ -495,12 +528,6 @@ hipStream_t fork_aux(Ctx& c, hipStream_t s);
 // whether launch_conv's plan runs this 1-D contraction on the weight-streamed fp16 or the weight-stationary kernel
 // without split-K (the kernels whose epilogue takes the fused NSF noise conv, ConvArgs::nz_*)
 bool conv_routes_wsb16(Ctx& c, const ConvArgs& a);
-// marks a synth_forward call whose rows all have the full length T (Ctx::synth_full_lengths) for its lifetime
-struct ScopedFullLengths {
-  Ctx& c;
-  explicit ScopedFullLengths(Ctx& cc, bool full = true) : c(cc) { c.synth_full_lengths = full; }
-  ~ScopedFullLengths() { c.synth_full_lengths = false; }
-};
 void join_aux(Ctx& c, hipStream_t s, hipStream_t ax);
 // launch one implicit-GEMM conv (1-D or 2-D) as conv_plan routes it, with optional event timing; flops = algorithmic
 // FLOPs (runtime_conv.cpp)

@@ -200,20 +200,9 @@ bool conv_routes_wsb16(Ctx& c, const ConvArgs& a_in) {
 }
 
 namespace {
-// the planned launch: the slab, the aux-stream throttle, conv_run and, with kernel timing on, its record
+// the planned launch: the slab, conv_run and, with kernel timing on, its record
 void run_planned(Ctx& c, const ConvPlan& p, ConvArgs& a, bool two_d, bool forced, hipStream_t s, double flops) {
   // split-K slabs are per stream: the aux stream's convs run concurrently with the caller's
-  // HuBERT's feature-encoder contractions (issued on the aux stream beside the U-Net, with ~1.5 ms of slack before the
-  // BiGRU) take 64 KB more LDS per workgroup: one or two of them per CU at most, so the U-Net's latency-bound chain
-  // finds free workgroup slots instead of waiting out ~50 us feature-conv workgroups. Same-box A/B (ms/step): r05ac
-  // none 13.53 / 13.47, 64 KB 13.28 / 13.35, 88 KB 13.25 / 13.27, 40 KB 13.39 / 13.51; r05ae none 13.53 / 13.54 /
-  // 13.48 / 13.51, 64 KB 13.39 / 13.16 / 13.37 / 13.33, 88 KB 13.48 / 13.29. Throttling HuBERT's transformer too
-  // (r05aa) costs +0.3-0.5 ms: it runs beside the BiGRU with little slack. RVCX_AUX_LDS=KB overrides (0: off)
-  static const int aux_lds = [] {
-    const char* e = rvcx_knob("RVCX_AUX_LDS");
-    return e ? std::max(0, std::atoi(e)) : 64;
-  }();
-  if (aux_lds > 0 && c.aux_front) a.lds_pad = aux_lds * 1024;
   if (p.ksplit > 1)
     a.ws = c.buf<float>(c.aux && s == c.aux ? "conv.splitk.aux" : "conv.splitk", (size_t)p.slab_floats, s);
   auto run = [&] {

@@ -4,6 +4,7 @@
 //   RMVPE : rvc/lib/predictors/RMVPE.py (E2E U-Net + BiGRU, MelSpectrogram, decode);
 //           MLX rvc_mlx/lib/mlx/rmvpe.py.
 #include <cmath>
+#include <utility>
 
 #include "model_build.h"
 
@@ -97,7 +98,7 @@ int64_t hubert_frames(int64_t n) {
 //     reads past a sequence's end;
 //   - attention masks the pad keys (run.mask); every other op is row-wise.
 static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv, int64_t lda, int B, int version,
-                       float* feats, int64_t cap, hipStream_t s) {
+                       float* feats, int64_t cap, hipStream_t s, int lds_pad = 0) {
   if (B < 1) throw Error(RVCX_E_INVALID, "hubert: batch < 1");
   int64_t T[8];
   T[0] = n;
@@ -145,6 +146,7 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
     ci.batch = B;
     ci.x_bs = T[i] * HCONV;
     ci.y_bs = T[i + 1] * HCONV;
+    ci.lds_pad = lds_pad;
     run1(c, ci, s);
     std::swap(cur, nxt);
   }
@@ -156,6 +158,7 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
   {
     ConvArgs fp = lin(nxt, HCONV, BL, HCONV, c.W("hb.fp.w"), HD, c.W("hb.fp.b"), hs, HD);
     fp.mask = mask;  // ragged: pad frames become the positional conv's zero padding
+    fp.lds_pad = lds_pad;
     run1(c, fp, s);
   }
   {  // hs + gelu(pos_conv(hs)) (groups as inner batch, sequences as outer batch), then encoder LayerNorm
@@ -177,6 +180,7 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
     p.res_mode = RES_ADD_POST;
     p.batch = B;
     p.x_bs = p.y_bs = p.res_bs = (long long)L * HD;
+    p.lds_pad = lds_pad;
     run1(c, p, s);
     check(layernorm_rows(hs2, nullptr, hs, c.W("hb.enc.ln.g"), c.W("hb.enc.ln.b"), BL, HD, 1e-5f, nullptr, s),
           "enc_ln");
@@ -187,12 +191,13 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
   r.version = version;
   r.feats = feats;
   r.mask = mask;
+  r.lds_pad = lds_pad;
   return r;
 }
 
 HubertRun hubert_front(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
-                       int64_t cap, hipStream_t s) {
-  return front(c, audio, n, nullptr, lda, B, version, feats, cap, s);
+                       int64_t cap, hipStream_t s, int lds_pad) {
+  return front(c, audio, n, nullptr, lda, B, version, feats, cap, s, lds_pad);
 }
 
 // encoder layers [l0, l1) on the hidden states the front end left in "hb.hs" (modeling_hubert.py
@@ -209,7 +214,11 @@ void hubert_layers(Ctx& c, const HubertRun& run, int l0, int l1, hipStream_t s) 
   const int hd = HD / HHEADS;
   for (int i = l0; i < l1; ++i) {
     const std::string q = "hb." + std::to_string(i);
-    run1(c, lin(hs, HD, BL, HD, c.W(q + ".qkv.w"), 3 * HD, c.W(q + ".qkv.b"), qkv, 3 * HD), s);
+    {
+      ConvArgs a1 = lin(hs, HD, BL, HD, c.W(q + ".qkv.w"), 3 * HD, c.W(q + ".qkv.b"), qkv, 3 * HD);
+      a1.lds_pad = run.lds_pad;
+      run1(c, a1, s);
+    }
     // softmax((q * hd^-0.5) k^T) v per head in one pass (flash_attn.hip): no [B][12][L][L] scores. Ragged batches
     // (run.mask): a pad key's score is -1e4, which is exp(-1e4 - max) == 0 in fp32 beside any valid key's (the scores
     // of LayerNormed rows are far inside +-9e3), so it adds exactly 0 to a valid query's sums
@@ -223,11 +232,13 @@ void hubert_layers(Ctx& c, const HubertRun& run, int l0, int l1, hipStream_t s) 
       a3.ldr = HD;
       a3.ln_g = c.W(q + ".ln1.g");
       a3.ln_b = c.W(q + ".ln1.b");
+      a3.lds_pad = run.lds_pad;
       run1(c, a3, s);
     }
     {
       ConvArgs f1 = lin(hs, HD, BL, HD, c.W(q + ".ff1.w"), HFF, c.W(q + ".ff1.b"), ff, HFF);
       f1.act = ACT_GELU;
+      f1.lds_pad = run.lds_pad;
       run1(c, f1, s);
       // v2's output is the last layer's LN itself: written straight into the caller's buffer (no tail copy)
       float* dst = (run.version != 1 && i == HUBERT_LAYERS - 1) ? run.feats : hs;
@@ -237,6 +248,7 @@ void hubert_layers(Ctx& c, const HubertRun& run, int l0, int l1, hipStream_t s) 
       f2.ldr = HD;
       f2.ln_g = c.W(q + ".ln2.g");
       f2.ln_b = c.W(q + ".ln2.b");
+      f2.lds_pad = run.lds_pad;
       run1(c, f2, s);
     }
   }
@@ -250,7 +262,9 @@ int64_t hubert_tail(Ctx& c, const HubertRun& run, hipStream_t s) {
   float* feats = run.feats;
   if (version == 1) {
     if (!c.dev.count("hb.final_proj.w")) throw Error(RVCX_E_STATE, "hubert: v1 needs final_proj weights");
-    run1(c, lin(hs, HD, BL, HD, c.W("hb.final_proj.w"), 256, c.W("hb.final_proj.b"), feats, 256), s);
+    ConvArgs fp = lin(hs, HD, BL, HD, c.W("hb.final_proj.w"), 256, c.W("hb.final_proj.b"), feats, 256);
+    fp.lds_pad = run.lds_pad;
+    run1(c, fp, s);
   }  // v2: the last layer wrote feats (hubert_layers)
   (void)outD;
   return run.L;
@@ -272,7 +286,7 @@ int64_t hubert_forward(Ctx& c, const float* audio, int64_t n, int version, float
 // feats + b*ld_rows*outD, one launch set for all rows. Returns the longest sequence's row count; rows_out[b] = L_b.
 // The rows of a sequence past L_b (up to the longest's) are written and hold no meaning.
 int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
-                         int64_t ld_rows, int64_t* rows_out, hipStream_t s) {
+                         int64_t ld_rows, int64_t* rows_out, hipStream_t s, bool force_ragged) {
   if (B < 1) throw Error(RVCX_E_INVALID, "hubert: batch < 1");
   int64_t n_max = 0;
   bool equal = true;
@@ -286,8 +300,8 @@ int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t 
   const int outD = version == 1 ? 256 : HD;
   // the layers write [B][L][outD] back to back: straight into the caller's rows when their stride is L
   float* dst = (ld_rows == L || B == 1) ? feats : c.buf<float>("hb.featv", (size_t)B * L * outD, s);
-  // equal lengths need no masks: the equal-length form, bit for bit (rvcx_workspace_bytes sizes the ragged form)
-  const HubertRun r = front(c, audio, n_max, equal && !c.sizing_plan ? nullptr : nv, lda, B, version, dst, L, s);
+  // equal lengths need no masks: the equal-length form, bit for bit
+  const HubertRun r = front(c, audio, n_max, equal && !force_ragged ? nullptr : nv, lda, B, version, dst, L, s);
   hubert_layers(c, r, 0, HUBERT_LAYERS, s);
   hubert_tail(c, r, s);
   if (dst != feats)
@@ -481,9 +495,11 @@ void finalize_rmvpe(Ctx& c) {
 // the buffer and its zeroing, one tag counter per 16-sequence slice, and the launches. tag_start < 0: the counters run
 // on from the earlier launches on this buffer (RMVPE); tag_start >= 0 (rvcx_gru_bidir, the tests): the buffer is
 // zeroed and every slice's counter set to it first, so no granule left by an earlier launch can carry a tag this one
-// waits for. Tv (device, optional): sequence b runs Tv[b] <= T steps in rows of stride T. Work the caller registered to go out beside the BiGRU (Ctx::before_gru) is issued from here.
+// waits for. Tv (device, optional): sequence b runs Tv[b] <= T steps in rows of stride T. beside_gru (optional): work
+// the caller wants to go out beside the BiGRU, issued from here.
 void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
-                   const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv) {
+                   const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv,
+                   const GruHook& beside_gru) {
   unsigned long long* xchg = c.buf<unsigned long long>("rm.xchg", gru_xchg_words(B), s);
   // a new (or regrown) allocation holds garbage tags: zeroed once, and the tag counters of its slices restart
   if (c.zero_once("rm.xchg", xchg, sizeof(unsigned long long) * gru_xchg_words(B), (long long)B, s))
@@ -496,15 +512,13 @@ void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, co
   // work the caller wants issued beside the BiGRU (which occupies 4 CUs): the gate event marks this point of the
   // stream, the BiGRU goes out first and the hook's (many) launches after it, so the host time spent issuing
   // them overlaps the BiGRU instead of delaying its launch
-  std::function<void(hipStream_t)> hook = std::move(c.before_gru);
-  c.before_gru = nullptr;
-  if (hook && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, s));
+  if (beside_gru && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, s));
   for (int g0 = 0; g0 < B; g0 += 16)  // at most 16 sequences per launch (16 x 4 working workgroups co-resident)
     check(gru_bidir(gi + (size_t)g0 * T * 6 * GRU_H, whh_f, bhh_f, whh_b, bhh_b, T, out + (size_t)g0 * T * 2 * GRU_H,
                     xchg + gru_xchg_words(g0), status, &c.gru_tags[xchg + gru_xchg_words(g0)], s, std::min(16, B - g0),
                     Tv ? Tv + g0 : nullptr),
           "gru");
-  if (hook) hook(s);
+  if (beside_gru) beside_gru(s);
 }
 
 // E2E on B mel chunk images [B][Fc][128] (already padded to a multiple of 32 frames) -> sal [B][Fc][360].
@@ -515,8 +529,9 @@ void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, co
 // own height on (ConvArgs::h_in), which is the zero padding a pass on that image alone has there, and the BiGRU runs
 // each sequence over its own frames; pooling, the 1x1 shortcuts, the layout change and the linears are row-wise. An
 // image's rows past its own height hold no meaning at any stage and no valid row reads them.
-static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int B = 1, const int* hv = nullptr,
-                      int ldh = 0) {
+// beside_gru: GruHook (runtime.h), issued beside this pass's BiGRU.
+static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, const GruHook& beside_gru, int B = 1,
+                      const int* hv = nullptr, int ldh = 0) {
   auto hl = [&](int level) { return hv ? hv + (size_t)level * ldh : nullptr; };
   int H = Fc, W = NMEL;
   // encoder: level outputs go to the second half of the decoder concat buffers
@@ -627,7 +642,7 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
   run1(c, lin(feat, 3 * NMEL, B * Fc, 3 * NMEL, c.W("rm.gru.wih"), 6 * GRU_H, c.W("rm.gru.bih"), gi, 6 * GRU_H), s);
   float* go = c.buf<float>("rm.gruout", (size_t)B * Fc * 2 * GRU_H, s);
   gru_bidir_run(c, gi, B, Fc, c.W("rm.gru.whh_f"), c.W("rm.gru.bhh_f"), c.W("rm.gru.whh_b"), c.W("rm.gru.bhh_b"), go, -1,
-                s, hl(0));
+                s, hl(0), beside_gru);
   ConvArgs f = lin(go, 2 * GRU_H, B * Fc, 2 * GRU_H, c.W("rm.fc.w"), NCLS, c.W("rm.fc.b"), sal, NCLS);
   f.act = ACT_SIGMOID;
   run1(c, f, s);
@@ -635,7 +650,7 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, int
 
 // B equal-length sequences: audio row b at audio + b*lda; f0 row b at f0 + b*F; hidden row b at hidden + b*F*360.
 int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
-                        int64_t cap, float* hidden, hipStream_t s) {
+                        int64_t cap, float* hidden, hipStream_t s, GruHook beside_gru) {
   if (B < 1) throw Error(RVCX_E_INVALID, "rmvpe: batch < 1");
   if (n < NFFT / 2 + 1) throw Error(RVCX_E_SHAPE, "rmvpe: input shorter than 513 samples");
   const int F = (int)(1 + n / HOP);
@@ -655,10 +670,12 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
   check(affine_inplace(img, (long long)B * Fp * NMEL, bn0[0], bn0[1], s), "bn0");
   float* sal = c.buf<float>("rm.sal", (size_t)B * Fp * NCLS, s);
   const int chunk = 32000;
+  // the first E2E pass takes the caller's hook; the later ones get none
+  auto hook_once = [&] { return std::exchange(beside_gru, nullptr); };
   if (Fp <= chunk) {
     for (int b0 = 0; b0 < B; b0 += 64) {  // the BiGRU keeps 4 co-resident workgroups per sequence
       const int nb = std::min(64, B - b0);
-      e2e_chunk(c, img + (size_t)b0 * Fp * NMEL, Fp, sal + (size_t)b0 * Fp * NCLS, s, nb);
+      e2e_chunk(c, img + (size_t)b0 * Fp * NMEL, Fp, sal + (size_t)b0 * Fp * NCLS, s, hook_once(), nb);
     }
   } else {
     // every chunk is an independent E2E pass (RMVPE.py:459-481: the U-Net pads each chunk's edges, the BiGRU
@@ -669,11 +686,11 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
       for (int k0 = 0; k0 < nfull; k0 += 8) {  // <= 8 chunks per pass: ~13 GB of U-Net activations
         const int nb = std::min(8, nfull - k0);
         const size_t r0 = (size_t)b * Fp + (size_t)k0 * chunk;
-        e2e_chunk(c, img + r0 * NMEL, chunk, sal + r0 * NCLS, s, nb);
+        e2e_chunk(c, img + r0 * NMEL, chunk, sal + r0 * NCLS, s, hook_once(), nb);
       }
       if (tail > 0) {
         const size_t r0 = (size_t)b * Fp + (size_t)nfull * chunk;
-        e2e_chunk(c, img + r0 * NMEL, tail, sal + r0 * NCLS, s);
+        e2e_chunk(c, img + r0 * NMEL, tail, sal + r0 * NCLS, s, hook_once());
       }
     }
   }
@@ -686,8 +703,8 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
 }
 
 int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double* f0, int64_t cap, float* hidden,
-                      hipStream_t s) {
-  return rmvpe_forward_b(c, audio, n, n, 1, thred, f0, cap, hidden, s);
+                      hipStream_t s, GruHook beside_gru) {
+  return rmvpe_forward_b(c, audio, n, n, 1, thred, f0, cap, hidden, s, std::move(beside_gru));
 }
 
 // B sequences of nv[b] samples in one launch set: row b has F_b = 1 + nv[b] / 160 frames and runs as an image of
@@ -699,10 +716,11 @@ int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double
 //   - the U-Net and the BiGRU take the rows' heights (e2e_chunk);
 //   - the decode and the salience copy stop at F_b.
 // Rows go through 64 images at a time, as rmvpe_forward_b's. The reference's 32000-frame chunking is not taken in this
-// form: a row that long is refused. Equal lengths are rmvpe_forward_b, bit for bit (rvcx_workspace_bytes sizes the
-// ragged form).
+// form: a row that long is refused. Equal lengths are rmvpe_forward_b, bit for bit, unless force_ragged
+// (rvcx_workspace_bytes sizes the ragged form).
 int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, float thred, double* f0,
-                        int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s) {
+                        int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s,
+                        bool force_ragged) {
   if (B < 1) throw Error(RVCX_E_INVALID, "rmvpe: batch < 1");
   int64_t n_max = 0;
   bool equal = true;
@@ -718,7 +736,7 @@ int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t l
     throw Error(RVCX_E_CAPACITY, "rmvpe: salience needs " + std::to_string(F_max64) + " frames per row");
   if (F_out)
     for (int b = 0; b < B; ++b) F_out[b] = 1 + nv[b] / HOP;
-  if (equal && !c.sizing_plan) {
+  if (equal && !force_ragged) {
     const int64_t F = F_max64;
     const bool f0_tight = ldf == F || B == 1, hid_tight = !hidden || ld_hidden == F || B == 1;
     double* f0b = f0_tight ? f0 : c.buf<double>("rm.f0v", (size_t)B * F, s);
@@ -757,7 +775,8 @@ int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t l
   float* sal = c.buf<float>("rm.sal", (size_t)B * Fp_max * NCLS, s);
   for (int b0 = 0; b0 < B; b0 += 64) {  // the BiGRU keeps 4 co-resident workgroups per sequence
     const int nb = std::min(64, B - b0);
-    e2e_chunk(c, img + (size_t)b0 * Fp_max * NMEL, Fp_max, sal + (size_t)b0 * Fp_max * NCLS, s, nb, dH + b0, B);
+    e2e_chunk(c, img + (size_t)b0 * Fp_max * NMEL, Fp_max, sal + (size_t)b0 * Fp_max * NCLS, s, nullptr, nb, dH + b0,
+              B);
   }
   if (hidden)
     for (int b = 0; b < B; ++b)

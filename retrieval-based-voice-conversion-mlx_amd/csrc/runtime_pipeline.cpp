@@ -172,13 +172,14 @@ int64_t vc_forward(Ctx& c, const float* audio, int64_t n, const int32_t* pitch, 
   int32_t* lens = c.buf<int32_t>("vc.len", 4, s);
   set_i32_once(c, "vc.len.T", lens, T, s);
   set_i32_once(c, "vc.len.sid", lens + 1, sid, s);
-  {
-    ScopedFullLengths full(c);
-    DecWindow win;
-    if (trim > 0 && c.use_dec_window()) win = {trim, (long long)T * upp - trim};
-    synth_forward(c, 1, T, phone, lens, pitch, pitchf, lens + 1, eps_z, eps_src, seed, out, nullptr, nullptr, s, 0, 0,
-                  nullptr, nullptr, win);
-  }
+  SynthCall syn;
+  syn.B = 1, syn.T = T;
+  syn.phone = phone, syn.lengths = lens, syn.pitch = pitch, syn.pitchf = pitchf, syn.sid = lens + 1;
+  syn.eps_z = eps_z, syn.eps_src = eps_src, syn.seed = seed;
+  syn.out = out;
+  syn.full_lengths = true;
+  if (trim > 0) syn.win = {trim, (long long)T * upp - trim};
+  synth_forward(c, syn, s);
   return (int64_t)T * upp;
 }
 
@@ -284,7 +285,7 @@ static void pitch_from_f0(Ctx& c, const rvcx_pipeline_opts& o, double* f0, int B
 
 int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_pipeline_opts& opts,
                             const float* eps_z, const float* eps_src, uint64_t seed, float* out, int64_t cap,
-                            double* f0_out, hipStream_t s) {
+                            double* f0_out, hipStream_t s, bool sizing) {
   check_pipeline_opts(c, opts, n);
   rvcx_pipeline_opts o = opts;
   if (o.f0_method == 4) o.f0_method = 0;  // one utterance: the ragged RMVPE pass is the single-row one
@@ -307,7 +308,7 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
     long long* dts = c.buf<long long>("pl.ts", (size_t)std::max(1, nts), s);
     check(split_points(filtered, n, (int)W, o.t_center, o.t_query, sum, dts, nts, s), "split_points");
     opt_ts.resize(nts);
-    if (nts > 0 && c.sizing_plan) {
+    if (nts > 0 && sizing) {
       // rvcx_workspace_bytes: the plan whose longest chunk is the longest any audio can give (each split point lies
       // in [k t_center - t_query, k t_center + t_query]): a middle chunk from the lowest split to the highest next one
       // (or, with one split, the first chunk up to its highest split); the rest centred
@@ -369,40 +370,47 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
   });
   // HuBERT's feature encoder (and the layers before the gate) on the aux stream beside the U-Net. Measured and removed:
   // issuing it from a later U-Net level on (neutral) and on a CU-masked stream of 64 / 128 CUs (+3.6 ms)
-  {
-    struct FrontScope {  // the throttle ends with the front end's issue, also when an exception ends it
-      Ctx& c;
-      ~FrontScope() { c.aux_front = false; }
-    } front_scope{c};
-    c.aux_front = ax != s;
-    for (size_t i : order) {
-      const int64_t len = chunks[i].a1 - chunks[i].a0;
-      const int64_t cap_rows = len / 320 + 8;
-      cfeats[i] = c.buf<float>("pl.hb" + std::to_string(i), (size_t)cap_rows * E, ax);
-      hruns[i] = hubert_front(c, pad32 + chunks[i].a0, len, len, 1, hubert_version_for(c), cfeats[i], cap_rows, ax);
-      if (chunks.size() == 1) {
-        hubert_layers(c, hruns[i], 0, split, ax);
-      } else {  // several chunks share the HuBERT workspace: each runs to completion before the next
-        hubert_layers(c, hruns[i], 0, HUBERT_LAYERS, ax);
-        cL[i] = hubert_tail(c, hruns[i], ax);
-      }
+  // Its contractions (issued with ~1.5 ms of slack before the BiGRU) take 64 KB more LDS per workgroup there
+  // (HubertRun::lds_pad): one or two of them per CU at most, so the U-Net's latency-bound chain finds free workgroup
+  // slots instead of waiting out ~50 us feature-conv workgroups. Same-box A/B (ms/step): r05ac none 13.53 / 13.47,
+  // 64 KB 13.28 / 13.35, 88 KB 13.25 / 13.27, 40 KB 13.39 / 13.51; r05ae none 13.53 / 13.54 / 13.48 / 13.51, 64 KB
+  // 13.39 / 13.16 / 13.37 / 13.33, 88 KB 13.48 / 13.29. Throttling HuBERT's transformer beside the BiGRU too (r05aa)
+  // costs +0.3-0.5 ms: it runs with little slack, so the gated remainder below goes out without the pad.
+  // RVCX_AUX_LDS=KB overrides (0: off)
+  static const int aux_lds = [] {
+    const char* e = rvcx_knob("RVCX_AUX_LDS");
+    return (e ? std::max(0, std::atoi(e)) : 64) * 1024;
+  }();
+  const int front_pad = ax != s ? aux_lds : 0;
+  for (size_t i : order) {
+    const int64_t len = chunks[i].a1 - chunks[i].a0;
+    const int64_t cap_rows = len / 320 + 8;
+    cfeats[i] = c.buf<float>("pl.hb" + std::to_string(i), (size_t)cap_rows * E, ax);
+    hruns[i] = hubert_front(c, pad32 + chunks[i].a0, len, len, 1, hubert_version_for(c), cfeats[i], cap_rows, ax,
+                            front_pad);
+    if (chunks.size() == 1) {
+      hubert_layers(c, hruns[i], 0, split, ax);
+    } else {  // several chunks share the HuBERT workspace: each runs to completion before the next
+      hubert_layers(c, hruns[i], 0, HUBERT_LAYERS, ax);
+      cL[i] = hubert_tail(c, hruns[i], ax);
     }
   }
-  // the caller records c.ev_gate on `main` where the rest may start (gate_here), then calls this
-  auto gate_here = [&](hipStream_t main) {
-    if (ax != main && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, main));
-  };
+  // The rest of HuBERT (one chunk: the layers from the gate on and the tail), issued once: by RMVPE beside its first
+  // BiGRU launch, which records c.ev_gate on `main` where the rest may start, or by issue_rest below
+  bool rest_issued = false;
   auto hubert_rest = [&](hipStream_t main) {
+    rest_issued = true;
     if (chunks.size() != 1) return;
     if (split < HUBERT_LAYERS && ax != main) RVCX_HIP(hipStreamWaitEvent(ax, c.ev_gate, 0));
+    hruns[0].lds_pad = 0;
     hubert_layers(c, hruns[0], split, HUBERT_LAYERS, ax);
     cL[0] = hubert_tail(c, hruns[0], ax);
   };
-  struct HookScope {
-    Ctx& c;
-    ~HookScope() { c.before_gru = nullptr; }
-  } hook_scope{c};
-  c.before_gru = hubert_rest;
+  auto issue_rest = [&] {  // where no BiGRU launch took it: gated here on s
+    if (rest_issued) return;
+    if (ax != s && c.ev_gate) RVCX_HIP(hipEventRecord(c.ev_gate, s));
+    hubert_rest(s);
+  };
   // 5. f0 over the whole padded input (pipeline.py:462-472) + get_f0 adjustments (:248-291)
   const int64_t F = 1 + m / W;
   int32_t* pitch = nullptr;
@@ -412,30 +420,17 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
   if (o.f0_method >= 1) {
     // CREPE / FCPE over the whole padded input: no BiGRU, so HuBERT's remaining layers go out first and overlap the
     // pitch network's convs on the aux stream
-    if (c.before_gru) {
-      auto rest = std::move(c.before_gru);
-      c.before_gru = nullptr;
-      gate_here(s);
-      rest(s);
-    }
+    issue_rest();
     f0_row(c, o, pad32, m, f0, F, "pl.f0f", s);
   } else {
-    rmvpe_forward(c, pad32, m, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, nullptr, s);
+    rmvpe_forward(c, pad32, m, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, nullptr, s, hubert_rest);
   }
-  if (c.before_gru) {  // RMVPE did not reach a BiGRU launch (cannot happen for valid input): issue it now
-    auto rest = std::move(c.before_gru);
-    c.before_gru = nullptr;
-    gate_here(s);
-    rest(s);
-  }
+  issue_rest();  // RMVPE did not reach a BiGRU launch (cannot happen for valid input): issue it now
   pitch = c.buf<int32_t>("pl.pitch", (size_t)F, s);
   pitchf = c.buf<float>("pl.pitchf", (size_t)F, s);
   pitch_from_f0(c, o, f0, 1, &F, F, pitch, pitchf, f0_out, F, s);
   } else {
-    auto rest = std::move(c.before_gru);
-    c.before_gru = nullptr;
-    gate_here(s);
-    rest(s);
+    issue_rest();
     if (f0_out) RVCX_HIP(hipMemsetAsync(f0_out, 0, sizeof(double) * (size_t)F, s));
   }
   join_aux(c, s, ax);
@@ -481,7 +476,7 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
                                    pitchf ? pitchf + ch.f_lo : nullptr, ch.f_hi - ch.f_lo, o.sid,
                                    o.protect, o.index_rate, eps_z ? eps_z + ez_off[i] : nullptr,
                                    eps_src ? eps_src + es_off[i] : nullptr, cseed[i], vc, cap_vc, s, cfeats[i], cL[i],
-                                   o.t_pad_tgt);
+                                   c.dec_window && !sizing ? o.t_pad_tgt : 0);
     const int64_t keep = nvc - 2 * o.t_pad_tgt;
     if (keep <= 0) throw Error(RVCX_E_SHAPE, "pipeline: chunk too short for the padding");
     if (nch == 1) {
@@ -527,7 +522,7 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
 void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
                            const rvcx_pipeline_opts& opts, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
-                           float* hidden_out, hipStream_t s) {
+                           float* hidden_out, hipStream_t s, bool sizing) {
   if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
   int64_t n_max = 0;
   bool equal = true;
@@ -543,7 +538,7 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   // f0_method 4: all rows in one ragged RMVPE pass; equal lengths (outside the arena query, which sizes the ragged
   // pass) and one row are method 0
   rvcx_pipeline_opts o = opts;
-  const bool ragged_f0 = o.f0_method == 4 && B > 1 && (!equal || c.sizing_plan);
+  const bool ragged_f0 = o.f0_method == 4 && B > 1 && (!equal || sizing);
   if (o.f0_method == 4) o.f0_method = 0;
   const int E = c.scfg.emb_dim, upp = c.scfg.upp();
   if (!equal && o.t_pad_tgt < (int64_t)dec_margin_frames(c.scfg) * upp)
@@ -556,7 +551,7 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
     throw Error(RVCX_E_INVALID, "pipeline_batch: the salience needs equal lengths, RMVPE and a pitch-guided model");
   if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension mismatch");
   // rvcx_workspace_bytes sizes the ragged form: masks, the gathered RMVPE group and one single-row RMVPE forward
-  const bool plain = equal && !c.sizing_plan;
+  const bool plain = equal && !sizing;
   const int64_t W = 160;
   const int64_t m_max = n_max + 2 * o.t_pad;
   const int64_t ldm = (m_max + 7) & ~int64_t(7);
@@ -604,7 +599,7 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   double* f0 = c.buf<double>("pb.f0", (size_t)B * F_max, s);
   float* feats = c.buf<float>("pb.feats", (size_t)B * L_max * E, s);
   hipStream_t ax = fork_aux(c, s);
-  hubert_forward_v(c, pad32, mv.data(), ldm, B, hubert_version_for(c), feats, L_max, nullptr, ax);
+  hubert_forward_v(c, pad32, mv.data(), ldm, B, hubert_version_for(c), feats, L_max, nullptr, ax, sizing);
   int32_t* pitch = nullptr;
   float* pitchf = nullptr;
   if (guided) {
@@ -613,7 +608,7 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
         f0_row(c, o, pad32 + (size_t)b * ldm, mv[b], f0 + (size_t)b * F_max, Fv[b], "pb.f0f", s);
     } else if (ragged_f0) {
       rmvpe_forward_v(c, pad32, mv.data(), ldm, B, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F_max, nullptr,
-                      nullptr, 0, s);
+                      nullptr, 0, s, sizing);
     } else {
       const float thr = o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f;
       // rows of equal length together; the groups largest first (rows x frames), so the work buffers a group shares
@@ -625,7 +620,7 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
           if (mv[g[0]] == mv[b]) g.push_back(b), placed = true;
         if (!placed) groups.push_back({b});
       }
-      if (c.sizing_plan) groups.push_back({0});
+      if (sizing) groups.push_back({0});
       std::stable_sort(groups.begin(), groups.end(), [&](const std::vector<int>& x, const std::vector<int>& y) {
         return (int64_t)x.size() * Fv[x[0]] > (int64_t)y.size() * Fv[y[0]];
       });
@@ -677,13 +672,14 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   //    samples the trim below keeps
   const int64_t nvc = Tv_max * upp;
   float* vc = c.buf<float>("pb.vc", (size_t)B * nvc, s);
-  {
-    ScopedFullLengths full(c, plain);
-    DecWindow win;
-    if (o.t_pad_tgt > 0 && c.use_dec_window()) win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
-    synth_forward(c, B, (int)Tv_max, phone, dTv, pc, pf, dsid, eps_z, eps_src, seed, vc, nullptr, nullptr, s, 0, 0,
-                  nullptr, nullptr, win);
-  }
+  SynthCall syn;
+  syn.B = B, syn.T = (int)Tv_max;
+  syn.phone = phone, syn.lengths = dTv, syn.pitch = pc, syn.pitchf = pf, syn.sid = dsid;
+  syn.eps_z = eps_z, syn.eps_src = eps_src, syn.seed = seed;
+  syn.out = vc;
+  syn.full_lengths = plain;
+  if (o.t_pad_tgt > 0 && c.dec_window && !sizing) syn.win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
+  synth_forward(c, syn, s);
   // 5. trim, volume envelope, peak normalisation of every row in one launch set each (pipeline.py:545-552)
   float* mx = c.buf<float>("pb.max", peak_normalize_ws_floats(B), s);
   if (o.volume_envelope == 1.0) {  // trim + normalise in one pass over all rows
@@ -709,14 +705,13 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
   const std::vector<int64_t> nv((size_t)B, n);
   std::vector<int64_t> n_out((size_t)B);
   pipeline_forward_rows(c, audio, nv.data(), lda, B, o, sids, eps_z, eps_src, seed, out, ldo, n_out.data(), f0_out,
-                        1 + (n + 2 * o.t_pad) / 160, hidden_out, s);
+                        1 + (n + 2 * o.t_pad) / 160, hidden_out, s, false);
   return n_out[0];
 }
 
 namespace {
 // rvcx_workspace_bytes plans from an empty, internally allocated pool: the caller's arena is detached for the scope and
-// attached again after (its regions are carved anew by the next call), the pool the plan took is dropped, and
-// Ctx::sizing_plan is set for the scope
+// attached again after (its regions are carved anew by the next call), and the pool the plan took is dropped
 struct SizingScope {
   Ctx& c;
   char* const arena;
@@ -725,20 +720,19 @@ struct SizingScope {
     c.release_pool();
     c.arena = nullptr;
     c.arena_bytes = 0;
-    c.sizing_plan = true;
   }
   ~SizingScope() {
     (void)hipDeviceSynchronize();  // release_pool without its throw: every measurement has synchronised its stream
     c.drop_pool();
     c.arena = arena;
     c.arena_bytes = arena_bytes;
-    c.sizing_plan = false;
   }
 };
 }  // namespace
 
 int64_t pipeline_workspace_bytes(Ctx& c, int B, int64_t n, const rvcx_pipeline_opts& opts, hipStream_t s) {
-  // the call itself on zero audio; the buffers outlive the scope, which synchronises the device before they are freed
+  // the call itself on zero audio, in its sizing form; the buffers outlive the scope, which synchronises the device
+  // before they are freed
   DevBuf audio, out;
   SizingScope scope(c);
   const int64_t m = n + 2 * opts.t_pad;
@@ -749,14 +743,14 @@ int64_t pipeline_workspace_bytes(Ctx& c, int B, int64_t n, const rvcx_pipeline_o
   auto measure = [&](const rvcx_pipeline_opts& o) {
     if (B == 1) {
       pipeline_forward_ex(c, static_cast<const double*>(audio.p), n, o, nullptr, nullptr, 0, static_cast<float*>(out.p),
-                          cap, nullptr, s);
+                          cap, nullptr, s, true);
     } else {
-      // B rows of n samples in the batched pipeline's sizing form (Ctx::sizing_plan): run as a ragged batch (masks,
+      // B rows of n samples in the batched pipeline's sizing form: run as a ragged batch (masks,
       // the gathered RMVPE group and one single-row RMVPE forward), whose regions hold the equal-length routes too
       std::vector<int32_t> sids((size_t)B, o.sid);
       std::vector<int64_t> nv((size_t)B, n), no((size_t)B);
       pipeline_forward_rows(c, static_cast<const double*>(audio.p), nv.data(), n, B, o, sids.data(), nullptr, nullptr, 0,
-                            static_cast<float*>(out.p), cap, no.data(), nullptr, 0, nullptr, s);
+                            static_cast<float*>(out.p), cap, no.data(), nullptr, 0, nullptr, s, true);
     }
     RVCX_HIP(hipStreamSynchronize(s));
     int64_t carved = (int64_t)c.carved;

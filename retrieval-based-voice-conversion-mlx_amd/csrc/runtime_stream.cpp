@@ -505,15 +505,20 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   const int64_t n_need = std::min<int64_t>(n_model, (int64_t)s.sola48 + s.block48 + s.cross48);
   int64_t n_clip = n_model;
   {
-    ScopedFullLengths full(c);  // every stream's hop is T frames (meta above)
+    SynthCall syn;
+    syn.B = Ba, syn.T = T;
+    syn.phone = phone, syn.lengths = dmeta, syn.sid = dmeta + B;
+    if (guided) syn.pitch = pitch, syn.pitchf = pitchf;
+    syn.eps_z = eps_z, syn.eps_src = eps_src, syn.seed = seed;
+    syn.out = model;
+    syn.gen_lowp = gen_precision;
+    syn.full_lengths = true;  // every stream's hop is T frames (meta above)
     // k_rt_sola reads a[off + j], off <= sola48, j < block48 + cross48: the only reader of the model's output where
     // it is neither resampled nor RMS-adjusted nor gated (the gate's statistics run over the whole row), so the
     // generator runs on that window alone
-    DecWindow win;
-    if (s.out_identity && !any_rms && !any_clean && c.use_dec_window()) win = {0, n_need};
-    synth_forward(c, Ba, T, phone, dmeta, guided ? pitch : nullptr, guided ? pitchf : nullptr, dmeta + B, eps_z,
-                  eps_src, seed, model, nullptr, nullptr, st, gen_precision, 0, nullptr, nullptr, win);
-    if (win.s1 >= 0) n_clip = n_need;
+    if (s.out_identity && !any_rms && !any_clean && c.dec_window) syn.win = {0, n_need};
+    synth_forward(c, syn, st);
+    if (syn.win.s1 >= 0) n_clip = n_need;
   }
   check(rt_clip(model, n_model, (int)n_clip, Ba, st), "rt_clip");
   if (any_rms) {  // pipeline.py:299-307 (source = the 16 kHz convert buffer); rows at exactly 1 are skipped

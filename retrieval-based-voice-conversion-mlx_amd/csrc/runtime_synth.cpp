@@ -360,18 +360,18 @@ void dec_window_frames(const SynthCfg& cf, int T, const DecWindow& win, int& fa,
 // alone, and conv_post writes the samples at their usual place in out. Every launch is planned for the full stage
 // length (ConvArgs::plan_T), so each sample of the window gets the arithmetic of the full-length run, bit for bit;
 // the samples within the margin of a cut edge see zero padding where the full run sees neighbours and are unspecified.
-void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, const float* f0, const float* g,
-                 const float* eps_src, uint64_t seed, float* out, hipStream_t s, int gen_lowp, bool noise_pre,
-                 const DecWindow& win) {
+void dec_forward(Ctx& c, const DecCall& call, hipStream_t s) {
+  const int B = call.B, T = call.T, gen_lowp = call.gen_lowp;
+  const bool noise_pre = call.noise_pre;
   const SynthCfg& cf = c.scfg;
   if (cf.f0 && cf.vocoder == 2) {
-    refinegan_forward(c, B, T, z_btc, mask, f0, g, eps_src, seed, out, s);
+    refinegan_forward(c, B, T, call.z_btc, call.mask, call.f0, call.g, call.eps_src, call.seed, call.out, s);
     return;
   }
   const int I = cf.I, C0 = cf.C0;
   const long long har_ld = (long long)T * cf.upp() + 2 * HAR_PAD;
   int fa, fb;
-  dec_window_frames(cf, T, win, fa, fb);
+  dec_window_frames(cf, T, call.win, fa, fb);
   const int Tc = fb - fa;                             // frames the generator runs on
   const long long har_off = (long long)fa * cf.upp();  // the window's first sample in the source rows and in out
   float* har = nullptr;
@@ -379,12 +379,12 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     if (noise_pre) {
       har = c.buf<float>("dec.har", (size_t)(B * har_ld), s);  // written by dec_noise_prepare
     } else {
-      har = dec_source(c, B, T, f0, eps_src, seed, s);
+      har = dec_source(c, B, T, call.f0, call.eps_src, call.seed, s);
     }
   }
   // conv_pre + cond(g)
   float* cv = c.buf<float>("dec.cvec", (size_t)B * C0, s);
-  run1(c, lin(g, cf.gin, B, cf.gin, c.W("dec.cond.w"), C0, c.W("dec.cond.b"), cv, C0), s);
+  run1(c, lin(call.g, cf.gin, B, cf.gin, c.W("dec.cond.w"), C0, c.W("dec.cond.b"), cv, C0), s);
   // stage buffers sized for the largest stage
   size_t maxe = (size_t)Tc * C0;
   {
@@ -400,10 +400,10 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
   float* t1 = c.buf<float>("dec.t", (size_t)B * maxe, s);
   {
     ConvArgs a =
-        conv1d(z_btc + (size_t)fa * I, I, Tc, I, c.W("dec.pre.w"), C0, 7, 1, 3, c.W("dec.pre.b"), xin, C0, Tc, B);
+        conv1d(call.z_btc + (size_t)fa * I, I, Tc, I, c.W("dec.pre.w"), C0, 7, 1, 3, c.W("dec.pre.b"), xin, C0, Tc, B);
     a.x_bs = (long long)T * I;
     a.plan_T = T;
-    a.pre_mask = mask + fa;
+    a.pre_mask = call.mask + fa;
     a.pre_mask_bs = T;
     a.res = cv;
     a.ldr = 0;
@@ -565,33 +565,32 @@ void dec_forward(Ctx& c, int B, int T, const float* z_btc, const float* mask, co
     off = offi;
   }
   // LeakyReLU(0.01) -> conv_post (no bias) -> tanh
-  check(conv_post_tanh(cur, B, curT, Cin, c.W("dec.post.w"), 7, 0.01f, out + har_off, s,
+  check(conv_post_tanh(cur, B, curT, Cin, c.W("dec.post.w"), 7, 0.01f, call.out + har_off, s,
                        c.host[0].at("__post_b__").v[0], fullT),
         "conv_post");
 }
 
 // ------------------------------------------------------------------ Synthesizer.infer
-void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* lengths, const int32_t* pitch,
-                   const float* pitchf, const int32_t* sid, const float* eps_z, const float* eps_src, uint64_t seed,
-                   float* out, float* zp_out, float* z_out, hipStream_t s, int gen_lowp, int head, float* mp_out,
-                   float* logsp_out, const DecWindow& win) {
+void synth_forward(Ctx& c, const SynthCall& call, hipStream_t s) {
+  const int B = call.B, T = call.T, head = call.head;
+  const uint64_t seed = call.seed;
   const SynthCfg& cf = c.scfg;
   const int H = cf.H, I = cf.I, F = cf.F, E = cf.emb_dim, nh = cf.n_heads, dk = H / nh;
   const long long BT = (long long)B * T;
   float* mask = c.buf<float>("te.mask", BT, s);
-  check(seq_mask(lengths, mask, B, T, s), "seq_mask");
+  check(seq_mask(call.lengths, mask, B, T, s), "seq_mask");
   float* g = c.buf<float>("spk.g", (size_t)B * cf.gin, s);
-  check(gather_rows(c.W("emb_g"), cf.gin, sid, g, B, cf.gin, s), "emb_g");
+  check(gather_rows(c.W("emb_g"), cf.gin, call.sid, g, B, cf.gin, s), "emb_g");
   // ---- TextEncoder (encoders.py:128-144)
   // x = emb_phone(phone) [+ emb_pitch(pitch) when pitch-guided, encoders.py:131-133]
   float* pe = nullptr;
   if (cf.f0) {
     pe = c.buf<float>("te.pe", BT * H, s);
-    check(gather_rows(c.W("te.emb_pitch"), H, pitch, pe, (int)BT, H, s), "emb_pitch");
+    check(gather_rows(c.W("te.emb_pitch"), H, call.pitch, pe, (int)BT, H, s), "emb_pitch");
   }
   float* x = c.buf<float>("te.x", BT * H, s);
   {
-    ConvArgs a = lin(phone, E, (int)BT, E, c.W("te.emb_phone.w"), H, c.W("te.emb_phone.b"), x, H);
+    ConvArgs a = lin(call.phone, E, (int)BT, E, c.W("te.emb_phone.w"), H, c.W("te.emb_phone.b"), x, H);
     a.res = pe;
     a.ldr = H;
     a.res_mode = pe ? RES_ADD_PRE : RES_NONE;
@@ -615,7 +614,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     // where a row is shorter than T: with every length T it is all ones, and its per-element loads in the key loop
     // cost the TextEncoder's attention ~1/3 of its time (the fill never fires: identical results)
     check(flash_attn(qkv, 3 * H, B, T, nh, dk, qscale, c.W(q + ".rel_k"), c.W(q + ".rel_v"), cf.window,
-                     c.synth_full_lengths ? nullptr : mask, part_o, part_ml, nsplit, att, H, s),
+                     call.full_lengths ? nullptr : mask, part_o, part_ml, nsplit, att, H, s),
           "flash_attn");
     {  // x = LN(x + conv_o(att)) (norm_layers_1, attentions.py:57-62) in the split-K combine, in place (one combine
        // block per row reads the row's residual before writing it): one launch instead of the GEMM + a LayerNorm pass
@@ -656,21 +655,21 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     run1(c, a, s);
   }
   // m_p / logs_p [B][T][I] for the caller (the return tuple of Synthesizer.infer, synthesizers.py:243)
-  if (mp_out)
-    RVCX_HIP(hipMemcpy2DAsync(mp_out, (size_t)I * 4, stats, (size_t)2 * I * 4, (size_t)I * 4, (size_t)BT,
+  if (call.mp_out)
+    RVCX_HIP(hipMemcpy2DAsync(call.mp_out, (size_t)I * 4, stats, (size_t)2 * I * 4, (size_t)I * 4, (size_t)BT,
                               hipMemcpyDeviceToDevice, s));
-  if (logsp_out)
-    RVCX_HIP(hipMemcpy2DAsync(logsp_out, (size_t)I * 4, stats + I, (size_t)2 * I * 4, (size_t)I * 4, (size_t)BT,
+  if (call.logsp_out)
+    RVCX_HIP(hipMemcpy2DAsync(call.logsp_out, (size_t)I * 4, stats + I, (size_t)2 * I * 4, (size_t)I * 4, (size_t)BT,
                               hipMemcpyDeviceToDevice, s));
   // ---- z_p = (m + exp(logs) * eps * 0.66666) * mask   (synthesizers.py:228)
   float* z = c.buf<float>("flow.z", BT * I, s);
   float* xf = c.buf<float>("flow.xf", BT * I, s);
-  check(zp_sample(stats, B, T, I, eps_z, splitmix(seed ^ 0x5a505f4e4f495345ull), mask, z, s), "zp_sample");
+  check(zp_sample(stats, B, T, I, call.eps_z, splitmix(seed ^ 0x5a505f4e4f495345ull), mask, z, s), "zp_sample");
   // rate (synthesizers.py:230-234): z_p, x_mask and nsff0 from frame head on; the noise was drawn over all T frames
   const int Tf = T - head;
   const long long BTf = (long long)B * Tf;
   const float* maskf = mask;
-  const float* pitchff = pitchf;
+  const float* pitchff = call.pitchf;
   if (head > 0) {
     if (head >= T) throw Error(RVCX_E_SHAPE, "synthesizer: rate leaves no frames");
     float* z2 = c.buf<float>("flow.z_rate", (size_t)BTf * I, s);
@@ -679,16 +678,16 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     float* m2 = c.buf<float>("te.mask_rate", (size_t)BTf, s);
     RVCX_HIP(hipMemcpy2DAsync(m2, (size_t)Tf * 4, mask + head, (size_t)T * 4, (size_t)Tf * 4, (size_t)B,
                               hipMemcpyDeviceToDevice, s));
-    if (pitchf) {
+    if (call.pitchf) {
       float* p2 = c.buf<float>("dec.pitchf_rate", (size_t)BTf, s);
-      RVCX_HIP(hipMemcpy2DAsync(p2, (size_t)Tf * 4, pitchf + head, (size_t)T * 4, (size_t)Tf * 4, (size_t)B,
+      RVCX_HIP(hipMemcpy2DAsync(p2, (size_t)Tf * 4, call.pitchf + head, (size_t)T * 4, (size_t)Tf * 4, (size_t)B,
                                 hipMemcpyDeviceToDevice, s));
       pitchff = p2;
     }
     z = z2;
     maskf = m2;
   }
-  if (zp_out) RVCX_HIP(hipMemcpyAsync(zp_out, z, BTf * I * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (call.zp_out) RVCX_HIP(hipMemcpyAsync(call.zp_out, z, BTf * I * sizeof(float), hipMemcpyDeviceToDevice, s));
   // the decoder's NSF source and multi-tap noise convs depend on f0 alone: issued now on the aux stream, beside the
   // flow's latency-bound chain, instead of between the decoder's ConvTransposes (kernel timing and RVCX_NO_OVERLAP
   // keep them on this stream, fork_aux)
@@ -696,7 +695,7 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
   bool noise_pre = false;
   if (cf.f0 && cf.vocoder != 2 && pitchff) {
     nax = fork_aux(c, s);
-    noise_pre = dec_noise_prepare(c, B, Tf, pitchff, eps_src, seed, nax);
+    noise_pre = dec_noise_prepare(c, B, Tf, pitchff, call.eps_src, seed, nax);
   }
   // ---- flow reverse (residuals.py:151-164, 233-258; modules.py:78-109)
   // hs [BTf][2H]: the WaveNet residual stream h (columns [0, H)) and its skip sum (columns [H, 2H))
@@ -755,10 +754,16 @@ void synth_forward(Ctx& c, int B, int T, const float* phone, const int32_t* leng
     }
     if (!fold) std::swap(z, xf);
   }
-  if (z_out) RVCX_HIP(hipMemcpyAsync(z_out, z, BTf * I * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (call.z_out) RVCX_HIP(hipMemcpyAsync(call.z_out, z, BTf * I * sizeof(float), hipMemcpyDeviceToDevice, s));
   // ---- dec(z * mask, nsff0, g)
   join_aux(c, s, nax);
-  dec_forward(c, B, Tf, z, maskf, pitchff, g, eps_src, seed, out, s, gen_lowp, noise_pre, win);
+  DecCall dec;
+  dec.B = B, dec.T = Tf;
+  dec.z_btc = z, dec.mask = maskf, dec.f0 = pitchff, dec.g = g;
+  dec.eps_src = call.eps_src, dec.seed = seed;
+  dec.out = call.out;
+  dec.gen_lowp = call.gen_lowp, dec.noise_pre = noise_pre, dec.win = call.win;
+  dec_forward(c, dec, s);
 }
 
 }  // namespace rvcx

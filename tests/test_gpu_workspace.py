@@ -49,6 +49,48 @@ def test_workspace_query_and_caller_arena(engine):
     assert torch.equal(engine.pipeline(audio, seed=7).cpu(), ref)
 
 
+def test_failed_calls_leave_the_context_clean(engine):
+    """A pipeline call refused with RVCX_E_OOM part-way through (arenas of 1/16 .. 1/2 of the queried size, so the
+    refusal comes at different stages) leaves nothing behind that a later call could see: a synthesizer call with a
+    short row (its key mask), RMVPE with its salience (the work issued beside its BiGRU) and the pipeline return
+    their bits from before the failures. The buffers the four arenas ran out at on MI355X (the error text names
+    them): hb.a (HuBERT's front end, on the aux stream), conv.splitk.aux (the split-K slab of HuBERT's convs on the aux
+    stream), conv.splitk (the slab of the caller's stream) and dec.nz1 (the generator's noise convs, after HuBERT,
+    RMVPE and the flow)."""
+    from rvcx import synthetic
+    from rvcx._lib import RvcxError
+    from rvcx.config import SYNTH_48K_V2
+
+    engine.set_pipeline_highpass()
+    opts = engine.pipeline_opts(t_pad=4800, t_pad_tgt=14400)
+    audio = _audio(8000)
+    rng = np.random.Generator(np.random.PCG64(31))  # tools/output_digests.py synth_inputs(cfg, 2, 40, 31)
+    phone = rng.standard_normal((2, 40, SYNTH_48K_V2.text_enc_hidden_dim)).astype(np.float32)
+    pitch = rng.integers(1, 256, size=(2, 40)).astype(np.int64)
+    pitchf = synthetic.f0_walk(2, 40, seed=32)
+    speech = synthetic.speech_like(10000, seed=21).astype(np.float32)
+
+    def calls():
+        f0, hidden = engine.rmvpe(speech, want_hidden=True)
+        return [engine.synth_infer(phone, [40, 33], pitch, pitchf, [0, 1], seed=7).cpu(), f0.cpu(), hidden.cpu(),
+                engine.pipeline_ex(audio, opts, seed=3).cpu()]
+
+    ref = calls()
+    need = engine.workspace_bytes(8000, opts=opts)
+    arena = torch.empty(need, dtype=torch.uint8, device=engine.device)
+    for frac in (16, 8, 4, 2):
+        try:
+            engine.set_workspace(arena[: need // frac])
+            with pytest.raises(RvcxError) as ei:
+                engine.pipeline_ex(audio, opts, seed=3)
+            assert ei.value.code == RVCX_E_OOM
+            print(f"need // {frac}: {ei.value}")
+        finally:
+            engine.set_workspace(None)
+        for got, want in zip(calls(), ref):
+            assert torch.equal(got, want)
+
+
 def test_workspace_bytes_grows_with_the_call(engine):
     engine.set_pipeline_highpass()
     # (the reflect pad needs n > t_pad = 1 s)

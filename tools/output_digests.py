@@ -7,7 +7,8 @@ synthesizer with each vocoder, a 6-hop stream group (once more with a volume env
 pipeline forms for f0_method 0 / 2 / 3 under autotune and under proposed pitch and with a volume envelope, the batched
 pipeline's salience, and the ragged forms: HuBERT over rows of five lengths, the pipeline over rows of three lengths
 (plain and with a volume envelope) and over two equal rows, RMVPE over rows of five lengths in one ragged pass and the
-ragged pipeline with it (f0_method 4).
+ragged pipeline with it (f0_method 4). Then, as plain integers, Engine.workspace_bytes of five calls: the arena query
+runs the pipelines in their sizing form.
 
     python tools/output_digests.py > digests.txt
 """
@@ -118,6 +119,13 @@ def main():
         opts = eng.pipeline_opts(pitch=2.0, t_pad=4800, t_pad_tgt=14400, f0_method=4)
         ys, f0s = eng.pipeline_batch_v(ragged, opts, sids=[0, 3, 7, 0], seed=3, want_f0=True)
         show("pipeline_batch_v ragged f0_method=4", *ys, *f0s)
+        ragged_kw = {"t_pad": 4800, "t_pad_tgt": 14400}
+        for B, n, kw in ((1, 24000, {}), (1, 24000, {"f0_method": 3}),
+                         (1, 128000, {"t_max": 48000, "t_center": 32000, "t_query": 8000}),
+                         (4, 40000, ragged_kw), (4, 40000, {**ragged_kw, "f0_method": 4})):
+            tag = "".join(f" {k}={v}" for k, v in kw.items())
+            need = eng.workspace_bytes(n, B=B, opts=eng.pipeline_opts(**kw))
+            print(f"workspace_bytes B={B} n={n}{tag}: {need}", flush=True)
     eng.close()
 
 
