@@ -190,7 +190,7 @@ int rvcx_dec_margin_frames(const rvcx_synth_desc* d, int* frames);
 typedef struct rvcx_conv_plan_form {
   int W_in, W_out, KH, KW, padh, padw; /* 2-D geometry (taps = KH * KW) */
   int out_map, out_cv;                 /* 1: the 2x2-phase ConvTranspose2d scatter with out_cv real channels */
-  int b_kn, lowp;                      /* weights stored [C_in][N]; the reduced-precision opt-in */
+  int lowp;                            /* the reduced-precision opt-in */
   int ldw;                             /* weight row stride, 0 = C_in */
   int64_t w_ts, w_bs, bias_bs;         /* weight tap stride (0 = N * C_in), per-batch weight and bias strides */
 } rvcx_conv_plan_form;

@@ -44,8 +44,9 @@ static void fill_rand(std::vector<float>& v, unsigned seed) {
   for (auto& x : v) x = (float)rand() / RAND_MAX * 2.f - 1.f;
 }
 
-// the config numbers of the command line and the output: -1 the size policy, 0-9 the native fp32 tiles, 10-16 the
-// bf16-split tiles, 20-29 the weight-streamed tiles, 30-39 the gather-streamed ones, 40 the weight-stationary kernel
+// the config numbers of the command line and the output (ConvTile): -1 the size policy, below 10 the native fp32 tiles
+// (1, 3), 10-19 the bf16-split tiles (12, 13), 20-29 the weight-streamed tiles, 30-39 the gather-streamed ones, 40 the
+// weight-stationary kernel; conv_plan refuses a number no family has
 static ConvForce force_of(int cfg, int pipe) {
   if (cfg < 0) return ConvForce{-1, TILE_NONE, pipe};
   const int kind = cfg < 10 ? CK_GEMM : (cfg < 20 ? CK_EMU : (cfg < 30 ? CK_WSB16 : (cfg < 40 ? CK_GS : CK_WST)));
@@ -90,7 +91,7 @@ int main(int argc, char** argv) {
     std::vector<float> ref((size_t)T * N), out((size_t)T * N);
     CK_(hipMemcpy(ref.data(), yr, ref.size() * 4, hipMemcpyDeviceToHost));
     // fmt 1: the two-plane fp16 image (math 3), fmt 2: its reduced-precision hi-plane mode
-    for (int cfg : {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 23, 24, 25, 27})
+    for (int cfg : {1, 3, 12, 13, 23, 24, 25, 27})
       for (int fmt : {0, 1, 2}) {
         if (fmt && cfg != 23 && cfg != 24 && cfg != 25 && cfg != 27) continue;
         if (si > 0 && (cfg != 23 || fmt == 0)) continue;
@@ -218,9 +219,10 @@ int main(int argc, char** argv) {
     // variants: (cfg, math, pipe); cfg -1 = the library's policy for that math
     struct V { int cfg, math, pipe; };
     std::vector<V> vars = {{-1, 2, 0}, {23, 2, -1}, {24, 2, -1}, {27, 2, -1}, {23, 3, -1}, {24, 3, -1}, {40, 3, -1}, {-1, 3, -1},
-                           {27, 3, -1}, {25, 3, -1}, {23, 4, -1}, {27, 4, -1}, {13, 2, -1}, {1, 1, -1}};
+                           {27, 3, -1}, {25, 3, -1}, {23, 4, -1}, {27, 4, -1}, {12, 2, -1}, {13, 2, -1}, {1, 1, -1},
+                           {3, 1, -1}};
     if (cs.taps == 1)
-      for (int c : {10, 12, 13, 14, 15}) vars.push_back({c, 2, 1});
+      for (int c : {12, 13}) vars.push_back({c, 2, 1});
     printf("%-28s", cs.name);
     for (size_t vi = 0; vi < vars.size(); ++vi) {
       const V& vv = vars[vi];

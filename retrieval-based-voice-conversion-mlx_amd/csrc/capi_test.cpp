@@ -63,7 +63,7 @@ int rvcx_conv_plan(const rvcx_conv_test_desc* d, const rvcx_conv_plan_form* f, i
   a.plan_T = plan_T;
   if (f) {
     a.W_in = f->W_in; a.W_out = f->W_out; a.KH = f->KH; a.KW = f->KW; a.padh = f->padh; a.padw = f->padw;
-    a.out_map = f->out_map; a.out_cv = f->out_cv; a.b_kn = f->b_kn; a.lowp = f->lowp;
+    a.out_map = f->out_map; a.out_cv = f->out_cv; a.lowp = f->lowp;
     if (f->ldw > 0) a.ldw = f->ldw;
     if (f->w_ts > 0) a.w_ts = f->w_ts;
     a.w_bs = f->w_bs; a.bias_bs = f->bias_bs;

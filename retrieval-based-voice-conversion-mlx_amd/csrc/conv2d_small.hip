@@ -463,7 +463,7 @@ bool conv2d_small_fits(const ConvArgs& a) {
   if (a.W_out < 16 || pix % a.W_out) return false;
   if ((long long)(pix / a.W_out + 2) * (a.W_out + 2) * (a.C_in / 4) > (long long)SIT * 256) return false;
   const bool epi = a.out_map == OUT_ROWS && a.acc_mode == ACC_STORE && !a.mask && a.pre_act == ACT_NONE &&
-                   !a.pre_mask && a.batch_inner == 1 && !a.b_kn && a.stride == 1 &&
+                   !a.pre_mask && a.batch_inner == 1 && a.stride == 1 &&
                    (a.res_mode == RES_NONE || a.res_mode == RES_ADD_POST) &&
                    (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_LRELU) && a.w_bs == 0 && a.bias_bs == 0;
   const bool align = (a.ldx % 4 == 0) && (a.x_bs % 4 == 0) && (a.ldw % 4 == 0) && (a.w_ts % 4 == 0) &&

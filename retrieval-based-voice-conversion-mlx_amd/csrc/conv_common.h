@@ -341,12 +341,11 @@ struct TilePos {
   int m0, h0, w0, rw, rh, n0, b, bi, zb, zsplit, ksplit;
 };
 
-// The block's accumulators -> HBM. Wave (wm, wn) holds TM x TN 32x32 tiles in the MFMA C layout: lane (li, hk),
-// register r is row (r&3) + 8(r>>2) + 4hk, column li. Split-K slices write their partial tile to the slab
-// (splitk_reduce_kernel applies the epilogue); otherwise the fused epilogue runs here.
-template <int TM, int TN, int WM, int WN, bool TWO_D>
-__device__ __forceinline__ void conv_store_tile(const ConvArgs& a, const TilePos& p, f32x16 (&acc)[TM][TN],
-                                                float* smem) {
+// The block's accumulators -> HBM, straight from registers. Wave (wm, wn) of the block's WM x WN holds one 32x32 tile
+// in the MFMA C layout: lane (li, hk), register r is row (r&3) + 8(r>>2) + 4hk, column li. Split-K slices write their
+// partial tile to the slab (splitk_reduce_kernel applies the epilogue); otherwise the fused epilogue runs here.
+template <int WN, bool TWO_D>
+__device__ __forceinline__ void conv_store_tile(const ConvArgs& a, const TilePos& p, const f32x16& acc) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -375,93 +374,54 @@ __device__ __forceinline__ void conv_store_tile(const ConvArgs& a, const TilePos
       }
     }
   };
+  const int n = p.n0 + wn * 32 + li;
+  const bool n_ok = n < a.N;
+  const float bn = (bias && n_ok) ? bias[n] : 0.f;
   if (!TWO_D && p.ksplit == 1 && a.out_map == OUT_ROWS) {
-    // 1-D rows: every accumulator of the wave straight from registers, one 32x32 tile after another, gather
-    // first: the residual, accumulate and mask operands of the lane's 16 outputs of a tile are all loaded before
-    // the first store. The stores may alias them (an in-place residual reads the very element it writes), so
+    // 1-D rows, gather first: the residual, accumulate and mask operands of the lane's 16 outputs are all loaded
+    // before the first store. The stores may alias them (an in-place residual reads the very element it writes), so
     // the compiler cannot hoist the loads across the stores itself and would expose one load latency per output
     // (16 per lane): the short-contraction convs (ResBlock k=3 at 32/64 channels) were latency-bound on exactly
     // that. Each element is read and written by this lane only, so the reorder is exact.
     const bool need_r = R && a.res_mode != RES_NONE;
     const bool need_d = a.acc_mode != ACC_STORE;
+    // element r sits at row mb + (r&3) + 8(r>>2) of column n: per-lane base pointers, constant row offsets
+    const int mb = p.m0 + wm * 32 + 4 * hk;
+    const bool full = p.m0 + wm * 32 + 32 <= a.T_out;
+    const float* Rl = need_r ? R + (long long)mb * a.ldr + n : nullptr;
+    float* Yl = Y + (long long)mb * a.ldy + n;
+    const float* Ml = MK ? MK + mb : nullptr;
+    auto row_ok = [&](int r) { return n_ok && (full || mb + (r & 3) + 8 * (r >> 2) < a.T_out); };
+    // two halves of 8 elements: one exposed load latency each, 24 staging registers instead of 48 (the
+    // VGPR count sets the workgroups per CU of this latency-bound kernel)
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
+    for (int h = 0; h < 2; ++h) {
+      float rv[8], dv[8], mv[8];
 #pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        const int n = p.n0 + wn * TN * 32 + tn * 32 + li;
-        const bool n_ok = n < a.N;
-        const float bn = (bias && n_ok) ? bias[n] : 0.f;
-        // element r sits at row mb + (r&3) + 8(r>>2) of column n: per-lane base pointers, constant row offsets
-        const int mb = p.m0 + wm * TM * 32 + tm * 32 + 4 * hk;
-        const bool full = p.m0 + wm * TM * 32 + tm * 32 + 32 <= a.T_out;
-        const float* Rl = need_r ? R + (long long)mb * a.ldr + n : nullptr;
-        float* Yl = Y + (long long)mb * a.ldy + n;
-        const float* Ml = MK ? MK + mb : nullptr;
-        auto row_ok = [&](int r) { return n_ok && (full || mb + (r & 3) + 8 * (r >> 2) < a.T_out); };
-        // two halves of 8 elements: one exposed load latency each, 24 staging registers instead of 48 (the
-        // VGPR count sets the workgroups per CU of this latency-bound kernel)
+      for (int i = 0; i < 8; ++i) {
+        const int r = 8 * h + i;
+        const int ro = (r & 3) + 8 * (r >> 2);
+        const bool ok = row_ok(r);
+        rv[i] = (ok && need_r) ? Rl[ro * a.ldr] : 0.f;
+        dv[i] = (ok && need_d) ? Yl[ro * a.ldy] : 0.f;
+        mv[i] = (ok && MK) ? Ml[ro] : 1.f;
+      }
+      float v[8];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          float rv[8], dv[8], mv[8];
+      for (int i = 0; i < 8; ++i) v[i] = acc[8 * h + i];
+      epi_math<8>(a, v, bn, rv, dv);
+      epi_mask<8>(MK, v, mv);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int r = 8 * h + i;
-            const int ro = (r & 3) + 8 * (r >> 2);
-            const bool ok = row_ok(r);
-            rv[i] = (ok && need_r) ? Rl[ro * a.ldr] : 0.f;
-            dv[i] = (ok && need_d) ? Yl[ro * a.ldy] : 0.f;
-            mv[i] = (ok && MK) ? Ml[ro] : 1.f;
-          }
-          float v[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = acc[tm][tn][8 * h + i];
-          epi_math<8>(a, v, bn, rv, dv);
-          epi_mask<8>(MK, v, mv);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int r = 8 * h + i;
-            if (row_ok(r)) Yl[((r & 3) + 8 * (r >> 2)) * a.ldy] = v[i];
-          }
-        }
+      for (int i = 0; i < 8; ++i) {
+        const int r = 8 * h + i;
+        if (row_ok(r)) Yl[((r & 3) + 8 * (r >> 2)) * a.ldy] = v[i];
       }
     }
     return;
   }
-  if constexpr (TM * TN == 1) {
-    // one accumulator per wave: straight from registers (fully unrolled, 16 values per lane)
-    const int n = p.n0 + wn * 32 + li;
-    const bool n_ok = n < a.N;
-    const float bn = (bias && n_ok) ? bias[n] : 0.f;
+  // every other form (2-D, the split-K slab, the ConvTranspose2d scatter): fully unrolled, 16 values per lane
 #pragma unroll
-    for (int r = 0; r < 16; ++r) emit(acc[0][0][r], wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hk, n, n_ok, bn);
-  } else {
-    // several accumulators per wave: stage one 32x32 tile at a time through the wave's own LDS slot
-    // (32 x 33 floats) and emit rows 2i + hk, column li; accumulator registers are only indexed with
-    // compile-time constants, so the large wave tiles keep them out of scratch
-    __syncthreads();  // every wave is done with the A/B tiles: their LDS becomes the staging area
-    float* Cs = smem + wave * (32 * 33);
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Cs[((r & 3) + 8 * (r >> 2) + 4 * hk) * 33 + li] = acc[tm][tn][r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int n = p.n0 + wn * TN * 32 + tn * 32 + li;
-        const bool n_ok = n < a.N;
-        const float bn = (bias && n_ok) ? bias[n] : 0.f;
-        for (int i = 0; i < 16; ++i) {
-          const int rr = 2 * i + hk;
-          emit(Cs[rr * 33 + li], wm * TM * 32 + tm * 32 + rr, n, n_ok, bn);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-    }
-  }
+  for (int r = 0; r < 16; ++r) emit(acc[r], wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hk, n, n_ok, bn);
 }
 
 // Block -> tile: the grid is 1-D over (M tile, N tile) with N fastest when ntn > 0, and the linear workgroup id
@@ -484,13 +444,12 @@ __device__ __forceinline__ void conv_block_coords(int ntn, int& bx, int& by, int
   }
 }
 
-// One tile configuration of the LDS-staged kernels: conv_gemm.hip (native fp32 MFMA, cfg 0..9) and conv_emu.hip (fp32
-// through a 3-way bf16 operand split, cfg 10..16). pipe: the double-buffered GEMM form; a split launch (ksplit > 1)
-// writes the slab and leaves the combine to the caller. hipErrorInvalidValue: the tile's LDS does not fit, or the
-// tile has no such form
+// One tile of the LDS-staged kernels: conv_gemm.hip (native fp32 MFMA, TILE_F32_*) and conv_emu.hip (fp32 through a
+// 3-way bf16 operand split, TILE_EMU_*). pipe: the double-buffered GEMM form; a split launch (ksplit > 1) writes the
+// slab and leaves the combine to the caller. hipErrorInvalidValue: the tile's LDS does not fit, the tile is not that
+// family's, or it has no such form
 hipError_t conv_gemm_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit, hipStream_t s);
 hipError_t conv_emu_launch(const ConvArgs& a, int cfg, bool two_d, bool pipe, int ksplit, hipStream_t s);
-bool conv_emu_tile(int cfg, int& BM, int& BN);
 // conv_tiny.hip: the one-thread-per-output kernels, the shapes they take and their launches
 bool tiny_fits(const ConvArgs& a);
 bool rows1x1_fits(const ConvArgs& a, bool two_d);

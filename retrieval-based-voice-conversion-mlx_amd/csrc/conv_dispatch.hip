@@ -16,7 +16,8 @@ namespace {
 // Tile per shape class, measured on MI355X (same-box A/B of the whole pipeline, bench.py at each policy):
 // one 32x32 accumulator per wave with 4 waves per block beats the larger per-wave tiles in the pipeline:
 // 128x32 for N <= 32 and for the long-tap 1-D convs (the generator's dilated ResBlock convs), 64x64
-// otherwise; split-K when the output grid cannot fill 256 CUs.
+// otherwise; split-K when the output grid cannot fill 256 CUs. Those two shapes are the LDS-staged tiles that exist
+// (ConvTile); the larger ones they beat are gone, their bench_conv tables kept (DESIGN.md §3 names the files).
 inline int env_cfg(const char* name, int dflt) {
   const char* e = rvcx_knob(name);
   return e ? std::atoi(e) : dflt;
@@ -58,13 +59,13 @@ int pick_cfg(const ConvArgs& a, bool two_d) {
   return TILE_F32_64x64;
 }
 
-inline bool cfg_tile(int cfg, int& BM, int& BN) {
-  if (conv_emu_tile(cfg, BM, BN)) return true;
-  if (cfg < 0 || cfg >= 10) return false;
-  static const int t[10][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 128}, {64, 128}, {256, 64},
-                               {64, 64}, {128, 32}, {128, 128}};
-  BM = t[cfg][0];
-  BN = t[cfg][1];
+// the LDS-staged tiles, the same two shapes in both arithmetics (ids from 10 on: the bf16 split, conv_emu.hip); an id
+// no family has -- the removed tiles' among them -- is refused
+inline bool lds_tile(int tile, int& BM, int& BN) {
+  const bool wide = tile == TILE_F32_64x64 || tile == TILE_EMU_64x64;
+  if (!wide && tile != TILE_F32_128x32 && tile != TILE_EMU_128x32) return false;
+  BM = wide ? 64 : 128;
+  BN = wide ? 64 : 32;
   return true;
 }
 
@@ -204,7 +205,7 @@ ConvPlan plan_gs(const ConvArgs& a, bool two_d) {
 // the LDS-staged families on tile `tile`; split_as_gs: the split is the gather-streamed tile's (below)
 ConvPlan plan_lds(const ConvArgs& a, bool two_d, int tile, int pipe, bool split_as_gs) {
   int BM, BN;
-  if (!cfg_tile(tile, BM, BN) || a.nz_har) return refused;  // no kernel with a 16x16 tile store took the noise conv
+  if (!lds_tile(tile, BM, BN) || a.nz_har) return refused;  // no kernel with a 16x16 tile store took the noise conv
   // the arithmetic: fp32 through bf16 planes (conv_emu.hip) or native fp32 (conv_gemm.hip)
   ConvPlan p{tile >= 10 ? CK_EMU : CK_GEMM, tile, 1, 0, -1, false, false};
   // plain GEMMs (1-D, one tap, stride 1) take the double-buffered pipeline unless pipe < 0; pipe > 0 forces it
@@ -215,15 +216,15 @@ ConvPlan plan_lds(const ConvArgs& a, bool two_d, int tile, int pipe, bool split_
   return p;
 }
 
-// one LDS-staged launch: the planned tile; where its halo does not fit in LDS (long strided taps) or the shape class
-// has no such instantiation, the two fallback tiles of that arithmetic, 64 x 64 then 128 x 32 (policy launches only)
+// one LDS-staged launch: the planned tile; where its halo does not fit in LDS (long strided taps), the other tile of
+// that arithmetic (policy launches only)
 hipError_t run_lds(const ConvPlan& p, const ConvArgs& a, bool two_d, bool fallback, hipStream_t s) {
   const bool emu = p.kind == CK_EMU;
   auto run = [&](int c, bool pipe) {
     return emu ? conv_emu_launch(a, c, two_d, pipe, p.ksplit, s) : conv_gemm_launch(a, c, two_d, pipe, p.ksplit, s);
   };
   hipError_t e = run(p.tile, p.pipe);
-  if (e == hipErrorInvalidValue && p.pipe) e = run(p.tile, false);  // tile without a GEMM-pipeline instantiation
+  if (e == hipErrorInvalidValue && p.pipe) e = run(p.tile, false);  // a forced pipeline on a conv that is no plain GEMM
   if (e == hipErrorInvalidValue && fallback) {
     for (int alt : {emu ? TILE_EMU_64x64 : TILE_F32_64x64, emu ? TILE_EMU_128x32 : TILE_F32_128x32}) {
       if (alt == p.tile) continue;

@@ -563,7 +563,7 @@ bool conv_gs_form(const ConvArgs& a, bool two_d) {
   // (store_tile16 maps it; a split launch's combine does, as for the LDS-staged kernel)
   const bool up2d = two_d && a.out_map == OUT_UPSAMPLE2D && a.out_cv > 0 && a.N == 4 * a.out_cv && !a.res &&
                     a.acc_mode == ACC_STORE && !a.mask && !a.nz_har;
-  const bool common = a.batch_inner == 1 && !a.b_kn && a.C_in % EK == 0 && a.C_in > 0 && a.taps >= 1 && vec_a &&
+  const bool common = a.batch_inner == 1 && a.C_in % EK == 0 && a.C_in > 0 && a.taps >= 1 && vec_a &&
                       (a.out_map == OUT_ROWS || up2d) && a.stride >= 1 && a.dil >= 1;
   if (!common) return false;
   // 32-bit element offsets within one batch entry (the A gather)

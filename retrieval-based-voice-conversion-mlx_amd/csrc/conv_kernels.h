@@ -39,12 +39,11 @@ struct ConvArgs {
   float pre_slope = 0.f;
   const float* pre_mask = nullptr;  // [b][row] multiplier applied to input rows (1-D only)
   long long pre_mask_bs = 0;
-  // B operand (weights): NK: w + tap*w_ts + n*ldw + c ; KN: w + tap*w_ts + c*ldw + n
+  // B operand (weights): w + tap*w_ts + n*ldw + c
   const float* w = nullptr;
   long long w_bs = 0;
   long long w_ts = 0;
   int ldw = 0;
-  int b_kn = 0;
   // geometry
   int taps = 1;
   int stride = 1, dil = 1, pad = 0;     // 1-D
@@ -89,7 +88,6 @@ struct ConvArgs {
   int batch = 1;
   int batch_inner = 1;
   long long x_bs2 = 0, w_bs2 = 0, y_bs2 = 0, res_bs2 = 0, bias_bs2 = 0;
-  int astage = 0;  // A-tile staging batch: 0 = default (1), 1 = serial, 4 = 4 loads in flight
   int math = 0;   // contraction arithmetic: 0 = default (RVCX_CONV_MATH), 1 = native fp32 MFMA, 2 = fp32 via 3 bf16 planes
   int w_static = 0;             // the B operand is a constant weight tensor (callers set it; enables the cache)
   // the pre-split weight image of the streamed kernels, in the format the plan names (ConvPlan::wsplit_fmt): the
@@ -137,9 +135,10 @@ struct ConvArgs {
 enum ConvKind : int { CK_WSB16 = 0, CK_WSB, CK_GS, CK_GSW, CK_RBPAIR, CK_SMALL2D, CK_EMU, CK_GEMM, CK_TINY, CK_WST,
                       CK_OTHER, CK_COUNT };
 const char* conv_kind_name(int k);
-// Tile ids, by the numbers DESIGN.md, profiles/ and bench_conv's command line know them by: the LDS-staged kernels'
-// native fp32 tiles 0..9 (conv_gemm.hip) and bf16-split tiles 10..16 (conv_emu.hip), the weight-streamed 23..27
-// (conv_wsb.hip), the gather-streamed 30 (conv_gs.hip)
+// Tile ids, by the numbers DESIGN.md, profiles/ and bench_conv's command line know them by. Every tile that exists is
+// listed: the LDS-staged kernels' native fp32 tiles 1 and 3 (conv_gemm.hip) and bf16-split tiles 12 and 13
+// (conv_emu.hip) -- the other ids below 20 named tiles the planner never chose and are gone --, the
+// weight-streamed 23..27 (conv_wsb.hip), the gather-streamed 30 (conv_gs.hip)
 enum ConvTile : int {
   TILE_NONE = -1,  // the family has one form (tiny, 3x3 small-channel, weight-stationary)
   TILE_F32_128x32 = 1, TILE_F32_64x64 = 3, TILE_EMU_128x32 = 12, TILE_EMU_64x64 = 13,

@@ -50,7 +50,7 @@ __global__ void conv_tiny_kernel(const ConvArgs a) {
       const float* Wt = Wb + (long long)tap * a.w_ts;
       for (int c = 0; c < a.C_in; ++c) {
         const float v = act_fn(X[(long long)g * a.ldx + c], a.pre_act, a.pre_slope) * pm;
-        const float wv = a.b_kn ? Wt[(long long)c * a.ldw + n] : Wt[(long long)n * a.ldw + c];
+        const float wv = Wt[(long long)n * a.ldw + c];
         acc = fmaf(v, wv, acc);
       }
     }
@@ -180,7 +180,7 @@ namespace {
 
 // conv_tiny_rows_kernel's shapes: only bias + activation in the epilogue, N in {16, 32}, 16-B aligned output rows
 inline bool tiny_rows_fits(const ConvArgs& a) {
-  return (a.N == 16 || a.N == 32) && a.pre_act == ACT_NONE && !a.pre_mask && !a.b_kn && a.batch_inner == 1 &&
+  return (a.N == 16 || a.N == 32) && a.pre_act == ACT_NONE && !a.pre_mask && a.batch_inner == 1 &&
          a.out_map == OUT_ROWS && a.res_mode == RES_NONE && !a.mask && a.acc_mode == ACC_STORE && a.alpha == 1.f &&
          (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_LRELU) && (a.ldy & 3) == 0 && (a.y_bs & 3) == 0 &&
          (reinterpret_cast<uintptr_t>(a.y) & 15) == 0 && a.gate_h == 0;

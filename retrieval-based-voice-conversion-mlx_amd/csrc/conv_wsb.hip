@@ -346,7 +346,7 @@ hipError_t launch_wsb16(const ConvArgs& a, int ksplit, hipStream_t s) {
 
 bool conv_wsb_eligible(const ConvArgs& a, bool two_d) {
   const bool vec_a = ((a.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && ((a.x_bs & 3) == 0);
-  return !two_d && a.batch_inner == 1 && !a.b_kn && a.C_in % EK == 0 && a.C_in > 0 && a.taps >= 1 && vec_a &&
+  return !two_d && a.batch_inner == 1 && a.C_in % EK == 0 && a.C_in > 0 && a.taps >= 1 && vec_a &&
          a.out_map == OUT_ROWS && a.stride == 1 && (a.taps - 1) * a.dil <= WSB_HALO && a.dil >= 1;
 }
 

@@ -328,7 +328,7 @@ bool conv_wst_fits(const ConvArgs& a, bool two_d) {
                      (!a.nz_har || (a.nz_C % 4 == 0 && a.nz_kk == 1));
   const bool shape = (a.C_in == 128 && a.N == 128 && (a.taps == 3 || a.taps == 2)) ||
                      (a.C_in == 64 && a.N == 64 && (a.taps == 3 || a.taps == 2));
-  return !two_d && shape && vec_a && vec_y && !a.lowp && a.batch_inner == 1 && !a.b_kn && a.out_map == OUT_ROWS &&
+  return !two_d && shape && vec_a && vec_y && !a.lowp && a.batch_inner == 1 && a.out_map == OUT_ROWS &&
          a.stride == 1 && a.dil >= 1 && (a.taps - 1) * a.dil <= WST_HMAX &&
          (a.pre_act == ACT_LRELU || a.pre_act == ACT_NONE) && !a.pre_mask && a.alpha == 1.f && !a.mask && (a.act == ACT_NONE || a.act == ACT_LRELU) &&
          (a.res_mode == RES_NONE || (a.res_mode == RES_ADD_POST && a.res)) && a.bias_bs == 0 && a.gate_h == 0 &&

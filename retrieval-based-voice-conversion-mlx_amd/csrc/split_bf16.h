@@ -43,7 +43,7 @@ __device__ __forceinline__ void put_split4(char* row, int c4, f32x4 v) {
   *reinterpret_cast<uint2*>(row + 2 * PLANE + c4 * 2) = l;
 }
 
-// one channel (KN-layout operands are transposed on their way into LDS)
+// one channel: the plane arithmetic the pre-split weight images state theirs by (conv_wsb.hip, resblock_fused.hip)
 __device__ __forceinline__ void put_split1(char* row, int c, float v) {
   const unsigned h = pk_bf16(v, 0.f);
   const float r = v - lo_f(h);

@@ -114,7 +114,7 @@ class ConvPlanForm(ctypes.Structure):
     """rvcx_conv_plan_form (include/rvcx_test.h): the record's fields a 1-D ConvTestDesc lacks."""
     _fields_ = [("W_in", ctypes.c_int), ("W_out", ctypes.c_int), ("KH", ctypes.c_int), ("KW", ctypes.c_int),
                 ("padh", ctypes.c_int), ("padw", ctypes.c_int), ("out_map", ctypes.c_int), ("out_cv", ctypes.c_int),
-                ("b_kn", ctypes.c_int), ("lowp", ctypes.c_int), ("ldw", ctypes.c_int), ("w_ts", ctypes.c_int64),
+                ("lowp", ctypes.c_int), ("ldw", ctypes.c_int), ("w_ts", ctypes.c_int64),
                 ("w_bs", ctypes.c_int64), ("bias_bs", ctypes.c_int64)]
 
 

@@ -11,7 +11,8 @@ the semantics documented at ConvArgs (csrc/conv_kernels.h) and spelled out by ep
     LN      y = LN(res + act(alpha (acc + bias)) mask) ln_g + ln_b over the N columns (biased variance)
 
 CASES is the table tests/test_gpu_conv_forms.py runs on the device and tests/test_conv_form_ref_cpu.py proves
-sensitive: one row per runtime call site, at the smallest shape that still reaches the site's kernel paths. `make`
+sensitive: one row per runtime call site, at the smallest shape that still reaches the site's kernel paths, and the
+edge forms of the LDS-staged families' gather that no site reaches (the lds.* rows). `make`
 draws a case's inputs, `place` / `gather` move logical arrays into and out of strided buffers whose every other
 element is a guard, `mutate` applies one of the deviations a wrong kernel could carry.
 """
@@ -109,6 +110,19 @@ CASES = [
     _c("rm.mel", "runtime_fe.cpp:671", ALL5, T_in=100, C_in=544, N=128, act=LOGCLAMP, slope=1e-5, bias=False,
        nonneg=True),
     _c("rm.fc", "runtime_fe.cpp:637", ALL5, T_in=100, C_in=512, N=360, act=SIGMOID),
+    # The edge forms of the LDS-staged families' shared gather (csrc/conv_lds.h), which no runtime site reaches (each
+    # has C_in % 4 == 0 and 16-byte aligned rows): the scalar channel tail with a last chunk padded by zero channels
+    # and a partial N tile, under a leaky-ReLU pre-activation and a row mask over non-zero rows (the mask applies to
+    # the activated value); rows no vector load may touch (odd row stride, view one float in: the GEMM pipeline
+    # unsplit, and its split over an odd number of chunks, which the LayerNorm forces); a strided dilated conv whose
+    # halo reads before row 0 and past an odd T_in, with T_out a multiple of neither tile's rows.
+    _c("lds.tail", "conv_lds.h lds_load4", ("f32", "emu"), B=2, T_in=150, C_in=50, N=40, taps=3, pad=1,
+       pre_act=LRELU, pre_slope=0.1, pre_mask=True, lengths=(150, 113)),
+    _c("lds.unaligned", "conv_lds.h lds_load4", ("f32", "emu"), B=2, T_in=70, C_in=64, N=64, ldx=65, x_col0=1),
+    _c("lds.unaligned_split", "conv_lds.h lds_slice", ("f32", "emu"), T_in=70, C_in=96, N=64, ldx=97, x_col0=1,
+       res="ln", ln=True),
+    _c("lds.strided", "conv_lds.h lds_src_row", ("f32", "emu"), B=2, T_in=131, C_in=64, N=48, taps=3, stride=2, pad=1,
+       dil=2),
 ]
 BY_NAME = {c["name"]: c for c in CASES}
 

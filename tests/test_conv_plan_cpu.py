@@ -55,7 +55,7 @@ def plan(lib, r):
     d.x_bs, d.y_bs, d.res_bs = r["x_bs4"], r["y_bs4"], r["res_bs4"]
     d.alpha, d.acc_div = (1.0 if r["alpha1"] else 2.0), 1.0
     f = _lib.ConvPlanForm()
-    for k in ("W_in", "W_out", "KH", "KW", "padh", "padw", "out_map", "out_cv", "b_kn", "lowp", "ldw", "w_bs", "bias_bs"):
+    for k in ("W_in", "W_out", "KH", "KW", "padh", "padw", "out_map", "out_cv", "lowp", "ldw", "w_bs", "bias_bs"):
         setattr(f, k, r[k])
     f.w_ts = 4 * r["N"] * r["ldw"] + r["w_ts4"]  # any tap stride with the recorded remainder modulo 4
     out = [ctypes.c_int(-99) for _ in range(4)]
