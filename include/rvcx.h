@@ -189,6 +189,20 @@ int rvcx_fcpe(rvcx_ctx* ctx, const float* d_audio, int64_t n, float threshold, i
  * interp_uv / pad_to tail stays with rvcx_fcpe. */
 int rvcx_fcpe_b(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld, int B, float threshold, int decoder_mode,
                 double* d_f0, float* d_salience, void* stream);
+/* rvcx_fcpe's raw track over B inputs of different lengths in one launch set: row b has n[b] samples (host array) at
+ * d_audio + b*lda (lda >= every n[b]; samples past n[b] are never read). Row b's f0 [F_b] fp64, F_b = n[b]/hop + 1
+ * (written to F_out[b], host, optional), lands at d_f0 + b*ldf, and its salience [F_b][out_dims] (d_salience,
+ * optional) at d_salience + b*ld_sal_frames*out_dims; ldf (and ld_sal_frames) must hold the longest row's frames, else
+ * RVCX_E_CAPACITY. Values of a row past F_b are not written. Every row equals rvcx_fcpe's (interp_uv = 0) on that input
+ * alone up to summation order: the mel reflects about the row's own end and repeats the row's own last frame, the
+ * k = 3 convs and the depthwise conv read zero past the row's own last frame, the GroupNorm statistics and the
+ * attention's sums run over the row's own frames. Equal lengths take rvcx_fcpe_b's path and B = 1 rvcx_fcpe's, bit
+ * for bit. Among rows of different lengths a row short enough for the mel's zero padding (n <= (win - hop + 1)/2: 432 samples
+ * for win 1024, hop 160) fails with RVCX_E_SHAPE: the per-row front end reflects. B < 1 is
+ * RVCX_E_INVALID. The interp_uv / pad_to tail stays with rvcx_fcpe. */
+int rvcx_fcpe_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, float threshold,
+                      int decoder_mode, double* d_f0, int64_t ldf, int64_t* F_out, float* d_salience,
+                      int64_t ld_sal_frames, void* stream);
 /* The decode alone (the tail of rvcx_fcpe after the network: FCPE.py:683-714, :877-902) on caller-given salience
  * d_salience [F][out_dims], with the loaded model's cent table and hop / sampling rate. d_f0 fp64 [pad_to when
  * interp_uv and pad_to > 0, else F]. */
@@ -301,7 +315,11 @@ typedef struct {
                                        zeros where unvoiced; the model's hop must be 160 at 16 kHz), 4 = RMVPE with
                                        the rows of a batch in one ragged pass (rvcx_rmvpe_batch_v; in
                                        rvcx_pipeline_batch_v only: a row's f0 then equals method 0's up to summation
-                                       order, not bit for bit. One utterance and equal lengths run as method 0) */
+                                       order, not bit for bit. One utterance and equal lengths run as method 0),
+                                       5 = FCPE with the rows of a batch in one ragged pass (rvcx_fcpe_batch_v; in
+                                       rvcx_pipeline_batch_v only, method 3's requirements: a row's f0 then equals
+                                       method 3's up to summation order. Equal lengths share rvcx_fcpe_b's batched
+                                       pass; one utterance runs as method 3) */
   float fcpe_threshold;             /* FCPE's voicing threshold (FCPE.get_f0's filter_radius, f0.py:71); <= 0: 0.006 */
 } rvcx_pipeline_opts;
 
@@ -344,7 +362,8 @@ int rvcx_pipeline_batch(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t
  * upsample + protect, the pitch packing, the trim, the volume envelope and the peak normalisation, whatever B is.
  * The pitch network runs per row under f0_method 0 (the default: a row's f0 is then rvcx_pipeline_ex's bit for bit),
  * rows of equal length inside the batch sharing one batched RMVPE pass; f0_method 4 runs all rows in one ragged RMVPE
- * pass (rvcx_rmvpe_batch_v: equal to the per-row pass up to summation order).
+ * pass (rvcx_rmvpe_batch_v: equal to the per-row pass up to summation order). FCPE likewise: per row under f0_method 3,
+ * all rows in one ragged pass under f0_method 5 (rvcx_fcpe_batch_v).
  * Noise when injected uses rvcx_pipeline_batch's layouts with T the longest row's frame count T_max = max_b
  * min((n[b] + 2 t_pad) / 160, 2 L_b): d_eps_z [B][inter][T_max], d_eps_src [B][T_max*upp]; row b consumes
  * d_eps_z[b][:, :T_b] and the first T_b*upp source draws, the draws a B = 1 call on that row consumes.
@@ -378,7 +397,8 @@ int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, doub
  *   longest first, so the work buffers grow only inside the first chunk), so the size holds for any audio of n samples.
  *   With f0_method 3 the FCPE network's scratch (mel, activations, the attention's ctx / ksum slab images) is carved
  *   in place of RMVPE's; the call is then sized under f0_method 0 as well and the larger size is reported.
- *   With f0_method 4 and B > 1 the ragged RMVPE pass is sized on B rows of n samples.
+ *   With f0_method 4 and B > 1 the ragged RMVPE pass is sized on B rows of n samples; with f0_method 5 the ragged
+ *   FCPE pass, and as under f0_method 3 the size also covers the same call under f0_method 0.
  * rvcx_set_workspace: hand the context a caller-owned device arena (e.g. a torch uint8 tensor's data_ptr(), 256-B
  *   aligned), valid until replaced or the context is destroyed: the pool is then carved from it and never allocated,
  *   and a call that would need more fails with RVCX_E_OOM. NULL, 0 returns to internal allocation. The current pool

@@ -160,6 +160,12 @@ int rvcx_performer_attention(rvcx_ctx* ctx, const float* d_q, const float* d_k, 
 int rvcx_performer_attention_b(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int H,
                                int T, const float* d_P, int M, float* d_out, void* stream);
 
+/* The same for B streams of different lengths in those launches: stream b has T[b] <= T_max rows (host array) in its
+ * slot of d_q, d_k, d_v, d_out [B][H][T_max][64]. Rows from T[b] on are neither read nor written, and stream b's rows
+ * equal rvcx_performer_attention's on that stream alone bit for bit. */
+int rvcx_performer_attention_v(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int H,
+                               const int32_t* T, int T_max, const float* d_P, int M, float* d_out, void* stream);
+
 /* The FCPE network's input alone, as rvcx_fcpe forms it (rvc/lib/predictors/FCPE.py: Wav2Mel.extract_mel :790-813 over
  * STFT.get_mel :102-168): d_audio [n] fp32 at the loaded model's sampling rate -> d_mel [F][num_mels], the log-mel of
  * every band, F = n / hop + 1 frames (*frames_out; cap_frames >= F). Needs RVCX_MODEL_FCPE finalized. */

@@ -232,6 +232,24 @@ int rvcx_fcpe_b(rvcx_ctx* ctx, const float* d_audio, int64_t n, int64_t ld, int 
   });
 }
 
+int rvcx_fcpe_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int64_t lda, int B, float threshold,
+                      int decoder_mode, double* d_f0, int64_t ldf, int64_t* F_out, float* d_salience,
+                      int64_t ld_sal_frames, void* stream) {
+  return guard(ctx, [&] {
+    if (!ctx->ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+    if (!d_audio || !d_f0 || !n || B < 1 || ldf < 1 || (d_salience && ld_sal_frames < 1) || decoder_mode < 0 ||
+        decoder_mode > 1)
+      throw Error(RVCX_E_INVALID, "rvcx_fcpe_batch_v: bad arguments");
+    for (int b = 0; b < B; ++b)
+      if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_fcpe_batch_v: bad row length");
+    set_device(ctx);
+    fcpe_forward_v(*ctx, d_audio, n, lda, B, threshold, decoder_mode, d_f0, ldf, d_salience, ld_sal_frames,
+                   static_cast<hipStream_t>(stream));
+    if (F_out)
+      for (int b = 0; b < B; ++b) F_out[b] = fcpe_frames(*ctx, n[b]);
+  });
+}
+
 int rvcx_fcpe_decode(rvcx_ctx* ctx, const float* d_salience, int64_t F, float threshold, int decoder_mode,
                      int interp_uv, int64_t pad_to, double* d_f0, void* stream) {
   return guard(ctx, [&] {

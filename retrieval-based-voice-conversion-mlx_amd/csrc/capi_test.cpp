@@ -396,6 +396,28 @@ int rvcx_performer_attention_b(rvcx_ctx* ctx, const float* d_q, const float* d_k
   });
 }
 
+int rvcx_performer_attention_v(rvcx_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int H,
+                               const int32_t* T, int T_max, const float* d_P, int M, float* d_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_q || !d_k || !d_v || !d_P || !d_out || !T || B <= 0 || H <= 0 || T_max <= 0 || M <= 0)
+      throw Error(RVCX_E_INVALID, "rvcx_performer_attention_v: bad argument");
+    for (int b = 0; b < B; ++b)
+      if (T[b] < 1 || T[b] > T_max) throw Error(RVCX_E_INVALID, "rvcx_performer_attention_v: bad row count");
+    if (M > PERFORMER_MAX_FEATURES || B > 4096 || (long long)B * H * T_max * 64 > INT32_MAX)
+      throw Error(RVCX_E_SHAPE, "rvcx_performer_attention_v: at most 512 features and 2^31 elements per operand");
+    set_device(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t* dT = ctx->buf<int32_t>("perf.test.T", (size_t)B, s);
+    RVCX_HIP(hipMemcpyAsync(dT, T, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, s));
+    float* ws = ctx->buf<float>("perf.test.ws", (size_t)performer_ws_floats(H, T_max, M, B), s);
+    const long long bs = (long long)H * T_max * 64;
+    check(performer_attention(d_q, d_k, d_v, (long long)T_max * 64, 64, H, T_max, d_P, M, ws, d_out,
+                              (long long)T_max * 64, 64, s, B, bs, bs, dT),
+          "performer_attention");
+    RVCX_HIP(hipStreamSynchronize(s));  // T is the caller's
+  });
+}
+
 int rvcx_kmeans_assign(rvcx_ctx* ctx, const float* d_x, int64_t n, int d, const float* d_cent, int64_t nlist,
                        int32_t* d_assign, float* d_dist, void* stream) {
   return guard(ctx, [&] {

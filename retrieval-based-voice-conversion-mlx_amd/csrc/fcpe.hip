@@ -3,7 +3,9 @@
 // magnitude of its mel is rmvpe_aux.hip's, shared with RMVPE). The Performer attention is performer_attn.hip; the convs
 // and linears run on the implicit-GEMM family. The kernels that pad or reduce over time (GroupNorm, the depthwise conv, the mel's padding
 // and repeated last frame) take B streams of one length per launch, grid z (or y) = stream, each stream on its own
-// rows; the row-wise ones (the decoders) run on the B F rows of all streams.
+// rows; the row-wise ones (the decoders) run on the B F rows of all streams. For utterances of different lengths each
+// of them also takes a device array of the streams' own frame counts inside slots of one length (fcpe_forward_v),
+// indexed by the grid's stream index, so the length is one scalar load and every branch on it is the workgroup's.
 #include <algorithm>
 #include <cmath>
 
@@ -32,16 +34,29 @@ __global__ void k_fcpe_dup_last(float* mel, int F, int C) {
   for (int c = threadIdx.x; c < C; c += blockDim.x) m[(long long)(F - 1) * C + c] = m[(long long)(F - 2) * C + c];
 }
 
+// The ragged form: stream b has Fv[b] <= F frames in its F-row slot. Row Fv[b] - 1 = a copy of row Fv[b] - 2 (written
+// by nobody here), rows Fv[b] .. F - 1 zero. One workgroup per (row from Fv[b] - 1 on, stream).
+__global__ void k_fcpe_mel_tail_v(float* mel, const int* Fv, int F, int C) {
+  const int Fb = Fv[blockIdx.y], t = Fb - 1 + (int)blockIdx.x;
+  if (t >= F) return;
+  float* m = mel + (long long)blockIdx.y * F * C;
+  for (int c = threadIdx.x; c < C; c += blockDim.x)
+    m[(long long)t * C + c] = t == Fb - 1 ? m[(long long)(Fb - 2) * C + c] : 0.f;
+}
+
 // GroupNorm(G, C) over time-major x [T][C] in place, then LeakyReLU(slope) (FCPE.py:626-630: the statistics of a
 // group run over its C / G channels x T frames). Two launches: k_gn_stats sums each of GN_TCHUNKS time chunks of a
 // group in fp64 (a fixed tree over the workgroup) into ws [G][GN_TCHUNKS][2]; k_gn_apply adds the chunks in chunk
 // order (every thread the same sequence: no atomics, run-to-run bit identical) and normalises. grid z = stream: B
-// sequences of T rows back to back, the statistics per (stream, group), ws [B][G][GN_TCHUNKS][2].
+// sequences of T rows back to back, the statistics per (stream, group), ws [B][G][GN_TCHUNKS][2]. With Tv, stream b
+// has Tv[b] <= T rows in its T-row slot (one scalar load per workgroup): the chunks are those of Tv[b] rows, so the
+// sums are the ones a call on that stream alone forms, and k_gn_apply sets the slot's rows from Tv[b] on to zero.
 constexpr int GN_TCHUNKS = FCPE_GN_CHUNKS;
-__global__ __launch_bounds__(256) void k_gn_stats(const float* x, int T, int C, int G, double* ws) {
+__global__ __launch_bounds__(256) void k_gn_stats(const float* x, int Ts, int C, int G, double* ws, const int* Tv) {
   __shared__ double s1[256], s2[256];
   const int g = blockIdx.y, cg = C / G, c0 = g * cg;
-  x += (long long)blockIdx.z * T * C;
+  const int T = Tv ? Tv[blockIdx.z] : Ts;
+  x += (long long)blockIdx.z * Ts * C;
   ws += (long long)blockIdx.z * G * GN_TCHUNKS * 2;
   const int per = (T + GN_TCHUNKS - 1) / GN_TCHUNKS;
   const int t_lo = min(T, (int)blockIdx.x * per), t_hi = min(T, t_lo + per);
@@ -67,11 +82,12 @@ __global__ __launch_bounds__(256) void k_gn_stats(const float* x, int T, int C, 
     ws[((long long)g * GN_TCHUNKS + blockIdx.x) * 2 + 1] = s2[0];
   }
 }
-__global__ __launch_bounds__(256) void k_gn_apply(float* x, int T, int C, int G, const double* ws, const float* gamma,
-                                                  const float* beta, float eps, float slope) {
+__global__ __launch_bounds__(256) void k_gn_apply(float* x, int Ts, int C, int G, const double* ws, const float* gamma,
+                                                  const float* beta, float eps, float slope, const int* Tv) {
   const int g = blockIdx.y, cg = C / G, c0 = g * cg;
-  const long long n = (long long)T * cg;
-  x += (long long)blockIdx.z * T * C;
+  const int T = Tv ? Tv[blockIdx.z] : Ts;
+  const long long n = (long long)T * cg, ns = (long long)Ts * cg;
+  x += (long long)blockIdx.z * Ts * C;
   ws += (long long)blockIdx.z * G * GN_TCHUNKS * 2;
   double a = 0.0, b = 0.0;
   for (int k = 0; k < GN_TCHUNKS; ++k) {
@@ -81,9 +97,13 @@ __global__ __launch_bounds__(256) void k_gn_apply(float* x, int T, int C, int G,
   const double mean = a / (double)n;
   const double var = fmax(b / (double)n - mean * mean, 0.0);
   const float mu = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)eps));
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < ns; i += (long long)gridDim.x * blockDim.x) {
     const int c = c0 + (int)(i % cg);
     float* p = x + (i / cg) * C + c;
+    if (i >= n) {  // a row past the stream's own end
+      *p = 0.f;
+      continue;
+    }
     const float v = (*p - mu) * rstd * gamma[c] + beta[c];
     *p = v > 0.f ? v : v * slope;
   }
@@ -94,16 +114,20 @@ __global__ __launch_bounds__(256) void k_gn_apply(float* x, int T, int C, int G,
 //   y[t][c] = swish(b[c] + sum_k w[k][c] g[t + k - pad][c])         depthwise conv, zero padding, Swish
 // One workgroup per (64 channels, 32 output frames, stream): the GLU'd rows t0 - pad .. t0 + 31 + K - 1 - pad sit in
 // LDS. grid z = stream (B sequences of T rows back to back): the zero padding is each stream's own, t outside [0, T).
+// With Tv, stream b ends at row Tv[b] <= T of its T-row slot: workgroups from there on exit (before the barrier: the
+// condition is the workgroup's), taps from there on read zero.
 constexpr int DW_T = 32, DW_MAXK = 64;
-__global__ __launch_bounds__(256) void k_glu_dw_swish(const float* x, int T, int C2, const float* w, const float* b,
-                                                       int K, int pad, float* y) {
+__global__ __launch_bounds__(256) void k_glu_dw_swish(const float* x, int Ts, int C2, const float* w, const float* b,
+                                                       int K, int pad, float* y, const int* Tv) {
   __shared__ float g[(DW_T + DW_MAXK - 1) * 64];
   const int cl = threadIdx.x & 63, tg = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
   const int t0 = blockIdx.y * DW_T;
   const int rows = DW_T + K - 1;
-  x += (long long)blockIdx.z * T * 2 * C2;
-  y += (long long)blockIdx.z * T * C2;
+  const int T = Tv ? Tv[blockIdx.z] : Ts;
+  if (t0 >= T) return;
+  x += (long long)blockIdx.z * Ts * 2 * C2;
+  y += (long long)blockIdx.z * Ts * C2;
   for (int i = tg; i < rows; i += 4) {
     const int t = t0 - pad + i;
     float v = 0.f;
@@ -132,11 +156,9 @@ __global__ __launch_bounds__(256) void k_glu_dw_swish(const float* x, int T, int
 //   mode 1 "argmax": cents = sum(ci y) / sum(y) over all bins
 // f0 = 10 * 2^(cents / 1200), 0 where max <= threshold (the reference's -inf cents). The fp32 products are summed in
 // fp64 and the quotient is taken in fp32; f0 is written as the exact fp32 value in fp64.
-__global__ void k_fcpe_decode(const float* sal, int F, int nb, const float* cent, float thr, int mode, double* f0) {
-  const int f = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+__device__ __forceinline__ void decode_frame(const float* s, int nb, const float* cent, float thr, int mode,
+                                             double* f0) {
   const int lane = threadIdx.x & 63;
-  if (f >= F) return;
-  const float* s = sal + (long long)f * nb;
   float best = -INFINITY;
   int bi = 0x7fffffff;
   double num = 0.0, den = 0.0;
@@ -161,6 +183,9 @@ __global__ void k_fcpe_decode(const float* sal, int F, int nb, const float* cent
   num = wave_sum(num);
   den = wave_sum(den);
   if (lane != 0) return;
+  // a frame with no value above -inf (all NaN) leaves bi at INT_MAX, and the window's `bi - 4 + j` then overflows:
+  // the compiler folds the clamp into max(bi, 4 - j) + (j - 4), which wraps to an index far below the row
+  bi = min(bi, nb - 1);
   if (mode == 0) {
     num = 0.0;
     den = 0.0;
@@ -171,7 +196,19 @@ __global__ void k_fcpe_decode(const float* sal, int F, int nb, const float* cent
     }
   }
   const float cents = (float)num / (float)den;
-  f0[f] = best <= thr ? 0.0 : (double)(10.f * exp2f(cents / 1200.f));
+  *f0 = best <= thr ? 0.0 : (double)(10.f * exp2f(cents / 1200.f));
+}
+__global__ void k_fcpe_decode(const float* sal, int F, int nb, const float* cent, float thr, int mode, double* f0) {
+  const int f = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (f >= F) return;
+  decode_frame(sal + (long long)f * nb, nb, cent, thr, mode, f0 + f);
+}
+// grid y = stream: its Fv[b] frames of the F-row slot, f0 rows of stride ldf
+__global__ void k_fcpe_decode_v(const float* sal, const int* Fv, int F, int nb, const float* cent, float thr, int mode,
+                                double* f0, long long ldf) {
+  const int f = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), b = blockIdx.y;
+  if (f >= Fv[b]) return;
+  decode_frame(sal + ((long long)b * F + f) * nb, nb, cent, thr, mode, f0 + b * ldf + f);
 }
 
 // FCPEF0Predictor.post_process (FCPE.py:877-902) on a raw track f0 [F]: e[i] = f0[nearest(i)] for i < n
@@ -254,21 +291,28 @@ hipError_t fcpe_dup_last_frame(float* mel, int B, int F, int C, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t fcpe_mel_tail_v(float* mel, int B, const int* Fv, int F, int F_min, int C, hipStream_t s) {
+  if (B < 1 || B > 65535 || F_min < 2 || F < F_min || C < 1 || !Fv) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_mel_tail_v, dim3(F - F_min + 1, B), dim3(TB), 0, s, mel, Fv, F, C);
+  return hipGetLastError();
+}
+
 hipError_t groupnorm_lrelu(float* x, int T, int C, int G, const float* gamma, const float* beta, float eps, float slope,
-                           double* ws, hipStream_t s, int B) {
+                           double* ws, hipStream_t s, int B, const int* Tv) {
   if (T < 1 || G < 1 || C % G || !ws || B < 1 || B > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_gn_stats, dim3(GN_TCHUNKS, G, B), dim3(256), 0, s, x, T, C, G, ws);
+  hipLaunchKernelGGL(k_gn_stats, dim3(GN_TCHUNKS, G, B), dim3(256), 0, s, x, T, C, G, ws, Tv);
   const long long n = (long long)T * (C / G);
   hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), G, B), dim3(256), 0, s, x, T,
-                     C, G, ws, gamma, beta, eps, slope);
+                     C, G, ws, gamma, beta, eps, slope, Tv);
   return hipGetLastError();
 }
 
 hipError_t glu_dwconv_swish(const float* x, int T, int C2, const float* w, const float* b, int K, int pad, float* y,
-                            hipStream_t s, int B) {
+                            hipStream_t s, int B, const int* Tv) {
   if (T < 1 || C2 % 64 || K < 1 || K > DW_MAXK || pad < 0 || pad >= K || B < 1 || B > 65535)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_glu_dw_swish, dim3(C2 / 64, (T + DW_T - 1) / DW_T, B), dim3(256), 0, s, x, T, C2, w, b, K, pad, y);
+  hipLaunchKernelGGL(k_glu_dw_swish, dim3(C2 / 64, (T + DW_T - 1) / DW_T, B), dim3(256), 0, s, x, T, C2, w, b, K, pad, y,
+                     Tv);
   return hipGetLastError();
 }
 
@@ -276,6 +320,13 @@ hipError_t fcpe_decode(const float* sal, int F, int nb, const float* cent, float
                        hipStream_t s) {
   if (F < 1 || nb < 1 || mode < 0 || mode > 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_fcpe_decode, dim3((F + 3) / 4), dim3(256), 0, s, sal, F, nb, cent, thr, mode, f0);
+  return hipGetLastError();
+}
+
+hipError_t fcpe_decode_v(const float* sal, int B, const int* Fv, int F, int nb, const float* cent, float thr, int mode,
+                         double* f0, long long ldf, hipStream_t s) {
+  if (B < 1 || B > 65535 || F < 1 || nb < 1 || mode < 0 || mode > 1 || ldf < F || !Fv) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fcpe_decode_v, dim3((F + 3) / 4, B), dim3(256), 0, s, sal, Fv, F, nb, cent, thr, mode, f0, ldf);
   return hipGetLastError();
 }
 

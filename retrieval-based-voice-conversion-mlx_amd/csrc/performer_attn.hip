@@ -27,6 +27,12 @@
 // Batch: B streams of one T per launch (grid z). Everything reduced over time -- ksum, ctx, the query's row maximum,
 // the denominator -- belongs to one (stream, head): the workspace holds ctx / ksum and the slabs' images per
 // (stream, head), and no load is clamped or reduced across a stream's rows. B = 1 is the single-utterance form.
+// Ragged: with Tv (a device array) stream b has Tv[b] <= T rows inside its T-row slot. The length is indexed by
+// blockIdx.z, so it is one scalar load and every branch on it is wave-uniform (the MFMAs sit inside them). Pass A ends
+// the stream's keys at Tv[b] and clamps its loads to row Tv[b] - 1; a slab wholly past Tv[b] loads nothing and writes
+// its zero image, so k_perf_combine adds the same slabs for every stream, the extra ones exact zeros: ctx / ksum, and
+// with them the output rows, are the B = 1 call's on that stream bit for bit. Pass B's waves past Tv[b] exit, rows past
+// Tv[b] are not stored.
 #include <cmath>
 
 #include "fcpe_kernels.h"
@@ -51,6 +57,7 @@ struct PerfArgs {
   int ld;
   const float* P;  // [M][64]
   int M, T, H;
+  const int* Tv;  // rows per stream (device), or null: T
   float c, c2, ratio;
 };
 
@@ -82,7 +89,8 @@ __global__ __launch_bounds__(256) void k_perf_kv(PerfArgs a, float* part_ctx, fl
   const int njt = (a.M + 15) / 16;
   const float* K = a.k + b * a.bs + h * a.hs;
   const float* V = a.v + b * a.bs + h * a.hs;
-  const int t_begin = slab * PA_SLAB, t_end = min(a.T, t_begin + PA_SLAB);
+  const int T = a.Tv ? a.Tv[b] : a.T;  // scalar: b is blockIdx.z
+  const int t_begin = slab * PA_SLAB, t_end = min(T, t_begin + PA_SLAB);
   f32x4 acc[PA_MAXJT][4];  // ctx^T tile (jj, dt): row d = 16 dt + 4 kq + r, column j = 16 (wave + 4 jj) + li
   float ks[PA_MAXJT];
 #pragma unroll
@@ -93,12 +101,12 @@ __global__ __launch_bounds__(256) void k_perf_kv(PerfArgs a, float* part_ctx, fl
   }
   for (int t0 = t_begin; t0 < t_end; t0 += 16) {
     f32x4 xa[4];
-    const float diag_li = load_rows(K, a.ld, t0, a.T, li, kq, a.c, a.c2, xa);
+    const float diag_li = load_rows(K, a.ld, t0, T, li, kq, a.c, a.c2, xa);
     float diag[4], va[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       diag[r] = __shfl(diag_li, 4 * kq + r, 64);  // row t0 + 4 kq + r
-      const int tv = min(t0 + 4 * kq + r, a.T - 1);
+      const int tv = min(t0 + 4 * kq + r, T - 1);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) va[r][dt] = V[(long long)tv * a.ld + 16 * dt + li];
     }
@@ -169,10 +177,11 @@ __global__ __launch_bounds__(256) void k_perf_out(PerfArgs a, const float* ctx, 
   const int h = blockIdx.y, b = blockIdx.z;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, kq = lane >> 4;
   const int t0 = (blockIdx.x * 4 + wave) * 16;
-  if (t0 >= a.T) return;
+  const int T = a.Tv ? a.Tv[b] : a.T;  // scalar: b is blockIdx.z
+  if (t0 >= T) return;
   const int njt = (a.M + 15) / 16;
   f32x4 xb[4];
-  const float diag = load_rows(a.q + b * a.bs + h * a.hs, a.ld, t0, a.T, li, kq, a.c, a.c2, xb);  // row t0 + li
+  const float diag = load_rows(a.q + b * a.bs + h * a.hs, a.ld, t0, T, li, kq, a.c, a.c2, xb);  // row t0 + li
   f32x4 dsh[PB_MAXJT];  // dash^T tile jt: row j = 16 jt + 4 kq + r, column t = t0 + li
   float mx = -INFINITY;
 #pragma unroll
@@ -216,7 +225,7 @@ __global__ __launch_bounds__(256) void k_perf_out(PerfArgs a, const float* ctx, 
     }
   }
   const float dinv = 1.f / (xor_sum16(den) + 1e-8f);
-  if (t0 + li < a.T) {
+  if (t0 + li < T) {
     float* y = out + b * out_bs + h * out_hs + (long long)(t0 + li) * out_ld + 4 * kq;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(y + 16 * dt) = o[dt] * dinv;
@@ -235,7 +244,7 @@ long long performer_ws_floats(int H, int T, int M, int B) {
 
 hipError_t performer_attention(const float* q, const float* k, const float* v, long long hs, int ld, int H, int T,
                                const float* P, int M, float* ws, float* out, long long out_hs, int out_ld,
-                               hipStream_t s, int B, long long bs, long long out_bs) {
+                               hipStream_t s, int B, long long bs, long long out_bs, const int* Tv) {
   if (H < 1 || T < 1 || M < 1 || M > PERFORMER_MAX_FEATURES || (ld & 3) || (hs & 3) || (out_ld & 3) || (out_hs & 3) ||
       B < 1 || B > 65535 || (bs & 3) || (out_bs & 3))
     return hipErrorInvalidValue;
@@ -253,6 +262,7 @@ hipError_t performer_attention(const float* q, const float* k, const float* v, l
   a.M = M;
   a.T = T;
   a.H = H;
+  a.Tv = Tv;
   a.c = 1.f / sqrtf(sqrtf((float)PD));  // 64^-0.25 (FCPE.py:185)
   a.c2 = a.c * a.c;
   a.ratio = (float)(1.0 / std::sqrt((double)M));  // M^-0.5 (FCPE.py:188)

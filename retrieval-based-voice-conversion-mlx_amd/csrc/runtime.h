@@ -311,6 +311,11 @@ int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B,
                        int64_t cap, float* sal_out, hipStream_t s);
 int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
                      double* f0, float* sal_out, int64_t cap, hipStream_t s);
+// the raw track for B inputs of nv[b] samples (host array) in one ragged pass: f0 row b (fcpe_frames(nv[b]) frames) at
+// f0 + b*ldf, its salience (optional) at sal_out + b*ld_sal*out_dims. Returns the longest row's frames. Equal lengths
+// are fcpe_forward_b and one row is fcpe_forward, unless `sizing` (the arena query sizes the ragged form).
+int64_t fcpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t ld, int B, float thr, int mode, double* f0,
+                       int64_t ldf, float* sal_out, int64_t ld_sal, hipStream_t s, bool sizing = false);
 // the decoders + post_process alone on salience [F][out_dims]
 int64_t fcpe_decode_run(Ctx& c, const float* sal, int64_t F, float thr, int mode, int interp_uv, int64_t pad_to,
                         double* f0, hipStream_t s);

@@ -10,6 +10,8 @@
 //   batch    fcpe_forward_b runs B streams of one length in one set of launches per layer (a realtime hop's f0 with
 //            rvcx_rt_desc::f0_method 1, rvcx_fcpe_b): activations [B][F][C], row-wise ops on the B F rows, everything
 //            padded or reduced over time per stream. fcpe_forward is its B = 1 case plus the interp_uv / pad_to tail
+//   ragged   fcpe_forward_v runs B utterances of different lengths through the same launches: activations
+//            [B][F_max][C], a device array of the rows' frame counts F_b in every kernel that pads or reduces over time
 #include <cmath>
 
 #include "model_build.h"
@@ -139,24 +141,15 @@ int fcpe_mel(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float* me
   return F;
 }
 
-// FCPEInfer.__call__ on B streams of n samples (row b at audio + b ld): f0 [B][F] (the raw track: zeros where
-// unvoiced), salience [B][F][out_dims] optional. Activations are [B][F][C] with the streams back to back, so
-// LayerNorm and every linear run once on the B F rows; what the network reduces or pads over time -- the mel's
-// framing, the k = 3 convs' zero padding (launch_conv's batch form), the GroupNorm statistics, the Performer's ctx /
-// ksum / row maximum / denominator, the depthwise conv's zero padding -- is per stream. B = 1 is fcpe_forward.
-int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float thr, int mode, double* f0,
-                       int64_t cap, float* sal_out, hipStream_t s) {
-  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
+// FCPE.forward (:657-665) on mel [B][F][n_mels] -> salience [B][F][out_dims]. dF (device, optional): stream b has
+// dF[b] <= F frames in its F-row slot and mel rows from dF[b] on are zero. The k = 3 convs then see the zero padding
+// of a run on that stream alone: stack.0 reads the zeroed mel rows, stack.3 the rows groupnorm_lrelu zeroes. The
+// attention, the GroupNorm statistics and the depthwise conv end at dF[b]. Rows past dF[b] of the other activations
+// hold whatever the row-wise ops make of them and never reach a valid row.
+static void fcpe_net(Ctx& c, const float* mel, int F, int B, const int* dF, float* sal, hipStream_t s) {
   const FcpeCfg& g = c.fcfg;
-  if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
-  if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
   const int C = g.n_chans, inner = g.n_heads * g.dim_head;
-  const int F = (int)fcpe_frames(c, n);
-  if (F > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(F) + " frames per stream");
-  const int R = B * F;  // rows of every row-wise op (fcpe_mel checks the range)
-  float* mel = c.buf<float>("fc.mel", (size_t)R * g.n_mels, s);
-  fcpe_mel(c, audio, n, ld, B, mel, s);
+  const int R = B * F;  // rows of every row-wise op (the callers check the range)
   // ---- input stack (:624-631): the k = 3 convs (zero pad 1) over each stream's own F rows
   float* x = c.buf<float>("fc.x", (size_t)R * C, s);
   float* x1 = c.buf<float>("fc.x1", (size_t)R * C, s);
@@ -164,7 +157,7 @@ int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B,
   launch_conv(c, conv1d(mel, g.n_mels, F, g.n_mels, c.W("fc.stack0.w"), C, 3, 1, 1, c.W("fc.stack0.b"), x1, C, F, B),
               false, s);
   double* gnws = c.buf<double>("fc.gnws", (size_t)B * 4 * FCPE_GN_CHUNKS * 2, s);
-  check(groupnorm_lrelu(x1, F, C, 4, c.W("fc.gn.g"), c.W("fc.gn.b"), 1e-5f, 0.01f, gnws, s, B), "fcpe_groupnorm");
+  check(groupnorm_lrelu(x1, F, C, 4, c.W("fc.gn.g"), c.W("fc.gn.b"), 1e-5f, 0.01f, gnws, s, B, dF), "fcpe_groupnorm");
   launch_conv(c, conv1d(x1, C, F, C, c.W("fc.stack3.w"), C, 3, 1, 1, c.W("fc.stack3.b"), x, C, F, B), false, s);
   // ---- PCmer (:270-283)
   float* qkv = c.buf<float>("fc.qkv", (size_t)R * 3 * inner, s);
@@ -178,7 +171,7 @@ int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B,
     launch_conv(c, lin(ln, C, R, C, c.W(dn(i, "qkv.w")), 3 * inner, c.W(dn(i, "qkv.b")), qkv, 3 * inner), false, s);
     check(performer_attention(qkv, qkv + inner, qkv + 2 * inner, g.dim_head, 3 * inner, g.n_heads, F,
                               c.W(dn(i, "proj")), g.n_feat, aws, att, g.dim_head, inner, s, B,
-                              (long long)F * 3 * inner, (long long)F * inner),
+                              (long long)F * 3 * inner, (long long)F * inner, dF),
           "performer_attention");
     {
       ConvArgs a = lin(att, inner, R, inner, c.W(dn(i, "out.w")), C, c.W(dn(i, "out.b")), x1, C);
@@ -192,7 +185,7 @@ int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B,
           "fcpe_ln");
     launch_conv(c, lin(ln, C, R, C, c.W(dn(i, "cf.pw1.w")), 4 * C, c.W(dn(i, "cf.pw1.b")), h4, 4 * C), false, s);
     check(glu_dwconv_swish(h4, F, 2 * C, c.W(dn(i, "cf.dw.w")), c.W(dn(i, "cf.dw.b")), g.conv_k, g.conv_k / 2, dw, s,
-                           B),
+                           B, dF),
           "fcpe_dwconv");
     {
       ConvArgs a = lin(dw, 2 * C, R, 2 * C, c.W(dn(i, "cf.pw2.w")), C, c.W(dn(i, "cf.pw2.b")), x, C);
@@ -204,14 +197,114 @@ int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B,
   }
   // ---- head (:663-665)
   check(layernorm_rows(x, nullptr, ln, c.W("fc.norm.g"), c.W("fc.norm.b"), R, C, 1e-5f, nullptr, s), "fcpe_ln");
-  float* sal = sal_out ? sal_out : c.buf<float>("fc.sal", (size_t)R * g.out_dims, s);
-  {
-    ConvArgs a = lin(ln, C, R, C, c.W("fc.dense.w"), g.out_dims, c.W("fc.dense.b"), sal, g.out_dims);
-    a.act = ACT_SIGMOID;
-    launch_conv(c, a, false, s);
-  }
+  ConvArgs a = lin(ln, C, R, C, c.W("fc.dense.w"), g.out_dims, c.W("fc.dense.b"), sal, g.out_dims);
+  a.act = ACT_SIGMOID;
+  launch_conv(c, a, false, s);
+}
+
+// FCPEInfer.__call__ on B streams of n samples (row b at audio + b ld): f0 [B][F] (the raw track: zeros where
+// unvoiced), salience [B][F][out_dims] optional. Activations are [B][F][C] with the streams back to back, so
+// LayerNorm and every linear run once on the B F rows; what the network reduces or pads over time -- the mel's
+// framing, the k = 3 convs' zero padding (launch_conv's batch form), the GroupNorm statistics, the Performer's ctx /
+// ksum / row maximum / denominator, the depthwise conv's zero padding -- is per stream. B = 1 is fcpe_forward.
+int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float thr, int mode, double* f0,
+                       int64_t cap, float* sal_out, hipStream_t s) {
+  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
+  const FcpeCfg& g = c.fcfg;
+  if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
+  if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
+  const int F = (int)fcpe_frames(c, n);
+  if (F > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(F) + " frames per stream");
+  float* mel = c.buf<float>("fc.mel", (size_t)B * F * g.n_mels, s);
+  fcpe_mel(c, audio, n, ld, B, mel, s);
+  float* sal = sal_out ? sal_out : c.buf<float>("fc.sal", (size_t)B * F * g.out_dims, s);
+  fcpe_net(c, mel, F, B, nullptr, sal, s);
   // the decoders are row-wise: B F rows, f0 [B][F]
-  check(fcpe_decode(sal, R, g.out_dims, c.W("fc.cent"), thr, mode, f0, s), "fcpe_decode");
+  check(fcpe_decode(sal, B * F, g.out_dims, c.W("fc.cent"), thr, mode, f0, s), "fcpe_decode");
+  return F;
+}
+
+// FCPEInfer.__call__ on B utterances of nv[b] samples (host array; row b at audio + b ld) in one launch set: row b has
+// F_b = fcpe_frames(nv[b]) frames inside [B][F_max][C]. Its f0 [F_b] lands at f0 + b ldf, its salience (optional) at
+// sal_out + b ld_sal out_dims; nothing is written past F_b. Per row:
+//   - the mel reflect-pads the row at its own end (samples past nv[b] are never read); its STFT frames past the row's
+//     own are computed on the zeros after it and overwritten: row F_b - 1 = a copy of row F_b - 2, rows from F_b on zero;
+//   - the network takes the rows' frame counts (fcpe_net); LayerNorm and every linear run once over the B F_max rows;
+//   - the decode stops at F_b.
+// Equal lengths are fcpe_forward_b, bit for bit, unless `sizing` (rvcx_workspace_bytes sizes the ragged form). A row of
+// the mel's zero-padding branch among rows of different lengths is refused: mel_forward's per-row form reflects.
+int64_t fcpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t ld, int B, float thr, int mode, double* f0,
+                       int64_t ldf, float* sal_out, int64_t ld_sal, hipStream_t s, bool sizing) {
+  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
+  if (B < 1 || B > 4096) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
+  const FcpeCfg& g = c.fcfg;
+  int64_t n_max = 0, n_min = INT64_MAX;
+  for (int b = 0; b < B; ++b) {
+    if (nv[b] < 1 || nv[b] > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
+    n_max = std::max(n_max, nv[b]);
+    n_min = std::min(n_min, nv[b]);
+  }
+  const bool equal = n_min == n_max;
+  if (ld < n_max && B > 1) throw Error(RVCX_E_INVALID, "fcpe: row stride shorter than the longest row");
+  const int64_t pl = (g.win - g.hop) / 2, pr = (g.win - g.hop + 1) / 2;
+  const bool ragged = B > 1 && (!equal || sizing);
+  // the zero-padding branch (pr >= n in fcpe_mel) is a whole-batch form only
+  if (ragged && std::max<int64_t>(pr, g.win - n_min - pl) >= n_min)
+    throw Error(RVCX_E_SHAPE, "fcpe: a row of " + std::to_string(n_min) +
+                                  " samples takes the mel's zero padding, which rows of different lengths do not run");
+  const int64_t F_max = fcpe_frames(c, n_max);
+  if (F_max > ldf) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(F_max) + " frames per row");
+  if (sal_out && F_max > ld_sal)
+    throw Error(RVCX_E_CAPACITY, "fcpe: salience needs " + std::to_string(F_max) + " frames per row");
+  if (!ragged) {
+    const int64_t F = F_max;
+    const bool f0_tight = ldf == F || B == 1, sal_tight = !sal_out || ld_sal == F || B == 1;
+    double* f0b = f0_tight ? f0 : c.buf<double>("fc.f0v", (size_t)B * F, s);
+    float* sb = sal_tight ? sal_out : c.buf<float>("fc.salv", (size_t)B * F * g.out_dims, s);
+    if (B == 1) {
+      fcpe_forward(c, audio, n_max, thr, mode, 0, 0, f0b, sb, F, s);
+    } else {
+      fcpe_forward_b(c, audio, n_max, ld, B, thr, mode, f0b, F, sb, s);
+    }
+    if (!f0_tight)
+      RVCX_HIP(hipMemcpy2DAsync(f0, (size_t)ldf * sizeof(double), f0b, (size_t)F * sizeof(double),
+                                (size_t)F * sizeof(double), B, hipMemcpyDeviceToDevice, s));
+    if (!sal_tight)
+      RVCX_HIP(hipMemcpy2DAsync(sal_out, (size_t)ld_sal * g.out_dims * sizeof(float), sb,
+                                (size_t)F * g.out_dims * sizeof(float), (size_t)F * g.out_dims * sizeof(float), B,
+                                hipMemcpyDeviceToDevice, s));
+    return F;
+  }
+  const MelSpec ms = mel_spec(g);
+  if ((int64_t)B * F_max > INT32_MAX / std::max(4 * g.n_chans, 2 * ms.nbin()))
+    throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  const int F = (int)F_max;
+  // the reflect branch: the STFT gives n / hop frames, one fewer than F_b, for every row
+  const int Fs = (int)((n_max + pl + pr - g.win) / g.hop + 1);
+  if (Fs != F - 1) throw Error(RVCX_E_SHAPE, "fcpe: unexpected framing");
+  // per-row lengths on device: n | F
+  std::vector<int32_t> hl(2 * (size_t)B);
+  int F_min = F;
+  for (int b = 0; b < B; ++b) {
+    hl[b] = (int32_t)nv[b];
+    hl[B + b] = (int32_t)fcpe_frames(c, nv[b]);
+    F_min = std::min(F_min, hl[B + b]);
+  }
+  int32_t* dl = c.buf<int32_t>("fc.lens", hl.size(), s);
+  RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
+  const int32_t *dn = dl, *dF = dl + B;
+  float* mel = c.buf<float>("fc.mel", (size_t)B * F * g.n_mels, s);
+  mel_forward(c, ms, "fc.", audio, n_max, ld, B, MelFrames{pl, pr, false, Fs, F, true}, mel, s, dn);
+  check(fcpe_mel_tail_v(mel, B, dF, F, F_min, g.n_mels, s), "fcpe_mel_tail");
+  float* sal = c.buf<float>("fc.sal", (size_t)B * F * g.out_dims, s);
+  fcpe_net(c, mel, F, B, dF, sal, s);
+  if (sal_out)
+    for (int b = 0; b < B; ++b)
+      RVCX_HIP(hipMemcpyAsync(sal_out + (size_t)b * ld_sal * g.out_dims, sal + (size_t)b * F * g.out_dims,
+                              (size_t)hl[B + b] * g.out_dims * sizeof(float), hipMemcpyDeviceToDevice, s));
+  check(fcpe_decode_v(sal, B, dF, F, g.out_dims, c.W("fc.cent"), thr, mode, f0, ldf, s), "fcpe_decode");
   return F;
 }
 

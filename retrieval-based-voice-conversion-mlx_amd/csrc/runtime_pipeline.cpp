@@ -215,13 +215,14 @@ int proposed_key(const std::vector<double>& f0, double threshold) {
 
 // f0_method of rvcx_pipeline_opts against the loaded models
 static void check_f0_method(const Ctx& c, const rvcx_pipeline_opts& o) {
-  if (o.f0_method < 0 || o.f0_method > 4)
+  if (o.f0_method < 0 || o.f0_method > 5)
     throw Error(RVCX_E_INVALID,
-                "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX), 2 (crepe, rvc/), 3 (fcpe) or 4 (rmvpe, ragged)");
+                "pipeline: f0_method must be 0 (rmvpe), 1 (crepe, MLX), 2 (crepe, rvc/), 3 (fcpe), 4 (rmvpe, ragged) or "
+                "5 (fcpe, ragged)");
   if (!c.scfg.f0) return;
   if ((o.f0_method == 1 || o.f0_method == 2) && !c.ready[RVCX_MODEL_CREPE])
     throw Error(RVCX_E_STATE, "pipeline: f0_method crepe but no CREPE weights finalized");
-  if (o.f0_method == 3) {
+  if (o.f0_method == 3 || o.f0_method == 5) {
     if (!c.ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "pipeline: f0_method fcpe but no FCPE weights finalized");
     if (c.fcfg.sr != 16000 || c.fcfg.hop != 160)  // the pipeline's pitch frames are 160 samples at 16 kHz
       throw Error(RVCX_E_SHAPE, "pipeline: the FCPE model must run at 16 kHz with hop_size 160");
@@ -289,6 +290,7 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
   check_pipeline_opts(c, opts, n);
   rvcx_pipeline_opts o = opts;
   if (o.f0_method == 4) o.f0_method = 0;  // one utterance: the ragged RMVPE pass is the single-row one
+  if (o.f0_method == 5) o.f0_method = 3;  // and the ragged FCPE pass likewise
   if (o.index_rate > 0 && c.ivf->view.d != c.scfg.emb_dim)
     throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension does not match the model's feature width");
   const int64_t W = 160;  // Pipeline.window
@@ -514,7 +516,8 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
 //   - f0: under f0_method 0 rows run through RMVPE's single-row forward, rows of equal length inside the batch together
 //     through the batched one, so a row's f0 is the single run's bit for bit; f0_method 4 runs all rows in one ragged
 //     pass (rmvpe_forward_v: a length per row in the mel's and the frames' reflect pads, the U-Net's zero padding and
-//     the BiGRU), equal to it up to summation order.
+//     the BiGRU), equal to it up to summation order. FCPE likewise: per row under f0_method 3 (bit for bit the single
+//     run's), all rows in one ragged pass under f0_method 5 (fcpe_forward_v), equal rows through fcpe_forward_b.
 //   - the generator runs over the common window [t_pad_tgt, Tv_max upp - t_pad_tgt) on z * mask, as the reference's
 //     own batched Synthesizer.infer does: a shorter row's last frames, within the generator's receptive field of its
 //     end, see the zeroed pad frames' activations where a run of that row alone sees the conv's zero padding. The trim
@@ -540,6 +543,9 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   rvcx_pipeline_opts o = opts;
   const bool ragged_f0 = o.f0_method == 4 && B > 1 && (!equal || sizing);
   if (o.f0_method == 4) o.f0_method = 0;
+  // f0_method 5: the same for FCPE, one row and (outside the arena query) no other case being method 3
+  const bool batch_fcpe = o.f0_method == 5 && B > 1;
+  if (o.f0_method == 5) o.f0_method = 3;
   const int E = c.scfg.emb_dim, upp = c.scfg.upp();
   if (!equal && o.t_pad_tgt < (int64_t)dec_margin_frames(c.scfg) * upp)
     throw Error(RVCX_E_INVALID, "pipeline_batch: rows of different lengths need t_pad_tgt >= " +
@@ -603,7 +609,10 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   int32_t* pitch = nullptr;
   float* pitchf = nullptr;
   if (guided) {
-    if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
+    if (batch_fcpe) {  // straight from the padded rows; equal lengths take the equal-length batch inside
+      fcpe_forward_v(c, pad32, mv.data(), ldm, B, o.fcpe_threshold > 0 ? o.fcpe_threshold : 0.006f, 0, f0, F_max, nullptr,
+                     0, s, sizing);
+    } else if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
       for (int b : order)
         f0_row(c, o, pad32 + (size_t)b * ldm, mv[b], f0 + (size_t)b * F_max, Fv[b], "pb.f0f", s);
     } else if (ragged_f0) {
@@ -763,7 +772,7 @@ int64_t pipeline_workspace_bytes(Ctx& c, int B, int64_t n, const rvcx_pipeline_o
     return carved;
   };
   int64_t need = measure(opts);
-  if (opts.f0_method == 3) {
+  if (opts.f0_method == 3 || opts.f0_method == 5) {
     // FCPE's scratch is carved in place of RMVPE's, which can be the larger: the size also holds the same call
     // with the default f0 method, so an arena sized for "fcpe" serves a caller that switches back
     rvcx_pipeline_opts o0 = opts;

@@ -189,6 +189,7 @@ SIG = {
     "rvcx_hubert_batch_v": (i32, [vp, vp, P(i64), i64, i32, i32, vp, i64, P(i64), vp]),
     "rvcx_rmvpe_batch": (i32, [vp, vp, i64, i64, i32, f32, vp, i64, P(i64), vp, vp]),
     "rvcx_rmvpe_batch_v": (i32, [vp, vp, P(i64), i64, i32, f32, vp, i64, P(i64), vp, i64, vp]),
+    "rvcx_fcpe_batch_v": (i32, [vp, vp, P(i64), i64, i32, f32, i32, vp, i64, P(i64), vp, i64, vp]),
     "rvcx_rt_default_desc": (i32, [P(RtDesc)]),
     "rvcx_rt_default_opts": (i32, [P(RtOpts)]),
     "rvcx_rt_create": (i32, [vp, P(RtDesc), P(vp)]),
@@ -224,6 +225,7 @@ TEST_SIG = {
     "rvcx_resblock_pair": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     "rvcx_performer_attention": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
     "rvcx_performer_attention_b": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
+    "rvcx_performer_attention_v": (i32, [vp, vp, vp, vp, i32, i32, P(i32), i32, vp, i32, vp, vp]),
     "rvcx_fcpe_mel": (i32, [vp, vp, i64, vp, i64, P(i64), vp]),
     "rvcx_set_dec_window": (i32, [vp, i32]),
     "rvcx_dec_margin_frames": (i32, [P(SynthDesc), P(i32)]),

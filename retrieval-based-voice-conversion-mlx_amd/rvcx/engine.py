@@ -265,6 +265,36 @@ class Engine(KernelTestMixin):
                                          f0.data_ptr(), _ptr(sal), self.stream()), "fcpe_b")
         return (f0, sal) if want_salience else f0
 
+    def fcpe_batch_v(self, audios, threshold: float = 0.006, decoder: str = "local_argmax",
+                     want_salience: bool = False):
+        """audios: a list of [N_b] arrays (at the model's sampling rate) of any lengths -> a list of the raw tracks f0
+        fp64 [N_b // hop + 1] on device (and the list of saliences [F_b, out_dims]), from one ragged pass over all rows
+        (rvcx_fcpe_batch_v: each row is `fcpe`'s on that row alone, up to summation order; equal lengths are
+        `fcpe_batch`'s bits, one row `fcpe`'s)."""
+        if self.fcpe_cfg is None:
+            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        t = self.torch
+        rows = [self._dev(a, t.float32).reshape(-1) for a in audios]
+        B = len(rows)
+        if B < 1:
+            return ([], []) if want_salience else []
+        ns = [int(r.numel()) for r in rows]
+        lda = max(ns)
+        a = t.zeros((B, lda), dtype=t.float32, device=self.device)
+        for b, r in enumerate(rows):
+            a[b, : ns[b]] = r
+        F, nb = self._fcpe_frames(lda), self.fcpe_cfg["out_dims"]
+        f0 = t.empty((B, F), dtype=t.float64, device=self.device)
+        sal = t.empty((B, F, nb), dtype=t.float32, device=self.device) if want_salience else None
+        F_arr = (ctypes.c_int64 * B)()
+        self._check(self.lib.rvcx_fcpe_batch_v(self.ctx, a.data_ptr(), (ctypes.c_int64 * B)(*ns), lda, B,
+                                               float(threshold), self._FCPE_DECODERS[decoder], f0.data_ptr(), F, F_arr,
+                                               _ptr(sal), F, self.stream()), "fcpe_batch_v")
+        f0s = [f0[b, : int(F_arr[b])] for b in range(B)]
+        if not want_salience:
+            return f0s
+        return f0s, [sal[b, : int(F_arr[b])] for b in range(B)]
+
     def fcpe_decode(self, salience, threshold: float = 0.006, decoder: str = "local_argmax", interp_uv: bool = False,
                     pad_to=None):
         """rvcx_fcpe_decode: the cents decoder (+ post_process) alone on salience [F][out_dims] -> f0 fp64."""

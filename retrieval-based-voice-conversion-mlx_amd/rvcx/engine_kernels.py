@@ -86,6 +86,23 @@ class KernelTestMixin:
                                                         self.stream()), "performer_attention_b")
         return out
 
+    def performer_attention_v(self, q, k, v, T, proj):
+        """performer_attention_batch for streams of different lengths in the same launches
+        (rvcx_performer_attention_v): q, k, v [B][H][max(T)][64], T the B row counts -> [B][H][max(T)][64]; stream b's
+        rows from T[b] on are neither read nor written (the output holds NaN there)."""
+        t = self.torch
+        q, k, v, pm = (self._dev(x, t.float32).contiguous() for x in (q, k, v, proj))
+        if q.dim() != 4 or q.shape[3] != 64 or k.shape != q.shape or v.shape != q.shape or pm.shape[1] != 64:
+            raise ValueError("performer_attention_v: q, k, v [B][H][T][64] and proj [M][64]")
+        B, H, Tm, _ = (int(x) for x in q.shape)
+        assert len(T) == B and max(T) == Tm
+        Tv = (ctypes.c_int32 * B)(*[int(x) for x in T])
+        out = t.full(q.shape, float("nan"), dtype=t.float32, device=self.device)
+        self._check(self.lib.rvcx_performer_attention_v(self.ctx, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, H, Tv, Tm,
+                                                        pm.data_ptr(), int(pm.shape[0]), out.data_ptr(),
+                                                        self.stream()), "performer_attention_v")
+        return out
+
     # ------------------------------------------------------------------ streaming, index build, RMVPE and decoder parts
     def rt_model_rows(self, group, rows: int, gated: bool):
         """The model rows [rows, frames * upp] of a StreamGroup's last hop before (gated False) or after the noise

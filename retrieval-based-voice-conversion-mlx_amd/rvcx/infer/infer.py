@@ -130,7 +130,10 @@ class RVCX:
                  rmvpe_path: Optional[str] = None, device: int = 0, semantics: str = "rvc", *,
                  synth_state: Optional[Mapping[str, np.ndarray]] = None, synth_cfg: Optional[SynthConfig] = None,
                  hubert_state: Optional[Mapping[str, np.ndarray]] = None,
-                 rmvpe_state: Optional[Mapping[str, np.ndarray]] = None, version: str = "v2"):
+                 rmvpe_state: Optional[Mapping[str, np.ndarray]] = None, version: str = "v2", fcpe_weights=None,
+                 fcpe_threshold: float = 0.006):
+        """fcpe_weights / fcpe_threshold: PipelineRVCX's (an FCPE checkpoint's path or its (state, config) pair, which
+        f0_method "fcpe" runs under semantics "rvc"; without it that method raises)."""
         self.config = config
         self.model_path = model_path
         if synth_state is None:
@@ -159,7 +162,7 @@ class RVCX:
         self.rmvpe_model = RMVPE0Predictor(self.engine)
         self.pipeline_config = config or Config()
         self.pipeline = PipelineRVCX(self.tgt_sr, self.pipeline_config, self.hubert_model, self.rmvpe_model,
-                                     semantics=semantics)
+                                     semantics=semantics, fcpe_weights=fcpe_weights, fcpe_threshold=fcpe_threshold)
 
     def convert(self, audio: np.ndarray, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75,
                 volume_envelope=1.0, protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, sid=0,
@@ -184,7 +187,7 @@ class RVCX:
         """`convert` over a list of 16 kHz utterances of any lengths -> the outputs in input order. Utterances of
         similar length share one batched pass (PipelineRVCX.pipeline_many: sorted by length, a batch filled while its
         shortest row is at least (1 - max_pad) of its longest, inputs above t_max converted alone). ragged_f0
-        (f0_method "rmvpe" only): the rows of a batch also share one ragged RMVPE pass."""
+        (f0_method "rmvpe" or "fcpe"): the rows of a batch also share one ragged pass of the pitch network."""
         from .pipeline import DEFAULT_BATCH, DEFAULT_MAX_PAD
 
         return self.pipeline.pipeline_many(

@@ -169,6 +169,13 @@ class FCPE:
             return self.engine.host(self.engine.fcpe(a, threshold)).astype(np.float32)
         return self.engine.host(self.engine.rmvpe(a, threshold * 5))
 
+    def get_f0_batch(self, audios, f0_min: float = 50.0, f0_max: float = 1100.0, threshold: float = 0.006, **kw):
+        """get_f0 over a list of utterances of any lengths in one ragged pass -> the list of f0 arrays."""
+        rows = [_np(a).reshape(-1).astype(np.float32) for a in audios]
+        if self.network:
+            return [self.engine.host(f).astype(np.float32) for f in self.engine.fcpe_batch_v(rows, threshold)]
+        return [self.engine.host(f) for f in self.engine.rmvpe_batch_v(rows, threshold * 5)]
+
 
 class PitchExtractor:
     """rvc_mlx/lib/mlx/pitch_extractors.py PitchExtractor (:19-216) for the methods this path runs on device:

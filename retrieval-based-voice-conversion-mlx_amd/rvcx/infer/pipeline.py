@@ -267,19 +267,19 @@ class PipelineRVCX:
         utterance above t_max goes through `pipeline` alone (the batched pass takes single-chunk rows). batch = 1 is
         the per-utterance loop. Batch k draws its noise from seed + k; noise_fn(i, T) -> (eps_z [inter, T], eps_src
         [T * upp]) injects utterance i's noise instead (T its synthesizer frames), as the tests do.
-        ragged_f0 (f0_method "rmvpe" only, else ValueError): the rows of a batch share one ragged RMVPE pass
-        (rvcx_pipeline_opts.f0_method 4) instead of one pass per row; a row's f0 then equals the per-row pass up to
-        summation order, not bit for bit."""
+        ragged_f0 (f0_method "rmvpe" or "fcpe", else ValueError): the rows of a batch share one ragged pass of the pitch
+        network (rvcx_pipeline_opts.f0_method 4 for RMVPE, 5 for the FCPE network) instead of one pass per row; a row's
+        f0 then equals the per-row pass up to summation order, not bit for bit."""
         from ..offline import bucket
 
-        if ragged_f0 and f0_method != "rmvpe":
-            raise ValueError(f'ragged_f0 runs RMVPE: f0_method must be "rmvpe", not {f0_method!r}')
+        if ragged_f0 and f0_method not in ("rmvpe", "fcpe"):
+            raise ValueError(f'ragged_f0 runs RMVPE or FCPE: f0_method must be "rmvpe" or "fcpe", not {f0_method!r}')
 
         eng, opts = self._pipeline_opts(model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance,
                                         volume_envelope, version, protect, f0_autotune, f0_autotune_strength,
                                         proposed_pitch, proposed_pitch_threshold)
-        if ragged_f0:
-            opts.f0_method = 4
+        if ragged_f0:  # "fcpe" is method 3 with its network loaded, method 0 as the MLX port's RMVPE fallback
+            opts.f0_method = 5 if int(opts.f0_method) == 3 else 4
         audios = [np.asarray(a, dtype=np.float64).reshape(-1) for a in audios]
         outs = [None] * len(audios)
         upp = eng.upp

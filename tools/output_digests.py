@@ -8,7 +8,8 @@ pipeline forms for f0_method 0 / 2 / 3 under autotune and under proposed pitch a
 pipeline's salience, and the ragged forms: HuBERT over rows of five lengths, the pipeline over rows of three lengths
 (plain and with a volume envelope) and over two equal rows, RMVPE over rows of five lengths in one ragged pass and the
 ragged pipeline with it (f0_method 4). Then, as plain integers, Engine.workspace_bytes of five calls: the arena query
-runs the pipelines in their sizing form.
+runs the pipelines in their sizing form. Last, FCPE over rows of five lengths in one ragged pass, the ragged pipeline
+with it (f0_method 5) and its arena query.
 
     python tools/output_digests.py > digests.txt
 """
@@ -126,6 +127,16 @@ def main():
             tag = "".join(f" {k}={v}" for k, v in kw.items())
             need = eng.workspace_bytes(n, B=B, opts=eng.pipeline_opts(**kw))
             print(f"workspace_bytes B={B} n={n}{tag}: {need}", flush=True)
+    if "rvcx_fcpe_batch_v" in _lib.exported_symbols():  # a library from before the ragged FCPE pass ends here
+        rows = [synthetic.speech_like(n, seed=70 + i).astype(f32) for i, n in
+                enumerate((1000, 2400, 13920, 20480, 48000))]
+        f0s, sals = eng.fcpe_batch_v(rows, want_salience=True)
+        show("fcpe_batch_v 5 rows", *f0s, *sals)
+        kw = {"t_pad": 4800, "t_pad_tgt": 14400, "f0_method": 5}
+        ys, f0s = eng.pipeline_batch_v(ragged, eng.pipeline_opts(pitch=2.0, **kw), sids=[0, 3, 7, 0], seed=3, want_f0=True)
+        show("pipeline_batch_v ragged f0_method=5", *ys, *f0s)
+        need = eng.workspace_bytes(40000, B=4, opts=eng.pipeline_opts(**kw))
+        print(f"workspace_bytes B=4 n=40000{''.join(f' {k}={v}' for k, v in kw.items())}: {need}", flush=True)
     eng.close()
 
 
