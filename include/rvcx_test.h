@@ -2,9 +2,9 @@
  * rvcx — kernel-level entry points for the numerics tests. Exported from librvcx.so beside the public C ABI
  * (include/rvcx.h) but not part of it: a product links rvcx.h alone, and nothing there refers to a declaration here.
  * Every entry that exists for the tests or for A/B timing lives in this header: the single kernels (convs, attention,
- * ResBlock pair, Performer, k-means, BiGRU, harmonic source), the planner query and the per-context switches that only
- * comparisons use (rvcx_set_conv_math, rvcx_set_dec_window). Conventions as in rvcx.h (device pointers, the call is
- * asynchronous on `stream`, rvcx_status returned, rvcx_last_error for the message).
+ * ResBlock pair, Performer, k-means, BiGRU, harmonic source, RefineGAN's three), the planner query and the per-context
+ * switches that only comparisons use (rvcx_set_conv_math, rvcx_set_dec_window). Conventions as in rvcx.h (device
+ * pointers, the call is asynchronous on `stream`, rvcx_status returned, rvcx_last_error for the message).
  */
 #ifndef RVCX_TEST_H_
 #define RVCX_TEST_H_
@@ -248,6 +248,28 @@ int rvcx_gru_bidir_v(rvcx_ctx* ctx, const float* d_gi, int B, const int* T, cons
  * finalized pitch-guided synthesizer with one of these two decoders. */
 int rvcx_dec_source(rvcx_ctx* ctx, int B, int T, const float* d_f0, const float* d_eps_src, uint64_t seed, float* d_har,
                     void* stream);
+
+/* The three elementwise kernels of the RefineGAN decoder alone (csrc/refinegan.hip), time-major rows as the decoder
+ * holds them. Extents are checked before anything is launched: a null pointer or a count below 1 is RVCX_E_INVALID, a
+ * geometry the kernel does not serve RVCX_E_SHAPE.
+ *
+ * rvcx_rg_resample_dw: torchaudio's kaiser-sinc resample(orig -> 1) on given taps (refinegan.py:410-419):
+ *   y[b][t][c] = sum_k x[b][t orig + k - width][c] ker[k], zero outside [0, T_in); d_x [B][T_in][C], d_ker [K],
+ *   K = 2 width + orig <= 8192 (the taps sit in LDS), d_y [B][T_out][C], 1 <= T_out <= ceil(T_in / orig). */
+int rvcx_rg_resample_dw(rvcx_ctx* ctx, const float* d_x, int B, int T_in, int C, const float* d_ker, int orig, int width,
+                        float* d_y, int T_out, void* stream);
+
+/* rvcx_rg_lerp_up_cat: y[b][t][0:C] = nn.Upsample(scale_factor = rate, mode "linear")(leaky ReLU(x, slope)) at t,
+ * y[b][t][C:C + Cd] = skip[b][t] (refinegan.py:426-429): d_x [B][T] rows of ldx >= C floats, d_skip [B][T rate][Cd],
+ * d_y [B][T rate] rows of ldy >= C + Cd floats (columns from C + Cd on are not written). */
+int rvcx_rg_lerp_up_cat(rvcx_ctx* ctx, const float* d_x, int B, int T, int C, int ldx, int rate, float slope,
+                        const float* d_skip, int Cd, float* d_y, int ldy, void* stream);
+
+/* rvcx_rg_adain: v = leaky ReLU(x + eps w[c], slope) (AdaIN, refinegan.py:74-94): d_x, d_y [B][T][C], d_w [C], d_eps
+ * in the reference's layout [B][C][T] (NULL: N(0, 1) drawn from `seed` at the same index); mode 0: y = v, 1: y += v,
+ * 2: y = (y + v) / div (div != 0). */
+int rvcx_rg_adain(rvcx_ctx* ctx, const float* d_x, int B, int T, int C, const float* d_w, const float* d_eps,
+                  uint64_t seed, float slope, float* d_y, int mode, float div, void* stream);
 
 #ifdef __cplusplus
 }

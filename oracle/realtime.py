@@ -210,7 +210,7 @@ class OracleVoiceChanger:
                 feats = feats * pitchff.unsqueeze(-1) + feats0 * (1 - pitchff.unsqueeze(-1))
             T = feats.shape[1]
             eps_z = self.noise_fn((1, self.sc.inter_channels, T), "z")
-            eps_src = self.noise_fn((1, T * self.sc.upp), "src")
+            eps_src = self.noise_fn((1, osynth.src_noise_floats(self.sc, 1, T)), "src")
             out = osynth.synth_infer(self.sw, self.sc, feats.float(), torch.tensor([p_len]).long(), pitch,
                                      pitchf.float(), self.sid, eps_z, eps_src)[0][0, 0]
             out = torch.clip(out, -1.0, 1.0)

@@ -2,8 +2,11 @@
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py). Functional torch-CPU
 restatement over a fused-weight dict ``w`` (reference state-dict names): fp32 as
-the reference runs it; the HiFi-GAN-NSF path follows the dtype of ``w`` and the
-inputs, so it also runs in float64 (tests/parity_anchor.py).
+the reference runs it; every path (HiFi-GAN-NSF, no-f0, MRF, RefineGAN) follows the
+dtype of ``w`` and the inputs, so it also runs in float64 (tests/parity_anchor.py).
+The MRF / RefineGAN harmonic source and RefineGAN's linear f0 upsampling stay
+float32 on purpose (harmonic_source); RefineGAN's resample kernel is built in the
+waveform's dtype (oracle.realtime.functional_resample).
 """
 from __future__ import annotations
 
@@ -323,6 +326,16 @@ def refinegan_noise_sizes(cfg, B: int, T: int):
         ch, t = ch // 2, t * r
         sizes += [B * ch * t] * 6
     return sizes
+
+
+def src_noise_floats(cfg, B: int, T: int) -> int:
+    """Floats of the decoder's flat source noise for B rows of T frames (the C-ABI layouts of include/rvcx.h): NSF
+    [B][T upp]; MRF [B][T upp][9] and [B][9] initial phases; RefineGAN every draw of refinegan_noise_sizes."""
+    voc = getattr(cfg, "vocoder", "HiFi-GAN")
+    if voc == "RefineGAN":
+        return sum(refinegan_noise_sizes(cfg, B, T))
+    H = 9 if voc == "MRF HiFi-GAN" else 1
+    return B * T * cfg.upp * H + (B * H if voc != "HiFi-GAN" else 0)
 
 
 def refinegan_generator(w, cfg, mel: Tensor, f0: Tensor, g: Tensor, eps_src: Tensor) -> Tensor:

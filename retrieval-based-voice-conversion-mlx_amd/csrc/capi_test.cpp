@@ -490,6 +490,44 @@ int rvcx_dec_source(rvcx_ctx* ctx, int B, int T, const float* d_f0, const float*
   });
 }
 
+int rvcx_rg_resample_dw(rvcx_ctx* ctx, const float* d_x, int B, int T_in, int C, const float* d_ker, int orig, int width,
+                        float* d_y, int T_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_x || !d_ker || !d_y || B < 1 || T_in < 1 || C < 1 || orig < 1 || width < 0 || T_out < 1)
+      throw Error(RVCX_E_INVALID, "rvcx_rg_resample_dw: bad argument");
+    const int64_t K = 2 * (int64_t)width + orig;
+    if (K > 8192 || T_out > ((int64_t)T_in + orig - 1) / orig || (int64_t)B * T_in * C > INT32_MAX)
+      throw Error(RVCX_E_SHAPE, "rvcx_rg_resample_dw: at most 8192 taps, T_out <= ceil(T_in / orig), 2^31 elements");
+    set_device(ctx);
+    check(resample_dw(d_x, B, T_in, C, d_ker, (int)K, orig, width, d_y, T_out, static_cast<hipStream_t>(stream)),
+          "resample_dw");
+  });
+}
+
+int rvcx_rg_lerp_up_cat(rvcx_ctx* ctx, const float* d_x, int B, int T, int C, int ldx, int rate, float slope,
+                        const float* d_skip, int Cd, float* d_y, int ldy, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_x || !d_skip || !d_y || B < 1 || T < 1 || C < 1 || Cd < 1 || rate < 1)
+      throw Error(RVCX_E_INVALID, "rvcx_rg_lerp_up_cat: bad argument");
+    if (ldx < C || ldy < (int64_t)C + Cd || (int64_t)B * T * rate * ldy > INT32_MAX || (int64_t)B * T * ldx > INT32_MAX)
+      throw Error(RVCX_E_SHAPE, "rvcx_rg_lerp_up_cat: ldx >= C, ldy >= C + Cd, 2^31 elements");
+    set_device(ctx);
+    check(lerp_up_cat(d_x, B, T, C, ldx, rate, slope, d_skip, Cd, d_y, ldy, static_cast<hipStream_t>(stream)),
+          "lerp_up_cat");
+  });
+}
+
+int rvcx_rg_adain(rvcx_ctx* ctx, const float* d_x, int B, int T, int C, const float* d_w, const float* d_eps,
+                  uint64_t seed, float slope, float* d_y, int mode, float div, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_x || !d_w || !d_y || B < 1 || T < 1 || C < 1 || mode < 0 || mode > 2 || (mode == 2 && div == 0.f))
+      throw Error(RVCX_E_INVALID, "rvcx_rg_adain: bad argument");
+    if ((int64_t)B * T * C > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_rg_adain: at most 2^31 elements");
+    set_device(ctx);
+    check(adain(d_x, B, T, C, d_w, d_eps, seed, slope, d_y, mode, div, static_cast<hipStream_t>(stream)), "adain");
+  });
+}
+
 int rvcx_rt_model_rows(rvcx_ctx* ctx, rvcx_rt* rt, int gated, float* d_dst, int64_t ld, void* stream) {
   return guard(ctx, [&] {
     if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_model_rows: null stream group");

@@ -237,6 +237,9 @@ TEST_SIG = {
     "rvcx_gru_bidir": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     "rvcx_gru_bidir_v": (i32, [vp, vp, i32, P(i32), vp, vp, vp, vp, vp, i64, vp]),
     "rvcx_dec_source": (i32, [vp, i32, i32, vp, vp, u64, vp, vp]),
+    "rvcx_rg_resample_dw": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp]),
+    "rvcx_rg_lerp_up_cat": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, i32, vp]),
+    "rvcx_rg_adain": (i32, [vp, vp, i32, i32, i32, vp, vp, u64, f32, vp, i32, f32, vp]),
 }
 
 EXPORTS = list(SIG)

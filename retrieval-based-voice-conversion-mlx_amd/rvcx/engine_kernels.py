@@ -183,6 +183,54 @@ class KernelTestMixin:
                     "dec_source")
         return out
 
+    # ------------------------------------------------------------------ RefineGAN's elementwise kernels
+    def _f32_on_device(self, who, **tensors):
+        t = self.torch
+        for name, v in tensors.items():
+            if v is not None and not (isinstance(v, t.Tensor) and v.dtype == t.float32 and v.device == self.device):
+                raise ValueError(f"{who}: {name} must be a float32 tensor on {self.device}")
+
+    def rg_resample_dw(self, x, ker, orig: int, width: int, y):
+        """RefineGAN's kaiser-sinc downsampling kernel alone (rvcx_rg_resample_dw, include/rvcx_test.h): x
+        [B][T_in][C], ker [2 width + orig] -> y [B][T_out][C], written in place. Every operand is a contiguous float32
+        device tensor passed as it is (y may be a view into a larger guard buffer)."""
+        self._f32_on_device("rg_resample_dw", x=x, ker=ker, y=y)
+        B, T_in, C = (int(v) for v in x.shape)
+        if not (x.is_contiguous() and y.is_contiguous() and ker.numel() == 2 * width + orig and
+                tuple(y.shape[::2]) == (B, C)):
+            raise ValueError("rg_resample_dw: x [B][T_in][C], ker [2 width + orig], y [B][T_out][C], contiguous")
+        self._check(self.lib.rvcx_rg_resample_dw(self.ctx, x.data_ptr(), B, T_in, C, ker.data_ptr(), int(orig),
+                                                 int(width), y.data_ptr(), int(y.shape[1]), self.stream()),
+                    "rg_resample_dw")
+        return y
+
+    def rg_lerp_up_cat(self, x, C: int, rate: int, slope: float, skip, y):
+        """RefineGAN's upsample + concat kernel alone (rvcx_rg_lerp_up_cat): x [B][T][ldx] (columns 0..C read), skip
+        [B][T rate][Cd] -> y [B][T rate][ldy], columns 0..C + Cd written in place."""
+        self._f32_on_device("rg_lerp_up_cat", x=x, skip=skip, y=y)
+        B, T, ldx = (int(v) for v in x.shape)
+        Cd, ldy = int(skip.shape[2]), int(y.shape[2])
+        if not (x.is_contiguous() and skip.is_contiguous() and y.is_contiguous() and
+                tuple(skip.shape[:2]) == (B, T * rate) == tuple(y.shape[:2])):
+            raise ValueError("rg_lerp_up_cat: x [B][T][ldx], skip [B][T rate][Cd], y [B][T rate][ldy], contiguous")
+        self._check(self.lib.rvcx_rg_lerp_up_cat(self.ctx, x.data_ptr(), B, T, int(C), ldx, int(rate), float(slope),
+                                                 skip.data_ptr(), Cd, y.data_ptr(), ldy, self.stream()),
+                    "rg_lerp_up_cat")
+        return y
+
+    def rg_adain(self, x, w, eps, y, slope: float = 0.2, mode: int = 0, div: float = 1.0, seed: int = 0):
+        """RefineGAN's AdaIN kernel alone (rvcx_rg_adain): x, y [B][T][C], w [C], eps [B][C][T] or None (drawn from
+        `seed`); mode 0 store, 1 add, 2 (y + v) / div, y written in place."""
+        self._f32_on_device("rg_adain", x=x, w=w, eps=eps, y=y)
+        B, T, C = (int(v) for v in x.shape)
+        if not (x.is_contiguous() and y.is_contiguous() and tuple(y.shape) == (B, T, C) and w.numel() == C and
+                (eps is None or (eps.is_contiguous() and tuple(eps.shape) == (B, C, T)))):
+            raise ValueError("rg_adain: x, y [B][T][C], w [C], eps [B][C][T], contiguous")
+        self._check(self.lib.rvcx_rg_adain(self.ctx, x.data_ptr(), B, T, C, w.data_ptr(), _ptr(eps),
+                                           ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(slope), y.data_ptr(),
+                                           int(mode), float(div), self.stream()), "rg_adain")
+        return y
+
     # ------------------------------------------------------------------ convs, attention, ResBlock pair
     def conv1d(self, x, w, bias=None, dilation: int = 1, padding: int = 0, stride: int = 1, math: str = "default"):
         """torch.nn.functional.conv1d(x.T[None], w, bias, stride, padding, dilation)[0].T on the device kernel:

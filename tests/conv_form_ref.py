@@ -64,6 +64,22 @@ def _rb(name, C, epi, T_out, routes=ALL6, B=3, wspread=False):
     return _c(name, "ResBlock convs batched (ADVICE r6; residuals.py:71-80)", routes, **kw)
 
 
+# The rg.* rows' routes as rvcx_conv_plan admits them (admitted_routes below; tests/test_conv_form_ref_cpu.py holds the
+# table to the planner): one input channel runs on the one-thread-per-output kernel alone, C_in = 16 and 80 are no
+# multiple of the streamed kernels' 32-channel step, 3 steps are too few for the LDS-staged split, and the
+# weight-stationary kernel takes none of these (7 or 11 taps, or C outside {64, 128}).
+LDS3 = ("policy", "f32", "emu")
+RG_ROUTES = {"rg.pre": ("policy",), "rg.down": LDS3, "rg.down_last": ALL5, "rg.cond": ALL5, "rg.mel": ALL5,
+             "rg.up_in640": ALL5, "rg.up_in80": LDS3, "rg.rb_c1": ALL5, "rg.rb_c2": ALL5,
+             "rg.rb32_c1": ("policy", "f32", "wsb", "gs")}
+
+# the family the size policy picks per rg.* row (csrc/conv_dispatch.hip conv_plan at these shapes); every family a
+# RefineGAN forward launches must be among them (tests/test_gpu_refinegan.py reads the launched families)
+RG_POLICY = {"rg.pre": "conv_tiny_kernel", "rg.down": "conv_emu_kernel", "rg.down_last": "conv_gs16_kernel",
+             "rg.cond": "conv_gs16_kernel", "rg.mel": "conv_gs16_kernel", "rg.up_in640": "conv_gs16_kernel",
+             "rg.up_in80": "conv_emu_kernel", "rg.rb_c1": "conv_gs16_kernel", "rg.rb_c2": "conv_gs16_kernel",
+             "rg.rb32_c1": "conv_gemm_kernel"}
+
 CASES = [
     _c("te.emb_phone", "runtime_synth.cpp:639", ALL5, T_in=150, C_in=768, N=192, alpha=ALPHA192, res="pre",
        act=LRELU, slope=0.1, mask=True, flat=(75, 41)),
@@ -110,6 +126,28 @@ CASES = [
     _c("rm.mel", "runtime_fe.cpp:671", ALL5, T_in=100, C_in=544, N=128, act=LOGCLAMP, slope=1e-5, bias=False,
        nonneg=True),
     _c("rm.fc", "runtime_fe.cpp:637", ALL5, T_in=100, C_in=512, N=360, act=SIGMOID),
+    # The RefineGAN decoder's launch_conv sites (runtime_refinegan.cpp), forms no other site issues: one input channel
+    # with unit row stride, the output written into the right half of the 512-wide concat, B entries of one row, C_in =
+    # 80 (no multiple of 32), 11 taps at dilation 5 on a T_in barely past their 50-row reach, and the ResBlock's second
+    # conv adding the buffer it writes (m = 1: r_in == dst). Routes: "policy" and every forced route rvcx_conv_plan
+    # admits for the form (RG_REFUSED holds the others; test_gpu_conv_forms.py shows each one refused, not rerouted).
+    _c("rg.pre", "runtime_refinegan.cpp:122", RG_ROUTES["rg.pre"], B=2, T_in=203, C_in=1, ldx=1, N=16, taps=7, pad=3),
+    _c("rg.down", "runtime_refinegan.cpp:142", RG_ROUTES["rg.down"], B=2, T_in=101, C_in=16, N=32, taps=7, pad=3),
+    _c("rg.down_last", "runtime_refinegan.cpp:142", RG_ROUTES["rg.down_last"], B=2, T_in=70, C_in=128, N=256, taps=7,
+       pad=3, ldy=512, y_col0=256),
+    _c("rg.cond", "runtime_refinegan.cpp:154", RG_ROUTES["rg.cond"], B=3, T_in=1, C_in=256, N=256),
+    _c("rg.mel", "runtime_refinegan.cpp:162", RG_ROUTES["rg.mel"], B=2, T_in=70, C_in=192, N=256, taps=7, pad=3,
+       pre_mask=True, lengths=(70, 41), res="pre", res_bcast=True, ldy=512),
+    _c("rg.up_in640", "runtime_refinegan.cpp:195", RG_ROUTES["rg.up_in640"], B=2, T_in=70, C_in=640, N=256, taps=7,
+       pad=3),
+    _c("rg.up_in80", "runtime_refinegan.cpp:195", RG_ROUTES["rg.up_in80"], B=2, T_in=131, C_in=80, N=32, taps=7,
+       pad=3),
+    _c("rg.rb_c1", "runtime_refinegan.cpp:216", RG_ROUTES["rg.rb_c1"], B=2, T_in=60, C_in=64, N=64, taps=11, dil=5,
+       pad=25, pre_act=LRELU, pre_slope=0.2, act=LRELU, slope=0.2),
+    _c("rg.rb_c2", "runtime_refinegan.cpp:224", RG_ROUTES["rg.rb_c2"], B=2, T_in=60, C_in=64, N=64, taps=11, pad=5,
+       res="post", res_inplace=True),
+    _c("rg.rb32_c1", "runtime_refinegan.cpp:216", RG_ROUTES["rg.rb32_c1"], B=2, T_in=131, C_in=32, N=32, taps=3, dil=5,
+       pad=5, pre_act=LRELU, pre_slope=0.2, act=LRELU, slope=0.2),
     # The edge forms of the LDS-staged families' shared gather (csrc/conv_lds.h), which no runtime site reaches (each
     # has C_in % 4 == 0 and 16-byte aligned rows): the scalar channel tail with a last chunk padded by zero channels
     # and a partial N tile, under a leaky-ReLU pre-activation and a row mask over non-zero rows (the mask applies to
@@ -146,8 +184,11 @@ def tiny(c):
         t["nz"] = dict(u=2, C=2, stride=c["nz"]["stride"])
     t["pad"] = min(c["pad"], (t["taps"] - 1) * c["dil"])
     # keep the relation of T_out to the natural length (rm.stft and the ConvTranspose phases leave input rows unused)
-    t["T_in"] = (T_out - 1) * c["stride"] + (t["taps"] - 1) * c["dil"] + 1 - 2 * t["pad"] + (
-        1 if c["T_out"] < (c["T_in"] + 2 * c["pad"] - c["dil"] * (c["taps"] - 1) - 1) // c["stride"] + 1 else 0)
+    short = 1 if c["T_out"] < (c["T_in"] + 2 * c["pad"] - c["dil"] * (c["taps"] - 1) - 1) // c["stride"] + 1 else 0
+    t_in = lambda: (T_out - 1) * c["stride"] + (t["taps"] - 1) * c["dil"] + 1 - 2 * t["pad"] + short  # noqa: E731
+    if t_in() < 1:  # a "same" conv whose padding is half its reach (rg.rb_c1: dilation 5): full padding leaves no input
+        t["pad"] = (t["taps"] - 1) * c["dil"] // 2
+    t["T_in"] = t_in()
     if c["lengths"]:
         t["lengths"] = (t["T_in"], max(t["T_in"] - 3, 1))
     if c["flat"]:
@@ -459,6 +500,57 @@ def mutate(d, c, mut):
         d["x"] = x
         return d, None
     return d, mut
+
+
+# ----------------------------------------------------------------- what the planner admits (host only)
+# rvcx_conv1d_ex's route table (csrc/capi_test.cpp): the arithmetic, a static weight, the forced family, the family the
+# launch has to get
+ROUTE_PLAN = {"policy": (0, 1, None, None), "f32": (1, 0, None, "conv_gemm_kernel"), "emu": (2, 0, None, "conv_emu_kernel"),
+              "wsb": (3, 1, "conv_wsb16_kernel", None), "gs": (3, 1, "conv_gs16_kernel", None),
+              "wst": (3, 1, "conv_wst16_kernel", None)}
+
+
+def admitted_routes(c, no_splitk=False):
+    """{route: kernel family} for every route of rvcx_conv1d_ex that admits case c, asked of rvcx_conv_plan on the
+    host (no context, no GPU) with the strides tests/test_gpu_conv_forms.py launches: a route is refused when no family
+    admits the form under it or the family is not the route's own. Plain forms only (no gate, LayerNorm, noise)."""
+    import ctypes
+
+    from rvcx import _lib
+
+    assert not (c["gate"] or c["ln"] or c["nz"] or c["G"] > 1)
+    lib, L = _lib.load(), layout(c)
+    kinds = {}
+    for i in range(64):
+        n = lib.rvcx_profile_kind_name(i)
+        if n:
+            kinds[n.decode()] = i
+    out = {}
+    for route, (math, stat, force, expect) in ROUTE_PLAN.items():
+        d = _lib.ConvTestDesc()
+        d.x, d.y, d.w = 0x100000 + 4 * c["x_col0"], 0x200000 + 4 * c["y_col0"], 0x300000  # read for alignment alone
+        d.bias = 0x400000 if c["bias"] else None
+        if c["res"]:
+            d.res = d.y if c["res_inplace"] else 0x500000
+            d.res_mode = {"pre": RES_ADD_PRE, "post": RES_ADD_POST, "rsub": RES_RSUB_POST}[c["res"]]
+            d.ldr, d.res_bs = L["ldr"], L["res_bs"]
+        if c["mask"]:
+            d.mask, d.mask_bs = 0x600000, c["T_out"]
+        if c["pre_mask"]:
+            d.pre_mask, d.pre_mask_bs = 0x700000, c["T_in"]
+        for k in ("T_in", "C_in", "N", "taps", "dil", "pad", "stride", "T_out", "pre_act", "act"):
+            setattr(d, k, c[k])
+        d.ldx, d.ldy, d.batch, d.batch_inner, d.x_bs, d.y_bs = L["ldx"], L["ldy"], c["B"], 1, L["x_bs"], L["y_bs"]
+        d.pre_slope, d.slope, d.alpha, d.acc_div, d.acc_mode = c["pre_slope"], c["slope"], c["alpha"], c["acc_div"], c["acc"]
+        d.no_splitk = 1 if no_splitk else 0
+        got = [ctypes.c_int(-1) for _ in range(4)]
+        rc = lib.rvcx_conv_plan(ctypes.byref(d), None, 0, stat, math, 0, kinds[force] if force else -1, -1,
+                                *[ctypes.byref(o) for o in got])
+        assert rc == 0, rc
+        kind = next((n for n, i in kinds.items() if i == got[0].value), "other")
+        if kind != "other" and (expect is None or kind == expect):
+            out[route] = kind
+    return out
 
 
 # ----------------------------------------------------------------- strided buffers with guards

@@ -1,7 +1,7 @@
 """Golden vectors for the synthesizer variants beside the default pitch-guided HiFi-GAN (NSF), by running the
 REFERENCE's own modules (survey container only; never on the GPU box).
 
-Run:  python tests/golden/make_golden_vocoders.py [nof0] [mrf] [refinegan]
+Run:  python tests/golden/make_golden_vocoders.py [nof0] [mrf] [refinegan] [refinegan_b3_40k]
 
   nof0       Synthesizer(use_f0=False): TextEncoder without emb_pitch + HiFiGANGenerator
              (rvc/lib/algorithm/synthesizers.py:84, :119-139, :233-239; generators/hifigan.py:9-104)
@@ -11,6 +11,8 @@ Run:  python tests/golden/make_golden_vocoders.py [nof0] [mrf] [refinegan]
              torchaudio is absent here: torchaudio.functional.resample is replaced by oracle.realtime's restatement
              of torchaudio 2.x (kaiser window), so that one piece is pinned to the restatement. Its noise (the AdaIN
              draws are ~1.8 M floats) is not stored: the seeds and draw shapes are, and tests regenerate it.
+  refinegan_b3_40k  the same on the 40 kHz upsample list, B = 3, T = 24, lengths (24, 17, 1), sids (3, 0, 108)
+             -> synth_refinegan_b3_40k.npz, in synth_refinegan_b1.npz's layout
 Each fixture holds the inputs, the recorded RNG draws and the reference outputs; weights are regenerated from the
 seeds (rvcx.synthetic) by the tests. Harness as in make_golden.py (stubs, seeded noise streams).
 """
@@ -117,7 +119,9 @@ def mrf():
     print("synth_mrf_b2: o", o.shape, float(o.abs().max()), float(o.std()))
 
 
-def refinegan():
+def refinegan(name="synth_refinegan_b1", base=SYNTH_48K_V2, lengths=(6,), sid=(2,), seed=SEED_IN + 20):
+    """One Synthesizer(vocoder="RefineGAN").infer on the upsample list of `base`, B = len(lengths) rows of lengths[0]
+    frames -> tests/golden/<name>.npz; the four seeds are seed .. seed + 3."""
     import types
 
     from oracle.realtime import functional_resample
@@ -127,16 +131,16 @@ def refinegan():
     fn.resample = functional_resample
     ta.functional = fn
     sys.modules["torchaudio.functional"] = fn
-    cfg = dataclasses.replace(SYNTH_48K_V2, vocoder="RefineGAN")
+    cfg = dataclasses.replace(base, vocoder="RefineGAN")
     net = build(cfg, "RefineGAN")
-    rng = np.random.Generator(np.random.PCG64(SEED_IN + 20))
-    B, T = 1, 6
+    rng = np.random.Generator(np.random.PCG64(seed))
+    B, T = len(lengths), int(lengths[0])
     phone = rng.standard_normal((B, T, 768)).astype(np.float32)
-    f0 = synthetic.f0_walk(B, T, seed=SEED_IN + 21)
+    f0 = synthetic.f0_walk(B, T, seed=seed + 1)
     pitch = rng.integers(1, 256, size=(B, T)).astype(np.int64)
-    lengths = np.array([T], np.int64)
-    sid = np.array([2], np.int64)
-    ns, us = mg.NoiseStream(SEED_IN + 22), UniformStream(SEED_IN + 23)
+    lengths = np.array(lengths, np.int64)
+    sid = np.array(sid, np.int64)
+    ns, us = mg.NoiseStream(seed + 2), UniformStream(seed + 3)
     orig_n, orig_u = torch.randn_like, torch.rand
     torch.randn_like, torch.rand = ns, us
     try:
@@ -148,10 +152,20 @@ def refinegan():
         torch.randn_like, torch.rand = orig_n, orig_u
     shapes = np.array([d.size for d in ns.draws], np.int64)
     assert len(ns.draws) == 2 + 24 and len(us.draws) == 1, (len(ns.draws), len(us.draws))
-    np.savez_compressed(os.path.join(mg.OUT, "synth_refinegan_b1.npz"), phone=phone, f0=f0, pitch=pitch,
-                        lengths=lengths, sid=sid, noise_seed=SEED_IN + 22, uniform_seed=SEED_IN + 23,
+    assert us.draws[0].size == B  # conftest.refinegan_noise regenerates the phases as random(B)
+    np.savez_compressed(os.path.join(mg.OUT, name + ".npz"), phone=phone, f0=f0, pitch=pitch,
+                        lengths=lengths, sid=sid, noise_seed=seed + 2, uniform_seed=seed + 3,
                         draw_sizes=shapes, o=o.numpy(), z=z.numpy(), seed_w=SEED_W)
-    print("synth_refinegan_b1: o", o.shape, float(o.abs().max()), float(o.std()))
+    print(name + ": o", o.shape, float(o.abs().max()), float(o.std()))
+
+
+def refinegan_b3_40k():
+    """The 40 kHz list (rvc/configs/40000.json: rates 10, 10, 2, 2), B = 3, T = 24, lengths (24, 17, 1): ragged rows, a
+    one-frame row, the speaker table's last row."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from synth_configs import CONFIGS
+
+    refinegan("synth_refinegan_b3_40k", CONFIGS["v2_40k"], (24, 17, 1), (3, 0, 108), SEED_IN + 30)
 
 
 def main():
@@ -167,6 +181,8 @@ def main():
         mrf()
     if "refinegan" in which:
         refinegan()
+    if "refinegan_b3_40k" in which:
+        refinegan_b3_40k()
 
 
 if __name__ == "__main__":

@@ -124,6 +124,24 @@ def test_recurrence_test_entries_are_exported_and_bound():
     assert callable(Engine.gru_bidir) and callable(Engine.dec_source)
 
 
+def test_refinegan_kernel_entries_are_exported_and_bound():
+    """rvcx_rg_resample_dw, rvcx_rg_lerp_up_cat, rvcx_rg_adain (include/rvcx_test.h): the three kernels of
+    csrc/refinegan.hip, declared in the test header alone, exported, bound with their prototypes, an Engine method each,
+    and refused without a context."""
+    from rvcx import _lib
+    from rvcx.engine import Engine
+
+    product, test = header_prototypes("rvcx.h"), header_prototypes("rvcx_test.h")
+    lib = _lib.load()
+    for name, nargs in (("rvcx_rg_resample_dw", 11), ("rvcx_rg_lerp_up_cat", 13), ("rvcx_rg_adain", 13)):
+        assert test.get(name) == nargs and name not in product and name not in _lib.EXPORTS
+        assert name in _lib.TEST_EXPORTS and name in _lib.exported_symbols()
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == nargs
+        assert _lib.STATUS[fn(*([None] + [0] * (nargs - 1)))] == "RVCX_E_INVALID"
+    assert callable(Engine.rg_resample_dw) and callable(Engine.rg_lerp_up_cat) and callable(Engine.rg_adain)
+
+
 def test_engine_refuses_without_gpu():
     import torch
 

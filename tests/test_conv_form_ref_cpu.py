@@ -98,6 +98,37 @@ def test_case_is_sensitive(name):
     assert not survived, f"{name}: not rejected: {survived}"
 
 
+RG = [c["name"] for c in cf.CASES if c["name"].startswith("rg.")]
+RG_POLICY = cf.RG_POLICY
+
+
+@pytest.mark.parametrize("name", RG)
+def test_refinegan_rows_list_the_routes_the_planner_admits(name):
+    """The rg.* rows (runtime_refinegan.cpp's launch_conv sites): the row's route list is exactly what rvcx_conv_plan
+    admits for its form, with and without split-K, and the policy's family is the recorded one."""
+    c = cf.BY_NAME[name]
+    assert c["site"].startswith("runtime_refinegan.cpp:")
+    for nsk in (False, True):
+        adm = cf.admitted_routes(c, nsk)
+        assert tuple(r for r in cf.ALL6 if r in adm) == c["routes"], (name, nsk, adm)
+        assert adm["policy"] == RG_POLICY[name], adm
+    print(f"\n{name} [{c['site']}]: policy -> {RG_POLICY[name]}; refused: "
+          f"{[r for r in cf.ALL6 if r not in c['routes']]}")
+
+
+def test_refinegan_rows_cover_every_launch_conv_site():
+    """Every launch_conv call of csrc/runtime_refinegan.cpp is cited by at least one rg.* row, by its line."""
+    import os
+    import re
+
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                       "retrieval-based-voice-conversion-mlx_amd", "csrc", "runtime_refinegan.cpp")
+    sites = {i + 1 for i, line in enumerate(open(src)) if re.search(r"\blaunch_conv\(", line)}
+    cited = {int(cf.BY_NAME[n]["site"].split(":")[1]) for n in RG}
+    assert sites and sites == cited, (sorted(sites), sorted(cited))
+    assert set(RG_POLICY) == set(RG)
+
+
 def test_every_listed_mutation_is_applied_somewhere():
     used = {m for c in cf.CASES for m in cf.applicable(c)}
     assert used == set(cf.MUTATIONS) - {"alpha_after_act"}, sorted(set(cf.MUTATIONS) - used)

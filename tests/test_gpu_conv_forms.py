@@ -288,6 +288,16 @@ def test_forced_routes_refuse_foreign_shapes(engine):
     _refused(engine, by["dec.ups_nz"], "emu", nsk=True)
 
 
+RG_REFUSED = [(c["name"], r) for c in cf.CASES if c["name"].startswith("rg.") for r in cf.ALL6 if r not in c["routes"]]
+
+
+@pytest.mark.parametrize("name,route", RG_REFUSED, ids=[f"{n}-{r}" for n, r in RG_REFUSED])
+def test_refinegan_rows_refused_routes_are_refused(engine, name, route):
+    """The routes rvcx_conv_plan does not admit for an rg.* row (tests/test_conv_form_ref_cpu.py holds the lists to the
+    planner): RVCX_E_SHAPE, nothing written, never another kernel."""
+    _refused(engine, cf.BY_NAME[name], route, nsk=True)
+
+
 def test_every_family_is_reached(engine):
     """Runs last. The union of the kinds the table reported covers every 1-D family of ConvKind (conv_wsb_kernel, the
     bf16 32x32x16 form, no longer exists; k_rb_pair and the 2-D families are not conv1d's), the policy alone reaches

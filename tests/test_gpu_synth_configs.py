@@ -170,9 +170,15 @@ def clip(rmvpe_w):
 
 @only(TWO)
 def test_pipeline_vs_oracle(cfg_engine, clip, hubert_w, rmvpe_w):
+    pipeline_vs_oracle(cfg_engine, clip, hubert_w, rmvpe_w)
+
+
+def pipeline_vs_oracle(cfg_engine, clip, hubert_w, rmvpe_w):
     """The decomposition and the bars of test_gpu_sizes.py rows 1-2 (and test_gpu_c2_parity.py's pipeline == staged):
     output shape; the salience-aware f0 check; voice_conversion fed the oracle's pitch within 1e-4 of the peak after
-    the configuration's trim; the pipeline within 1e-6 of the staged path; spectrogram correlation >= 0.999."""
+    the configuration's trim; the pipeline within 1e-6 of the staged path; spectrogram correlation >= 0.999. Shared
+    with tests/test_gpu_refinegan.py (the oracle draws the decoder's own noise layout); returns (audio, eps_z, eps_src,
+    the pipeline's output) for what a caller checks on top."""
     from oracle.metrics import spectrogram_correlation
     from oracle.pipeline import OraclePipeline
     from rvcx.config import HUBERT_BASE, RMVPE_CFG
@@ -215,15 +221,21 @@ def test_pipeline_vs_oracle(cfg_engine, clip, hubert_w, rmvpe_w):
     assert e_ref <= 1e-4, e_ref
     assert cons <= 1e-6, cons
     assert c >= 0.999, c
+    return audio, ez, es, out
 
 
 # ----------------------------------------------------------------- 5. streaming with a model that is not 48 kHz
 @only(("v2_40k",))
 def test_stream_group_matches_oracle(cfg_engine, hubert_w, rmvpe_w):
+    stream_group_vs_oracle(cfg_engine, hubert_w, rmvpe_w)
+
+
+def stream_group_vs_oracle(cfg_engine, hubert_w, rmvpe_w, hops=3, src_noise=None):
     """test_gpu_stream.test_stream_group_matches_oracle with a 40 kHz model: the hop's output goes through the second
     sinc resample tgt_sr -> 48000. That test's bars (geometry equal, vol rel <= 1e-5, SOLA offsets equal on >= 75 % of
     hops, per-hop spectrogram corr > 0.99) and, on hops whose offset equals the oracle's, max |diff| <= 2e-3 of the
-    hop's peak (test_gpu_stream_ref.py)."""
+    hop's peak (test_gpu_stream_ref.py). src_noise(rng, B, T) -> (the group's eps_src, [row b's own B = 1 block]) for a
+    decoder whose source noise is not [B][T upp] (tests/test_gpu_refinegan.py)."""
     from oracle.metrics import spectrogram_correlation
     from oracle.realtime import OracleVoiceChanger
     from rvcx import synthetic
@@ -231,7 +243,7 @@ def test_stream_group_matches_oracle(cfg_engine, hubert_w, rmvpe_w):
     from rvcx.realtime import StreamGroup
 
     name, cfg, w, eng = cfg_engine
-    B, hops, protect = 2, 3, 0.33
+    B, protect = 2, 0.33
     orc = [OracleVoiceChanger(w, cfg, hubert_w, HUBERT_BASE, rmvpe_w, RMVPE_CFG, read_chunk_size=96,
                               silent_threshold=-90.0, sid=b) for b in range(B)]
     grp = StreamGroup(eng, B, read_chunk_size=96, cross_fade_overlap_size=0.1, extra_convert_size=0.5,
@@ -251,13 +263,17 @@ def test_stream_group_matches_oracle(cfg_engine, hubert_w, rmvpe_w):
         for h in range(hops):
             x = audio[:, h * block:(h + 1) * block]
             ez = rng.standard_normal((B, I, T)).astype(np.float32)
-            es = rng.standard_normal((B, T * upp)).astype(np.float32)
+            if src_noise is None:
+                es = rng.standard_normal((B, T * upp)).astype(np.float32)
+                es_rows = [es[b:b + 1] for b in range(B)]
+            else:
+                es, es_rows = src_noise(rng, B, T)
             out, vol = grp.process(x, grp.opts(protect=protect), eps_z=ez, eps_src=es)
             torch.cuda.synchronize()
             eng.check_device_status()
             out, vol, offs = out.cpu().numpy(), vol.cpu().numpy(), grp.offs.cpu().numpy()
             for b in range(B):
-                it = iter([torch.from_numpy(ez[b:b + 1]), torch.from_numpy(es[b:b + 1])])
+                it = iter([torch.from_numpy(ez[b:b + 1]), torch.from_numpy(es_rows[b])])
                 orc[b].noise_fn = lambda shape, which, it=it: next(it)
                 ref, rvol = orc[b].on_request(x[b].copy(), protect=protect)
                 assert ref.shape == out[b].shape and np.any(ref)

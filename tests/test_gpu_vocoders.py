@@ -2,9 +2,13 @@
 (tests/golden/make_golden_vocoders.py) and the CPU oracle:
   * MRF HiFi-GAN (synthesizers.py:86-98, generators/hifigan_mrf.py): 9-harmonic per-sample source
     (source_harm.hip, exact double-accumulated phase scans), MRF blocks on the conv kernels, conv_post bias.
-Bars: latents rel <= 1e-4, waveform rel <= 2e-3 and spectrogram corr >= 0.999 (the NSF synth test's bar); the MRF
-fixture also on the float64 anchor (tests/parity_anchor.py). RefineGAN stays on its fixture bars: its oracle holds more
-fixed-dtype pieces (the kaiser-sinc resampling branch)."""
+  * RefineGAN (synthesizers.py:99-107, generators/refinegan.py): 1-harmonic source on the linearly upsampled f0,
+    kaiser-sinc downsampling branch, AdaIN-noised ParallelResBlocks (refinegan.hip, runtime_refinegan.cpp).
+Bars: latents rel <= 1e-4, waveform rel <= 2e-3 and spectrogram corr >= 0.999 (the NSF synth test's bar), and beside
+them, for both decoders, the float64 anchor (tests/parity_anchor.py): the device within K = 8 gaps of the oracle in
+float64 and (K + 1) of the stored fp32 output. The RefineGAN oracle follows the dtype of its weights (the resample
+kernel is built in the waveform's dtype; only the linear f0 upsampling and the source stay float32, as MRF's source
+does). tests/test_gpu_refinegan.py holds the other rates, lengths and whole paths."""
 import dataclasses
 
 import numpy as np
@@ -13,7 +17,7 @@ import torch
 
 import parity_anchor as pa
 from conftest import golden
-from parity_anchor import K, anchor, check_each
+from parity_anchor import K, anchor, check, check_each
 from test_gpu_models import anchored
 
 pytestmark = pytest.mark.gpu
@@ -139,6 +143,14 @@ def test_refinegan_synth_vs_reference(refinegan_engine):
     ref = g["o"].reshape(o.shape)
     assert rel_err(o, ref) < 2e-3, rel_err(o, ref)
     assert spectrogram_correlation(o[0], ref[0]) > 0.999
+    # beside the fixed bars, as the MRF fixture above: the same inputs on the oracle in float64
+    ez = eps_z.reshape(1, cfg.inter_channels, T)
+    anc = anchor(pa.synth_fn(refinegan_engine[1], g["phone"], g["lengths"], g["pitch"], g["f0"], g["sid"], ez, eps_src,
+                             cfg=cfg))
+    dev = {"z_p": zp.cpu().numpy(), "z": z.cpu().numpy(), "o": o}
+    check_each([(f"synth_refinegan_b1 {k} device vs fp64", dev[k], *anc[k], K) for k in ("z_p", "z", "o")])
+    anchored("synth_refinegan_b1 z", dev["z"], g["z"].transpose(0, 2, 1), *anc["z"], 1e-4)
+    anchored("synth_refinegan_b1 o", o, g["o"], *anc["o"], 2e-3)
 
 
 def test_refinegan_vs_oracle_longer(refinegan_engine):
@@ -168,3 +180,6 @@ def test_refinegan_vs_oracle_longer(refinegan_engine):
     assert rel_err(out, ref) < 2e-3, rel_err(out, ref)
     for b in range(B):
         assert spectrogram_correlation(out[b], ref[b]) > 0.999
+    # beside the 2e-3: K gaps of the oracle in float64 on the same inputs
+    ref64, gap = anchor(pa.synth_fn(w, phone, lengths, pitch, f0, sid, eps_z, eps_src, cfg=cfg))["o"]
+    check("refinegan (2, 40) o device vs fp64", out, ref64, gap, K)

@@ -155,3 +155,31 @@ def test_synth_refinegan_matches_reference():
                                                         _t(eps_z.reshape(1, cfg.inter_channels, T)), _t(eps_src))
     assert rel_err(z, g["z"]) < 1e-5
     assert rel_err(o, g["o"]) < 1e-4, rel_err(o, g["o"])
+
+
+def test_synth_refinegan_b3_40k_matches_reference():
+    """The second pin to the reference's own run (make_golden_vocoders.py refinegan_b3_40k): the 40 kHz upsample list
+    (rates 10, 10, 2, 2: resample kernels and AdaIN block shapes the 48 kHz fixture does not hold), B = 3, lengths
+    (24, 17, 1), sids (3, 0, 108). The file's bars: z 1e-5, o 1e-4."""
+    import dataclasses
+
+    from conftest import refinegan_noise
+    from oracle import synth as osynth
+    from rvcx import synthetic
+    from rvcx.weights import normalize_state
+    from synth_configs import CONFIGS
+
+    g = golden("synth_refinegan_b3_40k.npz")
+    cfg = dataclasses.replace(CONFIGS["v2_40k"], vocoder="RefineGAN")
+    w = normalize_state(synthetic.synth_state(int(g["seed_w"]), cfg))
+    eps_z, eps_src = refinegan_noise(g)
+    B, T = g["phone"].shape[:2]
+    assert (B, T) == (3, 24) and tuple(g["lengths"]) == (24, 17, 1) and tuple(g["sid"]) == (3, 0, 108)
+    assert [int(n) for n in g["draw_sizes"][1:]] == [s for i, s in enumerate(osynth.refinegan_noise_sizes(cfg, B, T))
+                                                     if i != 1] and eps_src.size == sum(
+        osynth.refinegan_noise_sizes(cfg, B, T))
+    o, mask, (z, z_p, m_p, logs_p) = osynth.synth_infer(w, cfg, _t(g["phone"]), _t(g["lengths"]), _t(g["pitch"]),
+                                                        _t(g["f0"]), _t(g["sid"]),
+                                                        _t(eps_z.reshape(B, cfg.inter_channels, T)), _t(eps_src))
+    assert rel_err(z, g["z"]) < 1e-5
+    assert rel_err(o, g["o"]) < 1e-4, rel_err(o, g["o"])
