@@ -287,6 +287,29 @@ int rvcx_set_highpass_sos(rvcx_ctx* ctx, const double* sos, int nsec);
 int rvcx_highpass_pad(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t t_pad, double* d_pad64, float* d_pad32,
                       void* stream);
 
+/* scipy.signal.resample_poly's output length for n input frames: ceil(n*up/down) after gcd reduction. Host only. */
+int rvcx_resample_poly_len(int64_t n, int up, int down, int64_t* n_out);
+
+/* Decode, channel downmix and scipy.signal.resample_poly(x, up, down) (window ("kaiser", 5.0), padtype "constant")
+ * in one launch: what the file loader does on the host before the pipeline, and a converted output delivered at
+ * another rate after it. B rows, ragged. d_x: interleaved frames of `dtype` (0 f64, 1 f32, 2 i16 scaled by 2^-15,
+ * 3 i32 scaled by 2^-31; 24-bit WAV data is left-justified int32), `channels` per frame, row stride ldx frames;
+ * n[b] >= 1 frames per row (host array). The mono sample is the channels' fp64 sum in channel order / channels.
+ * d_taps: device fp64 [ntaps], the filter h = firwin(2*half + 1, 1/M, window=("kaiser", 5.0)) * up with
+ * M = max(up, down), half = 10*M (up-scaled, unpadded, ntaps odd, ntaps == 20*max(up,down)+1, or ntaps == 1 with
+ * up == down == 1: decode and downmix only). With n_pre_pad = down - half % down and
+ * n_pre_remove = (half + n_pre_pad) / down, output j of a row is
+ *   y[j] = sum_i x[i] * h[c - i*up],  c = (j + n_pre_remove)*down - n_pre_pad,  0 <= i < n,  0 <= c - i*up < ntaps,
+ * accumulated in fp64 fma in ascending i; a row's result does not depend on B or on the other rows.
+ * d_y: fp64 [B][ldy], row b receives n_out[b] = ceil(n[b]*up/down) samples (host array out), the rest of the row is
+ * zeroed so d_y is a valid input of rvcx_pipeline_batch_v. No model has to be loaded.
+ * RVCX_E_INVALID: bad arguments (a null pointer, n[b] < 1 or > ldx, an unknown dtype, ntaps of another length).
+ * RVCX_E_SHAPE: ldy below a row's n_out; up / down not positive and coprime; ceil(ntaps / up) above 8191 input
+ * samples per output (a ratio whose filter does not fit the staged window, e.g. 1/410). */
+int rvcx_resample_poly_v(rvcx_ctx* ctx, const void* d_x, int dtype, int channels, const int64_t* n, int64_t ldx, int B,
+                         int up, int down, const double* d_taps, int64_t ntaps, double* d_y, int64_t ldy,
+                         int64_t* n_out, void* stream);
+
 /* Options of Pipeline.pipeline (rvc/infer/pipeline.py:390-408; rvc_mlx/infer/pipeline_mlx.py:263) that
  * reach the device path. Fill with rvcx_pipeline_default_opts, then override. Times are in samples. */
 typedef struct {

@@ -470,6 +470,62 @@ int rvcx_highpass_pad(rvcx_ctx* ctx, const double* d_audio, int64_t n, int64_t t
   });
 }
 
+// ceil(n*up/down) with up/down reduced; false when it does not fit an int64
+static bool resample_len(int64_t n, int up, int down, int64_t* out) {
+  const __int128 v = ((__int128)n * up + down - 1) / down;
+  if (v > (__int128)INT64_MAX) return false;
+  *out = (int64_t)v;
+  return true;
+}
+
+static int gcd_int(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b, b = t;
+  }
+  return a;
+}
+
+int rvcx_resample_poly_len(int64_t n, int up, int down, int64_t* n_out) {
+  if (!n_out || n < 0 || up < 1 || down < 1) return RVCX_E_INVALID;
+  const int g = gcd_int(up, down);
+  return resample_len(n, up / g, down / g, n_out) ? RVCX_OK : RVCX_E_INVALID;
+}
+
+int rvcx_resample_poly_v(rvcx_ctx* ctx, const void* d_x, int dtype, int channels, const int64_t* n, int64_t ldx, int B,
+                         int up, int down, const double* d_taps, int64_t ntaps, double* d_y, int64_t ldy,
+                         int64_t* n_out, void* stream) {
+  return guard(ctx, [&] {
+    if (!d_x || !n || !d_taps || !d_y || !n_out || B < 1 || B > 65535 || channels < 1 || channels > 65535 ||
+        dtype < 0 || dtype > 3 || ldx < 1 || ldy < 1)
+      throw Error(RVCX_E_INVALID, "rvcx_resample_poly_v: bad arguments");
+    if (up < 1 || down < 1 || gcd_int(up, down) != 1)
+      throw Error(RVCX_E_SHAPE, "rvcx_resample_poly_v: up and down must be positive and coprime");
+    if (ntaps != 20 * (int64_t)std::max(up, down) + 1 && !(ntaps == 1 && up == 1 && down == 1))
+      throw Error(RVCX_E_INVALID, "rvcx_resample_poly_v: ntaps must be 20*max(up, down) + 1 (or 1 for up == down == 1)");
+    std::vector<long long> rows(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+      int64_t no = 0;
+      if (n[b] < 1 || (B > 1 && n[b] > ldx) || !resample_len(n[b], up, down, &no))
+        throw Error(RVCX_E_INVALID, "rvcx_resample_poly_v: bad row length");
+      if (no > ldy) throw Error(RVCX_E_SHAPE, "rvcx_resample_poly_v: ldy below a row's output length");
+      rows[b] = n[b], rows[(size_t)B + b] = no;
+    }
+    const ResamplePlan p = resample_poly_plan(up, down, ntaps);
+    if (p.J < 1) throw Error(RVCX_E_SHAPE, "rvcx_resample_poly_v: ceil(ntaps / up) exceeds the staged input window");
+    if ((ldy + p.J - 1) / p.J > INT32_MAX) throw Error(RVCX_E_SHAPE, "rvcx_resample_poly_v: ldy too large");
+    set_device(ctx);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* hp = ctx->buf<double>("rs.taps", (size_t)up * p.K, st);
+    long long* dr = ctx->buf<long long>("rs.rows", rows.size(), st);
+    RVCX_HIP(hipMemcpyAsync(dr, rows.data(), sizeof(long long) * rows.size(), hipMemcpyHostToDevice, st));
+    check(resample_poly_taps(d_taps, ntaps, up, p.K, hp, st), "resample_poly_taps");
+    check(resample_poly_rows(p, d_x, dtype, channels, dr, ldx, B, up, down, hp, d_y, ldy, dr + B, st),
+          "resample_poly_rows");
+    for (int b = 0; b < B; ++b) n_out[b] = rows[(size_t)B + b];
+  });
+}
+
 int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, double semitones, float protect,
                   int64_t t_pad, int64_t t_pad_tgt, const float* d_eps_z, const float* d_eps_src, uint64_t seed,
                   float* d_out, int64_t cap, int64_t* n_out, double* d_f0, void* stream) {

@@ -9,6 +9,7 @@
 #include "ivf_kernels.h"
 #include "kernel_base.h"
 #include "pipeline_kernels.h"
+#include "resample_kernels.h"
 #include "rowops_kernels.h"
 #include "stream_kernels.h"
 #include "vocoder_kernels.h"

@@ -185,6 +185,8 @@ SIG = {
     "rvcx_set_workspace": (i32, [vp, vp, i64]),
     "rvcx_workspace_info": (i32, [vp, P(i64), P(i64), P(i64)]),
     "rvcx_highpass_pad": (i32, [vp, vp, i64, i64, vp, vp, vp]),
+    "rvcx_resample_poly_len": (i32, [i64, i32, i32, P(i64)]),
+    "rvcx_resample_poly_v": (i32, [vp, vp, i32, i32, P(i64), i64, i32, i32, i32, vp, i64, vp, i64, P(i64), vp]),
     "rvcx_hubert_batch": (i32, [vp, vp, i64, i64, i32, i32, vp, i64, P(i64), vp]),
     "rvcx_hubert_batch_v": (i32, [vp, vp, P(i64), i64, i32, i32, vp, i64, P(i64), vp]),
     "rvcx_rmvpe_batch": (i32, [vp, vp, i64, i64, i32, f32, vp, i64, P(i64), vp, vp]),

@@ -551,6 +551,60 @@ class Engine(KernelTestMixin):
                                                self.stream()), "highpass_pad")
         return p64, p32
 
+    _RESAMPLE_DTYPES = {"float64": 0, "float32": 1, "int16": 2, "int32": 3}
+
+    def resample_poly(self, rows, up: int, down: int, dtype=None, channels: int = 1):
+        """scipy.signal.resample_poly(x, up, down) of every row in one launch (rvcx_resample_poly_v), decode and channel
+        downmix included. rows: a list of arrays / tensors (or one) of float64, float32, int16 (scaled by 2^-15) or
+        int32 (2^-31) samples, [n] mono or [n, channels] interleaved frames, all of one dtype (`dtype`, a numpy dtype
+        or name; None: the first row's). Returns a list of fp64 device tensors [ceil(n up / down)] (one tensor for one
+        row); they are views of one zero-padded [B, ld] buffer, so they can go on into a batched pass as they are.
+        The filter is rvcx.resample.taps(up, down), kept on the device per (up, down)."""
+        from . import resample as rs
+
+        t = self.torch
+        single = not isinstance(rows, (list, tuple))
+        rows = [rows] if single else list(rows)
+        if not rows:
+            return []
+        ch = int(channels)
+        name = str(np.dtype(dtype)) if dtype is not None else \
+            str(rows[0].dtype).replace("torch.", "")
+        if name not in self._RESAMPLE_DTYPES:
+            raise TypeError(f"resample_poly takes float64, float32, int16 or int32 samples, not {name}")
+        tdt = getattr(t, name)
+        up, down = rs.reduce(up, down)
+        B = len(rows)
+        ns = []
+        for r in rows:
+            if r.ndim > 2 or (r.ndim == 2 and int(r.shape[1]) != ch) or (r.ndim == 1 and int(r.shape[0]) % ch):
+                raise ValueError(f"resample_poly: a row of shape {tuple(r.shape)} does not hold frames of {ch} channels")
+            ns.append(int(r.shape[0]) if r.ndim == 2 else int(r.shape[0]) // ch)
+        ldx = max(ns)
+        if B == 1:
+            x = self._dev(rows[0], tdt).reshape(-1)
+        elif not any(isinstance(r, t.Tensor) for r in rows):  # host rows: one padded image, one copy
+            hx = np.zeros((B, ldx * ch), dtype=name)
+            for b, r in enumerate(rows):
+                hx[b, : ns[b] * ch] = np.asarray(r, dtype=name).reshape(-1)
+            x = t.as_tensor(hx, device=self.device)
+        else:
+            x = t.zeros((B, ldx * ch), dtype=tdt, device=self.device)
+            for b, r in enumerate(rows):
+                x[b, : ns[b] * ch] = self._dev(r, tdt).reshape(-1)
+        cache = self.__dict__.setdefault("_resample_taps", {})
+        h = cache.get((up, down))
+        if h is None:
+            h = cache[(up, down)] = t.as_tensor(np.array(rs.taps(up, down)), device=self.device)
+        ldy = max(rs.plan(n, up, down)[2] for n in ns)
+        y = t.empty((B, ldy), dtype=t.float64, device=self.device)
+        no = (ctypes.c_int64 * B)()
+        self._check(self.lib.rvcx_resample_poly_v(self.ctx, x.data_ptr(), self._RESAMPLE_DTYPES[name], ch,
+                                                  (ctypes.c_int64 * B)(*ns), ldx, B, up, down, h.data_ptr(),
+                                                  h.numel(), y.data_ptr(), ldy, no, self.stream()), "resample_poly")
+        out = [y[b, : int(no[b])] for b in range(B)]
+        return out[0] if single else out
+
     def pipeline(self, audio, sid: int = 0, semitones: float = 0.0, protect: float = 0.33, t_pad: int = 16000,
                  t_pad_tgt: int = 48000, eps_z=None, eps_src=None, seed: int = 0, out=None, want_f0: bool = False):
         """One utterance (padded length <= t_max) through the whole device pipeline.

@@ -106,8 +106,12 @@ def _first_existing(cands):
     return None
 
 
-def load_audio(file_path: str, sr: int = 16000) -> np.ndarray:
-    """WAV -> mono float64 @sr (infer_mlx.py:91-104; resampling by polyphase filtering)."""
+def load_audio(file_path: str, sr: int = 16000, engine: Optional[Engine] = None):
+    """WAV -> mono float64 @sr (infer_mlx.py:91-104; resampling by polyphase filtering). With an engine the samples
+    go to the device as the file holds them and decode, downmix and resampling run there in one launch
+    (load_audio_device): the result is an fp64 device tensor, equal to the host route's up to summation order."""
+    if engine is not None:
+        return load_audio_device([file_path], engine, sr)[0]
     from math import gcd
 
     from scipy import signal
@@ -123,6 +127,31 @@ def load_audio(file_path: str, sr: int = 16000) -> np.ndarray:
         g = gcd(int(rate), int(sr))
         data = signal.resample_poly(data, sr // g, int(rate) // g)
     return data
+
+
+DEVICE_WAV_DTYPES = ("int16", "int32", "float32", "float64")  # what rvcx_resample_poly_v decodes
+
+
+def load_audio_device(paths, engine: Engine, sr: int = 16000):
+    """`load_audio` of every file on the device -> fp64 device tensors in input order. The files are grouped by
+    (rate, channels, dtype) and each group is decoded, downmixed and resampled in one rvcx_resample_poly_v launch.
+    A WAV of another sample type (uint8) goes through the host `load_audio` and is uploaded."""
+    from scipy.io import wavfile
+
+    out = [None] * len(paths)
+    groups: Dict[tuple, list] = {}
+    for i, p in enumerate(paths):
+        rate, data = wavfile.read(p)
+        if str(data.dtype) not in DEVICE_WAV_DTYPES:
+            out[i] = engine._dev(load_audio(p, sr), engine.torch.float64)
+            continue
+        ch = 1 if data.ndim == 1 else int(data.shape[1])
+        groups.setdefault((int(rate), ch, str(data.dtype)), []).append((i, data))
+    for (rate, ch, dt), items in groups.items():
+        ys = engine.resample_poly([d for _, d in items], sr, rate, dtype=dt, channels=ch)
+        for (i, _), y in zip(items, ys):
+            out[i] = y
+    return out
 
 
 class RVCX:
@@ -167,69 +196,105 @@ class RVCX:
     def convert(self, audio: np.ndarray, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75,
                 volume_envelope=1.0, protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, sid=0,
                 proposed_pitch=False, proposed_pitch_threshold=155.0, seed: int = 0,
-                split_audio: bool = False) -> np.ndarray:
-        """16 kHz mono audio -> converted float32 audio @tgt_sr (the body of infer_mlx.py:287-336). split_audio
-        converts the non-silent intervals one by one and merges them back with the gaps restored
-        (rvc/infer/infer.py:282-316)."""
+                split_audio: bool = False, resample_sr: int = 0) -> np.ndarray:
+        """16 kHz mono audio (numpy, or a device tensor as load_audio(engine=) returns it) -> converted float32 audio
+        @tgt_sr (the body of infer_mlx.py:287-336). split_audio converts the non-silent intervals one by one and
+        merges them back with the gaps restored (rvc/infer/infer.py:282-316). resample_sr: the output's rate
+        (`output_sr`); the output is resampled to it on the device when it is at least 16000 and not tgt_sr."""
         from ..split import merge_audio, process_audio
 
+        post = None if split_audio else self._resampler(resample_sr)
         chunks, intervals = process_audio(self.engine, audio, 16000) if split_audio else ([audio], None)
         outs = [self.pipeline.pipeline(self.hubert_model, self.net_g, sid, c, pitch, f0_method, index_path,
                                        index_rate, self.use_f0, volume_envelope, self.version, protect, f0_autotune,
-                                       f0_autotune_strength, proposed_pitch, proposed_pitch_threshold, seed=seed)
+                                       f0_autotune_strength, proposed_pitch, proposed_pitch_threshold, seed=seed,
+                                       post=post)
                 for c in chunks]
-        return merge_audio(chunks, outs, intervals, 16000, self.tgt_sr) if split_audio else outs[0]
+        if not split_audio:
+            return outs[0]
+        merged = merge_audio(chunks, outs, intervals, 16000, self.tgt_sr)
+        post = self._resampler(resample_sr)  # the merged signal is resampled, not its pieces
+        return merged if post is None else self.engine.host(post(merged))
+
+    def output_sr(self, resample_sr: int = 0) -> int:
+        """The rate `convert(..., resample_sr=)` delivers: resample_sr when it is at least 16000 and differs from
+        tgt_sr (the condition of rvc/infer/infer.py:279), else tgt_sr."""
+        r = int(resample_sr or 0)
+        return r if r >= 16000 and r != self.tgt_sr else self.tgt_sr
+
+    def _resampler(self, resample_sr):
+        """The output stage of resample_sr: float32 @tgt_sr -> float32 @resample_sr on the device (fp64 arithmetic,
+        rvcx_resample_poly_v), or None when the output stays at tgt_sr."""
+        sr = self.output_sr(resample_sr)
+        if sr == self.tgt_sr:
+            return None
+        eng = self.engine
+        return lambda y: eng.resample_poly(eng._dev(y, eng.torch.float32).reshape(-1), sr, self.tgt_sr).to(
+            eng.torch.float32)
 
     def convert_many(self, audios, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75, volume_envelope=1.0,
                      protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, sid=0, proposed_pitch=False,
                      proposed_pitch_threshold=155.0, seed: int = 0, batch: Optional[int] = None,
-                     max_pad: Optional[float] = None, noise_fn=None, ragged_f0: bool = False):
+                     max_pad: Optional[float] = None, noise_fn=None, ragged_f0: bool = False, resample_sr: int = 0):
         """`convert` over a list of 16 kHz utterances of any lengths -> the outputs in input order. Utterances of
         similar length share one batched pass (PipelineRVCX.pipeline_many: sorted by length, a batch filled while its
         shortest row is at least (1 - max_pad) of its longest, inputs above t_max converted alone). ragged_f0
-        (f0_method "rmvpe" or "fcpe"): the rows of a batch also share one ragged pass of the pitch network."""
+        (f0_method "rmvpe" or "fcpe"): the rows of a batch also share one ragged pass of the pitch network. An
+        utterance may be a device tensor; resample_sr as in `convert`."""
         from .pipeline import DEFAULT_BATCH, DEFAULT_MAX_PAD
 
         return self.pipeline.pipeline_many(
             self.hubert_model, self.net_g, sid, audios, pitch, f0_method, index_path, index_rate, self.use_f0,
             volume_envelope, self.version, protect, f0_autotune, f0_autotune_strength, proposed_pitch,
             proposed_pitch_threshold, seed=seed, batch=DEFAULT_BATCH if batch is None else batch,
-            max_pad=DEFAULT_MAX_PAD if max_pad is None else max_pad, noise_fn=noise_fn, ragged_f0=ragged_f0)
+            max_pad=DEFAULT_MAX_PAD if max_pad is None else max_pad, noise_fn=noise_fn, ragged_f0=ragged_f0,
+            post=self._resampler(resample_sr))
 
-    def infer_batch(self, input_dir, output_dir, **kw):
+    def infer_batch(self, input_dir, output_dir, device_load: bool = False, **kw):
         """convert_audio_batch (rvc/infer/infer.py:350-414) over the WAV files of input_dir: every file converted with
-        the options of `convert_many` and written under the same name to output_dir. Returns the output paths."""
+        the options of `convert_many` and written under the same name to output_dir (at resample_sr when that
+        applies). Returns the output paths. device_load: the files are decoded and resampled on the device, each group
+        of one (rate, channels, sample type) in one launch (load_audio_device), and stay there into the batched pass."""
         from scipy.io import wavfile
 
         names = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".wav"))
-        outs = self.convert_many([load_audio(os.path.join(input_dir, f)) for f in names], **kw)
+        files = [os.path.join(input_dir, f) for f in names]
+        audios = load_audio_device(files, self.engine) if device_load else [load_audio(f) for f in files]
+        outs = self.convert_many(audios, **kw)
         os.makedirs(output_dir, exist_ok=True)
         paths = []
         for f, y in zip(names, outs):
             paths.append(os.path.join(output_dir, f))
-            wavfile.write(paths[-1], self.tgt_sr, np.asarray(y, dtype=np.float32))
+            wavfile.write(paths[-1], self.output_sr(kw.get("resample_sr", 0)), np.asarray(y, dtype=np.float32))
         return paths
 
     def infer(self, audio_input, audio_output, pitch=0, f0_method="rmvpe", index_path=None, index_rate=0.75,
-              volume_envelope=1.0, protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, split_audio=False):
+              volume_envelope=1.0, protect=0.5, f0_autotune=False, f0_autotune_strength=1.0, split_audio=False,
+              device_load: bool = False, resample_sr: int = 0):
+        """device_load: the file is decoded and resampled to 16 kHz on the device (load_audio(engine=)).
+        resample_sr: as in `convert`; the file is written at that rate."""
         from scipy.io import wavfile
 
-        audio = load_audio(audio_input)
+        audio = load_audio(audio_input, engine=self.engine) if device_load else load_audio(audio_input)
         out = self.convert(audio, pitch, f0_method, index_path, index_rate, volume_envelope, protect, f0_autotune,
-                           f0_autotune_strength, split_audio=split_audio)
-        wavfile.write(audio_output, self.tgt_sr, out.astype(np.float32))
+                           f0_autotune_strength, split_audio=split_audio, resample_sr=resample_sr)
+        wavfile.write(audio_output, self.output_sr(resample_sr), out.astype(np.float32))
         return out
 
-    def build_index(self, audio_paths_or_arrays, out_path: str, algorithm: str = "Auto", seed: int = 0, **kw):
+    def build_index(self, audio_paths_or_arrays, out_path: str, algorithm: str = "Auto", seed: int = 0,
+                    device_load: bool = False, **kw):
         """The .index file that index_rate > 0 needs, from the speaker's audio: the HuBERT features of every file or
         16 kHz array, as rvc/train/extract/extract.py:133-139 saves them (files whose features hold NaN are skipped),
         then rvc/train/process/extract_index.py:37-70 on device (rvcx.infer.index.build_index) and write. Returns
-        the built IndexIVFFlat, which is this engine's loaded index."""
+        the built IndexIVFFlat, which is this engine's loaded index. device_load: files are loaded on the device."""
         from .index import build_index
 
         feats = []
         for a in audio_paths_or_arrays:
-            audio = load_audio(a) if isinstance(a, (str, os.PathLike)) else np.asarray(a)
+            if isinstance(a, (str, os.PathLike)):
+                audio = load_audio(a, engine=self.engine) if device_load else load_audio(a)
+            else:
+                audio = np.asarray(a)
             f = self.engine.host(self.engine.hubert(audio, self.version))
             if np.isnan(f).any():
                 continue

@@ -218,15 +218,16 @@ class PipelineRVCX:
     def pipeline(self, model, net_g, sid, audio, pitch=0, f0_method="rmvpe", file_index=None, index_rate=0.0,
                  pitch_guidance=True, volume_envelope=1.0, version="v2", protect=0.33, f0_autotune=False,
                  f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, eps_z=None,
-                 eps_src=None, seed: int = 0):
-        """Whole utterance -> float32 [N_out] @tgt_sr (pipeline.py:390-558)."""
+                 eps_src=None, seed: int = 0, post=None):
+        """Whole utterance -> float32 [N_out] @tgt_sr (pipeline.py:390-558). audio: a numpy array or a device tensor
+        (as the device loader returns it). post (device tensor -> device tensor) runs on the output before its copy
+        to the host (the resample_sr stage of rvcx.infer.RVCX)."""
         eng, opts = self._pipeline_opts(model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance,
                                         volume_envelope, version, protect, f0_autotune, f0_autotune_strength,
                                         proposed_pitch, proposed_pitch_threshold)
-        y, f0 = eng.pipeline_ex(np.asarray(audio, dtype=np.float64).reshape(-1), opts, eps_z=eps_z,
-                                eps_src=eps_src, seed=seed, want_f0=True)
+        y, f0 = eng.pipeline_ex(_row(audio), opts, eps_z=eps_z, eps_src=eps_src, seed=seed, want_f0=True)
         self.last_f0 = f0
-        return eng.host(y)
+        return eng.host(y if post is None else post(y))
 
     def _pipeline_opts(self, model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance, volume_envelope,
                        version, protect, f0_autotune, f0_autotune_strength, proposed_pitch, proposed_pitch_threshold):
@@ -260,7 +261,7 @@ class PipelineRVCX:
                       pitch_guidance=True, volume_envelope=1.0, version="v2", protect=0.33, f0_autotune=False,
                       f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, seed: int = 0,
                       batch: int = DEFAULT_BATCH, max_pad: float = DEFAULT_MAX_PAD, noise_fn=None,
-                      ragged_f0: bool = False):
+                      ragged_f0: bool = False, post=None):
         """`pipeline` over a list of utterances of any lengths -> the list of float32 outputs in input order.
         The utterances are grouped longest first into batches of up to `batch` rows whose shortest is at least
         (1 - max_pad) of the longest (rvcx.offline.bucket) and every batch is one rvcx_pipeline_batch_v pass; an
@@ -269,7 +270,9 @@ class PipelineRVCX:
         [T * upp]) injects utterance i's noise instead (T its synthesizer frames), as the tests do.
         ragged_f0 (f0_method "rmvpe" or "fcpe", else ValueError): the rows of a batch share one ragged pass of the pitch
         network (rvcx_pipeline_opts.f0_method 4 for RMVPE, 5 for the FCPE network) instead of one pass per row; a row's
-        f0 then equals the per-row pass up to summation order, not bit for bit."""
+        f0 then equals the per-row pass up to summation order, not bit for bit.
+        An utterance may be a device tensor (the device loader's rows): it stays on the device. post (device tensor ->
+        device tensor) runs on every output before its copy to the host."""
         from ..offline import bucket
 
         if ragged_f0 and f0_method not in ("rmvpe", "fcpe"):
@@ -280,9 +283,12 @@ class PipelineRVCX:
                                         proposed_pitch, proposed_pitch_threshold)
         if ragged_f0:  # "fcpe" is method 3 with its network loaded, method 0 as the MLX port's RMVPE fallback
             opts.f0_method = 5 if int(opts.f0_method) == 3 else 4
-        audios = [np.asarray(a, dtype=np.float64).reshape(-1) for a in audios]
+        audios = [_row(a) for a in audios]
         outs = [None] * len(audios)
         upp = eng.upp
+
+        def host(y):
+            return eng.host(y if post is None else post(y))
 
         def noise(i):
             return (None, None) if noise_fn is None else noise_fn(i, eng.pipeline_frames(len(audios[i]), opts))
@@ -290,12 +296,12 @@ class PipelineRVCX:
         t_max = int(opts.t_max)
         short = [i for i, a in enumerate(audios) if not (t_max > 0 and len(a) + 160 > t_max)]
         for i in sorted(set(range(len(audios))) - set(short)):  # long inputs: the split search and the chunk loop
-            outs[i] = eng.host(eng.pipeline_ex(audios[i], opts, seed=seed))
+            outs[i] = host(eng.pipeline_ex(audios[i], opts, seed=seed))
         for k, g in enumerate(bucket([len(audios[i]) for i in short], max(1, int(batch)), float(max_pad))):
             ids = [short[j] for j in g]
             if len(ids) == 1:
                 ez, es = noise(ids[0])
-                outs[ids[0]] = eng.host(eng.pipeline_ex(audios[ids[0]], opts, eps_z=ez, eps_src=es, seed=seed + k))
+                outs[ids[0]] = host(eng.pipeline_ex(audios[ids[0]], opts, eps_z=ez, eps_src=es, seed=seed + k))
                 continue
             ez = es = None
             if noise_fn is not None:
@@ -310,11 +316,18 @@ class PipelineRVCX:
                                       seed=seed + k)
             eng.check_device_status()
             for i, y in zip(ids, ys):
-                outs[i] = y.cpu().numpy()
+                outs[i] = (y if post is None else post(y)).cpu().numpy()
         return outs
 
 
 PipelineMLX = PipelineRVCX
+
+
+def _row(audio):
+    """One utterance as the engine takes it: fp64 [n], a torch tensor passed through, anything else as numpy."""
+    if hasattr(audio, "data_ptr"):
+        return audio.double().reshape(-1)
+    return np.asarray(audio, dtype=np.float64).reshape(-1)
 
 
 def proposed_key(f0: np.ndarray, threshold: float, limit: int = 12) -> int:
