@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "capi_common.h"
+#include "rows.h"
 
 extern char** environ;
 
@@ -240,8 +241,7 @@ int rvcx_fcpe_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, int
     if (!d_audio || !d_f0 || !n || B < 1 || ldf < 1 || (d_salience && ld_sal_frames < 1) || decoder_mode < 0 ||
         decoder_mode > 1)
       throw Error(RVCX_E_INVALID, "rvcx_fcpe_batch_v: bad arguments");
-    for (int b = 0; b < B; ++b)
-      if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_fcpe_batch_v: bad row length");
+    Rows("rvcx_fcpe_batch_v", n, B, lda, 1);
     set_device(ctx);
     fcpe_forward_v(*ctx, d_audio, n, lda, B, threshold, decoder_mode, d_f0, ldf, d_salience, ld_sal_frames,
                    static_cast<hipStream_t>(stream));
@@ -290,8 +290,7 @@ int rvcx_hubert_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, i
   return guard(ctx, [&] {
     if (!ctx->ready[RVCX_MODEL_HUBERT]) throw Error(RVCX_E_STATE, "hubert weights not finalized");
     if (!d_audio || !d_feats || !n || B < 1 || ld_rows < 1) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch_v: bad arguments");
-    for (int b = 0; b < B; ++b)
-      if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_hubert_batch_v: bad row length");
+    Rows("rvcx_hubert_batch_v", n, B, lda, 1);
     set_device(ctx);
     hubert_forward_v(*ctx, d_audio, n, lda, B, version == 1 ? 1 : 2, d_feats, ld_rows, L_out,
                      static_cast<hipStream_t>(stream));
@@ -317,8 +316,7 @@ int rvcx_rmvpe_batch_v(rvcx_ctx* ctx, const float* d_audio, const int64_t* n, in
     if (!ctx->ready[RVCX_MODEL_RMVPE]) throw Error(RVCX_E_STATE, "rmvpe weights not finalized");
     if (!d_audio || !d_f0 || !n || B < 1 || ldf < 1 || (d_hidden && ld_hidden_frames < 1))
       throw Error(RVCX_E_INVALID, "rvcx_rmvpe_batch_v: bad arguments");
-    for (int b = 0; b < B; ++b)
-      if (n[b] <= 0 || (B > 1 && n[b] > lda)) throw Error(RVCX_E_INVALID, "rvcx_rmvpe_batch_v: bad row length");
+    Rows("rvcx_rmvpe_batch_v", n, B, lda, 1);
     set_device(ctx);
     rmvpe_forward_v(*ctx, d_audio, n, lda, B, thred, d_f0, ldf, F_out, d_hidden, ld_hidden_frames,
                     static_cast<hipStream_t>(stream));
@@ -812,7 +810,7 @@ int rvcx_rt_default_desc(rvcx_rt_desc* d) {
   d->extra_convert_size = 0.5;
   d->silent_threshold = -90.0;
   d->f0_method = 0;
-  d->fcpe_threshold = 0.006f;  // rvc/realtime/pipeline.py:155
+  d->fcpe_threshold = FCPE_THRESHOLD;
   return RVCX_OK;
 }
 

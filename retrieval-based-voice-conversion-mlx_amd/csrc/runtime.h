@@ -297,23 +297,19 @@ void finalize_hubert(Ctx& c);
 void finalize_rmvpe(Ctx& c);
 void finalize_crepe(Ctx& c);
 void finalize_fcpe(Ctx& c);
-// FCPEInfer.__call__ (+ FCPEF0Predictor.post_process when interp_uv) on audio [n] fp32 (rvc/lib/predictors/FCPE.py
-// :758-764, :877-910): f0 fp64 [frames], salience [F][out_dims] optional. Returns the frames written to f0
-// (F = n / hop + 1, or pad_to when interp_uv and pad_to > 0); cap = the capacity of f0 in frames.
-int64_t fcpe_frames(const Ctx& c, int64_t n);
-// the network's input alone: Wav2Mel.extract_mel (FCPE.py:790-813) -> mel [fcpe_frames(n)][n_mels]; returns the frames
-// (B streams of n samples, row b at audio + b ld -> mel [B][frames][n_mels], each stream framed on its own)
+// FCPEInfer.__call__ (rvc/lib/predictors/FCPE.py:758-764) on fp32 audio, three entries to one body (runtime_fcpe.cpp
+// fcpe_rows): the raw track f0 fp64 (zeros where unvoiced), salience [.][out_dims] optional; cap = the frames f0 holds.
+int64_t fcpe_frames(const Ctx& c, int64_t n);  // the frames FCPEInfer gives for n samples
+// the network's input alone (Wav2Mel.extract_mel): B streams of n samples -> mel [B][fcpe_frames(n)][n_mels]
 int fcpe_mel(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float* mel, hipStream_t s);
-// FCPEInfer.__call__ for B streams of n samples in one set of launches (row b at audio + b ld): the raw track f0
-// [B][F] fp64 (zeros where unvoiced; cap = the frames per stream f0 holds), salience [B][F][out_dims] optional.
-// Returns F = fcpe_frames(n). fcpe_forward is its B = 1 case plus the interp_uv / pad_to tail.
+// B streams of n samples: f0 [B][F], salience [B][F][out_dims]. Returns F.
 int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float thr, int mode, double* f0,
                        int64_t cap, float* sal_out, hipStream_t s);
+// one utterance, then FCPEF0Predictor.post_process (:877-910) when interp_uv. Returns the frames written: F, or pad_to
 int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
                      double* f0, float* sal_out, int64_t cap, hipStream_t s);
-// the raw track for B inputs of nv[b] samples (host array) in one ragged pass: f0 row b (fcpe_frames(nv[b]) frames) at
-// f0 + b*ldf, its salience (optional) at sal_out + b*ld_sal*out_dims. Returns the longest row's frames. Equal lengths
-// are fcpe_forward_b and one row is fcpe_forward, unless `sizing` (the arena query sizes the ragged form).
+// B inputs of nv[b] samples (host array) in one ragged pass, row b at f0 + b*ldf / sal_out + b*ld_sal*out_dims. Returns
+// the longest row's frames. Equal lengths and one row are fcpe_forward_b's bits, unless `sizing` (the arena query).
 int64_t fcpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t ld, int B, float thr, int mode, double* f0,
                        int64_t ldf, float* sal_out, int64_t ld_sal, hipStream_t s, bool sizing = false);
 // the decoders + post_process alone on salience [F][out_dims]
@@ -347,13 +343,15 @@ int64_t hubert_tail(Ctx& c, const HubertRun& run, hipStream_t s);
 // on the aux stream). The RMVPE forwards issue it once, right after the launches of the first BiGRU group they reach;
 // Ctx::ev_gate is recorded on the stream before those launches, where the hook's work may start.
 using GruHook = std::function<void(hipStream_t)>;
-int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double* f0, int64_t cap, float* hidden,
-                      hipStream_t s, GruHook beside_gru = nullptr);
-// batched over B equal-length inputs (rows of stride lda); outputs back to back per sequence
+// batched over B equal-length inputs (rows of stride lda); outputs back to back per sequence (f0 row b at f0 + b*F)
 int64_t hubert_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, int version, float* feats,
                          int64_t cap, hipStream_t s);
 int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
                         int64_t cap, float* hidden, hipStream_t s, GruHook beside_gru = nullptr);
+inline int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double* f0, int64_t cap, float* hidden,
+                             hipStream_t s, GruHook beside_gru = nullptr) {
+  return rmvpe_forward_b(c, audio, n, n, 1, thred, f0, cap, hidden, s, std::move(beside_gru));
+}
 // RMVPE's BiGRU recurrence on the context's hand-off buffer (runtime_fe.cpp): gi [B][T][1536] -> out [B][T][512], 16
 // sequences per launch; tag_start < 0 continues the buffer's tag counters, >= 0 zeroes it and sets them (the tests).
 // Tv (device, optional): sequence b runs its own Tv[b] <= T steps in rows of stride T. beside_gru (optional) is issued
@@ -361,9 +359,9 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
 void gru_bidir_run(Ctx& c, const float* gi, int B, int T, const float* whh_f, const float* bhh_f, const float* whh_b,
                    const float* bhh_b, float* out, long long tag_start, hipStream_t s, const int* Tv = nullptr,
                    const GruHook& beside_gru = nullptr);
-// batched over B inputs of nv[b] samples (host array) in one ragged pass: f0 row b (F_b = 1 + nv[b] / 160 frames) at
-// f0 + b*ldf, its salience (optional) at hidden + b*ld_hidden*360; F_out[b] = F_b (host, optional). Returns the longest
-// row's frames. Equal lengths are rmvpe_forward_b, unless force_ragged (the arena query, which sizes the ragged form).
+// B inputs of nv[b] samples (host array) in one ragged pass: f0 row b (F_b = 1 + nv[b] / 160 frames) at f0 + b*ldf,
+// its salience (optional) at hidden + b*ld_hidden*360; F_out[b] = F_b (host, optional). Returns the longest row's
+// frames. Equal lengths take the pass without lengths (rmvpe_forward_b's bits), unless force_ragged (the arena query).
 int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, float thred, double* f0,
                         int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s,
                         bool force_ragged = false);
@@ -522,6 +520,21 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
 // arena is detached meanwhile and the pool is released again before it returns
 int64_t pipeline_workspace_bytes(Ctx& c, int B, int64_t n, const rvcx_pipeline_opts& o, hipStream_t s);
 rvcx_pipeline_opts default_pipeline_opts();
+// the reference predictors' voicing thresholds (FCPE's: rvc/realtime/pipeline.py:155); a positive one of the caller wins
+constexpr float RMVPE_THRESHOLD = 0.03f, FCPE_THRESHOLD = 0.006f;
+inline float or_default(float v, float d) { return v > 0 ? v : d; }
+inline float rmvpe_threshold(const rvcx_pipeline_opts& o) { return or_default(o.rmvpe_threshold, RMVPE_THRESHOLD); }
+inline float fcpe_threshold(const rvcx_pipeline_opts& o) { return or_default(o.fcpe_threshold, FCPE_THRESHOLD); }
+// whether the loaded FCPE gives the pipelines' pitch frames (160 samples at 16 kHz): RVCX_OK, RVCX_E_STATE without
+// finalized FCPE weights, RVCX_E_SHAPE for another rate or hop; and the refusal of f0 method "fcpe" that goes with it
+inline int fcpe_pitch_frames(const Ctx& c) {
+  return !c.ready[RVCX_MODEL_FCPE] ? RVCX_E_STATE : c.fcfg.sr == 16000 && c.fcfg.hop == 160 ? RVCX_OK : RVCX_E_SHAPE;
+}
+inline void require_fcpe_pitch_frames(const Ctx& c, const std::string& who) {
+  const int e = fcpe_pitch_frames(c);
+  if (e == RVCX_E_STATE) throw Error(e, who + ": f0_method fcpe but no FCPE weights finalized");
+  if (e != RVCX_OK) throw Error(e, who + ": the FCPE model must run at 16 kHz with hop_size 160");
+}
 int proposed_key(const std::vector<double>& f0, double threshold);
 int64_t hubert_frames(int64_t n);  // HuBERT output rows for n samples (0 when too short)
 void set_i32(int32_t* p, int32_t v, hipStream_t s);

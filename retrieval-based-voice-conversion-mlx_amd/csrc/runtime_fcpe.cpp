@@ -7,14 +7,13 @@
 //   convs    stack.0 / stack.3 (k 3) and every Linear / 1x1 conv on the implicit-GEMM family (launch_conv)
 //   attn     to_q | to_k | to_v as one GEMM into [F][3 x 512], then performer_attn.hip on the 8 heads in place
 //   conformer LN -> 1x1 (C -> 4C) -> GLU + depthwise k 31 + Swish (one kernel, fcpe.hip) -> 1x1 (2C -> C)
-//   batch    fcpe_forward_b runs B streams of one length in one set of launches per layer (a realtime hop's f0 with
-//            rvcx_rt_desc::f0_method 1, rvcx_fcpe_b): activations [B][F][C], row-wise ops on the B F rows, everything
-//            padded or reduced over time per stream. fcpe_forward is its B = 1 case plus the interp_uv / pad_to tail
-//   ragged   fcpe_forward_v runs B utterances of different lengths through the same launches: activations
-//            [B][F_max][C], a device array of the rows' frame counts F_b in every kernel that pads or reduces over time
+//   rows     fcpe_rows is the one pass over B rows, of one length (fcpe_forward_b: a realtime hop's f0 with
+//            rvcx_rt_desc::f0_method 1; fcpe_forward is B = 1 plus the interp_uv / pad_to tail) or of their own lengths
+//            (fcpe_forward_v): a device array of the frame counts F_b in every kernel that pads or reduces over time
 #include <cmath>
 
 #include "model_build.h"
+#include "rows.h"
 
 namespace rvcx {
 
@@ -93,52 +92,69 @@ void finalize_fcpe(Ctx& c) {
   c.alloc_weight("fc.cent", host_weight(c, M, "cent_table", {g.out_dims}).v);
 }
 
-// the frames FCPEInfer gives for n samples: n / hop + 1, or one more than the STFT's when that is fewer
-// (Wav2Mel.extract_mel appends one copy of the last frame, FCPE.py:808-812)
-int64_t fcpe_frames(const Ctx& c, int64_t n) {
-  const FcpeCfg& g = c.fcfg;
+// How Wav2Mel.extract_mel frames n samples (FCPE.py:805-813; STFT.get_mel :133-168): pl / pr samples of padding (zeros
+// when the reflection would not fit), Fs STFT frames and F in all: n / hop + 1, or Fs + 1 when that is fewer (:808-812)
+struct Framing {
+  int64_t pl, pr, Fs, F;
+  bool zero_pad;
+};
+static Framing framing(const FcpeCfg& g, int64_t n) {
   const int64_t pl = (g.win - g.hop) / 2, pr = std::max<int64_t>((g.win - g.hop + 1) / 2, g.win - n - pl);
-  const int64_t fs = (n + pl + pr - g.win) / g.hop + 1, nf = n / g.hop + 1;
-  return nf > fs ? fs + 1 : nf;
+  const int64_t Fs = (n + pl + pr - g.win) / g.hop + 1, nf = n / g.hop + 1;
+  return {pl, pr, Fs, nf > Fs ? Fs + 1 : nf, pr >= n};
 }
+
+// what every entry checks: the model, the decoder mode and the rows (nv == nullptr: B of n samples; none by default)
+static Rows checked_rows(const Ctx& c, int m, const int64_t* nv = nullptr, int64_t n = 1, int B = 1, int64_t ld = 0) {
+  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
+  if (m < 0 || m > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
+  if (B > 4096) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
+  const Rows r = nv ? Rows("fcpe", nv, B, ld) : Rows("fcpe", n, B, ld);
+  if (r.n_min < 1 || r.n_max > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
+  return r;
+}
+
+// The mel stage: B streams, the longest of n samples and framed as `fr`, -> the log-mel [B][F][n_mels], each stream
+// padded and framed on its own, with a copy of its last frame when the STFT gives one fewer than F. dn / dF (device):
+// stream b has dn[b] samples and dF[b] >= F_min frames; row F_b - 1 = row F_b - 2, zeros from F_b on.
+static void mel_stage(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, const Framing& fr, const int32_t* dn,
+               const int32_t* dF, int F_min, float* mel, hipStream_t s) {
+  const FcpeCfg& g = c.fcfg;
+  const MelSpec ms = mel_spec(g);
+  if ((int64_t)B * fr.F > INT32_MAX / std::max(4 * g.n_chans, 2 * ms.nbin()))
+    throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  const int F = (int)fr.F, Fm = (int)std::min(fr.Fs, fr.F);
+  mel_forward(c, ms, "fc.", audio, n, ld, B, MelFrames{fr.pl, fr.pr, fr.zero_pad, Fm, F, true}, mel, s, dn);
+  if (dF) check(fcpe_mel_tail_v(mel, B, dF, F, F_min, g.n_mels, s), "fcpe_mel_tail");
+  else if (F > Fm) check(fcpe_dup_last_frame(mel, B, F, g.n_mels, s), "fcpe_dup_last_frame");
+}
+
+// FCPEF0Predictor.post_process of the raw track [F] (or nothing, when it was written to f0 itself) -> f0 [n]
+static void post_process(Ctx& c, const double* raw, int64_t F, int64_t n, double* f0, hipStream_t s) {
+  if (raw == f0) return;
+  int* links = c.buf<int>("fc.links", (size_t)2 * n, s);
+  check(fcpe_post_process(raw, (int)F, (int)n, c.fcfg.hop, c.fcfg.sr, links, f0, s), "fcpe_post_process");
+}
+
+int64_t fcpe_frames(const Ctx& c, int64_t n) { return framing(c.fcfg, n).F; }
 
 int64_t fcpe_decode_run(Ctx& c, const float* sal, int64_t F, float thr, int mode, int interp_uv, int64_t pad_to,
                         double* f0, hipStream_t s) {
-  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
-  const FcpeCfg& g = c.fcfg;
-  if (F < 1 || F > INT32_MAX / g.out_dims || pad_to > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
-  if (!interp_uv) {
-    check(fcpe_decode(sal, (int)F, g.out_dims, c.W("fc.cent"), thr, mode, f0, s), "fcpe_decode");
-    return F;
-  }
-  const int64_t n = pad_to > 0 ? pad_to : F;
-  double* raw = c.buf<double>("fc.f0raw", (size_t)F, s);
-  int* links = c.buf<int>("fc.links", (size_t)2 * n, s);
-  check(fcpe_decode(sal, (int)F, g.out_dims, c.W("fc.cent"), thr, mode, raw, s), "fcpe_decode");
-  check(fcpe_post_process(raw, (int)F, (int)n, g.hop, g.sr, links, f0, s), "fcpe_post_process");
+  checked_rows(c, mode);
+  const int nb = c.fcfg.out_dims;
+  if (F < 1 || F > INT32_MAX / nb || pad_to > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  const int64_t n = interp_uv && pad_to > 0 ? pad_to : F;
+  double* raw = interp_uv ? c.buf<double>("fc.f0raw", (size_t)F, s) : f0;
+  check(fcpe_decode(sal, (int)F, nb, c.W("fc.cent"), thr, mode, raw, s), "fcpe_decode");
+  post_process(c, raw, F, n, f0, s);
   return n;
 }
 
-// Wav2Mel.extract_mel (FCPE.py:790-813; STFT.get_mel :133-168) on B streams of n samples (row b at audio + b ld): the
-// log-mel [B][F][n_mels] into `mel` (F = fcpe_frames(n) rows per stream). Every stream is padded, framed and, when the
-// STFT gives one frame fewer than F, extended by a copy of its own last frame: the STFT conv runs in launch_conv's
-// batch form over the streams' own padded rows, so no frame reads across a stream boundary. Returns F.
 int fcpe_mel(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float* mel, hipStream_t s) {
-  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-  const FcpeCfg& g = c.fcfg;
-  if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
-  if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
-  const MelSpec ms = mel_spec(g);
-  const int64_t pl = (g.win - g.hop) / 2, pr = std::max<int64_t>((g.win - g.hop + 1) / 2, g.win - n - pl);
-  const int Fs = (int)((n + pl + pr - g.win) / g.hop + 1);
-  const int F = (int)fcpe_frames(c, n), Fm = std::min(Fs, F);
-  if ((int64_t)B * F > INT32_MAX / std::max(4 * g.n_chans, 2 * ms.nbin()))
-    throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
-  // torch pads with zeros when the reflection would not fit (:138)
-  mel_forward(c, ms, "fc.", audio, n, ld, B, MelFrames{pl, pr, pr >= n, Fm, F, true}, mel, s);
-  if (F > Fm) check(fcpe_dup_last_frame(mel, B, F, g.n_mels, s), "fcpe_dup_last_frame");
-  return F;
+  checked_rows(c, 0, nullptr, n, B, ld);
+  const Framing fr = framing(c.fcfg, n);
+  mel_stage(c, audio, n, ld, B, fr, nullptr, nullptr, 0, mel, s);
+  return (int)fr.F;
 }
 
 // FCPE.forward (:657-665) on mel [B][F][n_mels] -> salience [B][F][out_dims]. dF (device, optional): stream b has
@@ -202,127 +218,93 @@ static void fcpe_net(Ctx& c, const float* mel, int F, int B, const int* dF, floa
   launch_conv(c, a, false, s);
 }
 
-// FCPEInfer.__call__ on B streams of n samples (row b at audio + b ld): f0 [B][F] (the raw track: zeros where
-// unvoiced), salience [B][F][out_dims] optional. Activations are [B][F][C] with the streams back to back, so
-// LayerNorm and every linear run once on the B F rows; what the network reduces or pads over time -- the mel's
-// framing, the k = 3 convs' zero padding (launch_conv's batch form), the GroupNorm statistics, the Performer's ctx /
-// ksum / row maximum / denominator, the depthwise conv's zero padding -- is per stream. B = 1 is fcpe_forward.
+// The one FCPE pass behind fcpe_forward, _b and _v (runtime.h), FCPEInfer.__call__: mel -> network -> decode on the B
+// rows `r` describes (row b at audio + b ld). The raw track of row b lands at f0 + b ldf, its salience (optional) at
+// sal_out + b ld_sal out_dims. Activations are [B][F][C] with the rows back to back, so LayerNorm and every linear run
+// once on the B F rows; what the network reduces or pads over time -- the mel's framing, the k = 3 convs' zero padding
+// (launch_conv's batch form), the GroupNorm statistics, the Performer's ctx / ksum / row maximum / denominator, the
+// depthwise conv's zero padding -- is per row.
+// nv == nullptr: B rows of r.n_max samples; the network writes the caller's salience (or its staging, below) in place.
+// nv[B] (host): row b has nv[b] samples and F_b = fcpe_frames(nv[b]) frames inside [B][F_max][C]; nothing written past
+// F_b. Per row:
+//   - the mel reflect-pads the row at its own end (samples past nv[b] are never read) and ends it as mel_stage says;
+//   - the network takes the rows' frame counts (fcpe_net); LayerNorm and every linear run once over the B F_max rows;
+//   - the decode and the salience copy stop at F_b.
+// A row of the zero-padding branch among rows of different lengths is refused: mel_forward's per-row form reflects.
+static int64_t fcpe_rows(Ctx& c, const float* audio, const Rows& r, const int64_t* nv, int64_t ld, float thr, int mode,
+                         double* f0, int64_t ldf, float* sal_out, int64_t ld_sal, hipStream_t s) {
+  const FcpeCfg& g = c.fcfg;
+  const int B = r.B, nb = g.out_dims;
+  // the zero-padding branch is a whole-batch form only
+  if (nv && framing(g, r.n_min).zero_pad)
+    throw Error(RVCX_E_SHAPE, "fcpe: a row of " + std::to_string(r.n_min) +
+                                  " samples takes the mel's zero padding, which rows of different lengths do not run");
+  const Framing fr = framing(g, r.n_max);
+  if (fr.F > ldf) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(fr.F) + " frames per row");
+  if (sal_out && fr.F > ld_sal)
+    throw Error(RVCX_E_CAPACITY, "fcpe: salience needs " + std::to_string(fr.F) + " frames per row");
+  const int F = (int)fr.F;
+  // the strides the pass itself writes: the caller's with lengths, else back to back and staged where those are wider
+  const int64_t sf = nv ? ldf : F, ss = nv ? ld_sal : F;
+  const Staged<double> f0s(c, "fc.f0v", f0, ldf, sf, B, s);
+  const Staged<float> sals(c, "fc.salv", sal_out, ld_sal * nb, ss * nb, B, s);
+  // the reflect branch: the STFT gives n / hop frames, one fewer than F_b, for every row
+  if (nv && fr.Fs != F - 1) throw Error(RVCX_E_SHAPE, "fcpe: unexpected framing");
+  // per-row lengths on device: n | F
+  LenCols len(2, nv ? B : 0);
+  const int32_t *dn = nullptr, *dF = nullptr;
+  int F_min = F;
+  if (nv) {
+    for (int b = 0; b < B; ++b) {
+      len.at(0, b) = (int32_t)nv[b];
+      len.at(1, b) = (int32_t)framing(g, nv[b]).F;
+      F_min = std::min(F_min, len.at(1, b));
+    }
+    len.upload(c, "fc.lens", s);
+    dn = len.col(0), dF = len.col(1);
+  }
+  float* mel = c.buf<float>("fc.mel", (size_t)B * F * g.n_mels, s);
+  mel_stage(c, audio, r.n_max, ld, B, fr, dn, dF, F_min, mel, s);
+  float* sal = !nv && sal_out ? sals.p : c.buf<float>("fc.sal", (size_t)B * F * nb, s);
+  fcpe_net(c, mel, F, B, dF, sal, s);
+  if (nv) {
+    if (sal_out)
+      for (int b = 0; b < B; ++b)
+        RVCX_HIP(hipMemcpyAsync(sal_out + (size_t)b * ld_sal * nb, sal + (size_t)b * F * nb,
+                                (size_t)len.at(1, b) * nb * sizeof(float), hipMemcpyDeviceToDevice, s));
+    check(fcpe_decode_v(sal, B, dF, F, nb, c.W("fc.cent"), thr, mode, f0, ldf, s), "fcpe_decode");
+  } else {
+    // the decoders are row-wise: B F rows, f0 [B][F]
+    check(fcpe_decode(sal, B * F, nb, c.W("fc.cent"), thr, mode, f0s.p, s), "fcpe_decode");
+  }
+  f0s.copy_out(s);
+  sals.copy_out(s);
+  return F;
+}
+
 int64_t fcpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t ld, int B, float thr, int mode, double* f0,
                        int64_t cap, float* sal_out, hipStream_t s) {
-  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
-  const FcpeCfg& g = c.fcfg;
-  if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
-  if (B < 1 || B > 4096 || ld < n) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
-  const int F = (int)fcpe_frames(c, n);
-  if (F > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(F) + " frames per stream");
-  float* mel = c.buf<float>("fc.mel", (size_t)B * F * g.n_mels, s);
-  fcpe_mel(c, audio, n, ld, B, mel, s);
-  float* sal = sal_out ? sal_out : c.buf<float>("fc.sal", (size_t)B * F * g.out_dims, s);
-  fcpe_net(c, mel, F, B, nullptr, sal, s);
-  // the decoders are row-wise: B F rows, f0 [B][F]
-  check(fcpe_decode(sal, B * F, g.out_dims, c.W("fc.cent"), thr, mode, f0, s), "fcpe_decode");
-  return F;
+  const Rows r = checked_rows(c, mode, nullptr, n, B, ld);
+  const int64_t lf = std::min(cap, fcpe_frames(c, n));  // back to back; a cap below the frame count is refused
+  return fcpe_rows(c, audio, r, nullptr, ld, thr, mode, f0, lf, sal_out, lf, s);
 }
 
-// FCPEInfer.__call__ on B utterances of nv[b] samples (host array; row b at audio + b ld) in one launch set: row b has
-// F_b = fcpe_frames(nv[b]) frames inside [B][F_max][C]. Its f0 [F_b] lands at f0 + b ldf, its salience (optional) at
-// sal_out + b ld_sal out_dims; nothing is written past F_b. Per row:
-//   - the mel reflect-pads the row at its own end (samples past nv[b] are never read); its STFT frames past the row's
-//     own are computed on the zeros after it and overwritten: row F_b - 1 = a copy of row F_b - 2, rows from F_b on zero;
-//   - the network takes the rows' frame counts (fcpe_net); LayerNorm and every linear run once over the B F_max rows;
-//   - the decode stops at F_b.
-// Equal lengths are fcpe_forward_b, bit for bit, unless `sizing` (rvcx_workspace_bytes sizes the ragged form). A row of
-// the mel's zero-padding branch among rows of different lengths is refused: mel_forward's per-row form reflects.
 int64_t fcpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t ld, int B, float thr, int mode, double* f0,
                        int64_t ldf, float* sal_out, int64_t ld_sal, hipStream_t s, bool sizing) {
-  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-  if (mode < 0 || mode > 1) throw Error(RVCX_E_INVALID, "fcpe: decoder_mode must be 0 (local_argmax) or 1 (argmax)");
-  if (B < 1 || B > 4096) throw Error(RVCX_E_INVALID, "fcpe: bad batch");
-  const FcpeCfg& g = c.fcfg;
-  int64_t n_max = 0, n_min = INT64_MAX;
-  for (int b = 0; b < B; ++b) {
-    if (nv[b] < 1 || nv[b] > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
-    n_max = std::max(n_max, nv[b]);
-    n_min = std::min(n_min, nv[b]);
-  }
-  const bool equal = n_min == n_max;
-  if (ld < n_max && B > 1) throw Error(RVCX_E_INVALID, "fcpe: row stride shorter than the longest row");
-  const int64_t pl = (g.win - g.hop) / 2, pr = (g.win - g.hop + 1) / 2;
-  const bool ragged = B > 1 && (!equal || sizing);
-  // the zero-padding branch (pr >= n in fcpe_mel) is a whole-batch form only
-  if (ragged && std::max<int64_t>(pr, g.win - n_min - pl) >= n_min)
-    throw Error(RVCX_E_SHAPE, "fcpe: a row of " + std::to_string(n_min) +
-                                  " samples takes the mel's zero padding, which rows of different lengths do not run");
-  const int64_t F_max = fcpe_frames(c, n_max);
-  if (F_max > ldf) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(F_max) + " frames per row");
-  if (sal_out && F_max > ld_sal)
-    throw Error(RVCX_E_CAPACITY, "fcpe: salience needs " + std::to_string(F_max) + " frames per row");
-  if (!ragged) {
-    const int64_t F = F_max;
-    const bool f0_tight = ldf == F || B == 1, sal_tight = !sal_out || ld_sal == F || B == 1;
-    double* f0b = f0_tight ? f0 : c.buf<double>("fc.f0v", (size_t)B * F, s);
-    float* sb = sal_tight ? sal_out : c.buf<float>("fc.salv", (size_t)B * F * g.out_dims, s);
-    if (B == 1) {
-      fcpe_forward(c, audio, n_max, thr, mode, 0, 0, f0b, sb, F, s);
-    } else {
-      fcpe_forward_b(c, audio, n_max, ld, B, thr, mode, f0b, F, sb, s);
-    }
-    if (!f0_tight)
-      RVCX_HIP(hipMemcpy2DAsync(f0, (size_t)ldf * sizeof(double), f0b, (size_t)F * sizeof(double),
-                                (size_t)F * sizeof(double), B, hipMemcpyDeviceToDevice, s));
-    if (!sal_tight)
-      RVCX_HIP(hipMemcpy2DAsync(sal_out, (size_t)ld_sal * g.out_dims * sizeof(float), sb,
-                                (size_t)F * g.out_dims * sizeof(float), (size_t)F * g.out_dims * sizeof(float), B,
-                                hipMemcpyDeviceToDevice, s));
-    return F;
-  }
-  const MelSpec ms = mel_spec(g);
-  if ((int64_t)B * F_max > INT32_MAX / std::max(4 * g.n_chans, 2 * ms.nbin()))
-    throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
-  const int F = (int)F_max;
-  // the reflect branch: the STFT gives n / hop frames, one fewer than F_b, for every row
-  const int Fs = (int)((n_max + pl + pr - g.win) / g.hop + 1);
-  if (Fs != F - 1) throw Error(RVCX_E_SHAPE, "fcpe: unexpected framing");
-  // per-row lengths on device: n | F
-  std::vector<int32_t> hl(2 * (size_t)B);
-  int F_min = F;
-  for (int b = 0; b < B; ++b) {
-    hl[b] = (int32_t)nv[b];
-    hl[B + b] = (int32_t)fcpe_frames(c, nv[b]);
-    F_min = std::min(F_min, hl[B + b]);
-  }
-  int32_t* dl = c.buf<int32_t>("fc.lens", hl.size(), s);
-  RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
-  const int32_t *dn = dl, *dF = dl + B;
-  float* mel = c.buf<float>("fc.mel", (size_t)B * F * g.n_mels, s);
-  mel_forward(c, ms, "fc.", audio, n_max, ld, B, MelFrames{pl, pr, false, Fs, F, true}, mel, s, dn);
-  check(fcpe_mel_tail_v(mel, B, dF, F, F_min, g.n_mels, s), "fcpe_mel_tail");
-  float* sal = c.buf<float>("fc.sal", (size_t)B * F * g.out_dims, s);
-  fcpe_net(c, mel, F, B, dF, sal, s);
-  if (sal_out)
-    for (int b = 0; b < B; ++b)
-      RVCX_HIP(hipMemcpyAsync(sal_out + (size_t)b * ld_sal * g.out_dims, sal + (size_t)b * F * g.out_dims,
-                              (size_t)hl[B + b] * g.out_dims * sizeof(float), hipMemcpyDeviceToDevice, s));
-  check(fcpe_decode_v(sal, B, dF, F, g.out_dims, c.W("fc.cent"), thr, mode, f0, ldf, s), "fcpe_decode");
-  return F;
+  const Rows r = checked_rows(c, mode, nv, 0, B, ld);
+  const bool ragged = B > 1 && (!r.equal || sizing);
+  return fcpe_rows(c, audio, r, ragged ? nv : nullptr, ld, thr, mode, f0, ldf, sal_out, ld_sal, s);
 }
 
-// One utterance: the B = 1 case of fcpe_forward_b, then FCPEF0Predictor.post_process when interp_uv.
 int64_t fcpe_forward(Ctx& c, const float* audio, int64_t n, float thr, int mode, int interp_uv, int64_t pad_to,
                      double* f0, float* sal_out, int64_t cap, hipStream_t s) {
-  if (!c.ready[M]) throw Error(RVCX_E_STATE, "fcpe weights not finalized");
-  const FcpeCfg& g = c.fcfg;
-  if (n < 1 || n > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: input length out of range");
-  const int64_t F = fcpe_frames(c, n);
-  const int64_t n_out = interp_uv && pad_to > 0 ? pad_to : F;
+  const Rows r = checked_rows(c, mode, nullptr, n, 1, n);
+  const int64_t F = fcpe_frames(c, n), n_out = interp_uv && pad_to > 0 ? pad_to : F;
   if (n_out > cap) throw Error(RVCX_E_CAPACITY, "fcpe: output needs " + std::to_string(n_out) + " frames");
-  if (!interp_uv) return fcpe_forward_b(c, audio, n, n, 1, thr, mode, f0, cap, sal_out, s);
-  if (n_out > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
-  double* raw = c.buf<double>("fc.f0raw", (size_t)F, s);
-  int* links = c.buf<int>("fc.links", (size_t)2 * n_out, s);
-  fcpe_forward_b(c, audio, n, n, 1, thr, mode, raw, F, sal_out, s);
-  check(fcpe_post_process(raw, (int)F, (int)n_out, g.hop, g.sr, links, f0, s), "fcpe_post_process");
+  if (interp_uv && n_out > INT32_MAX / 2) throw Error(RVCX_E_SHAPE, "fcpe: too many frames");
+  double* raw = interp_uv ? c.buf<double>("fc.f0raw", (size_t)F, s) : f0;
+  fcpe_rows(c, audio, r, nullptr, n, thr, mode, raw, F, sal_out, F, s);
+  post_process(c, raw, F, n_out, f0, s);
   return n_out;
 }
 

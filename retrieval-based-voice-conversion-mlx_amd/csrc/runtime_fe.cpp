@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "model_build.h"
+#include "rows.h"
 
 namespace rvcx {
 
@@ -116,19 +117,17 @@ static HubertRun front(Ctx& c, const float* audio, int64_t n, const int64_t* nv,
   Len T1((int)T[1]);  // conv0 frames per sequence
   if (nv) {
     // per-sequence conv0 frames | output frames on device, and the [B][L] mask of valid output frames
-    std::vector<int32_t> hl(2 * (size_t)B);
+    LenCols len(2, B);
     for (int r = 0; r < B; ++r) {
-      if (nv[r] > n) throw Error(RVCX_E_INVALID, "hubert: a row is longer than the batch's longest");
       const int64_t Lr = hubert_frames(nv[r]);
       if (Lr < 1) throw Error(RVCX_E_SHAPE, "hubert: input too short (" + std::to_string(nv[r]) + " samples)");
-      hl[r] = (int32_t)((nv[r] - HK[0]) / HS[0] + 1);
-      hl[B + r] = (int32_t)Lr;
+      len.at(0, r) = (int32_t)((nv[r] - HK[0]) / HS[0] + 1);
+      len.at(1, r) = (int32_t)Lr;
     }
-    int32_t* dl = c.buf<int32_t>("hb.lens", 2 * (size_t)B, s);
-    RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
+    len.upload(c, "hb.lens", s);
     mask = c.buf<float>("hb.mask", (size_t)BL, s);
-    check(seq_mask(dl + B, mask, B, L, s), "hubert_mask");
-    T1 = Len(dl);
+    check(seq_mask(len.col(1), mask, B, L, s), "hubert_mask");
+    T1 = Len(len.col(0));
   }
   // conv0 -> GroupNorm(512, 512) -> GELU in three launches (statistics, finalize, apply), the conv recomputed by each
   check(hubert_conv0_gn_gelu(audio, lda, c.W("hb.conv0"), T1, (int)T[1], HCONV, c.W("hb.gn.g"), c.W("hb.gn.b"), 1e-5f,
@@ -257,7 +256,7 @@ void hubert_layers(Ctx& c, const HubertRun& run, int l0, int l1, hipStream_t s) 
 // v2: last_hidden_state; v1: final_proj (pipeline.py:331-334)
 int64_t hubert_tail(Ctx& c, const HubertRun& run, hipStream_t s) {
   const int BL = run.B * run.L;
-  const int version = run.version, outD = version == 1 ? 256 : HD;
+  const int version = run.version;
   float* hs = c.buf<float>("hb.hs", (size_t)BL * HD, s);
   float* feats = run.feats;
   if (version == 1) {
@@ -266,7 +265,6 @@ int64_t hubert_tail(Ctx& c, const HubertRun& run, hipStream_t s) {
     fp.lds_pad = run.lds_pad;
     run1(c, fp, s);
   }  // v2: the last layer wrote feats (hubert_layers)
-  (void)outD;
   return run.L;
 }
 
@@ -282,31 +280,20 @@ int64_t hubert_forward(Ctx& c, const float* audio, int64_t n, int version, float
   return hubert_forward_b(c, audio, n, n, 1, version, feats, cap, s);
 }
 
-// B sequences of nv[b] samples (host array): sequence b's L_b = hubert_frames(nv[b]) feature rows at
-// feats + b*ld_rows*outD, one launch set for all rows. Returns the longest sequence's row count; rows_out[b] = L_b.
-// The rows of a sequence past L_b (up to the longest's) are written and hold no meaning.
+// (runtime.h) The rows of a sequence past its L_b, up to the longest's, are written and hold no meaning.
 int64_t hubert_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, int version, float* feats,
                          int64_t ld_rows, int64_t* rows_out, hipStream_t s, bool force_ragged) {
-  if (B < 1) throw Error(RVCX_E_INVALID, "hubert: batch < 1");
-  int64_t n_max = 0;
-  bool equal = true;
-  for (int b = 0; b < B; ++b) {
-    n_max = std::max(n_max, nv[b]);
-    equal = equal && nv[b] == nv[0];
-  }
-  if (lda < n_max && B > 1) throw Error(RVCX_E_INVALID, "hubert: row stride shorter than the longest row");
-  const int64_t L = hubert_frames(n_max);
+  const Rows r("hubert", nv, B, lda);
+  const int64_t L = hubert_frames(r.n_max);
   if (L > ld_rows) throw Error(RVCX_E_CAPACITY, "hubert: output needs " + std::to_string(L) + " rows per sequence");
   const int outD = version == 1 ? 256 : HD;
   // the layers write [B][L][outD] back to back: straight into the caller's rows when their stride is L
-  float* dst = (ld_rows == L || B == 1) ? feats : c.buf<float>("hb.featv", (size_t)B * L * outD, s);
+  const Staged<float> dst(c, "hb.featv", feats, ld_rows * outD, L * outD, B, s);
   // equal lengths need no masks: the equal-length form, bit for bit
-  const HubertRun r = front(c, audio, n_max, equal && !force_ragged ? nullptr : nv, lda, B, version, dst, L, s);
-  hubert_layers(c, r, 0, HUBERT_LAYERS, s);
-  hubert_tail(c, r, s);
-  if (dst != feats)
-    RVCX_HIP(hipMemcpy2DAsync(feats, (size_t)ld_rows * outD * sizeof(float), dst, (size_t)L * outD * sizeof(float),
-                              (size_t)L * outD * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+  const HubertRun run = front(c, audio, r.n_max, r.equal && !force_ragged ? nullptr : nv, lda, B, version, dst.p, L, s);
+  hubert_layers(c, run, 0, HUBERT_LAYERS, s);
+  hubert_tail(c, run, s);
+  dst.copy_out(s);
   if (rows_out)
     for (int b = 0; b < B; ++b) rows_out[b] = hubert_frames(nv[b]);
   return L;
@@ -648,20 +635,57 @@ static void e2e_chunk(Ctx& c, float* img, int Fc, float* sal, hipStream_t s, con
   run1(c, f, s);
 }
 
-// B equal-length sequences: audio row b at audio + b*lda; f0 row b at f0 + b*F; hidden row b at hidden + b*F*360.
-int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
-                        int64_t cap, float* hidden, hipStream_t s, GruHook beside_gru) {
-  if (B < 1) throw Error(RVCX_E_INVALID, "rmvpe: batch < 1");
-  if (n < NFFT / 2 + 1) throw Error(RVCX_E_SHAPE, "rmvpe: input shorter than 513 samples");
-  const int F = (int)(1 + n / HOP);
-  if (F > cap) throw Error(RVCX_E_CAPACITY, "rmvpe: output needs " + std::to_string(F) + " frames");
+// The one RMVPE pass: mel -> frame padding -> bn0 -> E2E, 64 images at a time -> salience copy -> decode, on the B rows
+// `r` describes (row b at audio + b*lda). f0 row b lands at f0 + b*ldf and its salience (optional) at
+// hidden + b*ld_hidden*360. rmvpe_forward, _b and _v (runtime.h) are its entries.
+// nv == nullptr: B rows of r.n_max samples; frames past mel2hidden's 32000-frame chunk (RMVPE.py:459-481) run by chunk.
+// nv[B] (host): row b has nv[b] <= r.n_max samples, F_b = 1 + nv[b] / 160 frames, and runs as an image of
+// Fp_b = 32 ceil(F_b / 32) frames inside [B][Fp_max][128]. In every stage a row's valid values are those of this pass
+// on that row alone, up to summation order:
+//   - the mel reflect-pads each row at its own end (samples past nv[b] are never read); the STFT and mel GEMMs run over
+//     all B F_max frames, a row's frames past F_b on the zeros after it (finite, never read);
+//   - the frame padding reflects about each row's own F_b up to Fp_b, zeros after;
+//   - the U-Net and the BiGRU take the rows' heights (e2e_chunk);
+//   - the decode and the salience copy stop at F_b.
+// The 32000-frame chunking is not taken in this form: a row that long is refused.
+static int64_t rmvpe_rows(Ctx& c, const float* audio, const Rows& r, const int64_t* nv, int64_t lda, float thred,
+                          double* f0, int64_t ldf, float* hidden, int64_t ld_hidden, hipStream_t s, GruHook hook) {
+  if (r.n_min < NFFT / 2 + 1) throw Error(RVCX_E_SHAPE, "rmvpe: input shorter than 513 samples");
+  const int B = r.B;
+  const int64_t n = r.n_max, F64 = 1 + n / HOP;
+  if (F64 > ldf) throw Error(RVCX_E_CAPACITY, "rmvpe: output needs " + std::to_string(F64) + " frames per row");
+  if (hidden && F64 > ld_hidden)
+    throw Error(RVCX_E_CAPACITY, "rmvpe: salience needs " + std::to_string(F64) + " frames per row");
+  const int chunk = 32000;
+  if (nv && 32 * ((F64 - 1) / 32 + 1) > chunk)
+    throw Error(RVCX_E_SHAPE, "rmvpe: a row of more than 32000 padded frames takes the single-row call");
+  const int F = (int)F64, Fp = 32 * ((F - 1) / 32 + 1);
+  // the strides the pass itself writes: the caller's with lengths, else back to back and staged where those are wider
+  const int64_t sf = nv ? ldf : F, sh = nv ? ld_hidden : F;
+  const Staged<double> f0s(c, "rm.f0v", f0, ldf, sf, B, s);
+  const Staged<float> hids(c, "rm.hidv", hidden, ld_hidden * NCLS, sh * NCLS, B, s);
+  // per-row lengths on device: n | F | the image heights Fp >> level, level 0 .. LEVELS
+  LenCols len(3 + LEVELS, nv ? B : 0);
+  const int32_t *dn = nullptr, *dF = nullptr, *dH = nullptr;
+  if (nv) {
+    for (int b = 0; b < B; ++b) {
+      const int Fb = (int)(1 + nv[b] / HOP), Fpb = 32 * ((Fb - 1) / 32 + 1);
+      if (Fpb - Fb >= Fb) check(hipErrorInvalidValue, "pad_frames");  // reflect_pad_rows' refusal of that row alone
+      len.at(0, b) = (int32_t)nv[b];
+      len.at(1, b) = Fb;
+      for (int l = 0; l <= LEVELS; ++l) len.at(2 + l, b) = Fpb >> l;
+    }
+    len.upload(c, "rm.lens", s);
+    dn = len.col(0), dF = len.col(1), dH = len.col(2);
+  }
   // MelSpectrogram (RMVPE.py:388-417): centre reflect pad 512, F frames, the mel GEMM over all B F rows at once
   float* mel = c.buf<float>("rm.melout", (size_t)B * F * NMEL, s);
-  mel_forward(c, MEL, "rm.", audio, n, lda, B, MelFrames{NFFT / 2, NFFT / 2, false, F, F, false}, mel, s);
+  mel_forward(c, MEL, "rm.", audio, n, lda, B, MelFrames{NFFT / 2, NFFT / 2, false, F, F, false}, mel, s, dn);
   // mel2hidden (RMVPE.py:445-482): reflect-pad frames to a multiple of 32, E2E per 32000-frame chunk
-  const int Fp = 32 * ((F - 1) / 32 + 1);
   float* img = c.buf<float>("rm.img", (size_t)B * Fp * NMEL, s);
-  if (Fp > F) {
+  if (nv) {
+    check(reflect_pad_rows_v(mel, dF, dH, F, Fp, NMEL, img, s, B), "pad_frames");
+  } else if (Fp > F) {
     check(reflect_pad_rows(mel, F, NMEL, Fp - F, img, s, B), "pad_frames");
   } else {
     RVCX_HIP(hipMemcpyAsync(img, mel, (size_t)B * F * NMEL * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -669,13 +693,13 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
   const auto& bn0 = c.host[2].at("__bn0__").v;
   check(affine_inplace(img, (long long)B * Fp * NMEL, bn0[0], bn0[1], s), "bn0");
   float* sal = c.buf<float>("rm.sal", (size_t)B * Fp * NCLS, s);
-  const int chunk = 32000;
   // the first E2E pass takes the caller's hook; the later ones get none
-  auto hook_once = [&] { return std::exchange(beside_gru, nullptr); };
+  auto hook_once = [&] { return std::exchange(hook, nullptr); };
   if (Fp <= chunk) {
     for (int b0 = 0; b0 < B; b0 += 64) {  // the BiGRU keeps 4 co-resident workgroups per sequence
       const int nb = std::min(64, B - b0);
-      e2e_chunk(c, img + (size_t)b0 * Fp * NMEL, Fp, sal + (size_t)b0 * Fp * NCLS, s, hook_once(), nb);
+      e2e_chunk(c, img + (size_t)b0 * Fp * NMEL, Fp, sal + (size_t)b0 * Fp * NCLS, s, hook_once(), nb,
+                dH ? dH + b0 : nullptr, B);
     }
   } else {
     // every chunk is an independent E2E pass (RMVPE.py:459-481: the U-Net pads each chunk's edges, the BiGRU
@@ -696,94 +720,29 @@ int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int 
   }
   if (hidden)
     for (int b = 0; b < B; ++b)
-      RVCX_HIP(hipMemcpyAsync(hidden + (size_t)b * F * NCLS, sal + (size_t)b * Fp * NCLS, (size_t)F * NCLS * sizeof(float),
-                              hipMemcpyDeviceToDevice, s));
-  check(rmvpe_decode(sal, F, NCLS, thred, f0, s, B, Fp), "decode");
+      RVCX_HIP(hipMemcpyAsync(hids.p + (size_t)b * sh * NCLS, sal + (size_t)b * Fp * NCLS,
+                              (size_t)(nv ? len.at(1, b) : F) * NCLS * sizeof(float), hipMemcpyDeviceToDevice, s));
+  check(rmvpe_decode(sal, F, NCLS, thred, f0s.p, s, B, Fp, dF, sf), "decode");
+  f0s.copy_out(s);
+  hids.copy_out(s);
   return F;
 }
 
-int64_t rmvpe_forward(Ctx& c, const float* audio, int64_t n, float thred, double* f0, int64_t cap, float* hidden,
-                      hipStream_t s, GruHook beside_gru) {
-  return rmvpe_forward_b(c, audio, n, n, 1, thred, f0, cap, hidden, s, std::move(beside_gru));
+int64_t rmvpe_forward_b(Ctx& c, const float* audio, int64_t n, int64_t lda, int B, float thred, double* f0,
+                        int64_t cap, float* hidden, hipStream_t s, GruHook beside_gru) {
+  const int64_t ld = std::min(cap, 1 + n / HOP);  // back to back; a cap below the frame count is refused as a stride is
+  return rmvpe_rows(c, audio, Rows("rmvpe", n, B, lda), nullptr, lda, thred, f0, ld, hidden, ld, s, std::move(beside_gru));
 }
 
-// B sequences of nv[b] samples in one launch set: row b has F_b = 1 + nv[b] / 160 frames and runs as an image of
-// Fp_b = 32 ceil(F_b / 32) frames inside [B][Fp_max][128]. In every stage a row's valid values are those of
-// rmvpe_forward on that row alone, up to summation order:
-//   - the mel reflect-pads each row at its own end (samples past nv[b] are never read); the STFT and mel GEMMs run over
-//     all B F_max frames, a row's frames past F_b on the zeros after it (finite, never read);
-//   - the frame padding reflects about each row's own F_b up to Fp_b, zeros after;
-//   - the U-Net and the BiGRU take the rows' heights (e2e_chunk);
-//   - the decode and the salience copy stop at F_b.
-// Rows go through 64 images at a time, as rmvpe_forward_b's. The reference's 32000-frame chunking is not taken in this
-// form: a row that long is refused. Equal lengths are rmvpe_forward_b, bit for bit, unless force_ragged
-// (rvcx_workspace_bytes sizes the ragged form).
 int64_t rmvpe_forward_v(Ctx& c, const float* audio, const int64_t* nv, int64_t lda, int B, float thred, double* f0,
                         int64_t ldf, int64_t* F_out, float* hidden, int64_t ld_hidden, hipStream_t s,
                         bool force_ragged) {
-  if (B < 1) throw Error(RVCX_E_INVALID, "rmvpe: batch < 1");
-  int64_t n_max = 0;
-  bool equal = true;
-  for (int b = 0; b < B; ++b) {
-    if (nv[b] < NFFT / 2 + 1) throw Error(RVCX_E_SHAPE, "rmvpe: input shorter than 513 samples");
-    n_max = std::max(n_max, nv[b]);
-    equal = equal && nv[b] == nv[0];
-  }
-  if (lda < n_max && B > 1) throw Error(RVCX_E_INVALID, "rmvpe: row stride shorter than the longest row");
-  const int64_t F_max64 = 1 + n_max / HOP;
-  if (F_max64 > ldf) throw Error(RVCX_E_CAPACITY, "rmvpe: output needs " + std::to_string(F_max64) + " frames per row");
-  if (hidden && F_max64 > ld_hidden)
-    throw Error(RVCX_E_CAPACITY, "rmvpe: salience needs " + std::to_string(F_max64) + " frames per row");
+  const Rows r("rmvpe", nv, B, lda);
+  const int64_t F = rmvpe_rows(c, audio, r, r.equal && !force_ragged ? nullptr : nv, lda, thred, f0, ldf, hidden,
+                               ld_hidden, s, nullptr);
   if (F_out)
     for (int b = 0; b < B; ++b) F_out[b] = 1 + nv[b] / HOP;
-  if (equal && !force_ragged) {
-    const int64_t F = F_max64;
-    const bool f0_tight = ldf == F || B == 1, hid_tight = !hidden || ld_hidden == F || B == 1;
-    double* f0b = f0_tight ? f0 : c.buf<double>("rm.f0v", (size_t)B * F, s);
-    float* hb = hid_tight ? hidden : c.buf<float>("rm.hidv", (size_t)B * F * NCLS, s);
-    rmvpe_forward_b(c, audio, n_max, lda, B, thred, f0b, F, hb, s);
-    if (!f0_tight)
-      RVCX_HIP(hipMemcpy2DAsync(f0, (size_t)ldf * sizeof(double), f0b, (size_t)F * sizeof(double),
-                                (size_t)F * sizeof(double), B, hipMemcpyDeviceToDevice, s));
-    if (!hid_tight)
-      RVCX_HIP(hipMemcpy2DAsync(hidden, (size_t)ld_hidden * NCLS * sizeof(float), hb, (size_t)F * NCLS * sizeof(float),
-                                (size_t)F * NCLS * sizeof(float), B, hipMemcpyDeviceToDevice, s));
-    return F;
-  }
-  const int chunk = 32000;
-  if (32 * ((F_max64 - 1) / 32 + 1) > chunk)
-    throw Error(RVCX_E_SHAPE, "rmvpe: a row of more than 32000 padded frames takes the single-row call");
-  const int F_max = (int)F_max64, Fp_max = 32 * ((F_max - 1) / 32 + 1);
-  // per-row lengths on device: n | F | the image heights Fp >> level, level 0 .. LEVELS
-  std::vector<int32_t> hl((size_t)(3 + LEVELS) * B);
-  for (int b = 0; b < B; ++b) {
-    const int F = (int)(1 + nv[b] / HOP), Fp = 32 * ((F - 1) / 32 + 1);
-    if (Fp - F >= F) check(hipErrorInvalidValue, "pad_frames");  // reflect_pad_rows' refusal of that row alone
-    hl[b] = (int32_t)nv[b];
-    hl[B + b] = F;
-    for (int l = 0; l <= LEVELS; ++l) hl[(size_t)(2 + l) * B + b] = Fp >> l;
-  }
-  int32_t* dl = c.buf<int32_t>("rm.lens", hl.size(), s);
-  RVCX_HIP(hipMemcpyAsync(dl, hl.data(), sizeof(int32_t) * hl.size(), hipMemcpyHostToDevice, s));
-  const int32_t *dn = dl, *dF = dl + B, *dH = dl + 2 * (size_t)B;
-  float* mel = c.buf<float>("rm.melout", (size_t)B * F_max * NMEL, s);
-  mel_forward(c, MEL, "rm.", audio, n_max, lda, B, MelFrames{NFFT / 2, NFFT / 2, false, F_max, F_max, false}, mel, s, dn);
-  float* img = c.buf<float>("rm.img", (size_t)B * Fp_max * NMEL, s);
-  check(reflect_pad_rows_v(mel, dF, dH, F_max, Fp_max, NMEL, img, s, B), "pad_frames");
-  const auto& bn0 = c.host[2].at("__bn0__").v;
-  check(affine_inplace(img, (long long)B * Fp_max * NMEL, bn0[0], bn0[1], s), "bn0");
-  float* sal = c.buf<float>("rm.sal", (size_t)B * Fp_max * NCLS, s);
-  for (int b0 = 0; b0 < B; b0 += 64) {  // the BiGRU keeps 4 co-resident workgroups per sequence
-    const int nb = std::min(64, B - b0);
-    e2e_chunk(c, img + (size_t)b0 * Fp_max * NMEL, Fp_max, sal + (size_t)b0 * Fp_max * NCLS, s, nullptr, nb, dH + b0,
-              B);
-  }
-  if (hidden)
-    for (int b = 0; b < B; ++b)
-      RVCX_HIP(hipMemcpyAsync(hidden + (size_t)b * ld_hidden * NCLS, sal + (size_t)b * Fp_max * NCLS,
-                              (size_t)hl[B + b] * NCLS * sizeof(float), hipMemcpyDeviceToDevice, s));
-  check(rmvpe_decode(sal, F_max, NCLS, thred, f0, s, B, Fp_max, dF, ldf), "decode");
-  return F_max;
+  return F;
 }
 
 }  // namespace rvcx

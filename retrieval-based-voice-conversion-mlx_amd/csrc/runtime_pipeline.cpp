@@ -11,7 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "runtime.h"
+#include "rows.h"
 
 namespace rvcx {
 
@@ -222,11 +222,7 @@ static void check_f0_method(const Ctx& c, const rvcx_pipeline_opts& o) {
   if (!c.scfg.f0) return;
   if ((o.f0_method == 1 || o.f0_method == 2) && !c.ready[RVCX_MODEL_CREPE])
     throw Error(RVCX_E_STATE, "pipeline: f0_method crepe but no CREPE weights finalized");
-  if (o.f0_method == 3 || o.f0_method == 5) {
-    if (!c.ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "pipeline: f0_method fcpe but no FCPE weights finalized");
-    if (c.fcfg.sr != 16000 || c.fcfg.hop != 160)  // the pipeline's pitch frames are 160 samples at 16 kHz
-      throw Error(RVCX_E_SHAPE, "pipeline: the FCPE model must run at 16 kHz with hop_size 160");
-  }
+  if (o.f0_method == 3 || o.f0_method == 5) require_fcpe_pitch_frames(c, "pipeline");
 }
 
 // the option checks of both pipeline forms, for utterances of n samples
@@ -246,7 +242,7 @@ static void check_pipeline_opts(const Ctx& c, const rvcx_pipeline_opts& o, int64
 static void f0_row(Ctx& c, const rvcx_pipeline_opts& o, const float* audio, int64_t m, double* f0, int64_t F,
                    const char* f0f, hipStream_t s) {
   if (o.f0_method == 3) {
-    fcpe_forward(c, audio, m, o.fcpe_threshold > 0 ? o.fcpe_threshold : 0.006f, 0, 0, 0, f0, nullptr, F, s);
+    fcpe_forward(c, audio, m, fcpe_threshold(o), 0, 0, 0, f0, nullptr, F, s);
   } else {
     crepe_forward(c, audio, m, 50.0, 1100.0, 0.1f, c.buf<float>(f0f, (size_t)F, s), f0, nullptr, nullptr, s,
                   o.f0_method == 2 ? 1 : 0);
@@ -425,7 +421,7 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
     issue_rest();
     f0_row(c, o, pad32, m, f0, F, "pl.f0f", s);
   } else {
-    rmvpe_forward(c, pad32, m, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F, nullptr, s, hubert_rest);
+    rmvpe_forward(c, pad32, m, rmvpe_threshold(o), f0, F, nullptr, s, hubert_rest);
   }
   issue_rest();  // RMVPE did not reach a BiGRU launch (cannot happen for valid input): issue it now
   pitch = c.buf<int32_t>("pl.pitch", (size_t)F, s);
@@ -526,17 +522,14 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
                            const rvcx_pipeline_opts& opts, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
                            float* hidden_out, hipStream_t s, bool sizing) {
-  if (B < 1) throw Error(RVCX_E_INVALID, "pipeline_batch: B < 1");
-  int64_t n_max = 0;
-  bool equal = true;
+  const Rows rows("pipeline_batch", nv, B, lda, 1);
+  const int64_t n_max = rows.n_max;
+  const bool equal = rows.equal;
   for (int b = 0; b < B; ++b) {
-    if (nv[b] <= 0 || (B > 1 && nv[b] > lda)) throw Error(RVCX_E_INVALID, "pipeline_batch: bad row length");
     check_pipeline_opts(c, opts, nv[b]);
     if (opts.t_max > 0 && nv[b] + 160 > opts.t_max)
       throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
     if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
-    n_max = std::max(n_max, nv[b]);
-    equal = equal && nv[b] == nv[0];
   }
   // f0_method 4: all rows in one ragged RMVPE pass; equal lengths (outside the arena query, which sizes the ragged
   // pass) and one row are method 0
@@ -578,19 +571,16 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   const int64_t F_max = 1 + m_max / W, L_max = hubert_frames(m_max);
   if (f0_out && ldf < F_max) throw Error(RVCX_E_CAPACITY, "pipeline_batch: f0 rows need " + std::to_string(F_max));
   // per-row lengths on device: L | Tv | sid | n | keep
-  int32_t* meta = c.buf<int32_t>("pb.meta", 5 * (size_t)B, s);
-  {
-    std::vector<int32_t> hm(5 * (size_t)B);
-    for (int b = 0; b < B; ++b) {
-      hm[b] = (int32_t)Lv[b];
-      hm[B + b] = (int32_t)Tvv[b];
-      hm[2 * B + b] = sids[b];
-      hm[3 * B + b] = (int32_t)nv[b];
-      hm[4 * B + b] = (int32_t)keep[b];
-    }
-    RVCX_HIP(hipMemcpyAsync(meta, hm.data(), sizeof(int32_t) * hm.size(), hipMemcpyHostToDevice, s));
+  LenCols meta(5, B);
+  for (int b = 0; b < B; ++b) {
+    meta.at(0, b) = (int32_t)Lv[b];
+    meta.at(1, b) = (int32_t)Tvv[b];
+    meta.at(2, b) = sids[b];
+    meta.at(3, b) = (int32_t)nv[b];
+    meta.at(4, b) = (int32_t)keep[b];
   }
-  const int32_t *dL = meta, *dTv = meta + B, *dsid = meta + 2 * B, *dn = meta + 3 * B, *dkeep = meta + 4 * B;
+  meta.upload(c, "pb.meta", s);
+  const int32_t *dL = meta.col(0), *dTv = meta.col(1), *dsid = meta.col(2), *dn = meta.col(3), *dkeep = meta.col(4);
   // 1. zero-phase high-pass + reflect pad per utterance, each with its own length (pipeline.py:439, :459)
   float* pad32 = c.buf<float>("pb.pad32", (size_t)B * ldm, s);
   double* pad64 = c.buf<double>("pb.pad64", (size_t)B * m_max, s);
@@ -610,16 +600,14 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   float* pitchf = nullptr;
   if (guided) {
     if (batch_fcpe) {  // straight from the padded rows; equal lengths take the equal-length batch inside
-      fcpe_forward_v(c, pad32, mv.data(), ldm, B, o.fcpe_threshold > 0 ? o.fcpe_threshold : 0.006f, 0, f0, F_max, nullptr,
-                     0, s, sizing);
+      fcpe_forward_v(c, pad32, mv.data(), ldm, B, fcpe_threshold(o), 0, f0, F_max, nullptr, 0, s, sizing);
     } else if (o.f0_method >= 1) {  // CREPE / FCPE per utterance (CREPE's frames of all rows would not batch any better)
       for (int b : order)
         f0_row(c, o, pad32 + (size_t)b * ldm, mv[b], f0 + (size_t)b * F_max, Fv[b], "pb.f0f", s);
     } else if (ragged_f0) {
-      rmvpe_forward_v(c, pad32, mv.data(), ldm, B, o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f, f0, F_max, nullptr,
-                      nullptr, 0, s, sizing);
+      rmvpe_forward_v(c, pad32, mv.data(), ldm, B, rmvpe_threshold(o), f0, F_max, nullptr, nullptr, 0, s, sizing);
     } else {
-      const float thr = o.rmvpe_threshold > 0 ? o.rmvpe_threshold : 0.03f;
+      const float thr = rmvpe_threshold(o);
       // rows of equal length together; the groups largest first (rows x frames), so the work buffers a group shares
       // with the next are not regrown
       std::vector<std::vector<int>> groups;
@@ -794,7 +782,7 @@ rvcx_pipeline_opts default_pipeline_opts() {
   std::memset(&o, 0, sizeof(o));
   o.version = 0;
   o.protect = 0.33f;
-  o.rmvpe_threshold = 0.03f;
+  o.rmvpe_threshold = RMVPE_THRESHOLD;
   o.t_pad = 16000;
   o.t_pad_tgt = 48000;
   o.t_query = 16000 * 6;
@@ -803,7 +791,7 @@ rvcx_pipeline_opts default_pipeline_opts() {
   o.f0_autotune_strength = 1.0;
   o.proposed_pitch_threshold = 155.0;
   o.volume_envelope = 1.0;
-  o.fcpe_threshold = 0.006f;
+  o.fcpe_threshold = FCPE_THRESHOLD;
   return o;
 }
 

@@ -89,7 +89,7 @@ struct RtState {
   DevBuf d_kin, d_kout, abuf[2], cbuf[2], pbuf[2], fbuf[2], sola, fade_in, offs, vol, volsq, gate, rows;
   int cur = 0;
   int f0_method = 0;  // 0 RMVPE, 1 FCPE (rvcx_rt_desc)
-  float fcpe_thr = 0.006f;
+  float fcpe_thr = FCPE_THRESHOLD;
   // the last hop's model rows [last_rows][last_n] as the noise gate read them and as it left them (the same buffer on
   // a hop without a cleaning stream): pool buffers of the context, valid until its next call (rvcx_rt_model_rows)
   const float *last_model = nullptr, *last_gated = nullptr;
@@ -178,11 +178,7 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   if (d.f0_method < 0 || d.f0_method > 1) throw Error(RVCX_E_INVALID, "stream: f0_method must be 0 (rmvpe) or 1 (fcpe)");
   if (c.scfg.f0 && d.f0_method == 0 && !c.ready[RVCX_MODEL_RMVPE])
     throw Error(RVCX_E_STATE, "stream: f0_method rmvpe but no RMVPE weights finalized");
-  if (c.scfg.f0 && d.f0_method == 1) {  // as the pipeline's f0_method 3 (runtime_pipeline.cpp check_f0_method)
-    if (!c.ready[RVCX_MODEL_FCPE]) throw Error(RVCX_E_STATE, "stream: f0_method fcpe but no FCPE weights finalized");
-    if (c.fcfg.sr != 16000 || c.fcfg.hop != 160)  // the pitch frames are 160 samples at 16 kHz
-      throw Error(RVCX_E_SHAPE, "stream: the FCPE model must run at 16 kHz with hop_size 160");
-  }
+  if (c.scfg.f0 && d.f0_method == 1) require_fcpe_pitch_frames(c, "stream");  // as the pipeline's f0_method 3
   if (d.n_streams < 1 || d.n_streams > 4096) throw Error(RVCX_E_INVALID, "stream: n_streams out of range");
   if (d.read_chunk_size < 1) throw Error(RVCX_E_INVALID, "stream: read_chunk_size < 1");
   auto r = std::make_unique<RtState>();
@@ -192,7 +188,7 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   s.B = d.n_streams;
   s.clean.assign((size_t)s.B, -1.f);
   s.f0_method = d.f0_method;
-  s.fcpe_thr = d.fcpe_threshold > 0 ? d.fcpe_threshold : 0.006f;  // the realtime filter_radius (pipeline.py:155)
+  s.fcpe_thr = or_default(d.fcpe_threshold, FCPE_THRESHOLD);
   // VoiceChanger.__init__ (core.py:351-354)
   s.block48 = d.read_chunk_size * 128;
   s.cross48 = (int)(d.cross_fade_overlap_size * AUDIO_SR);
@@ -420,12 +416,12 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   hubert_forward_b(c, conv, s.conv16, s.conv16, Ba, hubert_version_for(c), feats, L, ax);
   if (guided) {
   if (s.f0_method == 1) {  // the raw local_argmax track (pipeline.py:147-155), F = nf / 160 + 1 frames as RMVPE's
-    if (!c.ready[RVCX_MODEL_FCPE] || c.fcfg.sr != 16000 || c.fcfg.hop != 160)
+    if (fcpe_pitch_frames(c) != RVCX_OK)
       throw Error(RVCX_E_STATE, "stream: the FCPE model this group was created with has been replaced");
     if (fcpe_forward_b(c, conv + s.silence_front, nf, s.conv16, Ba, s.fcpe_thr, 0, f0, F, nullptr, st) != F)
       throw Error(RVCX_E_SHAPE, "stream: FCPE frame count differs from the pitch track's");
   } else {
-    rmvpe_forward_b(c, conv + s.silence_front, nf, s.conv16, Ba, 0.03f, f0, F, nullptr, st);
+    rmvpe_forward_b(c, conv + s.silence_front, nf, s.conv16, Ba, RMVPE_THRESHOLD, f0, F, nullptr, st);
   }
   }
   if (all) upload_plan();

@@ -84,6 +84,32 @@ class Engine(KernelTestMixin):
             return x.to(device=self.device, dtype=dtype).contiguous()
         return t.as_tensor(np.ascontiguousarray(x), dtype=dtype, device=self.device).contiguous()
 
+    def _opt(self, x, dtype, *shape):
+        """An optional argument on the device (reshaped when a shape is given); None stays None (a null pointer)."""
+        if x is None:
+            return None
+        return self._dev(x, dtype).reshape(*shape) if shape else self._dev(x, dtype)
+
+    @staticmethod
+    def _seed(seed: int):
+        return ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF)
+
+    def _pad_rows(self, audios, dtype):
+        """Rows of any lengths -> (a zero-padded [B, longest] device image, the rows' lengths); (None, []) for no rows."""
+        t = self.torch
+        rows = [self._dev(a, dtype).reshape(-1) for a in audios]
+        ns = [int(r.numel()) for r in rows]
+        if not rows:
+            return None, ns
+        a = t.zeros((len(rows), max(ns)), dtype=dtype, device=self.device)
+        for b, r in enumerate(rows):
+            a[b, : ns[b]] = r
+        return a, ns
+
+    def _need_fcpe(self):
+        if self.fcpe_cfg is None:
+            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+
     # ------------------------------------------------------------------ weights
     @staticmethod
     def _synth_desc(cfg: SynthConfig):
@@ -162,7 +188,7 @@ class Engine(KernelTestMixin):
         probs = t.empty((F, 360), dtype=t.float32, device=self.device) if want_probs else None
         fo = ctypes.c_int64(0)
         sem = {"mlx": 0, "rvc": 1}[semantics]
-        d = None if dither is None else self._dev(dither, t.float32).reshape(-1)
+        d = self._opt(dither, t.float32, -1)
         if d is not None and d.numel() != F:
             raise ValueError(f"dither needs {F} values")
         self._check(self.lib.rvcx_crepe_ex(self.ctx, a.data_ptr(), n, float(f0_min), float(f0_max), float(threshold),
@@ -183,7 +209,7 @@ class Engine(KernelTestMixin):
         F = int(p.shape[0])
         f0 = t.empty((F,), dtype=t.float32, device=self.device)
         per = t.empty((F,), dtype=t.float32, device=self.device)
-        d = None if dither is None else self._dev(dither, t.float32).reshape(-1)
+        d = self._opt(dither, t.float32, -1)
         self._check(self.lib.rvcx_crepe_decode(self.ctx, p.data_ptr(), F, float(f0_min), float(f0_max),
                                                float(threshold), {"mlx": 0, "rvc": 1}[semantics], _ptr(d),
                                                f0.data_ptr(), per.data_ptr(), self.stream()), "crepe_decode")
@@ -226,8 +252,7 @@ class Engine(KernelTestMixin):
         interp_uv: FCPEF0Predictor.post_process follows (:877-902; nearest expansion to pad_to frames, linear
         interpolation through the unvoiced ones) -> fp64 [pad_to or F]. sample_rate, when given, must be the
         model's: Wav2Mel's resampling branch (:795-803) is not built."""
-        if self.fcpe_cfg is None:
-            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        self._need_fcpe()
         if sample_rate is not None and int(sample_rate) != self.fcpe_cfg["sampling_rate"]:
             raise ValueError(f"fcpe: audio at {sample_rate} Hz, the model's mel runs at "
                              f"{self.fcpe_cfg['sampling_rate']} Hz (resampling is not supported)")
@@ -250,8 +275,7 @@ class Engine(KernelTestMixin):
         rate -> the raw track f0 fp64 [B, n // hop + 1], zeros where a frame's maximum <= threshold (and the salience
         [B, F, out_dims]). Each row is computed as rvcx_fcpe computes it alone: padding, statistics and the attention's
         sums are per stream."""
-        if self.fcpe_cfg is None:
-            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        self._need_fcpe()
         t = self.torch
         a = self._dev(audio, t.float32)
         if a.dim() != 2:
@@ -271,18 +295,12 @@ class Engine(KernelTestMixin):
         fp64 [N_b // hop + 1] on device (and the list of saliences [F_b, out_dims]), from one ragged pass over all rows
         (rvcx_fcpe_batch_v: each row is `fcpe`'s on that row alone, up to summation order; equal lengths are
         `fcpe_batch`'s bits, one row `fcpe`'s)."""
-        if self.fcpe_cfg is None:
-            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        self._need_fcpe()
         t = self.torch
-        rows = [self._dev(a, t.float32).reshape(-1) for a in audios]
-        B = len(rows)
-        if B < 1:
+        a, ns = self._pad_rows(audios, t.float32)
+        if a is None:
             return ([], []) if want_salience else []
-        ns = [int(r.numel()) for r in rows]
-        lda = max(ns)
-        a = t.zeros((B, lda), dtype=t.float32, device=self.device)
-        for b, r in enumerate(rows):
-            a[b, : ns[b]] = r
+        B, lda = a.shape
         F, nb = self._fcpe_frames(lda), self.fcpe_cfg["out_dims"]
         f0 = t.empty((B, F), dtype=t.float64, device=self.device)
         sal = t.empty((B, F, nb), dtype=t.float32, device=self.device) if want_salience else None
@@ -298,8 +316,7 @@ class Engine(KernelTestMixin):
     def fcpe_decode(self, salience, threshold: float = 0.006, decoder: str = "local_argmax", interp_uv: bool = False,
                     pad_to=None):
         """rvcx_fcpe_decode: the cents decoder (+ post_process) alone on salience [F][out_dims] -> f0 fp64."""
-        if self.fcpe_cfg is None:
-            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        self._need_fcpe()
         t = self.torch
         p = self._dev(salience, t.float32).reshape(-1, self.fcpe_cfg["out_dims"]).contiguous()
         F = int(p.shape[0])
@@ -360,15 +377,10 @@ class Engine(KernelTestMixin):
         batched pass over all rows (each row's frames are `hubert`'s on that row alone, up to summation order).
         ld_rows: frames between two rows' blocks in the output buffer (default: the longest row's frame count)."""
         t = self.torch
-        rows = [self._dev(a, t.float32).reshape(-1) for a in audios]
-        B = len(rows)
-        if B < 1:
+        a, ns = self._pad_rows(audios, t.float32)
+        if a is None:
             return []
-        ns = [int(r.numel()) for r in rows]
-        lda = max(ns)
-        a = t.zeros((B, lda), dtype=t.float32, device=self.device)
-        for b, r in enumerate(rows):
-            a[b, : ns[b]] = r
+        B, lda = a.shape
         D = 256 if version == "v1" else 768
         cap = max(1, hubert_frames(lda)) if ld_rows is None else int(ld_rows)
         out = t.empty((B, cap, D), dtype=t.float32, device=self.device)
@@ -396,15 +408,10 @@ class Engine(KernelTestMixin):
         the list of saliences [F_b, 360]), from one ragged pass over all rows (rvcx_rmvpe_batch_v: each row is `rmvpe`'s
         on that row alone, up to summation order)."""
         t = self.torch
-        rows = [self._dev(a, t.float32).reshape(-1) for a in audios]
-        B = len(rows)
-        if B < 1:
+        a, ns = self._pad_rows(audios, t.float32)
+        if a is None:
             return ([], []) if want_hidden else []
-        ns = [int(r.numel()) for r in rows]
-        lda = max(ns)
-        a = t.zeros((B, lda), dtype=t.float32, device=self.device)
-        for b, r in enumerate(rows):
-            a[b, : ns[b]] = r
+        B, lda = a.shape
         F = 1 + lda // 160
         f0 = t.empty((B, F), dtype=t.float64, device=self.device)
         hid = t.empty((B, F, 360), dtype=t.float32, device=self.device) if want_hidden else None
@@ -437,51 +444,40 @@ class Engine(KernelTestMixin):
                                           pitchf.data_ptr(), fs.data_ptr(), self.stream()), "f0_post")
         return coarse, pitchf, fs
 
-    def synth_infer(self, phone, lengths, pitch, pitchf, sid, eps_z=None, eps_src=None, seed: int = 0,
-                    want_latents: bool = False):
+    def _synth_args(self, phone, lengths, pitch, pitchf, sid, eps_z, eps_src):
+        """What the two Synthesizer.infer entries share: B, T, the pointers (None: null) of the device arguments before
+        the noise (phone, lengths, pitch, pitchf, sid) and of the noise (eps_z, eps_src), the tensors themselves (to be
+        kept alive over the call), out [B, T upp] and a maker of [B, T, I] outputs."""
         t = self.torch
         ph = self._dev(phone, t.float32)
         B, T = int(ph.shape[0]), int(ph.shape[1])
-        ln = self._dev(lengths, t.int32).reshape(B)
-        pc = None if pitch is None else self._dev(pitch, t.int32).reshape(B, T)
-        pf = None if pitchf is None else self._dev(pitchf, t.float32).reshape(B, T)
-        sd = self._dev(sid, t.int32).reshape(B)
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        args = (ph, self._dev(lengths, t.int32).reshape(B), self._opt(pitch, t.int32, B, T),
+                self._opt(pitchf, t.float32, B, T), self._dev(sid, t.int32).reshape(B))
+        noise = (self._opt(eps_z, t.float32), self._opt(eps_src, t.float32))
         out = t.empty((B, T * self.upp), dtype=t.float32, device=self.device)
         I = self.synth_cfg.inter_channels
-        zp = t.empty((B, T, I), dtype=t.float32, device=self.device) if want_latents else None
-        z = t.empty((B, T, I), dtype=t.float32, device=self.device) if want_latents else None
-        self._check(self.lib.rvcx_synth_infer(self.ctx, B, T, ph.data_ptr(), ln.data_ptr(), _ptr(pc),
-                                              _ptr(pf), sd.data_ptr(), _ptr(ez), _ptr(es),
-                                              ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(), _ptr(zp),
+        return (B, T, [_ptr(x) for x in args], [_ptr(x) for x in noise], args + noise, out,
+                lambda: t.empty((B, T, I), dtype=t.float32, device=self.device))
+
+    def synth_infer(self, phone, lengths, pitch, pitchf, sid, eps_z=None, eps_src=None, seed: int = 0,
+                    want_latents: bool = False):
+        B, T, args, noise, _keep, out, latent = self._synth_args(phone, lengths, pitch, pitchf, sid, eps_z, eps_src)
+        zp, z = (latent(), latent()) if want_latents else (None, None)
+        self._check(self.lib.rvcx_synth_infer(self.ctx, B, T, *args, *noise, self._seed(seed), out.data_ptr(), _ptr(zp),
                                               _ptr(z), self.stream()), "synth_infer")
         return (out, zp, z) if want_latents else out
 
     def synth_infer_ex(self, phone, lengths, pitch, pitchf, sid, rate=None, eps_z=None, eps_src=None, seed: int = 0):
         """Synthesizer.infer with rate and the full return value (rvcx_synth_infer_ex): -> (out [B][T' upp],
         z_p [B][T'][I], z [B][T'][I], m_p [B][T][I], logs_p [B][T][I]) with T' = T - int(T (1 - rate))."""
-        t = self.torch
-        ph = self._dev(phone, t.float32)
-        B, T = int(ph.shape[0]), int(ph.shape[1])
-        ln = self._dev(lengths, t.int32).reshape(B)
-        pc = None if pitch is None else self._dev(pitch, t.int32).reshape(B, T)
-        pf = None if pitchf is None else self._dev(pitchf, t.float32).reshape(B, T)
-        sd = self._dev(sid, t.int32).reshape(B)
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        B, T, args, noise, _keep, out, latent = self._synth_args(phone, lengths, pitch, pitchf, sid, eps_z, eps_src)
+        zp, z, mp, lp = latent(), latent(), latent(), latent()
         I = self.synth_cfg.inter_channels
-        out = t.empty((B, T * self.upp), dtype=t.float32, device=self.device)
-        zp = t.empty((B, T, I), dtype=t.float32, device=self.device)
-        z = t.empty((B, T, I), dtype=t.float32, device=self.device)
-        mp = t.empty((B, T, I), dtype=t.float32, device=self.device)
-        lp = t.empty((B, T, I), dtype=t.float32, device=self.device)
         tn = ctypes.c_int(0)
-        self._check(self.lib.rvcx_synth_infer_ex(self.ctx, B, T, ph.data_ptr(), ln.data_ptr(), _ptr(pc), _ptr(pf),
-                                                 sd.data_ptr(), -1.0 if rate is None else float(rate), _ptr(ez),
-                                                 _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(),
-                                                 zp.data_ptr(), z.data_ptr(), mp.data_ptr(), lp.data_ptr(),
-                                                 ctypes.byref(tn), self.stream()), "synth_infer_ex")
+        self._check(self.lib.rvcx_synth_infer_ex(self.ctx, B, T, *args, -1.0 if rate is None else float(rate), *noise,
+                                                 self._seed(seed), out.data_ptr(), zp.data_ptr(), z.data_ptr(),
+                                                 mp.data_ptr(), lp.data_ptr(), ctypes.byref(tn), self.stream()),
+                    "synth_infer_ex")
         Tn = int(tn.value)
         return (out.reshape(-1)[: B * Tn * self.upp].reshape(B, Tn * self.upp), zp.reshape(-1)[: B * Tn * I].reshape(B, Tn, I),
                 z.reshape(-1)[: B * Tn * I].reshape(B, Tn, I), mp, lp)
@@ -490,12 +486,12 @@ class Engine(KernelTestMixin):
         t = self.torch
         zz = self._dev(z, t.float32)
         B, I, T = zz.shape
-        f = None if f0 is None else self._dev(f0, t.float32).reshape(B, T)
+        f = self._opt(f0, t.float32, B, T)
         sd = self._dev(sid, t.int32).reshape(B)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        es = self._opt(eps_src, t.float32)
         out = t.empty((B, T * self.upp), dtype=t.float32, device=self.device)
         self._check(self.lib.rvcx_dec_only(self.ctx, B, T, zz.data_ptr(), _ptr(f), sd.data_ptr(), _ptr(es),
-                                           ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(),
+                                           self._seed(seed), out.data_ptr(),
                                            self.stream()), "dec_only")
         return out
 
@@ -505,16 +501,16 @@ class Engine(KernelTestMixin):
         t = self.torch
         a = self._dev(audio_pad, t.float32).reshape(-1)
         n = a.numel()
-        pc = None if pitch is None else self._dev(pitch, t.int32).reshape(-1)
-        pf = None if pitchf is None else self._dev(pitchf, t.float32).reshape(-1)
+        pc = self._opt(pitch, t.int32, -1)
+        pf = self._opt(pitchf, t.float32, -1)
         cap = (n // 160) * self.upp
         out = t.empty((cap,), dtype=t.float32, device=self.device)
         no = ctypes.c_int64(0)
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        ez = self._opt(eps_z, t.float32)
+        es = self._opt(eps_src, t.float32)
         self._check(self.lib.rvcx_voice_conversion(self.ctx, a.data_ptr(), n, _ptr(pc), _ptr(pf), int(sid),
                                                    float(protect), float(index_rate), _ptr(ez), _ptr(es),
-                                                   ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(), cap,
+                                                   self._seed(seed), out.data_ptr(), cap,
                                                    ctypes.byref(no), self.stream()), "voice_conversion")
         return out[: no.value]
 
@@ -618,11 +614,11 @@ class Engine(KernelTestMixin):
             out = t.empty((cap,), dtype=t.float32, device=self.device)
         f0 = t.empty((1 + m // 160,), dtype=t.float64, device=self.device) if want_f0 else None
         no = ctypes.c_int64(0)
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        ez = self._opt(eps_z, t.float32)
+        es = self._opt(eps_src, t.float32)
         self._check(self.lib.rvcx_pipeline(self.ctx, a.data_ptr(), n, int(sid), float(semitones), float(protect),
                                            int(t_pad), int(t_pad_tgt), _ptr(ez), _ptr(es),
-                                           ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(), out.numel(),
+                                           self._seed(seed), out.data_ptr(), out.numel(),
                                            ctypes.byref(no), _ptr(f0), self.stream()), "pipeline")
         res = out[: no.value]
         return (res, f0) if want_f0 else res
@@ -688,10 +684,10 @@ class Engine(KernelTestMixin):
             out = t.empty((cap,), dtype=t.float32, device=self.device)
         f0 = t.empty((1 + m // 160,), dtype=t.float64, device=self.device) if want_f0 else None
         no = ctypes.c_int64(0)
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        ez = self._opt(eps_z, t.float32)
+        es = self._opt(eps_src, t.float32)
         self._check(self.lib.rvcx_pipeline_ex(self.ctx, a.data_ptr(), n, ctypes.byref(opts), _ptr(ez), _ptr(es),
-                                              ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(), out.numel(),
+                                              self._seed(seed), out.data_ptr(), out.numel(),
                                               ctypes.byref(no), _ptr(f0), self.stream()), "pipeline_ex")
         res = out[: no.value]
         return (res, f0) if want_f0 else res
@@ -708,13 +704,13 @@ class Engine(KernelTestMixin):
         out = out.reshape(-1)[: B * ldo].reshape(B, ldo)
         sid = np.broadcast_to(np.asarray(sids, dtype=np.int32), (B,))
         sarr = (ctypes.c_int32 * B)(*[int(v) for v in sid])
-        ez = None if eps_z is None else self._dev(eps_z, t.float32)
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        ez = self._opt(eps_z, t.float32)
+        es = self._opt(eps_src, t.float32)
         F = 1 + m // 160
         f0 = t.empty((B, F), dtype=t.float64, device=self.device) if want_f0 else None
         hid = t.empty((B, F, 360), dtype=t.float32, device=self.device) if want_hidden else None
         head = (self.ctx, a.data_ptr())
-        mid = (lda, B, ctypes.byref(opts), sarr, _ptr(ez), _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+        mid = (lda, B, ctypes.byref(opts), sarr, _ptr(ez), _ptr(es), self._seed(seed),
                out.data_ptr(), ldo)
         if isinstance(ns, int):
             no = ctypes.c_int64(0)
@@ -750,15 +746,10 @@ class Engine(KernelTestMixin):
         Pipeline.pipeline of utterance b); with want_f0 also the list of the rows' adjusted f0 (fp64 [F_b]).
         eps_z [B, inter, T_max] / eps_src [B, T_max * upp] with T_max = max pipeline_frames(n_b): row b consumes
         eps_z[b, :, :T_b] and eps_src[b, :T_b * upp]."""
-        t = self.torch
-        rows = [self._dev(a, t.float64).reshape(-1) for a in audios]
-        B = len(rows)
-        if B < 1:
+        a, ns = self._pad_rows(audios, self.torch.float64)
+        if a is None:
             return ([], []) if want_f0 else []
-        ns = [int(r.numel()) for r in rows]
-        a = t.zeros((B, max(ns)), dtype=t.float64, device=self.device)
-        for b, r in enumerate(rows):
-            a[b, : ns[b]] = r
+        B = len(ns)
         out, no, f0, _ = self._pipeline_rows(a, ns, opts, sids, eps_z, eps_src, seed, None, want_f0, False)
         ys = [out[b, : no[b]] for b in range(B)]
         if not want_f0:

@@ -46,8 +46,7 @@ class KernelTestMixin:
     # ------------------------------------------------------------------ FCPE's parts
     def fcpe_mel(self, audio):
         """The FCPE network's input alone (rvcx_fcpe_mel, include/rvcx_test.h): audio [N] -> log-mel [F, num_mels]."""
-        if self.fcpe_cfg is None:
-            raise _lib.RvcxError(-5, "fcpe weights not loaded (Engine.load_fcpe)")
+        self._need_fcpe()
         t = self.torch
         a = self._dev(audio, t.float32).reshape(-1)
         F = self._fcpe_frames(a.numel())
@@ -176,10 +175,10 @@ class KernelTestMixin:
         t = self.torch
         f = self._dev(f0, t.float32)
         B, T = f.shape
-        es = None if eps_src is None else self._dev(eps_src, t.float32)
+        es = self._opt(eps_src, t.float32)
         out = t.empty((B, T * self.upp), dtype=t.float32, device=self.device)
         self._check(self.lib.rvcx_dec_source(self.ctx, B, T, f.data_ptr(), _ptr(es),
-                                             ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), out.data_ptr(), self.stream()),
+                                             self._seed(seed), out.data_ptr(), self.stream()),
                     "dec_source")
         return out
 
@@ -227,7 +226,7 @@ class KernelTestMixin:
                 (eps is None or (eps.is_contiguous() and tuple(eps.shape) == (B, C, T)))):
             raise ValueError("rg_adain: x, y [B][T][C], w [C], eps [B][C][T], contiguous")
         self._check(self.lib.rvcx_rg_adain(self.ctx, x.data_ptr(), B, T, C, w.data_ptr(), _ptr(eps),
-                                           ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(slope), y.data_ptr(),
+                                           self._seed(seed), float(slope), y.data_ptr(),
                                            int(mode), float(div), self.stream()), "rg_adain")
         return y
 
@@ -430,9 +429,9 @@ class KernelTestMixin:
         q = self._dev(qkv, torch.float32)
         B, T, H3 = (int(v) for v in q.shape)
         dk = H3 // 3 // n_heads
-        rk = None if rel_k is None else self._dev(rel_k, torch.float32)
-        rv = None if rel_v is None else self._dev(rel_v, torch.float32)
-        mk = None if mask is None else self._dev(mask, torch.float32)
+        rk = self._opt(rel_k, torch.float32)
+        rv = self._opt(rel_v, torch.float32)
+        mk = self._opt(mask, torch.float32)
         y = torch.empty((B, T, H3 // 3), dtype=torch.float32, device=self.device)
         self._check(self.lib.rvcx_flash_attention(self.ctx, _ptr(q), B, T, int(n_heads), dk, float(qscale), _ptr(rk),
                                                   _ptr(rv), int(window), _ptr(mk), _ptr(y), self.stream()),

@@ -201,10 +201,10 @@ class StreamGroup:
         arr, act = hop_arguments(self.n_streams, opts, active)
         self._apply_clean(opts, act)
         x = eng._dev(audio_in, t.float32).reshape(self.n_streams, self.block_frame)
-        ez = None if eps_z is None else eng._dev(eps_z, t.float32)
-        es = None if eps_src is None else eng._dev(eps_src, t.float32)
+        ez = eng._opt(eps_z, t.float32)
+        es = eng._opt(eps_src, t.float32)
         eng._check(eng.lib.rvcx_rt_process_v(eng.ctx, self.handle, x.data_ptr(), self.sids, arr, act, _ptr(ez),
-                                             _ptr(es), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+                                             _ptr(es), eng._seed(seed),
                                              self.out.data_ptr(), self.vol.data_ptr(), self.offs.data_ptr(),
                                              eng.stream()), "rt_process")
         return self.out, self.vol

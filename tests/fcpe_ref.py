@@ -154,3 +154,21 @@ def post_process(f0, hop: int, sr: int, pad_to=None) -> np.ndarray:
     if val.shape[0] == 1:
         return np.ones(n) * val[0]
     return np.interp(np.arange(n) * hop / sr, hop / sr * nz.numpy(), val, left=val[0], right=val[-1])
+
+
+# the Performer attention of the kernel-level GPU tests: FCPE's 8 heads of 64 channels, 266 random features
+ATTN_H, ATTN_D, ATTN_M = 8, 64, 266
+
+
+def attention_operands(T, pscale, seed):
+    """q, k, v [H][T][64] with element magnitudes spread over two decades (0.03 .. 3 times a unit normal) and a
+    gaussian-orthogonal P [266][64] with rows of chi(64) norm. pscale multiplies P's rows; q and k are divided by
+    it as well, because dash = c x . P_j would otherwise grow 30-fold and exp overflow fp32 (the tests assert the
+    largest exponent): dash keeps its scale, diag = |x|^2 / 2 shrinks 900-fold, and the row norms of P grow."""
+    H, D, M = ATTN_H, ATTN_D, ATTN_M
+    rng = np.random.Generator(np.random.PCG64(seed))
+    q, k, v = (rng.standard_normal((H, T, D)) * 0.3 * 10.0 ** rng.uniform(-1.0, 1.0, (H, T, D)) for _ in range(3))
+    blocks = [np.linalg.qr(rng.standard_normal((D, D)))[0].T for _ in range(5)]
+    P = np.concatenate(blocks)[:M] * np.linalg.norm(rng.standard_normal((M, D)), axis=1)[:, None] * pscale
+    f = np.float32
+    return (q / pscale).astype(f), (k / pscale).astype(f), v.astype(f), P.astype(f)

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 K = 8
 ULP32 = 2.0 ** -23  # one fp32 ulp of the largest element, relative to it
@@ -184,3 +185,32 @@ def dec_fn(w, z, f0, sid, eps_src, cfg=None):
         return o.reshape(o.shape[0], -1)
 
     return fn
+
+
+class PatchedF:
+    """torch.nn.functional with some functions replaced, to stand in for an oracle module's `F`."""
+
+    def __init__(self, **over):
+        self._over = over
+
+    def __getattr__(self, k):
+        return self._over[k] if k in self._over else getattr(F, k)
+
+
+def ratios(fn, anc, absolute=False):
+    """The fp32 oracle's distance to float64 per output, in units of max(gap, floor): what check() compares to K."""
+    got = _as_dict(fn(torch.float32))
+    out = {}
+    for k, (ref, gap) in anc.items():
+        floor = ULP32 * (1.0 if absolute else float(np.abs(ref).max()))
+        out[k] = float(np.abs(got[k] - ref).max()) / max(gap, floor)
+    return out
+
+
+def anchored(name, dev, stored, ref64, gap, old_bar, absolute=False):
+    """The stored reference output within 2 gap of float64, then the device within (K + 1) gap of the stored output;
+    the measured error is printed beside the fixed bar it also passed."""
+    stored = np.asarray(stored).reshape(ref64.shape)
+    check(f"{name} fixture vs fp64", stored, ref64, gap, 2, absolute)
+    err = check(f"{name} device vs fixture", np.asarray(dev).reshape(ref64.shape), stored, gap, K + 1, absolute)
+    print(f"{name}: measured {err:.3e}, fixed bar {old_bar:g}")

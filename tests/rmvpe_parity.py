@@ -101,6 +101,18 @@ def check_rmvpe(dev_f0, dev_hidden, ref, ref_f0, thred=THRED, max_err=None):
             "first_flip": int(fl[0]) if len(fl) else None}
 
 
+def check_salience(name, f0, hid, ref, gap):
+    """The salience within K gap (absolute) of float64 (parity_anchor.check), and the decode decisions float64 implies:
+    argmax and voicing on every frame whose margins exceed the error, f0 within the cents that error allows
+    (check_rmvpe)."""
+    import parity_anchor as pa
+    from oracle import rmvpe as orm
+
+    pa.check(name, hid, ref, gap, pa.K, absolute=True)
+    r = check_rmvpe(f0, hid, margins(ref), orm.decode(ref, 0.03), max_err=pa.K * max(gap, pa.ULP32))
+    print(f"{name}: window err {r['err']:.3e}, {r['n_near']} near-tied frames, flips {list(r['flips'])}")
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))

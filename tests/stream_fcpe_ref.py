@@ -3,6 +3,7 @@ get_f0 takes the raw local_argmax track from the FCPE restatement (tests/fcpe_re
 pipeline.py:148-155, where FCPE.get_f0 returns the network's track as it is (F = n // 160 + 1 frames, zeros where
 unvoiced, no interpolation). A second yardstick for the device's "fcpe" streams beside the reference run of
 tests/golden/make_golden_stream_fcpe.py: it shares no code with that script's torchfcpe adapter."""
+import numpy as np
 import torch
 
 import fcpe_ref as fr
@@ -29,3 +30,25 @@ class FcpeOracleVoiceChanger(OracleVoiceChanger):
         circular_write(f0_coarse, pitch)
         circular_write(f0, pitchf)
         return pitch.unsqueeze(0), pitchf.unsqueeze(0)
+
+
+def stream_inputs(g):
+    from rvcx import synthetic
+
+    S, H, blk = int(g["n_streams"]), int(g["hops"]), int(g["block"])
+    x = np.stack([synthetic.speech_like(blk * H, seed=int(g["input_seed0"]) + s, sr=48000).astype(np.float32)
+                  for s in range(S)])
+    hops = [int(h) for h in g["silent_hops"]]
+    x[int(g["silent_stream"]), hops[0] * blk:(hops[-1] + 1) * blk] = 0.0
+    return x
+
+
+def hop_noise(rngs, I, T, upp):
+    """The fixture's recorded noise for one hop: per stream PCG64 draws, eps_z then eps_src (make_golden.NoiseStream)."""
+    S = len(rngs)
+    ez = np.empty((S, I, T), np.float32)
+    es = np.empty((S, T * upp), np.float32)
+    for s in range(S):
+        ez[s] = rngs[s].standard_normal((1, I, T)).astype(np.float32)[0]
+        es[s] = rngs[s].standard_normal((1, T * upp, 1)).astype(np.float32).reshape(-1)
+    return ez, es

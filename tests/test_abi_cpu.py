@@ -8,27 +8,13 @@ import subprocess
 
 import pytest
 
+from abi_headers import header_prototypes
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the kernel-level entries that used to sit in rvcx.h: test-only, so declared in rvcx_test.h alone
 MOVED_TO_TEST_HEADER = ["rvcx_set_conv_math", "rvcx_conv1d", "rvcx_conv1d_gen", "rvcx_conv1d_ex", "rvcx_conv2d3x3",
                         "rvcx_convtranspose2d_s2", "rvcx_flash_attention", "rvcx_resblock_pair"]
-
-
-def header_prototypes(name):
-    """{entry point: number of parameters} of include/<name>: comments stripped, then every `int` / `const char*`
-    function named rvcx_*, its parameters counted by the top-level commas of the parameter list."""
-    src = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", name)).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*(?:int|const char\*)\s+(rvcx_[a-z0-9_]+)\s*\(([^;{}]*)\)\s*;", src, re.M):
-        params, depth, commas = m.group(2).strip(), 0, 0
-        for ch in params:
-            depth += ch in "(["
-            depth -= ch in ")]"
-            commas += ch == "," and depth == 0
-        assert m.group(1) not in protos, f"{m.group(1)} declared twice in {name}"
-        protos[m.group(1)] = 0 if params in ("", "void") else commas + 1
-    return protos
 
 
 def header_symbols():

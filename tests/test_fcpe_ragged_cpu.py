@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import fcpe_ref as fr
-from test_abi_cpu import header_prototypes
+from abi_headers import header_prototypes
 
 Z = dict(win_size=1024, hop_size=160)  # the front end of every FCPE checkpoint rvc/ ships
 

@@ -13,11 +13,11 @@ import torch
 import fcpe_ref as fr
 import parity_anchor as pa
 from conftest import golden
+from fcpe_ref import attention_operands as _attention_operands
 
 pytestmark = pytest.mark.gpu
 
 LENGTHS = (15000, 1000, 400)
-H, D, M = 8, 64, 266
 
 
 @pytest.fixture(scope="module")
@@ -43,19 +43,6 @@ def fcpe(engine):
 
 
 # ---------------------------------------------------------------- Performer attention, kernel level
-def _attention_operands(T, pscale, seed):
-    """q, k, v [H][T][64] with element magnitudes spread over two decades (0.03 .. 3 times a unit normal) and a
-    gaussian-orthogonal P [266][64] with rows of chi(64) norm. pscale multiplies P's rows; q and k are divided by
-    it as well, because dash = c x . P_j would otherwise grow 30-fold and exp overflow fp32 (the assertion on the
-    largest exponent below): dash keeps its scale, diag = |x|^2 / 2 shrinks 900-fold, and the row norms of P grow."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    q, k, v = (rng.standard_normal((H, T, D)) * 0.3 * 10.0 ** rng.uniform(-1.0, 1.0, (H, T, D)) for _ in range(3))
-    blocks = [np.linalg.qr(rng.standard_normal((D, D)))[0].T for _ in range(5)]
-    P = np.concatenate(blocks)[:M] * np.linalg.norm(rng.standard_normal((M, D)), axis=1)[:, None] * pscale
-    f = np.float32
-    return (q / pscale).astype(f), (k / pscale).astype(f), v.astype(f), P.astype(f)
-
-
 @pytest.mark.parametrize("pscale", [1.0, 30.0])
 @pytest.mark.parametrize("T", [7, 94, 301])
 def test_performer_attention_is_fp32_accurate(engine, T, pscale):

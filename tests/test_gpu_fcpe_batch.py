@@ -14,7 +14,7 @@ import torch
 import fcpe_ref as fr
 import parity_anchor as pa
 from conftest import golden
-from test_gpu_fcpe import D, H, M, _attention_operands
+from fcpe_ref import ATTN_D as D, ATTN_H as H, ATTN_M as M, attention_operands as _attention_operands
 
 pytestmark = pytest.mark.gpu
 

@@ -28,21 +28,16 @@ import torch
 
 import fcpe_ref as fr
 import parity_anchor as pa
+import ragged_rows
 from conftest import golden
-from test_gpu_fcpe import D, H, M, _attention_operands
-from test_gpu_rmvpe_ragged import PIPE_NS, PIPE_SIDS, SHORT_PAD, cents_apart, compare_row, noise_for
+from fcpe_ref import ATTN_D as D, ATTN_H as H, ATTN_M as M, attention_operands as _attention_operands
+from ragged_rows import PIPE_NS, PIPE_SIDS, SHORT_PAD, cents_apart, clip, compare_row, speech
 
 pytestmark = pytest.mark.gpu
 
 NS = (1000, 2400, 13920, 20480, 48000)
 FS = (7, 16, 88, 129, 301)
 THR = 0.5
-
-
-def speech(n, seed, scale=1.0):
-    from rvcx import synthetic
-
-    return (synthetic.speech_like(n, seed=seed) * scale).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -289,39 +284,21 @@ PIPE_SEEDS_FCPE = (100, 200, 300, 501)
 EQUAL_N, EQUAL_SEEDS = 9600, (200, 201, 202)
 
 
-def clip(n, seed):
-    from rvcx import synthetic
-
-    return synthetic.speech_like(n, seed=seed)
-
-
 def pipe_clips():
     return [clip(n, s) for n, s in zip(PIPE_NS, PIPE_SEEDS_FCPE)]
 
 
 def check_rows_vs_single(engine, audios, sids, seed, **kw):
-    """test_gpu_rmvpe_ragged.check_rows_vs_single with FCPE: pipeline_batch_v under f0_method 5 against pipeline_ex
-    under f0_method 3 on each utterance alone with its slice of the injected noise, at compare_row's bars (spectrogram
-    correlation > 0.999, max difference < 5e-3 of the peak, the adjusted f0 with the same voicing and within 0.1 cent
-    on EVERY frame)."""
-    engine.set_pipeline_highpass()
-    common = dict(pitch=2.0, protect=0.33, fcpe_threshold=THR, **kw)
-    opts = engine.pipeline_opts(f0_method=5, **common)
-    upp = engine.upp
-    Ts, ez, es = noise_for(engine, audios, opts, seed)
-    ys, f0s = engine.pipeline_batch_v(audios, opts, sids=sids, eps_z=ez, eps_src=es, want_f0=True)
-    ys, f0s = [engine.host(y) for y in ys], [engine.host(f) for f in f0s]
-    failed = []
-    for b, a in enumerate(audios):
-        o1 = engine.pipeline_opts(f0_method=3, sid=sids[b], **common)
-        y1, f1 = engine.pipeline_ex(a, o1, eps_z=np.ascontiguousarray(ez[b, :, :Ts[b]]).reshape(-1),
-                                    eps_src=es[b, :Ts[b] * upp], want_f0=True)
-        y1, f1 = engine.host(y1), engine.host(f1)
-        assert y1.shape == (Ts[b] * upp - 2 * int(opts.t_pad_tgt),)
+    """The ragged RMVPE test's procedure (ragged_rows.check_rows_vs_single) with FCPE: pipeline_batch_v under
+    f0_method 5 against pipeline_ex under f0_method 3 on each utterance alone with its slice of the injected noise, at
+    compare_row's bars (spectrogram correlation > 0.999, max difference < 5e-3 of the peak, the adjusted f0 with the
+    same voicing and within 0.1 cent on EVERY frame), the single run's track 20 .. 80 % voiced."""
+    def judge(b, name, y, y1, f0, f1):
         assert 0.2 < float((f1 > 0).mean()) < 0.8
-        failed += compare_row(f"row {b} n={len(a)} T={Ts[b]}", ys[b], y1, f0s[b], f1)
-    engine.check_device_status()
-    assert not failed, "; ".join(failed)
+        return compare_row(name, y, y1, f0, f1)
+
+    ragged_rows.check_rows_vs_single(engine, audios, sids, seed, dict(f0_method=5), dict(f0_method=3), judge, pitch=2.0,
+                                     protect=0.33, fcpe_threshold=THR, **kw)
 
 
 @pytest.mark.parametrize("envelope", [1.0, 0.5])

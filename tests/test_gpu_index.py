@@ -126,7 +126,7 @@ def test_pipeline_with_index_matches_oracle(engine, synth_w, hubert_w, rmvpe_w, 
     from rvcx.config import HUBERT_BASE
     from rvcx.infer import Config, HubertModel, PipelineMLX, RMVPE0Predictor, Synthesizer
 
-    from test_gpu_pipeline_api import NoiseRecorder, oracle_pipeline
+    from pipeline_ref import NoiseRecorder, oracle_pipeline
 
     # index over the oracle's HuBERT features of other speech (what extract_index.py builds from)
     train = synthetic.speech_like(16000 * 4, seed=31).astype(np.float32)

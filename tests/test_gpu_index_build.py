@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import golden
-from test_gpu_kmeans import _clustered, case1, check_assign, sqdist64
+from kmeans_ref import _clustered, case1, check_assign, sqdist64
 
 pytestmark = pytest.mark.gpu
 
@@ -177,7 +177,7 @@ def test_pipeline_uses_a_built_index(engine, synth_w, hubert_w, rmvpe_w, tmp_pat
     from rvcx.infer import Config, HubertModel, PipelineMLX, RMVPE0Predictor, Synthesizer
     from rvcx.infer.index import IndexIVFFlat
 
-    from test_gpu_pipeline_api import NoiseRecorder, oracle_pipeline
+    from pipeline_ref import NoiseRecorder, oracle_pipeline
 
     train = synthetic.speech_like(16000 * 4, seed=31).astype(np.float32)
     with torch.no_grad():

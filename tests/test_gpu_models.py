@@ -12,7 +12,7 @@ import torch
 
 import parity_anchor as pa
 from conftest import golden
-from parity_anchor import K, anchor, check
+from parity_anchor import anchor, anchored
 
 pytestmark = pytest.mark.gpu
 
@@ -20,15 +20,6 @@ pytestmark = pytest.mark.gpu
 def rel_err(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))
-
-
-def anchored(name, dev, stored, ref64, gap, old_bar, absolute=False):
-    """The stored reference output within 2 gap of float64, then the device within (K + 1) gap of the stored output;
-    the measured error is printed beside the fixed bar it also passed."""
-    stored = np.asarray(stored).reshape(ref64.shape)
-    check(f"{name} fixture vs fp64", stored, ref64, gap, 2, absolute)
-    err = check(f"{name} device vs fixture", np.asarray(dev).reshape(ref64.shape), stored, gap, K + 1, absolute)
-    print(f"{name}: measured {err:.3e}, fixed bar {old_bar:g}")
 
 
 def synth_anchor(w, g):

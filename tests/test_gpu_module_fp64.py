@@ -14,7 +14,7 @@ import torch
 
 import parity_anchor as pa
 from parity_anchor import K, anchor, check, check_each
-from rmvpe_parity import check_rmvpe, margins
+from rmvpe_parity import check_salience
 
 pytestmark = pytest.mark.gpu
 
@@ -47,16 +47,6 @@ def test_hubert_batch_vs_fp64(engine, hubert_w):
 
 
 # ----------------------------------------------------------------- RMVPE
-def check_salience(name, f0, hid, ref, gap):
-    """The salience within K gap (absolute) of float64, and the decode decisions float64 implies: argmax and voicing
-    on every frame whose margins exceed the error, f0 within the cents that error allows (rmvpe_parity.check_rmvpe)."""
-    from oracle import rmvpe as orm
-
-    check(name, hid, ref, gap, K, absolute=True)
-    r = check_rmvpe(f0, hid, margins(ref), orm.decode(ref, 0.03), max_err=K * max(gap, pa.ULP32))
-    print(f"{name}: window err {r['err']:.3e}, {r['n_near']} near-tied frames, flips {list(r['flips'])}")
-
-
 @pytest.mark.parametrize("n", [2720, 4960, 5280, 16000])
 def test_rmvpe_salience_vs_fp64(engine, rmvpe_w, n):
     """F = 18 (reflect pad 14), 32 (none), 34 (pad 30 of at most 33), 101 frames; the reference is float64 from the

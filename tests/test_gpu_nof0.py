@@ -11,8 +11,7 @@ import torch
 
 import parity_anchor as pa
 from conftest import golden
-from parity_anchor import K, anchor, check_each
-from test_gpu_models import anchored
+from parity_anchor import K, anchor, anchored, check_each
 
 pytestmark = pytest.mark.gpu
 

@@ -9,18 +9,14 @@ import numpy as np
 import pytest
 
 import parity_anchor as pa
+import ragged_rows
 from parity_anchor import K, anchor, check
+from ragged_rows import SHORT_PAD, clip, noise_for, speech
 
 pytestmark = pytest.mark.gpu
 
 NS = (40000, 400, 21000, 20700, 16000)
 LS = (124, 1, 65, 64, 49)
-
-
-def speech(n, seed):
-    from rvcx import synthetic
-
-    return synthetic.speech_like(n, seed=seed).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -102,21 +98,6 @@ def test_refusals(engine):
 
 
 # ----------------------------------------------------------------- the ragged pipeline (rvcx_pipeline_batch_v)
-def clip(n, seed):
-    from rvcx import synthetic
-
-    return synthetic.speech_like(n, seed=seed)
-
-
-def noise_for(engine, audios, opts, seed):
-    """Injected noise in the batch layouts, T = the longest row's frames; row b consumes ez[b, :, :T_b], es[b, :T_b upp]."""
-    Ts = [engine.pipeline_frames(len(a), opts) for a in audios]
-    rng = np.random.default_rng(seed)
-    ez = rng.standard_normal((len(audios), 192, max(Ts))).astype(np.float32)
-    es = rng.standard_normal((len(audios), max(Ts) * engine.upp)).astype(np.float32)
-    return Ts, ez, es
-
-
 def check_rows_vs_single(engine, audios, sids, seed, **kw):
     """Every row of the ragged pass against pipeline_ex on that utterance alone with its slice of the noise: equal
     shape and n_out, spectrogram correlation > 0.999, max difference < 5e-3 of the peak
@@ -131,41 +112,26 @@ def check_rows_vs_single(engine, audios, sids, seed, **kw):
     tests."""
     from oracle.metrics import spectrogram_correlation
 
-    engine.set_pipeline_highpass()
-    opts = engine.pipeline_opts(pitch=2.0, protect=0.33, **kw)
-    upp = engine.upp
-    Ts, ez, es = noise_for(engine, audios, opts, seed)
-    ys, f0s = engine.pipeline_batch_v(audios, opts, sids=sids, eps_z=ez, eps_src=es, want_f0=True)
-    ys = [engine.host(y) for y in ys]
-    f0s = [engine.host(f) for f in f0s]
-    failed = []
-    for b, a in enumerate(audios):
-        o1 = engine.pipeline_opts(pitch=2.0, protect=0.33, sid=sids[b], **kw)
-        y1, f1 = engine.pipeline_ex(a, o1, eps_z=np.ascontiguousarray(ez[b, :, :Ts[b]]).reshape(-1),
-                                    eps_src=es[b, :Ts[b] * upp], want_f0=True)
-        y1, f1 = engine.host(y1), engine.host(f1)
-        assert ys[b].shape == y1.shape == (Ts[b] * upp - 2 * int(opts.t_pad_tgt),), (b, ys[b].shape, y1.shape)
-        corr = spectrogram_correlation(ys[b], y1)
-        diff = float(np.abs(ys[b] - y1).max()) / max(float(np.abs(y1).max()), 1e-6)
-        df0 = float(np.abs(f0s[b] - f1).max()) if f0s[b].shape == f1.shape else float("inf")
-        print(f"\nrow {b} n={len(a)} T={Ts[b]}: corr {corr:.6f} max diff / peak {diff:.3e} max |f0 diff| {df0:.3e}")
+    def judge(b, name, y, y1, f0, f1):
+        failed = []
+        corr = spectrogram_correlation(y, y1)
+        diff = float(np.abs(y - y1).max()) / max(float(np.abs(y1).max()), 1e-6)
+        df0 = float(np.abs(f0 - f1).max()) if f0.shape == f1.shape else float("inf")
+        print(f"\n{name}: corr {corr:.6f} max diff / peak {diff:.3e} max |f0 diff| {df0:.3e}")
         if not (corr > 0.999 and diff < 5e-3):
-            failed.append(f"row {b}: corr {corr:.6f} diff {diff:.3e}")
-        if sum(len(x) == len(a) for x in audios) == 1:
-            if not np.array_equal(f0s[b], f1):
-                failed.append(f"row {b}: f0 differs from the single run's by up to {df0:.3e}")
+            failed.append(f"{name}: corr {corr:.6f} diff {diff:.3e}")
+        if sum(len(x) == len(audios[b]) for x in audios) == 1:
+            if not np.array_equal(f0, f1):
+                failed.append(f"{name}: f0 differs from the single run's by up to {df0:.3e}")
         else:
             voiced = f1 > 0
-            cents = float(np.abs(1200.0 * np.log2(f0s[b][voiced] / f1[voiced])).max()) if voiced.any() else 0.0
-            print(f"row {b} (batched RMVPE subgroup): max f0 difference {cents:.4f} cent")
-            if not (np.array_equal(f0s[b] > 0, voiced) and cents <= 0.1):
-                failed.append(f"row {b}: f0 differs from the single run's by {cents:.4f} cent or in voicing")
-    assert not failed, "; ".join(failed)
+            cents = float(np.abs(1200.0 * np.log2(f0[voiced] / f1[voiced])).max()) if voiced.any() else 0.0
+            print(f"{name} (batched RMVPE subgroup): max f0 difference {cents:.4f} cent")
+            if not (np.array_equal(f0 > 0, voiced) and cents <= 0.1):
+                failed.append(f"{name}: f0 differs from the single run's by {cents:.4f} cent or in voicing")
+        return failed
 
-
-# the 8000-sample row is shorter than the default t_pad (16000), which the reflect padding of either path refuses
-# (t_pad < n): these cases pad by 0.3 s, t_pad_tgt = 3 t_pad = 30 frames, three times the generator's receptive field
-SHORT_PAD = dict(t_pad=4800, t_pad_tgt=14400)
+    ragged_rows.check_rows_vs_single(engine, audios, sids, seed, {}, {}, judge, pitch=2.0, protect=0.33, **kw)
 
 
 def test_ragged_pipeline_matches_single(engine):

@@ -19,10 +19,9 @@ import torch
 
 import parity_anchor as pa
 import refinegan_ref as rr
-import test_gpu_synth_configs as sc
+import synth_configs as sc
 from conftest import golden, refinegan_noise
-from parity_anchor import K, anchor, check, check_each
-from test_gpu_models import anchored
+from parity_anchor import K, anchor, anchored, check, check_each
 
 pytestmark = pytest.mark.gpu
 
@@ -259,8 +258,8 @@ def test_ragged_batch_matches_single(engines):
     resamplers' taps, but on the oracle it is 1e-5 of the peak 10 frames before the end and 1e-6 at the 30 frames these
     options trim: far inside these bars."""
     from oracle.metrics import spectrogram_correlation
-    from test_gpu_ragged_batch import SHORT_PAD
-    from test_gpu_ragged_batch import clip as speech
+    from ragged_rows import SHORT_PAD
+    from ragged_rows import clip as speech
 
     _, cfg, _, eng = engines("rg_48k", front=True)
     ns, sids = [24000, 40000, 8000], [0, 3, 7]

@@ -14,7 +14,7 @@ tests/test_gpu_module_fp64.py anchors:
 Two pairs share a padded frame count but differ in reflect pad (14 / 0 and 30 / 0), one row sits at Fp_max, and the
 U-Net's deepest level has heights 1, 1, 2, 2, 4. The batch runs in the given order and reversed.
 
-Against float64 every row is held to test_gpu_module_fp64.check_salience: the salience within K = 8 gaps (absolute)
+Against float64 every row is held to rmvpe_parity.check_salience: the salience within K = 8 gaps (absolute)
 of anchor(parity_anchor.rmvpe_fn) on that row alone, the decode decisions through rmvpe_parity.check_rmvpe. That
 comparison exempts near-tied frames, so it says something only while few frames are near-tied: at most 10 % of any
 row's frames may be, at the worst admissible error K gap. On the CPU the oracle gives 1/18, 0/32, 0/34, 3/64 and 1/101
@@ -28,20 +28,15 @@ import numpy as np
 import pytest
 
 import parity_anchor as pa
+import ragged_rows
 from parity_anchor import K, anchor, check
-from rmvpe_parity import margins
-from test_gpu_module_fp64 import check_salience
+from ragged_rows import PIPE_NS, PIPE_SIDS, SHORT_PAD, cents_apart, clip, compare_row, speech
+from rmvpe_parity import check_salience, margins
 
 pytestmark = pytest.mark.gpu
 
 NS = (2720, 4960, 5280, 10080, 16000)
 FS = (18, 32, 34, 64, 101)
-
-
-def speech(n, seed):
-    from rvcx import synthetic
-
-    return synthetic.speech_like(n, seed=seed).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -66,11 +61,6 @@ def rows(rmvpe_w):
 def single(engine, rows):
     """engine.rmvpe on every row alone: (f0, salience)."""
     return [tuple(engine.host(x) for x in engine.rmvpe(a, 0.03, want_hidden=True)) for a, _, _, _ in rows]
-
-
-def cents_apart(f, g):
-    v = g > 0
-    return float(np.abs(1200.0 * np.log2(f[v] / g[v])).max()) if v.any() else 0.0
 
 
 @pytest.mark.parametrize("order", ["given", "reversed"])
@@ -215,49 +205,12 @@ def test_refusals(engine):
 
 
 # ----------------------------------------------------------------- the ragged pipeline with f0_method 4
-# t_pad 0.3 s as tests/test_gpu_ragged_batch.py's SHORT_PAD: t_pad_tgt = 30 frames, three times the generator's field
-SHORT_PAD = dict(t_pad=4800, t_pad_tgt=14400)
-PIPE_NS = (8000, 9600, 12000, 10400)
+# the rows and the 0.3 s pad of ragged_rows (PIPE_NS, SHORT_PAD: t_pad_tgt = 30 frames, three times the generator's field)
 PIPE_SEEDS = (112, 218, 334, 502)
-PIPE_SIDS = [0, 3, 7, 1]
-
-
-def clip(n, seed):
-    from rvcx import synthetic
-
-    return synthetic.speech_like(n, seed=seed)
 
 
 def pipe_clips():
     return [clip(n, s) for n, s in zip(PIPE_NS, PIPE_SEEDS)]
-
-
-def noise_for(engine, audios, opts, seed):
-    """Injected noise in the batch layouts, T = the longest row's frames; row b consumes ez[b, :, :T_b], es[b, :T_b upp]."""
-    Ts = [engine.pipeline_frames(len(a), opts) for a in audios]
-    rng = np.random.default_rng(seed)
-    ez = rng.standard_normal((len(audios), 192, max(Ts))).astype(np.float32)
-    es = rng.standard_normal((len(audios), max(Ts) * engine.upp)).astype(np.float32)
-    return Ts, ez, es
-
-
-def compare_row(name, y, y1, f0=None, f1=None):
-    """One row of a ragged-f0 pass against the single-utterance run: the bars of check_rows_vs_single (the f0 bars
-    where the caller has the rows' f0)."""
-    from oracle.metrics import spectrogram_correlation
-
-    assert y.shape == y1.shape, (name, y.shape, y1.shape)
-    corr = spectrogram_correlation(y, y1)
-    diff = float(np.abs(y - y1).max()) / max(float(np.abs(y1).max()), 1e-6)
-    same_voicing, cents = True, 0.0
-    if f0 is not None:
-        assert f0.shape == f1.shape, (name, f0.shape, f1.shape)
-        same_voicing = np.array_equal(f0 > 0, f1 > 0)
-        both = (f0 > 0) & (f1 > 0)
-        cents = cents_apart(f0[both], f1[both])
-    print(f"\n{name}: corr {corr:.6f} max diff / peak {diff:.3e} f0 {cents:.5f} cent same voicing {same_voicing}")
-    return [] if (corr > 0.999 and diff < 5e-3 and same_voicing and cents <= 0.1) else [
-        f"{name}: corr {corr:.6f} diff {diff:.3e} f0 {cents:.4f} cent, same voicing {same_voicing}"]
 
 
 def check_rows_vs_single(engine, audios, sids, seed, **kw):
@@ -273,22 +226,7 @@ def check_rows_vs_single(engine, audios, sids, seed, **kw):
     is 500 times tighter than the 50 cents of the oracle tests. No frame is exempt, so the clips are chosen (on the
     CPU, from the float64 oracle's salience of each row's high-passed, reflect-padded input) to have no frame whose
     argmax or voicing decision is near-tied at K gap: see PIPE_SEEDS."""
-    engine.set_pipeline_highpass()
-    opts = engine.pipeline_opts(pitch=2.0, protect=0.33, f0_method=4, **kw)
-    upp = engine.upp
-    Ts, ez, es = noise_for(engine, audios, opts, seed)
-    ys, f0s = engine.pipeline_batch_v(audios, opts, sids=sids, eps_z=ez, eps_src=es, want_f0=True)
-    ys, f0s = [engine.host(y) for y in ys], [engine.host(f) for f in f0s]
-    failed = []
-    for b, a in enumerate(audios):
-        o1 = engine.pipeline_opts(pitch=2.0, protect=0.33, sid=sids[b], **kw)
-        y1, f1 = engine.pipeline_ex(a, o1, eps_z=np.ascontiguousarray(ez[b, :, :Ts[b]]).reshape(-1),
-                                    eps_src=es[b, :Ts[b] * upp], want_f0=True)
-        y1, f1 = engine.host(y1), engine.host(f1)
-        assert y1.shape == (Ts[b] * upp - 2 * int(opts.t_pad_tgt),)
-        failed += compare_row(f"row {b} n={len(a)} T={Ts[b]}", ys[b], y1, f0s[b], f1)
-    engine.check_device_status()
-    assert not failed, "; ".join(failed)
+    ragged_rows.check_rows_vs_single(engine, audios, sids, seed, dict(f0_method=4), {}, pitch=2.0, protect=0.33, **kw)
 
 
 @pytest.mark.parametrize("envelope", [1.0, 0.5])

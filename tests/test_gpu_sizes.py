@@ -63,7 +63,7 @@ def test_c3_generator_b32_vs_reference(engine):
 def test_c4_batch8_30s_vs_reference_and_oracle(engine, synth_w, hubert_w, rmvpe_w):
     from oracle.metrics import spectrogram_correlation
     from rvcx import synthetic
-    from test_gpu_pipeline_api import NoiseRecorder, oracle_pipeline
+    from pipeline_ref import NoiseRecorder, oracle_pipeline
 
     g = golden("pipeline_c4_30s.npz")
     n, B = 480000, 8

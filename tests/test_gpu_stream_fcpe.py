@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from conftest import golden
-from test_stream_fcpe_cpu import hop_noise, stream_inputs
+from stream_fcpe_ref import hop_noise, stream_inputs
 
 pytestmark = pytest.mark.gpu
 

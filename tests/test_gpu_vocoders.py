@@ -18,7 +18,7 @@ import torch
 import parity_anchor as pa
 from conftest import golden
 from parity_anchor import K, anchor, check, check_each
-from test_gpu_models import anchored
+from parity_anchor import anchored
 
 pytestmark = pytest.mark.gpu
 

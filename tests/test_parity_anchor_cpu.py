@@ -24,27 +24,7 @@ import torch
 import torch.nn.functional as F
 
 import parity_anchor as pa
-from parity_anchor import K, anchor, check
-
-
-class PatchedF:
-    """torch.nn.functional with some functions replaced, to stand in for an oracle module's `F`."""
-
-    def __init__(self, **over):
-        self._over = over
-
-    def __getattr__(self, k):
-        return self._over[k] if k in self._over else getattr(F, k)
-
-
-def ratios(fn, anc, absolute=False):
-    """The fp32 oracle's distance to float64 per output, in units of max(gap, floor): what check() compares to K."""
-    got = pa._as_dict(fn(torch.float32))
-    out = {}
-    for k, (ref, gap) in anc.items():
-        floor = pa.ULP32 * (1.0 if absolute else float(np.abs(ref).max()))
-        out[k] = float(np.abs(got[k] - ref).max()) / max(gap, floor)
-    return out
+from parity_anchor import K, PatchedF, anchor, check, ratios
 
 
 # ----------------------------------------------------------------- anchor / check themselves

@@ -10,28 +10,7 @@ import torch
 
 import parity_anchor as pa
 from conftest import golden
-
-
-def stream_inputs(g):
-    from rvcx import synthetic
-
-    S, H, blk = int(g["n_streams"]), int(g["hops"]), int(g["block"])
-    x = np.stack([synthetic.speech_like(blk * H, seed=int(g["input_seed0"]) + s, sr=48000).astype(np.float32)
-                  for s in range(S)])
-    hops = [int(h) for h in g["silent_hops"]]
-    x[int(g["silent_stream"]), hops[0] * blk:(hops[-1] + 1) * blk] = 0.0
-    return x
-
-
-def hop_noise(rngs, I, T, upp):
-    """The fixture's recorded noise for one hop: per stream PCG64 draws, eps_z then eps_src (make_golden.NoiseStream)."""
-    S = len(rngs)
-    ez = np.empty((S, I, T), np.float32)
-    es = np.empty((S, T * upp), np.float32)
-    for s in range(S):
-        ez[s] = rngs[s].standard_normal((1, I, T)).astype(np.float32)[0]
-        es[s] = rngs[s].standard_normal((1, T * upp, 1)).astype(np.float32).reshape(-1)
-    return ez, es
+from stream_fcpe_ref import stream_inputs
 
 
 def test_fixture_conditions():

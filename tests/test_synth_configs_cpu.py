@@ -22,9 +22,8 @@ import torch
 import torch.nn.functional as F
 
 import parity_anchor as pa
-from parity_anchor import K, anchor
+from parity_anchor import K, PatchedF, anchor, ratios
 from synth_configs import CONFIGS, NAMES, margin_frames, weights_for
-from test_parity_anchor_cpu import PatchedF, ratios
 
 LENGTHS, SEED = (24, 17, 1), 7
 

@@ -9,10 +9,12 @@ pipeline's salience, and the ragged forms: HuBERT over rows of five lengths, the
 (plain and with a volume envelope) and over two equal rows, RMVPE over rows of five lengths in one ragged pass and the
 ragged pipeline with it (f0_method 4). Then, as plain integers, Engine.workspace_bytes of five calls: the arena query
 runs the pipelines in their sizing form. Last, FCPE over rows of five lengths in one ragged pass, the ragged pipeline
-with it (f0_method 5) and its arena query.
+with it (f0_method 5) and its arena query, and the strided copy-out of equal rows: HuBERT, RMVPE and FCPE over equal
+rows whose output rows the caller spaces wider than the pass writes them.
 
     python tools/output_digests.py > digests.txt
 """
+import ctypes
 import dataclasses
 import hashlib
 import os
@@ -39,6 +41,21 @@ def synth_inputs(cfg, B, T, seed):
     phone = rng.standard_normal((B, T, cfg.text_enc_hidden_dim)).astype(np.float32)
     pitch = rng.integers(1, 256, size=(B, T)).astype(np.int64)
     return phone, [T] * B, pitch, synthetic.f0_walk(B, T, seed=seed + 1), list(range(B))
+
+
+def strided_v(eng, entry, audios, F, nb, *mode):
+    """rvcx_rmvpe_batch_v / rvcx_fcpe_batch_v itself on equal rows, the f0 rows F + 5 and the salience rows F + 3 frames
+    apart (as run_rows_c of the ragged tests calls them): the rows' own frames of both outputs."""
+    t = eng.torch
+    a = eng._dev(np.stack(audios), t.float32)
+    B, n = a.shape
+    f0 = t.zeros((B, F + 5), dtype=t.float64, device=eng.device)
+    sal = t.zeros((B, F + 3, nb), dtype=t.float32, device=eng.device)
+    F_arr = (ctypes.c_int64 * B)()
+    eng._check(getattr(eng.lib, entry)(eng.ctx, a.data_ptr(), (ctypes.c_int64 * B)(*[n] * B), n, B, 0.03, *mode,
+                                       f0.data_ptr(), F + 5, F_arr, sal.data_ptr(), F + 3, eng.stream()), entry)
+    assert [int(v) for v in F_arr] == [F] * B
+    return f0[:, :F], sal[:, :F]
 
 
 def main():
@@ -137,6 +154,10 @@ def main():
         show("pipeline_batch_v ragged f0_method=5", *ys, *f0s)
         need = eng.workspace_bytes(40000, B=4, opts=eng.pipeline_opts(**kw))
         print(f"workspace_bytes B=4 n=40000{''.join(f' {k}={v}' for k, v in kw.items())}: {need}", flush=True)
+        eq = [synthetic.speech_like(5280, seed=80 + b).astype(f32) for b in range(3)]
+        show("hubert_batch_v equal rows strided", *eng.hubert_batch_v(eq[:2], ld_rows=16 + 3))
+        show("rmvpe_batch_v equal rows strided", *strided_v(eng, "rvcx_rmvpe_batch_v", eq, 34, 360))
+        show("fcpe_batch_v equal rows strided", *strided_v(eng, "rvcx_fcpe_batch_v", eq, 34, 360, 0))
     eng.close()
 
 
