@@ -403,6 +403,25 @@ int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n
                           const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
                           double* d_f0, int64_t ldf, void* stream);
 
+/* rvcx_pipeline_batch_v with a voice per row (the voice bank below): voices host [B], NULL = every row on the current
+ * voice, which is rvcx_pipeline_batch_v itself, bit for bit (rvcx_pipeline_batch_v and rvcx_pipeline_batch are this
+ * call with voices = NULL). The rows of one voice must be contiguous (RVCX_E_INVALID; the host sorts), every voice must
+ * exist (RVCX_E_INVALID) and be finalized (RVCX_E_STATE), and the voices must agree on sr, the product of the upsample
+ * rates, text_enc_hidden_dim, inter_channels, no_f0 and vocoder (RVCX_E_SHAPE). sids[b] is checked against row b's
+ * voice; index_rate > 0 needs an index on every voice in the batch (RVCX_E_STATE). The high-pass, the ragged HuBERT, the
+ * pitch network (any f0_method) and the f0 adjustments run once over all rows -- they do not depend on the voice, so
+ * under f0_method 0 a row's f0 is still the single run's bit for bit; retrieval (against each voice's own index) and
+ * Synthesizer.infer with per-row lengths and the common output window run once per voice on its row range at the
+ * batch's strides; the trim, the volume envelope and the peak normalisation once. Rows of different lengths need
+ * t_pad_tgt to cover the widest receptive field among the voices' generators. With several voices, injected source
+ * noise needs the HiFi-GAN-NSF layout (one row per batch row), and drawn noise (no d_eps_*) is keyed by the row within
+ * its voice's range under a seed derived from `seed` and the range's first row. The context's current voice is the
+ * same after the call as before, on an error too. */
+int rvcx_pipeline_batch_voices(rvcx_ctx* ctx, const double* d_audio, const int64_t* n, int64_t lda, int B,
+                               const rvcx_pipeline_opts* opts, const int32_t* sids, const int32_t* voices,
+                               const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo,
+                               int64_t* n_out, double* d_f0, int64_t ldf, void* stream);
+
 /* Single-chunk shorthand of rvcx_pipeline_ex (t_max = 0, defaults otherwise). */
 int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, double semitones, float protect,
                   int64_t t_pad, int64_t t_pad_tgt, const float* d_eps_z, const float* d_eps_src, uint64_t seed,
@@ -422,6 +441,10 @@ int rvcx_pipeline(rvcx_ctx* ctx, const double* d_audio, int64_t n, int sid, doub
  *   in place of RMVPE's; the call is then sized under f0_method 0 as well and the larger size is reported.
  *   With f0_method 4 and B > 1 the ragged RMVPE pass is sized on B rows of n samples; with f0_method 5 the ragged
  *   FCPE pass, and as under f0_method 3 the size also covers the same call under f0_method 0.
+ *   The query is made for the current voice. A call with a voice per row (rvcx_pipeline_batch_voices) is held by an
+ *   arena of the maximum of rvcx_workspace_bytes(B, n_max, opts) over the voices in use (select each, ask, take the
+ *   largest): the per-voice stages run on row ranges of at most B rows, the largest range first, in the buffers the
+ *   whole batch would take.
  * rvcx_set_workspace: hand the context a caller-owned device arena (e.g. a torch uint8 tensor's data_ptr(), 256-B
  *   aligned), valid until replaced or the context is destroyed: the pool is then carved from it and never allocated,
  *   and a call that would need more fails with RVCX_E_OOM. NULL, 0 returns to internal allocation. The current pool
@@ -640,6 +663,57 @@ int rvcx_config_info(const rvcx_ctx* ctx, char* buf, int64_t cap, int64_t* len);
 
 /* Upsampling factor of the loaded synthesizer (prod(upsample_rates); net_g.dec.upp). */
 int rvcx_synth_upp(const rvcx_ctx* ctx);
+
+/* Voice bank: several voice models resident in one context.
+ * A voice is everything that differs between two RVC checkpoints: the synthesizer configuration, the uploaded and
+ * packed RVCX_MODEL_SYNTH tensors with the pre-split weight images derived from them, and the feature index with its
+ * nprobe. HuBERT, RMVPE, CREPE, FCPE, the high-pass, the workspace and the profile belong to the context and are shared.
+ * The context has a CURRENT voice. Voice 0 exists from rvcx_create and is current; every entry point that reads or
+ * writes "the" synthesizer or "the" index (rvcx_set_synth_config, rvcx_upload / rvcx_finalize of RVCX_MODEL_SYNTH,
+ * rvcx_synth_*, rvcx_dec_only, rvcx_voice_conversion, rvcx_pipeline*, rvcx_index_*, rvcx_workspace_bytes,
+ * rvcx_rt_create) acts on the current voice.
+ * rvcx_voice_new: adds an empty voice and returns its id; the current voice stays. Ids are never reused within a
+ *   context, so a stale id is detected.
+ * rvcx_voice_select: host only -- no device call, no synchronisation, no copy of weight data. RVCX_E_INVALID for an
+ *   unknown or freed id. Like every other call on a context it must not run concurrently with another call on it.
+ * rvcx_voice_info: any live voice, current or not.
+ * rvcx_voice_free: synchronises the device, then releases the voice's tensors, the split images built from them and its
+ *   index. RVCX_E_STATE for voice 0 and for the current voice, RVCX_E_INVALID for an unknown or freed id. */
+typedef struct {
+  rvcx_synth_desc synth; /* as set; zeros before rvcx_set_synth_config */
+  int config_set;        /* rvcx_set_synth_config was called for this voice */
+  int ready;             /* RVCX_MODEL_SYNTH finalized */
+  int64_t index_d, index_ntotal, index_nlist, index_nprobe; /* zeros without an index */
+  int64_t weight_bytes;  /* the packed tensors in HBM */
+  int64_t split_bytes;   /* the pre-split weight images built from them so far (they are built on first use) */
+} rvcx_voice_desc;
+int rvcx_voice_new(rvcx_ctx* ctx, int* voice);
+int rvcx_voice_select(rvcx_ctx* ctx, int voice);
+int rvcx_voice_current(const rvcx_ctx* ctx, int* voice);
+int rvcx_voice_info(rvcx_ctx* ctx, int voice, rvcx_voice_desc* desc);
+int rvcx_voice_free(rvcx_ctx* ctx, int voice);
+
+/* A voice per stream slot. rvcx_rt_create takes its geometry from the current voice and starts every slot on it; a
+ * slot's voice then stays with the slot whatever rvcx_voice_select does later, and a hop leaves the context's current
+ * voice as it found it, on an error too.
+ * rvcx_rt_set_voice (stream_index -1 = every slot): the voice must agree with the group's geometry voice on sr, the
+ *   product of the upsample rates, text_enc_hidden_dim, inter_channels, no_f0 and vocoder (what fixes the buffer
+ *   geometry, the HuBERT version and the layout of injected noise), else RVCX_E_SHAPE; RVCX_E_INVALID for an unknown or
+ *   freed id or a stream_index outside [-1, n_streams), RVCX_E_STATE for a voice that is not finalized. A refused call
+ *   changes no slot. The slot's state is not cleared: a newcomer calls rvcx_rt_reset_stream, a user who switches voice
+ *   keeps the SOLA crossfade.
+ * rvcx_rt_get_voices: out [n_streams].
+ * The hop (rvcx_rt_process*) runs its front end (ingest, the pitch network, the f0 adjustments, HuBERT) once over all
+ * active rows. The compact rows are ordered by voice: groups by their lowest active slot, rows within a group by slot
+ * (one voice in use: slot order, as before). Retrieval (against that voice's index), upsample + protect and one
+ * Synthesizer.infer then run per voice on its contiguous row range, and the hop's tail (volume envelope, gate,
+ * resample, SOLA) once. sids[b] is checked against the slot's voice; index_rate > 0 on a slot whose voice has no index
+ * and a freed voice in an active slot give RVCX_E_STATE (the group is usable again after rvcx_rt_set_voice). Drawn
+ * noise is keyed by the row within its voice's range, under a seed derived from `seed` and the range's first row (one
+ * voice in use: by compact row under `seed`, as before). With more than one voice in a hop, injected source noise
+ * needs the HiFi-GAN-NSF layout (as with idle slots). */
+int rvcx_rt_set_voice(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, int voice);
+int rvcx_rt_get_voices(const rvcx_rt* rt, int32_t* out);
 
 #ifdef __cplusplus
 }

@@ -86,7 +86,12 @@ int rvcx_upload(rvcx_ctx* ctx, int model, const char* name, const float* host, c
 int rvcx_finalize(rvcx_ctx* ctx, int model) {
   return guard(ctx, [&] {
     set_device(ctx);
-    if (model == RVCX_MODEL_SYNTH) {
+    if (model == RVCX_MODEL_SYNTH) {  // packed into the current voice's own tensor map
+      struct Packing {
+        bool& f;
+        explicit Packing(bool& b) : f(b) { f = true; }
+        ~Packing() { f = false; }
+      } packing(ctx->packing_synth);
       finalize_synth(*ctx);
     } else if (model == RVCX_MODEL_HUBERT) {
       finalize_hubert(*ctx);
@@ -105,6 +110,78 @@ int rvcx_finalize(rvcx_ctx* ctx, int model) {
 }
 
 int rvcx_synth_upp(const rvcx_ctx* ctx) { return ctx ? ctx->scfg.upp() : 0; }
+
+// ------------------------------------------------------------------ voice bank
+int rvcx_voice_new(rvcx_ctx* ctx, int* voice) {
+  return guard(ctx, [&] {
+    if (!voice) throw Error(RVCX_E_INVALID, "rvcx_voice_new: null output");
+    *voice = ctx->new_voice();
+  });
+}
+
+int rvcx_voice_select(rvcx_ctx* ctx, int voice) {
+  return guard(ctx, [&] { ctx->select_voice(voice); });
+}
+
+int rvcx_voice_current(const rvcx_ctx* ctx, int* voice) {
+  if (!ctx || !voice) return RVCX_E_INVALID;
+  *voice = ctx->cur_voice;
+  return RVCX_OK;
+}
+
+int rvcx_voice_info(rvcx_ctx* ctx, int voice, rvcx_voice_desc* desc) {
+  return guard(ctx, [&] {
+    if (!desc) throw Error(RVCX_E_INVALID, "rvcx_voice_info: null desc");
+    if (!ctx->has_voice(voice)) throw Error(RVCX_E_INVALID, "rvcx_voice_info: the voice does not exist (or was freed)");
+    std::memset(desc, 0, sizeof(*desc));
+    const bool cur = voice == ctx->cur_voice;
+    const Voice* v = cur ? nullptr : &ctx->voices.at(voice);
+    const SynthCfg& g = cur ? ctx->scfg : v->scfg;
+    desc->config_set = (cur ? ctx->synth_cfg_set : v->synth_cfg_set) ? 1 : 0;
+    desc->ready = (cur ? ctx->ready[RVCX_MODEL_SYNTH] : v->ready) ? 1 : 0;
+    if (desc->config_set) {
+      rvcx_synth_desc& d = desc->synth;
+      d.inter_channels = g.I, d.hidden_channels = g.H, d.filter_channels = g.F;
+      d.n_heads = g.n_heads, d.n_layers = g.n_layers, d.kernel_size = g.ksize;
+      d.n_resblocks = (int)g.rb_k.size();
+      d.n_dilations = g.rb_d.empty() ? 0 : (int)g.rb_d[0].size();
+      for (size_t j = 0; j < g.rb_k.size(); ++j) {
+        d.resblock_kernel_sizes[j] = g.rb_k[j];
+        for (size_t m = 0; m < g.rb_d[j].size(); ++m) d.resblock_dilation_sizes[j][m] = g.rb_d[j][m];
+      }
+      d.n_upsample = (int)g.ups.size();
+      for (size_t i = 0; i < g.ups.size(); ++i) d.upsample_rates[i] = g.ups[i], d.upsample_kernel_sizes[i] = g.up_k[i];
+      d.upsample_initial_channel = g.C0;
+      d.spk_embed_dim = g.n_spk, d.gin_channels = g.gin, d.sr = g.sr, d.text_enc_hidden_dim = g.emb_dim;
+      d.no_f0 = g.f0 ? 0 : 1, d.vocoder = g.vocoder;
+    }
+    if (const IvfIndex* ix = cur ? ctx->ivf.get() : v->ivf.get()) {
+      desc->index_d = ix->view.d, desc->index_ntotal = ix->view.ntotal;
+      desc->index_nlist = ix->view.nlist, desc->index_nprobe = ix->view.nprobe;
+    }
+    ctx->voice_bytes(voice, &desc->weight_bytes, &desc->split_bytes);
+  });
+}
+
+int rvcx_voice_free(rvcx_ctx* ctx, int voice) {
+  return guard(ctx, [&] {
+    RVCX_HIP(hipSetDevice(ctx->device));
+    ctx->free_voice(voice);
+  });
+}
+
+int rvcx_rt_set_voice(rvcx_ctx* ctx, rvcx_rt* rt, int stream_index, int voice) {
+  return guard(ctx, [&] {
+    if (!rt || !rt->s) throw Error(RVCX_E_INVALID, "rt_set_voice: null stream group");
+    rt_set_voice(*ctx, *rt->s, stream_index, voice);
+  });
+}
+
+int rvcx_rt_get_voices(const rvcx_rt* rt, int32_t* out) {
+  if (!rt || !rt->s || !out) return RVCX_E_INVALID;
+  rt_get_voices(*rt->s, out);
+  return RVCX_OK;
+}
 
 int rvcx_hubert(rvcx_ctx* ctx, const float* d_audio, int64_t n, int version, float* d_feats, int64_t cap_rows,
                 int64_t* rows_out, void* stream) {
@@ -942,13 +1019,23 @@ int rvcx_pipeline_batch_v(rvcx_ctx* ctx, const double* d_audio, const int64_t* n
                           const rvcx_pipeline_opts* opts, const int32_t* sids, const float* d_eps_z,
                           const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo, int64_t* n_out,
                           double* d_f0, int64_t ldf, void* stream) {
+  return rvcx_pipeline_batch_voices(ctx, d_audio, n, lda, B, opts, sids, nullptr, d_eps_z, d_eps_src, seed, d_out, ldo,
+                                    n_out, d_f0, ldf, stream);
+}
+
+int rvcx_pipeline_batch_voices(rvcx_ctx* ctx, const double* d_audio, const int64_t* n, int64_t lda, int B,
+                               const rvcx_pipeline_opts* opts, const int32_t* sids, const int32_t* voices,
+                               const float* d_eps_z, const float* d_eps_src, uint64_t seed, float* d_out, int64_t ldo,
+                               int64_t* n_out, double* d_f0, int64_t ldf, void* stream) {
   return guard(ctx, [&] {
-    if (!pipeline_ready(ctx)) throw Error(RVCX_E_STATE, "models not finalized");
+    // the current voice's synthesizer when no voices are given; each row's voice is checked by the rows themselves
+    if (!(voices ? ctx->ready[RVCX_MODEL_HUBERT] && ctx->ready[RVCX_MODEL_RMVPE] : pipeline_ready(ctx)))
+      throw Error(RVCX_E_STATE, "models not finalized");
     if (!d_audio || !n || !opts || !sids || !d_out || !n_out || B < 1)
       throw Error(RVCX_E_INVALID, "rvcx_pipeline_batch_v: bad arguments");
     set_device(ctx);
     pipeline_forward_rows(*ctx, d_audio, n, lda, B, *opts, sids, d_eps_z, d_eps_src, seed, d_out, ldo, n_out, d_f0, ldf,
-                          nullptr, static_cast<hipStream_t>(stream), false);
+                          nullptr, static_cast<hipStream_t>(stream), false, voices);
   });
 }
 

@@ -108,6 +108,29 @@ struct IvfIndex {
   int size_enc = -1;
 };
 
+// A voice: everything that differs between two RVC checkpoints. The context's members of the same names hold the
+// current voice; the other voices of the bank are parked in Ctx::voices and change places with them on select_voice
+// (map and vector swaps on the host: no device call, no copy of weight data).
+struct Voice {
+  SynthCfg scfg;
+  bool synth_cfg_set = false;
+  std::map<std::string, HostTensor> host;                // the uploaded synthesizer tensors (Ctx::host[0])
+  std::map<std::string, std::unique_ptr<DevBuf>> sdev;  // their packed images
+  std::vector<UpsLayer> ups;
+  std::unique_ptr<IvfIndex> ivf;
+  bool ready = false;
+};
+
+// what two voices must share to be served by one stream group or one batch: the quantities that fix the buffer
+// geometry, the HuBERT version and the layouts of injected noise
+struct VoiceGeom {
+  int sr = 0, upp = 0, emb_dim = 0, I = 0, f0 = 0, vocoder = 0;
+  bool operator==(const VoiceGeom& o) const {
+    return sr == o.sr && upp == o.upp && emb_dim == o.emb_dim && I == o.I && f0 == o.f0 && vocoder == o.vocoder;
+  }
+};
+inline VoiceGeom voice_geom(const SynthCfg& g) { return {g.sr, g.upp(), g.emb_dim, g.I, g.f0 ? 1 : 0, g.vocoder}; }
+
 struct Ctx {
   int device = 0;
   std::string err;
@@ -115,9 +138,23 @@ struct Ctx {
   bool synth_cfg_set = false;
   FcpeCfg fcfg;
   std::map<std::string, HostTensor> host[5];  // synth, hubert, rmvpe, crepe, fcpe
-  std::map<std::string, std::unique_ptr<DevBuf>> dev;  // packed weights
+  std::map<std::string, std::unique_ptr<DevBuf>> dev;  // packed weights of the shared models
+  // packed weights of the current voice's synthesizer (finalize_synth packs into it: packing_synth); W looks here first
+  std::map<std::string, std::unique_ptr<DevBuf>> sdev;
+  bool packing_synth = false;
   bool ready[5] = {false, false, false, false, false};
   std::vector<UpsLayer> ups;
+  // the voice bank: voice 0 exists from the start and is current. voices holds every live id; the current voice's entry
+  // is hollow (its state is in the members above). Ids are never reused.
+  std::map<int, Voice> voices;
+  int cur_voice = 0, next_voice = 1;
+  Ctx() { voices[0]; }
+  bool has_voice(int id) const { return voices.count(id) != 0; }
+  int new_voice();
+  void select_voice(int id);  // host only; throws RVCX_E_INVALID for an unknown or freed id
+  void free_voice(int id);    // synchronises the device; RVCX_E_STATE for voice 0 and the current voice
+  // bytes of a voice's packed tensors, and of the pre-split images built from them so far
+  void voice_bytes(int id, int64_t* weight_bytes, int64_t* split_bytes);
   // pipeline high-pass (rvc/infer/pipeline.py:22-27), normalised so a[0] = 1
   int hp_order = 0;
   std::vector<double> hp_b, hp_a, hp_zi;
@@ -254,6 +291,17 @@ struct Ctx {
     for (const auto& kv : ws) t += kv.second ? kv.second->bytes : 0;
     return t;
   }
+};
+
+// A call that serves several voices selects each in turn (host only) and leaves the context's current voice as it
+// found it, on an exception too. A voice freed meanwhile cannot be the one to return to: the current voice is never freed.
+struct VoiceScope {
+  Ctx& c;
+  int saved;
+  explicit VoiceScope(Ctx& ctx) : c(ctx), saved(ctx.cur_voice) {}
+  ~VoiceScope() { c.select_voice(saved); }
+  VoiceScope(const VoiceScope&) = delete;
+  VoiceScope& operator=(const VoiceScope&) = delete;
 };
 
 template <class T>
@@ -453,6 +501,9 @@ void rt_geometry(const RtState& s, int64_t* g);
 void rt_reset(Ctx& c, RtState& s, hipStream_t st);
 void rt_reset_stream(Ctx& c, RtState& s, int stream_index, hipStream_t st);
 int rt_streams(const RtState& s);
+// the voice of slot b (-1: every slot); refusals as rvcx_rt_set_voice documents them, no slot changed then
+void rt_set_voice(Ctx& c, RtState& s, int b, int voice);
+void rt_get_voices(const RtState& s, int32_t* out);
 // opts [B], one per slot; active [B] (0 = the slot sits this hop out) or null = every slot active
 void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts* opts,
                 const uint8_t* active, const float* eps_z, const float* eps_src, uint64_t seed, float* out48,
@@ -510,11 +561,12 @@ int64_t pipeline_forward_batch(Ctx& c, const double* audio, int64_t n, int64_t l
                                float* out, int64_t ldo, double* f0_out, float* hidden_out, hipStream_t s);
 // The batched pipeline. B utterances of nv[b] samples (host array), rows of stride lda: out row b n_out[b] samples,
 // f0_out row b at stride ldf; hidden_out (RMVPE's salience) only for rows of one length. pipeline_forward_batch above
-// is this with every nv[b] = n.
+// is this with every nv[b] = n. voices (host [B], optional): the voice of each row, rows of one voice contiguous
+// (rvcx_pipeline_batch_voices); null = every row on the current voice.
 void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
                            const rvcx_pipeline_opts& o, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
-                           float* hidden_out, hipStream_t s, bool sizing);
+                           float* hidden_out, hipStream_t s, bool sizing, const int32_t* voices = nullptr);
 // rvcx_workspace_bytes: the pool a pipeline call of B utterances of n samples under o takes, measured by running it on
 // zero audio from an empty pool (B = 1 pipeline_forward_ex, B > 1 pipeline_forward_rows in its sizing form); a caller
 // arena is detached meanwhile and the pool is released again before it returns

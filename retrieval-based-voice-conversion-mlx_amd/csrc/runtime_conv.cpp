@@ -76,9 +76,72 @@ void join_aux(Ctx& c, hipStream_t s, hipStream_t ax) {
 }
 
 float* Ctx::W(const std::string& name) const {
-  auto it = dev.find(name);
-  if (it == dev.end()) throw Error(RVCX_E_STATE, "packed weight not found: " + name);
+  auto it = sdev.find(name);
+  if (it == sdev.end()) {
+    it = dev.find(name);
+    if (it == dev.end()) throw Error(RVCX_E_STATE, "packed weight not found: " + name);
+  }
   return static_cast<float*>(it->second->p);
+}
+
+int Ctx::new_voice() {
+  const int id = next_voice++;
+  voices.emplace(id, Voice());
+  return id;
+}
+
+// The members that make up the current voice change places with a parked entry. Twice per select: the current state
+// into its own (hollow) entry, then the chosen entry's state into the members.
+static void swap_voice(Ctx& c, Voice& v) {
+  std::swap(c.scfg, v.scfg);
+  std::swap(c.synth_cfg_set, v.synth_cfg_set);
+  c.host[RVCX_MODEL_SYNTH].swap(v.host);
+  c.sdev.swap(v.sdev);
+  c.ups.swap(v.ups);
+  c.ivf.swap(v.ivf);
+  std::swap(c.ready[RVCX_MODEL_SYNTH], v.ready);
+}
+
+void Ctx::select_voice(int id) {
+  if (id == cur_voice) return;
+  auto it = voices.find(id);
+  if (it == voices.end()) throw Error(RVCX_E_INVALID, "voice " + std::to_string(id) + " does not exist (or was freed)");
+  swap_voice(*this, voices.at(cur_voice));
+  swap_voice(*this, it->second);
+  cur_voice = id;
+}
+
+void Ctx::voice_bytes(int id, int64_t* weight_bytes, int64_t* split_bytes) {
+  if (!has_voice(id)) throw Error(RVCX_E_INVALID, "voice " + std::to_string(id) + " does not exist (or was freed)");
+  const auto& m = id == cur_voice ? sdev : voices.at(id).sdev;
+  int64_t wb = 0, sb = 0;
+  for (const auto& kv : m) {
+    wb += (int64_t)kv.second->bytes;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(kv.second->p), hi = lo + kv.second->bytes;
+    for (const auto& e : wsplit_cache) {
+      const uintptr_t u = reinterpret_cast<uintptr_t>(std::get<0>(e.first));
+      if (u >= lo && u < hi && e.second) sb += (int64_t)e.second->bytes;
+    }
+    for (const auto& e : rb_wsplit_cache) {
+      const uintptr_t u = reinterpret_cast<uintptr_t>(e.first.first);
+      if (u >= lo && u < hi && e.second) sb += (int64_t)e.second->bytes;
+    }
+  }
+  if (weight_bytes) *weight_bytes = wb;
+  if (split_bytes) *split_bytes = sb;
+}
+
+void Ctx::free_voice(int id) {
+  if (!has_voice(id)) throw Error(RVCX_E_INVALID, "voice " + std::to_string(id) + " does not exist (or was freed)");
+  if (id == 0 || id == cur_voice) throw Error(RVCX_E_STATE, "voice 0 and the current voice cannot be freed");
+  RVCX_HIP(hipDeviceSynchronize());
+  Voice& v = voices.at(id);
+  for (const auto& kv : v.sdev) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(kv.second->p);
+    wranges.erase(lo);
+    drop_splits(lo, lo + kv.second->bytes);
+  }
+  voices.erase(id);  // the tensors and the index go with the entry
 }
 
 float* Ctx::alloc_weight(const std::string& name, const std::vector<float>& data) {
@@ -92,6 +155,7 @@ float* Ctx::alloc_weight(const std::string& name, const std::vector<float>& data
   b->bytes = bytes;
   RVCX_HIP(hipMemcpy(b->p, data.data(), data.size() * sizeof(float), hipMemcpyHostToDevice));
   float* p = static_cast<float*>(b->p);
+  auto& dev = packing_synth ? sdev : this->dev;  // the current voice's tensors, or the shared models'
   auto old = dev.find(name);
   if (old != dev.end()) {
     const uintptr_t o = reinterpret_cast<uintptr_t>(old->second->p);

@@ -521,16 +521,53 @@ int64_t pipeline_forward_ex(Ctx& c, const double* audio, int64_t n, const rvcx_p
 void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64_t lda, int B,
                            const rvcx_pipeline_opts& opts, const int32_t* sids, const float* eps_z, const float* eps_src,
                            uint64_t seed, float* out, int64_t ldo, int64_t* n_out, double* f0_out, int64_t ldf,
-                           float* hidden_out, hipStream_t s, bool sizing) {
+                           float* hidden_out, hipStream_t s, bool sizing, const int32_t* voices) {
   const Rows rows("pipeline_batch", nv, B, lda, 1);
   const int64_t n_max = rows.n_max;
   const bool equal = rows.equal;
+  // The rows of one voice are a contiguous range. Steps 1-2 (high-pass, HuBERT, the pitch network) do not depend on
+  // the voice and run once; retrieval, upsample + protect and Synthesizer.infer (steps 3-4) run per voice on its range
+  // at the batch's strides; step 5 once. The voices are selected in turn (host only) and the current one comes back.
+  struct Group {
+    int voice, r0, n;
+  };
+  std::vector<Group> groups;
   for (int b = 0; b < B; ++b) {
-    check_pipeline_opts(c, opts, nv[b]);
-    if (opts.t_max > 0 && nv[b] + 160 > opts.t_max)
-      throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
-    if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
+    const int v = voices ? voices[b] : c.cur_voice;
+    if (!groups.empty() && groups.back().voice == v) {
+      ++groups.back().n;
+      continue;
+    }
+    for (const Group& g : groups)
+      if (g.voice == v) throw Error(RVCX_E_INVALID, "pipeline_batch: the rows of one voice must be contiguous");
+    if (!c.has_voice(v))
+      throw Error(RVCX_E_INVALID, "pipeline_batch: voice " + std::to_string(v) + " does not exist (or was freed)");
+    groups.push_back({v, b, 1});
   }
+  VoiceScope restore(c);
+  int margin = 0;  // the widest receptive field among the voices' generators
+  for (auto g = groups.rbegin(); g != groups.rend(); ++g) {  // last to first: the first group's voice stays selected
+    c.select_voice(g->voice);
+    if (!c.ready[RVCX_MODEL_SYNTH])
+      throw Error(RVCX_E_STATE, "pipeline_batch: voice " + std::to_string(g->voice) + " is not finalized");
+    for (int b = g->r0; b < g->r0 + g->n; ++b) {
+      check_pipeline_opts(c, opts, nv[b]);
+      if (opts.t_max > 0 && nv[b] + 160 > opts.t_max)
+        throw Error(RVCX_E_INVALID, "pipeline_batch: utterances longer than t_max take the single-utterance path");
+      if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "pipeline_batch: sid out of range");
+    }
+    if (opts.index_rate > 0 && c.ivf->view.d != c.scfg.emb_dim)
+      throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension mismatch");
+    margin = std::max(margin, dec_margin_frames(c.scfg));
+  }
+  const VoiceGeom geom = voice_geom(c.scfg);
+  for (const Group& g : groups)
+    if (g.voice != c.cur_voice && !(voice_geom(c.voices.at(g.voice).scfg) == geom))
+      throw Error(RVCX_E_SHAPE, "pipeline_batch: the voices of one batch must agree on sr, upsample product, "
+                                "text_enc_hidden_dim, inter_channels, no_f0 and vocoder");
+  if (groups.size() > 1 && eps_src && geom.vocoder != 0)
+    throw Error(RVCX_E_INVALID, "pipeline_batch: injected source noise with several voices needs the HiFi-GAN-NSF "
+                                "noise layout");
   // f0_method 4: all rows in one ragged RMVPE pass; equal lengths (outside the arena query, which sizes the ragged
   // pass) and one row are method 0
   rvcx_pipeline_opts o = opts;
@@ -540,15 +577,14 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   const bool batch_fcpe = o.f0_method == 5 && B > 1;
   if (o.f0_method == 5) o.f0_method = 3;
   const int E = c.scfg.emb_dim, upp = c.scfg.upp();
-  if (!equal && o.t_pad_tgt < (int64_t)dec_margin_frames(c.scfg) * upp)
+  if (!equal && o.t_pad_tgt < (int64_t)margin * upp)
     throw Error(RVCX_E_INVALID, "pipeline_batch: rows of different lengths need t_pad_tgt >= " +
-                                    std::to_string((int64_t)dec_margin_frames(c.scfg) * upp) +
+                                    std::to_string((int64_t)margin * upp) +
                                     " samples (the generator's receptive field): a shorter row's last frames differ from "
                                     "a run of that row alone, and only the trim removes them");
   const bool guided = c.scfg.f0;  // no f0, pitch or protect without pitch guidance (pipeline.py:324-365)
   if (hidden_out && !(equal && guided && o.f0_method == 0))
     throw Error(RVCX_E_INVALID, "pipeline_batch: the salience needs equal lengths, RMVPE and a pitch-guided model");
-  if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "pipeline: feature index dimension mismatch");
   // rvcx_workspace_bytes sizes the ragged form: masks, the gathered RMVPE group and one single-row RMVPE forward
   const bool plain = equal && !sizing;
   const int64_t W = 160;
@@ -651,7 +687,11 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   const float* fx = feats;
   if (o.index_rate > 0) {
     float* fr = c.buf<float>("pb.feats_idx", (size_t)B * L_max * E, s);
-    index_retrieve(c, feats, B * L_max, E, o.index_rate, fr, s);
+    for (const Group& g : groups) {  // each voice's rows against its own index
+      c.select_voice(g.voice);
+      const size_t at = (size_t)g.r0 * L_max * E;
+      index_retrieve(c, feats + at, (int64_t)g.n * L_max, E, o.index_rate, fr + at, s);
+    }
     fx = fr;
   }
   float* phone = c.buf<float>("pb.phone", (size_t)B * Tv_max * E, s);
@@ -665,18 +705,32 @@ void pipeline_forward_rows(Ctx& c, const double* audio, const int64_t* nv, int64
   check(upsample2_protect(fx, feats, dL, (int)L_max, E, phone, dTv, (int)Tv_max,
                           (guided && o.protect < 0.5f) ? pitchf : nullptr, F_max, o.protect, s, B),
         "upsample");
-  // 4. one Synthesizer.infer with per-row lengths (pipeline.py:365-372), the generator over the common window: the
-  //    samples the trim below keeps
+  // 4. one Synthesizer.infer per voice with per-row lengths (pipeline.py:365-372), on its rows at the batch's strides;
+  //    the generator over the common window: the samples the trim below keeps. Injected noise is one row per batch row
+  //    (the NSF layout, checked above for several voices); drawn noise is keyed by the row within the call, so the
+  //    voices after the first draw under seeds of their own.
   const int64_t nvc = Tv_max * upp;
   float* vc = c.buf<float>("pb.vc", (size_t)B * nvc, s);
-  SynthCall syn;
-  syn.B = B, syn.T = (int)Tv_max;
-  syn.phone = phone, syn.lengths = dTv, syn.pitch = pc, syn.pitchf = pf, syn.sid = dsid;
-  syn.eps_z = eps_z, syn.eps_src = eps_src, syn.seed = seed;
-  syn.out = vc;
-  syn.full_lengths = plain;
-  if (o.t_pad_tgt > 0 && c.dec_window && !sizing) syn.win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
-  synth_forward(c, syn, s);
+  // the largest group first: the work buffers the groups share are then never regrown (an arena holds them once)
+  std::vector<const Group*> by_size;
+  for (const Group& g : groups) by_size.push_back(&g);
+  std::stable_sort(by_size.begin(), by_size.end(), [](const Group* x, const Group* y) { return x->n > y->n; });
+  for (const Group* gp : by_size) {
+    const Group& g = *gp;
+    c.select_voice(g.voice);
+    const size_t r0 = (size_t)g.r0;
+    SynthCall syn;
+    syn.B = g.n, syn.T = (int)Tv_max;
+    syn.phone = phone + r0 * Tv_max * E, syn.lengths = dTv + r0, syn.sid = dsid + r0;
+    if (pc) syn.pitch = pc + r0 * Tv_max, syn.pitchf = pf + r0 * Tv_max;
+    syn.eps_z = eps_z ? eps_z + r0 * geom.I * Tv_max : nullptr;
+    syn.eps_src = eps_src ? eps_src + r0 * nvc : nullptr;
+    syn.seed = seed + 0x9E3779B97F4A7C15ull * (uint64_t)g.r0;
+    syn.out = vc + r0 * nvc;
+    syn.full_lengths = plain;
+    if (o.t_pad_tgt > 0 && c.dec_window && !sizing) syn.win = {o.t_pad_tgt, nvc - o.t_pad_tgt};
+    synth_forward(c, syn, s);
+  }
   // 5. trim, volume envelope, peak normalisation of every row in one launch set each (pipeline.py:545-552)
   float* mx = c.buf<float>("pb.max", peak_normalize_ws_floats(B), s);
   if (o.volume_envelope == 1.0) {  // trim + normalise in one pass over all rows

@@ -98,6 +98,10 @@ struct RtState {
   // per slot: the noise gate's strength (rt_set_clean), negative = the slot does not clean. A setting of the slot like
   // its sid, not hop state: rt_reset / rt_reset_stream leave it.
   std::vector<float> clean;
+  // per slot: its voice (rt_set_voice), a setting like the sid; geom: what every voice of the group shares, taken from
+  // the voice the group was created on
+  std::vector<int> voice;
+  VoiceGeom geom;
 };
 
 // TorchGate's filter half widths as Python's double arithmetic gives them: n_grad_freq = int(500 / (sr / (n_fft / 2))),
@@ -146,7 +150,7 @@ void rt_set_clean(Ctx& c, RtState& s, int b, int clean_audio, double clean_stren
   if (clean_audio) {
     if (!(clean_strength >= 0.0 && clean_strength <= 1.0))
       throw Error(RVCX_E_INVALID, "stream: clean_strength must lie in [0, 1]");
-    const int64_t n_model = (int64_t)s.feat * c.scfg.upp();
+    const int64_t n_model = (int64_t)s.feat * s.geom.upp;
     if (n_model < 2 * SG_NFFT) throw Error(RVCX_E_INVALID, "stream: clean_audio needs a model row of 2048 samples");
     try {
       spectral_gate_check(n_model, s.tgt_sr);
@@ -187,6 +191,8 @@ RtState* rt_create(Ctx& c, const rvcx_rt_desc& d) {
   const int window = 160;
   s.B = d.n_streams;
   s.clean.assign((size_t)s.B, -1.f);
+  s.voice.assign((size_t)s.B, c.cur_voice);
+  s.geom = voice_geom(c.scfg);
   s.f0_method = d.f0_method;
   s.fcpe_thr = or_default(d.fcpe_threshold, FCPE_THRESHOLD);
   // VoiceChanger.__init__ (core.py:351-354)
@@ -285,6 +291,36 @@ void rt_reset(Ctx& c, RtState& s, hipStream_t st) {
 
 int rt_streams(const RtState& s) { return s.B; }
 
+namespace {
+// a voice of the bank without selecting it: its configuration, readiness and index wherever they are held
+struct VoiceRef {
+  const SynthCfg* cfg = nullptr;
+  bool ready = false;
+  const IvfIndex* ivf = nullptr;
+};
+VoiceRef voice_ref(const Ctx& c, int id) {
+  if (id == c.cur_voice) return {&c.scfg, c.ready[RVCX_MODEL_SYNTH], c.ivf.get()};
+  const Voice& v = c.voices.at(id);
+  return {&v.scfg, v.ready, v.ivf.get()};
+}
+}  // namespace
+
+void rt_set_voice(Ctx& c, RtState& s, int b, int voice) {
+  if (b < -1 || b >= s.B) throw Error(RVCX_E_INVALID, "stream: stream_index out of range");
+  if (!c.has_voice(voice)) throw Error(RVCX_E_INVALID, "stream: voice " + std::to_string(voice) + " does not exist (or was freed)");
+  const VoiceRef v = voice_ref(c, voice);
+  if (!v.ready) throw Error(RVCX_E_STATE, "stream: voice " + std::to_string(voice) + " is not finalized");
+  if (!(voice_geom(*v.cfg) == s.geom))
+    throw Error(RVCX_E_SHAPE, "stream: voice " + std::to_string(voice) + " differs from the group's geometry voice in sr, "
+                              "upsample product, text_enc_hidden_dim, inter_channels, no_f0 or vocoder");
+  for (int i = 0; i < s.B; ++i)
+    if (b < 0 || i == b) s.voice[(size_t)i] = voice;
+}
+
+void rt_get_voices(const RtState& s, int32_t* out) {
+  for (int i = 0; i < s.B; ++i) out[i] = s.voice[(size_t)i];
+}
+
 // One slot back to its created state. Both halves of each ping-pong pair are cleared, so the slot reads zeros
 // whichever half is current; no other slot's bytes are touched.
 void rt_reset_stream(Ctx& c, RtState& s, int b, hipStream_t st) {
@@ -305,38 +341,60 @@ void rt_reset_stream(Ctx& c, RtState& s, int b, hipStream_t st) {
 void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, const rvcx_rt_opts* opts,
                 const uint8_t* active, const float* eps_z, const float* eps_src, uint64_t seed, float* out48,
                 float* vol_out, int* offs_out, hipStream_t st) {
-  const int B = s.B, E = c.scfg.emb_dim, upp = c.scfg.upp(), I = c.scfg.I;
-  // the active slots in slot order are the compact rows
+  const int B = s.B, E = s.geom.emb_dim, upp = s.geom.upp, I = s.geom.I;
+  // The compact rows are the active slots ordered by voice: the voice groups by their lowest active slot, the rows of a
+  // group by slot. With one voice in use that is slot order.
+  struct Group {
+    int voice, r0, n, k0, n_ret;  // rows [r0, r0 + n); its retrieving rows are entries [k0, k0 + n_ret) of the plan's seqs
+  };
+  std::vector<Group> groups;
   std::vector<int> slot2row(B, -1), row2slot;
-  for (int b = 0; b < B; ++b)
-    if (!active || active[b]) {
-      slot2row[b] = (int)row2slot.size();
-      row2slot.push_back(b);
-    }
+  for (int b = 0; b < B; ++b) {
+    if ((active && !active[b]) || slot2row[b] >= 0) continue;
+    Group g{s.voice[(size_t)b], (int)row2slot.size(), 0, 0, 0};
+    for (int q = b; q < B; ++q)
+      if ((!active || active[q]) && s.voice[(size_t)q] == g.voice) {
+        slot2row[q] = (int)row2slot.size();
+        row2slot.push_back(q);
+      }
+    g.n = (int)row2slot.size() - g.r0;
+    groups.push_back(g);
+  }
   const int Ba = (int)row2slot.size();
-  const bool all = Ba == B;
-  const bool guided = c.scfg.f0;  // no get_f0, pitch or protect without pitch guidance (pipeline.py:242-293)
+  bool all = Ba == B;  // the row map is the identity (every slot active, in slot order): it is not passed then
+  for (int r = 0; r < Ba && all; ++r) all = row2slot[r] == r;
+  const bool guided = s.geom.f0 != 0;  // no get_f0, pitch or protect without pitch guidance (pipeline.py:242-293)
+  for (const Group& g : groups) {  // a slot's voice may have been freed or re-finalized since rt_set_voice
+    if (!c.has_voice(g.voice))
+      throw Error(RVCX_E_STATE, "stream: voice " + std::to_string(g.voice) + " of an active slot was freed");
+    const VoiceRef v = voice_ref(c, g.voice);
+    if (!v.ready || !(voice_geom(*v.cfg) == s.geom))
+      throw Error(RVCX_E_STATE, "stream: voice " + std::to_string(g.voice) + " of an active slot is not finalized, or "
+                                "no longer has the group's geometry");
+  }
   int n_ret = 0, n_prop = 0;
   bool any_tune = false, any_rms = false, any_clean = false;
   const int64_t n_model = (int64_t)s.feat * upp;
   for (int r = 0; r < Ba; ++r) {
     const int b = row2slot[r];
     const rvcx_rt_opts& o = opts[b];
-    if (sids[b] < 0 || sids[b] >= c.scfg.n_spk) throw Error(RVCX_E_INVALID, "stream: sid out of range");
-    if (o.index_rate > 0 && !c.ivf) throw Error(RVCX_E_STATE, "stream: index_rate > 0 but no feature index loaded");
+    const VoiceRef v = voice_ref(c, s.voice[(size_t)b]);
+    if (sids[b] < 0 || sids[b] >= v.cfg->n_spk) throw Error(RVCX_E_INVALID, "stream: sid out of range");
+    if (o.index_rate > 0 && !v.ivf) throw Error(RVCX_E_STATE, "stream: index_rate > 0 but no feature index loaded");
     if (o.gen_precision < 0 || o.gen_precision > 1)
       throw Error(RVCX_E_INVALID, "stream: gen_precision must be 0 (fp32) or 1 (fp16 generator)");
     if (o.gen_precision != opts[row2slot[0]].gen_precision)
       throw Error(RVCX_E_INVALID, "stream: the active streams of one hop must agree on gen_precision");
-    if (o.index_rate > 0 && c.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "stream: index dimension mismatch");
+    if (o.index_rate > 0 && v.ivf->view.d != E) throw Error(RVCX_E_SHAPE, "stream: index dimension mismatch");
     n_ret += o.index_rate > 0 ? 1 : 0;
     any_tune |= o.f0_autotune != 0;
     n_prop += (!o.f0_autotune && o.proposed_pitch) ? 1 : 0;
     any_rms |= o.volume_envelope != 1.0;
     any_clean |= s.clean[b] >= 0.f;  // validated when it was set (rt_set_clean)
   }
-  if (!all && eps_src && c.scfg.vocoder != 0)
-    throw Error(RVCX_E_INVALID, "stream: injected source noise with idle slots needs the HiFi-GAN-NSF noise layout");
+  if ((!all || groups.size() > 1) && eps_src && s.geom.vocoder != 0)
+    throw Error(RVCX_E_INVALID, "stream: injected source noise with idle slots or several voices needs the HiFi-GAN-NSF "
+                                "noise layout");
   if (Ba == 0) {  // nobody took part: zero outputs, no state touched
     RVCX_HIP(hipMemsetAsync(out48, 0, sizeof(float) * (size_t)B * s.block48, st));
     if (vol_out) RVCX_HIP(hipMemsetAsync(vol_out, 0, sizeof(float) * B, st));
@@ -361,6 +419,10 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   int32_t* h_meta = reinterpret_cast<int32_t*>(at(P.meta));
   std::memcpy(at(P.slot2row), slot2row.data(), sizeof(int) * B);
   std::memcpy(at(P.row2slot), row2slot.data(), sizeof(int) * Ba);
+  for (Group& g : groups) {
+    for (int r = 0; r < g.r0; ++r) g.k0 += opts[row2slot[r]].index_rate > 0 ? 1 : 0;
+    for (int r = g.r0; r < g.r0 + g.n; ++r) g.n_ret += opts[row2slot[r]].index_rate > 0 ? 1 : 0;
+  }
   for (int r = 0, k = 0; r < Ba; ++r) {
     const int b = row2slot[r];
     const rvcx_rt_opts& o = opts[b];
@@ -413,7 +475,7 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   const int64_t L = hubert_frames(s.conv16);
   float* feats = c.buf<float>("rt.feats", (size_t)Ba * L * E, st);
   hipStream_t ax = fork_aux(c, st);  // batched HuBERT beside the batched f0 network (pipeline.py:233-254)
-  hubert_forward_b(c, conv, s.conv16, s.conv16, Ba, hubert_version_for(c), feats, L, ax);
+  hubert_forward_b(c, conv, s.conv16, s.conv16, Ba, E == 256 ? 1 : 2, feats, L, ax);
   if (guided) {
   if (s.f0_method == 1) {  // the raw local_argmax track (pipeline.py:147-155), F = nf / 160 + 1 frames as RMVPE's
     if (fcpe_pitch_frames(c) != RVCX_OK)
@@ -466,13 +528,19 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   join_aux(c, st, ax);
   // 4. index retrieval of rows skip_head // 2 .. (pipeline.py:264-268, :336-352): one search over every row that
   // retrieves, each blended at its own rate; the rest of the features is a plain copy
+  // -- per voice, against that voice's index
+  VoiceScope restore(c);  // the groups select their voices; the context's current voice comes back, on an error too
   const float* fx = feats;
   if (n_ret > 0) {
     float* fr = c.buf<float>("rt.feats_idx", (size_t)Ba * L * E, st);
     RVCX_HIP(hipMemcpyAsync(fr, feats, sizeof(float) * (size_t)Ba * L * E, hipMemcpyDeviceToDevice, st));
-    index_retrieve_rows(c, feats, L, s.skip_head / 2, E, n_ret, reinterpret_cast<const int*>(dplan + P.seqs),
-                        reinterpret_cast<const float*>(dplan + P.rate),
-                        reinterpret_cast<const float*>(dplan + P.one_minus_rate), fr, st);
+    for (const Group& g : groups) {
+      if (g.n_ret == 0) continue;
+      c.select_voice(g.voice);
+      index_retrieve_rows(c, feats, L, s.skip_head / 2, E, g.n_ret, reinterpret_cast<const int*>(dplan + P.seqs) + g.k0,
+                          reinterpret_cast<const float*>(dplan + P.rate),
+                          reinterpret_cast<const float*>(dplan + P.one_minus_rate), fr, st);
+    }
     fx = fr;
   }
   // 5. x2 upsample [:p_len] + protect; pitch tails (pipeline.py:270-293)
@@ -485,8 +553,8 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
                reinterpret_cast<const float*>(dplan + P.protect), reinterpret_cast<const int*>(dplan + P.use_protect),
                pitch, static_cast<const int*>(s.pbuf[nxt].p), pitchf, d_r2s, Ba, st),
         "rt_up2");
-  // 6. one batched Synthesizer.infer over the B_act rows (pipeline.py:295-297), clip (:93). Injected noise is
-  // indexed by slot, so with idle slots the active slots' rows are gathered first.
+  // 6. one batched Synthesizer.infer per voice over its rows (pipeline.py:295-297), clip (:93). Injected noise is
+  // indexed by slot, so unless the row map is the identity the active slots' rows are gathered first.
   if (!all && eps_z) {
     float* ez = c.buf<float>("rt.eps_z", (size_t)Ba * I * T, st);
     check(gather_rows(eps_z, I * T, d_r2s, ez, Ba, I * T, st), "rt_eps_z");
@@ -500,13 +568,18 @@ void rt_process(Ctx& c, RtState& s, const float* in48, const int32_t* sids, cons
   float* model = c.buf<float>("rt.model", (size_t)Ba * n_model, st);
   const int64_t n_need = std::min<int64_t>(n_model, (int64_t)s.sola48 + s.block48 + s.cross48);
   int64_t n_clip = n_model;
-  {
+  for (const Group& g : groups) {
+    c.select_voice(g.voice);
+    const size_t r0 = (size_t)g.r0;
     SynthCall syn;
-    syn.B = Ba, syn.T = T;
-    syn.phone = phone, syn.lengths = dmeta, syn.sid = dmeta + B;
-    if (guided) syn.pitch = pitch, syn.pitchf = pitchf;
-    syn.eps_z = eps_z, syn.eps_src = eps_src, syn.seed = seed;
-    syn.out = model;
+    syn.B = g.n, syn.T = T;
+    syn.phone = phone + r0 * T * E, syn.lengths = dmeta + r0, syn.sid = dmeta + B + r0;
+    if (guided) syn.pitch = pitch + r0 * T, syn.pitchf = pitchf + r0 * T;
+    // the NSF layout is one row of noise per batch row (checked above for several groups); drawn noise is keyed by the
+    // row within the call, so the groups after the first draw under seeds of their own
+    syn.eps_z = eps_z ? eps_z + r0 * I * T : nullptr, syn.eps_src = eps_src ? eps_src + r0 * n_model : nullptr;
+    syn.seed = seed + 0x9E3779B97F4A7C15ull * (uint64_t)g.r0;
+    syn.out = model + r0 * n_model;
     syn.gen_lowp = gen_precision;
     syn.full_lengths = true;  // every stream's hop is T frames (meta above)
     // k_rt_sola reads a[off + j], off <= sola48, j < block48 + cross48: the only reader of the model's output where

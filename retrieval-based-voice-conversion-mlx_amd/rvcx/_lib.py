@@ -47,6 +47,13 @@ class SynthDesc(ctypes.Structure):
 VOCODERS = {"HiFi-GAN": 0, "MRF HiFi-GAN": 1, "RefineGAN": 2}
 
 
+class VoiceDesc(ctypes.Structure):
+    """rvcx_voice_desc (include/rvcx.h)."""
+    _fields_ = [("synth", SynthDesc), ("config_set", ctypes.c_int), ("ready", ctypes.c_int),
+                ("index_d", ctypes.c_int64), ("index_ntotal", ctypes.c_int64), ("index_nlist", ctypes.c_int64),
+                ("index_nprobe", ctypes.c_int64), ("weight_bytes", ctypes.c_int64), ("split_bytes", ctypes.c_int64)]
+
+
 class PipelineOpts(ctypes.Structure):
     """rvcx_pipeline_opts (include/rvcx.h)."""
     _fields_ = [
@@ -210,6 +217,15 @@ SIG = {
     "rvcx_profile_read_kinds": (i32, [vp, P(f64), P(f64), P(i64), P(f64), i32, P(f64), P(f64), P(f64), P(f64),
                                       P(i64)]),
     "rvcx_profile_kind_name": (ctypes.c_char_p, [i32]),
+    "rvcx_pipeline_batch_voices": (i32, [vp, vp, P(i64), i64, i32, P(PipelineOpts), P(ctypes.c_int32),
+                                         P(ctypes.c_int32), vp, vp, u64, vp, i64, P(i64), vp, i64, vp]),
+    "rvcx_voice_new": (i32, [vp, P(i32)]),
+    "rvcx_voice_select": (i32, [vp, i32]),
+    "rvcx_voice_current": (i32, [vp, P(i32)]),
+    "rvcx_voice_info": (i32, [vp, i32, P(VoiceDesc)]),
+    "rvcx_voice_free": (i32, [vp, i32]),
+    "rvcx_rt_set_voice": (i32, [vp, vp, i32, i32]),
+    "rvcx_rt_get_voices": (i32, [vp, P(ctypes.c_int32)]),
 }
 
 # kernel-level entry points for the numerics tests (include/rvcx_test.h): exported, not part of the product ABI

@@ -43,9 +43,76 @@ class Engine(KernelTestMixin):
         if rc != 0:
             raise _lib.RvcxError(rc, f"rvcx_create(device={device}) failed")
         self.ctx = ctx
-        self.synth_cfg: Optional[SynthConfig] = None
+        # the voice bank (rvcx_voice_*): per voice id its SynthConfig and whether its synthesizer is loaded; voice 0
+        # exists from the start and is current. synth_cfg and loaded["synth"] follow the current voice.
+        self._voices = {0: {"cfg": None, "loaded": False}}
+        self._voice = 0
         self.loaded = {"synth": False, "hubert": False, "rmvpe": False, "crepe": None, "fcpe": None}
         self.fcpe_cfg = None
+
+    @property
+    def synth_cfg(self) -> Optional[SynthConfig]:
+        return self._voices[self._voice]["cfg"]
+
+    @synth_cfg.setter
+    def synth_cfg(self, cfg):
+        self._voices[self._voice]["cfg"] = cfg
+
+    # ------------------------------------------------------------------ voice bank
+    @property
+    def voice(self) -> int:
+        """The current voice: the one every synthesizer, pipeline and index method acts on."""
+        return self._voice
+
+    @property
+    def voice_ids(self):
+        return sorted(self._voices)
+
+    def select_voice(self, voice: int):
+        """rvcx_voice_select: host only (no device call, no copy). RvcxError(RVCX_E_INVALID) for an unknown or freed
+        id."""
+        self._check(self.lib.rvcx_voice_select(self.ctx, int(voice)), "voice_select")
+        self._voice = int(voice)
+        self.loaded["synth"] = self._voices[self._voice]["loaded"]
+
+    def add_voice(self, state: Mapping[str, np.ndarray], cfg: SynthConfig = SYNTH_48K_V2, index=None) -> int:
+        """A new resident voice: the synthesizer `state` under `cfg` and, optionally, its feature index (the bytes of
+        a faiss IndexIVFFlat file). Returns its id; the current voice is the same before and after."""
+        v = ctypes.c_int(0)
+        self._check(self.lib.rvcx_voice_new(self.ctx, ctypes.byref(v)), "voice_new")
+        vid, back = int(v.value), self._voice
+        self._voices[vid] = {"cfg": None, "loaded": False}
+        self.select_voice(vid)
+        try:
+            self.load_synth(state, cfg)
+            if index is not None:
+                self.index_load(index)
+        except Exception:
+            self.select_voice(back)
+            self.free_voice(vid)
+            raise
+        self.select_voice(back)
+        return vid
+
+    def voice_info(self, voice: Optional[int] = None) -> dict:
+        """rvcx_voice_info of any live voice (None: the current one): its SynthConfig as loaded here, ready, the index
+        (dict(d, ntotal, nlist, nprobe) or None), weight_bytes (the packed tensors) and split_bytes (the pre-split
+        weight images built from them so far)."""
+        vid = self._voice if voice is None else int(voice)
+        d = _lib.VoiceDesc()
+        self._check(self.lib.rvcx_voice_info(self.ctx, vid, ctypes.byref(d)), "voice_info")
+        index = None
+        if d.index_ntotal or d.index_nlist:
+            index = {"d": d.index_d, "ntotal": d.index_ntotal, "nlist": d.index_nlist, "nprobe": d.index_nprobe}
+        return {"id": vid, "cfg": self._voices[vid]["cfg"], "ready": bool(d.ready), "sr": int(d.synth.sr),
+                "upp": int(np.prod([d.synth.upsample_rates[i] for i in range(d.synth.n_upsample)], dtype=np.int64)),
+                "index": index, "weight_bytes": int(d.weight_bytes), "split_bytes": int(d.split_bytes)}
+
+    def free_voice(self, voice: int):
+        """rvcx_voice_free: synchronises the device and releases the voice's tensors, split images and index.
+        RvcxError(RVCX_E_STATE) for voice 0 and the current voice."""
+        self._check(self.lib.rvcx_voice_free(self.ctx, int(voice)), "voice_free")
+        self._voices.pop(int(voice), None)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -154,7 +221,7 @@ class Engine(KernelTestMixin):
         self.set_synth_config(cfg)
         st = {k: v for k, v in normalize_state(state).items() if not k.startswith("enc_q.")}
         self.upload_state(_lib.RVCX_MODEL_SYNTH, st)
-        self.loaded["synth"] = True
+        self.loaded["synth"] = self._voices[self._voice]["loaded"] = True
 
     def load_hubert(self, state: Mapping[str, np.ndarray]):
         st = {k: v for k, v in normalize_state(state).items() if k != "masked_spec_embed"}
@@ -692,13 +759,15 @@ class Engine(KernelTestMixin):
         res = out[: no.value]
         return (res, f0) if want_f0 else res
 
-    def _pipeline_rows(self, a, ns, opts, sids, eps_z, eps_src, seed, out, want_f0, want_hidden):
+    def _pipeline_rows(self, a, ns, opts, sids, eps_z, eps_src, seed, out, want_f0, want_hidden, voices=None):
         """What rvcx_pipeline_batch and rvcx_pipeline_batch_v share: a [B, lda] fp64 on device, rows of ns samples
-        (an int: the equal-length entry). Returns (out [B, ldo], n_out per row, f0 [B, F] or None, salience or None)."""
+        (an int: the equal-length entry). voices: None, or a voice id per row, rows of one voice contiguous
+        (rvcx_pipeline_batch_voices). Returns (out [B, ldo], n_out per row, f0 [B, F] or None, salience or None)."""
         t = self.torch
         B, lda = int(a.shape[0]), int(a.shape[1])
         m = lda + 2 * int(opts.t_pad)
-        ldo = (m // 160) * self.upp
+        # the voices of one batch share the upsample product; the current voice need not be one of them
+        ldo = (m // 160) * (self.upp if voices is None else self.voice_info(voices[0])["upp"])
         if out is None or out.numel() < B * ldo:
             out = t.empty((B, ldo), dtype=t.float32, device=self.device)
         out = out.reshape(-1)[: B * ldo].reshape(B, ldo)
@@ -718,8 +787,13 @@ class Engine(KernelTestMixin):
                                                      self.stream()), "pipeline_batch")
             return out, [int(no.value)] * B, f0, hid
         no = (ctypes.c_int64 * B)()
-        self._check(self.lib.rvcx_pipeline_batch_v(*head, (ctypes.c_int64 * B)(*ns), *mid, no, _ptr(f0), F,
-                                                   self.stream()), "pipeline_batch_v")
+        if voices is None:
+            self._check(self.lib.rvcx_pipeline_batch_v(*head, (ctypes.c_int64 * B)(*ns), *mid, no, _ptr(f0), F,
+                                                       self.stream()), "pipeline_batch_v")
+        else:
+            varr = (ctypes.c_int32 * B)(*[int(v) for v in voices])
+            self._check(self.lib.rvcx_pipeline_batch_voices(*head, (ctypes.c_int64 * B)(*ns), *mid[:4], varr, *mid[4:],
+                                                            no, _ptr(f0), F, self.stream()), "pipeline_batch_voices")
         return out, [int(v) for v in no], f0, hid
 
     def pipeline_batch(self, audio, opts: "_lib.PipelineOpts", sids=0, eps_z=None, eps_src=None, seed: int = 0,
@@ -740,17 +814,22 @@ class Engine(KernelTestMixin):
         return min(m // 160, 2 * hubert_frames(m))
 
     def pipeline_batch_v(self, audios, opts: "_lib.PipelineOpts", sids=0, eps_z=None, eps_src=None, seed: int = 0,
-                         want_f0: bool = False):
+                         want_f0: bool = False, voices=None):
         """Utterances of different lengths (a list of fp64 [n_b] arrays @16 kHz, each within t_max) through one
         batched pass (rvcx_pipeline_batch_v). Returns a list of fp32 [n_out_b] device tensors (row b =
         Pipeline.pipeline of utterance b); with want_f0 also the list of the rows' adjusted f0 (fp64 [F_b]).
         eps_z [B, inter, T_max] / eps_src [B, T_max * upp] with T_max = max pipeline_frames(n_b): row b consumes
-        eps_z[b, :, :T_b] and eps_src[b, :T_b * upp]."""
+        eps_z[b, :, :T_b] and eps_src[b, :T_b * upp].
+        voices: None (every row on the current voice), one voice id, or one per row with the rows of one voice
+        contiguous (rvcx_pipeline_batch_voices): HuBERT and the pitch network run once over all rows, retrieval and the
+        synthesizer once per voice."""
         a, ns = self._pad_rows(audios, self.torch.float64)
         if a is None:
             return ([], []) if want_f0 else []
         B = len(ns)
-        out, no, f0, _ = self._pipeline_rows(a, ns, opts, sids, eps_z, eps_src, seed, None, want_f0, False)
+        if voices is not None:
+            voices = [int(v) for v in np.broadcast_to(np.asarray(voices, dtype=np.int64), (B,))]
+        out, no, f0, _ = self._pipeline_rows(a, ns, opts, sids, eps_z, eps_src, seed, None, want_f0, False, voices)
         ys = [out[b, : no[b]] for b in range(B)]
         if not want_f0:
             return ys

@@ -37,6 +37,24 @@ class Config:
         return self.x_pad, self.x_query, self.x_center, self.x_max
 
 
+class VoiceRef:
+    """One resident voice as pipeline_many takes it per utterance: the engine's voice id (Engine.add_voice) and what the
+    reference reads from the checkpoint for a call -- tgt_sr, pitch_guidance (cpt["f0"]), version -- plus the voice's
+    own .index file (None: none)."""
+
+    def __init__(self, id: int, tgt_sr: int, pitch_guidance: bool = True, version: str = "v2", file_index=None):
+        self.id, self.tgt_sr, self.pitch_guidance = int(id), int(tgt_sr), bool(pitch_guidance)
+        self.version, self.file_index = version, file_index
+
+
+def voice_key(cfg, retrieves: bool):
+    """What the voices of one batched pass must share (rvcx_pipeline_batch_voices): the sampling rate, the upsample
+    product, the embedding width, inter_channels, pitch guidance and the vocoder of the synthesizer -- and, since a
+    batch has one index_rate, whether the voice retrieves at all. cfg: a SynthConfig."""
+    return (int(cfg.sr), int(np.prod(cfg.upsample_rates)), int(cfg.text_enc_hidden_dim), int(cfg.inter_channels),
+            bool(cfg.use_f0), str(cfg.vocoder), bool(retrieves))
+
+
 # pipeline_many's defaults: the best setting measured on a 64-utterance job of 2-30 s clips
 # (profiles/ragged_batch_times.txt: 829.5 ms against 850.1 ms, 848.0 .. 850.8, for the per-utterance loop)
 DEFAULT_BATCH = 8
@@ -155,16 +173,25 @@ class PipelineRVCX:
         if getattr(eng, "_hp", None) is None:
             eng.set_pipeline_highpass(self.sample_rate)  # pipeline.py:22-27
 
+    def set_tgt_sr(self, tgt_sr: int):
+        """The output rate of the voice a call runs on (RVCX selects a voice per call): tgt_sr and the padding in
+        output samples that follows from it."""
+        self.tgt_sr = int(tgt_sr)
+        self.t_pad_tgt = int(self.tgt_sr * self.x_pad)
+
     def load_index(self, file_index: str, eng=None):
-        """faiss.read_index + reconstruct_n (pipeline.py:430-434), cached per (path, mtime, size)."""
+        """faiss.read_index + reconstruct_n (pipeline.py:430-434) into the engine's current voice, cached per voice and
+        (path, mtime, size): two voices that alternate each keep their own index resident."""
         from .index import IndexIVFFlat
 
         eng = eng or self._engine()
         st = os.stat(file_index)
         key = (os.path.abspath(file_index), st.st_mtime_ns, st.st_size, id(eng))
-        if getattr(self, "_index_key", None) != key or eng.index_info() is None:
-            self.index = IndexIVFFlat(eng, path=file_index)
-            self._index_key = key
+        cache = self.__dict__.setdefault("_index_cache", {})  # voice id -> (key, handle)
+        hit = cache.get(eng.voice)
+        if hit is None or hit[0] != key or eng.index_info() is None:
+            cache[eng.voice] = hit = (key, IndexIVFFlat(eng, path=file_index))
+        self._index_key, self.index = hit  # the last one asked for, as before
         return self.index
 
     # ------------------------------------------------------------------ API (pipeline_mlx.py:135-373)
@@ -261,8 +288,14 @@ class PipelineRVCX:
                       pitch_guidance=True, volume_envelope=1.0, version="v2", protect=0.33, f0_autotune=False,
                       f0_autotune_strength=1.0, proposed_pitch=False, proposed_pitch_threshold=155.0, seed: int = 0,
                       batch: int = DEFAULT_BATCH, max_pad: float = DEFAULT_MAX_PAD, noise_fn=None,
-                      ragged_f0: bool = False, post=None):
+                      ragged_f0: bool = False, post=None, voices=None):
         """`pipeline` over a list of utterances of any lengths -> the list of float32 outputs in input order.
+        voices: None (every utterance on the engine's current voice), or one ``VoiceRef`` per utterance, in any order
+        (the voices of rvcx.infer.RVCX): the utterances are first split by what the voices of one batch must share
+        (the synthesizer's geometry, and whether the voice retrieves), then bucketed by length as below; each batch's
+        rows are ordered by voice and go through one rvcx_pipeline_batch_voices pass -- HuBERT and the pitch network
+        once over all rows, retrieval and the synthesizer once per voice. pitch_guidance, version and file_index are
+        then each voice's own (file_index here is the fallback for a voice without one); `post` must serve every voice.
         The utterances are grouped longest first into batches of up to `batch` rows whose shortest is at least
         (1 - max_pad) of the longest (rvcx.offline.bucket) and every batch is one rvcx_pipeline_batch_v pass; an
         utterance above t_max goes through `pipeline` alone (the batched pass takes single-chunk rows). batch = 1 is
@@ -277,6 +310,11 @@ class PipelineRVCX:
 
         if ragged_f0 and f0_method not in ("rmvpe", "fcpe"):
             raise ValueError(f'ragged_f0 runs RMVPE or FCPE: f0_method must be "rmvpe" or "fcpe", not {f0_method!r}')
+        if voices is not None:
+            return self._pipeline_many_voices(
+                model, sid, audios, voices, pitch, f0_method, file_index, index_rate, volume_envelope, protect,
+                f0_autotune, f0_autotune_strength, proposed_pitch, proposed_pitch_threshold, seed, batch, max_pad,
+                noise_fn, ragged_f0, post)
 
         eng, opts = self._pipeline_opts(model, sid, pitch, f0_method, file_index, index_rate, pitch_guidance,
                                         volume_envelope, version, protect, f0_autotune, f0_autotune_strength,
@@ -318,6 +356,83 @@ class PipelineRVCX:
             for i, y in zip(ids, ys):
                 outs[i] = (y if post is None else post(y)).cpu().numpy()
         return outs
+
+    def _pipeline_many_voices(self, model, sid, audios, voices, pitch, f0_method, file_index, index_rate,
+                              volume_envelope, protect, f0_autotune, f0_autotune_strength, proposed_pitch,
+                              proposed_pitch_threshold, seed, batch, max_pad, noise_fn, ragged_f0, post):
+        """pipeline_many with a VoiceRef per utterance. post: None, or {voice id: device tensor -> device tensor}."""
+        from ..offline import bucket_voices
+
+        eng = self._engine(model)
+        audios = [_row(a) for a in audios]
+        voices = list(voices)
+        if len(voices) != len(audios):
+            raise ValueError(f"voices has {len(voices)} entries for {len(audios)} utterances")
+        back, back_sr = eng.voice, self.tgt_sr
+        post = post or {}
+        try:
+            # per voice: its checks, its index (loaded into that voice) and its options; what its batch must share
+            by_id, opts, keys = {}, {}, {}
+            for v in voices:
+                if v.id in by_id:
+                    continue
+                by_id[v.id] = v
+                eng.select_voice(v.id)
+                self.set_tgt_sr(v.tgt_sr)
+                _, o = self._pipeline_opts(model, sid, pitch, f0_method, v.file_index or file_index, index_rate,
+                                           v.pitch_guidance, volume_envelope, v.version, protect, f0_autotune,
+                                           f0_autotune_strength, proposed_pitch, proposed_pitch_threshold)
+                if ragged_f0:
+                    o.f0_method = 5 if int(o.f0_method) == 3 else 4
+                opts[v.id] = o
+                keys[v.id] = voice_key(eng.synth_cfg, o.index_rate > 0)
+            vids = [v.id for v in voices]
+            outs = [None] * len(audios)
+
+            def host(y, vid):
+                return eng.host(y if post.get(vid) is None else post[vid](y))
+
+            def noise(i):
+                if noise_fn is None:
+                    return None, None
+                return noise_fn(i, eng.pipeline_frames(len(audios[i]), opts[vids[i]]))
+
+            def alone(i, **kw):
+                eng.select_voice(vids[i])
+                return host(eng.pipeline_ex(audios[i], opts[vids[i]], **kw), vids[i])
+
+            t_max = int(next(iter(opts.values())).t_max)
+            short = [i for i, a in enumerate(audios) if not (t_max > 0 and len(a) + 160 > t_max)]
+            for i in sorted(set(range(len(audios))) - set(short)):
+                outs[i] = alone(i, seed=seed)
+            plan = bucket_voices([len(audios[i]) for i in short], [vids[i] for i in short], keys, max(1, int(batch)),
+                                 float(max_pad))
+            for k, g in enumerate(plan):
+                ids = [short[j] for j in g]
+                if len(ids) == 1:
+                    ez, es = noise(ids[0])
+                    outs[ids[0]] = alone(ids[0], eps_z=ez, eps_src=es, seed=seed + k)
+                    continue
+                o = opts[vids[ids[0]]]
+                ez = es = None
+                if noise_fn is not None:
+                    upp = eng.voice_info(vids[ids[0]])["upp"]
+                    Ts = [eng.pipeline_frames(len(audios[i]), o) for i in ids]
+                    per = [noise(i) for i in ids]
+                    ez = np.zeros((len(ids), per[0][0].shape[0], max(Ts)), np.float32)
+                    es = np.zeros((len(ids), max(Ts) * upp), np.float32)
+                    for r, (z, sct) in enumerate(per):
+                        ez[r, :, :Ts[r]] = z
+                        es[r, :Ts[r] * upp] = sct
+                ys = eng.pipeline_batch_v([audios[i] for i in ids], o, sids=int(o.sid), eps_z=ez, eps_src=es,
+                                          seed=seed + k, voices=[vids[i] for i in ids])
+                eng.check_device_status()
+                for i, y in zip(ids, ys):
+                    outs[i] = (y if post.get(vids[i]) is None else post[vids[i]](y)).cpu().numpy()
+            return outs
+        finally:
+            eng.select_voice(back)
+            self.set_tgt_sr(back_sr)
 
 
 PipelineMLX = PipelineRVCX

@@ -69,6 +69,32 @@ def bucket(lengths: Sequence[int], batch: int, max_pad: float) -> List[List[int]
     return out
 
 
+def order_by_voice(positions: Sequence[int], voices: Sequence) -> List[int]:
+    """``positions`` reordered so that the rows of one voice are contiguous, as the batched pipeline takes them: the
+    voices in order of their first row, the rows of a voice in their given order. ``voices[p]`` is the voice of
+    position p."""
+    first: Dict = {}
+    for p in positions:
+        first.setdefault(voices[p], len(first))
+    return sorted(positions, key=lambda p: first[voices[p]])  # stable: the given order within a voice
+
+
+def bucket_voices(lengths: Sequence[int], voices: Sequence, keys: Dict, batch: int, max_pad: float) -> List[List[int]]:
+    """``bucket`` for utterances of several voices. ``voices[i]`` is utterance i's voice and ``keys[voice]`` what a
+    voice must share with the others of its batch (a hashable: the synthesizer's geometry, whether it retrieves).
+    The utterances are split by key first (the keys in order of their first utterance), each part is bucketed by
+    length, and every batch's rows are then ordered by voice (``order_by_voice``). Returns positions of ``lengths``.
+    With one voice this is ``bucket``."""
+    parts: Dict = {}
+    for i, v in enumerate(voices):
+        parts.setdefault(keys[v], []).append(i)
+    out: List[List[int]] = []
+    for ids in parts.values():
+        for g in bucket([lengths[i] for i in ids], batch, max_pad):
+            out.append(order_by_voice([ids[j] for j in g], voices))
+    return out
+
+
 def plan(job: Sequence[Utterance], world: int, rank: int, batch: int, max_pad: Optional[float] = None) -> Plan:
     """max_pad None: batches of equal length only. A value: ``bucket``'s rule inside the shard (the shards themselves
     do not depend on it)."""

@@ -86,8 +86,43 @@ def check_slot(n_streams: int, stream) -> int:
     return int(stream)
 
 
+def slot_voices(n_streams: int, voices, current: int):
+    """The voice id of each slot, checked on the host: ``voices`` None (every slot on ``current``), one id (every
+    slot on it) or a sequence of ``n_streams`` ids. ValueError for a wrong length or something that is no id."""
+    def one(v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+            raise ValueError(f"voice {v!r} is not a voice id (Engine.add_voice returns them)")
+        return int(v)
+
+    if voices is None:
+        return [int(current)] * n_streams
+    if isinstance(voices, (int, np.integer)):
+        return [one(voices)] * n_streams
+    each = [one(v) for v in voices]
+    if len(each) != n_streams:
+        raise ValueError(f"voices has {len(each)} entries for {n_streams} streams")
+    return each
+
+
+def zero_rate_without_index(arr, voices, has_index, active=None):
+    """rvc/realtime only retrieves when an index is loaded (pipeline.py:264), here per voice: the index_rate of every
+    active slot whose voice has no index becomes 0, in place in the ctypes array ``arr``. ``has_index``: voice id ->
+    bool."""
+    for b, v in enumerate(voices):
+        if (active is None or active[b]) and arr[b].index_rate > 0 and not has_index[v]:
+            arr[b].index_rate = 0.0
+    return arr
+
+
 class StreamGroup:
     """B streams sharing one buffer geometry, converted together each hop on one Engine.
+
+    voices: the voice of each slot (``Engine.add_voice`` ids): None = the Engine's current voice, one id, or one per
+    slot. The group takes its geometry from the first slot's voice; every other voice must agree with it on the
+    sampling rate, the upsample product, the embedding width, inter_channels, pitch guidance and the vocoder
+    (RvcxError RVCX_E_SHAPE otherwise). A slot keeps its voice whatever ``Engine.select_voice`` does later;
+    ``set_voice`` changes it. The hop runs the pitch network and HuBERT once over all slots and the synthesizer once per
+    voice in use.
 
     f0_method "rmvpe" (the default) or "fcpe": the pitch network every hop runs, batched over the B convert buffers.
     "fcpe" uses the checkpoint loaded with ``Engine.load_fcpe`` (16 kHz, hop 160) and needs no RMVPE weights; its raw
@@ -100,8 +135,10 @@ class StreamGroup:
     def __init__(self, engine: Engine, n_streams: int = 1, read_chunk_size: int = 192,
                  cross_fade_overlap_size: float = 0.1, extra_convert_size: float = 0.5,
                  silent_threshold: float = -90.0, sid=0, f0_method: str = "rmvpe", fcpe_threshold: float = 0.006,
-                 clean_audio: bool = False, clean_strength: float = 0.5):
+                 clean_audio: bool = False, clean_strength: float = 0.5, voices=None):
         method = _f0_method_id(f0_method)
+        n_streams = int(n_streams)
+        voices = slot_voices(n_streams, voices, engine.voice)
         self.clean_audio, self.clean_strength = bool(clean_audio), check_clean_strength(clean_strength)
         if f0_method == "fcpe" and getattr(engine, "fcpe_cfg", None) is None:
             raise ValueError('f0_method "fcpe" needs an FCPE checkpoint on the Engine (Engine.load_fcpe)')
@@ -115,8 +152,23 @@ class StreamGroup:
         d.silent_threshold = float(silent_threshold)
         d.f0_method, d.fcpe_threshold = method, float(fcpe_threshold)
         h = ctypes.c_void_p()
-        engine._check(lib.rvcx_rt_create(engine.ctx, ctypes.byref(d), ctypes.byref(h)), "rt_create")
+        # the group takes its geometry from the first slot's voice (rvcx_rt_create reads the current one)
+        back = engine.voice
+        if voices[0] != back:
+            engine.select_voice(voices[0])
+        try:
+            engine._check(lib.rvcx_rt_create(engine.ctx, ctypes.byref(d), ctypes.byref(h)), "rt_create")
+        finally:
+            if voices[0] != back:
+                engine.select_voice(back)
         self.handle = h
+        try:
+            for b, v in enumerate(voices):
+                if v != voices[0]:
+                    engine._check(lib.rvcx_rt_set_voice(engine.ctx, h, b, v), "rt_set_voice")
+        except Exception:
+            self.close()
+            raise
         g = (ctypes.c_int64 * 12)()
         engine._check(lib.rvcx_rt_geometry(h, g), "rt_geometry")
         self.geometry = dict(zip(GEOMETRY_FIELDS, list(g)))
@@ -141,6 +193,28 @@ class StreamGroup:
         except Exception:
             pass
 
+    @property
+    def voices(self):
+        """The voice id of each slot (rvcx_rt_get_voices)."""
+        out = (ctypes.c_int32 * self.n_streams)()
+        self.engine._check(self.engine.lib.rvcx_rt_get_voices(self.handle, out), "rt_get_voices")
+        return [int(v) for v in out]
+
+    def set_voice(self, stream: Optional[int], voice: int):
+        """Move one slot (``stream=None``: every slot) to another resident voice. The slot's buffers are kept: a user
+        who switches voice keeps the SOLA crossfade, a newcomer also calls ``reset(stream=i)``. RvcxError for a voice
+        that does not fit the group (RVCX_E_SHAPE), does not exist (RVCX_E_INVALID) or is not loaded (RVCX_E_STATE);
+        the slot then keeps its voice."""
+        eng = self.engine
+        slot = -1 if stream is None else check_slot(self.n_streams, stream)
+        vid = slot_voices(1, voice, 0)[0]
+        eng._check(eng.lib.rvcx_rt_set_voice(eng.ctx, self.handle, slot, vid), "rt_set_voice")
+
+    def _has_index(self, voices):
+        eng = self.engine
+        return {v: (eng.index_info() if v == eng.voice else eng.voice_info(v)["index"]) is not None
+                for v in set(voices)}
+
     def reset(self, stream: Optional[int] = None):
         """Clear the whole group (``stream=None``) or one slot: its audio / convert / pitch buffers and SOLA tail go
         back to zeros, asynchronously on the current stream, and no other slot is touched -- for a user who takes over
@@ -163,8 +237,10 @@ class StreamGroup:
         whose setting changes; an RtOpts without them means the group's defaults."""
         o = _lib.RtOpts()
         self.engine.lib.rvcx_rt_default_opts(ctypes.byref(o))
-        # rvc/realtime only retrieves when an index is loaded (pipeline.py:264); index_rate alone does not
-        loaded = self.engine.index_info() is not None
+        # rvc/realtime only retrieves when an index is loaded (pipeline.py:264); index_rate alone does not. The rule is
+        # per voice: the rate survives here when any slot's voice has an index, and ``process`` zeroes it for the slots
+        # whose voice has none.
+        loaded = any(self._has_index(self.voices).values())
         o.f0_up_key, o.index_rate, o.protect = float(f0_up_key), float(index_rate) if loaded else 0.0, float(protect)
         o.volume_envelope, o.f0_autotune = float(volume_envelope), int(bool(f0_autotune))
         o.f0_autotune_strength, o.proposed_pitch = float(f0_autotune_strength), int(bool(proposed_pitch))
@@ -199,6 +275,14 @@ class StreamGroup:
         t = eng.torch
         opts = self.opts() if opts is None else opts if isinstance(opts, _lib.RtOpts) else list(opts)
         arr, act = hop_arguments(self.n_streams, opts, active)
+        if any(o.index_rate > 0 for o in arr):
+            # where some of the group's voices have an index and some have none, ``opts`` could not apply the
+            # reference's rule (it does not know the slot): it is completed here, per slot. With no index at all a
+            # rate set by hand is refused by the library, as before.
+            voices = self.voices
+            has = self._has_index(voices)
+            if any(has.values()) and not all(has.values()):
+                zero_rate_without_index(arr, voices, has, act)
         self._apply_clean(opts, act)
         x = eng._dev(audio_in, t.float32).reshape(self.n_streams, self.block_frame)
         ez = eng._opt(eps_z, t.float32)
